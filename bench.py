@@ -9,11 +9,17 @@ integer constants broadcast once over RCCL (xGMI), images sharded by rank, no pe
         --master-port P bench.py --gpus N --steps K --warmup W        # what the driver runs for N > 1
 
 Prints ONE JSON line on rank 0 (contract in the task statement).  A "step" = one forward of the hot path
-over one resident per-GPU batch.  The timed region (EXACTLY K steps between barriers, max over ranks) is repeated
-until at least `--min-seconds` (default 3 s) of timed GPU work has accumulated and at least `--reps` times, so that
-the clocks are in steady state; `value` is the MEDIAN repetition (all repetitions are listed).  `roofline`: the int8 MFMA GEMM class and the HBM-bound operators, each timed with HIP events
+over one resident per-GPU batch.  A plain run sets up, warms up (W steps), times EXACTLY K steps once (between barriers,
+max over ranks), writes the last step's logits if `--dump-outputs DIR` is given, and prints the headline line.
+
+    python bench.py --full                            # everything below as well
+
+With `--full` the run also checks every image of the timed mode against an unsliced forward and the golden prefix against the
+reference's logits, and the timed region of K steps is repeated until at least `--min-seconds` (default 3 s) of timed GPU work
+has accumulated and at least `--reps` times, so that the clocks are in steady state; `value` is then the MEDIAN repetition (all
+repetitions are listed).  `roofline` (--full): the int8 MFMA GEMM class and the HBM-bound operators, each timed with HIP events
 on the launch stream while the same forward is issued ONE C-ABI CALL PER OPERATOR on a single stream
-(`timed_on`), which is not the sliced / hipGraph path that produced `value`.  `cpu_baseline` (N = 1 only): the
+(`timed_on`), which is not the sliced / hipGraph path that produced `value`.  `cpu_baseline` (--full, N = 1 only): the
 PyTorch-CPU counterpart of the reference's fake-quant path and the OpenMP C port of the integer algorithm on the host
 cores, plus the DeiT-T batch-1 latency of BASELINE.json configs[0].
 """
@@ -277,6 +283,26 @@ def cpu_baseline(family, cfg, weights, scales, golden_dir, target_seconds=12.0):
     return out
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much over all ranks
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: each device tensor as out_dir/<name>.npy (<name>_rank<r>.npy when world > 1), in float64 — the int32
+    logits are exact there.  An array over this rank's share of DUMP_BYTES is written as a fixed, seeded sample of its rows,
+    the row indices beside it as <name>_sample_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // world // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float64)
+        stem = name if world == 1 else f"{name}_rank{rank}"
+        row_bytes = a[0].nbytes + 8
+        if a.shape[0] * row_bytes > budget:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], budget // row_bytes, replace=False))
+            np.save(os.path.join(out_dir, stem + "_sample_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, stem + ".npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` outside a launcher: start N ranks (one per GPU) and relay rank 0's line."""
     import torch
@@ -295,25 +321,32 @@ def self_launch(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (forwards) of the timed region")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=3, help="minimum repetitions of the K-step timed region (value = median)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the sliced-vs-unsliced and golden-prefix checks, repetitions of the timed region "
+                         "(--reps, --min-seconds), the per-operator roofline, the box probe, the PMC traffic passes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the int32 logits, as float64) to DIR/<name>.npy")
+    ap.add_argument("--reps", type=int, default=3, help="--full: minimum repetitions of the K-step timed region (value = median)")
     ap.add_argument("--min-seconds", type=float, default=3.0,
-                    help="keep repeating the timed region until this much timed GPU work has accumulated (steady clocks; long enough "
-                         "for a 5-second utilisation sampler to see the GPU busy)")
+                    help="--full: keep repeating the timed region until this much timed GPU work has accumulated (steady clocks; long "
+                         "enough for a 5-second utilisation sampler to see the GPU busy)")
     ap.add_argument("--model", default="deit_small", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="images per GPU (default: the BASELINE.json config's share)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=2)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out cpu_baseline")
+    ap.add_argument("--profile-steps", type=int, default=2, help="--full: instrumented per-operator steps of the roofline block")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("IVIT_STREAMS", "0")),
                     help="batch slices on the runner's internal HIP streams (0 = per-model default)")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("IVIT_GRAPH", "1")), help="replay a captured hipGraph")
     ap.add_argument("--measure-traffic", type=int, default=1,
-                    help="N = 1: measure roofline.traffic with two rocprofv3 PMC subprocess passes after the timed region (~25 s); 0 / failure: the committed profiles/pmc_traffic.json")
-    ap.add_argument("--box-probe", type=int, default=1, help="0: skip the MFMA / copy probe (profiling runs: keeps its kernels out of the trace)")
+                    help="--full, N = 1: measure roofline.traffic with two rocprofv3 PMC subprocess passes after the timed region (~25 s); 0 / failure: the committed profiles/pmc_traffic.json")
+    ap.add_argument("--box-probe", type=int, default=1, help="--full: 0 skips the MFMA / copy probe (profiling runs: keeps its kernels out of the trace)")
     ap.add_argument("--auto-mode", type=int, default=1,
                     help="unless --streams / --graph are given: try (default slices + hipGraph) and (one stream, eager) untimed, time the faster")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -405,25 +438,28 @@ def main():
         best = min(mode_trials, key=lambda m: m["ms_per_step"])
         streams, args.graph = best["streams"], int(best["hipgraph"])
     step = make_step(streams, args.graph)
-    # every image of the timed mode (slices on internal streams, hipGraph) against ONE unsliced forward on the current stream,
-    # five times, before anything is timed: a race between slices shows up in some image of some run, never reliably in the
-    # golden prefix checked below
+    # --full: every image of the timed mode (slices on internal streams, hipGraph) against ONE unsliced forward on the current
+    # stream, five times, before anything is timed: a race between slices shows up in some image of some run, never reliably in
+    # the golden prefix checked below
     ok_all = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ref_all = eng.forward(imgs, nslices=1).clone()
         ok_all = all(bool(torch.equal(step(), ref_all)) for _ in range(5))
         del ref_all
     # a wrong image is not a benchmark result: no JSON line, non-zero exit — on EVERY rank (rank 0 alone leaving would
     # strand the others in the next barrier until the RCCL timeout)
-    all_ranks_exit_unless(ok_all is not False, "bench.py: the sliced / graph forward differs from the unsliced forward in at least one image; nothing timed")
+    if args.full:
+        all_ranks_exit_unless(ok_all is not False, "bench.py: the sliced / graph forward differs from the unsliced forward in at least one image; nothing timed")
     for _ in range(args.warmup):
         step()
+    # a plain run times the K steps once; --full repeats them (value = median repetition)
+    reps, min_seconds = (args.reps, args.min_seconds) if args.full else (1, 0.0)
     rep_dt = []
-    while len(rep_dt) < max(1, args.reps) or (sum(rep_dt) < args.min_seconds and len(rep_dt) < 200):
+    while len(rep_dt) < max(1, reps) or (sum(rep_dt) < min_seconds and len(rep_dt) < 200):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            logits = step()
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -434,21 +470,24 @@ def main():
     dt = sorted(rep_dt)[len(rep_dt) // 2]
     ms_per_step = dt / args.steps * 1e3
     value = batch * world * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": logits}, rank, world)
 
-    # parity guard inside the bench: the first images of rank 0 are the golden batch
+    # --full: parity guard inside the bench: the first images of rank 0 are the golden batch
     ok = None
-    if rank == 0 and batch >= gb:
+    if rank == 0 and args.full and batch >= gb:
         want = g["logits_int"]
         if os.environ.get("IVIT_BENCH_SELFTEST_WRONG_GOLDEN"):      # tests/test_gpu_parity.py only: every rank must leave, non-zero
             want = want + 1
         ok = bool(np.array_equal(step()[:gb].cpu().numpy(), want))
-    all_ranks_exit_unless(ok is not False, "bench.py: logits of the golden prefix differ from the reference's; nothing reported")
+    if args.full:
+        all_ranks_exit_unless(ok is not False, "bench.py: logits of the golden prefix differ from the reference's; nothing reported")
 
-    box = box_probe(local_rank) if (rank == 0 and args.box_probe) else None
-    live = measure_traffic_live(args.model) if (rank == 0 and world == 1 and args.measure_traffic) else None
+    box = box_probe(local_rank) if (rank == 0 and args.full and args.box_probe) else None
+    live = measure_traffic_live(args.model) if (rank == 0 and args.full and world == 1 and args.measure_traffic) else None
     # per-operator HIP-event timing (separate instrumented steps, one stream, one C-ABI call per operator)
     per = {}
-    if rank == 0 and args.profile_steps > 0:
+    if rank == 0 and args.full and args.profile_steps > 0:
         eng.forward_ops(imgs)
         with EventTimer(eng.h, torch) as et:
             for _ in range(args.profile_steps):
@@ -466,9 +505,9 @@ def main():
                     per_unfused = et2.summary()
             finally:
                 eng.fuse_ln_mlp = eng.fuse_ln_qkv = True
-    if rank == 0:
+    lin_ops, bmm_ops = (vit_ops_per_image if family == "vit" else swin_ops_per_image)(cfg)
+    if rank == 0 and args.full:
         ps = max(args.profile_steps, 1)
-        lin_ops, bmm_ops = (vit_ops_per_image if family == "vit" else swin_ops_per_image)(cfg)
         # (round 6: the qkv layer of a D = 384 block carries norm1 in its prologue — ivit_layernorm_linear_i8_qkv_planned; the whole
         # launch, LayerNorm included, is inside the time the class's OPs are divided by)
         is_gemm = lambda n: (n.startswith("ivit_linear_i8") or n.startswith("ivit_mlp_fused") or n == "ivit_patch_embed" or
@@ -603,6 +642,7 @@ def main():
         }
         breakdown = {n: {"ms_per_step": round(v[0] / ps, 4), "launches": v[1] // ps}
                      for n, v in sorted(per.items(), key=lambda kv: -kv[1][0])}
+    if rank == 0:
         out = {
             "metric": "images/sec + int8-MFMA-roofline% for DeiT-S bs256@224 on 1/2/4/8 MI355X",
             "value": round(value, 1), "unit": "images/s", "n_gpus": world, "steps": args.steps,
@@ -613,18 +653,21 @@ def main():
                        "global_batch": batch * world, "parallelism": f"dp{world} (batch-sharded, weights RCCL-broadcast once)",
                        "streams_per_gpu": streams, "hipgraph": bool(args.graph),
                        "launch_mode_trials": mode_trials},
-            "repetitions_ms_per_step": [round(d / args.steps * 1e3, 4) for d in rep_dt],
-            "value_is": "median repetition",
+            "value_is": "median repetition" if args.full else f"one timed region of {args.steps} steps",
             "model_int8_tops": round((lin_ops + bmm_ops) * batch * world / (ms_per_step * 1e-3) / 1e12, 1),
             "model_roofline_frac": round((lin_ops + bmm_ops) * batch / (ms_per_step * 1e-3) / 1e12 / INT8_PEAK_TOPS, 4),
-            "bit_exact_vs_reference_golden": ok,
-            "all_images_equal_unsliced_forward": ok_all,
-            "roofline": roofline,
-            "box": box,
-            "kernel_breakdown_ms": breakdown,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(family, cfg, weights, scales, os.path.join(ROOT, "tests", "golden"))
+        if args.full:
+            out.update({
+                "repetitions_ms_per_step": [round(d / args.steps * 1e3, 4) for d in rep_dt],
+                "bit_exact_vs_reference_golden": ok,
+                "all_images_equal_unsliced_forward": ok_all,
+                "roofline": roofline,
+                "box": box,
+                "kernel_breakdown_ms": breakdown,
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(family, cfg, weights, scales, os.path.join(ROOT, "tests", "golden"))
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

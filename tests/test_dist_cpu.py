@@ -167,3 +167,25 @@ def test_bench_refuses_missing_devices():
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode != 0
     assert "--gpus 2" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_within_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: int32 logits land as float64 without loss, one file per rank when world > 1; an output over the
+    byte budget becomes a fixed, seeded sample of its rows (the same rows on every run), written with its row indices."""
+    import bench
+    t = torch.arange(-600, 600, dtype=torch.int32).reshape(120, 10) * 3_000_000
+    bench.dump_outputs(str(tmp_path / "whole"), {"logits": t}, 0, 1)
+    a = np.load(tmp_path / "whole" / "logits.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, t.numpy().astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "ranks"), {"logits": t}, 1, 2)
+    assert sorted(p.name for p in (tmp_path / "ranks").iterdir()) == ["logits_rank1.npy"]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"logits": t}, 0, 1)
+    rows = np.load(tmp_path / "s1" / "logits_sample_rows.npy")
+    s = np.load(tmp_path / "s1" / "logits.npy")
+    assert sum(p.stat().st_size - 128 for p in (tmp_path / "s1").iterdir()) <= 4000
+    assert len(rows) == 4000 // (10 * 8 + 8) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(s, t.numpy()[rows.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "logits_sample_rows.npy"))
+    assert np.array_equal(s, np.load(tmp_path / "s2" / "logits.npy"))

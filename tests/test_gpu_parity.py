@@ -2043,10 +2043,10 @@ def test_bench_two_ranks_on_one_gpu():
     """bench.py's `world > 1` branch (broadcast of the constants blob, the barriers, the MAX all-reduce over ranks, the
     every-rank exit) had never executed on a GPU: run it as the driver launches it — torch.distributed.run, 2 ranks — with both
     ranks on device 0 and gloo as the transport (bench.py: IVIT_DIST_BACKEND, `local_rank % device_count`).  Then the same
-    with a deliberately wrong golden: BOTH ranks must leave non-zero, promptly, and print no JSON line."""
+    with a deliberately wrong golden: BOTH ranks must leave non-zero, promptly, and print no JSON line (the checks are --full's)."""
     import json
     import time
-    args = ["bench.py", "--gpus", "2", "--model", "deit_tiny", "--batch", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    args = ["bench.py", "--gpus", "2", "--model", "deit_tiny", "--batch", "8", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
             "--profile-steps", "0", "--min-seconds", "0", "--reps", "1"]
     r = _run_ranks(args, {}, 300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -2061,6 +2061,37 @@ def test_bench_two_ranks_on_one_gpu():
     assert bad.returncode != 0 and time.time() - t0 < 120
     assert not [ln for ln in bad.stdout.splitlines() if ln.startswith("{")], "a wrong golden prefix must not produce a bench line"
     assert "golden prefix differ" in bad.stderr
+
+
+def test_bench_plain_run_dumps_last_step_logits(tmp_path):
+    """a plain bench run (no --full) times exactly --steps steps once and prints the headline keys without the parts that take
+    runs of their own; the logits it writes with --dump-outputs are the timed path's, for the seeded batch bench.py builds
+    (golden images first, then seed 101): every image equals the CPU oracle's."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from oracle import oracle as orc
+    cmd = [sys.executable, "bench.py", "--model", "deit_tiny", "--batch", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["unit"] == "images/s" and out["higher_is_better"] is True and out["dtype"] == "int8"
+    assert out["steps"] == 3 and out["value_is"] == "one timed region of 3 steps"
+    assert out["value"] > 0 and abs(out["value"] - 8 * 1e3 / out["ms_per_step"]) < 1e-3 * out["value"]
+    assert not {"roofline", "box", "kernel_breakdown_ms", "cpu_baseline", "repetitions_ms_per_step"} & set(out)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["logits.npy"]
+    got = np.load(tmp_path / "logits.npy")
+    assert got.dtype == np.float64 and got.shape == (8, 1000)
+    g = load_golden("deit_tiny_b1.npz")
+    cfg = iv.CONFIGS["deit_tiny"]
+    gb = int(g["batch"])
+    imgs = np.concatenate([iv.make_images_int8(cfg, gb, int(g["images_seed"])), iv.make_images_int8(cfg, 8, seed=101)])[:8]
+    ref, _ = orc.OracleViT(cfg, iv.make_vit_weights(cfg, int(g["seed"])), golden_scales(g)).forward(imgs)
+    assert np.array_equal(ref[:gb], g["logits_int"])
+    assert np.array_equal(got, ref.astype(np.float64))
 
 
 def test_engine_forward_sharded_over_two_ranks():

@@ -1,4 +1,4 @@
-run() { python bench.py --model $2 --no-cpu-baseline --measure-traffic 0 --profile-steps 0 --box-probe 0 --min-seconds 1 $3 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 $2 $3:', d['ms_per_step'], d['value'], d['config'].get('streams_per_gpu'), d.get('bit_exact_vs_reference_golden'), d.get('all_images_equal_unsliced_forward'))"; }
+run() { python bench.py --full --model $2 --no-cpu-baseline --measure-traffic 0 --profile-steps 0 --box-probe 0 --min-seconds 1 $3 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 $2 $3:', d['ms_per_step'], d['value'], d['config'].get('streams_per_gpu'), d.get('bit_exact_vs_reference_golden'), d.get('all_images_equal_unsliced_forward'))"; }
 for i in 1 2 3; do
   for m in swin_tiny; do run tree $m; IVIT_LIB=build/ab/noshare.so run noshare $m; done
 done
