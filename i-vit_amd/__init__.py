@@ -25,6 +25,7 @@ _LAZY = {
     "swin_tiny_patch4_window7_224": ("swin_quant", "swin_tiny_patch4_window7_224"),
     "swin_small_patch4_window7_224": ("swin_quant", "swin_small_patch4_window7_224"),
     "swin_base_patch4_window7_224": ("swin_quant", "swin_base_patch4_window7_224"),
+    "swin_base_patch4_window12_384": ("swin_quant", "swin_base_patch4_window12_384"),
     "SwinEngine": ("swin_engine", "SwinEngine"),
     "load_reference_state_dict": ("checkpoint", "load_reference_state_dict"),
 }

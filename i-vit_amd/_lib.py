@@ -9,7 +9,7 @@ import subprocess
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 SO_PATH = os.environ.get("IVIT_LIB") or os.path.join(_CSRC, "libivit_hip.so")
-SOURCES = ["ivit_hip.hip", "ivit_device.h", "ivit_gemm.h", "ivit_elementwise.h", "ivit_layernorm.h", "ivit_attention.h", "ivit_gemm2.h", "ivit_gemm3.h", "ivit_gemm_wreg.h", "ivit_swin.h", "ivit_mlp.h", "ivit_mlp_rs.h", "ivit_swin_mlp_rs.h", "ivit_model.h"]
+SOURCES = ["ivit_hip.hip", "ivit_device.h", "ivit_gemm.h", "ivit_elementwise.h", "ivit_layernorm.h", "ivit_attention.h", "ivit_gemm2.h", "ivit_gemm3.h", "ivit_gemm_wreg.h", "ivit_swin.h", "ivit_mlp.h", "ivit_mlp_rs.h", "ivit_swin_mlp_rs.h", "ivit_swin12.h", "ivit_model.h"]
 _THIS = os.path.abspath(__file__)
 # -packed-fp32-ops: no v_pk_{add,mul,fma}_f32 anywhere in the library.  Round 4 traced the sporadic one-LSB differences of
 # layernorm_reg_kernel<192, 1> beside QuantLinear GEMM workgroups to that instruction class; round 5 to one form of it:
@@ -144,7 +144,7 @@ class SwinParams(ctypes.Structure):
         ("pe", LinParams), ("s_bn", ctypes.c_float), ("pn", LnParams), ("dy_qact1", ctypes.c_void_p),
         ("blocks_host", ctypes.POINTER(SwinBlock)), ("merges_host", ctypes.POINTER(SwinMerge)),
         ("s_norm_in", ctypes.c_float), ("n", LnParams), ("dy_pool", Dyadic),
-        ("head_w", ctypes.c_void_p), ("head_b", ctypes.c_void_p),
+        ("head_w", ctypes.c_void_p), ("head_b", ctypes.c_void_p), ("s_pool", ctypes.c_float),
     ]
 
 
@@ -222,6 +222,7 @@ SIGNATURES = {
     "ivit_shiftmax_masked": [_P, _P, _L, _I, _I, _F, _I, _P, _I, _I, _P, _I],
     "ivit_requant_i32_bcast": [_P, _P, Dyadic, _P, _L, Dyadic, _I, _P, _L],
     "ivit_avgpool_requant": [_P, _P, _I, _I, _I, Dyadic, _P],
+    "ivit_avgpool_requant_scaled": [_P, _P, _I, _I, _I, _F, Dyadic, _P],
     "ivit_layernorm_tokenorder": [_P, _P, _L, _I, _F, _P, _P, _I, _P],
     "ivit_debug_div": [_P, _P, _P, _P, _P, _L],
     "ivit_debug_requotient": [_P, _P, _P, _P, _P, _L],

@@ -22,6 +22,7 @@
 #include "ivit_mlp_rs.h"
 #include "ivit_swin_mlp_rs.h"
 #include "ivit_gemm_ws.h"
+#include "ivit_swin12.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -1349,7 +1350,16 @@ int ivit_avgpool_requant(ivit_handle h, const int8_t *x, int B, int L, int C, iv
     CHECK_H(h);
     REQUIRE(h, x && out8 && B > 0 && L > 0 && C > 0, "bad arguments");
     REQUIRE(h, (L & 1) == 1, "token count must be odd (no rounding ties; see kernel comment)");
-    avgpool_requant_kernel<<<(unsigned)((B * C + 255) / 256), 256, 0, h->stream>>>(x, B, L, C, dy, out8);
+    avgpool_requant_kernel<<<(unsigned)((B * C + 255) / 256), 256, 0, h->stream>>>(x, B, L, C, 0.f, dy, out8);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+int ivit_avgpool_requant_scaled(ivit_handle h, const int8_t *x, int B, int L, int C, float scale, ivit_dyadic dy,
+                                int8_t *out8) {
+    CHECK_H(h);
+    REQUIRE(h, x && out8 && B > 0 && L > 0 && C > 0 && scale > 0.f, "bad arguments");
+    avgpool_requant_kernel<<<(unsigned)((B * C + 255) / 256), 256, 0, h->stream>>>(x, B, L, C, scale, dy, out8);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1499,14 +1509,51 @@ int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int C, int H, i
 
 extern "C" {
 
+// window 12 (ivit_swin12.h window_attention12_kernel): arithmetic Shiftmax only
+static int window_attention12_launch(ivit_handle h, const int8_t *qkv, ivit_dyadic dy_qk, ivit_dyadic dy_a, const int16_t *relb,
+                                     float s_softmax, bool tables, ivit_dyadic dy_pv, int8_t *ctx, int B, int R, int shift,
+                                     int heads, int dh) {
+    if (tables) {
+        snprintf(h->err, sizeof(h->err), "window_attention: the Shiftmax-table form is built for window 7 only; "
+                                         "use ivit_window_attention_fused at window 12");
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    if (dh != 32 || (R % 12) != 0) {
+        snprintf(h->err, sizeof(h->err), "window_attention: window 12 is built for head dim 32 and R %% 12 == 0");
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    REQUIRE(h, shift >= 0 && shift < 12 && s_softmax > 0.f, "bad shift / scale");
+    REQUIRE(h, fabs(dy_qk.m * dy_qk.r) < 2048.0 && fabs(dy_pv.m * dy_pv.r) < 1024.0, "requant factor out of range");
+    REQUIRE(h, ((uintptr_t)relb & 15) == 0, "relb must be 16-byte aligned (staged in 16-byte pieces)");
+    WinAttn12Args a;
+    memset(&a, 0, sizeof(a));
+    a.qkv = qkv; a.ctx = ctx; a.relb = relb; a.B = B; a.R = R; a.shift = shift; a.heads = heads;
+    a.dy_qk = dy_qk; a.dy_a = dy_a; a.dy_pv = dy_pv; a.s = s_softmax;
+    const long long nwin = (long long)B * (R / 12) * (R / 12);
+    // windows per block: the slab (41.5 KB) is staged once per block, so as many as keep >= 3 blocks per resident
+    // slot (2 per CU of the handle's CU share, ivit_set_cu_share), at most 8
+    const long long slots = 2LL * persistent_cus(h);
+    int wpb = 8;
+    while (wpb > 1 && ((nwin + wpb - 1) / wpb) * heads < 3 * slots) wpb >>= 1;
+    a.wpb = wpb;
+    int st = set_dyn_lds(h, (const void *)window_attention12_kernel<12>, WA12_SMEM);
+    if (st) return st;
+    const long long groups = (nwin + wpb - 1) / wpb;      // grid: whole groups of 8 window groups (see the kernel)
+    window_attention12_kernel<12><<<dim3((unsigned)(((groups + 7) / 8) * 8 * heads)), WA12_THREADS, WA12_SMEM, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
 static int window_attention_impl(ivit_handle h, const int8_t *qkv, ivit_dyadic dy_qk, ivit_dyadic dy_a,
                                  const int16_t *relb, float s_softmax, const uint16_t *aq, const float *et, const uint8_t *cls,
                                  int nc, int t_count, int dmin, ivit_dyadic dy_pv, int8_t *ctx, int B, int R,
                                  int window, int shift, int heads, int dh) {
     CHECK_H(h);
     REQUIRE(h, qkv && relb && ctx && B > 0 && R > 0 && heads > 0, "bad arguments");
+    if (window == 12) return window_attention12_launch(h, qkv, dy_qk, dy_a, relb, s_softmax, aq != nullptr, dy_pv, ctx, B, R,
+                                                       shift, heads, dh);
     if (window != 7 || dh != 32 || (R % 7) != 0) {
-        snprintf(h->err, sizeof(h->err), "%s: built for window 7, head dim 32, R %% 7 == 0", __func__);
+        snprintf(h->err, sizeof(h->err), "%s: built for windows 7 and 12, head dim 32, R %% window == 0", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
     REQUIRE(h, shift >= 0 && shift < 7 && s_softmax > 0.f, "bad shift / scale");

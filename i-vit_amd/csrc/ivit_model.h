@@ -478,6 +478,7 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
         for (int bj = 0; bj < c.depths[li]; ++bj, ++bi) {
             const ivit_swin_block &b = m->blocks[bi];
             const int shift = (bj % 2 == 0 || res <= c.window_size) ? 0 : c.window_size / 2;
+            const int wsz = res <= c.window_size ? res : c.window_size;     // SwinTransformerBlock.__init__
             const ivit_linear_plan *lp = m->lin_plans.empty() ? nullptr : &m->lin_plans[4 * bi];
             // norm1 inside the qkv launch where that layer runs on gemm_ws_qkv_kernel (C = 384, activations in natural token order)
             rc = (IVIT_OPT_SWIN_WS && lp && lp[0] && li != 0) ? ivit_layernorm_linear_i8_requant_planned(h, lp[0], x, b.s_in, b.n1.bias_int, b.n1.sc, b.n1.dy, qkv, (int)M)
@@ -491,11 +492,11 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             }
             if (b.exp_aq)
                 RUN(ivit_window_attention_fused_lut(h, qkv, b.dy_qk, b.dy_a, b.relb, b.s_softmax, b.exp_aq, b.exp_t, b.exp_cls,
-                                                    b.exp_nc, b.exp_tcount, b.exp_dmin, b.dy_pv, ctx, B, res, c.window_size,
+                                                    b.exp_nc, b.exp_tcount, b.exp_dmin, b.dy_pv, ctx, B, res, wsz,
                                                     shift, heads, C / heads));
             else
                 RUN(ivit_window_attention_fused(h, qkv, b.dy_qk, b.dy_a, b.relb, b.s_softmax, b.dy_pv, ctx, B, res,
-                                                c.window_size, shift, heads, C / heads));
+                                                wsz, shift, heads, C / heads));
             if (lp && lp[1]) RUN(ivit_linear_i8_requant_residual_planned(h, lp[1], ctx, b.res1_main, b.res1_res, x, y, (int)M));
             else RUN(ivit_linear_i8_requant_residual(h, ctx, b.proj.w, b.proj.b, b.proj.dy, b.res1_main, b.res1_res, x, y, (int)M, C, C));
             { int16_t *t = x; x = y; y = t; }
@@ -548,7 +549,8 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
     }
     const int C = E << (c.num_layers - 1);
     RUN(swin_ln(m, h, x, M, C, P.s_norm_in, P.n, L, false, a8));
-    RUN(ivit_avgpool_requant(h, a8, B, L, C, P.dy_pool, pool));
+    RUN((L & 1) ? ivit_avgpool_requant(h, a8, B, L, C, P.dy_pool, pool)
+                : ivit_avgpool_requant_scaled(h, a8, B, L, C, P.s_pool, P.dy_pool, pool));
     RUN(ivit_linear_i8(h, pool, P.head_w, P.head_b, logits, B, c.num_classes, C));
 #undef RUN
     return IVIT_OK;
@@ -582,16 +584,30 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
     REQUIRE(h, cfg->num_layers == 1 || params->merges_host, "merges_host missing");
     REQUIRE(h, max_slices >= 1 && max_slices <= 16, "max_slices must be in [1, 16]");
     int nb = 0;
+    const int grid = cfg->img_size / cfg->patch_size;
+    if (cfg->window_size != 7 && cfg->window_size != 12) {
+        snprintf(h->err, sizeof(h->err), "ivit_swin_create: built for windows 7 and 12 and head dim 32");
+        return IVIT_ERR_UNSUPPORTED;
+    }
     for (int li = 0; li < cfg->num_layers; ++li) {
-        if (cfg->window_size != 7 || cfg->num_heads[li] <= 0 || ((cfg->embed_dim << li) / cfg->num_heads[li]) != 32) {
-            snprintf(h->err, sizeof(h->err), "ivit_swin_create: built for window 7 and head dim 32");
+        if (cfg->num_heads[li] <= 0 || ((cfg->embed_dim << li) / cfg->num_heads[li]) != 32 ||
+            (cfg->embed_dim << li) % cfg->num_heads[li] != 0) {
+            snprintf(h->err, sizeof(h->err), "ivit_swin_create: built for windows 7 and 12 and head dim 32");
             return IVIT_ERR_UNSUPPORTED;
         }
         nb += cfg->depths[li];
+        // every stage resolution a multiple of the window, or at most the window (then one unshifted window of that
+        // resolution, SwinTransformerBlock.__init__) whose size the fused attention is built for
+        REQUIRE(h, (grid % (1 << li)) == 0, "every stage resolution must be a multiple of the window");
+        const int res = grid >> li, wsz = res <= cfg->window_size ? res : cfg->window_size;
+        REQUIRE(h, res % wsz == 0, "every stage resolution must be a multiple of the window");
+        if (wsz != 7 && wsz != 12) {
+            snprintf(h->err, sizeof(h->err), "ivit_swin_create: stage %d runs window %d; built for windows 7 and 12", li, wsz);
+            return IVIT_ERR_UNSUPPORTED;
+        }
     }
-    const int grid = cfg->img_size / cfg->patch_size;
-    REQUIRE(h, (grid >> (cfg->num_layers - 1)) % 7 == 0 && grid % (7 << (cfg->num_layers - 1)) == 0,
-            "every stage resolution must be a multiple of the window");
+    REQUIRE(h, ((grid >> (cfg->num_layers - 1)) * (grid >> (cfg->num_layers - 1))) % 2 == 1 || params->s_pool > 0.f,
+            "s_pool (the pool's input scale) is needed for an even final token count");
     ivit_swin_s *m = new (std::nothrow) ivit_swin_s();
     if (!m) return IVIT_ERR_HIP;
     m->h = h; m->cfg = *cfg; m->prm = *params;

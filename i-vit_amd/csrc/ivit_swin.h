@@ -66,14 +66,38 @@ __global__ __launch_bounds__(256) void requant_bcast_kernel(const int32_t *__res
 // The reference averages fl(Q*s) in fp32 and the next QuantAct takes round(fl(mean/s)); with
 // L odd the exact quotient sum(Q)/L is never within 1/(2L) of a tie, far outside fp32 noise,
 // so z = rne(sum(Q)/L) in integers (pinned against the fp32 restatement in the oracle).
-__global__ __launch_bounds__(256) void avgpool_requant_kernel(const int8_t *__restrict__ x, int B, int L, int C,
+// With L even (window 12 at 384 px: L = 144) ties are reachable and the fp32 sequence decides them, so it is restated:
+// X = fl(Q*s), the token sum in torch's order for a reduction over the strided token dim (ATen vectorized_outer_sum:
+// per channel a sequential sum with the 16-step cascade, cascade_seq_sum_dev), mean = fl(sum/L), z = rint(fl(mean/s)).
+// -ffp-contract=off keeps every product and sum a separate rounding.  `s` is the input scale (unused for odd L).
+__device__ __forceinline__ float pool_x(const int8_t *x, int l, int C, float s) { return (float)x[(long long)l * C] * s; }
+__global__ __launch_bounds__(256) void avgpool_requant_kernel(const int8_t *__restrict__ x, int B, int L, int C, float s,
                                                               ivit_dyadic dy, int8_t *__restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B * C) return;
     const int b = i / C, c = i - b * C;
-    int sum = 0;
-    for (int l = 0; l < L; ++l) sum += (int)x[((long long)b * L + l) * C + c];
-    const int z = (int)__builtin_rint((double)sum / (double)L);
+    int z;
+    if (L & 1) {
+        int sum = 0;
+        for (int l = 0; l < L; ++l) sum += (int)x[((long long)b * L + l) * C + c];
+        z = (int)__builtin_rint((double)sum / (double)L);
+    } else {
+        const int8_t *xc = x + (long long)b * L * C + c;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int l = 0;
+        for (; l + 16 <= L;) {
+            for (int j = 0; j < 16; ++j, ++l) a0 += pool_x(xc, l, C, s);
+            a1 += a0; a0 = 0.f;
+            if ((l & 0xF0) != 0) continue;
+            a2 += a1; a1 = 0.f;
+            if ((l & 0xF00) != 0) continue;
+            a3 += a2; a2 = 0.f;
+        }
+        for (; l < L; ++l) a0 += pool_x(xc, l, C, s);
+        a0 += a1; a0 += a2; a0 += a3;
+        const float mean = a0 / (float)L;
+        z = (int)rintf(mean / s);
+    }
     out[i] = (int8_t)rq_c((double)z, dy.m * dy.r, -128, 127);
 }
 

@@ -93,7 +93,8 @@ def freeze_swin(cfg, weights, scales, exp_tables=False):
             c[p + "attn.relb"] = np.ascontiguousarray(
                 _rne_times(bias, dyadic(s[p + "attn.qact_table"], s[p + "attn.qact2"]))).astype(np.int16)
             c[p + "attn.s_softmax"] = s[p + "attn.qact2"]
-            tabs = shiftmax_tables(s[p + "attn.qact2"]) if exp_tables else None   # exp_int by table where no shift mask applies
+            # exp_int by table where no shift mask applies; the table form is built for window 7 only (window 12: arithmetic)
+            tabs = shiftmax_tables(s[p + "attn.qact2"]) if exp_tables and ws == 7 else None
             if tabs is not None:                               # else: the kernel's arithmetic path for this layer
                 c[p + "attn.exp_aq"], c[p + "attn.exp_t"], c[p + "attn.exp_cls"] = tabs["aq"], tabs["t"], tabs["cls"]
                 # three small integers, carried with the fp32 host scalars (exact: t_count <= 16384)
@@ -121,6 +122,7 @@ def freeze_swin(cfg, weights, scales, exp_tables=False):
     c["norm.s_in"] = s_x
     norm("norm", "qact2")
     c["dy_pool"] = dyadic(s["qact2"], s["qact3"])
+    c["pool.s_in"] = s["qact2"]
     c["head.scale"] = linear("head", s["qact3"], None)
     return c
 
@@ -184,10 +186,28 @@ def swin_native_params(cfg, table, f, dy, base):
     prm.merges_host = ctypes.cast(merges, ctypes.POINTER(L.SwinMerge))
     prm.s_norm_in, prm.n, prm.dy_pool = f["norm.s_in"], ln("norm"), dy["dy_pool"]
     prm.head_w, prm.head_b = a("head.w"), a("head.b")
+    prm.s_pool = f["pool.s_in"]
     c = L.SwinConfigC(cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.embed_dim, cfg.num_layers, cfg.window_size,
                       int(cfg.mlp_ratio), cfg.num_classes, (ctypes.c_int * 4)(*(list(cfg.depths) + [0] * 4)[:4]),
                       (ctypes.c_int * 4)(*(list(cfg.num_heads) + [0] * 4)[:4]))
     return c, prm, (blocks, merges)
+
+
+FUSED_WINDOWS = (7, 12)      # window sizes the fused windowed attention is built for (head dim 32)
+
+
+def check_swin_windows(cfg):
+    """IvitError unless the fused path covers cfg: head dim 32 everywhere, and every stage resolution a multiple of the
+    window or at most the window (then the stage is one unshifted window of that resolution, SwinTransformerBlock.__init__),
+    with every window that results in FUSED_WINDOWS."""
+    if any((cfg.embed_dim * 2 ** i) // h != 32 or (cfg.embed_dim * 2 ** i) % h for i, h in enumerate(cfg.num_heads)):
+        raise _lib.IvitError("the fused windowed attention is built for head dim 32")
+    for li in range(cfg.num_layers):
+        res = cfg.grid // 2 ** li
+        wsz = min(cfg.window_size, res)
+        if wsz not in FUSED_WINDOWS or res % wsz:
+            raise _lib.IvitError(f"the fused windowed attention is built for windows {FUSED_WINDOWS}: stage {li} has "
+                                 f"resolution {res} and window {wsz}")
 
 
 class SwinEngine:
@@ -198,8 +218,7 @@ class SwinEngine:
             raise _lib.IvitError("SwinEngine needs a HIP device; the product path has no CPU fallback")
         self.cfg, self.device = cfg, torch.device(device)
         torch.cuda.set_device(self.device)
-        if cfg.window_size != 7 or any((cfg.embed_dim * 2 ** i) // h != 32 for i, h in enumerate(cfg.num_heads)):
-            raise _lib.IvitError("the fused windowed attention is built for window 7 / head dim 32")
+        check_swin_windows(cfg)
         blob, table, host = packed if packed is not None else pack_swin_constants(freeze_swin(cfg, weights, scales, exp_tables))
         self.table, self.host_consts = table, host
         self.blob = torch.from_numpy(blob).to(self.device) if isinstance(blob, np.ndarray) else blob.to(self.device)
@@ -335,6 +354,7 @@ class SwinEngine:
             for bj in range(depth):
                 p = f"layers.{li}.blocks.{bj}."
                 shift = 0 if (bj % 2 == 0 or res <= cfg.window_size) else cfg.window_size // 2
+                wsz = min(cfg.window_size, res)
                 self._ln(x, M, C, f[p + "s_in"], p + "norm1", L, li == 0, ws["a8"])
                 call("ivit_linear_i8_requant", P(ws["a8"]), self.ptr(p + "attn.qkv.w"), self.ptr(p + "attn.qkv.b"),
                      self.ptr(p + "attn.qkv.dy"), 8, P(ws["qkv"]), M, 3 * C, C)
@@ -343,11 +363,11 @@ class SwinEngine:
                          self.ptr(p + "attn.relb"), f[p + "attn.s_softmax"], self.ptr(p + "attn.exp_aq"),
                          self.ptr(p + "attn.exp_t"), self.ptr(p + "attn.exp_cls"), int(f[p + "attn.exp_nc"]),
                          int(f[p + "attn.exp_tcount"]), int(f[p + "attn.exp_dmin"]), dy[p + "attn.dy_pv"], P(ws["ctx"]),
-                         B, res, cfg.window_size, shift, heads, C // heads)
+                         B, res, wsz, shift, heads, C // heads)
                 else:
                     call("ivit_window_attention_fused", P(ws["qkv"]), dy[p + "attn.dy_qk"], dy[p + "attn.dy_a"],
                          self.ptr(p + "attn.relb"), f[p + "attn.s_softmax"], dy[p + "attn.dy_pv"], P(ws["ctx"]),
-                         B, res, cfg.window_size, shift, heads, C // heads)
+                         B, res, wsz, shift, heads, C // heads)
                 call("ivit_linear_i8_requant_residual", P(ws["ctx"]), self.ptr(p + "attn.proj.w"), self.ptr(p + "attn.proj.b"),
                      self.ptr(p + "attn.proj.dy"), dy[p + "res1.dy_main"], dy[p + "res1.dy_res"], P(x), P(y), M, C, C)
                 x, y = y, x
@@ -370,7 +390,7 @@ class SwinEngine:
                 call("ivit_widen_i8_i16", P(ws["ctx"]), P(x), M * 2 * C)
         C = E * 2 ** (cfg.num_layers - 1)
         self._ln(x, M, C, f["norm.s_in"], "norm", L, False, ws["a8"])
-        call("ivit_avgpool_requant", P(ws["a8"]), B, L, C, dy["dy_pool"], P(ws["pool"]))
+        call("ivit_avgpool_requant_scaled", P(ws["a8"]), B, L, C, f["pool.s_in"], dy["dy_pool"], P(ws["pool"]))
         call("ivit_linear_i8", P(ws["pool"]), self.ptr("head.w"), self.ptr("head.b"), P(ws["logits"]), B, cfg.num_classes, C)
         return ws["logits"]
 

@@ -21,7 +21,7 @@ from .quant_modules import (QuantLinear, QuantAct, IntLayerNorm, IntSoftmax, Int
 from .synth import SwinConfig
 
 __all__ = ["swin_tiny_patch4_window7_224", "swin_small_patch4_window7_224", "swin_base_patch4_window7_224",
-           "SwinTransformer"]
+           "swin_base_patch4_window12_384", "SwinTransformer"]
 
 
 def window_partition(x, window_size):
@@ -315,7 +315,8 @@ class SwinTransformer(nn.Module):
         d = fz.dyadic(_f32(s), s3)
         out = torch.empty(B, C, dtype=torch.int8, device=x.device)
         xc = x.contiguous()
-        handle(x.device).call("ivit_avgpool_requant", _ptr(xc), B, L, C, _dyv(d), _ptr(out))
+        # the input scale decides rounding ties of the mean at even L (384 px, window 12: L = 144)
+        handle(x.device).call("ivit_avgpool_requant_scaled", _ptr(xc), B, L, C, float(np.asarray(_f32(s)).reshape(-1)[0]), _dyv(d), _ptr(out))
         return out, self.qact3.act_scaling_factor
 
     def forward(self, x):
@@ -336,7 +337,8 @@ def _swin(pretrained=False, **kw):
     if pretrained:
         raise NotImplementedError("pretrained checkpoints need network access; load a state dict instead")
     kw.setdefault("norm_layer", partial(IntLayerNorm, eps=1e-6))
-    return SwinTransformer(patch_size=4, window_size=7, **kw)
+    kw.setdefault("window_size", 7)
+    return SwinTransformer(patch_size=4, **kw)
 
 
 def swin_tiny_patch4_window7_224(pretrained=False, **kwargs):
@@ -348,4 +350,13 @@ def swin_small_patch4_window7_224(pretrained=False, **kwargs):
 
 
 def swin_base_patch4_window7_224(pretrained=False, **kwargs):
+    return _swin(pretrained, embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), **kwargs)
+
+
+def swin_base_patch4_window12_384(pretrained=False, **kwargs):
+    """Swin-B at 384 px with a 12 x 12 window (the official patch4_window12_384 checkpoints).
+    The reference has no factory for it (its factories fix window 7); it builds the same model as
+    SwinTransformer(img_size=384, window_size=12, embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32))."""
+    kwargs.setdefault("img_size", 384)
+    kwargs.setdefault("window_size", 12)
     return _swin(pretrained, embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), **kwargs)

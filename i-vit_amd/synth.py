@@ -150,6 +150,12 @@ SWIN_CONFIGS = {
     "swin_tiny": SwinConfig("swin_tiny"),
     "swin_small": SwinConfig("swin_small", depths=(2, 2, 18, 2)),
     "swin_base": SwinConfig("swin_base", embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32)),
+    # window 12: stage 0 is 24 x 24 (4 windows, shift 6), stage 1 one 12 x 12 window and a pool over 144 tokens
+    "micro_swin_w12": SwinConfig("micro_swin_w12", img_size=96, num_classes=10, embed_dim=32, depths=(2, 2),
+                                 num_heads=(1, 2), window_size=12),
+    # Swin-B at 384 px with a 12 x 12 window (the patch4_window12_384 checkpoints): stages 96 / 48 / 24 / 12
+    "swin_base_384": SwinConfig("swin_base_384", img_size=384, embed_dim=128, depths=(2, 2, 18, 2),
+                                num_heads=(4, 8, 16, 32), window_size=12),
 }
 
 

@@ -48,7 +48,10 @@ enum {
     IVIT_ERR_NO_DEVICE = 4
 };
 
-/* 100 * major + minor.  104 (round 6): ivit_set_cu_share, ivit_linear_i8_requant8_store16 (additions only).
+/* 100 * major + minor.  105: ivit_avgpool_requant_scaled (addition); ivit_swin_params gains s_pool at its END — ivit_swin_create
+ * copies the whole struct, so a caller compiled against an older header must be rebuilt (its struct is shorter than the
+ * library reads); windows 12 in ivit_window_attention_fused / ivit_swin_create.
+ * 104 (round 6): ivit_set_cu_share, ivit_linear_i8_requant8_store16 (additions only).
  * 103 (round 6): ivit_linear_plan_prepare_ws, ivit_layernorm_linear_i8_qkv_planned,
  * ivit_linear_i8_requant_residual_layernorm_planned, ivit_layernorm_linear_i8_requant_planned, ivit_patch_embed,
  * ivit_layernorm_mlp_fused_planned (additions only).
@@ -57,7 +60,7 @@ enum {
  * fields exp_* at their END (added in 100 without a bump: a caller compiled against an older layout must be rebuilt).
  * Parameter structs are read field by field: ZERO-INITIALISE them (memset / = {0}) before filling — exp_aq == NULL (and
  * exp_nc == exp_tcount == exp_dmin == 0) selects the arithmetic Shiftmax, anything else is taken as device pointers.        */
-#define IVIT_VERSION 104
+#define IVIT_VERSION 105
 int ivit_version(void);
 const char *ivit_status_string(int status);
 
@@ -69,6 +72,7 @@ int ivit_set_stream(ivit_handle h, void *hip_stream);
  * grids for; 0 (the default) = every CU of the device.  A caller that runs several handles side by side on slices of a batch — what
  * ivit_vit_forward / ivit_swin_forward do internally with nslices > 1 — gives each handle its share (CUs / slices): a slice's launch then
  * has the per-workgroup geometry of the unsliced one and the slices' kernels run on disjoint CUs (Swin-T b256, two slices: +2.0 %).
+ * The window-12 attention sizes its windows per block for the share too (fewer CUs: more windows per block).
  * No reference counterpart (the reference has no launch geometry); results do not depend on it. */
 int ivit_set_cu_share(ivit_handle h, int cus);
 const char *ivit_last_error(ivit_handle h);
@@ -375,7 +379,9 @@ int ivit_graph_destroy(ivit_graph g);
  * SwinTransformerBlock.forward (:251-301), WindowAttention.forward (:121-169), PatchMerging.forward
  * (:328-349) and PatchEmbed.forward (layers_quant.py:184-196) chained natively; activations stay in natural
  * token order, roll / window partition / reverse are index arithmetic inside ivit_window_attention_fused.
- * Built for window 7 and head dim 32 (every reference factory).  Same conventions as ivit_vit_*.      */
+ * Built for window 7 (every reference factory) or 12 (patch4_window12_384), head dim 32; a stage whose
+ * resolution is at most the window runs one window of that resolution, unshifted (SwinTransformerBlock).
+ * Same conventions as ivit_vit_*.                                                               */
 typedef struct ivit_ln_params { const float *bias_int; const float *sc; const ivit_dyadic *dy; } ivit_ln_params;
 typedef struct ivit_lin_params { const int8_t *w; const int32_t *b; const ivit_dyadic *dy; } ivit_lin_params;
 
@@ -411,6 +417,7 @@ typedef struct ivit_swin_params {
     float s_norm_in; ivit_ln_params n;                     /* norm -> qact2                                     */
     ivit_dyadic dy_pool;                                   /* avgpool -> qact3                                  */
     const int8_t *head_w; const int32_t *head_b;
+    float s_pool;                                          /* qact2 scale: the pool's input (even token counts) */
 } ivit_swin_params;
 
 typedef struct ivit_swin_s *ivit_swin;
@@ -436,6 +443,11 @@ int ivit_requant_i32_bcast(ivit_handle h, const int32_t *z, ivit_dyadic dy, cons
 /* AdaptiveAvgPool1d(1) over L (odd) tokens + QuantAct(8) (:553-555): x int8 [B,L,C] -> [B,C]   */
 int ivit_avgpool_requant(ivit_handle h, const int8_t *x, int B, int L, int C, ivit_dyadic dy,
                          int8_t *out8);
+/* The same for any L, given the input scale: with L even rounding ties are reachable and are
+ * decided by the reference's fp32 sequence (fl(Q*s), torch's token-sum order, fl(sum/L),
+ * rint(fl(mean/s))), restated exactly; odd L gives the outputs of ivit_avgpool_requant.      */
+int ivit_avgpool_requant_scaled(ivit_handle h, const int8_t *x, int B, int L, int C, float scale,
+                                ivit_dyadic dy, int8_t *out8);
 /* IntLayerNorm whose row sums follow torch's order for a TOKEN-contiguous input — what the
  * reference computes in Swin stage 0, where activations keep the layout of
  * flatten(2).transpose(1,2) (layers_quant.py:188).  Same outputs as
@@ -459,15 +471,17 @@ int ivit_patch_norm_tokenorder(ivit_handle h, const int8_t *x8, int64_t rows, in
  * Shiftmax 8 bit on attn (+ shift mask, :151-156) -> attn.v -> qact3 — including torch.roll,
  * window_partition and their inverses (swin_quant.py:18-50, 268-287) as index arithmetic.
  * qkv int8 [B, R, R, 3, heads, dh] in natural token order; ctx int8 [B, R*R, heads*dh] natural order.
- * relb int16 [heads, 49, 49] = rq(quantised bias table gathered by relative_position_index,
- * dy(qact_table -> qact2)); dy_a = dy(qact_attn1 -> qact2).  Built for window 7, dh 32.       */
+ * relb int16 [heads, N, N] (N = window^2) = rq(quantised bias table gathered by
+ * relative_position_index, dy(qact_table -> qact2)); dy_a = dy(qact_attn1 -> qact2).
+ * Built for window 7 (R % 7 == 0) and window 12 (R % 12 == 0, relb 16-byte aligned), dh 32.  */
 int ivit_window_attention_fused(ivit_handle h, const int8_t *qkv, ivit_dyadic dy_qk, ivit_dyadic dy_a,
                                 const int16_t *relb, float s_softmax, ivit_dyadic dy_pv, int8_t *ctx,
                                 int B, int R, int window, int shift, int heads, int dh);
 /* The same with Shiftmax's exp_int (IntSoftmax.int_exp_shift, quant_modules.py:469-481) taken from the tables of
  * ivit_attention_fused_lut (ivit_amd.freeze.shiftmax_tables for the layer's frozen qact2 scale; same layout, alignment and
  * errors) in the windows that carry no shift mask; windows under the mask (swin_quant.py:151-156) keep the arithmetic
- * form, because the float -100 enters between the requotient's multiply and divide.  Same integers as the entry above. */
+ * form, because the float -100 enters between the requotient's multiply and divide.  Same integers as the entry above.
+ * Window 7 only (IVIT_ERR_UNSUPPORTED at window 12).                                                                  */
 int ivit_window_attention_fused_lut(ivit_handle h, const int8_t *qkv, ivit_dyadic dy_qk, ivit_dyadic dy_a,
                                     const int16_t *relb, float s_softmax, const uint16_t *exp_aq, const float *exp_t,
                                     const uint8_t *exp_cls, int nclass, int t_count, int dmin, ivit_dyadic dy_pv,

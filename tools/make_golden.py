@@ -292,6 +292,12 @@ def main():
         # swin_base_patch4_window7_224 (swin_quant.py:609-627): embed 128, heads 4/8/16/32 — channel counts no other fixture has
         swin_fixture(models, "swin_base", 1, 1, 0, False, "swin_base_b1.npz")
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "--window12":
+        # window 12 (SwinTransformer(window_size=12), the patch4_window12_384 family): the micro model and
+        # Swin-B at 384 px with checksums only
+        swin_fixture(models, "micro_swin_w12", 2, 4, 0, False, "micro_swin_w12_b2.npz")
+        swin_fixture(models, "swin_base_384", 1, 1, 0, False, "swin_base_384_b1.npz")
+        return
     op_fixtures(models)
     model_fixture(models, "micro_vit", 2, 4, 0, True, "micro_vit_b2.npz")
     model_fixture(models, "micro_vit2h", 3, 4, 0, True, "micro_vit2h_b3.npz")
