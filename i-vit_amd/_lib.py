@@ -9,7 +9,8 @@ import subprocess
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 SO_PATH = os.environ.get("IVIT_LIB") or os.path.join(_CSRC, "libivit_hip.so")
-SOURCES = ["ivit_hip.hip", "ivit_device.h", "ivit_gemm.h", "ivit_elementwise.h", "ivit_layernorm.h", "ivit_attention.h", "ivit_gemm2.h", "ivit_gemm3.h", "ivit_gemm_wreg.h", "ivit_swin.h", "ivit_mlp.h", "ivit_mlp_rs.h", "ivit_swin_mlp_rs.h", "ivit_swin12.h", "ivit_model.h"]
+# the one translation unit and every header it may include: an edit to any of them rebuilds the library
+SOURCES = ["ivit_hip.hip"] + sorted(f for f in os.listdir(_CSRC) if f.endswith(".h"))
 _THIS = os.path.abspath(__file__)
 # -packed-fp32-ops: no v_pk_{add,mul,fma}_f32 anywhere in the library.  Round 4 traced the sporadic one-LSB differences of
 # layernorm_reg_kernel<192, 1> beside QuantLinear GEMM workgroups to that instruction class; round 5 to one form of it:
@@ -42,7 +43,7 @@ class Dyadic(ctypes.Structure):
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, s) for s in SOURCES if os.path.exists(os.path.join(_CSRC, s))]
+    srcs = [os.path.join(_CSRC, s) for s in SOURCES]
     hdr = os.path.join(os.path.dirname(_CSRC), "..", "include", "ivit.h")
     newest = max(os.path.getmtime(p) for p in srcs + [hdr, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
@@ -230,7 +231,7 @@ SIGNATURES = {
     "ivit_embed_finish": [_P, _P, _P, _P, Dyadic, Dyadic, _P, _I, _I, _I],
     "ivit_patch_embed": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, Dyadic, Dyadic, _P, _I],
 }
-OTHER_SYMBOLS = ["ivit_version", "ivit_status_string", "ivit_last_error", "ivit_linear_plan_destroy", "ivit_mlp_plan_destroy", "ivit_linear_plan_query", "ivit_debug_plan_scratch", "ivit_mlp_plan_select"]
+OTHER_SYMBOLS = ["ivit_version", "ivit_status_string", "ivit_last_error", "ivit_linear_plan_destroy", "ivit_mlp_plan_destroy", "ivit_linear_plan_query", "ivit_mlp_plan_select"]
 
 _lib = None
 
@@ -257,8 +258,6 @@ def load():
     lib.ivit_linear_plan_destroy.restype = ctypes.c_int
     lib.ivit_linear_plan_query.argtypes = [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]
     lib.ivit_linear_plan_query.restype = ctypes.c_int
-    lib.ivit_debug_plan_scratch.argtypes = [_P, _P, _I]
-    lib.ivit_debug_plan_scratch.restype = ctypes.c_int
     lib.ivit_mlp_plan_select.argtypes = [_P, _I]
     lib.ivit_mlp_plan_select.restype = ctypes.c_int
     lib.ivit_mlp_plan_destroy.argtypes = [_P]

@@ -41,15 +41,7 @@ struct AttnArgs {
 
 // wavefronts per workgroup.  8 = two workgroups per CU fill the 16 wave slots that 121 registers allow (round 4, after the prologue
 // changes: 52-54 us against 60-61 with 7, which had been the better choice in round 3; 6: slower)
-#ifndef ATT_WAVES
 #define ATT_WAVES 8
-#endif
-#ifndef ATT_PROBE          // timing probes only (results invalid): 1 first gather lane-linear, 2 second gather lane-linear with the
-#define ATT_PROBE 0        // first one dead, 4 second gather lane-linear with the first one kept alive, 8 no second gather
-#endif
-#ifndef ATT_PERMLANE       // probe: 1 = row maximum by v_permlane16/32_swap, 2 = the partner accumulators of the row sum likewise
-#define ATT_PERMLANE 2     // (instead of ds_bpermute).  Same box, interleaved twice: 1 costs +3 us (it sits on the tile's critical path), 2 gains 0.3
-#endif
 #define ATT_DH 64
 
 __device__ __forceinline__ int att_kswz(int row, int g) {   // 16-byte chunk position in a K row
@@ -79,14 +71,11 @@ struct AttCfg {
 // entries that depends on vmax alone: the wave fetches its 16 queries' lines (256 B each, from the 64 KB rowtab in L2) into LDS
 // once the row maxima are known and every score then costs a saturating subtract, an address and one ds_read_b32 — the
 // class-of-v gather, its address arithmetic and the per-workgroup copy of the two-level tables are gone.
-#ifndef ATT_MINW           // waves per SIMD the kernel is compiled for (probe; 1 = whatever the workgroup size implies)
-#define ATT_MINW 1
-#endif
 // VROW (round 6, with LUT = 2): v arrives ROW-major [B*H, T, 64] like q and k (p.ldv == 0) and is transposed on its way into the
 // LDS — four keys x 16 channels per thread, byte-transposed in registers with v_perm — instead of v^T [B*H, 64, ldv] written by the
 // qkv GEMM with sixteen byte stores per token (which cost that GEMM ~20 % of its time).
 template <int NB, bool FAST, int TT = 0, int LUT = 0, bool VROW = false>
-__global__ __launch_bounds__(ATT_WAVES * 64, ATT_MINW) void attn_fused_kernel(AttnArgs p) {
+__global__ __launch_bounds__(ATT_WAVES * 64, 1) void attn_fused_kernel(AttnArgs p) {
     using C = AttCfg<NB>;
     extern __shared__ __attribute__((aligned(16))) char dsmem[];
     char *sK = dsmem;
@@ -142,7 +131,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, ATT_MINW) void attn_fused_kernel(At
         if (c < 64 * C::NT && t0 < T) vreg[i] = *reinterpret_cast<const v4i *>(vg + (long long)d * p.ldv + t0);
     }
     }
-    if (LUT == 1 && !(ATT_PROBE & 32)) {
+    if (LUT == 1) {
         // table offsets are staged as BYTE offsets into sT (x4: t_count <= 16384 keeps them in 16 bits): a score's
         // table address is then one v_lshl_add_u32 on top of the saturating distance
         const int n4 = p.t_count >> 2, a4 = p.nc * 32;          // whole 16-byte chunks (the launcher checks the alignment)
@@ -238,7 +227,6 @@ __global__ __launch_bounds__(ATT_WAVES * 64, ATT_MINW) void attn_fused_kernel(At
     const int nqt = (T + 15) >> 4;         // query tiles
     const int nvec = T >> 3, size = nvec >> 2;
 
-    if (ATT_PROBE & 16) return;           // prologue only
     // (round 6: requesting this fragment together with the K / V^T rows of the prologue measured 0.5-1 us SLOWER on one box)
     v4i qnext = {0, 0, 0, 0};
     if (wave < nqt && wave * 16 + qi < T) qnext = *reinterpret_cast<const v4i *>(qg + (wave * 16 + qi) * 64 + g * 16);
@@ -276,17 +264,10 @@ __global__ __launch_bounds__(ATT_WAVES * 64, ATT_MINW) void attn_fused_kernel(At
                 for (int r = 0; r < 4; ++r) f[j][r] = 0.f;
             }
         }
-        // the query's four lanes (qi, qi + 16, qi + 32, qi + 48): two register swaps instead of two trips through the LDS crossbar —
-        // v_permlane16_swap(a, a) leaves (rows 0 0 2 2 | rows 1 1 3 3), v_permlane32_swap(a, a) (rows 0 1 0 1 | rows 2 3 2 3)
-        if (ATT_PERMLANE & 1) {
-            auto s16 = __builtin_amdgcn_permlane16_swap((unsigned)qmax, (unsigned)qmax, false, false);
-            qmax = max((int)s16[0], (int)s16[1]);
-            auto s32 = __builtin_amdgcn_permlane32_swap((unsigned)qmax, (unsigned)qmax, false, false);
-            qmax = max((int)s32[0], (int)s32[1]);
-        } else {
-            qmax = max(qmax, __shfl_xor(qmax, 16));
-            qmax = max(qmax, __shfl_xor(qmax, 32));
-        }
+        // the query's four lanes (qi, qi + 16, qi + 32, qi + 48).  (v_permlane16/32_swap instead of the two trips through the LDS
+        // crossbar measured +3 us here: the exchange sits on the tile's critical path)
+        qmax = max(qmax, __shfl_xor(qmax, 16));
+        qmax = max(qmax, __shfl_xor(qmax, 32));
         const float mx = sXq[qmax + 128 - VB];
         // byte offset of aq[class(vmax)][v' = 0]: ((class * 256 + 128) - VB) * 2
         const int rowbase2 = LUT == 1 ? ((int)sCls[qmax + 128 - VB] * 256 + 128 - VB) * 2 : 0;
@@ -344,7 +325,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, ATT_MINW) void attn_fused_kernel(At
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             e1[jj][r] = (int)*reinterpret_cast<__attribute__((address_space(3))) const unsigned short *>(
-                                (size_t)(ATT_PROBE & 1 ? aqrow + ((unsigned)(threadIdx.x & 63) << 1) : (((unsigned)__float_as_int(f[j0 + jj][r]) << 1) + aqrow)));
+                                (size_t)(((unsigned)__float_as_int(f[j0 + jj][r]) << 1) + aqrow));
                     }
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj)
@@ -363,9 +344,8 @@ __global__ __launch_bounds__(ATT_WAVES * 64, ATT_MINW) void attn_fused_kernel(At
                         const int j = j0 + jj;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            if (ATT_PROBE & 4) asm volatile("" :: "v"(e1[jj][r]));
-                            const float e = ATT_PROBE & 8 ? __int_as_float(e1[jj][r]) : *reinterpret_cast<__attribute__((address_space(3))) const float *>(
-                                (att_lds_c *)(size_t)(unsigned)C::SMEM + (ATT_PROBE & 6 ? ((unsigned)(threadIdx.x & 63) << 2) + (ATT_PROBE & 2 ? (unsigned)e1[jj][r] & 0u : 0u) : (unsigned)e1[jj][r]));
+                            const float e = *reinterpret_cast<__attribute__((address_space(3))) const float *>(
+                                (att_lds_c *)(size_t)(unsigned)C::SMEM + (unsigned)e1[jj][r]);
                             f[j][r] = (j * 16 + 15 < T || j * 16 + g * 4 + r < T) ? e : 0.f;
                         }
                     }
@@ -438,15 +418,9 @@ __global__ __launch_bounds__(ATT_WAVES * 64, ATT_MINW) void attn_fused_kernel(At
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             // lane ^ 32's accumulators, needed on the lower 32 lanes only: after v_permlane32_swap(a, a) the second result holds
-            // (upper half | upper half)
-            float o0, o1;
-            if (ATT_PERMLANE & 2) {
-                o0 = __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(A0[0][r]), __float_as_uint(A0[0][r]), false, false)[1]);
-                o1 = __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(A0[1][r]), __float_as_uint(A0[1][r]), false, false)[1]);
-            } else {
-                o0 = __shfl_xor(A0[0][r], 32);
-                o1 = __shfl_xor(A0[1][r], 32);
-            }
+            // (upper half | upper half).  One register swap instead of a trip through the LDS crossbar (ds_bpermute): 0.3 us faster
+            const float o0 = __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(A0[0][r]), __float_as_uint(A0[0][r]), false, false)[1]);
+            const float o1 = __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(A0[1][r]), __float_as_uint(A0[1][r]), false, false)[1]);
             pl[r] = ((A0[0][r] + o0) + A0[1][r]) + o1;   // valid on lanes g = 0 (l=r) and g = 1 (l=4+r)
         }
         float fin = 0.f;

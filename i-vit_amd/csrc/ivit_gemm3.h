@@ -27,13 +27,6 @@
 #pragma once
 #include "ivit_gemm2.h"
 
-// ablation mask, compile time only (a run-time test would split every k-step into several basic blocks and
-// forbid the MFMA / VALU interleaving the kernels are built around): build with -DG3_DBG=<mask> into a scratch
-// library and point IVIT_LIB at it.  1 = no operand DMA after the first unit, 2 = no LDS fragment reads / MFMAs,
-// 4 = no epilogue arithmetic, 8 = no output stores.  Results are invalid, timing only.
-#ifndef G3_DBG
-#define G3_DBG 0
-#endif
 #define G3_NS 3
 #define G3_STG_LD 136
 #define G3_CONST_BYTES 1536
@@ -207,24 +200,20 @@ __global__ __launch_bounds__(G3Cfg<ASTAT>::NT, 2) void gemm_ps_kernel(GemmArgs p
         if (u_load >= u_end) { infl = 0; return; }
         const int row0 = l_tm << BMSH, col0 = l_tn << 7;
         if (l_kt == 0) g3_issue_consts(p, col0, cst0 + l_par * G3_CONST_BYTES, wave, lane);
-        const bool skip = (G3_DBG & 1) && u_load != u_first;     // ablation: no operand traffic after the first unit
         if (ASTAT) {
             if (l_need_a) {
-                if (!skip) g3_issue_a256(A, p.lda, p.M, row0, l_kt * G2_BK, smem + l_kt * 16384, tid);
+                g3_issue_a256(A, p.lda, p.M, row0, l_kt * G2_BK, smem + l_kt * 16384, tid);
                 infl = 3;
             } else {
                 infl = 1;
             }
-            if (!skip) g3_issue_w128(B, p.ldb, p.N, col0, l_kt * G2_BK, ring + l_slot * Cf::STAGE, tid);
+            g3_issue_w128(B, p.ldb, p.N, col0, l_kt * G2_BK, ring + l_slot * Cf::STAGE, tid);
         } else {
-            if (!skip) {
-                const int8_t *abase[2] = {A + (long long)min(row0 + (tid >> 2), p.M - 1) * p.lda,
-                                          A + (long long)min(row0 + ((tid + G2Cfg<128>::THREADS) >> 2), p.M - 1) * p.lda};
-                g2_issue<128>(abase, B, p.ldb, p.N, col0, l_kt * G2_BK, ring + l_slot * Cf::STAGE, tid);
-            }
+            const int8_t *abase[2] = {A + (long long)min(row0 + (tid >> 2), p.M - 1) * p.lda,
+                                      A + (long long)min(row0 + ((tid + G2Cfg<128>::THREADS) >> 2), p.M - 1) * p.lda};
+            g2_issue<128>(abase, B, p.ldb, p.N, col0, l_kt * G2_BK, ring + l_slot * Cf::STAGE, tid);
             infl = 4;
         }
-        if (skip) infl = 0;
         l_slot = (l_slot == G3_NS - 1) ? 0 : l_slot + 1;
         if (++l_kt == nk) {
             l_kt = 0;
@@ -270,7 +259,7 @@ __global__ __launch_bounds__(G3Cfg<ASTAT>::NT, 2) void gemm_ps_kernel(GemmArgs p
                     const int id = tid + i * NT, row = id >> 3, c = id & 7;
                     const int grow = prev.row0 + row, gcol = prev.col0 + c * 16;
                     const v4i v = g3_stg_read16(stg + row * G3_STG_LD + c * 16);
-                    if (grow < p.M && gcol < p.N && !(G3_DBG & 8))
+                    if (grow < p.M && gcol < p.N)
                         *reinterpret_cast<v4i *>(reinterpret_cast<int8_t *>(p.out) + (long long)grow * p.ldc + gcol) = v;
                 } else {
                     // rows-fastest: a wave covers 64 consecutive tokens of one 16-channel piece
@@ -398,7 +387,7 @@ __global__ __launch_bounds__(G3Cfg<ASTAT>::NT, 2) void gemm_ps_kernel(GemmArgs p
                 issue_next();
                 asm volatile("" ::: "memory");
             }
-            if (HAS_CUR && !(G3_DBG & 2)) {
+            if (HAS_CUR) {
                 const char *sB = ring + c_slot * Cf::STAGE + (ASTAT ? 0 : 8192);
                 const char *sA = ASTAT ? smem + kt * 16384 : ring + c_slot * Cf::STAGE;
                 v4i a[2], b[2];
@@ -436,7 +425,7 @@ __global__ __launch_bounds__(G3Cfg<ASTAT>::NT, 2) void gemm_ps_kernel(GemmArgs p
                 }
             }
             if (HAS_CUR) c_slot = (c_slot == G3_NS - 1) ? 0 : c_slot + 1;
-            if (!(G3_DBG & 4)) epi_main(ch_t);
+            epi_main(ch_t);
         };
         kstep(std::integral_constant<int, 0>{}, 0);
         kstep(std::integral_constant<int, 1>{}, 1);
@@ -484,8 +473,7 @@ __global__ __launch_bounds__(G3Cfg<ASTAT>::NT, 2) void gemm_ps_kernel(GemmArgs p
 // step already requests unit i+1's).  A unit is 3 k-steps of 128 columns (n rounds of them for K = n * 384); a k-step is
 // four SECTIONS of 4 MFMAs per wave (8 waves as 4 (tokens) x 2 (channels), 64 x 64 per wave).
 //
-// What the timeline trace (G3_TRACE, tools/gemm3_trace.py) and the ablation builds said, and what the kernel does
-// about it (profiles/README.md has the numbers):
+// What timeline traces and ablation builds said, and what the kernel does about it (profiles/README.md has the numbers):
 //   * a global_load_lds takes ~0.85 us from issue to landing: the ring runs two k-steps ahead, across unit boundaries;
 //   * a section that reads fragments or multipliers from the LDS and uses them at once stalls ~200 cycles with at most
 //     one MFMA in flight: everything a section consumes is requested one section earlier, and the step's barrier sits
@@ -506,7 +494,7 @@ __global__ __launch_bounds__(G3Cfg<ASTAT>::NT, 2) void gemm_ps_kernel(GemmArgs p
 //     spill reload carries an s_waitcnt vmcnt(0) that drains the DMA ring;
 //   * the counted wait is `s_waitcnt vmcnt(C)` with C = the smallest count the steady state produces (4, or 8 with A
 //     streaming) whenever the exact count n >= C — only stricter, never wrong — and falls back to smaller immediates at
-//     a workgroup's first and last units (ga_wait_vm_fast; the exact jump table stays behind G3_WAIT_TABLE).
+//     a workgroup's first and last units (ga_wait_vm_fast; the exact jump table, ga_wait_vm, serves the prologue).
 // Where it stands (fc1, 50432 x 1536 x 384): 45.6 us = 1.30 POP/s.  The matrix pipe sustains 47 cycles per MFMA on
 // random int8 data and the fp64 requant costs ~19 SIMD-cycles per 64 outputs that do NOT hide behind MFMAs of the
 // other wave (tools/ubench/overlap.hip: 46.6 cycles per MFMA alone, 72 with this kernel's 1.33 outputs per MFMA):
@@ -518,23 +506,6 @@ __global__ __launch_bounds__(G3Cfg<ASTAT>::NT, 2) void gemm_ps_kernel(GemmArgs p
 #define GA_WSTAGE 16384               // 128 channels x 128 B
 #define GA_RING (GA_NK * GA_WSTAGE)
 #define GA_SMEM (GA_PANEL + GA_RING + 3 * G3_CONST_BYTES)
-// timeline instrumentation (compile time, -DG3_TRACE=1 into a scratch library): wave w of workgroup 0 stamps
-// s_memtime at six points of every k-step of three units into LDS and dumps them behind the plan's store
-// scratch (read back with ivit_debug_plan_scratch).  Points 0..3: start of section 0..3; 4 / 5: before / after the
-// counted wait (the barrier follows 5).  The stamps themselves cost ~80 cycles each.
-#ifndef G3_TRACE
-#define G3_TRACE 0
-#endif
-// 1: waves 4..7 run at s_setprio 1.  Zero-sum (timeline trace): whichever SIMD mate has the priority finishes its
-// step ~500 cycles earlier and waits that much longer at the barrier; kept as a switch for experiments.
-#ifndef G3_PRIO
-#define G3_PRIO 0
-#endif
-// 1: counted waits through the jump table (exact); 0: two inline levels (ga_wait_vm_fast)
-#ifndef G3_WAIT_TABLE
-#define G3_WAIT_TABLE 0
-#endif
-#define GA_TRACE_BYTES (G3_TRACE ? 8 * 3 * 6 * 4 * 8 : 0)
 
 // wait until at most n (uniform, SGPR) vector-memory instructions of this wave are outstanding, and for all LDS
 // traffic.  s_waitcnt only takes an immediate, so the wait is an indexed jump into a table of 48 eight-byte
@@ -638,12 +609,11 @@ __device__ __forceinline__ void ga_dma16(const int8_t *sbase, unsigned voff, uns
 
 template <int EPI, bool MULTI, bool FMA>
 __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
-    __shared__ __attribute__((aligned(128))) char smem[GA_SMEM + GA_TRACE_BYTES];
+    __shared__ __attribute__((aligned(128))) char smem[GA_SMEM];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1, half = lane >> 5;
     constexpr bool OUT8 = (EPI == EPI_RQ8_CH || EPI == EPI_QKV);
     constexpr bool RES = (EPI == EPI_RQ16_CH_RES);
-    if (G3_PRIO && wave >= 4) __builtin_amdgcn_s_setprio(1);
     const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
     const unsigned ring_lds = smem_lds + GA_PANEL, cst_lds = ring_lds + GA_RING;
 
@@ -698,24 +668,22 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
     auto issue_slice = [&](auto s_t, const GaUnit &u, const int round) __attribute__((always_inline)) {
         constexpr int S = decltype(s_t)::value;
         const int kb = round * (GA_BK * GA_NK) + S * GA_BK;
-        if (!((G3_DBG & 1) && u.row0 + u.col0 != 0)) {
-            const int t = tid_once(), r = t >> 3, ck = ((t & 7) ^ ((t >> 4) & 7)) * 16;
-            // scalar slice bases, opaque so that the address stays (SGPR base) + (32-bit VGPR offset)
-            const int8_t *sa = A + kb, *sb = B + kb;
-            asm volatile("" : "+s"(sa), "+s"(sb));
-            if (MULTI || u.need_a) {
+        const int t = tid_once(), r = t >> 3, ck = ((t & 7) ^ ((t >> 4) & 7)) * 16;
+        // scalar slice bases, opaque so that the address stays (SGPR base) + (32-bit VGPR offset)
+        const int8_t *sa = A + kb, *sb = B + kb;
+        asm volatile("" : "+s"(sa), "+s"(sb));
+        if (MULTI || u.need_a) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    ga_dma16(sa, (unsigned)min(a_row0 + r + i * 64, p.M - 1) * (unsigned)p.lda + ck,
-                             smem_lds + S * GA_ASLICE + i * 8192 + dma_lane0);
-                issued += 4;
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                ga_dma16(sb, (unsigned)min(w_col0 + r + i * 64, p.N - 1) * (unsigned)p.ldb + ck,
-                         ring_lds + S * GA_WSTAGE + i * 8192 + dma_lane0);
-            issued += 2;
+            for (int i = 0; i < 4; ++i)
+                ga_dma16(sa, (unsigned)min(a_row0 + r + i * 64, p.M - 1) * (unsigned)p.lda + ck,
+                         smem_lds + S * GA_ASLICE + i * 8192 + dma_lane0);
+            issued += 4;
         }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            ga_dma16(sb, (unsigned)min(w_col0 + r + i * 64, p.N - 1) * (unsigned)p.ldb + ck,
+                     ring_lds + S * GA_WSTAGE + i * 8192 + dma_lane0);
+        issued += 2;
         mark[S] = issued;
     };
     auto issue_consts = [&](int col0, int cb) __attribute__((always_inline)) {
@@ -741,13 +709,6 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
 
     const double cm = p.dy_main.m * p.dy_main.r, cr = p.dy_res.m * p.dy_res.r;
     const float rcpT = 1.0f / (float)(p.T > 0 ? p.T : 1);
-    int tr_unit = -2;     // trace: index of the current unit relative to the first traced one
-    auto trace = [&](int kt, int pt) __attribute__((always_inline)) {
-        if (G3_TRACE && bid == 0 && lane == 0 && tr_unit >= 0 && tr_unit < 3) {
-            unsigned long long *tb = reinterpret_cast<unsigned long long *>(smem + GA_SMEM);
-            tb[(wave * 3 + tr_unit) * 24 + kt * 8 + pt] = __builtin_readcyclecounter();
-        }
-    };
     v4i resv[8];          // residual pieces in flight / waiting for their sub-tile's epilogue: [(j*2 + i)*2 + piece]
     (void)resv;
     typedef double v2d __attribute__((ext_vector_type(2)));
@@ -818,7 +779,6 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
             ga_swap32(dpk[0], dpk[2]);
             ga_swap32(dpk[1], dpk[3]);
             const v4i v = {dpk[0], dpk[2], dpk[1], dpk[3]};
-            if (G3_DBG & 8) return;
             typedef unsigned v4u __attribute__((ext_vector_type(4)));
             if constexpr (EPI == EPI_RQ8_CH) {
                 const unsigned off = ok ? (unsigned)grow * (unsigned)p.ldc + (unsigned)gcol : GA_OOB;
@@ -960,7 +920,6 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
         auto section = [&](auto pp_t, auto q_t) __attribute__((always_inline)) {
             constexpr int PP = decltype(pp_t)::value, Q = decltype(q_t)::value, G = PP * 4 + Q;
             constexpr int KTN = Q == 3 ? (PP + 1) % GA_NK : PP, QN = (Q + 1) & 3;
-            if (G3_TRACE && HAS_CUR) { if (G == 0) ++tr_unit; trace(PP, Q); }
             if (HAS_CUR) {
                 // Refill of ring slot SL (free once everybody passed step SL's barrier with its reads done) with slice SL
                 // of the next round / unit.  The waves take turns: wave w requests its pieces in section dma_q of the
@@ -990,7 +949,7 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
             __builtin_amdgcn_sched_barrier(0);
             auto slot = [&](auto m_t) __attribute__((always_inline)) {
                 constexpr int m = decltype(m_t)::value;
-                if (HAS_CUR && !(G3_DBG & 2))
+                if (HAS_CUR)
                     accC[m & 1][m >> 1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fb[G & 1][m >> 1], fa[G & 1][m & 1], accC[m & 1][m >> 1], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (m == 0) {
@@ -1003,18 +962,8 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
                     }
                 }
                 if constexpr (HAS_PREV) {
-                    if (!(G3_DBG & 4)) {
-                        if constexpr (OUT8) chunk8(std::integral_constant<int, G * 4 + m>{});
-                        else chunk16(std::integral_constant<int, G * 4 + m>{});
-                    } else if constexpr ((G * 4 + m) % 12 == 11) {
-                        // ablation: no requant work, one raw store per sub-tile keeps the MFMAs alive
-                        constexpr int C = (G * 4 + m) / 12;
-                        typedef unsigned v4u __attribute__((ext_vector_type(4)));
-                        const v4u v = {(unsigned)accP[C & 1][C >> 1][0], (unsigned)accP[C & 1][C >> 1][5],
-                                       (unsigned)accP[C & 1][C >> 1][10], (unsigned)accP[C & 1][C >> 1][15]};
-                        __builtin_amdgcn_raw_buffer_store_b128(v, ga_rsrc(p.dummy), (unsigned)(tid_once() & 63) * 16, 0, 0);
-                        issued += 1;
-                    }
+                    if constexpr (OUT8) chunk8(std::integral_constant<int, G * 4 + m>{});
+                    else chunk16(std::integral_constant<int, G * 4 + m>{});
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
@@ -1036,14 +985,9 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
                 if (HAS_CUR) n = issued - mark[(PP + 1) % GA_NK];
                 if (HAS_CUR && PP == 2) n = min(n, issued - mark_cst);
                 if (RES && HAS_PREV && PP < (EH < 0 ? 2 : 1)) n = min(n, issued - mark_res[PP < 2 ? PP : 0]);
-                if (G3_TRACE && HAS_CUR) { __builtin_amdgcn_sched_barrier(0); trace(PP, 4); }
-                if (HAS_CUR || (RES && HAS_PREV && PP < (EH < 0 ? 2 : 1))) {
-                    if (G3_WAIT_TABLE) ga_wait_vm(n);
-                    else ga_wait_vm_fast<MULTI ? 8 : 4, MULTI ? 6 : 2>(n);
-                }
+                if (HAS_CUR || (RES && HAS_PREV && PP < (EH < 0 ? 2 : 1))) ga_wait_vm_fast<MULTI ? 8 : 4, MULTI ? 6 : 2>(n);
                 if constexpr (RES && HAS_PREV && PP < (EH < 0 ? 2 : 1))      // tie the residual registers to the wait
                     asm volatile("" : "+v"(resv[PP * 4]), "+v"(resv[PP * 4 + 1]), "+v"(resv[PP * 4 + 2]), "+v"(resv[PP * 4 + 3]));
-                if (G3_TRACE && HAS_CUR) trace(PP, 5);
                 if (HAS_CUR) __builtin_amdgcn_s_barrier();
             }
             asm volatile("" ::: "memory");
@@ -1132,10 +1076,4 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
     }
 #undef GA_UNIT
 #undef GA_DRAIN
-    if (G3_TRACE && bid == 0) {
-        __syncthreads();
-        unsigned long long *dst = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(p.dummy) + 1024);
-        const unsigned long long *tb = reinterpret_cast<const unsigned long long *>(smem + GA_SMEM);
-        for (int k = tid; k < GA_TRACE_BYTES / 8; k += 512) dst[k] = tb[k];
-    }
 }

@@ -17,7 +17,7 @@
 //     behind a store (loads and stores retire through one in-order counter on this chip: a wait for a load is a wait for every
 //     store in front of it).
 //
-// Measured stand-alone at DeiT-S b256 (tools/gemm_ws_probe.py): profiles/README.md, round 6.
+// Measured stand-alone at DeiT-S b256: profiles/README.md, round 6.
 #pragma once
 #include "ivit_layernorm.h"
 #include <type_traits>
@@ -35,9 +35,6 @@
 #define WS_SMEM (WS_SLN + WS_K * 20)
 #define WS_THREADS 512
 #define WS_MAGIC 6755399441055744.0
-#ifndef WS_TRACE
-#define WS_TRACE 0                               // probe builds: cycle stamps of workgroup WS_TRACE - 1 ([8 waves][64])
-#endif
 
 struct WsArgs {
     const int8_t *x;          // [M][384] 8-bit activations (LN = false)
@@ -58,7 +55,6 @@ struct WsArgs {
     int16_t *out16;
     double cm, cr;
     int8_t *ln_out8;          // EPI_RES16 with LN = true: norm2 + qact3 of out16's rows (ln_s .. ln_dy are norm2's), [M][384]
-    long long *trace;
 };
 #define WS_EPI_QKV8 0
 #define WS_EPI_RES16 1
@@ -91,14 +87,6 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63, tok = lane & 31, kh = lane >> 5, e = kh ^ ws_g(tok);
-    int n_stamp = 0;
-    auto stamp = [&]() __attribute__((always_inline)) {
-        if (WS_TRACE) {
-            if (blockIdx.x == WS_TRACE - 1 && (threadIdx.x & 63) == 0 && n_stamp < 64) p.trace[wave * 64 + n_stamp] = __builtin_readcyclecounter();
-            ++n_stamp;
-        }
-    };
-    stamp();
 
     const int ntt = (p.M + 31) >> 5;
     const int t_beg = (int)((long long)ntt * blockIdx.x / gridDim.x), t_end = (int)((long long)ntt * (blockIdx.x + 1) / gridDim.x);
@@ -138,7 +126,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                     for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)t[c], p.ln_s, ys);
                 }
                 const unsigned rowa = sm_lds + tokl * 64 + (k & 1) * 8 + 4 * hh, gk = (unsigned)((k >> 1) ^ ws_g(tokl));
-                G::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, p.ln_bias_int, p.ln_sc, p.ln_dy,
+                G::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY,
                        [&](int i, unsigned pk0, unsigned) __attribute__((always_inline)) {
                            *(lds_u32 *)(size_t)(rowa + (i >> 1) * WS_KBLK + ((gk ^ ((i & 1) * 2)) << 4)) = pk0;
                        });
@@ -166,7 +154,6 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
         const int na = (n_own + 1) >> 1, ntask = n_own > 1 ? 2 * ncp : ncp;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        stamp();
 
         const unsigned fa0 = sm_lds + tok * 64 + e * 16, fa1 = sm_lds + tok * 64 + (e ^ 2) * 16;
         for (int task = wave; task < ntask; task += 8) {
@@ -190,7 +177,6 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                 v4i bf[2][NT];
                 v16i acc[2][NT];
                 const unsigned fb0 = fa0 + tb * 2048, fb1 = fa1 + tb * 2048;
-                stamp();
                 int toff[NT];
 #pragma unroll
                 for (int t = 0; t < NT; ++t) toff[t] = *(lds_i32 *)(size_t)(sm_lds + WS_SOFF + ((tb + t) * 32 + tok) * 4);
@@ -233,7 +219,6 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                         for (int t = 0; t < NT; ++t)
                             acc[c][t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(W[c][ks], bf[ks & 1][t], acc[c][t], 0, 0, 0);
                 }
-                stamp();
                 // requant to 8 bits: fma(z, c, magic + 128) leaves Q + 128 in the low dword; the two packs saturate to [0, 255]
                 // = clamp(Q, -128, 127) + 128; the xor takes the bias off again.  One (channel tile, token tile) at a time:
                 // sixteen channels of a token per lane, one 16-byte store
@@ -330,9 +315,8 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)t[c], p.ln_s, ys);
                 }
-                G::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, p.ln_bias_int, p.ln_sc, p.ln_dy, p.ln_out8 + row * WS_K + 8 * k + 4 * hh);
+                G::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, p.ln_out8 + row * WS_K + 8 * k + 4 * hh);
             }
         }
-        stamp();
     }
 }

@@ -110,28 +110,6 @@ int ivit_set_cu_share(ivit_handle h, int cus) {
 
 const char *ivit_last_error(ivit_handle h) { return h ? h->err : "null handle"; }
 
-// tuning / ablation switches are read once per process (thread-safe static initialisation at the call site)
-// Experiment switches of the dispatch are COMPILE-TIME options (build a scratch library with -DIVIT_OPT_...=n and point
-// IVIT_LIB at it): a stray environment variable must not change which kernel a user of the library gets.
-#ifndef IVIT_OPT_GEMM3
-#define IVIT_OPT_GEMM3 7                // epilogues on the persistent pipelined kernels: 1 requant, 2 qkv scatter, 4 requant + residual
-#endif
-#ifndef IVIT_OPT_GEMM3_RES_MIN_N
-#define IVIT_OPT_GEMM3_RES_MIN_N 512    // residual flavour on the persistent kernel from this output width on
-#endif
-#ifndef IVIT_OPT_GEMM3_FMA
-#define IVIT_OPT_GEMM3_FMA (-1)         // -1: as the plan proves; 0 / 1: force the two-rounding / single-FMA requant (1 only where proven)
-#endif
-#ifndef G2_DBG
-#define G2_DBG 0
-#endif
-#ifndef IVIT_OPT_GEMM_BM
-#define IVIT_OPT_GEMM_BM 0              // 0: tile height by the occupancy estimate; 128 / 256: forced
-#endif
-#ifndef IVIT_OPT_ATTN_GENERIC
-#define IVIT_OPT_ATTN_GENERIC 0         // 1: run-time token count; 2: arithmetic Shiftmax even when tables are given
-#endif
-
 static inline int grid_for(ivit_handle h, long long work_items, int per_block) {
     long long g = (work_items + per_block - 1) / per_block;
     long long cap = (long long)h->num_cu * 16;
@@ -198,15 +176,12 @@ static int launch_gemm(ivit_handle h, GemmArgs &a, int nb) {
 template <int EPI>
 static int launch_gemm2(ivit_handle h, GemmArgs &a) {
     a.tiles_n = (a.N + G2_BN - 1) / G2_BN;
-    constexpr int force_bm = IVIT_OPT_GEMM_BM;
-    a.dbg = G2_DBG;                      // 0; timing probes: 1 main loop only, 2 no row stores, 3 no requant arithmetic
     // tile height: estimated time ~ ceil(tiles / resident slots) * rows per tile; 256-row tiles run
     // 2 per CU, 128-row tiles 3 per CU.  Ties go to the larger tile (better operand reuse).
     const long long t256 = (long long)((a.M + 255) / 256) * a.tiles_n, t128 = (long long)((a.M + 127) / 128) * a.tiles_n;
     const long long s256 = 2LL * h->num_cu, s128 = (G2_NSTAGE128 == 2 ? 4LL : 3LL) * h->num_cu;
     const long long c256 = ((t256 + s256 - 1) / s256) * 256, c128 = ((t128 + s128 - 1) / s128) * 128;
-    const bool use128 = force_bm ? (force_bm == 128) : (c128 < c256);
-    if (use128) gemm_glds_kernel<EPI, 128><<<dim3((unsigned)t128), 256, 0, h->stream>>>(a);
+    if (c128 < c256) gemm_glds_kernel<EPI, 128><<<dim3((unsigned)t128), 256, 0, h->stream>>>(a);
     else gemm_glds_kernel<EPI, 256><<<dim3((unsigned)t256), 512, 0, h->stream>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -219,11 +194,8 @@ static inline bool use_gemm2(const GemmArgs &a) { return (a.K % 32) == 0 && a.K 
 
 // short-K streaming kernel (ivit_gemm_wreg.h): K = 96 / 128 / 192 with whole 32-channel tiles in groups of 3 or 2, plain row-major
 // operands, enough rows to keep every CU busy
-#ifndef IVIT_OPT_GEMM_WREG
-#define IVIT_OPT_GEMM_WREG 1
-#endif
 static inline int wreg_nct(const GemmArgs &a) {
-    if (!IVIT_OPT_GEMM_WREG || a.K % 32 || !(a.K == 96 || a.K == 128 || a.K == 192) || a.N % 32 || a.lda != a.K || a.ldb != a.K ||
+    if (a.K % 32 || !(a.K == 96 || a.K == 128 || a.K == 192) || a.N % 32 || a.lda != a.K || a.ldb != a.K ||
         a.ldc != a.N || a.M < 8192 || a.inner != 1)
         return 0;
     const int nt = a.N / 32;
@@ -554,14 +526,6 @@ int ivit_linear_plan_destroy(ivit_linear_plan p) {
     return IVIT_OK;
 }
 
-int ivit_debug_plan_scratch(ivit_linear_plan p, void *host_dst, int nbytes) {
-    if (!p || !host_dst || nbytes <= 0 || nbytes > 8192) return IVIT_ERR_INVALID;
-    ivit_device_guard g;
-    if (!g.enter(p->device)) return IVIT_ERR_HIP;
-    if (hipDeviceSynchronize() != hipSuccess) return IVIT_ERR_HIP;
-    return hipMemcpy(host_dst, (char *)p->dummy + 1024, (size_t)nbytes, hipMemcpyDeviceToHost) == hipSuccess ? IVIT_OK : IVIT_ERR_HIP;
-}
-
 int ivit_linear_plan_query(ivit_linear_plan p, int *pipelined_ok, int *single_fma_ok) {
     if (!p) return IVIT_ERR_INVALID;
     if (pipelined_ok) *pipelined_ok = p->pipelined_ok;
@@ -571,23 +535,18 @@ int ivit_linear_plan_query(ivit_linear_plan p, int *pipelined_ok, int *single_fm
 
 }  // extern "C"
 
-// persistent pipelined kernel: shapes it is built for (anything else runs on gemm_glds_kernel / gemm_nt_kernel)
-// IVIT_GEMM3: bit mask of the epilogues that run on the persistent pipelined kernels — 1 requant (8/16-bit), 2 qkv
-// scatter, 4 requant + residual; the others stay on the launch-per-tile kernels (A/B and fallback).
+// persistent pipelined kernel: shapes it is built for (anything else runs on gemm_glds_kernel / gemm_nt_kernel).
+// epi_bit: the epilogue asking — 1 requant (8/16-bit), 2 qkv scatter, 4 requant + residual
 static inline bool use_gemm3(const ivit_linear_plan_s *pl, const GemmArgs &a, int epi_bit) {
-    constexpr int on = IVIT_OPT_GEMM3;
     // the residual flavour on a narrow output (N = 384: three channel tiles per 256-token panel, 77 % balance, and its
     // 32 resident residual registers) measured no better in-model than the launch-per-tile kernel: N >= 512 only
-    constexpr int res_min_n = IVIT_OPT_GEMM3_RES_MIN_N;
+    constexpr int res_min_n = 512;      // residual flavour on the persistent kernel from this output width on
     if (epi_bit == 4 && a.N < res_min_n) return false;
-    return (on & epi_bit) && pl->pipelined_ok && (a.K % 64) == 0 && a.K >= 320 && (a.N % 16) == 0 && (a.ldc % 16) == 0 &&
+    return pl->pipelined_ok && (a.K % 64) == 0 && a.K >= 320 && (a.N % 16) == 0 && (a.ldc % 16) == 0 &&
            (a.lda % 16) == 0 && (a.ldb % 16) == 0 && a.M >= 128;
 }
 
 // ---- D = 384 qkv on the register-resident-weights kernel (ivit_gemm_ws.h), with or without norm1 in its prologue
-#ifndef IVIT_OPT_QKV_WS
-#define IVIT_OPT_QKV_WS 1               // A/B: ivit_linear_i8_qkv_planned(ldv = 0) on gemm_ws_qkv_kernel where the plan is prepared
-#endif
 static inline bool qkv_ws_ok(const ivit_linear_plan_s *pl, int B, int T, int H, int dh) {
     return pl->wf && dh == 64 && pl->K == WS_K && pl->N == 3 * H * dh && pl->N % 192 == 0 && (long long)B * H * T * 64 < (1ll << 31) && (long long)B * T < (1ll << 26);
 }
@@ -598,7 +557,7 @@ static int launch_qkv_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8
     WsArgs a;
     a.x = x8; a.wf = pl->wf; a.bias = pl->bias_eff; a.cq = pl->cq; a.q = q; a.k = k; a.v = v;
     a.M = B * T; a.N = pl->N; a.T = T; a.H = H; a.dummy = pl->dummy;
-    a.x16 = x16; a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy; a.trace = nullptr;
+    a.x16 = x16; a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy;
     a.residual = nullptr; a.out16 = nullptr; a.cm = a.cr = 0.0; a.ln_out8 = nullptr;
     static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
     const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
@@ -639,9 +598,6 @@ static int launch_qkv_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8
     return IVIT_OK;
 }
 
-#ifndef IVIT_OPT_RES_WS
-#define IVIT_OPT_RES_WS 1               // A/B: ivit_linear_i8_requant_residual_planned on gemm_ws_qkv_kernel<.., EPI_RES16> where the plan is prepared
-#endif
 static int launch_res_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, double cm, double cr, const int16_t *residual,
                          int16_t *out, int M, float ln_s = 0.f, const float *ln_bias_int = nullptr, const float *ln_sc = nullptr,
                          const ivit_dyadic *ln_dy = nullptr, int8_t *ln_out8 = nullptr) {
@@ -649,7 +605,7 @@ static int launch_res_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8
     WsArgs a;
     a.x = x8; a.wf = pl->wf; a.bias = pl->bias_eff; a.cq = pl->cq; a.q = a.k = a.v = nullptr;
     a.M = M; a.N = pl->N; a.T = 1; a.H = 1; a.dummy = pl->dummy;
-    a.x16 = nullptr; a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy; a.trace = nullptr;
+    a.x16 = nullptr; a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy;
     a.residual = residual; a.out16 = out; a.cm = cm; a.cr = cr; a.ln_out8 = ln_out8;
     static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
     const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
@@ -679,16 +635,14 @@ static int launch_gemm3(ivit_handle h, const ivit_linear_plan_s *pl, GemmArgs &a
     a.cq = pl->cq;
     a.bias = pl->bias_eff;
     a.dummy = pl->dummy;
-    constexpr int force_fma = IVIT_OPT_GEMM3_FMA, wg_per_cu = 2;
-    constexpr bool astat_on = true;
-    a.dbg = 0;
-    const bool fma = force_fma >= 0 ? (force_fma != 0 && pl->single_fma_ok) : (pl->single_fma_ok != 0);
+    constexpr int wg_per_cu = 2;
+    const bool fma = pl->single_fma_ok != 0;
     // gemm_as_kernel: K = n * 384; the qkv scatter additionally needs whole units inside one of q / k / v and whole
     // 32-channel groups inside one head.  Its operand offsets are 32-bit and its epilogue goes through buffer
     // resources (offsets < 2^31, out-of-range lanes parked at 0x80000000): larger tensors take the 64-bit kernels.
     const long long out_bytes = (EPI == EPI_QKV) ? std::max((long long)a.M * a.D, (long long)(a.M / (a.T > 0 ? a.T : 1) + 1) * a.D * a.ldv)
                                                  : (long long)a.M * a.ldc * ((EPI == EPI_RQ8_CH) ? 1 : 2);
-    const bool astat = astat_on && (a.K % (GA_BK * GA_NK)) == 0 && a.M >= 256 && (a.N % 32) == 0 &&
+    const bool astat = (a.K % (GA_BK * GA_NK)) == 0 && a.M >= 256 && (a.N % 32) == 0 &&
                        (long long)a.M * a.lda < (1LL << 32) && (long long)a.N * a.ldb < (1LL << 32) &&
                        out_bytes < (1LL << 31) &&
                        (EPI != EPI_QKV || ((a.D % 128) == 0 && (a.dh % 32) == 0));
@@ -727,7 +681,7 @@ int ivit_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan pl, const int
     REQUIRE(h, bits == 8 || bits == 16, "bits must be 8 or 16");
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy;
-    if (IVIT_OPT_QKV_WS && bits == 8 && pl->wf && pl->K == WS_K && M < (1 << 26))      // prepared plan: tokens of a CU in LDS, weight slabs in registers
+    if (bits == 8 && pl->wf && pl->K == WS_K && M < (1 << 26))      // prepared plan: tokens of a CU in LDS, weight slabs in registers
         return launch_qkv_ws(h, pl, x, nullptr, 0.f, nullptr, nullptr, nullptr, (int8_t *)out, nullptr, nullptr, M, 1, 0);
     if (use_gemm3(pl, a, 1)) return bits == 8 ? launch_gemm3<EPI_RQ8_CH>(h, pl, a) : launch_gemm3<EPI_RQ16_CH>(h, pl, a);
     return ivit_linear_i8_requant(h, x, pl->w, pl->bias, pl->dy, bits, out, M, pl->N, pl->K);
@@ -751,7 +705,7 @@ int ivit_linear_i8_requant_residual_planned(ivit_handle h, ivit_linear_plan pl, 
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy; a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual;
     const bool res_fast = fabs(dy_main.m * dy_main.r) < RQ_FAST_CLIM && fabs(dy_res.m * dy_res.r) < RQ_FAST_CLIM;
-    if (IVIT_OPT_RES_WS && pl->wf && res_fast && pl->K == WS_K && M < (1 << 26))
+    if (pl->wf && res_fast && pl->K == WS_K && M < (1 << 26))
         return launch_res_ws(h, pl, x, dy_main.m * dy_main.r, dy_res.m * dy_res.r, residual, out, M);
     if (use_gemm3(pl, a, 4) && res_fast) return launch_gemm3<EPI_RQ16_CH_RES>(h, pl, a);
     return ivit_linear_i8_requant_residual(h, x, pl->w, pl->bias, pl->dy, dy_main, dy_res, residual, out, M, pl->N, pl->K);
@@ -782,7 +736,7 @@ int ivit_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, const int8_t 
     GemmArgs a = linear_args(x, pl->w, pl->bias, B * T, 3 * D, D);
     a.dy_ch = pl->dy; a.q = q; a.k = k; a.vt = vt;
     a.T = T; a.H = H; a.dh = dh; a.ldv = ldv; a.D = D;
-    if (IVIT_OPT_QKV_WS && ldv == 0 && qkv_ws_ok(pl, B, T, H, dh)) return launch_qkv_ws(h, pl, x, nullptr, 0.f, nullptr, nullptr, nullptr, q, k, vt, B, T, H);
+    if (ldv == 0 && qkv_ws_ok(pl, B, T, H, dh)) return launch_qkv_ws(h, pl, x, nullptr, 0.f, nullptr, nullptr, nullptr, q, k, vt, B, T, H);
     if (use_gemm3(pl, a, 2) && (long long)B * T < (1 << 23)) return launch_gemm3<EPI_QKV>(h, pl, a);
     return ivit_linear_i8_qkv(h, x, pl->w, pl->bias, pl->dy, q, k, vt, B, T, H, dh, ldv);
 }
@@ -822,16 +776,7 @@ int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, con
 
 }  // extern "C"
 
-#ifndef IVIT_OPT_SWIN_MLP_RS
-#define IVIT_OPT_SWIN_MLP_RS 1          // A/B builds: 0 = the narrow-stage fused Mlp always on the phase-by-phase kernel
-#endif
 // ---- fused Mlp (+ residual QuantAct) for D = 384, hidden = 1536 (ivit_mlp.h)
-#ifndef IVIT_OPT_MLP_RS
-#define IVIT_OPT_MLP_RS 1               // A/B builds: 0 = the shape-based default never picks the role-split kernel
-#endif
-#ifndef IVIT_OPT_MLP_LNH
-#define IVIT_OPT_MLP_LNH 1               // ivit_layernorm_mlp_fused_planned: 1 = the LayerNorm of every row first, 2 = the first unit's rows first, the rest
-#endif                                   // by the consumer waves beside the producers' first fc1 (bit-exact, 2.69 against 2.65 ms per forward: not the default)
 struct ivit_mlp_plan_s {
     ivit_linear_plan fc1, fc2;      // borrowed: must outlive this plan
     v4i *w1f, *w2f;                 // fragment-ordered copies of the two weight matrices (one allocation)
@@ -876,7 +821,7 @@ int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan f
     {   // the dynamic-LDS attributes of the kernels this plan will launch: once, here
         const void *fn = p->fma ? (const void *)mlp384_kernel<true> : (const void *)mlp384_kernel<false>;
         const void *fr = p->fma ? (const void *)mlp384rs_kernel<true> : (const void *)mlp384rs_kernel<false>;
-        const void *fl = p->fma ? (const void *)mlp384rs_kernel<true, IVIT_OPT_MLP_LNH> : (const void *)mlp384rs_kernel<false, IVIT_OPT_MLP_LNH>;
+        const void *fl = p->fma ? (const void *)mlp384rs_kernel<true, 1> : (const void *)mlp384rs_kernel<false, 1>;
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_SMEM);
         if (e == hipSuccess) e = hipFuncSetAttribute(fr, hipFuncAttributeMaxDynamicSharedMemorySize, RS_SMEM);
         if (e == hipSuccess) e = hipFuncSetAttribute(fl, hipFuncAttributeMaxDynamicSharedMemorySize, RS_SMEM);
@@ -913,7 +858,7 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
     a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy;
     a.x = x; a.w1f = p->w1f; a.w2f = p->w2f; a.b1 = p->fc1->bias_eff; a.b2 = p->fc2->bias_eff;
     a.cq1 = p->fc1->cq; a.cq2 = p->fc2->cq; a.tab = gelu_table; a.residual = residual; a.out = out;
-    a.cm = dy_main.m * dy_main.r; a.cr = dy_res.m * dy_res.r; a.M = M; a.trace = nullptr;
+    a.cm = dy_main.m * dy_main.r; a.cr = dy_res.m * dy_res.r; a.M = M;
     if (!(fabs(a.cm) < RQ_FAST_CLIM && fabs(a.cr) < RQ_FAST_CLIM)) {
         snprintf(h->err, sizeof(h->err), "%s: residual multipliers out of the fast range", __func__);
         return IVIT_ERR_UNSUPPORTED;
@@ -928,7 +873,7 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
     // two kernels, the same integers.  The role-split one (producer waves on fc1 of unit u + 1 beside consumer waves on
     // ShiftGELU / fc2 / epilogue of unit u) needs a second unit per workgroup to overlap anything: with one unit per CU it only
     // ties with the lock-step kernel (45.0 vs 44.6 us at M = 20480), from two units on it wins (profiles/README.md, round 5)
-    const bool role_split = p->kernel == 2 || (p->kernel == 0 && IVIT_OPT_MLP_RS && nunits > (long long)grid);
+    const bool role_split = p->kernel == 2 || (p->kernel == 0 && nunits > (long long)grid);
     if (ln_dy && !role_split) {
         snprintf(h->err, sizeof(h->err), "%s: the LayerNorm prologue exists in the role-split kernel only (two units per CU or more)", __func__);
         return IVIT_ERR_UNSUPPORTED;
@@ -936,8 +881,8 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
     if (role_split) {
         a.w1f = p->w1r; a.w2f = p->w2r;
         if (ln_dy) {
-            if (p->fma) mlp384rs_kernel<true, IVIT_OPT_MLP_LNH><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
-            else mlp384rs_kernel<false, IVIT_OPT_MLP_LNH><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
+            if (p->fma) mlp384rs_kernel<true, 1><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
+            else mlp384rs_kernel<false, 1><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
         } else if (p->fma) mlp384rs_kernel<true><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
         else mlp384rs_kernel<false><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
     } else if (p->fma) mlp384_kernel<true><<<grid, MLP_THREADS, MLP_SMEM, h->stream>>>(a);
@@ -989,19 +934,18 @@ template <int NB>
 static int launch_attn(ivit_handle h, const AttnArgs &a, int BH) {
     const double cq = a.dy_qk.m * a.dy_qk.r, cp = a.dy_pv.m * a.dy_pv.r;
     const bool fast = (cq < 512.0 && cq > -512.0 && cp < 512.0 && cp > -512.0);
-    constexpr bool dyn_t = (IVIT_OPT_ATTN_GENERIC & 1) != 0, no_lut = (IVIT_OPT_ATTN_GENERIC & 2) != 0;
-    const bool lut = a.aq && a.et && a.cls && !no_lut;
+    const bool lut = a.aq && a.et && a.cls;
     if (a.rowtab) {     // row-line tables (ivit_attention_fused_rowlut): the multipliers were checked by the caller
         if (a.ldv == 0) {   // v row-major
-            if (NB == 4 && a.T == 197 && !dyn_t) return launch_attn2<NB, true, 197, 2, true>(h, a, BH);
-            if (NB == 10 && a.T == 577 && !dyn_t) return launch_attn2<NB, true, 577, 2, true>(h, a, BH);
+            if (NB == 4 && a.T == 197) return launch_attn2<NB, true, 197, 2, true>(h, a, BH);
+            if (NB == 10 && a.T == 577) return launch_attn2<NB, true, 577, 2, true>(h, a, BH);
             return launch_attn2<NB, true, 0, 2, true>(h, a, BH);
         }
-        if (NB == 4 && a.T == 197 && !dyn_t) return launch_attn2<NB, true, 197, 2>(h, a, BH);
-        if (NB == 10 && a.T == 577 && !dyn_t) return launch_attn2<NB, true, 577, 2>(h, a, BH);
+        if (NB == 4 && a.T == 197) return launch_attn2<NB, true, 197, 2>(h, a, BH);
+        if (NB == 10 && a.T == 577) return launch_attn2<NB, true, 577, 2>(h, a, BH);
         return launch_attn2<NB, true, 0, 2>(h, a, BH);
     }
-    if (fast && !dyn_t) {
+    if (fast) {
         if (NB == 4 && a.T == 197) return lut ? launch_attn2<NB, true, 197, true>(h, a, BH) : launch_attn2<NB, true, 197>(h, a, BH);
         if (NB == 10 && a.T == 577) return lut ? launch_attn2<NB, true, 577, true>(h, a, BH) : launch_attn2<NB, true, 577>(h, a, BH);
     }
@@ -1245,17 +1189,10 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
         } while (0)
         switch (C) {
             // lanes per row = 4 S (measured on DeiT-S b256: S = 1 23.2 us, S = 2 20.1, S = 4 20.2 — shorter per-wave instruction
-            // chains and more waves per SIMD beat the cheaper quad-only reduction).  S = 1 exists in probe builds only
-            // (ivit_layernorm.h has its history)
+            // chains and more waves per SIMD beat the cheaper quad-only reduction).  ivit_layernorm.h has the history of S = 1
             case 96: LNR_LAUNCH(96, 2);        // Swin-T/S stage 0 (token-order sums use their own kernel)
             case 128: LNR_LAUNCH(128, 2);      // Swin-B stage 0
-#if IVIT_PROBE_LN192_S1 == 2
-            case 192: break;                   // probe: C = 192 on layernorm16_kernel, the round-2 LayerNorm
-#elif IVIT_PROBE_LN192_S1
-            case 192: LNR_LAUNCH(192, 1);      // probe builds only (tools/ln_s1_probe.sh)
-#else
             case 192: LNR_LAUNCH(192, 2);      // DeiT-T, Swin stage 1
-#endif
             case 256: LNR_LAUNCH(256, 2);
             case 384: LNR_LAUNCH(384, 2);      // DeiT-S, Swin stage 2, PatchMerging
             case 512: LNR_LAUNCH(512, 4);
@@ -1475,9 +1412,6 @@ int ivit_embed_finish(ivit_handle h, const int16_t *patch16, const int32_t *z_cl
     return IVIT_OK;
 }
 
-#ifndef IVIT_OPT_PATCH_EMBED
-#define IVIT_OPT_PATCH_EMBED 1          // A/B: 0 = ivit_patch_embed always answers IVIT_ERR_UNSUPPORTED (im2col + GEMM + embed_finish launches)
-#endif
 int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int C, int H, int W, int P, const int8_t *w, const int32_t *bias,
                      const ivit_dyadic *dy_ch, const int32_t *z_cls, const int16_t *pos, ivit_dyadic dy_x, ivit_dyadic dy_pos,
                      int16_t *x16, int D) {
@@ -1486,7 +1420,7 @@ int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int C, int H, i
     const int gh = H / P, gw = W / P, np = gh * gw, K = C * P * P, T = np + 1;
     const bool fast = fabs(dy_x.m * dy_x.r) < RQ_FAST_CLIM && fabs(dy_pos.m * dy_pos.r) < RQ_FAST_CLIM;
     GemmArgs a = linear_args(images, w, bias, B * np, D, K);
-    if (!IVIT_OPT_PATCH_EMBED || P != 16 || H % 16 || W % 16 || (D % 8) != 0 || (K % 64) != 0 || !fast || !use_gemm2(a) || (long long)B * np >= (1ll << 30) ||
+    if (P != 16 || H % 16 || W % 16 || (D % 8) != 0 || (K % 64) != 0 || !fast || !use_gemm2(a) || (long long)B * np >= (1ll << 30) ||
         (long long)T * D / 8 >= (1 << 22) || B > 65535) {
         snprintf(h->err, sizeof(h->err), "%s: built for 16 x 16 patches, K %% 64 == 0, both multipliers in the fast range", __func__);
         return IVIT_ERR_UNSUPPORTED;
@@ -1498,7 +1432,6 @@ int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int C, int H, i
     a.out = x16; a.dy_ch = dy_ch; a.dy_main = dy_x; a.dy_res = dy_pos; a.residual = pos;
     a.img = images; a.img_C = C; a.img_H = H; a.img_W = W; a.pe_gw = gw; a.pe_P = np;
     a.tiles_n = (a.N + G2_BN - 1) / G2_BN;
-    a.dbg = 0;
     const long long t128 = (long long)((a.M + 127) / 128) * a.tiles_n;
     gemm_glds_kernel<EPI_RQ16_CH_RES, 128, true><<<dim3((unsigned)t128), 256, 0, h->stream>>>(a);
     LAUNCH_CHECK(h);
@@ -1632,7 +1565,7 @@ int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32
     const unsigned grid = (unsigned)(ntiles < h->num_cu ? ntiles : h->num_cu);
     // role-split form (ivit_swin_mlp_rs.h: producers on fc1 of tile i + 1 beside consumers on ShiftGELU / fc2 of tile i) when a
     // workgroup has at least two tiles to overlap; the phase-by-phase kernel otherwise
-    if (IVIT_OPT_SWIN_MLP_RS && ntiles >= 2 * (long long)grid) swin_mlp_rs_kernel<<<grid, SR_THREADS, SR_SMEM, h->stream>>>(a);
+    if (ntiles >= 2 * (long long)grid) swin_mlp_rs_kernel<<<grid, SR_THREADS, SR_SMEM, h->stream>>>(a);
     else swin_mlp_fused_kernel<<<grid, MF_THREADS, MF_SMEM, h->stream>>>(a);
     LAUNCH_CHECK(h);
     return IVIT_OK;

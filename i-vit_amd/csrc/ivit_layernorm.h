@@ -44,36 +44,19 @@ __device__ __forceinline__ float ln_dpp(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
 
-// S = 1 (4 lanes per row, quad_perm broadcasts) is NOT dispatched (S = 2 is the faster form) and does not compile outside the
-// probe build (-DIVIT_PROBE_LN192_S1=1, tools/ln_s1_probe.sh, tools/ubench/ln_s1_standalone.hip).  History: it returned one-LSB
+// S = 1 (4 lanes per row, quad_perm broadcasts) is not built: S = 2 is the faster form.  History: it returned one-LSB
 // differences in rows 12..15 of a wave in 1-4 % of the launches that shared a SIMD with MFMA-issuing waves.  Round 5 reduced that
 // to one instruction form hipcc used in its running sums — v_pk_add_f32 ... op_sel:[0,1] op_sel_hi:[1,0], whose low lane takes
 // src1's HIGH dword: beside MFMAs that dword is occasionally read as 0 on lanes 48..63 (profiles/r05_hazard/README.md,
 // tools/ubench/pk_opsel_hazard.hip).  The library is built with -packed-fp32-ops off (i-vit_amd/_lib.py), which removes the form
 // here, in the S = 4 kernels and in the token-order kernels whose ISA had packed fp32.
 // 32 rows per block whatever the split: the per-block staging of the channel constants (an fp64 division each) stays ~8 %
-#ifndef LNR_TB
 #define LNR_TB 128
-#endif
 #define LNR_THREADS(S) (LNR_TB * (S))
-// timing probes only (tools/ubench/ln_probe.hip): 1 = no output-pass arithmetic, 2 = no second sum, 4 = no Newton loop
-#ifndef LNR_ABLATE
-#define LNR_ABLATE 0
-#endif
-// probes of the S = 1 form only (tools/ln_s1_probe.sh): 1 = s_nop 7 around every DPP group, 2 = ds_bpermute instead of DPP,
-// 3 = per-channel constants straight from global memory instead of the LDS copy
-#ifndef LNR_S1_VARIANT
-#define LNR_S1_VARIANT 0
-#endif
-#ifndef IVIT_PROBE_LN192_S1
-#define IVIT_PROBE_LN192_S1 0
-#endif
 // register budget by values per lane (CC / 4S): <= 24 -> 8 waves per SIMD, <= 48 -> 5, <= 64 -> 4, more -> 3 (no scratch in any
 // instantiation the dispatcher uses)
 #define LNR_VPL(CC, S) ((CC) / (4 * (S)))
-#ifndef LNR_W48
 #define LNR_W48 5
-#endif
 #define LNR_MIN_WAVES(CC, S) (LNR_VPL(CC, S) <= 24 ? 8 : (LNR_VPL(CC, S) <= 48 ? LNR_W48 : (LNR_VPL(CC, S) <= 64 ? 4 : 3)))
 // Everything after the row is in registers as x = fl(fl(Q*s)/s): both torch-order sums, the integer Newton iteration, the
 // output pass with the per-channel constants of the block's LDS copy, the store.  Shared by the one-shot kernel and the
@@ -82,6 +65,7 @@ template <int CC, int S>
 struct LnGroup {
     static constexpr int LPR = 4 * S, EPC = 8 / S, NSTEP = CC / 32, RPW = 64 / LPR;
     static_assert(CC % 32 == 0 && NSTEP < 256, "whole 32-element steps, at most one cascade level above the first");
+    static_assert(S == 2 || S == 4, "8 or 16 lanes per row (the 4-lanes-per-row form is not built: see the note above)");
 
     // ((g0 + g1) + g2) + g3 over the accumulator groups, then vector lanes 0..7 in order; every lane of the row gets it.
     // Lane j = S k + h of a row: group k + 1 is S lanes up (DPP row shifts; a row's 4 S lanes never straddle a DPP row of
@@ -91,35 +75,10 @@ struct LnGroup {
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             const float a = NSTEP >= 16 ? a0[e] + a1[e] : a0[e];
-            if constexpr (S == 1) {
-#if LNR_S1_VARIANT == 2
-                // probe: the same four-lane exchange through the LDS crossbar (ds_bpermute) instead of DPP
-                const int l0 = (int)(threadIdx.x & 63) & ~3;
-                float t = __shfl(a, l0);
-                t += __shfl(a, l0 + 1);
-                t += __shfl(a, l0 + 2);
-                t += __shfl(a, l0 + 3);
-                p[e] = t;
-#else
-                float aa = a;
-#if LNR_S1_VARIANT == 1
-                asm volatile("s_nop 7" : "+v"(aa));        // probe: wait states between the producer of `a` and its DPP readers
-#endif
-                float t = ln_quad_bcast<0>(aa);
-                t += ln_quad_bcast<1>(aa);
-                t += ln_quad_bcast<2>(aa);
-                t += ln_quad_bcast<3>(aa);
-#if LNR_S1_VARIANT == 1
-                asm volatile("s_nop 7" : "+v"(t));
-#endif
-                p[e] = t;
-#endif
-            } else {
-                float t = a + ln_dpp<0x100 + S>(a);
-                t += ln_dpp<0x100 + 2 * S>(a);
-                t += ln_dpp<0x100 + 3 * S>(a);
-                p[e] = t;
-            }
+            float t = a + ln_dpp<0x100 + S>(a);
+            t += ln_dpp<0x100 + 2 * S>(a);
+            t += ln_dpp<0x100 + 3 * S>(a);
+            p[e] = t;
         }
         float fin = 0.f;
 #pragma unroll
@@ -158,8 +117,7 @@ struct LnGroup {
     template <typename DMA_SYNC = std::false_type, typename OP = int8_t *>
     static __device__ __forceinline__ void run(float (&xv)[NSTEP][EPC], int j, int k, int cb0, bool fastrq, bool live,
                                                const double *cC, const float *cB, const float *cSc, const float *cY,
-                                               const float *bias_int, const float *sc, const ivit_dyadic *dy, OP op,
-                                               DMA_SYNC = DMA_SYNC{}) {
+                                               OP op, DMA_SYNC = DMA_SYNC{}) {
         // ---- first sum
         float a0[EPC], a1[EPC];
 #pragma unroll
@@ -181,14 +139,14 @@ struct LnGroup {
             for (int e = 0; e < EPC; ++e) {
                 const float y = xv[i][e] - mean;
                 xv[i][e] = y;
-                if (!(LNR_ABLATE & 2)) a0[e] += y * y;
+                a0[e] += y * y;
             }
             cascade(i, a0, a1);
         }
         const float var = finish(a0, a1, j, k);
         // integer Newton iteration; k' == k is a fixed point of the remaining steps, so the early exit is exact
         float kk = 65536.0f;
-        for (int n = 0; n < ((LNR_ABLATE & 4) ? 0 : 10); ++n) {
+        for (int n = 0; n < 10; ++n) {
             const float kn = floorf((kk + floorf(var / kk)) * 0.5f);
             const bool same = (kn == kk);
             kk = kn;
@@ -211,13 +169,8 @@ struct LnGroup {
 #pragma unroll
             for (int e4 = 0; e4 < EPC; e4 += (EPC >= 4 ? 4 : 2)) {
                 if constexpr (EPC >= 4) {
-#if LNR_S1_VARIANT == 3
-                    v4f b4 = *reinterpret_cast<const v4f *>(bias_int + cb + e4), s4 = *reinterpret_cast<const v4f *>(sc + cb + e4), y4;
-                    for (int e = 0; e < 4; ++e) y4[e] = rcp_rn(s4[e]);
-#else
                     const v4f b4 = *reinterpret_cast<const v4f *>(cB + cb + e4), s4 = *reinterpret_cast<const v4f *>(cSc + cb + e4),
                               y4 = *reinterpret_cast<const v4f *>(cY + cb + e4);
-#endif
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { bi[e4 + e] = b4[e]; scv[e4 + e] = s4[e]; yv[e4 + e] = y4[e]; }
                 } else {
@@ -227,19 +180,14 @@ struct LnGroup {
 #pragma unroll
             for (int e = 0; e < EPC; e += 2) {
                 typedef double v2d __attribute__((ext_vector_type(2)));
-#if LNR_S1_VARIANT == 3
-                cv[e] = dy[cb + e].m * dy[cb + e].r; cv[e + 1] = dy[cb + e + 1].m * dy[cb + e + 1].r;
-#else
                 const v2d c2 = *reinterpret_cast<const v2d *>(cC + cb + e);
                 cv[e] = c2[0]; cv[e + 1] = c2[1];
-#endif
             }
             unsigned pk[2] = {0, 0};
             if constexpr (decltype(fast)::value) {
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) {
                     const float o = floorf(xv[i][e] * Fh) + bi[e];
-                    if (LNR_ABLATE & 1) { pk[e >> 2] |= ((unsigned)__float_as_int(o) & 0xffu) << (8 * (e & 3)); continue; }
                     const float zz = rintf(requotient_m(o, scv[e], yv[e]));
                     const int v = __double2loint((double)zz * cv[e] + (6755399441055744.0 + 128.0));
                     pk[e >> 2] |= (unsigned)min(max(v, 0), 255) << (8 * (e & 3));
@@ -308,9 +256,6 @@ __global__ __launch_bounds__(LNR_THREADS(S), LNR_MIN_WAVES(CC, S)) void layernor
                                                                      const float *__restrict__ sc,
                                                                      const ivit_dyadic *__restrict__ dy,
                                                                      int8_t *__restrict__ out, int merge_R = 0) {
-#if !IVIT_PROBE_LN192_S1
-    static_assert(S != 1, "the 4-lanes-per-row form is a probe (see the note above)");
-#endif
     typedef LnGroup<CC, S> G;
     constexpr int LPR = G::LPR, EPC = G::EPC, NSTEP = G::NSTEP, RPW = G::RPW, RPB = (LNR_THREADS(S) / 64) * RPW;
     __shared__ __attribute__((aligned(16))) double cC[CC];
@@ -343,7 +288,7 @@ __global__ __launch_bounds__(LNR_THREADS(S), LNR_MIN_WAVES(CC, S)) void layernor
 #pragma unroll
         for (int e = 0; e < EPC; ++e) xv[i][e] = requotient_m((float)t[e], s, ys);
     }
-    G::run(xv, j, k, 8 * k + EPC * hh, fastrq, live, cC, cB, cSc, cY, bias_int, sc, dy, out + row * CC + 8 * k + EPC * hh);
+    G::run(xv, j, k, 8 * k + EPC * hh, fastrq, live, cC, cB, cSc, cY, out + row * CC + 8 * k + EPC * hh);
 }
 
 // diagnostics: requotient_m against the IEEE sequence fl(fl(q*d)/d), element-wise

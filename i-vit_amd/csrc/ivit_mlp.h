@@ -28,9 +28,7 @@
 #define MLP_C 384
 #define MLP_HD 1536
 #define MLP_TT 5                               // token tiles (of 16) a unit may have: 4 or 5
-#ifndef MLP_WAVES
 #define MLP_WAVES 8
-#endif
 #define MLP_NJ (MLP_C / 16 / MLP_WAVES)        // channel tiles per wave and step: 2 (12 waves) or 3 (8 waves)
 //                         // three per SIMD: a lone wave issues a 16x16x64 MFMA every ~34 cycles, the pipe takes one per ~17
 #define MLP_THREADS (MLP_WAVES * 64)
@@ -42,25 +40,7 @@
 #define MLP_STAB (MLP_SA + MLP_KS1 * MLP_KBLK)    // one ShiftGELU table line (256 B) per half-wave
 #define MLP_SMEM (MLP_STAB + 2 * MLP_WAVES * 256)
 #define MLP_MAGIC 6755399441055744.0
-#ifndef MLP_PRIO_YOUNG
-#define MLP_PRIO_YOUNG 0
-#endif
-#ifndef MLP_FC2_SYNC
-#define MLP_FC2_SYNC 0                        // raw s_barrier every n k-steps of the fc2 K loop (0: none)
-#endif
-#ifndef MLP_WD
 #define MLP_WD 3                              // weight fragments in flight ahead of the MFMAs that consume them
-#endif
-// timeline instrumentation (tools/ubench/mlp_probe.hip, -DMLP_TRACE=1): every wave of workgroup 0 stamps s_memtime at the
-// phase boundaries of its first units into p.trace[(unit_index * 8 + wave) * 8 + point]
-#ifndef MLP_TRACE
-#define MLP_TRACE 0
-#endif
-// timing ablations (probe builds only; results invalid): 1 = no weight loads after the prologue, 2 = no activation-fragment
-// LDS reads after the prologue, 4 = no requant epilogue arithmetic
-#ifndef MLP_ABLATE
-#define MLP_ABLATE 0
-#endif
 
 struct MlpArgs {
     const int8_t *x;          // [M, 384] int8 (LayerNorm + requant output)
@@ -73,7 +53,6 @@ struct MlpArgs {
     double cm, cr;            // qact4: main and identity multipliers
     long long M;
     int balanced;             // unit schedule: 0 = 64-token units dealt round-robin, 1 = contiguous tile ranges cut into units of <= 5 tiles
-    unsigned long long *trace;   // MLP_TRACE builds only
     // mlp384rs_kernel<FMA, LNH = true> (ivit_layernorm_mlp_fused_planned): norm2 + qact3 of this workgroup's rows first, from the block's 16-bit
     // stream (`residual` is that stream), into x (a scratch of M x 384 bytes that only this launch reads)
     float ln_s;
@@ -132,7 +111,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
     constexpr int AREG = (MLP_TT * 16 * 24 + MLP_THREADS - 1) / MLP_THREADS;
     static_assert(NJ * 16 * MLP_WAVES == MLP_C && CT1 % NJ == 0, "wave count must split 96 / 24 channel tiles evenly");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (MLP_PRIO_YOUNG && wave >= MLP_WAVES / 2) __builtin_amdgcn_s_setprio(1);      // probe: static priority for the younger half
     typedef double v2d __attribute__((ext_vector_type(2)));
 
     // ---- this workgroup's units: (first tile, tiles) of unit i
@@ -154,16 +132,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
         return (int)min((long long)(MLP_TT - 1), ntiles - t0);
     };
 
-    int tr_unit = 0;
-    auto stamp = [&](int pt) __attribute__((always_inline)) {
-        if (MLP_TRACE) {
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");       // the phase's own loads and stores count
-            if (blockIdx.x == 0 && tr_unit < 4 && (threadIdx.x & 63) == 0)
-                p.trace[(tr_unit * MLP_WAVES + wave) * 8 + pt] = __builtin_readcyclecounter();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
     // activation tile of a unit (rows x 24 chunks of 16 B): global -> registers (a_fetch), registers -> LDS (a_commit)
     v4i areg[AREG];
     auto a_fetch = [&](long long tile0, int ntt) __attribute__((always_inline)) {
@@ -193,7 +161,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
     auto unit_body = [&](auto ntt_c, const int ntt, const long long tile0, const long long next_tile0, const int next_ntt) __attribute__((always_inline)) {
         constexpr int NTT = decltype(ntt_c)::value;       // tiles the body multiplies; `ntt` <= NTT of them belong to this unit
         const long long tok0 = tile0 * 16;
-        stamp(0);
         // per-lane indices from an opaque copy of the thread id: every LDS address below is (a handful of per-lane bases) +
         // immediates, recomputed per unit — left visible, the ~150 loop-invariant addresses of the unrolled phases are
         // hoisted out of the unit loop into registers and spilled
@@ -201,7 +168,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, tl = lane & 15, g = lane >> 4;
         const unsigned fb = tl * 64 + mlp_phi(tl, g) * 16;          // this lane's B-fragment chunk inside a K block, token tile 0
-        stamp(1);
 
         // ---- fc1 + qact_gelu (8 bit) into the hidden tile
         {
@@ -231,8 +197,8 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
             for (int s = 0; s < NS1; ++s) {
                 const int chunk = s / MLP_KS1, ks = s - chunk * MLP_KS1, ct0 = wave * CT1 + chunk * NJ;
                 __builtin_amdgcn_sched_barrier(0);
-                if (s + WD < NS1 && !(MLP_ABLATE & 1)) load_w(s + WD, (s + WD) % (WD + 1));
-                if (s + 1 < NS1 && !(MLP_ABLATE & 2)) load_b(s + 1, (s + 1) & 1);
+                if (s + WD < NS1) load_w(s + WD, (s + WD) % (WD + 1));
+                if (s + 1 < NS1) load_b(s + 1, (s + 1) & 1);
                 if (ks == 1) {                       // this chunk's multipliers: consumed five steps on
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
@@ -253,8 +219,7 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int tt = 0; tt < NTT; ++tt)
-                        acc[j][tt] = (MLP_ABLATE & 8) ? (acc[j][tt] ^ wf[s % (WD + 1)][j] ^ bf[s & 1][tt])
-                                                      : __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[s % (WD + 1)][j], bf[s & 1][tt], acc[j][tt], 0, 0, 0);
+                        acc[j][tt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[s % (WD + 1)][j], bf[s & 1][tt], acc[j][tt], 0, 0, 0);
                 if (ks == MLP_KS1 - 1) {
                     if (chunk == 0) __syncthreads();                       // B1: the hidden tile is free
 #pragma unroll
@@ -280,9 +245,7 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
                 }
             }
         }
-        stamp(2);
         __syncthreads();                                                    // B2
-        stamp(3);
 
         // ---- ShiftGELU (+ qact1) in place, half a wavefront per token, NTT tokens per half-wave: the token's 1536 hidden
         // bytes are read once (12 dwords per lane) and stay in registers from the row maximum (packed byte maxima, then 5
@@ -343,7 +306,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
         }
         if (next_ntt > 0) a_commit(next_ntt);
         __syncthreads();                                                    // B3
-        stamp(5);
 
         // ---- fc2 + qact2 (16 bit) + qact4 with the identity branch (16 bit)
         {
@@ -380,20 +342,15 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
 #pragma unroll
             for (int s = 0; s < MLP_KS2; ++s) {
                 __builtin_amdgcn_sched_barrier(0);
-                // keep the two waves of a SIMD abreast: the older one wins every MFMA slot, finishes its K loop thousands of
-                // cycles early and leaves the younger one alone at the single-wave 16x16x64 rate (half the pipe)
-                if (MLP_FC2_SYNC && s > 0 && (s % (MLP_FC2_SYNC ? MLP_FC2_SYNC : 1)) == 0) __builtin_amdgcn_s_barrier();
-                if (s + WD < MLP_KS2 && !(MLP_ABLATE & 1)) load_w(s + WD, (s + WD) % (WD + 1));
-                if (s + 1 < MLP_KS2 && !(MLP_ABLATE & 2)) load_b(s + 1, (s + 1) & 1);
+                if (s + WD < MLP_KS2) load_w(s + WD, (s + WD) % (WD + 1));
+                if (s + 1 < MLP_KS2) load_b(s + 1, (s + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int tt = 0; tt < NTT; ++tt)
-                        acc[j][tt] = (MLP_ABLATE & 8) ? (acc[j][tt] ^ wf[s % (WD + 1)][j] ^ bf[s & 1][tt])
-                                                      : __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[s % (WD + 1)][j], bf[s & 1][tt], acc[j][tt], 0, 0, 0);
+                        acc[j][tt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[s % (WD + 1)][j], bf[s & 1][tt], acc[j][tt], 0, 0, 0);
             }
-            stamp(6);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const int ch0 = (wave * NJ + j) * 16 + 4 * g;
@@ -420,8 +377,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES / 4) void mlp384_kernel(MlpA
                 }
             }
         }
-        stamp(7);
-        ++tr_unit;
     };
 
     // ---- the unit stream

@@ -46,34 +46,9 @@
 #define RS_F_A 2
 #define RS_F_D 3
 #define RS_F_R 4                                 // .. 15
-#define RS_F_L 16                                // LNH = 2: consumers done with the LayerNorm of units 1 ..
-#ifndef RS_WR
 #define RS_WR 9                                  // producer: slots of the weight-fragment ring (RS_WR - 1 k-steps in flight); divides 12 * RS_HD
-#endif
-#ifndef RS_HD
 #define RS_HD 6                                  // producer: requantised rounds parked in registers; divides 12
-#endif
-#ifndef RS_WD2
 #define RS_WD2 3                                 // consumer: k-steps of weight fragments in flight (3 fragments each)
-#endif
-#ifndef RS_TRACE
-#define RS_TRACE 0
-#endif
-#ifndef RS_ABL
-#define RS_ABL 0                                 // probe builds, timing only (results invalid): 1 no ShiftGELU body, 2 no epilogue arithmetic,
-#endif                                           // 4 no producer requant arithmetic
-#ifndef RS_HELP
-#define RS_HELP 1                                // the consumers multiply rounds 6..11 of the FIRST unit's fc1 (they have nothing else to do yet)
-#endif
-#ifndef RS_GSPLIT
-#define RS_GSPLIT 1                              // ShiftGELU of a unit on all sixteen half-waves (0: the consumers' eight)
-#endif
-#ifndef RS_DBG_ROLE
-#define RS_DBG_ROLE 3                            // probe builds: 1 = producers only, 2 = consumers only (resource usage per role)
-#endif
-#ifndef RS_DBG_NT
-#define RS_DBG_NT 3                              // probe builds: 1 = two-tile bodies only, 2 = three-tile bodies only
-#endif
 
 __device__ __forceinline__ int rs_chan_of_row(int rho) { return ((rho >> 2) & 1) * 16 + (rho >> 3) * 4 + (rho & 3); }
 __device__ __forceinline__ int rs_g(int tok) { return ((tok >> 1) & 3) ^ ((tok >> 3) & 3) ^ ((tok >> 4) & 1); }
@@ -125,8 +100,7 @@ __device__ __forceinline__ void rs_wait(unsigned flag_addr, unsigned target) {
                  : "=&v"(v), "=&s"(cnt), "=&s"(tmp) : "v"(flag_addr), "s"(target) : "memory", "scc");
 }
 
-// LNH: 0 = the activations are 8-bit (p.x); 1 = norm2 of every row of the workgroup first, by all eight waves; 2 = only the first unit's rows
-// first, the rest by the four consumer waves beside the producers' fc1 of the first unit (the consumers then do not help with that fc1)
+// LNH: 0 = the activations are 8-bit (p.x); 1 = norm2 of every row of the workgroup first, by all eight waves
 template <bool FMA, int LNH = 0>
 __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
     extern __shared__ __attribute__((aligned(256))) char sm[];
@@ -156,21 +130,15 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
         if (p.balanced) return (int)(unit_tile0(i + 1) - unit_tile0(i));
         return (int)min((long long)(MLP_TT - 1), ntiles - unit_tile0(i));
     };
-    auto stamp = [&](int u, int pt) __attribute__((always_inline)) {
-        if (RS_TRACE) {
-            if (blockIdx.x == 0 && u < 4 && (threadIdx.x & 63) == 0) p.trace[(u * 8 + wave) * 8 + pt] = __builtin_readcyclecounter();
-        }
-    };
-    // cumulative hand-over targets: in the first unit the consumers produce too (RS_HELP)
-    constexpr bool HELP = RS_HELP && LNH != 2;
-    constexpr unsigned NP0 = HELP ? 8 : 4, NG = RS_GSPLIT ? 8 : 4;
-    auto fh_target = [&](int u) -> unsigned { return NP0 + 4u * (unsigned)u; };      // F_H / F_A after unit u
+    // cumulative hand-over targets: in the first unit the consumers produce too, so F_H / F_A count eight producers there and
+    // four after; ShiftGELU runs on all eight waves, so F_G counts eight per unit
+    auto fh_target = [&](int u) -> unsigned { return 8u + 4u * (unsigned)u; };      // F_H / F_A after unit u
 
     if (threadIdx.x < 32) reinterpret_cast<unsigned *>(sm + RS_SFLAG)[threadIdx.x] = 0;
     if (threadIdx.x < 96) reinterpret_cast<int *>(sm + RS_SMAX)[threadIdx.x] = (int)0x80000000;
     // ---- norm2 + qact3 (vit_quant.py:139-140) of the rows this workgroup will multiply (LnGroup<384, 2>: layernorm_reg_kernel's arithmetic,
     // 8 rows per wave and pass), into the 8-bit scratch p.x; the units fetch their activation tiles from it (L2) as before.  The LayerNorm's
-    // constants sit in the ShiftGELU table-line slots, which nobody touches before the first ShiftGELU (LNH = 2: before F_L)
+    // constants sit in the ShiftGELU table-line slots, which nobody touches before the first ShiftGELU
     typedef LnGroup<MLP_C, 2> LG;
     double *cC = reinterpret_cast<double *>(sm + RS_STAB);
     float *cB = reinterpret_cast<float *>(sm + RS_STAB + MLP_C * 8), *cSc = cB + MLP_C, *cY = cSc + MLP_C;
@@ -193,7 +161,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)t[c], p.ln_s, ys);
             }
-            LG::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, p.ln_bias_int, p.ln_sc, p.ln_dy, a8 + row * MLP_C + 8 * k + 4 * hh);
+            LG::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, a8 + row * MLP_C + 8 * k + 4 * hh);
         }
     };
     // unit range [u0, u1) of this workgroup: contiguous rows in the balanced schedule, one 64-token unit at a time otherwise
@@ -207,7 +175,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
     };
     if constexpr (LNH != 0) {
         ln_fast = ln_stage_constants<MLP_C, RS_THREADS>(p.ln_bias_int, p.ln_sc, p.ln_dy, cC, cB, cSc, cY);
-        ln_units(0, LNH == 2 ? 1 : nu, wave, 8);
+        ln_units(0, nu, wave, 8);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's bytes are in the L2 before anybody's DMA asks for them
     }
     __syncthreads();
@@ -274,7 +242,6 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
         };
         load_bias(it0 * RS_HD);
         rs_wait(fl + 4 * RS_F_D, (unsigned)u + 1);
-        stamp(u, 0);
         load_b(0, 0);
         for (int it = it0; it < it1; ++it) {
             const v4i *wq = w1 + (size_t)it * SPI * 256;
@@ -315,7 +282,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
                             const double c = cq[2 * q + (i >> 1)][i & 1];
                             const double tq = FMA ? __builtin_fma((double)acc[t][4 * q + i], c, MLP_MAGIC + 128.0)
                                                   : ((double)acc[t][4 * q + i] * c + (MLP_MAGIC + 128.0));
-                            o[i] = (RS_ABL & 4) ? acc[t][4 * q + i] : __double2loint(tq);
+                            o[i] = __double2loint(tq);
                         }
                         mx[t] = max(max(mx[t], o[0]), o[1]);
                         mx[t] = max(max(mx[t], o[2]), o[3]);
@@ -332,13 +299,11 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        stamp(u, 1);
         // the activation tile is dead for this wave (the look-ahead read of k-step 0 above is discarded)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         rs_signal(fl + 4 * RS_F_A);
         if (loader && next_ntt > 0) {
             rs_wait(fl + 4 * RS_F_A, fh_target(u));
-            if (LNH == 2) rs_wait(fl + 4 * RS_F_L, 4u);      // the consumers' LayerNorm of the later units' rows is in the L2
             a_dma(next_tile0, next_ntt);
         }
 #pragma unroll
@@ -353,34 +318,33 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             rs_signal(fl + 4 * RS_F_D);
         }
-        stamp(u, 2);
     };
 
     // ------------------------------------------------------------------------------------------------------------------------
-    // ShiftGELU (+ qact1) of a unit in place, half a wavefront per token: half-wave `hwid` of NHW takes tokens hwid + NHW i.
+    // ShiftGELU (+ qact1) of a unit in place, half a wavefront per token: half-wave `hwid` of the sixteen takes tokens hwid + 16 i.
     // The row maximum comes from the producers (RS_SMAX, reset here); per token: its 256-byte table line global -> one of this
     // half-wave's two LDS slots, the row's 12 dwords per lane, 48 byte gathers, write-back.  Gathers are issued three dwords
     // (12 gathers) ahead of the merge that consumes them (lgkmcnt counts 15 at most), their addresses are one SDWA each.
-    auto gelu = [&](auto nt_c, auto nhw_c, const int nvalid) __attribute__((always_inline)) {
-        constexpr int NT = decltype(nt_c)::value, NHW = decltype(nhw_c)::value;
+    auto gelu = [&](auto nt_c, const int nvalid) __attribute__((always_inline)) {
+        constexpr int NT = decltype(nt_c)::value, NHW = 16;
         constexpr int NTK = (NT == 3 ? 80 : 64) / NHW;                                   // tokens per half-wave
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, l32 = lane & 31;
-        const int hwid = (NHW == 16 ? wave * 2 : (wave - 4) * 2) + (lane >> 5);
+        const int hwid = wave * 2 + (lane >> 5);
         const unsigned rowa = sm_lds + RS_SH + hwid * 64 + (l32 & 15) * 4 + (l32 >> 4) * RS_KBLK;    // token hwid, K blocks l32 >> 4 (+ 2 m)
         const unsigned rowb = rowa + 12 * RS_KBLK;
         const unsigned maxa = sm_lds + RS_SMAX + hwid * 4;
         v2i line[NTK];
 #pragma unroll
         for (int i = 0; i < NTK; ++i)
-            if (i * NHW < nvalid && !(RS_ABL & 1)) {     // tokens NHW i .. NHW i + NHW - 1, one per half-wave: all valid or none
+            if (i * NHW < nvalid) {     // tokens NHW i .. NHW i + NHW - 1, one per half-wave: all valid or none
                 const int qb = *(lds_i32 *)(size_t)(maxa + i * NHW * 4);          // max(Q) + 128
                 line[i] = reinterpret_cast<const v2i *>(p.tab + (size_t)qb * 256)[l32];
             }
 #pragma unroll
         for (int i = 0; i < NTK; ++i)
-            if (i * NHW < nvalid && !(RS_ABL & 1)) {
+            if (i * NHW < nvalid) {
                 if (l32 == 0) *(lds_i32 *)(size_t)(maxa + i * NHW * 4) = (int)0x80000000;
                 const unsigned base = sm_lds + RS_STAB + (hwid * 2 + (i & 1)) * 256;
                 *(lds_v2i *)(size_t)(base + l32 * 8) = line[i];
@@ -440,34 +404,29 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
             for (int s = 0; s < RS_WR - 1; ++s) wf[s] = w1[(size_t)s * 256];
         }
         for (int u = 0; u < nu; ++u) {
-            const int ntt = unit_ntt(u), it1 = (HELP && u == 0) ? 12 / RS_HD / 2 : 12 / RS_HD;
-            if (!(RS_DBG_ROLE & 1)) continue;
-            if (ntt == MLP_TT && (RS_DBG_NT & 2)) {
+            const int ntt = unit_ntt(u), it1 = u == 0 ? 12 / RS_HD / 2 : 12 / RS_HD;
+            if (ntt == MLP_TT) {
                 produce(std::integral_constant<int, 3>{}, wave, wf, u, 0, it1, unit_tile0(u + 1), unit_ntt(u + 1), wave == 0);
-                if (RS_GSPLIT) { rs_wait(fl + 4 * RS_F_H, fh_target(u)); if (LNH == 2) rs_wait(fl + 4 * RS_F_L, 4u); gelu(std::integral_constant<int, 3>{}, std::integral_constant<int, 16>{}, ntt * 16); }
-            } else if (RS_DBG_NT & 1) {
+                rs_wait(fl + 4 * RS_F_H, fh_target(u));
+                gelu(std::integral_constant<int, 3>{}, ntt * 16);
+            } else {
                 produce(std::integral_constant<int, 2>{}, wave, wf, u, 0, it1, unit_tile0(u + 1), unit_ntt(u + 1), wave == 0);
-                if (RS_GSPLIT) { rs_wait(fl + 4 * RS_F_H, fh_target(u)); if (LNH == 2) rs_wait(fl + 4 * RS_F_L, 4u); gelu(std::integral_constant<int, 2>{}, std::integral_constant<int, 16>{}, ntt * 16); }
+                rs_wait(fl + 4 * RS_F_H, fh_target(u));
+                gelu(std::integral_constant<int, 2>{}, ntt * 16);
             }
         }
     } else {
         // =========================================================================================== consumers
         const int j = wave - 4;
-        if constexpr (LNH == 2) {
-            ln_units(1, nu, j, 4);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            rs_signal(fl + 4 * RS_F_L);
-            rs_wait(fl + 4 * RS_F_L, 4u);                    // every consumer is done with the constants in the table-line slots
-        }
-        if (HELP && (RS_DBG_ROLE & 1)) {
+        {
             // the first unit's fc1, second half of the rounds: nothing else for a consumer to do until a hidden tile exists
-            static_assert(!RS_HELP || 12 / RS_HD == 2, "the first unit is split by iterations");
+            static_assert(12 / RS_HD == 2, "the first unit is split by iterations");
             v4i wfh[RS_WR];
             const v4i *w1 = p.w1f + (size_t)RS_HD * 12 * 256 + j * 64 + (threadIdx.x & 63);
 #pragma unroll
             for (int s = 0; s < RS_WR - 1; ++s) wfh[s] = w1[(size_t)s * 256];
-            if (unit_ntt(0) == MLP_TT && (RS_DBG_NT & 2)) produce(std::integral_constant<int, 3>{}, j, wfh, 0, 1, 2, 0, 0, false);
-            else if (RS_DBG_NT & 1) produce(std::integral_constant<int, 2>{}, j, wfh, 0, 1, 2, 0, 0, false);
+            if (unit_ntt(0) == MLP_TT) produce(std::integral_constant<int, 3>{}, j, wfh, 0, 1, 2, 0, 0, false);
+            else produce(std::integral_constant<int, 2>{}, j, wfh, 0, 1, 2, 0, 0, false);
         }
         auto c_unit = [&](auto nt_c, const int u, const long long tile0, const int ntt) __attribute__((always_inline)) {
             constexpr int NT = decltype(nt_c)::value;
@@ -491,11 +450,8 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
 #pragma unroll
             for (int s = 0; s < RS_WD2; ++s) load_w(s, s);
             rs_wait(fl + 4 * RS_F_H, fh_target(u));
-            stamp(u, 3);
-            if (RS_GSPLIT) gelu(nt_c, std::integral_constant<int, 16>{}, nvalid);
-            else gelu(nt_c, std::integral_constant<int, 8>{}, nvalid);
-            rs_wait(fl + 4 * RS_F_G, NG * (unsigned)(u + 1));
-            stamp(u, 4);
+            gelu(nt_c, nvalid);
+            rs_wait(fl + 4 * RS_F_G, 8u * (unsigned)(u + 1));
             // ---- fc2: output channels 96 j + 32 ct + 16 kh + v of token t * 32 + tok in acc[ct][t][v]
             v16i acc[3][NT];
             {
@@ -523,7 +479,6 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
                                                                                 ks == 0 ? bias[ct] : acc[ct][t], 0, 0, 0);
                 }
             }
-            stamp(u, 5);
             // ---- qact2 (16 bit) + qact4 with the identity branch: 16 consecutive channels of a token per lane.  The identity rows
             // of tile n + 2 and the multipliers of the next channel tile are requested while tile n is requantised
             const long long tok0 = tile0 * 16;
@@ -560,7 +515,6 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int v = 2 * d + h;
-                        if (RS_ABL & 2) { o[h] = acc[ct][t][v] ^ (int)rw ^ (int)c2[ct & 1][v >> 1][v & 1]; continue; }
                         const int t16 = min(max(mlp_rq<FMA>(acc[ct][t][v], c2[ct & 1][v >> 1][v & 1]), -32768), 32767);
                         const int r = h ? ((int)rw >> 16) : (int)(short)(rw & 0xffffu);
                         o[h] = rq_fast(r, p.cr) + rq_fast(t16, p.cm);         // both terms < 2^31 / 2: the sum is the reference's fp64 sum
@@ -574,13 +528,11 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
                     *reinterpret_cast<v4i *>(p.out + row * MLP_C + ch0 + 8) = o1;
                 }
             }
-            stamp(u, 6);
         };
         for (int u = 0; u < nu; ++u) {
             const int ntt = unit_ntt(u);
-            if (!(RS_DBG_ROLE & 2)) continue;
-            if (ntt == MLP_TT && (RS_DBG_NT & 2)) c_unit(std::integral_constant<int, 3>{}, u, unit_tile0(u), ntt);
-            else if (RS_DBG_NT & 1) c_unit(std::integral_constant<int, 2>{}, u, unit_tile0(u), ntt);
+            if (ntt == MLP_TT) c_unit(std::integral_constant<int, 3>{}, u, unit_tile0(u), ntt);
+            else c_unit(std::integral_constant<int, 2>{}, u, unit_tile0(u), ntt);
         }
     }
 }

@@ -30,26 +30,6 @@ struct ivit_graph_s {
     hipGraphExec_t exec;
 };
 
-#ifndef IVIT_OPT_V_ROWMAJOR
-#define IVIT_OPT_V_ROWMAJOR 1          // A/B: v row-major between the qkv GEMM and the row-table attention
-#endif
-#ifndef IVIT_OPT_LN_QKV
-#define IVIT_OPT_LN_QKV 1              // A/B: norm1 inside the qkv GEMM's prologue (ivit_layernorm_linear_i8_qkv_planned) where v is row-major
-#endif
-#ifndef IVIT_OPT_PROJ_WS
-#define IVIT_OPT_PROJ_WS 1             // A/B: attn.proj + qact2 of a D = 384 block on gemm_ws_qkv_kernel (prepared plan)
-#endif
-#ifndef IVIT_OPT_PROJ_LN
-#define IVIT_OPT_PROJ_LN 0              // A/B: norm2 in the tail of the attn.proj launch (ivit_linear_i8_requant_residual_layernorm_planned): same-box
-                                       // 2.785 ms against 2.657 with norm2 as its own launch (the tail runs behind a barrier, two waves per SIMD)
-#endif
-#ifndef IVIT_OPT_LN_MLP
-#define IVIT_OPT_LN_MLP 1              // A/B: norm2 in the head of the fused Mlp's launch (ivit_layernorm_mlp_fused_planned)
-#endif
-#ifndef IVIT_OPT_ATTN_ROWTAB
-#define IVIT_OPT_ATTN_ROWTAB 1         // A/B: Shiftmax by row tables (one gather per score) where a layer's table lines fit
-#endif
-
 namespace {
 
 inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -86,9 +66,6 @@ SliceLayout slice_layout(const ivit_vit_s *m, int B) {
     return L;
 }
 
-#ifndef IVIT_OPT_SLICE_CU_SHARE
-#define IVIT_OPT_SLICE_CU_SHARE 1       // A/B: a slice's persistent D = 384 kernels sized for num_cu / slices (ivit_ctx::cu_share)
-#endif
 inline int slice_begin(int batch, int nslices, int i) { return (int)(((long long)batch * i) / nslices); }
 inline int max_slice(int batch, int nslices) { return (batch + nslices - 1) / nslices; }
 
@@ -123,11 +100,10 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         const ivit_vit_block &b = m->blocks[i];
         // a layer on the row-table attention takes v ROW-major (ldv = 0: the qkv GEMM stores 16 bytes per lane instead of 16 byte
         // stores, the attention kernel transposes on its way into the LDS); the other attention forms read v^T
-        const int ldv = (m->fused_attention && m->has_rowtab[i] && IVIT_OPT_V_ROWMAJOR) ? 0 : ld;
+        const int ldv = (m->fused_attention && m->has_rowtab[i]) ? 0 : ld;
         // norm1's 8-bit output has one consumer: where the qkv GEMM keeps a CU's tokens in LDS it is computed there (round 6)
-        rc = (IVIT_OPT_LN_QKV && ldv == 0) ? ivit_layernorm_linear_i8_qkv_planned(h, m->plans[4 * i], x, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy,
-                                                                                  q, k, vt, B, T, H, dh)
-                                           : IVIT_ERR_UNSUPPORTED;
+        rc = ldv == 0 ? ivit_layernorm_linear_i8_qkv_planned(h, m->plans[4 * i], x, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, q, k, vt, B, T, H, dh)
+                      : IVIT_ERR_UNSUPPORTED;
         if (rc == IVIT_ERR_UNSUPPORTED) {
             RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, a8));
             RUN(ivit_linear_i8_qkv_planned(h, m->plans[4 * i], a8, q, k, vt, B, T, H, dh, ldv));
@@ -150,32 +126,27 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
             RUN(ivit_shiftmax(h, s8, (int64_t)B * H * T, T, ld, b.s_softmax, 16, p16, ld));
             RUN(ivit_attn_pv_requant(h, p16, vt, b.dy_pv, ctx8, B, H, T, dh, ld, ld));
         }
-        // attn.proj + qact2 with the identity branch, then norm2 + qact3 and the Mlp.  norm2 can ride in the TAIL of the proj launch (the kernel
-        // owns whole rows per workgroup: built, bit-exact, slower, IVIT_OPT_PROJ_LN = 0) or in the HEAD of the fused Mlp's launch
-        // (ivit_layernorm_mlp_fused_planned, IVIT_OPT_LN_MLP)
+        // attn.proj + qact2 with the identity branch, then norm2 + qact3 and the Mlp.  norm2 rides in the HEAD of the fused Mlp's launch
+        // (ivit_layernorm_mlp_fused_planned) where that kernel takes the shape; in the tail of the proj launch it measured slower
+        // (profiles/README.md)
         const bool mlp_fast = m->mlp_plans[i] && fabs(b.res2_main.m * b.res2_main.r) < RQ_FAST_CLIM &&
                               fabs(b.res2_res.m * b.res2_res.r) < RQ_FAST_CLIM;
-        rc = IVIT_OPT_PROJ_LN ? ivit_linear_i8_requant_residual_layernorm_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, M,
-                                                                                b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8)
-                              : IVIT_ERR_UNSUPPORTED;
-        bool ln2_done = rc != IVIT_ERR_UNSUPPORTED;
-        if (!ln2_done) RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, M));
-        else RUN(rc);
+        RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, M));
         { int16_t *t = x; x = y; y = t; }
-        bool mlp_done = false;
-        if (!ln2_done && mlp_fast && IVIT_OPT_LN_MLP) {
-            rc = ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8, m->gelu_tab + (size_t)i * 65536,
-                                                  b.res2_main, b.res2_res, y, M);
-            if (rc != IVIT_ERR_UNSUPPORTED) { RUN(rc); ln2_done = mlp_done = true; }
-        }
-        if (!ln2_done) RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8));
-        if (mlp_done) {
-        } else if (mlp_fast) {     // hidden tensor stays in LDS
-            RUN(ivit_mlp_fused_planned(h, m->mlp_plans[i], a8, m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, x, y, M));
+        rc = mlp_fast ? ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8,
+                                                         m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, y, M)
+                      : IVIT_ERR_UNSUPPORTED;
+        if (rc == IVIT_ERR_UNSUPPORTED) {
+            RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8));
+            if (mlp_fast) {     // hidden tensor stays in LDS
+                RUN(ivit_mlp_fused_planned(h, m->mlp_plans[i], a8, m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, x, y, M));
+            } else {
+                RUN(ivit_linear_i8_requant_planned(h, m->plans[4 * i + 2], a8, 8, h8, M));
+                RUN(ivit_shiftgelu_requant_lut(h, h8, M, Hd, m->gelu_tab + (size_t)i * 65536, g8));
+                RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, M));
+            }
         } else {
-            RUN(ivit_linear_i8_requant_planned(h, m->plans[4 * i + 2], a8, 8, h8, M));
-            RUN(ivit_shiftgelu_requant_lut(h, h8, M, Hd, m->gelu_tab + (size_t)i * 65536, g8));
-            RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, M));
+            RUN(rc);
         }
         { int16_t *t = x; x = y; y = t; }
     }
@@ -218,7 +189,7 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
     m->max_slices = max_slices;
     m->fork = nullptr;
     hipError_t e = hipMalloc((void **)&m->gelu_tab, (size_t)cfg->depth * 65536);
-    if (e == hipSuccess && m->fused_attention && IVIT_OPT_ATTN_ROWTAB) e = hipMalloc((void **)&m->rowtab, (size_t)cfg->depth * 256 * 64 * sizeof(float));
+    if (e == hipSuccess && m->fused_attention) e = hipMalloc((void **)&m->rowtab, (size_t)cfg->depth * 256 * 64 * sizeof(float));
     if (e != hipSuccess) {
         snprintf(h->err, sizeof(h->err), "ivit_vit_create: hipMalloc: %s", hipGetErrorString(e));
         delete m;
@@ -243,8 +214,8 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
             rc = ivit_linear_plan_create(h, lin[k].w, lin[k].bias, lin[k].dy, lin[k].N, lin[k].K, &pl);
             if (rc != IVIT_OK) { ivit_vit_destroy(m); return rc; }
             // the qkv layer of a D = 384, dh = 64 model also runs on gemm_ws_qkv_kernel (weights in its fragment order)
-            if (k == 0 && IVIT_OPT_LN_QKV && D == WS_K && D / cfg->num_heads == 64) (void)ivit_linear_plan_prepare_ws(h, pl);
-            if (k == 1 && IVIT_OPT_PROJ_WS && D == WS_K) (void)ivit_linear_plan_prepare_ws(h, pl);      // attn.proj + residual on the same kernel
+            if (k == 0 && D == WS_K && D / cfg->num_heads == 64) (void)ivit_linear_plan_prepare_ws(h, pl);
+            if (k == 1 && D == WS_K) (void)ivit_linear_plan_prepare_ws(h, pl);      // attn.proj + residual on the same kernel
             m->plans.push_back(pl);
         }
         ivit_mlp_plan mp = nullptr;
@@ -332,7 +303,7 @@ int ivit_vit_forward(ivit_vit m, const int8_t *images, int batch, int nslices, v
     for (int i = 0; i < nslices; ++i) {
         const int b0 = slice_begin(batch, nslices, i), b1 = slice_begin(batch, nslices, i + 1);
         if (hipStreamWaitEvent(m->streams[i], m->fork, 0) != hipSuccess) return IVIT_ERR_HIP;
-        m->slice_h[i]->cu_share = IVIT_OPT_SLICE_CU_SHARE ? std::max(1, persistent_cus(h) / nslices) : 0;      // a share of the caller's own share
+        m->slice_h[i]->cu_share = std::max(1, persistent_cus(h) / nslices);      // a share of the caller's own share
         rc = run_slice(m, m->slice_h[i], images + (size_t)b0 * img_bytes, b1 - b0, max_slice(batch, nslices),
                        (char *)workspace + stride * (size_t)i,
                        logits + (size_t)b0 * m->cfg.num_classes);
@@ -397,7 +368,7 @@ struct ivit_swin_s {
     bool fused_mlp;                   // stage-0 Mlp in one kernel (ivit_mlp_fused)
     std::vector<ivit_linear_plan> mlp_lin;   // per block: fc1, fc2 plans of the C = 384 stage (null elsewhere)
     std::vector<ivit_mlp_plan> mlp_plans;    // per block: fused Mlp plan (C = 384, hidden 1536) or null
-    std::vector<ivit_linear_plan> lin_plans; // per block: qkv, proj, fc1, fc2 plans where C % 384 == 0 (IVIT_OPT_SWIN_PLANS), else null
+    std::vector<ivit_linear_plan> lin_plans; // per block: qkv, proj plans prepared for gemm_ws_qkv_kernel where C == 384, else null
     int8_t *gelu_tab;                 // [nblocks][65536]
     int max_slices;
     std::vector<ivit_handle> slice_h;
@@ -405,22 +376,6 @@ struct ivit_swin_s {
     std::vector<hipEvent_t> done;
     hipEvent_t fork;
 };
-
-#ifndef IVIT_OPT_MERGE_LN
-#define IVIT_OPT_MERGE_LN 1            // A/B: PatchMerging's gather folded into its LayerNorm (ivit_patch_merge_layernorm_requant)
-#endif
-#ifndef IVIT_OPT_SWIN_WS
-#define IVIT_OPT_SWIN_WS 1             // A/B: the C = 384 stage's qkv (+ norm1) and proj layers on gemm_ws_qkv_kernel
-#endif
-#ifndef IVIT_OPT_MERGE_W16
-#define IVIT_OPT_MERGE_W16 1            // A/B: PatchMerging's reduction stores its 8-bit QuantAct as int16 (no ivit_widen_i8_i16 pass)
-#endif
-#ifndef IVIT_OPT_SWIN_LN_MLP
-#define IVIT_OPT_SWIN_LN_MLP 0
-#endif
-#ifndef IVIT_OPT_SWIN_PLANS
-#define IVIT_OPT_SWIN_PLANS 0          // A/B: the C = 384 / 768 stages' QuantLinear layers on the planned (persistent) kernels
-#endif
 
 namespace {
 
@@ -479,13 +434,13 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             const ivit_swin_block &b = m->blocks[bi];
             const int shift = (bj % 2 == 0 || res <= c.window_size) ? 0 : c.window_size / 2;
             const int wsz = res <= c.window_size ? res : c.window_size;     // SwinTransformerBlock.__init__
-            const ivit_linear_plan *lp = m->lin_plans.empty() ? nullptr : &m->lin_plans[4 * bi];
+            const ivit_linear_plan *lp = &m->lin_plans[2 * bi];
             // norm1 inside the qkv launch where that layer runs on gemm_ws_qkv_kernel (C = 384, activations in natural token order)
-            rc = (IVIT_OPT_SWIN_WS && lp && lp[0] && li != 0) ? ivit_layernorm_linear_i8_requant_planned(h, lp[0], x, b.s_in, b.n1.bias_int, b.n1.sc, b.n1.dy, qkv, (int)M)
-                                                              : IVIT_ERR_UNSUPPORTED;
+            rc = (lp[0] && li != 0) ? ivit_layernorm_linear_i8_requant_planned(h, lp[0], x, b.s_in, b.n1.bias_int, b.n1.sc, b.n1.dy, qkv, (int)M)
+                                    : IVIT_ERR_UNSUPPORTED;
             if (rc == IVIT_ERR_UNSUPPORTED) {
                 RUN(swin_ln(m, h, x, M, C, b.s_in, b.n1, L, li == 0, a8));
-                if (lp && lp[0]) RUN(ivit_linear_i8_requant_planned(h, lp[0], a8, 8, qkv, (int)M));
+                if (lp[0]) RUN(ivit_linear_i8_requant_planned(h, lp[0], a8, 8, qkv, (int)M));
                 else RUN(ivit_linear_i8_requant(h, a8, b.qkv.w, b.qkv.b, b.qkv.dy, 8, qkv, (int)M, 3 * C, C));
             } else {
                 RUN(rc);
@@ -497,39 +452,30 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             else
                 RUN(ivit_window_attention_fused(h, qkv, b.dy_qk, b.dy_a, b.relb, b.s_softmax, b.dy_pv, ctx, B, res,
                                                 wsz, shift, heads, C / heads));
-            if (lp && lp[1]) RUN(ivit_linear_i8_requant_residual_planned(h, lp[1], ctx, b.res1_main, b.res1_res, x, y, (int)M));
+            if (lp[1]) RUN(ivit_linear_i8_requant_residual_planned(h, lp[1], ctx, b.res1_main, b.res1_res, x, y, (int)M));
             else RUN(ivit_linear_i8_requant_residual(h, ctx, b.proj.w, b.proj.b, b.proj.dy, b.res1_main, b.res1_res, x, y, (int)M, C, C));
             { int16_t *t = x; x = y; y = t; }
             const bool mlp384 = m->mlp_plans[bi] && fabs(b.res2_main.m * b.res2_main.r) < RQ_FAST_CLIM &&
                                 fabs(b.res2_res.m * b.res2_res.r) < RQ_FAST_CLIM;
-            // C = 384 stage: norm2 can ride in the head of the fused Mlp's launch (natural token order) — measured SLOWER here (Swin-T b256,
-            // two slices: 4.76 against 4.70 ms same-box; the LayerNorm launch of one slice overlaps the other slice's kernels) and off
-            rc = (IVIT_OPT_SWIN_LN_MLP && mlp384 && li != 0)
-                     ? ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[bi], x, b.s_mid, b.n2.bias_int, b.n2.sc, b.n2.dy, a8,
-                                                        m->gelu_tab + (size_t)bi * 65536, b.res2_main, b.res2_res, y, M)
-                     : IVIT_ERR_UNSUPPORTED;
-            const bool ln_mlp = rc != IVIT_ERR_UNSUPPORTED;
-            if (ln_mlp) RUN(rc);
-            else RUN(swin_ln(m, h, x, M, C, b.s_mid, b.n2, L, li == 0, a8));
-            if (ln_mlp) {
-            } else if (C == 96 && c.mlp_ratio == 4 && m->fused_mlp) {     // narrow stage: hidden tensor stays in LDS
+            // norm2 is a launch of its own in every stage.  (In the head of the C = 384 stage's fused Mlp it measured slower: Swin-T b256,
+            // two slices, 4.76 against 4.70 ms same-box; the LayerNorm launch of one slice overlaps the other slice's kernels)
+            RUN(swin_ln(m, h, x, M, C, b.s_mid, b.n2, L, li == 0, a8));
+            if (C == 96 && c.mlp_ratio == 4 && m->fused_mlp) {     // narrow stage: hidden tensor stays in LDS
                 RUN(ivit_mlp_fused(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, m->gelu_tab + (size_t)bi * 65536, b.fc2.w, b.fc2.b,
                                    b.fc2.dy, b.res2_main, b.res2_res, x, y, M, C, 4 * C));
             } else if (mlp384) {                                    // C = 384 stage: weights streamed, hidden tile in LDS
                 RUN(ivit_mlp_fused_planned(h, m->mlp_plans[bi], a8, m->gelu_tab + (size_t)bi * 65536, b.res2_main, b.res2_res, x, y, M));
             } else {
-                if (lp && lp[2]) RUN(ivit_linear_i8_requant_planned(h, lp[2], a8, 8, h8, (int)M));
-                else RUN(ivit_linear_i8_requant(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, 8, h8, (int)M, c.mlp_ratio * C, C));
+                RUN(ivit_linear_i8_requant(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, 8, h8, (int)M, c.mlp_ratio * C, C));
                 RUN(ivit_shiftgelu_requant_lut(h, h8, M, c.mlp_ratio * C, m->gelu_tab + (size_t)bi * 65536, g8));
-                if (lp && lp[3]) RUN(ivit_linear_i8_requant_residual_planned(h, lp[3], g8, b.res2_main, b.res2_res, x, y, (int)M));
-                else RUN(ivit_linear_i8_requant_residual(h, g8, b.fc2.w, b.fc2.b, b.fc2.dy, b.res2_main, b.res2_res, x, y, (int)M, C, c.mlp_ratio * C));
+                RUN(ivit_linear_i8_requant_residual(h, g8, b.fc2.w, b.fc2.b, b.fc2.dy, b.res2_main, b.res2_res, x, y, (int)M, C, c.mlp_ratio * C));
             }
             { int16_t *t = x; x = y; y = t; }
         }
         if (li < c.num_layers - 1) {     // PatchMerging: gather -> LN(4C) -> qact1(8) -> reduction -> qact2(8)
             const ivit_swin_merge &g = m->merges[li];
             // the 2 x 2 gather rides in the LayerNorm's loads (round 6: as a pass of its own it was 32 us per merge at Swin-T b256)
-            rc = IVIT_OPT_MERGE_LN ? ivit_patch_merge_layernorm_requant(h, x, B, res, C, g.s_in, g.n.bias_int, g.n.sc, g.n.dy, a8) : IVIT_ERR_UNSUPPORTED;
+            rc = ivit_patch_merge_layernorm_requant(h, x, B, res, C, g.s_in, g.n.bias_int, g.n.sc, g.n.dy, a8);
             const bool merged = rc == IVIT_OK;
             if (!merged && rc != IVIT_ERR_UNSUPPORTED) RUN(rc);
             if (!merged) RUN(ivit_patch_merge_gather(h, x, 16, B, res, C, t16));
@@ -538,7 +484,7 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             M = (long long)B * L;
             if (!merged) RUN(swin_ln(m, h, t16, M, 4 * C, g.s_in, g.n, L, false, a8));
             // reduction -> qact2(8), stored as the 16-bit stream the next stage reads (round 6: the widening pass was 16 us per merge)
-            rc = IVIT_OPT_MERGE_W16 ? ivit_linear_i8_requant8_store16(h, a8, g.red.w, nullptr, g.red.dy, x, (int)M, 2 * C, 4 * C) : IVIT_ERR_UNSUPPORTED;
+            rc = ivit_linear_i8_requant8_store16(h, a8, g.red.w, nullptr, g.red.dy, x, (int)M, 2 * C, 4 * C);
             if (rc == IVIT_ERR_UNSUPPORTED) {
                 RUN(ivit_linear_i8_requant(h, a8, g.red.w, nullptr, g.red.dy, 8, ctx, (int)M, 2 * C, 4 * C));
                 RUN(ivit_widen_i8_i16(h, ctx, x, M * 2 * C));
@@ -645,26 +591,16 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
                 m->mlp_lin.push_back(p1);
                 m->mlp_lin.push_back(p2);
                 m->mlp_plans.push_back(mp);
-                if (IVIT_OPT_SWIN_PLANS || IVIT_OPT_SWIN_WS) {
-                    ivit_linear_plan q[4] = {nullptr, nullptr, nullptr, nullptr};
-                    if (!IVIT_OPT_SWIN_PLANS) {
-                        // round 6: the C = 384 stage's qkv and proj layers on gemm_ws_qkv_kernel (prepared plans), norm1 inside the qkv launch
-                        if (C == WS_K) {
-                            if (ivit_linear_plan_create(h, b.qkv.w, b.qkv.b, b.qkv.dy, 3 * C, C, &q[0]) != IVIT_OK) q[0] = nullptr;
-                            if (q[0] && ivit_linear_plan_prepare_ws(h, q[0]) != IVIT_OK) { (void)ivit_linear_plan_destroy(q[0]); q[0] = nullptr; }
-                            if (ivit_linear_plan_create(h, b.proj.w, b.proj.b, b.proj.dy, C, C, &q[1]) != IVIT_OK) q[1] = nullptr;
-                            if (q[1] && ivit_linear_plan_prepare_ws(h, q[1]) != IVIT_OK) { (void)ivit_linear_plan_destroy(q[1]); q[1] = nullptr; }
-                        }
-                    } else if (C % 384 == 0) {
-                        if (ivit_linear_plan_create(h, b.qkv.w, b.qkv.b, b.qkv.dy, 3 * C, C, &q[0]) != IVIT_OK) q[0] = nullptr;
-                        if (ivit_linear_plan_create(h, b.proj.w, b.proj.b, b.proj.dy, C, C, &q[1]) != IVIT_OK) q[1] = nullptr;
-                        if (!mp) {
-                            if (ivit_linear_plan_create(h, b.fc1.w, b.fc1.b, b.fc1.dy, cfg->mlp_ratio * C, C, &q[2]) != IVIT_OK) q[2] = nullptr;
-                            if (ivit_linear_plan_create(h, b.fc2.w, b.fc2.b, b.fc2.dy, C, cfg->mlp_ratio * C, &q[3]) != IVIT_OK) q[3] = nullptr;
-                        }
-                    }
-                    for (int k = 0; k < 4; ++k) m->lin_plans.push_back(q[k]);
+                // round 6: the C = 384 stage's qkv and proj layers on gemm_ws_qkv_kernel (prepared plans), norm1 inside the qkv launch
+                ivit_linear_plan q[2] = {nullptr, nullptr};
+                if (C == WS_K) {
+                    if (ivit_linear_plan_create(h, b.qkv.w, b.qkv.b, b.qkv.dy, 3 * C, C, &q[0]) != IVIT_OK) q[0] = nullptr;
+                    if (q[0] && ivit_linear_plan_prepare_ws(h, q[0]) != IVIT_OK) { (void)ivit_linear_plan_destroy(q[0]); q[0] = nullptr; }
+                    if (ivit_linear_plan_create(h, b.proj.w, b.proj.b, b.proj.dy, C, C, &q[1]) != IVIT_OK) q[1] = nullptr;
+                    if (q[1] && ivit_linear_plan_prepare_ws(h, q[1]) != IVIT_OK) { (void)ivit_linear_plan_destroy(q[1]); q[1] = nullptr; }
                 }
+                m->lin_plans.push_back(q[0]);
+                m->lin_plans.push_back(q[1]);
             }
     }
     if (max_slices > 1) {
@@ -714,7 +650,7 @@ int ivit_swin_forward(ivit_swin m, const int8_t *images, int batch, int nslices,
     for (int i = 0; i < nslices; ++i) {
         const int b0 = slice_begin(batch, nslices, i), b1 = slice_begin(batch, nslices, i + 1);
         if (hipStreamWaitEvent(m->streams[i], m->fork, 0) != hipSuccess) return IVIT_ERR_HIP;
-        m->slice_h[i]->cu_share = IVIT_OPT_SLICE_CU_SHARE ? std::max(1, persistent_cus(h) / nslices) : 0;      // a share of the caller's own share
+        m->slice_h[i]->cu_share = std::max(1, persistent_cus(h) / nslices);      // a share of the caller's own share
         rc = swin_run_slice(m, m->slice_h[i], images + (size_t)b0 * img_bytes, b1 - b0, (char *)workspace + stride * (size_t)i,
                             logits + (size_t)b0 * m->cfg.num_classes);
         if (rc != IVIT_OK) return rc;

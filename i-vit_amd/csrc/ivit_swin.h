@@ -229,9 +229,7 @@ __global__ __launch_bounds__(256) void layernorm_tokenorder_kernel(const XT *__r
 // and runs its serial phase on 32 of 256 threads).  A thread keeps ONE channel group for the whole block — block size
 // (C / 8) x 16 — so its eight per-channel constants live in registers; the order-sensitive sums and the integer square
 // root run on 128 threads, one token each, on rows staged as fp32 with an odd pitch (conflict-free per-token walks).
-#ifndef LNT8_ROWS
 #define LNT8_ROWS 96       // 37 KB of LDS per block = 4 blocks per CU (128 rows: 3 blocks, the requant pass 10 % slower; 64: no better)
-#endif
 template <int OUTM, int CC, typename XT>
 __global__ __launch_bounds__(CC / 8 * 16) void layernorm_tokenorder8_kernel(const XT *__restrict__ x, long long rows, float s,
                                                                             const float *__restrict__ bias_int,
@@ -373,13 +371,8 @@ struct WinAttnArgs {
 // LUT = true:  8 wavefronts x p.wpw windows each, so that the Shiftmax tables of the layer (up to 24 KB, the same for every
 //              head and window) and the slab are staged once per 8 * wpw windows; windows under the shift mask (the float
 //              -100 lives between the requotient's multiply and divide) keep the arithmetic shift-exp.
-#ifndef WA_PROBE          // timing probes only (results invalid): 1 no shift-exp arithmetic, 2 no score gathers (requant only),
-#define WA_PROBE 0         // 4 no global stores, 8 return after the operand loads
-#endif
 #define WA_FIXED(NW) ((NW) * (2048 + 64) + 4816 + 512 + 1024)
-#ifndef WA_MINW
 #define WA_MINW 6          // waves per SIMD the arithmetic kernel is compiled for (80 registers, three spilled dwords outside the score loops; 4: +3 %, 8: +18 %)
-#endif
 template <bool LUT>
 __global__ __launch_bounds__(LUT ? 512 : 256, LUT ? 4 : WA_MINW) void window_attention_kernel(WinAttnArgs p) {
     constexpr int NW = LUT ? 8 : 4;
@@ -508,7 +501,6 @@ __global__ __launch_bounds__(LUT ? 512 : 256, LUT ? 4 : WA_MINW) void window_att
             vf[kt][w] = (int)word;
         }
 
-    if ((WA_PROBE & 8) && (vf[0][0] ^ vf[1][3] ^ qf[0][0] ^ kf[1][1]) != 0x12345678) return;
     const double c_qk = p.dy_qk.m * p.dy_qk.r, c_pv = p.dy_pv.m * p.dy_pv.r;
     const float x0 = floorf(-1.0f / s), nx0 = 15.0f * x0;
     const RcpC x0r = rcp_prepare(x0);
@@ -533,7 +525,6 @@ __global__ __launch_bounds__(LUT ? 512 : 256, LUT ? 4 : WA_MINW) void window_att
             kk = (i == 24 && half) ? 48 : key;
             const int z = kt ? acc1[r] : acc0[r];
             const int v = min(max(__double2loint((double)z * c_qk + 6755399441055744.0), -128), 127);
-            if (WA_PROBE & 2) return v;
             return min(max((int)sTa[v + 128] + (int)sRel[qq * 49 + kk], -128), 127);
         };
         if (LUT && !masked) {
@@ -583,7 +574,7 @@ __global__ __launch_bounds__(LUT ? 512 : 256, LUT ? 4 : WA_MINW) void window_att
             }
             mx = fmaxf(mx, __shfl_xor(mx, 32));
 #pragma unroll
-            for (int i = 0; i < 25; ++i) f[i] = (WA_PROBE & 1) ? f[i] - mx : shift_exp_nonpos(f[i] - mx, x0r, nx0, 15);
+            for (int i = 0; i < 25; ++i) f[i] = shift_exp_nonpos(f[i] - mx, x0r, nx0, 15);
         }
         // torch-order row sum (n = 49), lane-local partials for l = 4*half + e
         float pl[4];
@@ -634,7 +625,7 @@ __global__ __launch_bounds__(LUT ? 512 : 256, LUT ? 4 : WA_MINW) void window_att
         auto s02 = __builtin_amdgcn_permlane32_swap(W[0], W[2], false, false);
         auto s13 = __builtin_amdgcn_permlane32_swap(W[1], W[3], false, false);
         const v4i outv = {(int)s02[0], (int)s02[1], (int)s13[0], (int)s13[1]};   // d = 16*half .. +16
-        if (qlive && (!(WA_PROBE & 4) || outv[0] == 0x12345678)) *reinterpret_cast<v4i *>(p.ctx + tok_off(q) * C + head * 32 + half * 16) = outv;
+        if (qlive) *reinterpret_cast<v4i *>(p.ctx + tok_off(q) * C + head * 32 + half * 16) = outv;
     }
     }
 }

@@ -48,7 +48,8 @@ enum {
     IVIT_ERR_NO_DEVICE = 4
 };
 
-/* 100 * major + minor.  105: ivit_avgpool_requant_scaled (addition); ivit_swin_params gains s_pool at its END — ivit_swin_create
+/* 100 * major + minor.  106: the debug entry that copied a plan's store scratch to the host is gone (only probe builds wrote it).
+ * 105: ivit_avgpool_requant_scaled (addition); ivit_swin_params gains s_pool at its END — ivit_swin_create
  * copies the whole struct, so a caller compiled against an older header must be rebuilt (its struct is shorter than the
  * library reads); windows 12 in ivit_window_attention_fused / ivit_swin_create.
  * 104 (round 6): ivit_set_cu_share, ivit_linear_i8_requant8_store16 (additions only).
@@ -60,7 +61,7 @@ enum {
  * fields exp_* at their END (added in 100 without a bump: a caller compiled against an older layout must be rebuilt).
  * Parameter structs are read field by field: ZERO-INITIALISE them (memset / = {0}) before filling — exp_aq == NULL (and
  * exp_nc == exp_tcount == exp_dmin == 0) selects the arithmetic Shiftmax, anything else is taken as device pointers.        */
-#define IVIT_VERSION 105
+#define IVIT_VERSION 106
 int ivit_version(void);
 const char *ivit_status_string(int status);
 
@@ -145,9 +146,6 @@ int ivit_linear_plan_create(ivit_handle h, const int8_t *w, const int32_t *bias,
 int ivit_linear_plan_destroy(ivit_linear_plan p);
 /* pipelined_ok: the persistent kernel may be used; single_fma_ok: its one-FMA requant form is exact.        */
 int ivit_linear_plan_query(ivit_linear_plan p, int *pipelined_ok, int *single_fma_ok);
-/* debug: copy the 8 KB behind the plan's store scratch to the host (kernel timeline traces of -DG3_TRACE builds;
- * zeros in production builds).  Synchronises the device.                                                     */
-int ivit_debug_plan_scratch(ivit_linear_plan p, void *host_dst, int nbytes);
 int ivit_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, int bits, void *out, int M);
 int ivit_linear_i8_requant_residual_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, ivit_dyadic dy_main,
                                             ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int M);

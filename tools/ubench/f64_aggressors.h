@@ -1,4 +1,4 @@
-// One-instruction-class aggressor kernels shared by pk_f64_hazard.hip (synthetic victim) and ln_s1_standalone.hip (the real
+// One-instruction-class aggressor kernels of pk_f64_hazard.hip (synthetic victim; round 5 also ran them beside the real
 // LayerNorm victim): every wave issues ONE kind of instruction in a tight loop, 16 per iteration.
 #pragma once
 #include <hip/hip_runtime.h>

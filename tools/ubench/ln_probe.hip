@@ -1,5 +1,5 @@
 // Stand-alone timing probe for layernorm_reg_kernel (ivit_layernorm.h): DeiT-S shape, random int16 rows.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DLN_ABLATE=n] tools/ubench/ln_probe.hip -o tools/ubench/ln_probe
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/ubench/ln_probe.hip -o tools/ubench/ln_probe
 #include "../../i-vit_amd/csrc/ivit_layernorm.h"
 #include <stdio.h>
 #include <stdlib.h>
