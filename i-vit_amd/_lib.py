@@ -184,6 +184,8 @@ SIGNATURES = {
     "ivit_vit_create": [_P, ctypes.POINTER(VitConfig), ctypes.POINTER(VitParams), _I, ctypes.POINTER(_P)],
     "ivit_vit_destroy": [_P],
     "ivit_vit_workspace_bytes": [_P, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
+    "ivit_vit_fused_mlp_blocks": [_P, _I, ctypes.POINTER(_I)],
+    "ivit_swin_fused_mlp_blocks": [_P, _I, ctypes.POINTER(_I * 4)],
     "ivit_vit_workspace_init": [_P, _P, ctypes.c_size_t, _I, _I],
     "ivit_vit_forward": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P],
     "ivit_vit_graph_create": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P, ctypes.POINTER(_P)],

@@ -16,7 +16,7 @@ struct ivit_vit_s {
     float *rowtab;                    // [depth][256][64] Shiftmax row tables (ivit_shiftmax_rowtable) or null
     std::vector<char> has_rowtab;     // per block: its scale's table lines fit 64 entries and the multipliers are in the fast range
     std::vector<ivit_linear_plan> plans;   // per block: qkv, proj, fc1, fc2 (frozen QuantLinear plans, ivit_linear_plan_create)
-    std::vector<ivit_mlp_plan> mlp_plans;  // per block: fused Mlp plan (D = 384), or null -> fc1 / ShiftGELU / fc2 launches
+    std::vector<ivit_mlp_plan> mlp_plans;  // per block: fused Mlp plan (D = 384 or 192), or null -> fc1 / ShiftGELU / fc2 launches
     int max_slices;
     std::vector<ivit_handle> slice_h; // one handle per internal stream
     std::vector<hipStream_t> streams;
@@ -64,6 +64,13 @@ SliceLayout slice_layout(const ivit_vit_s *m, int B) {
     }
     L.total = o;
     return L;
+}
+
+// THE rule for "this block's Mlp is one ivit_mlp_fused_planned launch at M tokens": run_slice, swin_run_slice and the
+// ivit_*_fused_mlp_blocks queries all ask here.  No token-count threshold: at width 192 the fused launch measured faster than
+// the three-launch chain at every size tried, 197 tokens (DeiT-T batch 1: 15.8 against 20.0 us) to 200 704 (profiles/README.md)
+inline bool mlp_plan_fuses(ivit_mlp_plan mp, ivit_dyadic res_main, ivit_dyadic res_res, long long /*M*/) {
+    return mp && fabs(res_main.m * res_main.r) < RQ_FAST_CLIM && fabs(res_res.m * res_res.r) < RQ_FAST_CLIM;
 }
 
 inline int slice_begin(int batch, int nslices, int i) { return (int)(((long long)batch * i) / nslices); }
@@ -129,8 +136,7 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         // attn.proj + qact2 with the identity branch, then norm2 + qact3 and the Mlp.  norm2 rides in the HEAD of the fused Mlp's launch
         // (ivit_layernorm_mlp_fused_planned) where that kernel takes the shape; in the tail of the proj launch it measured slower
         // (profiles/README.md)
-        const bool mlp_fast = m->mlp_plans[i] && fabs(b.res2_main.m * b.res2_main.r) < RQ_FAST_CLIM &&
-                              fabs(b.res2_res.m * b.res2_res.r) < RQ_FAST_CLIM;
+        const bool mlp_fast = mlp_plan_fuses(m->mlp_plans[i], b.res2_main, b.res2_res, M);
         RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, M));
         { int16_t *t = x; x = y; y = t; }
         rc = mlp_fast ? ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8,
@@ -219,7 +225,7 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
             m->plans.push_back(pl);
         }
         ivit_mlp_plan mp = nullptr;
-        if (D == MLP_C && Hd == MLP_HD && ivit_mlp_plan_create(h, m->plans[4 * i + 2], m->plans[4 * i + 3], &mp) != IVIT_OK) mp = nullptr;
+        if (((D == MLP_C && Hd == MLP_HD) || (D == M192_C && Hd == M192_HD)) && ivit_mlp_plan_create(h, m->plans[4 * i + 2], m->plans[4 * i + 3], &mp) != IVIT_OK) mp = nullptr;
         m->mlp_plans.push_back(mp);
     }
     if (max_slices > 1) {
@@ -264,6 +270,16 @@ int ivit_vit_workspace_bytes(ivit_vit m, int batch, int nslices, size_t *bytes) 
     if (!m) return IVIT_ERR_INVALID;
     REQUIRE(m->h, bytes && batch > 0 && nslices >= 1 && nslices <= m->max_slices && nslices <= batch, "bad arguments");
     *bytes = slice_layout(m, max_slice(batch, nslices)).total * (size_t)nslices;
+    return IVIT_OK;
+}
+
+int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, blocks && batch > 0, "bad arguments");
+    int n = 0;
+    for (int i = 0; i < m->cfg.depth; ++i)
+        n += mlp_plan_fuses(m->mlp_plans[i], m->blocks[i].res2_main, m->blocks[i].res2_res, (long long)batch * m->T);
+    *blocks = n;
     return IVIT_OK;
 }
 
@@ -366,8 +382,8 @@ struct ivit_swin_s {
     int grid, nblocks;
     ivit_dyadic dy_qact1_host;        // host copy of prm.dy_qact1[0]
     bool fused_mlp;                   // stage-0 Mlp in one kernel (ivit_mlp_fused)
-    std::vector<ivit_linear_plan> mlp_lin;   // per block: fc1, fc2 plans of the C = 384 stage (null elsewhere)
-    std::vector<ivit_mlp_plan> mlp_plans;    // per block: fused Mlp plan (C = 384, hidden 1536) or null
+    std::vector<ivit_linear_plan> mlp_lin;   // per block: fc1, fc2 plans of the C = 384 and C = 192 stages (null elsewhere)
+    std::vector<ivit_mlp_plan> mlp_plans;    // per block: fused Mlp plan (C = 384 / hidden 1536, C = 192 / hidden 768) or null
     std::vector<ivit_linear_plan> lin_plans; // per block: qkv, proj plans prepared for gemm_ws_qkv_kernel where C == 384, else null
     int8_t *gelu_tab;                 // [nblocks][65536]
     int max_slices;
@@ -406,6 +422,12 @@ int swin_ln(const ivit_swin_s *m, ivit_handle h, const int16_t *x, long long M, 
             int L, bool token_order, int8_t *out8) {
     if (token_order) return ivit_layernorm_tokenorder_requant(h, x, M, C, s_in, n.bias_int, n.sc, n.dy, L, out8);
     return ivit_layernorm_requant(h, x, M, C, C, s_in, n.bias_int, n.sc, n.dy, out8);
+}
+
+// how block `bi` (width C) issues its Mlp at M tokens: 0 = fc1 / ShiftGELU / fc2, 1 = ivit_mlp_fused (narrow stage), 2 = ivit_mlp_fused_planned
+int swin_mlp_mode(const ivit_swin_s *m, int bi, int C, long long M) {
+    if (C == 96 && m->cfg.mlp_ratio == 4 && m->fused_mlp) return 1;
+    return mlp_plan_fuses(m->mlp_plans[bi], m->blocks[bi].res2_main, m->blocks[bi].res2_res, M) ? 2 : 0;
 }
 
 int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, char *ws, int32_t *logits) {
@@ -455,15 +477,14 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             if (lp[1]) RUN(ivit_linear_i8_requant_residual_planned(h, lp[1], ctx, b.res1_main, b.res1_res, x, y, (int)M));
             else RUN(ivit_linear_i8_requant_residual(h, ctx, b.proj.w, b.proj.b, b.proj.dy, b.res1_main, b.res1_res, x, y, (int)M, C, C));
             { int16_t *t = x; x = y; y = t; }
-            const bool mlp384 = m->mlp_plans[bi] && fabs(b.res2_main.m * b.res2_main.r) < RQ_FAST_CLIM &&
-                                fabs(b.res2_res.m * b.res2_res.r) < RQ_FAST_CLIM;
+            const int mlp_mode = swin_mlp_mode(m, bi, C, M);
             // norm2 is a launch of its own in every stage.  (In the head of the C = 384 stage's fused Mlp it measured slower: Swin-T b256,
             // two slices, 4.76 against 4.70 ms same-box; the LayerNorm launch of one slice overlaps the other slice's kernels)
             RUN(swin_ln(m, h, x, M, C, b.s_mid, b.n2, L, li == 0, a8));
-            if (C == 96 && c.mlp_ratio == 4 && m->fused_mlp) {     // narrow stage: hidden tensor stays in LDS
+            if (mlp_mode == 1) {                                    // narrow stage: hidden tensor stays in LDS
                 RUN(ivit_mlp_fused(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, m->gelu_tab + (size_t)bi * 65536, b.fc2.w, b.fc2.b,
                                    b.fc2.dy, b.res2_main, b.res2_res, x, y, M, C, 4 * C));
-            } else if (mlp384) {                                    // C = 384 stage: weights streamed, hidden tile in LDS
+            } else if (mlp_mode == 2) {                             // C = 192 and C = 384 stages: weights streamed, hidden tile in LDS
                 RUN(ivit_mlp_fused_planned(h, m->mlp_plans[bi], a8, m->gelu_tab + (size_t)bi * 65536, b.res2_main, b.res2_res, x, y, M));
             } else {
                 RUN(ivit_linear_i8_requant(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, 8, h8, (int)M, c.mlp_ratio * C, C));
@@ -575,7 +596,7 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
         int rc = ivit_shiftgelu_build_table(h, m->blocks[i].s_gelu, m->blocks[i].dy_gelu, m->gelu_tab + (size_t)i * 65536);
         if (rc != IVIT_OK) { ivit_swin_destroy(m); return rc; }
     }
-    {   // fused Mlp plans for the C = 384 stage (hidden 1536)
+    {   // fused Mlp plans for the C = 192 (hidden 768) and C = 384 (hidden 1536) stages
         int bi = 0;
         for (int li = 0; li < cfg->num_layers; ++li)
             for (int bj = 0; bj < cfg->depths[li]; ++bj, ++bi) {
@@ -583,9 +604,9 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
                 ivit_linear_plan p1 = nullptr, p2 = nullptr;
                 ivit_mlp_plan mp = nullptr;
                 const ivit_swin_block &b = m->blocks[bi];
-                if (C == MLP_C && cfg->mlp_ratio * C == MLP_HD &&
-                    ivit_linear_plan_create(h, b.fc1.w, b.fc1.b, b.fc1.dy, MLP_HD, MLP_C, &p1) == IVIT_OK &&
-                    ivit_linear_plan_create(h, b.fc2.w, b.fc2.b, b.fc2.dy, MLP_C, MLP_HD, &p2) == IVIT_OK) {
+                if ((C == MLP_C || C == M192_C) && cfg->mlp_ratio == 4 &&
+                    ivit_linear_plan_create(h, b.fc1.w, b.fc1.b, b.fc1.dy, 4 * C, C, &p1) == IVIT_OK &&
+                    ivit_linear_plan_create(h, b.fc2.w, b.fc2.b, b.fc2.dy, C, 4 * C, &p2) == IVIT_OK) {
                     if (ivit_mlp_plan_create(h, p1, p2, &mp) != IVIT_OK) mp = nullptr;
                 }
                 m->mlp_lin.push_back(p1);
@@ -631,6 +652,20 @@ int ivit_swin_workspace_bytes(ivit_swin m, int batch, int nslices, size_t *bytes
     if (!m) return IVIT_ERR_INVALID;
     REQUIRE(m->h, bytes && batch > 0 && nslices >= 1 && nslices <= m->max_slices && nslices <= batch, "bad arguments");
     *bytes = swin_layout(m, max_slice(batch, nslices)).total * (size_t)nslices;
+    return IVIT_OK;
+}
+
+int ivit_swin_fused_mlp_blocks(ivit_swin m, int batch, int blocks_per_stage[4]) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, blocks_per_stage && batch > 0, "bad arguments");
+    int bi = 0;
+    for (int li = 0; li < 4; ++li) {
+        blocks_per_stage[li] = 0;
+        if (li >= m->cfg.num_layers) continue;
+        const int res = m->grid >> li;
+        for (int bj = 0; bj < m->cfg.depths[li]; ++bj, ++bi)
+            blocks_per_stage[li] += swin_mlp_mode(m, bi, m->cfg.embed_dim << li, (long long)batch * res * res) != 0;
+    }
     return IVIT_OK;
 }
 

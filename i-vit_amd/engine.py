@@ -148,7 +148,7 @@ class ViTEngine:
         # native runner (forward) holds its own plans, and an engine that only runs forward() no longer keeps a second
         # copy of the fragment-ordered Mlp weights (14 MB for DeiT-S).  use_plans = False issues the unplanned kernels
         self.use_plans = True
-        self.use_fused_mlp = True       # forward_ops: ivit_mlp_fused_planned where a fused plan exists (D = 384)
+        self.use_fused_mlp = True       # forward_ops: ivit_mlp_fused_planned where a fused plan exists (D = 384 or 192)
         self._plans = {}
         self._mlp_plans = {}
         self._build_native()

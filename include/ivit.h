@@ -48,7 +48,9 @@ enum {
     IVIT_ERR_NO_DEVICE = 4
 };
 
-/* 100 * major + minor.  106: the debug entry that copied a plan's store scratch to the host is gone (only probe builds wrote it).
+/* 100 * major + minor.  107: ivit_mlp_plan_create also takes 192 -> 768 -> 192 (DeiT-Tiny, Swin stage 1);
+ * ivit_vit_fused_mlp_blocks, ivit_swin_fused_mlp_blocks (additions only).
+ * 106: the debug entry that copied a plan's store scratch to the host is gone (only probe builds wrote it).
  * 105: ivit_avgpool_requant_scaled (addition); ivit_swin_params gains s_pool at its END — ivit_swin_create
  * copies the whole struct, so a caller compiled against an older header must be rebuilt (its struct is shorter than the
  * library reads); windows 12 in ivit_window_attention_fused / ivit_swin_create.
@@ -61,7 +63,7 @@ enum {
  * fields exp_* at their END (added in 100 without a bump: a caller compiled against an older layout must be rebuilt).
  * Parameter structs are read field by field: ZERO-INITIALISE them (memset / = {0}) before filling — exp_aq == NULL (and
  * exp_nc == exp_tcount == exp_dmin == 0) selects the arithmetic Shiftmax, anything else is taken as device pointers.        */
-#define IVIT_VERSION 106
+#define IVIT_VERSION 107
 int ivit_version(void);
 const char *ivit_status_string(int status);
 
@@ -356,6 +358,9 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
 int ivit_vit_destroy(ivit_vit m);
 /* Caller-provided workspace: bytes for `batch` images cut into `nslices` slices.               */
 int ivit_vit_workspace_bytes(ivit_vit m, int batch, int nslices, size_t *bytes);
+/* How many blocks of a forward of `batch` images in ONE slice issue their Mlp as a single launch (the fused kernels of
+ * ivit_mlp_plan_create); the other blocks run fc1 / ShiftGELU / fc2 as three.  Decided by the rule the forward itself applies. */
+int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks);
 /* Must run once per (workspace, batch, nslices) before the first forward (zeroes the padded
  * key columns of the transposed V buffers); asynchronous on the handle's stream.               */
 int ivit_vit_workspace_init(ivit_vit m, void *workspace, size_t bytes, int batch, int nslices);
@@ -423,6 +428,10 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
                      int max_slices, ivit_swin *out);
 int ivit_swin_destroy(ivit_swin m);
 int ivit_swin_workspace_bytes(ivit_swin m, int batch, int nslices, size_t *bytes);
+/* Per stage: how many blocks of a forward of `batch` images in ONE slice issue their Mlp as a single launch (ivit_mlp_fused in
+ * the C = 96 stage, ivit_mlp_fused_planned in the C = 192 and C = 384 stages).  Decided by the rule the forward itself applies;
+ * stages the model does not have report 0.                                                                             */
+int ivit_swin_fused_mlp_blocks(ivit_swin m, int batch, int blocks_per_stage[4]);
 int ivit_swin_forward(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace,
                       size_t bytes, int32_t *logits);
 int ivit_swin_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace,
@@ -493,19 +502,22 @@ int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32
                    const int8_t *gelu_table, const int8_t *w2, const int32_t *b2, const ivit_dyadic *dy2,
                    ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M,
                    int C, int hidden);
-/* The same chain for C = 384, hidden = 1536 (DeiT-S, Swin stage 2) on frozen linear plans: both weight matrices are
- * re-laid-out once in MFMA-fragment order and stream L2 -> registers, the hidden tile of 64 tokens lives in LDS between
- * fc1, the ShiftGELU table pass and fc2 (csrc/ivit_mlp.h).  The linear plans are borrowed and must outlive the Mlp plan.
- * IVIT_ERR_UNSUPPORTED for other shapes, for plans whose requant bound is not provable, and (at call time) for
+/* The same chain on frozen linear plans, at two widths: C = 384, hidden = 1536 (DeiT-S, Swin stage 2) and C = 192,
+ * hidden = 768 (DeiT-Tiny, Swin-T / S stage 1).  Both weight matrices are re-laid-out once in MFMA-fragment order and
+ * stream L2 -> registers, the hidden tile of a unit of up to 80 tokens lives in LDS between fc1, the ShiftGELU table pass
+ * and fc2 (csrc/ivit_mlp.h, csrc/ivit_mlp_rs.h; csrc/ivit_mlp192.h: two four-wave workgroups per CU).  x, residual and out
+ * are [M, C] of the plan's width.  The linear plans are borrowed and must outlive the Mlp plan.
+ * IVIT_ERR_UNSUPPORTED for other shapes (fc1 must be [4C x C] and fc2 [C x 4C] with C = 384 or 192), for plans whose requant bound is not provable, and (at call time) for
  * residual multipliers >= 2^9: callers then run the unfused chain.  Replaces layers_quant.py:144-153 +
  * vit_quant.py:141-142 (swin_quant.py:296-300) like ivit_mlp_fused.                                        */
 typedef struct ivit_mlp_plan_s *ivit_mlp_plan;
 int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan fc2, ivit_mlp_plan *out);
 int ivit_mlp_plan_destroy(ivit_mlp_plan p);
-/* Tuning / test switch: which of the plan's two kernels ivit_mlp_fused_planned launches.  0 = by shape (the default:
+/* Tuning / test switch: which of a width-384 plan's two kernels ivit_mlp_fused_planned launches.  0 = by shape (the default:
  * the role-split kernel of csrc/ivit_mlp_rs.h from two 80-token units per CU on, the lock-step kernel of csrc/ivit_mlp.h
  * below that), 1 = lock-step, 2 = role-split.  Both compute the same integers (layers_quant.py:144-153).  NOT safe to call
- * while another thread or stream is inside ivit_mlp_fused_planned on the same plan: it rewrites a field the launch reads.  */
+ * while another thread or stream is inside ivit_mlp_fused_planned on the same plan: it rewrites a field the launch reads.
+ * A width-192 plan has the lock-step kernel only: 0 and 1 succeed, 2 returns IVIT_ERR_UNSUPPORTED and changes nothing.  */
 int ivit_mlp_plan_select(ivit_mlp_plan p, int kernel);
 int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, const int8_t *gelu_table,
                            ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual, int16_t *out,
@@ -514,7 +526,7 @@ int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, cons
  * normalises the rows it is going to multiply (x16 [M, 384], the block's 16-bit stream, which is also the identity branch; scale /
  * bias_int / sc / ln_dy as for ivit_layernorm_requant) into scratch8 [M, 384] and reads its activation tiles from there.  out ==
  * ivit_layernorm_requant followed by ivit_mlp_fused_planned.  IVIT_ERR_UNSUPPORTED (nothing launched) where ivit_mlp_fused_planned is,
- * and where the launch would run on the lock-step kernel (fewer than two units per CU).                                        */
+ * where the launch would run on the lock-step kernel (fewer than two units per CU), and on a width-192 plan.                      */
 int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int,
                                      const float *sc, const ivit_dyadic *ln_dy, int8_t *scratch8, const int8_t *gelu_table,
                                      ivit_dyadic dy_main, ivit_dyadic dy_res, int16_t *out, int64_t M);
