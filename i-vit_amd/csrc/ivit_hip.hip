@@ -20,7 +20,6 @@
 #include "ivit_swin.h"
 #include "ivit_mlp.h"
 #include "ivit_mlp_rs.h"
-#include "ivit_mlp192.h"
 #include "ivit_swin_mlp_rs.h"
 #include "ivit_gemm_ws.h"
 #include "ivit_swin12.h"
@@ -777,72 +776,24 @@ int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, con
 
 }  // extern "C"
 
-// ---- fused Mlp (+ residual QuantAct) for D = 384, hidden = 1536 (ivit_mlp.h, ivit_mlp_rs.h) and D = 192, hidden = 768 (ivit_mlp192.h)
+// ---- fused Mlp (+ residual QuantAct) for D = 384, hidden = 1536 (ivit_mlp.h, ivit_mlp_rs.h) and D = 192, hidden = 768 (ivit_mlp.h)
 struct ivit_mlp_plan_s {
     ivit_linear_plan fc1, fc2;      // borrowed: must outlive this plan
     int width;                      // 384 or 192
     v4i *w1f, *w2f;                 // fragment-ordered copies of the two weight matrices (one allocation)
-    v4i *w1r, *w2r;                 // the same in the role-split kernel's order (ivit_mlp_rs.h), same allocation
+    v4i *w1r, *w2r;                 // width 384: the same in the role-split kernel's order (ivit_mlp_rs.h), same allocation; else null
     int fma;                        // both layers: one fused rounding == the reference's two
-    int kernel;                     // 0 = by shape, 1 = lock-step (mlp384_kernel), 2 = role-split (mlp384rs_kernel): ivit_mlp_plan_select
+    int kernel;                     // 0 = by shape, 1 = lock-step (mlp384_kernel / mlp192_kernel), 2 = role-split (mlp384rs_kernel): ivit_mlp_plan_select
     int device;
 };
-
-// width 192: one kernel (mlp192_kernel), one fragment-ordered copy of each weight matrix
-static int mlp192_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan fc2, ivit_mlp_plan *out) {
-    const size_t wbytes = (size_t)M192_C * M192_HD;
-    char *dev = nullptr;
-    if (hipMalloc((void **)&dev, 2 * wbytes) != hipSuccess) { snprintf(h->err, sizeof(h->err), "%s: hipMalloc failed", __func__); return IVIT_ERR_HIP; }
-    mlp192_swizzle_kernel<<<144, 256, 0, h->stream>>>(fc1->w, M192_HD, M192_C, (v4i *)dev);
-    mlp192_swizzle_kernel<<<144, 256, 0, h->stream>>>(fc2->w, M192_C, M192_HD, (v4i *)(dev + wbytes));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // plan creation is a build-time call
-    const int fma = fc1->single_fma_ok && fc2->single_fma_ok;
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(fma ? (const void *)mlp192_kernel<true> : (const void *)mlp192_kernel<false>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, M192_SMEM);
-    ivit_mlp_plan_s *p = e == hipSuccess ? new (std::nothrow) ivit_mlp_plan_s() : nullptr;
-    if (!p) {
-        (void)hipFree(dev);
-        snprintf(h->err, sizeof(h->err), "%s: %s", __func__, e == hipSuccess ? "out of memory" : hipGetErrorString(e));
-        return IVIT_ERR_HIP;
-    }
-    p->fc1 = fc1; p->fc2 = fc2; p->width = M192_C; p->w1f = (v4i *)dev; p->w2f = (v4i *)(dev + wbytes);
-    p->w1r = p->w2r = nullptr;
-    p->fma = fma;
-    p->kernel = 0;
-    p->device = h->device;
-    *out = p;
-    return IVIT_OK;
-}
-
-// mlp192_kernel: two workgroups per CU of the handle's share; workgroup b walks the tile range [T b / G, T (b + 1) / G)
-static int mlp192_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, const int8_t *gelu_table, ivit_dyadic dy_main,
-                         ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M) {
-    Mlp192Args a;
-    a.x = x; a.w1f = p->w1f; a.w2f = p->w2f; a.b1 = p->fc1->bias_eff; a.b2 = p->fc2->bias_eff;
-    a.cq1 = p->fc1->cq; a.cq2 = p->fc2->cq; a.tab = gelu_table; a.residual = residual; a.out = out;
-    a.cm = dy_main.m * dy_main.r; a.cr = dy_res.m * dy_res.r; a.M = M;
-    if (!(fabs(a.cm) < RQ_FAST_CLIM && fabs(a.cr) < RQ_FAST_CLIM)) {
-        snprintf(h->err, sizeof(h->err), "%s: residual multipliers out of the fast range", __func__);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    REQUIRE(h, h->device == p->device, "plan and handle live on different devices");
-    const long long ntiles = (M + 15) / 16, slots = (long long)M192_WG_PER_CU * persistent_cus(h);
-    const unsigned grid = (unsigned)(ntiles < slots ? ntiles : slots);
-    if (p->fma) mlp192_kernel<true><<<grid, M192_THREADS, M192_SMEM, h->stream>>>(a);
-    else mlp192_kernel<false><<<grid, M192_THREADS, M192_SMEM, h->stream>>>(a);
-    LAUNCH_CHECK(h);
-    return IVIT_OK;
-}
 
 extern "C" {
 
 int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan fc2, ivit_mlp_plan *out) {
     CHECK_H(h);
     REQUIRE(h, fc1 && fc2 && out, "null argument");
-    const bool w384 = fc1->K == MLP_C && fc1->N == MLP_HD && fc2->K == MLP_HD && fc2->N == MLP_C;
-    const bool w192 = fc1->K == M192_C && fc1->N == M192_HD && fc2->K == M192_HD && fc2->N == M192_C;
+    const bool w384 = fc1->K == Mlp384Geo::C && fc1->N == Mlp384Geo::HD && fc2->K == Mlp384Geo::HD && fc2->N == Mlp384Geo::C;
+    const bool w192 = fc1->K == Mlp192Geo::C && fc1->N == Mlp192Geo::HD && fc2->K == Mlp192Geo::HD && fc2->N == Mlp192Geo::C;
     if (!w384 && !w192) {
         snprintf(h->err, sizeof(h->err), "%s: built for 384 -> 1536 -> 384 and 192 -> 768 -> 192", __func__);
         return IVIT_ERR_UNSUPPORTED;
@@ -851,47 +802,49 @@ int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan f
         snprintf(h->err, sizeof(h->err), "%s: |(acc + bias) * c| < 2^31 not provable for these weights", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
-    if (w192) return mlp192_plan_create(h, fc1, fc2, out);
-    const size_t wbytes = (size_t)MLP_C * MLP_HD;
+    // one fragment-ordered copy of each weight matrix for the lock-step kernel; width 384: two more for the role-split kernel
+    const size_t wbytes = (size_t)fc1->K * fc1->N;
     char *dev = nullptr;
-    if (hipMalloc((void **)&dev, 4 * wbytes) != hipSuccess) { snprintf(h->err, sizeof(h->err), "%s: hipMalloc failed", __func__); return IVIT_ERR_HIP; }
-    mlp_swizzle_kernel<<<256, 256, 0, h->stream>>>(fc1->w, MLP_HD, MLP_C, (v4i *)dev);
-    mlp_swizzle_kernel<<<256, 256, 0, h->stream>>>(fc2->w, MLP_C, MLP_HD, (v4i *)(dev + wbytes));
-    rs_swizzle_w1_kernel<<<144, 256, 0, h->stream>>>(fc1->w, (v4i *)(dev + 2 * wbytes));
-    rs_swizzle_w2_kernel<<<144, 256, 0, h->stream>>>(fc2->w, (v4i *)(dev + 3 * wbytes));
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {     // plan creation is a build-time call
+    if (hipMalloc((void **)&dev, (w384 ? 4 : 2) * wbytes) != hipSuccess) { snprintf(h->err, sizeof(h->err), "%s: hipMalloc failed", __func__); return IVIT_ERR_HIP; }
+    if (w384) {
+        mlp_swizzle_kernel<<<256, 256, 0, h->stream>>>(fc1->w, fc1->N, fc1->K, (v4i *)dev);
+        mlp_swizzle_kernel<<<256, 256, 0, h->stream>>>(fc2->w, fc2->N, fc2->K, (v4i *)(dev + wbytes));
+        rs_swizzle_w1_kernel<<<144, 256, 0, h->stream>>>(fc1->w, (v4i *)(dev + 2 * wbytes));
+        rs_swizzle_w2_kernel<<<144, 256, 0, h->stream>>>(fc2->w, (v4i *)(dev + 3 * wbytes));
+    } else {
+        mlp192_swizzle_kernel<<<144, 256, 0, h->stream>>>(fc1->w, fc1->N, fc1->K, (v4i *)dev);
+        mlp192_swizzle_kernel<<<144, 256, 0, h->stream>>>(fc2->w, fc2->N, fc2->K, (v4i *)(dev + wbytes));
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // plan creation is a build-time call
+    // the dynamic-LDS attributes of the kernels this plan will launch: once, here
+    const bool fma = fc1->single_fma_ok && fc2->single_fma_ok;
+    auto lds = [&](const void *fn, int bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
+    if (w384) {
+        lds(fma ? (const void *)mlp384_kernel<true> : (const void *)mlp384_kernel<false>, Mlp384Geo::SMEM);
+        lds(fma ? (const void *)mlp384rs_kernel<true> : (const void *)mlp384rs_kernel<false>, RS_SMEM);
+        lds(fma ? (const void *)mlp384rs_kernel<true, 1> : (const void *)mlp384rs_kernel<false, 1>, RS_SMEM);
+    } else {
+        lds(fma ? (const void *)mlp192_kernel<true> : (const void *)mlp192_kernel<false>, Mlp192Geo::SMEM);
+    }
+    ivit_mlp_plan_s *p = e == hipSuccess ? new (std::nothrow) ivit_mlp_plan_s() : nullptr;
+    if (!p) {
         (void)hipFree(dev);
-        snprintf(h->err, sizeof(h->err), "%s: HIP error", __func__);
+        snprintf(h->err, sizeof(h->err), "%s: %s", __func__, e == hipSuccess ? "out of memory" : hipGetErrorString(e));
         return IVIT_ERR_HIP;
     }
-    ivit_mlp_plan_s *p = new (std::nothrow) ivit_mlp_plan_s();
-    if (!p) { (void)hipFree(dev); return IVIT_ERR_HIP; }
-    p->fc1 = fc1; p->fc2 = fc2; p->width = MLP_C; p->w1f = (v4i *)dev; p->w2f = (v4i *)(dev + wbytes);
-    p->w1r = (v4i *)(dev + 2 * wbytes); p->w2r = (v4i *)(dev + 3 * wbytes);
-    p->fma = fc1->single_fma_ok && fc2->single_fma_ok;
+    p->fc1 = fc1; p->fc2 = fc2; p->width = fc1->K; p->w1f = (v4i *)dev; p->w2f = (v4i *)(dev + wbytes);
+    p->w1r = w384 ? (v4i *)(dev + 2 * wbytes) : nullptr; p->w2r = w384 ? (v4i *)(dev + 3 * wbytes) : nullptr;
+    p->fma = fma;
     p->kernel = 0;
     p->device = h->device;
-    {   // the dynamic-LDS attributes of the kernels this plan will launch: once, here
-        const void *fn = p->fma ? (const void *)mlp384_kernel<true> : (const void *)mlp384_kernel<false>;
-        const void *fr = p->fma ? (const void *)mlp384rs_kernel<true> : (const void *)mlp384rs_kernel<false>;
-        const void *fl = p->fma ? (const void *)mlp384rs_kernel<true, 1> : (const void *)mlp384rs_kernel<false, 1>;
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute(fr, hipFuncAttributeMaxDynamicSharedMemorySize, RS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute(fl, hipFuncAttributeMaxDynamicSharedMemorySize, RS_SMEM);
-        if (e != hipSuccess) {
-            snprintf(h->err, sizeof(h->err), "%s: attr: %s", __func__, hipGetErrorString(e));
-            (void)hipFree(dev);
-            delete p;
-            return IVIT_ERR_HIP;
-        }
-    }
     *out = p;
     return IVIT_OK;
 }
 
 int ivit_mlp_plan_select(ivit_mlp_plan p, int kernel) {
     if (!p || kernel < 0 || kernel > 2) return IVIT_ERR_INVALID;
-    if (p->width == M192_C && kernel == 2) return IVIT_ERR_UNSUPPORTED;      // width 192 has the lock-step kernel only
+    if (p->width == Mlp192Geo::C && kernel == 2) return IVIT_ERR_UNSUPPORTED;      // width 192 has the lock-step kernel only
     p->kernel = kernel;
     return IVIT_OK;
 }
@@ -918,9 +871,21 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
         return IVIT_ERR_UNSUPPORTED;
     }
     REQUIRE(h, h->device == p->device, "plan and handle live on different devices");
-    // one workgroup per CU.  64-token units round-robin unless cutting contiguous tile ranges into units of <= 5 tiles
+    const long long ntiles = (M + 15) / 16;
+    if (p->width == Mlp192Geo::C) {
+        // two workgroups per CU of the handle's share; workgroup b walks the tile range [T b / G, T (b + 1) / G).  Lock-step only
+        // (ivit_layernorm_mlp_fused_planned refuses this width before it comes here)
+        const long long slots = (long long)Mlp192Geo::WG_PER_CU * persistent_cus(h);
+        const unsigned grid = (unsigned)(ntiles < slots ? ntiles : slots);
+        a.balanced = 1;
+        if (p->fma) mlp192_kernel<true><<<grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, h->stream>>>(a);
+        else mlp192_kernel<false><<<grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, h->stream>>>(a);
+        LAUNCH_CHECK(h);
+        return IVIT_OK;
+    }
+    // width 384: one workgroup per CU.  64-token units round-robin unless cutting contiguous tile ranges into units of <= 5 tiles
     // saves a whole round (a unit costs a pass over both weight matrices whatever its size)
-    const long long ntiles = (M + 15) / 16, nunits = (ntiles + MLP_TT - 2) / (MLP_TT - 1);
+    const long long nunits = (ntiles + MLP_TT - 2) / (MLP_TT - 1);
     const unsigned grid = (unsigned)(nunits < persistent_cus(h) ? nunits : persistent_cus(h));
     const long long rounds_fixed = (nunits + grid - 1) / grid, rounds_bal = (ntiles + (long long)MLP_TT * grid - 1) / ((long long)MLP_TT * grid);
     a.balanced = rounds_bal < rounds_fixed;
@@ -949,7 +914,6 @@ int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, cons
                            ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M) {
     CHECK_H(h);
     REQUIRE(h, p && x && gelu_table && residual && out && M > 0, "bad arguments");
-    if (p->width == M192_C) return mlp192_launch(h, p, x, gelu_table, dy_main, dy_res, residual, out, M);
     return mlp_fused_launch(h, p, x, gelu_table, dy_main, dy_res, residual, out, M, 0.f, nullptr, nullptr, nullptr);
 }
 

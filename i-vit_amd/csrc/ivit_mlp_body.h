@@ -1,138 +1,60 @@
-// ivit_mlp192.h — Mlp.forward + the block's residual QuantAct as ONE kernel at width 192 (DeiT-Tiny: every block; Swin-T / S: stage 1):
-//   fc1 -> qact_gelu (8 bit) -> ShiftGELU -> qact1 (8 bit) -> fc2 -> qact2 (16 bit) -> qact4(+identity) (16 bit)
-// (models/layers_quant.py:144-153, then vit_quant.py:141-142 / swin_quant.py:296-300).  The scheme of ivit_mlp.h (weights in
-// MFMA-fragment order streamed L2 -> registers, the hidden tile of a unit in LDS only, no barrier inside the GEMM phases)
-// re-cut for a 768-byte hidden row:
-//
-//   * a unit is up to 80 tokens: hidden 80 x 768 B = 60 KB + activations 80 x 192 B = 15 KB + table lines 2 KB = 77 KB of
-//     LDS, so TWO workgroups of four waves share a CU (154 KB of 160) and one of them multiplies while the other is in its
-//     ShiftGELU phase or waits at a barrier;
-//   * one pass over both weight matrices is 288 KB (1.18 MB at width 384), i.e. 3.7 KB per token of a full unit against
-//     14.7 KB there;
-//   * fc2's 12 output-channel tiles split as 4 waves x 3 tiles, fc1's 48 as 4 waves x 4 chunks of 3: the register picture
-//     of a wave (3 channel tiles x 5 token tiles of accumulators) is the one mlp384_kernel has at eight waves.
-//
-// Shapes: v_mfma_i32_16x16x64_i8, weights as the A operand (rows = channels), activations as B (columns = tokens): a lane
-// holds 4 consecutive channels of one token per accumulator, which pack into one dword.  LDS images are K-blocked,
-// [64-column block][80 tokens][64 B], with the chunk permutation mlp_phi of ivit_mlp.h (conflict-free ds_read_b128).
-#pragma once
-#include <type_traits>
-#include "ivit_device.h"
-#include "ivit_mlp.h"
-
-#define M192_C 192
-#define M192_HD 768
-#define M192_TT 5                                 // token tiles (of 16) a unit may have: 4 or 5
-#define M192_WAVES 4
-#define M192_NJ 3                                 // channel tiles per wave and step
-#define M192_THREADS (M192_WAVES * 64)
-#define M192_KS1 (M192_C / 64)                    // 3 column steps of fc1
-#define M192_KS2 (M192_HD / 64)                   // 12 column steps of fc2
-#define M192_KBLK (M192_TT * 16 * 64)             // one 64-column block of an LDS image: [80 tokens][64 B]
-#define M192_SH 0                                 // hidden tile [12][80][64 B]
-#define M192_SA (M192_KS2 * M192_KBLK)            // activation tile [3][80][64 B]
-#define M192_STAB (M192_SA + M192_KS1 * M192_KBLK)    // one ShiftGELU table line (256 B) per half-wave
-#define M192_SMEM (M192_STAB + 2 * M192_WAVES * 256)
-#define M192_WG_PER_CU 2
-#define M192_WD 3                                 // weight fragments in flight ahead of the MFMAs that consume them
-
-struct Mlp192Args {
-    const int8_t *x;          // [M, 192] int8 (LayerNorm + requant output)
-    const v4i *w1f, *w2f;     // fragment-ordered weights (mlp192_swizzle_kernel)
-    const int32_t *b1, *b2;   // biases (never null: the plans' bias_eff)
-    const double *cq1, *cq2;  // per-channel c = m * 2^-e
-    const int8_t *tab;        // ShiftGELU(+requant) table [256 maxima][256 values]
-    const int16_t *residual;  // [M, 192] identity branch
-    int16_t *out;             // [M, 192]
-    double cm, cr;            // qact4: main and identity multipliers
-    long long M;
-};
-
-// weights [N][K] int8 -> fragments of 64 lanes x 16 B, lane l = W[ct*16 + (l & 15)][ks*64 + (l >> 4)*16 ...], in the order the
-// kernel consumes them: fragment f = step * 12 + wave * 3 + j, step = chunk * (K / 64) + ks, channel tile
-// ct = wave * T + chunk * 3 + j with T = N / 16 / 4 tiles per wave.  What the four waves request in one step is one
-// contiguous 12 KB window.
-__global__ __launch_bounds__(256) void mlp192_swizzle_kernel(const int8_t *__restrict__ w, int N, int K, v4i *__restrict__ wf) {
-    const int nks = K >> 6, T = (N >> 4) / M192_WAVES;
-    const long long total = (long long)(N >> 4) * nks * 64;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int l = (int)(i & 63);
-        const int f = (int)(i >> 6), step = f / (M192_NJ * M192_WAVES), r = f - step * (M192_NJ * M192_WAVES);
-        const int chunk = step / nks, ks = step - chunk * nks, ct = (r / M192_NJ) * T + chunk * M192_NJ + (r % M192_NJ);
-        wf[i] = *reinterpret_cast<const v4i *>(w + (long long)(ct * 16 + (l & 15)) * K + ks * 64 + (l >> 4) * 16);
-    }
-}
-
-// FMA: both plans prove |z * m| < 2^53 (one fused rounding == the reference's two), else multiply and add separately.
-// Both plans prove |z * c| < 2^31 (the host refuses the kernel otherwise); |cm|, |cr| < 2^9 (host-checked) for rq_fast.
-//
-// Units: the token axis is cut into tiles of 16; workgroup b owns the contiguous tile range [T b / G, T (b + 1) / G) and walks
-// it in equal units of <= 5 tiles (a unit costs one pass over both weight matrices whatever its size, so units are as large
-// as the LDS allows and as few as possible).  The unit body is instantiated for 4 and for 5 tiles; a unit with fewer tiles
-// runs the 4-tile body on clamped rows and stores only its own.
-//
-// Software pipeline of both GEMM phases as in mlp384_kernel: step s issues the weight fragments of step s + WD and the
-// activation fragments of step s + 1, then its own MFMAs (pinned with scheduling fences).
-template <bool FMA>
-__global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
+// ivit_mlp_body.h — the body of the lock-step fused-Mlp kernel (the scheme: ivit_mlp.h).  Not a header of its own: ivit_mlp.h includes it
+// once inside each entry point (mlp384_kernel, mlp192_kernel), which supplies `G` (the geometry), `FMA` and `p` (MlpArgs).  One
+// text, so that a change to the barriers, the prefetch distances or ShiftGELU reaches every width; included rather than called,
+// so that each entry point compiles exactly as if the body were written out in it.
     extern __shared__ __attribute__((aligned(256))) char sm[];
-    constexpr int NJ = M192_NJ;
-    constexpr int CT1 = M192_HD / 16 / M192_WAVES;    // 12 channel tiles of fc1 per wave, in chunks of NJ
-    constexpr int NCH = CT1 / NJ, NS1 = NCH * M192_KS1, WD = M192_WD;   // fc1 chunks, fc1 steps, weight prefetch distance
-    constexpr int ACH = M192_C / 16;                  // 16-byte chunks of an activation row
-    constexpr int AREG = (M192_TT * 16 * ACH + M192_THREADS - 1) / M192_THREADS;
-    static_assert(NJ * 16 * M192_WAVES == M192_C && CT1 % NJ == 0, "wave count must split 48 / 12 channel tiles evenly");
-    static_assert(M192_KS1 >= 3, "the fc1 pipeline loads a chunk's multipliers at its first step and the next bias at its second");
-    static_assert(M192_WG_PER_CU * M192_SMEM <= 160 * 1024, "two workgroups per CU");
+    constexpr int NJ = G::NJ;                       // channel tiles per step
+    constexpr int CT1 = G::HD / 16 / G::WAVES;      // channel tiles of fc1 per wave, in chunks of NJ
+    constexpr int NCH = CT1 / NJ, NS1 = NCH * G::KS1, WD = G::WD;   // fc1 chunks, fc1 steps, weight prefetch distance
+    constexpr int ACH = G::C / 16;                  // 16-byte chunks of an activation row
+    constexpr int AREG = (G::TT * 16 * ACH + G::THREADS - 1) / G::THREADS;
+    static_assert(NJ * 16 * G::WAVES == G::C && CT1 % NJ == 0, "wave count must split the channel tiles of fc1 and fc2 evenly");
+    static_assert(G::KS1 >= 3 && G::CQ_STEP < G::BIAS_STEP && G::BIAS_STEP < G::KS1 - 1,
+                  "the fc1 pipeline loads a chunk's multipliers, then the next bias, both before the chunk's last step");
+    static_assert(G::WG_PER_CU * G::SMEM <= 160 * 1024, "WG_PER_CU workgroups share a CU's LDS");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     typedef double v2d __attribute__((ext_vector_type(2)));
 
     // ---- this workgroup's units: (first tile, tiles) of unit i
-    const long long ntiles = (p.M + 15) >> 4;
-    const long long t_beg = ntiles * blockIdx.x / gridDim.x, t_end = ntiles * (blockIdx.x + 1) / gridDim.x;
-    const int n_own = (int)(t_end - t_beg);
-    const int nu = (n_own + M192_TT - 1) / M192_TT;
-    if (nu <= 0) return;
-    auto unit_tile0 = [&](int i) -> long long { return t_beg + (long long)n_own * i / nu; };
-    auto unit_ntt = [&](int i) -> int { return i >= nu ? 0 : (int)(unit_tile0(i + 1) - unit_tile0(i)); };
+    MLP_UNIT_SCHEDULE(G::TT, G::ROUND_ROBIN);
 
-    // activation tile of a unit (rows x 12 chunks of 16 B): global -> registers (a_fetch), registers -> LDS (a_commit).  Row and
-    // chunk of a lane come from an opaque copy of the thread id: left visible, the eight per-lane addresses are hoisted out of
-    // the unit loop and spilled
+    // activation tile of a unit (rows x ACH chunks of 16 B): global -> registers (a_fetch), registers -> LDS (a_commit).  With
+    // G::OPAQUE_A, row and chunk of a lane come from an opaque copy of the thread id
     v4i areg[AREG];
     auto a_fetch = [&](long long tile0, int ntt) __attribute__((always_inline)) {
         int t = threadIdx.x;
-        asm volatile("" : "+v"(t));
+        if constexpr (G::OPAQUE_A) asm volatile("" : "+v"(t));
 #pragma unroll
         for (int i = 0; i < AREG; ++i) {
-            const int ch = t + i * M192_THREADS, row = ch / ACH, c16 = ch - row * ACH;
+            const int ch = t + i * G::THREADS, row = ch / ACH, c16 = ch - row * ACH;
             if (ch < ntt * 16 * ACH) {
                 const long long grow = min(tile0 * 16 + row, p.M - 1);
-                areg[i] = *reinterpret_cast<const v4i *>(p.x + grow * M192_C + c16 * 16);
+                areg[i] = *reinterpret_cast<const v4i *>(p.x + grow * G::C + c16 * 16);
             }
         }
     };
     auto a_commit = [&](int ntt) __attribute__((always_inline)) {
         int t = threadIdx.x;
-        asm volatile("" : "+v"(t));
+        if constexpr (G::OPAQUE_A) asm volatile("" : "+v"(t));
 #pragma unroll
         for (int i = 0; i < AREG; ++i) {
-            const int ch = t + i * M192_THREADS, row = ch / ACH, c16 = ch - row * ACH;
+            const int ch = t + i * G::THREADS, row = ch / ACH, c16 = ch - row * ACH;
             if (ch < ntt * 16 * ACH)
-                *reinterpret_cast<v4i *>(sm + M192_SA + (c16 >> 2) * M192_KBLK + row * 64 + mlp_phi(row, c16 & 3) * 16) = areg[i];
+                *reinterpret_cast<v4i *>(sm + G::SA + (c16 >> 2) * G::KBLK + row * 64 + mlp_phi(row, c16 & 3) * 16) = areg[i];
         }
     };
 
     // ------------------------------------------------------------------------------------------------------------------
     // one unit of NTT token tiles starting at tile `tile0`; (next_tile0, next_ntt): the unit whose activations to prefetch
     // Barriers: B1 before the first hidden write (every wave is done reading the previous unit's hidden tile; placed AFTER the
-    // first chunk's K loop), B2 hidden tile complete / activation tile dead, B3 hidden tile rewritten by ShiftGELU and the
-    // NEXT unit's activation tile committed.
+    // first chunk's K loop, so a wave that finished its fc2 early already multiplies for the next unit), B2 hidden tile
+    // complete / activation tile dead, B3 hidden tile rewritten by ShiftGELU and the NEXT unit's activation tile committed.
     auto unit_body = [&](auto ntt_c, const int ntt, const long long tile0, const long long next_tile0, const int next_ntt) __attribute__((always_inline)) {
         constexpr int NTT = decltype(ntt_c)::value;       // tiles the body multiplies; `ntt` <= NTT of them belong to this unit
         const long long tok0 = tile0 * 16;
-        // per-lane indices from an opaque copy of the thread id (keeps the unrolled phases' LDS addresses from being hoisted
-        // out of the unit loop into registers)
+        // per-lane indices from an opaque copy of the thread id: every LDS address below is (a handful of per-lane bases) +
+        // immediates, recomputed per unit — left visible, the ~150 loop-invariant addresses of the unrolled phases are
+        // hoisted out of the unit loop into registers and spilled
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, tl = lane & 15, g = lane >> 4;
@@ -145,13 +67,13 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
             v2d cq[NJ][2];
             auto load_w = [&](int s, int slot) __attribute__((always_inline)) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) wf[slot][j] = w1[(size_t)(s * NJ * M192_WAVES + j) * 64];
+                for (int j = 0; j < NJ; ++j) wf[slot][j] = w1[(size_t)(s * NJ * G::WAVES + j) * 64];
             };
             auto load_b = [&](int s, int slot) __attribute__((always_inline)) {
-                const int ks = s % M192_KS1;
+                const int ks = s % G::KS1;
 #pragma unroll
                 for (int tt = 0; tt < NTT; ++tt)
-                    bf[slot][tt] = *reinterpret_cast<const v4i *>(sm + M192_SA + ks * M192_KBLK + tt * 1024 + fb);
+                    bf[slot][tt] = *reinterpret_cast<const v4i *>(sm + G::SA + ks * G::KBLK + tt * 1024 + fb);
             };
             auto load_bias = [&](int chunk) __attribute__((always_inline)) {
 #pragma unroll
@@ -164,11 +86,11 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
             load_bias(0);
 #pragma unroll
             for (int s = 0; s < NS1; ++s) {
-                const int chunk = s / M192_KS1, ks = s - chunk * M192_KS1, ct0 = wave * CT1 + chunk * NJ;
+                const int chunk = s / G::KS1, ks = s - chunk * G::KS1, ct0 = wave * CT1 + chunk * NJ;
                 __builtin_amdgcn_sched_barrier(0);
                 if (s + WD < NS1) load_w(s + WD, (s + WD) % (WD + 1));
                 if (s + 1 < NS1) load_b(s + 1, (s + 1) & 1);
-                if (ks == 0) {                       // this chunk's multipliers: consumed two steps on
+                if (ks == G::CQ_STEP) {              // this chunk's multipliers: consumed at its last step
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
                         const int ch0 = (ct0 + j) * 16 + 4 * g;
@@ -183,13 +105,13 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
 #pragma unroll
                         for (int tt = 0; tt < NTT; ++tt) acc[j][tt] = bias_n[j];
                 }
-                if (ks == 1 && chunk + 1 < NCH) load_bias(chunk + 1);      // the next chunk's bias, two steps ahead
+                if (ks == G::BIAS_STEP && chunk + 1 < NCH) load_bias(chunk + 1);      // the next chunk's bias, consumed at its first step
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int tt = 0; tt < NTT; ++tt)
                         acc[j][tt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[s % (WD + 1)][j], bf[s & 1][tt], acc[j][tt], 0, 0, 0);
-                if (ks == M192_KS1 - 1) {
+                if (ks == G::KS1 - 1) {
                     if (chunk == 0) __syncthreads();                       // B1: the hidden tile is free
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
@@ -207,7 +129,7 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
                             const unsigned w01 = __builtin_amdgcn_perm((unsigned)o[1], (unsigned)o[0], 0x0c0c0400u);
                             const unsigned w23 = __builtin_amdgcn_perm((unsigned)o[3], (unsigned)o[2], 0x0c0c0400u);
                             const int tok = tt * 16 + tl;
-                            *reinterpret_cast<unsigned *>(sm + M192_SH + kb * M192_KBLK + tok * 64 + mlp_phi(tok, cc) * 16 + 4 * g) =
+                            *reinterpret_cast<unsigned *>(sm + G::SH + kb * G::KBLK + tok * 64 + mlp_phi(tok, cc) * 16 + 4 * g) =
                                 __builtin_amdgcn_perm(w23, w01, 0x05040100u);
                         }
                     }
@@ -216,8 +138,8 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
         }
         __syncthreads();                                                    // B2
 
-        // ---- ShiftGELU (+ qact1) in place, half a wavefront per token, NTT * 2 tokens per half-wave: the token's 768 hidden
-        // bytes are read once (6 dwords per lane) and stay in registers from the row maximum (packed byte maxima, then 5
+        // ---- ShiftGELU (+ qact1) in place, half a wavefront per token, NTOK tokens per half-wave: the token's HD hidden
+        // bytes are read once (NW dwords per lane) and stay in registers from the row maximum (packed byte maxima, then 5
         // shuffles) over the fetch of the maximum's 256-byte table line (global -> this half-wave's LDS slot) to the byte
         // gathers and the write-back.  No workgroup barrier inside.  The next unit's activations travel meanwhile.
         if (next_ntt > 0) a_fetch(next_tile0, next_ntt);
@@ -226,21 +148,22 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
             typedef __attribute__((address_space(3))) const unsigned char lds_u8;
             typedef unsigned short v2us __attribute__((ext_vector_type(2)));
             const unsigned sm_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char *)sm;
-            const unsigned base = sm_lds + M192_STAB + hw * 256;           // 256-byte aligned: byte | base is the address
-            constexpr int NW = M192_KS2 / 2;                                 // dwords of a row per lane
-            constexpr int NTOK = (NTT * 16 + 2 * M192_WAVES - 1) / (2 * M192_WAVES);     // tokens per half-wave
+            const unsigned base = sm_lds + G::STAB + hw * 256;           // 256-byte aligned: byte | base is the address
+            constexpr int NW = G::KS2 / 2;                                           // dwords of a hidden row per lane
+            constexpr int NTOK = (NTT * 16 + 2 * G::WAVES - 1) / (2 * G::WAVES);     // tokens per half-wave
             unsigned w[NTOK][NW];
             v2i line[NTOK];
-            // pass 1: rows -> registers, row maxima, all table-line requests in flight together
+            // pass 1: rows -> registers, row maxima, all table-line requests in flight together (one exposed L2 latency
+            // per unit instead of one per token)
 #pragma unroll
             for (int i = 0; i < NTOK; ++i) {
-                const int t = hw + i * 2 * M192_WAVES;
+                const int t = hw + i * 2 * G::WAVES;
                 if (t < NTT * 16) {
-                    const unsigned *hp = reinterpret_cast<const unsigned *>(sm + M192_SH + t * 64) + (l32 & 15) + (l32 >> 4) * (M192_KBLK / 4);
+                    const unsigned *hp = reinterpret_cast<const unsigned *>(sm + G::SH + t * 64) + (l32 & 15) + (l32 >> 4) * (G::KBLK / 4);
                     v2us me = {0, 0}, mo = {0, 0};                          // running maxima of the even / odd bytes (biased)
 #pragma unroll
                     for (int m = 0; m < NW; ++m) {
-                        w[i][m] = hp[m * (M192_KBLK / 2)] ^ 0x80808080u;    // K blocks 2m, 2m + 1 (the upper 16 lanes): Q + 128
+                        w[i][m] = hp[m * (G::KBLK / 2)] ^ 0x80808080u;     // K blocks 2m, 2m + 1 (the upper 16 lanes): Q + 128
                         me = __builtin_elementwise_max(me, __builtin_bit_cast(v2us, __builtin_amdgcn_perm(0u, w[i][m], 0x0c020c00u)));
                         mo = __builtin_elementwise_max(mo, __builtin_bit_cast(v2us, __builtin_amdgcn_perm(0u, w[i][m], 0x0c030c01u)));
                     }
@@ -255,10 +178,10 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
             // belongs to this half-wave and the previous token's gathers were consumed by its write-back
 #pragma unroll
             for (int i = 0; i < NTOK; ++i) {
-                const int t = hw + i * 2 * M192_WAVES;
+                const int t = hw + i * 2 * G::WAVES;
                 if (t < NTT * 16) {
-                    unsigned *hp = reinterpret_cast<unsigned *>(sm + M192_SH + t * 64) + (l32 & 15) + (l32 >> 4) * (M192_KBLK / 4);
-                    reinterpret_cast<v2i *>(sm + M192_STAB + hw * 256)[l32] = line[i];
+                    unsigned *hp = reinterpret_cast<unsigned *>(sm + G::SH + t * 64) + (l32 & 15) + (l32 >> 4) * (G::KBLK / 4);
+                    reinterpret_cast<v2i *>(sm + G::STAB + hw * 256)[l32] = line[i];
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
@@ -266,7 +189,7 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
                         const unsigned x = w[i][m];
                         const unsigned b0 = *(lds_u8 *)(size_t)(base | (x & 0xffu)), b1 = *(lds_u8 *)(size_t)(base | ((x >> 8) & 0xffu));
                         const unsigned b2 = *(lds_u8 *)(size_t)(base | ((x >> 16) & 0xffu)), b3 = *(lds_u8 *)(size_t)(base | (x >> 24));
-                        hp[m * (M192_KBLK / 2)] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+                        hp[m * (G::KBLK / 2)] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
                     }
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -282,12 +205,12 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
             v4i wf[WD + 1][NJ], bf[2][NTT], acc[NJ][NTT];
             auto load_w = [&](int s, int slot) __attribute__((always_inline)) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) wf[slot][j] = w2[(size_t)(s * NJ * M192_WAVES + j) * 64];
+                for (int j = 0; j < NJ; ++j) wf[slot][j] = w2[(size_t)(s * NJ * G::WAVES + j) * 64];
             };
             auto load_b = [&](int s, int slot) __attribute__((always_inline)) {
 #pragma unroll
                 for (int tt = 0; tt < NTT; ++tt)
-                    bf[slot][tt] = *reinterpret_cast<const v4i *>(sm + M192_SH + s * M192_KBLK + tt * 1024 + fb);
+                    bf[slot][tt] = *reinterpret_cast<const v4i *>(sm + G::SH + s * G::KBLK + tt * 1024 + fb);
             };
 #pragma unroll
             for (int s = 0; s < WD; ++s) load_w(s, s);
@@ -305,14 +228,14 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
                 for (int tt = 0; tt < NTT; ++tt) {
                     acc[j][tt] = b4;
                     const long long tok = min(tok0 + tt * 16 + tl, p.M - 1);
-                    rs[j][tt] = *reinterpret_cast<const v2i *>(p.residual + tok * M192_C + ch0);
+                    rs[j][tt] = *reinterpret_cast<const v2i *>(p.residual + tok * G::C + ch0);
                 }
             }
 #pragma unroll
-            for (int s = 0; s < M192_KS2; ++s) {
+            for (int s = 0; s < G::KS2; ++s) {
                 __builtin_amdgcn_sched_barrier(0);
-                if (s + WD < M192_KS2) load_w(s + WD, (s + WD) % (WD + 1));
-                if (s + 1 < M192_KS2) load_b(s + 1, (s + 1) & 1);
+                if (s + WD < G::KS2) load_w(s + WD, (s + WD) % (WD + 1));
+                if (s + 1 < G::KS2) load_b(s + 1, (s + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
@@ -340,7 +263,7 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
                     }
                     const long long tok = tok0 + tt * 16 + tl;
                     if (tok < p.M && tt < ntt)         // a short unit's surplus tiles belong to the next unit
-                        *reinterpret_cast<v2i *>(p.out + tok * M192_C + ch0) =
+                        *reinterpret_cast<v2i *>(p.out + tok * G::C + ch0) =
                             v2i{(int)__builtin_amdgcn_perm((unsigned)o[1], (unsigned)o[0], 0x05040100u),
                                 (int)__builtin_amdgcn_perm((unsigned)o[3], (unsigned)o[2], 0x05040100u)};
                 }
@@ -355,7 +278,7 @@ __global__ __launch_bounds__(M192_THREADS, 2) void mlp192_kernel(Mlp192Args p) {
     for (int i = 0; i < nu; ++i) {
         const long long tile0 = unit_tile0(i), tile1 = unit_tile0(i + 1);
         const int ntt = unit_ntt(i), next_ntt = unit_ntt(i + 1);
-        if (ntt == M192_TT) unit_body(std::integral_constant<int, M192_TT>{}, ntt, tile0, tile1, next_ntt);
-        else unit_body(std::integral_constant<int, M192_TT - 1>{}, ntt, tile0, tile1, next_ntt);
+        if (ntt == G::TT) unit_body(std::integral_constant<int, G::TT>{}, ntt, tile0, tile1, next_ntt);
+        else unit_body(std::integral_constant<int, G::TT - 1>{}, ntt, tile0, tile1, next_ntt);
     }
-}
+

@@ -115,21 +115,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
     const unsigned fl = sm_lds + RS_SFLAG;
 
     // ---- this workgroup's units (the schedule of mlp384_kernel)
-    const long long ntiles = (p.M + 15) >> 4;
-    const long long t_beg = ntiles * blockIdx.x / gridDim.x, t_end = ntiles * (blockIdx.x + 1) / gridDim.x;
-    const int n_own = (int)(t_end - t_beg);
-    const long long nfix = (ntiles + MLP_TT - 2) / (MLP_TT - 1);
-    const int nu = p.balanced ? (n_own + MLP_TT - 1) / MLP_TT : (int)((nfix - (long long)blockIdx.x + gridDim.x - 1) / gridDim.x);
-    if (nu <= 0) return;
-    auto unit_tile0 = [&](int i) -> long long {
-        if (p.balanced) return t_beg + (long long)n_own * i / nu;
-        return min(((long long)blockIdx.x + (long long)i * gridDim.x) * (MLP_TT - 1), ntiles);
-    };
-    auto unit_ntt = [&](int i) -> int {
-        if (i >= nu) return 0;
-        if (p.balanced) return (int)(unit_tile0(i + 1) - unit_tile0(i));
-        return (int)min((long long)(MLP_TT - 1), ntiles - unit_tile0(i));
-    };
+    MLP_UNIT_SCHEDULE(MLP_TT, true);
     // cumulative hand-over targets: in the first unit the consumers produce too, so F_H / F_A count eight producers there and
     // four after; ShiftGELU runs on all eight waves, so F_G counts eight per unit
     auto fh_target = [&](int u) -> unsigned { return 8u + 4u * (unsigned)u; };      // F_H / F_A after unit u

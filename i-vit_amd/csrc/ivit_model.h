@@ -66,6 +66,11 @@ SliceLayout slice_layout(const ivit_vit_s *m, int B) {
     return L;
 }
 
+// the shapes ivit_mlp_plan_create has a kernel for: width C, hidden size Hd
+inline bool mlp_plan_shape(int C, int Hd) {
+    return (C == Mlp384Geo::C && Hd == Mlp384Geo::HD) || (C == Mlp192Geo::C && Hd == Mlp192Geo::HD);
+}
+
 // THE rule for "this block's Mlp is one ivit_mlp_fused_planned launch at M tokens": run_slice, swin_run_slice and the
 // ivit_*_fused_mlp_blocks queries all ask here.  No token-count threshold: at width 192 the fused launch measured faster than
 // the three-launch chain at every size tried, 197 tokens (DeiT-T batch 1: 15.8 against 20.0 us) to 200 704 (profiles/README.md)
@@ -225,7 +230,7 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
             m->plans.push_back(pl);
         }
         ivit_mlp_plan mp = nullptr;
-        if (((D == MLP_C && Hd == MLP_HD) || (D == M192_C && Hd == M192_HD)) && ivit_mlp_plan_create(h, m->plans[4 * i + 2], m->plans[4 * i + 3], &mp) != IVIT_OK) mp = nullptr;
+        if (mlp_plan_shape(D, Hd) && ivit_mlp_plan_create(h, m->plans[4 * i + 2], m->plans[4 * i + 3], &mp) != IVIT_OK) mp = nullptr;
         m->mlp_plans.push_back(mp);
     }
     if (max_slices > 1) {
@@ -604,7 +609,7 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
                 ivit_linear_plan p1 = nullptr, p2 = nullptr;
                 ivit_mlp_plan mp = nullptr;
                 const ivit_swin_block &b = m->blocks[bi];
-                if ((C == MLP_C || C == M192_C) && cfg->mlp_ratio == 4 &&
+                if (mlp_plan_shape(C, cfg->mlp_ratio * C) &&
                     ivit_linear_plan_create(h, b.fc1.w, b.fc1.b, b.fc1.dy, 4 * C, C, &p1) == IVIT_OK &&
                     ivit_linear_plan_create(h, b.fc2.w, b.fc2.b, b.fc2.dy, C, 4 * C, &p2) == IVIT_OK) {
                     if (ivit_mlp_plan_create(h, p1, p2, &mp) != IVIT_OK) mp = nullptr;

@@ -505,7 +505,7 @@ int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32
 /* The same chain on frozen linear plans, at two widths: C = 384, hidden = 1536 (DeiT-S, Swin stage 2) and C = 192,
  * hidden = 768 (DeiT-Tiny, Swin-T / S stage 1).  Both weight matrices are re-laid-out once in MFMA-fragment order and
  * stream L2 -> registers, the hidden tile of a unit of up to 80 tokens lives in LDS between fc1, the ShiftGELU table pass
- * and fc2 (csrc/ivit_mlp.h, csrc/ivit_mlp_rs.h; csrc/ivit_mlp192.h: two four-wave workgroups per CU).  x, residual and out
+ * and fc2 (csrc/ivit_mlp.h: one lock-step kernel body at both widths, two four-wave workgroups per CU at width 192; csrc/ivit_mlp_rs.h).  x, residual and out
  * are [M, C] of the plan's width.  The linear plans are borrowed and must outlive the Mlp plan.
  * IVIT_ERR_UNSUPPORTED for other shapes (fc1 must be [4C x C] and fc2 [C x 4C] with C = 384 or 192), for plans whose requant bound is not provable, and (at call time) for
  * residual multipliers >= 2^9: callers then run the unfused chain.  Replaces layers_quant.py:144-153 +

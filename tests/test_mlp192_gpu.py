@@ -1,4 +1,4 @@
-"""Fused Mlp at width 192 (ivit_mlp_fused_planned on a 192 -> 768 -> 192 plan, csrc/ivit_mlp192.h): DeiT-Tiny's blocks and
+"""Fused Mlp at width 192 (ivit_mlp_fused_planned on a 192 -> 768 -> 192 plan, mlp192_kernel of csrc/ivit_mlp.h): DeiT-Tiny's blocks and
 stage 1 of Swin-T / Swin-S.  Bit-exact everywhere: against the CPU oracle's operators, against the three-launch chain the
 kernel replaces, and through the native runners against the reference's logits."""
 import ctypes

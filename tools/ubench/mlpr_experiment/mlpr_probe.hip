@@ -72,7 +72,7 @@ int main(int argc, char **argv) {
     }
     MlpArgs a;
     a.x = x; a.w1f = w1f; a.w2f = w2f; a.b1 = b1; a.b2 = b2; a.cq1 = c1; a.cq2 = c2; a.tab = tab; a.residual = res; a.out = out;
-    a.cm = 0.645; a.cr = 0.871; a.M = M; a.trace = tr; a.balanced = 1;
+    a.cm = 0.645; a.cr = 0.871; a.M = M; a.balanced = 1;
     hipFuncSetAttribute((const void *)mlp384_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_SMEM);
     const long long nunits = ((M + 15) / 16 + MLP_TT - 2) / (MLP_TT - 1);
     const unsigned grid = (unsigned)(nunits < 256 ? nunits : 256);
