@@ -776,14 +776,15 @@ int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, con
 
 }  // extern "C"
 
-// ---- fused Mlp (+ residual QuantAct) for D = 384, hidden = 1536 (ivit_mlp.h, ivit_mlp_rs.h) and D = 192, hidden = 768 (ivit_mlp.h)
+// ---- fused Mlp (+ residual QuantAct) for D = 384, hidden = 1536 (ivit_mlp.h, ivit_mlp_rs.h), D = 256, hidden = 1024 and D = 192,
+// hidden = 768 (ivit_mlp.h)
 struct ivit_mlp_plan_s {
     ivit_linear_plan fc1, fc2;      // borrowed: must outlive this plan
-    int width;                      // 384 or 192
+    int width;                      // 384, 256 or 192
     v4i *w1f, *w2f;                 // fragment-ordered copies of the two weight matrices (one allocation)
     v4i *w1r, *w2r;                 // width 384: the same in the role-split kernel's order (ivit_mlp_rs.h), same allocation; else null
     int fma;                        // both layers: one fused rounding == the reference's two
-    int kernel;                     // 0 = by shape, 1 = lock-step (mlp384_kernel / mlp192_kernel), 2 = role-split (mlp384rs_kernel): ivit_mlp_plan_select
+    int kernel;                     // 0 = by shape, 1 = lock-step (mlp384_kernel / mlp256_kernel / mlp192_kernel), 2 = role-split (mlp384rs_kernel): ivit_mlp_plan_select
     int device;
 };
 
@@ -794,8 +795,9 @@ int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan f
     REQUIRE(h, fc1 && fc2 && out, "null argument");
     const bool w384 = fc1->K == Mlp384Geo::C && fc1->N == Mlp384Geo::HD && fc2->K == Mlp384Geo::HD && fc2->N == Mlp384Geo::C;
     const bool w192 = fc1->K == Mlp192Geo::C && fc1->N == Mlp192Geo::HD && fc2->K == Mlp192Geo::HD && fc2->N == Mlp192Geo::C;
-    if (!w384 && !w192) {
-        snprintf(h->err, sizeof(h->err), "%s: built for 384 -> 1536 -> 384 and 192 -> 768 -> 192", __func__);
+    const bool w256 = fc1->K == Mlp256Geo::C && fc1->N == Mlp256Geo::HD && fc2->K == Mlp256Geo::HD && fc2->N == Mlp256Geo::C;
+    if (!w384 && !w256 && !w192) {
+        snprintf(h->err, sizeof(h->err), "%s: built for 384 -> 1536 -> 384, 256 -> 1024 -> 256 and 192 -> 768 -> 192", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
     if (!fc1->pipelined_ok || !fc2->pipelined_ok) {
@@ -811,6 +813,9 @@ int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan f
         mlp_swizzle_kernel<<<256, 256, 0, h->stream>>>(fc2->w, fc2->N, fc2->K, (v4i *)(dev + wbytes));
         rs_swizzle_w1_kernel<<<144, 256, 0, h->stream>>>(fc1->w, (v4i *)(dev + 2 * wbytes));
         rs_swizzle_w2_kernel<<<144, 256, 0, h->stream>>>(fc2->w, (v4i *)(dev + 3 * wbytes));
+    } else if (w256) {
+        mlp256_swizzle_kernel<<<256, 256, 0, h->stream>>>(fc1->w, fc1->N, fc1->K, (v4i *)dev);
+        mlp256_swizzle_kernel<<<256, 256, 0, h->stream>>>(fc2->w, fc2->N, fc2->K, (v4i *)(dev + wbytes));
     } else {
         mlp192_swizzle_kernel<<<144, 256, 0, h->stream>>>(fc1->w, fc1->N, fc1->K, (v4i *)dev);
         mlp192_swizzle_kernel<<<144, 256, 0, h->stream>>>(fc2->w, fc2->N, fc2->K, (v4i *)(dev + wbytes));
@@ -824,6 +829,8 @@ int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan f
         lds(fma ? (const void *)mlp384_kernel<true> : (const void *)mlp384_kernel<false>, Mlp384Geo::SMEM);
         lds(fma ? (const void *)mlp384rs_kernel<true> : (const void *)mlp384rs_kernel<false>, RS_SMEM);
         lds(fma ? (const void *)mlp384rs_kernel<true, 1> : (const void *)mlp384rs_kernel<false, 1>, RS_SMEM);
+    } else if (w256) {
+        lds(fma ? (const void *)mlp256_kernel<true> : (const void *)mlp256_kernel<false>, Mlp256Geo::SMEM);
     } else {
         lds(fma ? (const void *)mlp192_kernel<true> : (const void *)mlp192_kernel<false>, Mlp192Geo::SMEM);
     }
@@ -844,7 +851,7 @@ int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan f
 
 int ivit_mlp_plan_select(ivit_mlp_plan p, int kernel) {
     if (!p || kernel < 0 || kernel > 2) return IVIT_ERR_INVALID;
-    if (p->width == Mlp192Geo::C && kernel == 2) return IVIT_ERR_UNSUPPORTED;      // width 192 has the lock-step kernel only
+    if (p->width != Mlp384Geo::C && kernel == 2) return IVIT_ERR_UNSUPPORTED;      // widths 192 and 256 have the lock-step kernel only
     p->kernel = kernel;
     return IVIT_OK;
 }
@@ -872,13 +879,17 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
     }
     REQUIRE(h, h->device == p->device, "plan and handle live on different devices");
     const long long ntiles = (M + 15) / 16;
-    if (p->width == Mlp192Geo::C) {
-        // two workgroups per CU of the handle's share; workgroup b walks the tile range [T b / G, T (b + 1) / G).  Lock-step only
-        // (ivit_layernorm_mlp_fused_planned refuses this width before it comes here)
-        const long long slots = (long long)Mlp192Geo::WG_PER_CU * persistent_cus(h);
+    if (p->width != Mlp384Geo::C) {
+        // widths 192 and 256: WG_PER_CU workgroups per CU of the handle's share; workgroup b walks the tile range [T b / G, T (b + 1) / G).
+        // Lock-step only (ivit_layernorm_mlp_fused_planned refuses these widths before it comes here)
+        const bool w256 = p->width == Mlp256Geo::C;
+        const long long slots = (long long)(w256 ? Mlp256Geo::WG_PER_CU : Mlp192Geo::WG_PER_CU) * persistent_cus(h);
         const unsigned grid = (unsigned)(ntiles < slots ? ntiles : slots);
         a.balanced = 1;
-        if (p->fma) mlp192_kernel<true><<<grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, h->stream>>>(a);
+        if (w256) {
+            if (p->fma) mlp256_kernel<true><<<grid, Mlp256Geo::THREADS, Mlp256Geo::SMEM, h->stream>>>(a);
+            else mlp256_kernel<false><<<grid, Mlp256Geo::THREADS, Mlp256Geo::SMEM, h->stream>>>(a);
+        } else if (p->fma) mlp192_kernel<true><<<grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, h->stream>>>(a);
         else mlp192_kernel<false><<<grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, h->stream>>>(a);
         LAUNCH_CHECK(h);
         return IVIT_OK;
@@ -910,6 +921,37 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
     return IVIT_OK;
 }
 
+// ivit_mlp_fused at C = 128, hidden = 512 (Swin-B stage 0): the lock-step body on the caller's own operands (mlp128_kernel; nothing is
+// kept between calls but the per-device LDS attribute), two workgroups per CU of the handle's share
+static int mlp128_launch(ivit_handle h, const int8_t *x, const int8_t *w1, const int32_t *b1, const ivit_dyadic *dy1, const int8_t *gelu_table,
+                         const int8_t *w2, const int32_t *b2, const ivit_dyadic *dy2, ivit_dyadic dy_main, ivit_dyadic dy_res,
+                         const int16_t *residual, int16_t *out, int64_t M) {
+    MlpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.w1f = reinterpret_cast<const v4i *>(w1); a.w2f = reinterpret_cast<const v4i *>(w2); a.b1 = b1; a.b2 = b2;
+    a.cq1 = reinterpret_cast<const double *>(dy1); a.cq2 = reinterpret_cast<const double *>(dy2);
+    a.tab = gelu_table; a.residual = residual; a.out = out;
+    a.cm = dy_main.m * dy_main.r; a.cr = dy_res.m * dy_res.r; a.M = M; a.balanced = 1;
+    if (!(fabs(a.cm) < RQ_FAST_CLIM && fabs(a.cr) < RQ_FAST_CLIM)) {
+        snprintf(h->err, sizeof(h->err), "ivit_mlp_fused: residual multipliers out of the fast range at C = 128");
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    REQUIRE(h, (((uintptr_t)x | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)dy1 | (uintptr_t)dy2 | (uintptr_t)b1 | (uintptr_t)b2) & 15) == 0 &&
+                   (((uintptr_t)residual | (uintptr_t)out) & 7) == 0,
+            "C = 128: x, w1, w2, b1, b2, dy1, dy2 must be 16-byte aligned, residual and out 8-byte aligned");
+    static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
+    const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
+    if (!cached || !attr_dev[h->device].load(std::memory_order_acquire)) {
+        hipError_t e = hipFuncSetAttribute((const void *)mlp128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Mlp128Geo::SMEM);
+        if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "mlp_fused attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+        if (cached) attr_dev[h->device].store(true, std::memory_order_release);
+    }
+    const long long ntiles = (M + 15) / 16, slots = (long long)Mlp128Geo::WG_PER_CU * persistent_cus(h);
+    mlp128_kernel<<<(unsigned)(ntiles < slots ? ntiles : slots), Mlp128Geo::THREADS, Mlp128Geo::SMEM, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
 int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, const int8_t *gelu_table, ivit_dyadic dy_main,
                            ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M) {
     CHECK_H(h);
@@ -923,7 +965,7 @@ int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16
     CHECK_H(h);
     REQUIRE(h, p && x16 && bias_int && sc && ln_dy && scratch8 && gelu_table && out && M > 0, "bad arguments");
     if (p->width != MLP_C) {
-        snprintf(h->err, sizeof(h->err), "%s: the LayerNorm prologue exists at width 384 only", __func__);
+        snprintf(h->err, sizeof(h->err), "%s: the LayerNorm prologue exists at width 384 only", __func__);      // not at 192, not at 256
         return IVIT_ERR_UNSUPPORTED;
     }
     return mlp_fused_launch(h, p, scratch8, gelu_table, dy_main, dy_res, x16, out, M, scale, bias_int, sc, ln_dy);
@@ -1568,8 +1610,11 @@ int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32
                    int hidden) {
     CHECK_H(h);
     REQUIRE(h, x && w1 && dy1 && gelu_table && w2 && dy2 && residual && out && M > 0, "bad arguments");
+    if (C == Mlp128Geo::C && hidden == Mlp128Geo::HD)
+        return mlp128_launch(h, x, w1, b1, dy1, gelu_table, w2, b2, dy2, dy_main, dy_res, residual, out, M);
     if (C != MF_C || hidden != MF_HD) {
-        snprintf(h->err, sizeof(h->err), "%s: built for C = 96, hidden = 384 (weights resident in LDS)", __func__);
+        snprintf(h->err, sizeof(h->err), "%s: built for C = 96, hidden = 384 (weights resident in LDS) and C = 128, hidden = 512 (weights streamed from L2)",
+                 __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
     // the dynamic-LDS attribute is per device (one process-wide flag left the second GPU of a process without it)

@@ -1,5 +1,6 @@
 // ivit_mlp.h — Mlp.forward + the block's residual QuantAct as ONE kernel for the D = 384 models (DeiT-S, Swin stage 2) and, with
-// the same body re-cut (below: "Width 192"), the D = 192 ones (DeiT-Tiny: every block; Swin-T / S: stage 1):
+// the same body re-cut (below: "Width 192", "Width 256", "Width 128"), the D = 192 ones (DeiT-Tiny: every block; Swin-T / S: stage 1)
+// and Swin-B's stages 1 and 0:
 //   fc1 -> qact_gelu (8 bit) -> ShiftGELU -> qact1 (8 bit) -> fc2 -> qact2 (16 bit) -> qact4(+identity) (16 bit)
 // (models/layers_quant.py:144-153, then vit_quant.py:141-142 / swin_quant.py:296-300).  The 4 D-wide hidden tensor never
 // exists in HBM: per 64-token unit it is produced into LDS by fc1, rewritten in place by the ShiftGELU table and consumed
@@ -30,6 +31,24 @@
 // chunks of 3: the register picture of a wave (3 channel tiles x 5 token tiles of accumulators) is the one mlp384_kernel has at
 // eight waves.  Units are always contiguous tile ranges.  No LayerNorm-headed form: that prologue lives in the role-split
 // kernel (ivit_mlp_rs.h), which needs two 80-token units per workgroup to overlap anything and exists at width 384 only.
+//
+// Width 256 (mlp256_kernel; Swin-B stage 1, hidden row 1024 B).  Eight waves, two channel tiles each (NJ = 2): fc1's 64 tiles are
+// 8 waves x 4 chunks of 2, fc2's 16 are 8 x 2.  Hidden 80 KB + activations 20 KB + table lines 4 KB = 104 KB: one workgroup per
+// CU.  One pass over both weight matrices is 512 KB, 6.6 KB per token of a full unit.  Contiguous tile ranges, lock-step only.
+//
+// Width 128 (mlp128_kernel; Swin-B stage 0, hidden row 512 B), behind the STATELESS entry ivit_mlp_fused: there is no plan, so
+// nothing is laid out or precomputed for it (G::DIRECT).  The weights are read row-major — a fragment of the lock-step layout
+// is 16 rows x 64 contiguous bytes of W, so a lane loads its 16 bytes from W[(ct * 16 + (l & 15)) * K + ks * 64 + (l >> 4) * 16];
+// both matrices are 128 KB and stay in L2 — the multipliers are m * 2^-e of the caller's ivit_dyadic tables, formed where
+// they are consumed, a null bias is zeros, and the requant form is chosen at run time, once per workgroup: the magic-number
+// form where |z c| < 2^31 holds for every channel, v_rndne_f64 + saturating convert otherwise (as swin_mlp_rs_kernel does at
+// C = 96, whose whole-launch register-resident weights would be 128 KB over 16 waves here and do not fit).  Four waves, NJ = 2;
+// hidden 40 KB + activations 10 KB + table lines 2 KB = 52 KB.  TWO workgroups share a CU (199 VGPRs, no scratch).  Three fit the
+// LDS (156 of 160 KB) but not the registers: at <= 168 VGPRs the unit body keeps 128 B per lane in scratch (20 B with units of 4
+// tiles and a prefetch distance of 2), and measured on one box against this cut it wins only at one unit per workgroup
+// (50 176 tokens: 37 against 43 us) and loses at 12 544 (31 against 22 us, the chain: 27) and at 200 704 (122 against 114-120):
+// profiles/README.md.  fc1 has two column steps per chunk: a chunk's multipliers and the next chunk's bias are both requested at
+// step 0.
 #pragma once
 #include <type_traits>
 #include "ivit_device.h"
@@ -41,16 +60,17 @@ struct MlpGeo {
     static constexpr int C = C_, HD = 4 * C_;
     static constexpr int TT = 5;                            // token tiles (of 16) a unit may have: 4 or 5
     static constexpr int WAVES = WAVES_;
-    static constexpr int NJ = C / 16 / WAVES;               // channel tiles per wave and step: 3 at both widths (2 with 12 waves)
+    static constexpr int NJ = C / 16 / WAVES;               // channel tiles per wave and step: 3 at widths 384 and 192 (2 with 12 waves), 2 at 256 and 128
     //                         // waves / 4 per SIMD: a lone wave issues a 16x16x64 MFMA every ~34 cycles, the pipe takes one per ~17
     static constexpr int THREADS = WAVES * 64;
-    static constexpr int KS1 = C / 64, KS2 = HD / 64;       // column steps of fc1 (6 / 3) and of fc2 (24 / 12)
+    static constexpr int KS1 = C / 64, KS2 = HD / 64;       // column steps of fc1 (6 / 4 / 3 / 2) and of fc2 (24 / 16 / 12 / 8)
     static constexpr int KBLK = TT * 16 * 64;               // one 64-column block of an LDS image: [80 tokens][64 B]
     static constexpr int SH = 0;                            // hidden tile [KS2][80][64 B]
     static constexpr int SA = KS2 * KBLK;                   // activation tile [KS1][80][64 B]
     static constexpr int STAB = SA + KS1 * KBLK;            // one ShiftGELU table line (256 B) per half-wave
     static constexpr int SMEM = STAB + 2 * WAVES * 256;
     static constexpr int WD = 3;                            // weight fragments in flight ahead of the MFMAs that consume them
+    static constexpr bool DIRECT = false;                   // operands as a plan prepared them (fragment-ordered weights, c = m * 2^-e, a bias)
 };
 struct Mlp384Geo : MlpGeo<384, 8> {
     static constexpr int WG_PER_CU = 1;                     // 154 KB of LDS
@@ -65,6 +85,20 @@ struct Mlp192Geo : MlpGeo<192, 4> {
     //                                                         hoisted out of the unit loop and spilled
     static constexpr bool ROUND_ROBIN = false;              // contiguous tile ranges only: the round-robin branch compiles away
 };
+struct Mlp256Geo : MlpGeo<256, 8> {
+    static constexpr int WG_PER_CU = 1;                     // 104 KB of LDS
+    static constexpr int CQ_STEP = 1, BIAS_STEP = 2;        // fc1 has 4 column steps
+    static constexpr bool OPAQUE_A = false;
+    static constexpr bool ROUND_ROBIN = false;
+};
+struct Mlp128Geo : MlpGeo<128, 4> {
+    static constexpr int WG_PER_CU = 2;                     // 2 x 52 KB of LDS; a third does not fit the registers (above)
+    static constexpr int CQ_STEP = 0, BIAS_STEP = 0;        // fc1 has only 2 column steps: both loads at the first
+    static constexpr bool OPAQUE_A = true;
+    static constexpr bool ROUND_ROBIN = false;
+    static constexpr bool DIRECT = true;                    // ivit_mlp_fused's operands as the caller holds them: row-major int8 weights, ivit_dyadic
+    //                                                         tables, biases that may be null (MlpArgs: the same fields, re-read)
+};
 // width 384 by its old names (ivit_mlp_rs.h, the host side, tools/ubench/mlpr_experiment)
 #define MLP_C Mlp384Geo::C
 #define MLP_HD Mlp384Geo::HD
@@ -77,7 +111,7 @@ struct Mlp192Geo : MlpGeo<192, 4> {
 
 struct MlpArgs {
     const int8_t *x;          // [M, C] int8 (LayerNorm + requant output)
-    const v4i *w1f, *w2f;     // fragment-ordered weights (mlp_swizzle_kernel / mlp192_swizzle_kernel)
+    const v4i *w1f, *w2f;     // fragment-ordered weights (mlp_swizzle_kernel / mlp256_swizzle_kernel / mlp192_swizzle_kernel)
     const int32_t *b1, *b2;   // biases (never null: the plans' bias_eff)
     const double *cq1, *cq2;  // per-channel c = m * 2^-e
     const int8_t *tab;        // ShiftGELU(+requant) table [256 maxima][256 values]
@@ -85,7 +119,9 @@ struct MlpArgs {
     int16_t *out;             // [M, C]
     double cm, cr;            // qact4: main and identity multipliers
     long long M;
-    // width 384 only from here on (mlp192_kernel reads none of it)
+    // G::DIRECT (mlp128_kernel): w1f / w2f are the row-major int8 matrices [HD][C] / [C][HD], cq1 / cq2 the ivit_dyadic tables
+    // (m, 2^-e) of the two layers, b1 / b2 may be null
+    // width 384 only from here on (the other widths read none of it)
     int balanced;             // unit schedule: 0 = 64-token units dealt round-robin, 1 = contiguous tile ranges cut into units of <= 5 tiles
     // mlp384rs_kernel<FMA, LNH = true> (ivit_layernorm_mlp_fused_planned): norm2 + qact3 of this workgroup's rows first, from the block's 16-bit
     // stream (`residual` is that stream), into x (a scratch of M x 384 bytes that only this launch reads)
@@ -119,10 +155,14 @@ __device__ __forceinline__ int mlp_phi(int tok, int chunk) {
     }
 MLP_SWIZZLE_KERNEL(mlp_swizzle_kernel, Mlp384Geo)
 MLP_SWIZZLE_KERNEL(mlp192_swizzle_kernel, Mlp192Geo)
+MLP_SWIZZLE_KERNEL(mlp256_swizzle_kernel, Mlp256Geo)
 
-template <bool FMA>
+// requant of an accumulator, before the clamp.  RQ 1: one FMA onto the magic number (the plan proved it equal to the reference's
+// two roundings); 0: multiply, then add the magic number; both need |z c| < 2^31.  2: v_rndne_f64 + saturating convert, any c.
+template <int RQ>
 __device__ __forceinline__ int mlp_rq(int z, double c) {
-    const double t = FMA ? __builtin_fma((double)z, c, MLP_MAGIC) : ((double)z * c + MLP_MAGIC);
+    if constexpr (RQ == 2) return rint_sat_i32((double)z * c);
+    const double t = RQ ? __builtin_fma((double)z, c, MLP_MAGIC) : ((double)z * c + MLP_MAGIC);
     return __double2loint(t);
 }
 
@@ -179,4 +219,31 @@ template <bool FMA>
 __global__ __launch_bounds__(Mlp192Geo::THREADS, Mlp192Geo::WAVES * Mlp192Geo::WG_PER_CU / 4) void mlp192_kernel(MlpArgs p) {
     typedef Mlp192Geo G;
 #include "ivit_mlp_body.h"
+}
+template <bool FMA>
+__global__ __launch_bounds__(Mlp256Geo::THREADS, Mlp256Geo::WAVES * Mlp256Geo::WG_PER_CU / 4) void mlp256_kernel(MlpArgs p) {
+    typedef Mlp256Geo G;
+#include "ivit_mlp_body.h"
+}
+// width 128: the body once per requant form (FMA here is mlp_rq's RQ: 0 or 2), and the kernel that picks between them — every
+// workgroup reads the 640 multipliers and biases once and asks whether |z c| < 2^31 holds for all of them, with |z| <= K * 2^14
+// + |bias| (the bound swin_mlp_rs_kernel uses)
+template <int FMA>
+__device__ __forceinline__ void mlp128_body(const MlpArgs &p) {
+    typedef Mlp128Geo G;
+#include "ivit_mlp_body.h"
+}
+__global__ __launch_bounds__(Mlp128Geo::THREADS, Mlp128Geo::WAVES * Mlp128Geo::WG_PER_CU / 4) void mlp128_kernel(MlpArgs p) {
+    typedef Mlp128Geo G;
+    bool wide = false;
+    for (int ch = threadIdx.x; ch < G::HD + G::C; ch += G::THREADS) {
+        const bool first = ch < G::HD;
+        const int n = first ? ch : ch - G::HD;
+        const ivit_dyadic d = reinterpret_cast<const ivit_dyadic *>(first ? p.cq1 : p.cq2)[n];
+        const int32_t *b = first ? p.b1 : p.b2;
+        const double zmax = (double)(first ? G::C : G::HD) * 16384.0 + fabs((double)(b ? b[n] : 0));
+        wide |= !(fabs(d.m * d.r) * zmax < 2147483000.0);
+    }
+    if (__syncthreads_or(wide)) mlp128_body<2>(p);
+    else mlp128_body<0>(p);
 }

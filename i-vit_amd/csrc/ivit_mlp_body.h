@@ -1,5 +1,6 @@
 // ivit_mlp_body.h — the body of the lock-step fused-Mlp kernel (the scheme: ivit_mlp.h).  Not a header of its own: ivit_mlp.h includes it
-// once inside each entry point (mlp384_kernel, mlp192_kernel), which supplies `G` (the geometry), `FMA` and `p` (MlpArgs).  One
+// once inside each entry point (mlp384_kernel, mlp256_kernel, mlp192_kernel, mlp128_body), which supplies `G` (the geometry), `FMA` (the
+// requant form: mlp_rq) and `p` (MlpArgs).  One
 // text, so that a change to the barriers, the prefetch distances or ShiftGELU reaches every width; included rather than called,
 // so that each entry point compiles exactly as if the body were written out in it.
     extern __shared__ __attribute__((aligned(256))) char sm[];
@@ -9,11 +10,18 @@
     constexpr int ACH = G::C / 16;                  // 16-byte chunks of an activation row
     constexpr int AREG = (G::TT * 16 * ACH + G::THREADS - 1) / G::THREADS;
     static_assert(NJ * 16 * G::WAVES == G::C && CT1 % NJ == 0, "wave count must split the channel tiles of fc1 and fc2 evenly");
-    static_assert(G::KS1 >= 3 && G::CQ_STEP < G::BIAS_STEP && G::BIAS_STEP < G::KS1 - 1,
+    // (the two may share a step: the multipliers are requested in the step's first fenced region, the bias — after the step has
+    // copied the current one into its accumulators — in the second, so the multipliers still come back first)
+    static_assert(G::KS1 >= 2 && G::CQ_STEP <= G::BIAS_STEP && G::BIAS_STEP < G::KS1 - 1,
                   "the fc1 pipeline loads a chunk's multipliers, then the next bias, both before the chunk's last step");
     static_assert(G::WG_PER_CU * G::SMEM <= 160 * 1024, "WG_PER_CU workgroups share a CU's LDS");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     typedef double v2d __attribute__((ext_vector_type(2)));
+    // G::DIRECT: four channels' (m, 2^-e) pairs as the caller's table holds them -> their multipliers c = m * 2^-e
+    auto dy_c = [](const v2d (&d)[4], v2d (&c)[2]) __attribute__((always_inline)) {
+        c[0] = v2d{d[0][0] * d[0][1], d[1][0] * d[1][1]};
+        c[1] = v2d{d[2][0] * d[2][1], d[3][0] * d[3][1]};
+    };
 
     // ---- this workgroup's units: (first tile, tiles) of unit i
     MLP_UNIT_SCHEDULE(G::TT, G::ROUND_ROBIN);
@@ -63,11 +71,18 @@
         // ---- fc1 + qact_gelu (8 bit) into the hidden tile
         {
             const v4i *w1 = p.w1f + (size_t)(wave * NJ) * 64 + lane;
+            // G::DIRECT: this lane's 16 bytes of the fragment (this wave's first channel tile, column step 0) of the row-major W1 [HD][C];
+            // every other fragment of the wave is a compile-time offset from it
+            const int8_t *w1d = reinterpret_cast<const int8_t *>(p.w1f) + (wave * CT1 * 16 + tl) * G::C + g * 16;
             v4i wf[WD + 1][NJ], bf[2][NTT], acc[NJ][NTT], bias_n[NJ];
-            v2d cq[NJ][2];
+            v2d cq[NJ][2], dq[G::DIRECT ? NJ : 1][4];
             auto load_w = [&](int s, int slot) __attribute__((always_inline)) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) wf[slot][j] = w1[(size_t)(s * NJ * G::WAVES + j) * 64];
+                for (int j = 0; j < NJ; ++j) {
+                    if constexpr (G::DIRECT)
+                        wf[slot][j] = *reinterpret_cast<const v4i *>(w1d + (((s / G::KS1) * NJ + j) * 16) * G::C + (s % G::KS1) * 64);
+                    else wf[slot][j] = w1[(size_t)(s * NJ * G::WAVES + j) * 64];
+                }
             };
             auto load_b = [&](int s, int slot) __attribute__((always_inline)) {
                 const int ks = s % G::KS1;
@@ -77,8 +92,10 @@
             };
             auto load_bias = [&](int chunk) __attribute__((always_inline)) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    bias_n[j] = *reinterpret_cast<const v4i *>(p.b1 + (wave * CT1 + chunk * NJ + j) * 16 + 4 * g);
+                for (int j = 0; j < NJ; ++j) {
+                    if (G::DIRECT && !p.b1) bias_n[j] = v4i{0, 0, 0, 0};
+                    else bias_n[j] = *reinterpret_cast<const v4i *>(p.b1 + (wave * CT1 + chunk * NJ + j) * 16 + 4 * g);
+                }
             };
 #pragma unroll
             for (int s = 0; s < WD; ++s) load_w(s, s);
@@ -94,8 +111,13 @@
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
                         const int ch0 = (ct0 + j) * 16 + 4 * g;
-                        cq[j][0] = *reinterpret_cast<const v2d *>(p.cq1 + ch0);
-                        cq[j][1] = *reinterpret_cast<const v2d *>(p.cq1 + ch0 + 2);
+                        if constexpr (G::DIRECT) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) dq[j][e] = reinterpret_cast<const v2d *>(p.cq1)[ch0 + e];
+                        } else {
+                            cq[j][0] = *reinterpret_cast<const v2d *>(p.cq1 + ch0);
+                            cq[j][1] = *reinterpret_cast<const v2d *>(p.cq1 + ch0 + 2);
+                        }
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -115,6 +137,7 @@
                     if (chunk == 0) __syncthreads();                       // B1: the hidden tile is free
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
+                        if constexpr (G::DIRECT) dy_c(dq[j], cq[j]);
                         const int ch0 = (ct0 + j) * 16 + 4 * g;               // this lane's 4 hidden channels
                         const int kb = ch0 >> 6, cc = (ch0 >> 4) & 3;           // fc2 K block and chunk of these channels
 #pragma unroll
@@ -202,10 +225,14 @@
         // ---- fc2 + qact2 (16 bit) + qact4 with the identity branch (16 bit)
         {
             const v4i *w2 = p.w2f + (size_t)(wave * NJ) * 64 + lane;
+            const int8_t *w2d = reinterpret_cast<const int8_t *>(p.w2f) + (wave * NJ * 16 + tl) * G::HD + g * 16;      // G::DIRECT: as w1d, of W2 [C][HD]
             v4i wf[WD + 1][NJ], bf[2][NTT], acc[NJ][NTT];
             auto load_w = [&](int s, int slot) __attribute__((always_inline)) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) wf[slot][j] = w2[(size_t)(s * NJ * G::WAVES + j) * 64];
+                for (int j = 0; j < NJ; ++j) {
+                    if constexpr (G::DIRECT) wf[slot][j] = *reinterpret_cast<const v4i *>(w2d + (j * 16) * G::HD + s * 64);
+                    else wf[slot][j] = w2[(size_t)(s * NJ * G::WAVES + j) * 64];
+                }
             };
             auto load_b = [&](int s, int slot) __attribute__((always_inline)) {
 #pragma unroll
@@ -215,15 +242,18 @@
 #pragma unroll
             for (int s = 0; s < WD; ++s) load_w(s, s);
             load_b(0, 0);
-            // identity rows and multipliers of this lane's outputs: requested now, consumed after the K loop
+            // identity rows and multipliers of this lane's outputs: requested now, consumed after the K loop (G::DIRECT: the multipliers
+            // are read and formed after the loop, from L2-resident tables: the form that was measured)
             v2i rs[NJ][NTT];
             v2d c2[NJ][2];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const int ch0 = (wave * NJ + j) * 16 + 4 * g;
-                c2[j][0] = *reinterpret_cast<const v2d *>(p.cq2 + ch0);
-                c2[j][1] = *reinterpret_cast<const v2d *>(p.cq2 + ch0 + 2);
-                const v4i b4 = *reinterpret_cast<const v4i *>(p.b2 + ch0);
+                if constexpr (!G::DIRECT) {
+                    c2[j][0] = *reinterpret_cast<const v2d *>(p.cq2 + ch0);
+                    c2[j][1] = *reinterpret_cast<const v2d *>(p.cq2 + ch0 + 2);
+                }
+                const v4i b4 = (G::DIRECT && !p.b2) ? v4i{0, 0, 0, 0} : *reinterpret_cast<const v4i *>(p.b2 + ch0);
 #pragma unroll
                 for (int tt = 0; tt < NTT; ++tt) {
                     acc[j][tt] = b4;
@@ -246,6 +276,12 @@
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const int ch0 = (wave * NJ + j) * 16 + 4 * g;
+                if constexpr (G::DIRECT) {
+                    v2d d[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) d[e] = reinterpret_cast<const v2d *>(p.cq2)[ch0 + e];
+                    dy_c(d, c2[j]);
+                }
 #pragma unroll
                 for (int tt = 0; tt < NTT; ++tt) {
                     int t16[4];

@@ -68,14 +68,17 @@ SliceLayout slice_layout(const ivit_vit_s *m, int B) {
 
 // the shapes ivit_mlp_plan_create has a kernel for: width C, hidden size Hd
 inline bool mlp_plan_shape(int C, int Hd) {
-    return (C == Mlp384Geo::C && Hd == Mlp384Geo::HD) || (C == Mlp192Geo::C && Hd == Mlp192Geo::HD);
+    return (C == Mlp384Geo::C && Hd == Mlp384Geo::HD) || (C == Mlp256Geo::C && Hd == Mlp256Geo::HD) || (C == Mlp192Geo::C && Hd == Mlp192Geo::HD);
 }
 
 // THE rule for "this block's Mlp is one ivit_mlp_fused_planned launch at M tokens": run_slice, swin_run_slice and the
 // ivit_*_fused_mlp_blocks queries all ask here.  No token-count threshold: at width 192 the fused launch measured faster than
 // the three-launch chain at every size tried, 197 tokens (DeiT-T batch 1: 15.8 against 20.0 us) to 200 704 (profiles/README.md)
+inline bool mlp_res_fast(ivit_dyadic res_main, ivit_dyadic res_res) {
+    return fabs(res_main.m * res_main.r) < RQ_FAST_CLIM && fabs(res_res.m * res_res.r) < RQ_FAST_CLIM;
+}
 inline bool mlp_plan_fuses(ivit_mlp_plan mp, ivit_dyadic res_main, ivit_dyadic res_res, long long /*M*/) {
-    return mp && fabs(res_main.m * res_main.r) < RQ_FAST_CLIM && fabs(res_res.m * res_res.r) < RQ_FAST_CLIM;
+    return mp && mlp_res_fast(res_main, res_res);
 }
 
 inline int slice_begin(int batch, int nslices, int i) { return (int)(((long long)batch * i) / nslices); }
@@ -386,9 +389,9 @@ struct ivit_swin_s {
     std::vector<ivit_swin_merge> merges;
     int grid, nblocks;
     ivit_dyadic dy_qact1_host;        // host copy of prm.dy_qact1[0]
-    bool fused_mlp;                   // stage-0 Mlp in one kernel (ivit_mlp_fused)
-    std::vector<ivit_linear_plan> mlp_lin;   // per block: fc1, fc2 plans of the C = 384 and C = 192 stages (null elsewhere)
-    std::vector<ivit_mlp_plan> mlp_plans;    // per block: fused Mlp plan (C = 384 / hidden 1536, C = 192 / hidden 768) or null
+    bool fused_mlp;                   // stage-0 Mlp in one kernel (ivit_mlp_fused: C = 96 or C = 128)
+    std::vector<ivit_linear_plan> mlp_lin;   // per block: fc1, fc2 plans of the C = 384, C = 256 and C = 192 stages (null elsewhere)
+    std::vector<ivit_mlp_plan> mlp_plans;    // per block: fused Mlp plan (C = 384 / hidden 1536, C = 256 / hidden 1024, C = 192 / hidden 768) or null
     std::vector<ivit_linear_plan> lin_plans; // per block: qkv, proj plans prepared for gemm_ws_qkv_kernel where C == 384, else null
     int8_t *gelu_tab;                 // [nblocks][65536]
     int max_slices;
@@ -432,6 +435,8 @@ int swin_ln(const ivit_swin_s *m, ivit_handle h, const int16_t *x, long long M, 
 // how block `bi` (width C) issues its Mlp at M tokens: 0 = fc1 / ShiftGELU / fc2, 1 = ivit_mlp_fused (narrow stage), 2 = ivit_mlp_fused_planned
 int swin_mlp_mode(const ivit_swin_s *m, int bi, int C, long long M) {
     if (C == 96 && m->cfg.mlp_ratio == 4 && m->fused_mlp) return 1;
+    // C = 128 (Swin-B stage 0): the same entry, which at this width takes residual multipliers in the fast range only
+    if (C == Mlp128Geo::C && m->cfg.mlp_ratio == 4 && m->fused_mlp && mlp_res_fast(m->blocks[bi].res2_main, m->blocks[bi].res2_res)) return 1;
     return mlp_plan_fuses(m->mlp_plans[bi], m->blocks[bi].res2_main, m->blocks[bi].res2_res, M) ? 2 : 0;
 }
 
@@ -489,7 +494,7 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             if (mlp_mode == 1) {                                    // narrow stage: hidden tensor stays in LDS
                 RUN(ivit_mlp_fused(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, m->gelu_tab + (size_t)bi * 65536, b.fc2.w, b.fc2.b,
                                    b.fc2.dy, b.res2_main, b.res2_res, x, y, M, C, 4 * C));
-            } else if (mlp_mode == 2) {                             // C = 192 and C = 384 stages: weights streamed, hidden tile in LDS
+            } else if (mlp_mode == 2) {                             // C = 192, C = 256 and C = 384 stages: weights streamed, hidden tile in LDS
                 RUN(ivit_mlp_fused_planned(h, m->mlp_plans[bi], a8, m->gelu_tab + (size_t)bi * 65536, b.res2_main, b.res2_res, x, y, M));
             } else {
                 RUN(ivit_linear_i8_requant(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, 8, h8, (int)M, c.mlp_ratio * C, C));
@@ -601,7 +606,7 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
         int rc = ivit_shiftgelu_build_table(h, m->blocks[i].s_gelu, m->blocks[i].dy_gelu, m->gelu_tab + (size_t)i * 65536);
         if (rc != IVIT_OK) { ivit_swin_destroy(m); return rc; }
     }
-    {   // fused Mlp plans for the C = 192 (hidden 768) and C = 384 (hidden 1536) stages
+    {   // fused Mlp plans for the C = 192 (hidden 768), C = 256 (hidden 1024) and C = 384 (hidden 1536) stages
         int bi = 0;
         for (int li = 0; li < cfg->num_layers; ++li)
             for (int bj = 0; bj < cfg->depths[li]; ++bj, ++bi) {

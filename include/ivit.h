@@ -48,7 +48,9 @@ enum {
     IVIT_ERR_NO_DEVICE = 4
 };
 
-/* 100 * major + minor.  107: ivit_mlp_plan_create also takes 192 -> 768 -> 192 (DeiT-Tiny, Swin stage 1);
+/* 100 * major + minor.  108: ivit_mlp_plan_create also takes 256 -> 1024 -> 256 and ivit_mlp_fused also C = 128, hidden = 512
+ * (Swin-B stages 1 and 0); no prototype changed, no entry added.
+ * 107: ivit_mlp_plan_create also takes 192 -> 768 -> 192 (DeiT-Tiny, Swin stage 1);
  * ivit_vit_fused_mlp_blocks, ivit_swin_fused_mlp_blocks (additions only).
  * 106: the debug entry that copied a plan's store scratch to the host is gone (only probe builds wrote it).
  * 105: ivit_avgpool_requant_scaled (addition); ivit_swin_params gains s_pool at its END — ivit_swin_create
@@ -63,7 +65,7 @@ enum {
  * fields exp_* at their END (added in 100 without a bump: a caller compiled against an older layout must be rebuilt).
  * Parameter structs are read field by field: ZERO-INITIALISE them (memset / = {0}) before filling — exp_aq == NULL (and
  * exp_nc == exp_tcount == exp_dmin == 0) selects the arithmetic Shiftmax, anything else is taken as device pointers.        */
-#define IVIT_VERSION 107
+#define IVIT_VERSION 108
 int ivit_version(void);
 const char *ivit_status_string(int status);
 
@@ -429,7 +431,7 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
 int ivit_swin_destroy(ivit_swin m);
 int ivit_swin_workspace_bytes(ivit_swin m, int batch, int nslices, size_t *bytes);
 /* Per stage: how many blocks of a forward of `batch` images in ONE slice issue their Mlp as a single launch (ivit_mlp_fused in
- * the C = 96 stage, ivit_mlp_fused_planned in the C = 192 and C = 384 stages).  Decided by the rule the forward itself applies;
+ * the C = 96 / C = 128 stage, ivit_mlp_fused_planned in the C = 192, C = 256 and C = 384 stages).  Decided by the rule the forward itself applies;
  * stages the model does not have report 0.                                                                             */
 int ivit_swin_fused_mlp_blocks(ivit_swin m, int batch, int blocks_per_stage[4]);
 int ivit_swin_forward(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace,
@@ -495,19 +497,22 @@ int ivit_window_attention_fused_lut(ivit_handle h, const int8_t *qkv, ivit_dyadi
                                     int8_t *ctx, int B, int R, int window, int shift, int heads, int dh);
 /* Fused Mlp.forward + closing QuantAct(identity) for a narrow stage (layers_quant.py:144-153,
  * swin_quant.py:293-296): fc1 -> qact_gelu(8) -> ShiftGELU -> qact1(8) -> fc2 -> qact2(16) -> qact4(16, +identity)
- * with both weight matrices resident in LDS and the hidden tensor never written to HBM.
+ * with the hidden tensor never written to HBM.  Stateless: the operands are the caller's own arrays, nothing is kept between calls.
  * x int8 [M, C] (norm2 -> qact3), gelu_table from ivit_shiftgelu_build_table, residual / out int16 [M, C].
- * Built for C = 96, hidden = 384 (Swin-T/S stage 0); other shapes: IVIT_ERR_UNSUPPORTED.               */
+ * Built for C = 96, hidden = 384 (Swin-T/S stage 0: both weight matrices resident in LDS or registers) and for C = 128,
+ * hidden = 512 (Swin-B stage 0: the lock-step kernel of csrc/ivit_mlp.h reading w1 / w2 row-major from L2; there x, w1, w2, b1, b2,
+ * dy1, dy2 must be 16-byte aligned, and residual multipliers >= 2^9 are IVIT_ERR_UNSUPPORTED with nothing launched);
+ * other shapes: IVIT_ERR_UNSUPPORTED.                                                                   */
 int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32_t *b1, const ivit_dyadic *dy1,
                    const int8_t *gelu_table, const int8_t *w2, const int32_t *b2, const ivit_dyadic *dy2,
                    ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M,
                    int C, int hidden);
-/* The same chain on frozen linear plans, at two widths: C = 384, hidden = 1536 (DeiT-S, Swin stage 2) and C = 192,
- * hidden = 768 (DeiT-Tiny, Swin-T / S stage 1).  Both weight matrices are re-laid-out once in MFMA-fragment order and
+/* The same chain on frozen linear plans, at three widths: C = 384, hidden = 1536 (DeiT-S, Swin-T / S stage 2), C = 256,
+ * hidden = 1024 (Swin-B stage 1) and C = 192, hidden = 768 (DeiT-Tiny, Swin-T / S stage 1).  Both weight matrices are re-laid-out once in MFMA-fragment order and
  * stream L2 -> registers, the hidden tile of a unit of up to 80 tokens lives in LDS between fc1, the ShiftGELU table pass
- * and fc2 (csrc/ivit_mlp.h: one lock-step kernel body at both widths, two four-wave workgroups per CU at width 192; csrc/ivit_mlp_rs.h).  x, residual and out
+ * and fc2 (csrc/ivit_mlp.h: one lock-step kernel body at every width, two four-wave workgroups per CU at width 192; csrc/ivit_mlp_rs.h).  x, residual and out
  * are [M, C] of the plan's width.  The linear plans are borrowed and must outlive the Mlp plan.
- * IVIT_ERR_UNSUPPORTED for other shapes (fc1 must be [4C x C] and fc2 [C x 4C] with C = 384 or 192), for plans whose requant bound is not provable, and (at call time) for
+ * IVIT_ERR_UNSUPPORTED for other shapes (fc1 must be [4C x C] and fc2 [C x 4C] with C = 384, 256 or 192), for plans whose requant bound is not provable, and (at call time) for
  * residual multipliers >= 2^9: callers then run the unfused chain.  Replaces layers_quant.py:144-153 +
  * vit_quant.py:141-142 (swin_quant.py:296-300) like ivit_mlp_fused.                                        */
 typedef struct ivit_mlp_plan_s *ivit_mlp_plan;
@@ -517,7 +522,7 @@ int ivit_mlp_plan_destroy(ivit_mlp_plan p);
  * the role-split kernel of csrc/ivit_mlp_rs.h from two 80-token units per CU on, the lock-step kernel of csrc/ivit_mlp.h
  * below that), 1 = lock-step, 2 = role-split.  Both compute the same integers (layers_quant.py:144-153).  NOT safe to call
  * while another thread or stream is inside ivit_mlp_fused_planned on the same plan: it rewrites a field the launch reads.
- * A width-192 plan has the lock-step kernel only: 0 and 1 succeed, 2 returns IVIT_ERR_UNSUPPORTED and changes nothing.  */
+ * A width-192 or width-256 plan has the lock-step kernel only: 0 and 1 succeed, 2 returns IVIT_ERR_UNSUPPORTED and changes nothing.  */
 int ivit_mlp_plan_select(ivit_mlp_plan p, int kernel);
 int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, const int8_t *gelu_table,
                            ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual, int16_t *out,
@@ -526,7 +531,7 @@ int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, cons
  * normalises the rows it is going to multiply (x16 [M, 384], the block's 16-bit stream, which is also the identity branch; scale /
  * bias_int / sc / ln_dy as for ivit_layernorm_requant) into scratch8 [M, 384] and reads its activation tiles from there.  out ==
  * ivit_layernorm_requant followed by ivit_mlp_fused_planned.  IVIT_ERR_UNSUPPORTED (nothing launched) where ivit_mlp_fused_planned is,
- * where the launch would run on the lock-step kernel (fewer than two units per CU), and on a width-192 plan.                      */
+ * where the launch would run on the lock-step kernel (fewer than two units per CU), and on a width-192 or width-256 plan.         */
 int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int,
                                      const float *sc, const ivit_dyadic *ln_dy, int8_t *scratch8, const int8_t *gelu_table,
                                      ivit_dyadic dy_main, ivit_dyadic dy_res, int16_t *out, int64_t M);
