@@ -185,6 +185,7 @@ SIGNATURES = {
     "ivit_vit_destroy": [_P],
     "ivit_vit_workspace_bytes": [_P, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
     "ivit_vit_fused_mlp_blocks": [_P, _I, ctypes.POINTER(_I)],
+    "ivit_vit_cls_tail": [_P, _I, ctypes.POINTER(_I)],
     "ivit_swin_fused_mlp_blocks": [_P, _I, ctypes.POINTER(_I * 4)],
     "ivit_vit_workspace_init": [_P, _P, ctypes.c_size_t, _I, _I],
     "ivit_vit_forward": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P],
@@ -213,6 +214,10 @@ SIGNATURES = {
     "ivit_attention_fused_lut": [_P, _P, _P, _P, Dyadic, _F, _P, _P, _P, _I, _I, _I, Dyadic, _P, _I, _I, _I, _I, _I],
     "ivit_shiftmax_rowtable": [_P, _P, _P, _P, _I, _I, _I, _P],
     "ivit_attention_fused_rowlut": [_P, _P, _P, _P, Dyadic, _F, _P, _I, Dyadic, _P, _I, _I, _I, _I, _I],
+    "ivit_attention_fused_cls": [_P, _P, _P, _P, Dyadic, _F, Dyadic, _P, _P, _P, _I, _I, _I, _I, _I],
+    "ivit_attention_fused_lut_cls": [_P, _P, _P, _P, Dyadic, _F, _P, _P, _P, _I, _I, _I, Dyadic, _P, _P, _P, _I, _I, _I, _I, _I],
+    "ivit_attention_fused_rowlut_cls": [_P, _P, _P, _P, Dyadic, _F, _P, _I, Dyadic, _P, _P, _P, _I, _I, _I, _I, _I],
+    "ivit_gather_rows_i16": [_P, _P, _L, _I, _L, _P],
     "ivit_requant_i32": [_P, _P, _P, _I, _P, _P, _I, _P, _L, _I],
     "ivit_requant_f32": [_P, _P, _P, _I, _P, _P, _I, _P, _L, _I],
     "ivit_shiftmax": [_P, _P, _L, _I, _I, _F, _I, _P, _I],

@@ -31,6 +31,12 @@ struct AttnArgs {
     // optional ROW tables (ivit_shiftmax_rowtable): rowtab[vmax + 128][dd] = exp_int of a score v = vmax + dmin + dd in a row
     // whose maximum is vmax, dd = max(v - vmax, dmin) - dmin in [0, 64): both table levels above folded per row maximum
     const float *rowtab;       // [256][64]
+    // class-token form (CLS = true) only: the first nq query rows of every image are worked and written to ctx as [B, ctx_rows, H*64]
+    // (the whole-T form works T rows into [B, T, H*64]); and the workgroup's 64-channel piece of row b*T of the 16-bit stream
+    // x16 [B*T, H*64] goes to x_cls [B, H*64] — the identity rows of the proj that follows (both null: no copy)
+    int nq, ctx_rows;
+    const int16_t *x16;
+    int16_t *x_cls;
 };
 #define ATT_HAS_ROWTAB 1
 // LDS of the row-line form: per wavefront 16 lines (one per query of the tile) of 64 entries at a pitch of 66 dwords — 8-byte
@@ -74,7 +80,9 @@ struct AttCfg {
 // VROW (round 6, with LUT = 2): v arrives ROW-major [B*H, T, 64] like q and k (p.ldv == 0) and is transposed on its way into the
 // LDS — four keys x 16 channels per thread, byte-transposed in registers with v_perm — instead of v^T [B*H, 64, ldv] written by the
 // qkv GEMM with sixteen byte stores per token (which cost that GEMM ~20 % of its time).
-template <int NB, bool FAST, int TT = 0, int LUT = 0, bool VROW = false>
+// CLS: K and V are staged whole, but only the query tiles of rows [0, p.nq) are worked (the last block of a ViT: the head reads
+// the class token's row alone, and a context row depends on its own q row only); the waves without a tile help stage and stop.
+template <int NB, bool FAST, int TT = 0, int LUT = 0, bool VROW = false, bool CLS = false>
 __global__ __launch_bounds__(ATT_WAVES * 64, 1) void attn_fused_kernel(AttnArgs p) {
     using C = AttCfg<NB>;
     extern __shared__ __attribute__((aligned(16))) char dsmem[];
@@ -224,19 +232,26 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 1) void attn_fused_kernel(AttnArgs 
     const double c_qk = p.dy_qk.m * p.dy_qk.r, c_pv = p.dy_pv.m * p.dy_pv.r;
     // |q.k| <= 64*2^14 = 2^20 and |sum P*v| <= 2^15*2^7 = 2^22 (sum P <= 2^15): rq_fast is exact if |c| < 2^9
     const int ntile = (T + 15) >> 4;       // live 16-key tiles
-    const int nqt = (T + 15) >> 4;         // query tiles
+    const int nqt = CLS ? (p.nq + 15) >> 4 : (T + 15) >> 4;         // query tiles
+    const int qrows = CLS ? p.nq : T, orows = CLS ? p.ctx_rows : T;   // query rows worked; rows per image in ctx
+    if constexpr (CLS) {
+        // the identity rows: 64 channels x 2 bytes of row b*T, eight 16-byte pieces, by a wave that has no query tile
+        if (p.x16 && wave == ATT_WAVES - 1 && lane < 8)
+            *reinterpret_cast<v4i *>(p.x_cls + (long long)b * (p.H * 64) + h * 64 + lane * 8) =
+                *reinterpret_cast<const v4i *>(p.x16 + (long long)b * T * (p.H * 64) + h * 64 + lane * 8);
+    }
     const int nvec = T >> 3, size = nvec >> 2;
 
     // (round 6: requesting this fragment together with the K / V^T rows of the prologue measured 0.5-1 us SLOWER on one box)
     v4i qnext = {0, 0, 0, 0};
-    if (wave < nqt && wave * 16 + qi < T) qnext = *reinterpret_cast<const v4i *>(qg + (wave * 16 + qi) * 64 + g * 16);
+    if (wave < nqt && wave * 16 + qi < qrows) qnext = *reinterpret_cast<const v4i *>(qg + (wave * 16 + qi) * 64 + g * 16);
     for (int qt = wave; qt < nqt; qt += ATT_WAVES) {
         const int q0 = qt * 16;
         // ---- Q fragment (B operand): query qi, dh bytes [16g, 16g+16)
         const v4i qf = qnext;
         if (qt + ATT_WAVES < nqt) {            // the next tile's fragment travels while this one is worked on
             qnext = v4i{0, 0, 0, 0};
-            if (q0 + ATT_WAVES * 16 + qi < T) qnext = *reinterpret_cast<const v4i *>(qg + (q0 + ATT_WAVES * 16 + qi) * 64 + g * 16);
+            if (q0 + ATT_WAVES * 16 + qi < qrows) qnext = *reinterpret_cast<const v4i *>(qg + (q0 + ATT_WAVES * 16 + qi) * 64 + g * 16);
         }
 
         // ---- S^T tiles -> requant -> x~ = fl(fl(Q*s)/s) by table; running integer max
@@ -501,9 +516,9 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 1) void attn_fused_kernel(AttnArgs 
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         {
             const int row = lane >> 2, ch = lane & 3;
-            if (q0 + row < T) {
+            if (q0 + row < qrows) {
                 v4i v = *reinterpret_cast<const v4i *>(so + row * 64 + ch * 16);
-                *reinterpret_cast<v4i *>(p.ctx + ((long long)b * T + q0 + row) * (p.H * 64) + h * 64 + ch * 16) = v;
+                *reinterpret_cast<v4i *>(p.ctx + ((long long)b * orows + q0 + row) * (p.H * 64) + h * 64 + ch * 16) = v;
             }
         }
         __builtin_amdgcn_wave_barrier();

@@ -973,7 +973,7 @@ int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16
 
 }  // extern "C"
 
-template <int NB, bool FAST, int TT = 0, int LUT = 0, bool VROW = false>
+template <int NB, bool FAST, int TT = 0, int LUT = 0, bool VROW = false, bool CLS = false>
 static int launch_attn2(ivit_handle h, const AttnArgs &a, int BH) {
     const size_t lds = AttCfg<NB>::SMEM + (LUT == 2 ? (size_t)ATT_ROWLINE_BYTES
                                                    : (LUT == 1 ? (size_t)((a.t_count + 3) & ~3) * 4 + (size_t)a.nc * 512 + 256 : 0));
@@ -983,13 +983,13 @@ static int launch_attn2(ivit_handle h, const AttnArgs &a, int BH) {
         static std::atomic<int> set_dev[IVIT_MAX_DEVICES];
         const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
         if (!cached || set_dev[h->device].load(std::memory_order_acquire) < (int)lds) {
-            hipError_t e = hipFuncSetAttribute((const void *)attn_fused_kernel<NB, FAST, TT, LUT, VROW>,
+            hipError_t e = hipFuncSetAttribute((const void *)attn_fused_kernel<NB, FAST, TT, LUT, VROW, CLS>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "attn attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
             if (cached) set_dev[h->device].store((int)lds, std::memory_order_release);
         }
     }
-    attn_fused_kernel<NB, FAST, TT, LUT, VROW><<<BH, ATT_WAVES * 64, lds, h->stream>>>(a);
+    attn_fused_kernel<NB, FAST, TT, LUT, VROW, CLS><<<BH, ATT_WAVES * 64, lds, h->stream>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "attn launch: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
     return IVIT_OK;
@@ -1018,12 +1018,27 @@ static int launch_attn(ivit_handle h, const AttnArgs &a, int BH) {
     return fast ? launch_attn2<NB, true>(h, a, BH) : launch_attn2<NB, false>(h, a, BH);
 }
 
+// the class-token form (a.nq != 0): the same Shiftmax forms, token count at run time (one query tile per workgroup: the
+// folded tile tests of the fixed-T instantiations have nothing to pay for)
+template <int NB>
+static int launch_attn_cls(ivit_handle h, const AttnArgs &a, int BH) {
+    const double cq = a.dy_qk.m * a.dy_qk.r, cp = a.dy_pv.m * a.dy_pv.r;
+    const bool fast = (cq < 512.0 && cq > -512.0 && cp < 512.0 && cp > -512.0);
+    const bool lut = a.aq && a.et && a.cls;
+    if (a.rowtab) return a.ldv == 0 ? launch_attn2<NB, true, 0, 2, true, true>(h, a, BH) : launch_attn2<NB, true, 0, 2, false, true>(h, a, BH);
+    if (fast && lut) return launch_attn2<NB, true, 0, 1, false, true>(h, a, BH);
+    return fast ? launch_attn2<NB, true, 0, 0, false, true>(h, a, BH) : launch_attn2<NB, false, 0, 0, false, true>(h, a, BH);
+}
+
+// cls_out: ctx8 is the compact [B, H*dh] buffer of the class-token rows (ivit_attention_fused*_cls); x16 / x_cls: their identity rows
 static int attention_fused_impl(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt, ivit_dyadic dy_qk,
                                 float s_softmax, ivit_dyadic dy_pv, int8_t *ctx8, int B, int H, int T, int dh, int ldv,
                                 const uint16_t *aq, const float *et, const uint8_t *cls, int nc, int t_count, int dmin,
-                                const float *rowtab = nullptr) {
+                                const float *rowtab = nullptr, bool cls_out = false, const int16_t *x16 = nullptr, int16_t *x_cls = nullptr) {
     CHECK_H(h);
     REQUIRE(h, q && k && vt && ctx8 && B > 0 && H > 0 && T > 0 && s_softmax > 0.f, "bad arguments");
+    REQUIRE(h, (x16 == nullptr) == (x_cls == nullptr) && (cls_out || !x16), "x16 and x_cls go together (both null: no identity rows)");
+    REQUIRE(h, !cls_out || (((uintptr_t)x16 | (uintptr_t)x_cls | (uintptr_t)ctx8) & 15) == 0, "ctx_cls, x16 and x_cls must be 16-byte aligned");
     REQUIRE(h, ((ldv % 16) == 0 && ldv >= T) || (ldv == 0 && rowtab), "ldv must be a multiple of 16 and >= T (0 = v row-major: ivit_attention_fused_rowlut only)");
     if (dh != 64 || T > 640) {
         snprintf(h->err, sizeof(h->err), "ivit_attention_fused: built for dh == 64, T <= 640");
@@ -1037,6 +1052,12 @@ static int attention_fused_impl(ivit_handle h, const int8_t *q, const int8_t *k,
     a.q = q; a.k = k; a.vt = vt; a.ctx = ctx8; a.T = T; a.H = H; a.ldv = ldv;
     a.s_softmax = s_softmax; a.dy_qk = dy_qk; a.dy_pv = dy_pv;
     a.aq = aq; a.et = et; a.cls = cls; a.nc = nc; a.t_count = t_count; a.dmin = dmin; a.rowtab = rowtab;
+    a.nq = cls_out ? 1 : 0; a.ctx_rows = cls_out ? 1 : T; a.x16 = x16; a.x_cls = x_cls;
+    if (cls_out) {
+        if (T <= 64) return launch_attn_cls<1>(h, a, B * H);
+        if (T <= 256) return launch_attn_cls<4>(h, a, B * H);
+        return launch_attn_cls<10>(h, a, B * H);
+    }
     if (T <= 64) return launch_attn<1>(h, a, B * H);
     if (T <= 256) return launch_attn<4>(h, a, B * H);
     return launch_attn<10>(h, a, B * H);
@@ -1096,6 +1117,59 @@ extern "C" int ivit_attention_fused_rowlut(ivit_handle h, const int8_t *q, const
         return IVIT_ERR_UNSUPPORTED;
     }
     return attention_fused_impl(h, q, k, vt, dy_qk, s_softmax, dy_pv, ctx8, B, H, T, dh, ldv, nullptr, nullptr, nullptr, 0, 0, dmin, rowtab);
+}
+
+// ---- the class-token forms: the context of token 0 of every image into ctx_cls [B, H*dh], its identity row of x16 into x_cls
+extern "C" int ivit_attention_fused_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt, ivit_dyadic dy_qk,
+                                        float s_softmax, ivit_dyadic dy_pv, int8_t *ctx_cls, const int16_t *x16, int16_t *x_cls,
+                                        int B, int H, int T, int dh, int ldv) {
+    return attention_fused_impl(h, q, k, vt, dy_qk, s_softmax, dy_pv, ctx_cls, B, H, T, dh, ldv, nullptr, nullptr, nullptr, 0, 0, 0,
+                                nullptr, true, x16, x_cls);
+}
+
+extern "C" int ivit_attention_fused_lut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt, ivit_dyadic dy_qk,
+                                            float s_softmax, const uint16_t *exp_aq, const float *exp_t, const uint8_t *exp_cls,
+                                            int nclass, int t_count, int dmin, ivit_dyadic dy_pv, int8_t *ctx_cls,
+                                            const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv) {
+    if (h && !(exp_aq && exp_t && exp_cls)) { snprintf(h->err, sizeof(h->err), "%s: null table", __func__); return IVIT_ERR_INVALID; }
+    return attention_fused_impl(h, q, k, vt, dy_qk, s_softmax, dy_pv, ctx_cls, B, H, T, dh, ldv, exp_aq, exp_t, exp_cls, nclass, t_count,
+                                dmin, nullptr, true, x16, x_cls);
+}
+
+extern "C" int ivit_attention_fused_rowlut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt, ivit_dyadic dy_qk,
+                                               float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv, int8_t *ctx_cls,
+                                               const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv) {
+    if (!h) return IVIT_ERR_INVALID;
+    REQUIRE(h, rowtab && ((uintptr_t)rowtab & 15) == 0 && dmin <= 0 && dmin >= -63, "bad row table (16-byte aligned, 1 - dmin <= 64)");
+    const double cq = dy_qk.m * dy_qk.r, cp = dy_pv.m * dy_pv.r;
+    if (!(cq < 512.0 && cq > -512.0 && cp < 512.0 && cp > -512.0)) {
+        snprintf(h->err, sizeof(h->err), "%s: requant multipliers out of the fast range (use ivit_attention_fused_lut_cls)", __func__);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return attention_fused_impl(h, q, k, vt, dy_qk, s_softmax, dy_pv, ctx_cls, B, H, T, dh, ldv, nullptr, nullptr, nullptr, 0, 0, dmin,
+                                rowtab, true, x16, x_cls);
+}
+
+// out[r][:] = x[r * row_stride ...][:C]: `rows` rows of C 16-bit values, 16 bytes per thread (the stand-alone form of the identity-row
+// copy that the class-token attention does on the side)
+__global__ __launch_bounds__(256) void gather_rows16_kernel(const int16_t *__restrict__ x, long long row_stride, int C8, long long n,
+                                                            int16_t *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long r = i / C8;
+    const int c = (int)(i - r * C8);
+    reinterpret_cast<v4i *>(out)[i] = *reinterpret_cast<const v4i *>(x + r * row_stride + c * 8);
+}
+
+extern "C" int ivit_gather_rows_i16(ivit_handle h, const int16_t *x, int64_t rows, int C, int64_t row_stride, int16_t *out) {
+    CHECK_H(h);
+    REQUIRE(h, x && out && rows > 0 && C > 0 && row_stride >= C, "bad arguments");
+    REQUIRE(h, (C % 8) == 0 && (row_stride % 8) == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0, "C and row_stride multiples of 8, x and out 16-byte aligned");
+    const long long n = (long long)rows * (C / 8);
+    REQUIRE(h, n < (1LL << 31) * 256, "too many rows");
+    gather_rows16_kernel<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(x, row_stride, C / 8, n, out);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
 }
 
 // ---------------------------------------------------------------- requant

@@ -81,6 +81,14 @@ inline bool mlp_plan_fuses(ivit_mlp_plan mp, ivit_dyadic res_main, ivit_dyadic r
     return mp && mlp_res_fast(res_main, res_res);
 }
 
+// THE rule for "the last block runs its attention, proj, norm2 and Mlp on the class-token rows only": run_slice and ivit_vit_cls_tail
+// ask here.  Everything behind a block's attention is row-local and a context row depends on its own q row alone, while the head reads
+// row 0 of each image only — so behind the last block's qkv GEMM (k and v need every token) the other T - 1 rows are work nobody
+// reads.  Needs the fused attention (its class-token form) and the dead PatchEmbed buffers large enough for the compact rows
+inline bool cls_tail(const ivit_vit_s *m) {
+    return m->fused_attention && (size_t)m->num_patches * m->Kp >= (size_t)m->cfg.embed_dim;
+}
+
 inline int slice_begin(int batch, int nslices, int i) { return (int)(((long long)batch * i) / nslices); }
 inline int max_slice(int batch, int nslices) { return (batch + nslices - 1) / nslices; }
 
@@ -116,6 +124,10 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         // a layer on the row-table attention takes v ROW-major (ldv = 0: the qkv GEMM stores 16 bytes per lane instead of 16 byte
         // stores, the attention kernel transposes on its way into the LDS); the other attention forms read v^T
         const int ldv = (m->fused_attention && m->has_rowtab[i]) ? 0 : ld;
+        // last block: from the attention on, the B class-token rows only (cls_tail), compact in the buffers PatchEmbed has left:
+        // context rows in `patches`, the identity rows — copied by the attention launch — in `patch16`
+        const bool tail = i == c.depth - 1 && cls_tail(m);
+        const int Mb = tail ? B : M;      // rows behind the attention
         // norm1's 8-bit output has one consumer: where the qkv GEMM keeps a CU's tokens in LDS it is computed there (round 6)
         rc = ldv == 0 ? ivit_layernorm_linear_i8_qkv_planned(h, m->plans[4 * i], x, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, q, k, vt, B, T, H, dh)
                       : IVIT_ERR_UNSUPPORTED;
@@ -125,7 +137,19 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         } else {
             RUN(rc);
         }
-        if (m->fused_attention) {
+        if (tail) {
+            int8_t *ctxc = patches;
+            if (m->has_rowtab[i])
+                RUN(ivit_attention_fused_rowlut_cls(h, q, k, vt, b.dy_qk, b.s_softmax, m->rowtab + (size_t)i * 256 * 64, b.exp_dmin, b.dy_pv,
+                                                    ctxc, x, patch16, B, H, T, dh, ldv));
+            else if (b.exp_aq)
+                RUN(ivit_attention_fused_lut_cls(h, q, k, vt, b.dy_qk, b.s_softmax, b.exp_aq, b.exp_t, b.exp_cls, b.exp_nc,
+                                                 b.exp_tcount, b.exp_dmin, b.dy_pv, ctxc, x, patch16, B, H, T, dh, ld));
+            else
+                RUN(ivit_attention_fused_cls(h, q, k, vt, b.dy_qk, b.s_softmax, b.dy_pv, ctxc, x, patch16, B, H, T, dh, ld));
+            ctx8 = ctxc;
+            x = patch16;                // [B, D]; proj writes y, the Mlp writes patch16 again
+        } else if (m->fused_attention) {
             if (m->has_rowtab[i])      // one gather per score (round 6)
                 RUN(ivit_attention_fused_rowlut(h, q, k, vt, b.dy_qk, b.s_softmax, m->rowtab + (size_t)i * 256 * 64, b.exp_dmin, b.dy_pv,
                                                 ctx8, B, H, T, dh, ldv));
@@ -144,28 +168,29 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         // attn.proj + qact2 with the identity branch, then norm2 + qact3 and the Mlp.  norm2 rides in the HEAD of the fused Mlp's launch
         // (ivit_layernorm_mlp_fused_planned) where that kernel takes the shape; in the tail of the proj launch it measured slower
         // (profiles/README.md)
-        const bool mlp_fast = mlp_plan_fuses(m->mlp_plans[i], b.res2_main, b.res2_res, M);
-        RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, M));
+        const bool mlp_fast = mlp_plan_fuses(m->mlp_plans[i], b.res2_main, b.res2_res, Mb);
+        RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, Mb));
         { int16_t *t = x; x = y; y = t; }
         rc = mlp_fast ? ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8,
-                                                         m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, y, M)
+                                                         m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, y, Mb)
                       : IVIT_ERR_UNSUPPORTED;
         if (rc == IVIT_ERR_UNSUPPORTED) {
-            RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8));
+            RUN(ivit_layernorm_requant(h, x, Mb, D, D, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8));
             if (mlp_fast) {     // hidden tensor stays in LDS
-                RUN(ivit_mlp_fused_planned(h, m->mlp_plans[i], a8, m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, x, y, M));
+                RUN(ivit_mlp_fused_planned(h, m->mlp_plans[i], a8, m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, x, y, Mb));
             } else {
-                RUN(ivit_linear_i8_requant_planned(h, m->plans[4 * i + 2], a8, 8, h8, M));
-                RUN(ivit_shiftgelu_requant_lut(h, h8, M, Hd, m->gelu_tab + (size_t)i * 65536, g8));
-                RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, M));
+                RUN(ivit_linear_i8_requant_planned(h, m->plans[4 * i + 2], a8, 8, h8, Mb));
+                RUN(ivit_shiftgelu_requant_lut(h, h8, Mb, Hd, m->gelu_tab + (size_t)i * 65536, g8));
+                RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, Mb));
             }
         } else {
             RUN(rc);
         }
         { int16_t *t = x; x = y; y = t; }
     }
-    // final norm on the class-token rows only (row stride T*D), then the head's int32 accumulators
-    RUN(ivit_layernorm_requant(h, x, B, D, (int64_t)T * D, P.s_ln, P.n_bias_int, P.n_sc, P.n_dy, cls8));
+    // final norm on the class-token rows only (row stride T*D; D where the last block left them compact), then the head's int32
+    // accumulators
+    RUN(ivit_layernorm_requant(h, x, B, D, cls_tail(m) ? (int64_t)D : (int64_t)T * D, P.s_ln, P.n_bias_int, P.n_sc, P.n_dy, cls8));
     RUN(ivit_linear_i8(h, cls8, P.head_w, P.head_b, logits, B, c.num_classes, D));
 #undef RUN
     return IVIT_OK;
@@ -288,6 +313,13 @@ int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks) {
     for (int i = 0; i < m->cfg.depth; ++i)
         n += mlp_plan_fuses(m->mlp_plans[i], m->blocks[i].res2_main, m->blocks[i].res2_res, (long long)batch * m->T);
     *blocks = n;
+    return IVIT_OK;
+}
+
+int ivit_vit_cls_tail(ivit_vit m, int batch, int *on) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, on && batch > 0, "bad arguments");
+    *on = cls_tail(m) ? 1 : 0;
     return IVIT_OK;
 }
 

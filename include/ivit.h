@@ -48,7 +48,10 @@ enum {
     IVIT_ERR_NO_DEVICE = 4
 };
 
-/* 100 * major + minor.  108: ivit_mlp_plan_create also takes 256 -> 1024 -> 256 and ivit_mlp_fused also C = 128, hidden = 512
+/* 100 * major + minor.  109: the class-token forms of the fused attention (ivit_attention_fused_cls, ivit_attention_fused_lut_cls,
+ * ivit_attention_fused_rowlut_cls), ivit_gather_rows_i16, ivit_vit_cls_tail (additions only): ivit_vit_forward runs the last
+ * block's attention, proj, norm2 and Mlp on the class-token rows only.
+ * 108: ivit_mlp_plan_create also takes 256 -> 1024 -> 256 and ivit_mlp_fused also C = 128, hidden = 512
  * (Swin-B stages 1 and 0); no prototype changed, no entry added.
  * 107: ivit_mlp_plan_create also takes 192 -> 768 -> 192 (DeiT-Tiny, Swin stage 1);
  * ivit_vit_fused_mlp_blocks, ivit_swin_fused_mlp_blocks (additions only).
@@ -65,7 +68,7 @@ enum {
  * fields exp_* at their END (added in 100 without a bump: a caller compiled against an older layout must be rebuilt).
  * Parameter structs are read field by field: ZERO-INITIALISE them (memset / = {0}) before filling — exp_aq == NULL (and
  * exp_nc == exp_tcount == exp_dmin == 0) selects the arithmetic Shiftmax, anything else is taken as device pointers.        */
-#define IVIT_VERSION 108
+#define IVIT_VERSION 109
 int ivit_version(void);
 const char *ivit_status_string(int status);
 
@@ -243,6 +246,26 @@ int ivit_attention_fused_rowlut(ivit_handle h, const int8_t *q, const int8_t *k,
                                 ivit_dyadic dy_qk, float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv,
                                 int8_t *ctx8, int B, int H, int T, int dh, int ldv);
 
+/* Class-token forms of the three entries above (vit_quant.py:70-83 for query row 0 of every image; the head, vit_quant.py:271-281,
+ * reads that row alone).  A context row depends on its own q row and on k and v of all tokens: K and V are staged as in the whole-T
+ * form and one query tile is worked.  ctx_cls int8 [B, H*dh] receives what the whole-T entry writes to rows b*T of ctx8, the same
+ * integers.  x16 / x_cls (both NULL: skipped): row b*T of the 16-bit stream x16 [B*T, H*dh] is copied to x_cls [B, H*dh] on the side
+ * — the identity rows of the attn.proj that follows (vit_quant.py:135).  ctx_cls, x16 and x_cls 16-byte aligned; otherwise the
+ * arguments, limits and status codes of the whole-T entry of the same Shiftmax form.                                               */
+int ivit_attention_fused_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
+                             ivit_dyadic dy_qk, float s_softmax, ivit_dyadic dy_pv, int8_t *ctx_cls,
+                             const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
+int ivit_attention_fused_lut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
+                                 ivit_dyadic dy_qk, float s_softmax, const uint16_t *exp_aq, const float *exp_t,
+                                 const uint8_t *exp_cls, int nclass, int t_count, int dmin, ivit_dyadic dy_pv,
+                                 int8_t *ctx_cls, const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
+int ivit_attention_fused_rowlut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
+                                    ivit_dyadic dy_qk, float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv,
+                                    int8_t *ctx_cls, const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
+/* out[r, :] = x[r * row_stride : r * row_stride + C] for r < rows (16-bit values; x[:, 0] of vit_quant.py:272 with
+ * row_stride = T * C): the identity-row copy above as a launch of its own.  C and row_stride multiples of 8, 16-byte aligned.    */
+int ivit_gather_rows_i16(ivit_handle h, const int16_t *x, int64_t rows, int C, int64_t row_stride, int16_t *out);
+
 /* ---- a3  QuantAct.forward with a previous scale -> fixedpoint_mul.forward
  * (quant_modules.py:197-206, quant_utils.py:192-253).  z int32 or float (integer-valued;
  * the I-LayerNorm output exceeds int32), [rows, C];  dy has nch = 1 or C entries;
@@ -363,6 +386,10 @@ int ivit_vit_workspace_bytes(ivit_vit m, int batch, int nslices, size_t *bytes);
 /* How many blocks of a forward of `batch` images in ONE slice issue their Mlp as a single launch (the fused kernels of
  * ivit_mlp_plan_create); the other blocks run fc1 / ShiftGELU / fc2 as three.  Decided by the rule the forward itself applies. */
 int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks);
+/* *on = 1 when a forward of `batch` images runs the last block's attention, attn.proj, norm2 and Mlp on the class-token rows only
+ * (B rows instead of B*T; the head reads no other row, vit_quant.py:271-281): models on the fused attention (dh == 64, T <= 640).
+ * Same logits either way.  Decided by the rule the forward itself applies.                                                      */
+int ivit_vit_cls_tail(ivit_vit m, int batch, int *on);
 /* Must run once per (workspace, batch, nslices) before the first forward (zeroes the padded
  * key columns of the transposed V buffers); asynchronous on the handle's stream.               */
 int ivit_vit_workspace_init(ivit_vit m, void *workspace, size_t bytes, int batch, int nslices);
