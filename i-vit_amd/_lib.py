@@ -185,6 +185,7 @@ SIGNATURES = {
     "ivit_vit_destroy": [_P],
     "ivit_vit_workspace_bytes": [_P, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
     "ivit_vit_fused_mlp_blocks": [_P, _I, ctypes.POINTER(_I)],
+    "ivit_vit_fused_qkv_blocks": [_P, _I, ctypes.POINTER(_I)],
     "ivit_vit_cls_tail": [_P, _I, ctypes.POINTER(_I)],
     "ivit_swin_fused_mlp_blocks": [_P, _I, ctypes.POINTER(_I * 4)],
     "ivit_vit_workspace_init": [_P, _P, ctypes.c_size_t, _I, _I],
@@ -206,6 +207,7 @@ SIGNATURES = {
     "ivit_layernorm_linear_i8_requant_planned": [_P, _P, _P, _F, _P, _P, _P, _P, _I],
     "ivit_linear_i8_requant_residual_layernorm_planned": [_P, _P, _P, Dyadic, Dyadic, _P, _P, _I, _F, _P, _P, _P, _P],
     "ivit_layernorm_linear_i8_qkv_planned": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
+    "ivit_layernorm_linear_i8_qkv_ldv_planned": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I],
     "ivit_bmm_nt_i8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L],
     "ivit_bmm_nt_u16i8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L],
     "ivit_attn_qk_requant": [_P, _P, _P, Dyadic, _P, _I, _I, _I, _I],

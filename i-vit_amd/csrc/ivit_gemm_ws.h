@@ -18,27 +18,48 @@
 //     store in front of it).
 //
 // Measured stand-alone at DeiT-S b256: profiles/README.md, round 6.
+//
+// The text above is the K = 384 geometry (Ws384Geo).  The same source at K = 192 (Ws192Geo: DeiT-Tiny, Swin stage 1): 6 k-steps, 3 K blocks,
+// 48 weight registers per slab, 14 tiles per panel swept in pairs by a loop, and — for layers whose attention reads v^T — a second store form
+// of the qkv epilogue (VT).  Measured: profiles/README.md, "Width 192 on the weights-in-registers GEMM".
 #pragma once
 #include "ivit_layernorm.h"
 #include <type_traits>
 
-#define WS_K 384
-#define WS_KS 12                                 // k-steps of 32
-#define WS_MAXT 7                                // 32-token tiles of a panel in LDS
-#define WS_TOK (WS_MAXT * 32)
-#define WS_KBLK (WS_TOK * 64)
-#define WS_SOFF (6 * WS_KBLK)                     // output row offset of each token of the panel (int)
-#define WS_SBIAS (WS_SOFF + WS_TOK * 4)           // the layer's bias (int32 x N) and multipliers (double x N)
+// One source, two widths.  K = 384: 7 tiles x 32 tokens x 384 B = 86 KB per panel, 96 weight registers per slab.  K = 192: a tile is
+// 6 KB and a slab 48 registers; the LDS that frees goes to a panel twice as long (14 tiles, the same 86 KB: a CU that owns more than
+// 7 tiles — Swin stage 1 at large batch — passes half as many panel barriers), the registers stay free (the sweep is two token tiles
+// as at 384: at four, EPI_RES16's identity rows alone are 64 registers).  VT: the geometry also builds the v^T store form of the
+// qkv epilogue, which keeps a second per-token offset table behind the LayerNorm constants
+template <int K_, int MAXT_, bool VT_>
+struct WsGeo {
+    static constexpr int K = K_;
+    static constexpr int KS = K_ / 32;                  // k-steps of 32
+    static constexpr int KB = K_ / 64;                  // K blocks of 64 columns
+    static constexpr int MAXT = MAXT_;                  // 32-token tiles of a panel in LDS
+    static constexpr int TOK = MAXT * 32;
+    static constexpr int KBLK = TOK * 64;
+    static constexpr int SOFF = KB * KBLK;              // output row offset of each token of the panel (int)
+    static constexpr int SBIAS = SOFF + TOK * 4;        // the layer's bias (int32 x N) and multipliers (double x N)
+    static constexpr int MAXN = 1536;
+    static constexpr int SCQ = SBIAS + MAXN * 4;
+    static constexpr int SLN = SCQ + MAXN * 8;          // LayerNorm's per-channel constants: c (double), bias_int, sc, 1 / sc (float) x K
+    static constexpr int SVOFF = SLN + K * 20;          // v^T form: offset of each token's column in its image's v^T (int)
+    static constexpr bool VT = VT_;
+    static constexpr int SMEM = SVOFF + (VT ? TOK * 4 : 0);
+    static_assert(K % 64 == 0 && TOK <= 512 && KBLK % 256 == 0, "whole K blocks; one thread per token of a panel; K blocks a whole number of bank periods apart");
+    static_assert(SMEM <= 160 * 1024, "one workgroup per CU");
+};
+typedef WsGeo<384, 7, false> Ws384Geo;
+typedef WsGeo<192, 14, true> Ws192Geo;
 #define WS_MAXN 1536
-#define WS_SCQ (WS_SBIAS + WS_MAXN * 4)
-#define WS_SLN (WS_SCQ + WS_MAXN * 8)             // LayerNorm's per-channel constants: c (double), bias_int, sc, 1 / sc (float) x 384
-#define WS_SMEM (WS_SLN + WS_K * 20)
+inline bool ws_width(int K) { return K == Ws384Geo::K || K == Ws192Geo::K; }
 #define WS_THREADS 512
 #define WS_MAGIC 6755399441055744.0
 
 struct WsArgs {
-    const int8_t *x;          // [M][384] 8-bit activations (LN = false)
-    const v4i *wf;            // swizzled weights: fragment (ct * 12 + ks) * 64 + lane
+    const int8_t *x;          // [M][K] 8-bit activations (LN = false)
+    const v4i *wf;            // swizzled weights: fragment (ct * (K / 32) + ks) * 64 + lane
     const int32_t *bias;      // [N]
     const double *cq;         // [N]
     int8_t *q, *k, *v;        // [B*H][T][64] each
@@ -47,6 +68,7 @@ struct WsArgs {
     // LN = true: the block's 16-bit input and norm1's constants (the arguments of ivit_layernorm_requant)
     const int16_t *x16;
     float ln_s;
+    int ldv;                  // EPI_QKV8 with VT = true: v is v^T [B*H][64][ldv], element (b, h, t, ch) at ((b * H + h) * 64 + ch) * ldv + t
     const float *ln_bias_int, *ln_sc;
     const ivit_dyadic *ln_dy;
     // EPI = WS_EPI_RES16 (attn.proj + qact2 with the identity branch, vit_quant.py:137-138 + quant_utils.py:238-244): out16 [M][N]
@@ -63,18 +85,20 @@ struct WsArgs {
 __device__ __forceinline__ int ws_chan_of_row(int rho) { return ((rho >> 2) & 1) * 16 + (rho >> 3) * 4 + (rho & 3); }
 __device__ __forceinline__ int ws_g(int tok) { return ((tok >> 1) & 3) ^ ((tok >> 3) & 3) ^ ((tok >> 4) & 1); }
 
-// weights [N][384] -> fragments of 64 lanes x 16 B: fragment ct * 12 + ks, lane l = (row l & 31, k half l >> 5)
-__global__ __launch_bounds__(256) void ws_swizzle_kernel(const int8_t *__restrict__ w, v4i *__restrict__ wf, int N) {
-    const int nfrag = N / 32 * WS_KS;
+// weights [N][K] -> fragments of 64 lanes x 16 B: fragment ct * (K / 32) + ks, lane l = (row l & 31, k half l >> 5)
+__global__ __launch_bounds__(256) void ws_swizzle_kernel(const int8_t *__restrict__ w, v4i *__restrict__ wf, int N, int K) {
+    const int nks = K / 32, nfrag = N / 32 * nks;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nfrag * 64; i += gridDim.x * 256) {
-        const int l = i & 63, f = i >> 6, ct = f / WS_KS, ks = f - ct * WS_KS;
+        const int l = i & 63, f = i >> 6, ct = f / nks, ks = f - ct * nks;
         const int ch = 32 * ct + ws_chan_of_row(l & 31);
-        wf[i] = *reinterpret_cast<const v4i *>(w + (size_t)ch * WS_K + 32 * ks + 16 * (l >> 5));
+        wf[i] = *reinterpret_cast<const v4i *>(w + (size_t)ch * K + 32 * ks + 16 * (l >> 5));
     }
 }
 
-template <bool FMA, bool LN, int EPI = WS_EPI_QKV8>
+template <class G, bool FMA, bool LN, int EPI = WS_EPI_QKV8, bool VT = false>
 __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
+    static_assert(!VT || (G::VT && EPI == WS_EPI_QKV8), "the v^T store form belongs to the qkv scatter of a geometry that keeps its table");
+    static_assert(!(LN && EPI == WS_EPI_RES16) || G::K == 384, "norm2 in the proj launch is built at 384 only");
     extern __shared__ __attribute__((aligned(256))) char sm[];
     typedef double v2d __attribute__((ext_vector_type(2)));
     typedef __attribute__((address_space(3))) char lds_c;
@@ -92,23 +116,23 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
     const int t_beg = (int)((long long)ntt * blockIdx.x / gridDim.x), t_end = (int)((long long)ntt * (blockIdx.x + 1) / gridDim.x);
     const int ncp = p.N >> 6, ncp3 = ncp / 3;                 // 64-channel slabs; per q | k | v
     for (int i = tid; i < p.N; i += WS_THREADS) {
-        reinterpret_cast<int *>(sm + WS_SBIAS)[i] = p.bias[i];
-        reinterpret_cast<double *>(sm + WS_SCQ)[i] = p.cq[i];
+        reinterpret_cast<int *>(sm + G::SBIAS)[i] = p.bias[i];
+        reinterpret_cast<double *>(sm + G::SCQ)[i] = p.cq[i];
     }
     const unsigned lane16 = lane * 16;
-    double *cC = reinterpret_cast<double *>(sm + WS_SLN);
-    float *cB = reinterpret_cast<float *>(sm + WS_SLN + WS_K * 8), *cSc = cB + WS_K, *cY = cSc + WS_K;
+    double *cC = reinterpret_cast<double *>(sm + G::SLN);
+    float *cB = reinterpret_cast<float *>(sm + G::SLN + G::K * 8), *cSc = cB + G::K, *cY = cSc + G::K;
     bool ln_fast = false;
     constexpr bool LN_HEAD = LN && EPI != WS_EPI_RES16, LN_TAIL = LN && EPI == WS_EPI_RES16;
-    if constexpr (LN) ln_fast = ln_stage_constants<WS_K, WS_THREADS>(p.ln_bias_int, p.ln_sc, p.ln_dy, cC, cB, cSc, cY);
+    if constexpr (LN) ln_fast = ln_stage_constants<G::K, WS_THREADS>(p.ln_bias_int, p.ln_sc, p.ln_dy, cC, cB, cSc, cY);
 
-    for (int t0 = t_beg; t0 < t_end; t0 += WS_MAXT) {
-        const int n_own = min(WS_MAXT, t_end - t0);
+    for (int t0 = t_beg; t0 < t_end; t0 += G::MAXT) {
+        const int n_own = min(G::MAXT, t_end - t0);
         if (t0 != t_beg) __syncthreads();            // a later panel: every wave is done with the previous one
         if constexpr (LN_HEAD) {
             // ---- norm1 + qact1 of the panel's rows into the LDS image: 8 rows per wave and pass, 8 lanes per row, lane (k, h)
             // owns channels 32 i + 8 k + 4 h .. + 3 of every step i — 4 bytes of chunk (i & 1) * 2 + (k >> 1) of K block i >> 1
-            typedef LnGroup<WS_K, 2> G;
+            typedef LnGroup<G::K, 2> LG;
             const int j = lane & 7, k = j >> 1, hh = j & 1;
             const float ys = rcp_rn(p.ln_s);
             // (the phase is VALU-issue-bound like layernorm_reg_kernel itself: requesting pass n + 1's rows ahead, or two rows per lane
@@ -117,18 +141,18 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                 const int tokl = r0 + (lane >> 3);
                 const long long row_raw = (long long)t0 * 32 + tokl;
                 const bool live = row_raw < p.M;
-                const int16_t *xp = p.x16 + (live ? row_raw : (long long)p.M - 1) * WS_K + 8 * k + 4 * hh;
-                float xv[G::NSTEP][G::EPC];
+                const int16_t *xp = p.x16 + (live ? row_raw : (long long)p.M - 1) * G::K + 8 * k + 4 * hh;
+                float xv[LG::NSTEP][LG::EPC];
 #pragma unroll
-                for (int i = 0; i < G::NSTEP; ++i) {
+                for (int i = 0; i < LG::NSTEP; ++i) {
                     const LnRaw<4>::T t = *reinterpret_cast<const LnRaw<4>::T *>(xp + 32 * i);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)t[c], p.ln_s, ys);
                 }
                 const unsigned rowa = sm_lds + tokl * 64 + (k & 1) * 8 + 4 * hh, gk = (unsigned)((k >> 1) ^ ws_g(tokl));
-                G::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY,
+                LG::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY,
                        [&](int i, unsigned pk0, unsigned) __attribute__((always_inline)) {
-                           *(lds_u32 *)(size_t)(rowa + (i >> 1) * WS_KBLK + ((gk ^ ((i & 1) * 2)) << 4)) = pk0;
+                           *(lds_u32 *)(size_t)(rowa + (i >> 1) * G::KBLK + ((gk ^ ((i & 1) * 2)) << 4)) = pk0;
                        });
             }
         } else {
@@ -136,19 +160,20 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
             for (int tg = wave; tg < n_own * 2; tg += 8) {
                 const int tokl = tg * 16 + (lane >> 2), c = (lane & 3) ^ ws_g(tokl);
                 const long long grow = min((long long)t0 * 32 + tokl, (long long)p.M - 1);
-                const int8_t *src = p.x + grow * WS_K + c * 16;
+                const int8_t *src = p.x + grow * G::K + c * 16;
 #pragma unroll
-                for (int kb = 0; kb < 6; ++kb) {
-                    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(kb * WS_KBLK + tg * 1024));
+                for (int kb = 0; kb < G::KB; ++kb) {
+                    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(kb * G::KBLK + tg * 1024));
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + kb * 64),
                                                      (__attribute__((address_space(3))) void *)(sm + dst), 16, 0, 0);
                 }
             }
         }
         // output row offset of every token of the panel: (b * H * T + t_in_image) * 64
-        if (tid < WS_TOK) {
+        if (tid < G::TOK) {
             const int row = min(t0 * 32 + tid, p.M - 1), b = row / p.T;
-            reinterpret_cast<int *>(sm + WS_SOFF)[tid] = (b * p.H * p.T + (row - b * p.T)) * 64;
+            reinterpret_cast<int *>(sm + G::SOFF)[tid] = (b * p.H * p.T + (row - b * p.T)) * 64;
+            if constexpr (VT) reinterpret_cast<int *>(sm + G::SVOFF)[tid] = b * p.H * 64 * p.ldv + (row - b * p.T);
         }
         // tasks: (slab, token half); half a = tiles [0, na), half b = [na, n_own)
         const int na = (n_own + 1) >> 1, ntask = n_own > 1 ? 2 * ncp : ncp;
@@ -161,17 +186,22 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
             const int tb0 = half ? na : 0, te = half ? n_own : na;
             // the slab's weights: NOT carried from task to task (loop-carried and redefined behind their last use, the compiler
             // copies all 96 registers at the back edge and spills); the partner wave of the SIMD works through the latency
-            v4i W[2][WS_KS];
+            v4i W[2][G::KS];
             {
-                const char *wq = reinterpret_cast<const char *>(p.wf + (size_t)cp * 2 * WS_KS * 64);
+                const char *wq = reinterpret_cast<const char *>(p.wf + (size_t)cp * 2 * G::KS * 64);
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
-                    for (int ks = 0; ks < WS_KS; ++ks) W[c][ks] = *reinterpret_cast<const v4i *>(wq + lane16 + (c * WS_KS + ks) * 1024);
+                    for (int ks = 0; ks < G::KS; ++ks) W[c][ks] = *reinterpret_cast<const v4i *>(wq + lane16 + (c * G::KS + ks) * 1024);
             }
             const int chb = 64 * cp + 16 * kh;
             const int which = EPI == WS_EPI_QKV8 ? cp / max(ncp3, 1) : 0;
             int8_t *obase = (which == 0 ? p.q : which == 1 ? p.k : p.v) + (size_t)(cp - which * ncp3) * p.T * 64 + 16 * kh;
+            // v^T form: a V slab's lane (token, h) stores its 16 channels as 16 bytes, one per row of the head's [64][ldv] — the 32 lanes
+            // of a half-wave are 32 consecutive tokens, so every store instruction writes runs of consecutive bytes (two where an image
+            // boundary falls inside the tile).  Only tokens t < T exist, so the columns t >= T keep their zeros
+            const bool vslab = VT && which == 2;
+            int8_t *vbase = VT ? p.v + (size_t)((cp - 2 * ncp3) * 64 + 16 * kh) * p.ldv : nullptr;
             auto sweep = [&](auto nt_c, const int tb) __attribute__((always_inline)) {
                 constexpr int NT = decltype(nt_c)::value;
                 v4i bf[2][NT];
@@ -179,11 +209,12 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                 const unsigned fb0 = fa0 + tb * 2048, fb1 = fa1 + tb * 2048;
                 int toff[NT];
 #pragma unroll
-                for (int t = 0; t < NT; ++t) toff[t] = *(lds_i32 *)(size_t)(sm_lds + WS_SOFF + ((tb + t) * 32 + tok) * 4);
+                for (int t = 0; t < NT; ++t)
+                    toff[t] = *(lds_i32 *)(size_t)(sm_lds + (vslab ? G::SVOFF : G::SOFF) + ((tb + t) * 32 + tok) * 4);
                 auto load_b = [&](int ks, int slot) __attribute__((always_inline)) {
 #pragma unroll
                     for (int t = 0; t < NT; ++t)
-                        bf[slot][t] = *(lds_v4i *)(size_t)(((ks & 1) ? fb1 : fb0) + (ks >> 1) * WS_KBLK + t * 2048);
+                        bf[slot][t] = *(lds_v4i *)(size_t)(((ks & 1) ? fb1 : fb0) + (ks >> 1) * G::KBLK + t * 2048);
                 };
                 load_b(0, 0);
                 // EPI_RES16: the identity rows of this sweep, requested in front of its K loop (a vector load issued behind the
@@ -204,14 +235,14 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
                     for (int q4 = 0; q4 < 4; ++q4) {
-                        const v4i b4 = *(lds_v4i *)(size_t)(sm_lds + WS_SBIAS + (chb + 32 * c + 4 * q4) * 4);
+                        const v4i b4 = *(lds_v4i *)(size_t)(sm_lds + G::SBIAS + (chb + 32 * c + 4 * q4) * 4);
 #pragma unroll
                         for (int t = 0; t < NT; ++t) { acc[c][t][4 * q4] = b4[0]; acc[c][t][4 * q4 + 1] = b4[1]; acc[c][t][4 * q4 + 2] = b4[2]; acc[c][t][4 * q4 + 3] = b4[3]; }
                     }
 #pragma unroll
-                for (int ks = 0; ks < WS_KS; ++ks) {
+                for (int ks = 0; ks < G::KS; ++ks) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if (ks + 1 < WS_KS) load_b(ks + 1, (ks + 1) & 1);
+                    if (ks + 1 < G::KS) load_b(ks + 1, (ks + 1) & 1);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int c = 0; c < 2; ++c)
@@ -226,7 +257,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                 for (int c = 0; c < 2; ++c) {
                     v2d cqv[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) cqv[j] = *(lds_v2d *)(size_t)(sm_lds + WS_SCQ + (chb + 32 * c + 2 * j) * 8);
+                    for (int j = 0; j < 8; ++j) cqv[j] = *(lds_v2d *)(size_t)(sm_lds + G::SCQ + (chb + 32 * c + 2 * j) * 8);
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         if constexpr (EPI == WS_EPI_RES16) {
@@ -282,17 +313,33 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                         const int row = (t0 + tb + t) * 32 + tok;
                         if constexpr (EPI == WS_EPI_RQ8) {
                             if (row < p.M) *reinterpret_cast<v4i *>(p.q + (long long)row * p.N + chb + 32 * c) = o4;
+                        } else if (vslab) {
+                            if (row < p.M) {
+                                int8_t *vp = vbase + toff[t] + (size_t)(32 * c) * p.ldv;
+#pragma unroll
+                                for (int i = 0; i < 16; ++i) vp[(size_t)i * p.ldv] = (int8_t)(o4[i >> 2] >> (8 * (i & 3)));
+                            }
+                        } else if constexpr (G::MAXT > 8) {
+                            // (the long-panel form predicates the store: with the select below the compiler keeps so much of the
+                            // requant in flight across its sweep loop that the kernel spills)
+                            if (row < p.M) *reinterpret_cast<v4i *>(obase + toff[t] + 32 * c) = o4;
                         } else {
                             *reinterpret_cast<v4i *>(row < p.M ? obase + toff[t] + 32 * c : (int8_t *)p.dummy + lane16) = o4;
                         }
                     }
                 }
             };
-            // a half has one to four tiles
             int tb = tb0;
-            if (te - tb > 2) { sweep(std::integral_constant<int, 2>{}, tb); tb += 2; }
-            if (te - tb == 2) sweep(std::integral_constant<int, 2>{}, tb);
-            else sweep(std::integral_constant<int, 1>{}, tb);
+            if constexpr (G::MAXT <= 8) {
+                // a half has one to four tiles
+                if (te - tb > 2) { sweep(std::integral_constant<int, 2>{}, tb); tb += 2; }
+                if (te - tb == 2) sweep(std::integral_constant<int, 2>{}, tb);
+                else sweep(std::integral_constant<int, 1>{}, tb);
+            } else {
+                // a half has one to MAXT / 2 tiles: pairs, then the odd one
+                for (; te - tb >= 2; tb += 2) sweep(std::integral_constant<int, 2>{}, tb);
+                if (te - tb == 1) sweep(std::integral_constant<int, 1>{}, tb);
+            }
         }
         if constexpr (LN_TAIL) {
             // ---- norm2 + qact3 of the panel's rows (vit_quant.py:139-140): every channel of a row was produced by this workgroup;
@@ -300,22 +347,22 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
             // the L2 they were just written to.  Same arithmetic as layernorm_reg_kernel<384, 2>, bytes to ln_out8 [M][384]
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            typedef LnGroup<WS_K, 2> G;
+            typedef LnGroup<G::K, 2> LG;
             const int j = lane & 7, k = j >> 1, hh = j & 1;
             const float ys = rcp_rn(p.ln_s);
             for (int r0 = wave * 8; r0 < n_own * 32; r0 += 64) {
                 const long long row_raw = (long long)t0 * 32 + r0 + (lane >> 3);
                 const bool live = row_raw < p.M;
                 const long long row = live ? row_raw : (long long)p.M - 1;
-                const int16_t *xp = p.out16 + row * WS_K + 8 * k + 4 * hh;
-                float xv[G::NSTEP][G::EPC];
+                const int16_t *xp = p.out16 + row * G::K + 8 * k + 4 * hh;
+                float xv[LG::NSTEP][LG::EPC];
 #pragma unroll
-                for (int i = 0; i < G::NSTEP; ++i) {
+                for (int i = 0; i < LG::NSTEP; ++i) {
                     const LnRaw<4>::T t = *reinterpret_cast<const LnRaw<4>::T *>(xp + 32 * i);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)t[c], p.ln_s, ys);
                 }
-                G::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, p.ln_out8 + row * WS_K + 8 * k + 4 * hh);
+                LG::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, p.ln_out8 + row * G::K + 8 * k + 4 * hh);
             }
         }
     }

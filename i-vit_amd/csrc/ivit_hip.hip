@@ -546,30 +546,52 @@ static inline bool use_gemm3(const ivit_linear_plan_s *pl, const GemmArgs &a, in
            (a.lda % 16) == 0 && (a.ldb % 16) == 0 && a.M >= 128;
 }
 
-// ---- D = 384 qkv on the register-resident-weights kernel (ivit_gemm_ws.h), with or without norm1 in its prologue
-static inline bool qkv_ws_ok(const ivit_linear_plan_s *pl, int B, int T, int H, int dh) {
-    return pl->wf && dh == 64 && pl->K == WS_K && pl->N == 3 * H * dh && pl->N % 192 == 0 && (long long)B * H * T * 64 < (1ll << 31) && (long long)B * T < (1ll << 26);
+// ---- D = 384 / 192 qkv, plain 8-bit and proj + residual layers on the register-resident-weights kernel (ivit_gemm_ws.h), with or
+// without norm1 in its prologue.  ldv = 0: v row-major; ldv >= T: v^T (the K = 192 geometry only)
+static inline bool ws_plan_ok(const ivit_linear_plan_s *pl, long long M) { return pl->wf && ws_width(pl->K) && M < (1 << 26); }
+static inline bool qkv_ws_ok(const ivit_linear_plan_s *pl, int B, int T, int H, int dh, int ldv = 0) {
+    if (!(pl->wf && dh == 64 && ws_width(pl->K) && pl->N == 3 * H * dh && pl->N % 192 == 0 && (long long)B * H * T * 64 < (1ll << 31) &&
+          (long long)B * T < (1ll << 26)))
+        return false;
+    return ldv == 0 || (pl->K == Ws192Geo::K && ldv >= T && ldv % 16 == 0 && (long long)B * H * 64 * ldv < (1ll << 31));
 }
-static int launch_qkv_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, const int16_t *x16, float ln_s,
-                         const float *ln_bias_int, const float *ln_sc, const ivit_dyadic *ln_dy, int8_t *q, int8_t *k, int8_t *v,
-                         int B, int T, int H) {
+template <class G, bool FMA, bool LN, int EPI, bool VT = false>
+static hipError_t ws_attr() {
+    return hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<G, FMA, LN, EPI, VT>, hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM);
+}
+template <class G, bool LN, int EPI, bool VT = false>
+static void ws_launch(bool fma, unsigned grid, hipStream_t st, const WsArgs &a) {
+    if (fma) gemm_ws_qkv_kernel<G, true, LN, EPI, VT><<<grid, WS_THREADS, G::SMEM, st>>>(a);
+    else gemm_ws_qkv_kernel<G, false, LN, EPI, VT><<<grid, WS_THREADS, G::SMEM, st>>>(a);
+}
+template <class G>
+static int launch_qkv_ws_g(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, const int16_t *x16, float ln_s,
+                           const float *ln_bias_int, const float *ln_sc, const ivit_dyadic *ln_dy, int8_t *q, int8_t *k, int8_t *v,
+                           int B, int T, int H, int ldv) {
     if (h->device != pl->device) { snprintf(h->err, sizeof(h->err), "qkv: plan and handle live on different devices"); return IVIT_ERR_INVALID; }
+    if (ldv != 0 && !G::VT) { snprintf(h->err, sizeof(h->err), "qkv: no v^T store form at K = %d", G::K); return IVIT_ERR_UNSUPPORTED; }
     WsArgs a;
     a.x = x8; a.wf = pl->wf; a.bias = pl->bias_eff; a.cq = pl->cq; a.q = q; a.k = k; a.v = v;
     a.M = B * T; a.N = pl->N; a.T = T; a.H = H; a.dummy = pl->dummy;
     a.x16 = x16; a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy;
-    a.residual = nullptr; a.out16 = nullptr; a.cm = a.cr = 0.0; a.ln_out8 = nullptr;
+    a.residual = nullptr; a.out16 = nullptr; a.cm = a.cr = 0.0; a.ln_out8 = nullptr; a.ldv = ldv;
     static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
     const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
     if (!cached || !attr_dev[h->device].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<true, true, WS_EPI_RQ8>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<true, false, WS_EPI_RQ8>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<false, true, WS_EPI_RQ8>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<false, false, WS_EPI_RQ8>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
+        hipError_t e = ws_attr<G, true, true, WS_EPI_QKV8>();
+        if (e == hipSuccess) e = ws_attr<G, true, false, WS_EPI_QKV8>();
+        if (e == hipSuccess) e = ws_attr<G, false, true, WS_EPI_QKV8>();
+        if (e == hipSuccess) e = ws_attr<G, false, false, WS_EPI_QKV8>();
+        if (e == hipSuccess) e = ws_attr<G, true, true, WS_EPI_RQ8>();
+        if (e == hipSuccess) e = ws_attr<G, true, false, WS_EPI_RQ8>();
+        if (e == hipSuccess) e = ws_attr<G, false, true, WS_EPI_RQ8>();
+        if (e == hipSuccess) e = ws_attr<G, false, false, WS_EPI_RQ8>();
+        if constexpr (G::VT) {
+            if (e == hipSuccess) e = ws_attr<G, true, true, WS_EPI_QKV8, true>();
+            if (e == hipSuccess) e = ws_attr<G, true, false, WS_EPI_QKV8, true>();
+            if (e == hipSuccess) e = ws_attr<G, false, true, WS_EPI_QKV8, true>();
+            if (e == hipSuccess) e = ws_attr<G, false, false, WS_EPI_QKV8, true>();
+        }
         if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "qkv attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
         if (cached) attr_dev[h->device].store(true, std::memory_order_release);
     }
@@ -579,54 +601,69 @@ static int launch_qkv_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8
     const bool fma = pl->single_fma_ok;
     if (H == 0) {       // plain 8-bit output [M][N] (q = out8; T = 1)
         a.T = 1; a.H = 1;
-        if (x16) {
-            if (fma) gemm_ws_qkv_kernel<true, true, WS_EPI_RQ8><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
-            else gemm_ws_qkv_kernel<false, true, WS_EPI_RQ8><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
-        } else {
-            if (fma) gemm_ws_qkv_kernel<true, false, WS_EPI_RQ8><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
-            else gemm_ws_qkv_kernel<false, false, WS_EPI_RQ8><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
+        if (x16) ws_launch<G, true, WS_EPI_RQ8>(fma, grid, h->stream, a);
+        else ws_launch<G, false, WS_EPI_RQ8>(fma, grid, h->stream, a);
+    } else if (ldv != 0) {
+        if constexpr (G::VT) {
+            if (x16) ws_launch<G, true, WS_EPI_QKV8, true>(fma, grid, h->stream, a);
+            else ws_launch<G, false, WS_EPI_QKV8, true>(fma, grid, h->stream, a);
         }
     } else if (x16) {
-        if (fma) gemm_ws_qkv_kernel<true, true><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
-        else gemm_ws_qkv_kernel<false, true><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
+        ws_launch<G, true, WS_EPI_QKV8>(fma, grid, h->stream, a);
     } else {
-        if (fma) gemm_ws_qkv_kernel<true, false><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
-        else gemm_ws_qkv_kernel<false, false><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
+        ws_launch<G, false, WS_EPI_QKV8>(fma, grid, h->stream, a);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "qkv launch: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
     return IVIT_OK;
 }
+static int launch_qkv_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, const int16_t *x16, float ln_s,
+                         const float *ln_bias_int, const float *ln_sc, const ivit_dyadic *ln_dy, int8_t *q, int8_t *k, int8_t *v,
+                         int B, int T, int H, int ldv = 0) {
+    return pl->K == Ws192Geo::K ? launch_qkv_ws_g<Ws192Geo>(h, pl, x8, x16, ln_s, ln_bias_int, ln_sc, ln_dy, q, k, v, B, T, H, ldv)
+                                : launch_qkv_ws_g<Ws384Geo>(h, pl, x8, x16, ln_s, ln_bias_int, ln_sc, ln_dy, q, k, v, B, T, H, ldv);
+}
 
-static int launch_res_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, double cm, double cr, const int16_t *residual,
-                         int16_t *out, int M, float ln_s = 0.f, const float *ln_bias_int = nullptr, const float *ln_sc = nullptr,
-                         const ivit_dyadic *ln_dy = nullptr, int8_t *ln_out8 = nullptr) {
+template <class G>
+static int launch_res_ws_g(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, double cm, double cr, const int16_t *residual,
+                           int16_t *out, int M, float ln_s, const float *ln_bias_int, const float *ln_sc, const ivit_dyadic *ln_dy,
+                           int8_t *ln_out8) {
+    constexpr bool TAIL = G::K == 384;      // norm2 in the launch's tail: built at 384 only
     if (h->device != pl->device) { snprintf(h->err, sizeof(h->err), "linear: plan and handle live on different devices"); return IVIT_ERR_INVALID; }
+    if (ln_out8 && !TAIL) { snprintf(h->err, sizeof(h->err), "linear: no LayerNorm tail at K = %d", G::K); return IVIT_ERR_UNSUPPORTED; }
     WsArgs a;
     a.x = x8; a.wf = pl->wf; a.bias = pl->bias_eff; a.cq = pl->cq; a.q = a.k = a.v = nullptr;
     a.M = M; a.N = pl->N; a.T = 1; a.H = 1; a.dummy = pl->dummy;
     a.x16 = nullptr; a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy;
-    a.residual = residual; a.out16 = out; a.cm = cm; a.cr = cr; a.ln_out8 = ln_out8;
+    a.residual = residual; a.out16 = out; a.cm = cm; a.cr = cr; a.ln_out8 = ln_out8; a.ldv = 0;
     static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
     const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
     if (!cached || !attr_dev[h->device].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<true, false, WS_EPI_RES16>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<false, false, WS_EPI_RES16>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<true, true, WS_EPI_RES16>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<false, true, WS_EPI_RES16>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_SMEM);
+        hipError_t e = ws_attr<G, true, false, WS_EPI_RES16>();
+        if (e == hipSuccess) e = ws_attr<G, false, false, WS_EPI_RES16>();
+        if constexpr (TAIL) {
+            if (e == hipSuccess) e = ws_attr<G, true, true, WS_EPI_RES16>();
+            if (e == hipSuccess) e = ws_attr<G, false, true, WS_EPI_RES16>();
+        }
         if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "linear attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
         if (cached) attr_dev[h->device].store(true, std::memory_order_release);
     }
     const int ntt = (M + 31) / 32;
     const unsigned grid = (unsigned)(ntt < persistent_cus(h) ? ntt : persistent_cus(h));
     if (ln_out8) {
-        if (pl->single_fma_ok) gemm_ws_qkv_kernel<true, true, WS_EPI_RES16><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
-        else gemm_ws_qkv_kernel<false, true, WS_EPI_RES16><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
-    } else if (pl->single_fma_ok) gemm_ws_qkv_kernel<true, false, WS_EPI_RES16><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
-    else gemm_ws_qkv_kernel<false, false, WS_EPI_RES16><<<grid, WS_THREADS, WS_SMEM, h->stream>>>(a);
+        if constexpr (TAIL) ws_launch<G, true, WS_EPI_RES16>(pl->single_fma_ok, grid, h->stream, a);
+    } else {
+        ws_launch<G, false, WS_EPI_RES16>(pl->single_fma_ok, grid, h->stream, a);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "linear launch: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
     return IVIT_OK;
+}
+static int launch_res_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, double cm, double cr, const int16_t *residual,
+                         int16_t *out, int M, float ln_s = 0.f, const float *ln_bias_int = nullptr, const float *ln_sc = nullptr,
+                         const ivit_dyadic *ln_dy = nullptr, int8_t *ln_out8 = nullptr) {
+    return pl->K == Ws192Geo::K ? launch_res_ws_g<Ws192Geo>(h, pl, x8, cm, cr, residual, out, M, ln_s, ln_bias_int, ln_sc, ln_dy, ln_out8)
+                                : launch_res_ws_g<Ws384Geo>(h, pl, x8, cm, cr, residual, out, M, ln_s, ln_bias_int, ln_sc, ln_dy, ln_out8);
 }
 
 template <int EPI>
@@ -681,7 +718,7 @@ int ivit_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan pl, const int
     REQUIRE(h, bits == 8 || bits == 16, "bits must be 8 or 16");
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy;
-    if (bits == 8 && pl->wf && pl->K == WS_K && M < (1 << 26))      // prepared plan: tokens of a CU in LDS, weight slabs in registers
+    if (bits == 8 && ws_plan_ok(pl, M))      // prepared plan: tokens of a CU in LDS, weight slabs in registers
         return launch_qkv_ws(h, pl, x, nullptr, 0.f, nullptr, nullptr, nullptr, (int8_t *)out, nullptr, nullptr, M, 1, 0);
     if (use_gemm3(pl, a, 1)) return bits == 8 ? launch_gemm3<EPI_RQ8_CH>(h, pl, a) : launch_gemm3<EPI_RQ16_CH>(h, pl, a);
     return ivit_linear_i8_requant(h, x, pl->w, pl->bias, pl->dy, bits, out, M, pl->N, pl->K);
@@ -691,8 +728,8 @@ int ivit_layernorm_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan pl,
                                              const float *sc, const ivit_dyadic *ln_dy, int8_t *out8, int M) {
     CHECK_H(h);
     REQUIRE(h, pl && x16 && bias_int && sc && ln_dy && out8 && M > 0, "bad arguments");
-    if (!(pl->wf && pl->K == WS_K && M < (1 << 26))) {
-        snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 384 plan", __func__);
+    if (!ws_plan_ok(pl, M)) {
+        snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 192 or 384 plan", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
     return launch_qkv_ws(h, pl, nullptr, x16, scale, bias_int, sc, ln_dy, out8, nullptr, nullptr, M, 1, 0);
@@ -705,7 +742,7 @@ int ivit_linear_i8_requant_residual_planned(ivit_handle h, ivit_linear_plan pl, 
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy; a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual;
     const bool res_fast = fabs(dy_main.m * dy_main.r) < RQ_FAST_CLIM && fabs(dy_res.m * dy_res.r) < RQ_FAST_CLIM;
-    if (pl->wf && res_fast && pl->K == WS_K && M < (1 << 26))
+    if (res_fast && ws_plan_ok(pl, M))
         return launch_res_ws(h, pl, x, dy_main.m * dy_main.r, dy_res.m * dy_res.r, residual, out, M);
     if (use_gemm3(pl, a, 4) && res_fast) return launch_gemm3<EPI_RQ16_CH_RES>(h, pl, a);
     return ivit_linear_i8_requant_residual(h, x, pl->w, pl->bias, pl->dy, dy_main, dy_res, residual, out, M, pl->N, pl->K);
@@ -718,7 +755,7 @@ int ivit_linear_i8_requant_residual_layernorm_planned(ivit_handle h, ivit_linear
     CHECK_H(h);
     REQUIRE(h, pl && x && out && residual && M > 0 && ln_bias_int && ln_sc && ln_dy && ln_out8, "bad arguments");
     const bool res_fast = fabs(dy_main.m * dy_main.r) < RQ_FAST_CLIM && fabs(dy_res.m * dy_res.r) < RQ_FAST_CLIM;
-    if (!(pl->wf && res_fast && pl->K == WS_K && pl->N == WS_K && M < (1 << 26))) {
+    if (!(pl->wf && res_fast && pl->K == Ws384Geo::K && pl->N == Ws384Geo::K && M < (1 << 26))) {
         snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a 384 x 384 plan and residual multipliers in the fast range", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
@@ -736,7 +773,7 @@ int ivit_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, const int8_t 
     GemmArgs a = linear_args(x, pl->w, pl->bias, B * T, 3 * D, D);
     a.dy_ch = pl->dy; a.q = q; a.k = k; a.vt = vt;
     a.T = T; a.H = H; a.dh = dh; a.ldv = ldv; a.D = D;
-    if (ldv == 0 && qkv_ws_ok(pl, B, T, H, dh)) return launch_qkv_ws(h, pl, x, nullptr, 0.f, nullptr, nullptr, nullptr, q, k, vt, B, T, H);
+    if (qkv_ws_ok(pl, B, T, H, dh, ldv)) return launch_qkv_ws(h, pl, x, nullptr, 0.f, nullptr, nullptr, nullptr, q, k, vt, B, T, H, ldv);
     if (use_gemm3(pl, a, 2) && (long long)B * T < (1 << 23)) return launch_gemm3<EPI_QKV>(h, pl, a);
     return ivit_linear_i8_qkv(h, x, pl->w, pl->bias, pl->dy, q, k, vt, B, T, H, dh, ldv);
 }
@@ -746,14 +783,14 @@ int ivit_linear_plan_prepare_ws(ivit_handle h, ivit_linear_plan pl) {
     REQUIRE(h, pl, "null plan");
     REQUIRE(h, h->device == pl->device, "plan and handle live on different devices");
     if (pl->wf) return IVIT_OK;
-    if (pl->K != WS_K || pl->N % 64 != 0 || pl->N > WS_MAXN || !pl->pipelined_ok) {
-        snprintf(h->err, sizeof(h->err), "%s: built for K = 384, N a multiple of 64 up to %d, |(acc + bias) * c| < 2^31", __func__, WS_MAXN);
+    if (!ws_width(pl->K) || pl->N % 64 != 0 || pl->N > WS_MAXN || !pl->pipelined_ok) {
+        snprintf(h->err, sizeof(h->err), "%s: built for K = 192 or 384, N a multiple of 64 up to %d, |(acc + bias) * c| < 2^31", __func__, WS_MAXN);
         return IVIT_ERR_UNSUPPORTED;
     }
     v4i *wf = nullptr;
-    hipError_t e = hipMalloc((void **)&wf, (size_t)pl->N * WS_K);
+    hipError_t e = hipMalloc((void **)&wf, (size_t)pl->N * pl->K);
     if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "%s: hipMalloc: %s", __func__, hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    ws_swizzle_kernel<<<64, 256, 0, h->stream>>>(pl->w, wf, pl->N);
+    ws_swizzle_kernel<<<64, 256, 0, h->stream>>>(pl->w, wf, pl->N, pl->K);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);       // plan preparation is a build-time call
     if (e != hipSuccess) { (void)hipFree(wf); snprintf(h->err, sizeof(h->err), "%s: %s", __func__, hipGetErrorString(e)); return IVIT_ERR_HIP; }
@@ -768,10 +805,25 @@ int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, con
     REQUIRE(h, pl && x16 && bias_int && sc && ln_dy && q && k && v && B > 0 && T > 0 && H > 0 && dh > 0, "bad arguments");
     REQUIRE(h, pl->N == 3 * H * dh && pl->K == H * dh, "plan shape is not [3*H*dh, H*dh]");
     if (!qkv_ws_ok(pl, B, T, H, dh)) {
-        snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 384, dh = 64 plan and B*H*T*64 < 2^31", __func__);
+        snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 192 or 384, dh = 64 plan and B*H*T*64 < 2^31", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
     return launch_qkv_ws(h, pl, nullptr, x16, scale, bias_int, sc, ln_dy, q, k, v, B, T, H);
+}
+
+int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan pl, const int16_t *x16, float scale, const float *bias_int,
+                                             const float *sc, const ivit_dyadic *ln_dy, int8_t *q, int8_t *k, int8_t *vt, int B, int T,
+                                             int H, int dh, int ldv) {
+    CHECK_H(h);
+    REQUIRE(h, pl && x16 && bias_int && sc && ln_dy && q && k && vt && B > 0 && T > 0 && H > 0 && dh > 0, "bad arguments");
+    REQUIRE(h, pl->N == 3 * H * dh && pl->K == H * dh, "plan shape is not [3*H*dh, H*dh]");
+    REQUIRE(h, ldv == 0 || (ldv >= T && ldv % 16 == 0), "ldv: 0 (v row-major [B*H, T, dh]) or a multiple of 16 >= T (v^T)");
+    if (!qkv_ws_ok(pl, B, T, H, dh, ldv)) {
+        snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 192 or 384, dh = 64 plan, B*H*T*64 < 2^31, and K = 192 "
+                                         "with B*H*64*ldv < 2^31 for v^T", __func__);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return launch_qkv_ws(h, pl, nullptr, x16, scale, bias_int, sc, ln_dy, q, k, vt, B, T, H, ldv);
 }
 
 }  // extern "C"

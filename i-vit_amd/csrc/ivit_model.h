@@ -81,6 +81,15 @@ inline bool mlp_plan_fuses(ivit_mlp_plan mp, ivit_dyadic res_main, ivit_dyadic r
     return mp && mlp_res_fast(res_main, res_res);
 }
 
+// THE rule for "this block's norm1 + qkv is one ivit_layernorm_linear_i8_qkv_ldv_planned launch at B images": run_slice and
+// ivit_vit_fused_qkv_blocks ask here.  It is the entry's own acceptance test — a prepared plan (D = 192 or 384, dh = 64) and, for a
+// layer that keeps v^T (no Shiftmax row table), width 192.  No token-count threshold: see profiles/README.md, "Width 192 on the
+// weights-in-registers GEMM"
+inline bool qkv_plan_fuses(const ivit_vit_s *m, int i, int B) {
+    const int H = m->cfg.num_heads, ldv = (m->fused_attention && m->has_rowtab[i]) ? 0 : m->ld;
+    return qkv_ws_ok(m->plans[4 * i], B, m->T, H, m->cfg.embed_dim / H, ldv);
+}
+
 // THE rule for "the last block runs its attention, proj, norm2 and Mlp on the class-token rows only": run_slice and ivit_vit_cls_tail
 // ask here.  Everything behind a block's attention is row-local and a context row depends on its own q row alone, while the head reads
 // row 0 of each image only — so behind the last block's qkv GEMM (k and v need every token) the other T - 1 rows are work nobody
@@ -128,9 +137,11 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         // context rows in `patches`, the identity rows — copied by the attention launch — in `patch16`
         const bool tail = i == c.depth - 1 && cls_tail(m);
         const int Mb = tail ? B : M;      // rows behind the attention
-        // norm1's 8-bit output has one consumer: where the qkv GEMM keeps a CU's tokens in LDS it is computed there (round 6)
-        rc = ldv == 0 ? ivit_layernorm_linear_i8_qkv_planned(h, m->plans[4 * i], x, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, q, k, vt, B, T, H, dh)
-                      : IVIT_ERR_UNSUPPORTED;
+        // norm1's 8-bit output has one consumer: where the qkv GEMM keeps a CU's tokens in LDS it is computed there (round 6; D = 192 too,
+        // with v in either layout)
+        rc = qkv_plan_fuses(m, i, B) ? ivit_layernorm_linear_i8_qkv_ldv_planned(h, m->plans[4 * i], x, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy,
+                                                                                q, k, vt, B, T, H, dh, ldv)
+                                     : IVIT_ERR_UNSUPPORTED;
         if (rc == IVIT_ERR_UNSUPPORTED) {
             RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, a8));
             RUN(ivit_linear_i8_qkv_planned(h, m->plans[4 * i], a8, q, k, vt, B, T, H, dh, ldv));
@@ -252,9 +263,9 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
             ivit_linear_plan pl = nullptr;
             rc = ivit_linear_plan_create(h, lin[k].w, lin[k].bias, lin[k].dy, lin[k].N, lin[k].K, &pl);
             if (rc != IVIT_OK) { ivit_vit_destroy(m); return rc; }
-            // the qkv layer of a D = 384, dh = 64 model also runs on gemm_ws_qkv_kernel (weights in its fragment order)
-            if (k == 0 && D == WS_K && D / cfg->num_heads == 64) (void)ivit_linear_plan_prepare_ws(h, pl);
-            if (k == 1 && D == WS_K) (void)ivit_linear_plan_prepare_ws(h, pl);      // attn.proj + residual on the same kernel
+            // the qkv layer of a D = 192 or 384, dh = 64 model also runs on gemm_ws_qkv_kernel (weights in its fragment order)
+            if (k == 0 && ws_width(D) && D / cfg->num_heads == 64) (void)ivit_linear_plan_prepare_ws(h, pl);
+            if (k == 1 && ws_width(D)) (void)ivit_linear_plan_prepare_ws(h, pl);      // attn.proj + residual on the same kernel
             m->plans.push_back(pl);
         }
         ivit_mlp_plan mp = nullptr;
@@ -312,6 +323,15 @@ int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks) {
     int n = 0;
     for (int i = 0; i < m->cfg.depth; ++i)
         n += mlp_plan_fuses(m->mlp_plans[i], m->blocks[i].res2_main, m->blocks[i].res2_res, (long long)batch * m->T);
+    *blocks = n;
+    return IVIT_OK;
+}
+
+int ivit_vit_fused_qkv_blocks(ivit_vit m, int batch, int *blocks) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, blocks && batch > 0, "bad arguments");
+    int n = 0;
+    for (int i = 0; i < m->cfg.depth; ++i) n += qkv_plan_fuses(m, i, batch);
     *blocks = n;
     return IVIT_OK;
 }
@@ -654,9 +674,11 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
                 m->mlp_lin.push_back(p1);
                 m->mlp_lin.push_back(p2);
                 m->mlp_plans.push_back(mp);
-                // round 6: the C = 384 stage's qkv and proj layers on gemm_ws_qkv_kernel (prepared plans), norm1 inside the qkv launch
+                // round 6: the C = 384 stage's qkv and proj layers on gemm_ws_qkv_kernel (prepared plans), norm1 inside the qkv launch.
+                // (The kernel has a K = 192 geometry too, but with stage 1's qkv layer on it Swin-T b256 measured 1.1 % slower:
+                // profiles/README.md, "Width 192 on the weights-in-registers GEMM")
                 ivit_linear_plan q[2] = {nullptr, nullptr};
-                if (C == WS_K) {
+                if (C == Ws384Geo::K) {
                     if (ivit_linear_plan_create(h, b.qkv.w, b.qkv.b, b.qkv.dy, 3 * C, C, &q[0]) != IVIT_OK) q[0] = nullptr;
                     if (q[0] && ivit_linear_plan_prepare_ws(h, q[0]) != IVIT_OK) { (void)ivit_linear_plan_destroy(q[0]); q[0] = nullptr; }
                     if (ivit_linear_plan_create(h, b.proj.w, b.proj.b, b.proj.dy, C, C, &q[1]) != IVIT_OK) q[1] = nullptr;

@@ -48,7 +48,10 @@ enum {
     IVIT_ERR_NO_DEVICE = 4
 };
 
-/* 100 * major + minor.  109: the class-token forms of the fused attention (ivit_attention_fused_cls, ivit_attention_fused_lut_cls,
+/* 100 * major + minor.  110: ivit_linear_plan_prepare_ws also takes K = 192 plans, and every entry that runs on a prepared plan takes
+ * them (ivit_linear_i8_qkv_planned also with v^T there); ivit_layernorm_linear_i8_qkv_ldv_planned, ivit_vit_fused_qkv_blocks
+ * (additions only): ivit_vit_forward runs norm1 + qkv of a D = 192, dh = 64 block as one launch and its attn.proj on the same kernel.
+ * 109: the class-token forms of the fused attention (ivit_attention_fused_cls, ivit_attention_fused_lut_cls,
  * ivit_attention_fused_rowlut_cls), ivit_gather_rows_i16, ivit_vit_cls_tail (additions only): ivit_vit_forward runs the last
  * block's attention, proj, norm2 and Mlp on the class-token rows only.
  * 108: ivit_mlp_plan_create also takes 256 -> 1024 -> 256 and ivit_mlp_fused also C = 128, hidden = 512
@@ -68,7 +71,7 @@ enum {
  * fields exp_* at their END (added in 100 without a bump: a caller compiled against an older layout must be rebuilt).
  * Parameter structs are read field by field: ZERO-INITIALISE them (memset / = {0}) before filling — exp_aq == NULL (and
  * exp_nc == exp_tcount == exp_dmin == 0) selects the arithmetic Shiftmax, anything else is taken as device pointers.        */
-#define IVIT_VERSION 109
+#define IVIT_VERSION 110
 int ivit_version(void);
 const char *ivit_status_string(int status);
 
@@ -188,6 +191,16 @@ int ivit_linear_i8_requant_residual_layernorm_planned(ivit_handle h, ivit_linear
 int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan p, const int16_t *x16, float scale,
                                          const float *bias_int, const float *sc, const ivit_dyadic *ln_dy, int8_t *q,
                                          int8_t *k, int8_t *v, int B, int T, int H, int dh);
+/* Width 192 (DeiT-Tiny, Swin stage 1): ivit_linear_plan_prepare_ws also takes K = 192, and a prepared K = 192 plan is accepted wherever a
+ * prepared K = 384 one is, except by ivit_linear_i8_requant_residual_layernorm_planned.  At K = 192 the kernel also has a v^T store form:
+ * ivit_linear_i8_qkv_planned with ldv >= T, ldv % 16 == 0 runs on it, and so does
+ * ivit_layernorm_linear_i8_qkv_ldv_planned = ivit_layernorm_linear_i8_qkv_planned with the layout of v as an argument: ldv == 0 is that
+ * entry; ldv >= T with ldv % 16 == 0 stores v TRANSPOSED, element (b, h, t, ch) at vt[((b * H + h) * 64 + ch) * ldv + t], the layout of
+ * ivit_linear_i8_qkv.  Columns t >= T of v^T are not written.  IVIT_ERR_UNSUPPORTED (nothing launched) where the ldv == 0 entry returns
+ * it, and for v^T on a K = 384 plan or with B*H*64*ldv >= 2^31.                                                               */
+int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan p, const int16_t *x16, float scale,
+                                             const float *bias_int, const float *sc, const ivit_dyadic *ln_dy, int8_t *q,
+                                             int8_t *k, int8_t *vt, int B, int T, int H, int dh, int ldv);
 
 /* ---- a2  QuantMatMul.forward  (quant_modules.py:223-228), batched, "NT" form:
  * C[b] = A[b] (M x K) * B[b]^T (B[b] is N x K), int32.  q·kᵀ: A=q, B=k.
@@ -386,6 +399,10 @@ int ivit_vit_workspace_bytes(ivit_vit m, int batch, int nslices, size_t *bytes);
 /* How many blocks of a forward of `batch` images in ONE slice issue their Mlp as a single launch (the fused kernels of
  * ivit_mlp_plan_create); the other blocks run fc1 / ShiftGELU / fc2 as three.  Decided by the rule the forward itself applies. */
 int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks);
+/* How many blocks of a forward of `batch` images in ONE slice issue norm1 + qact1 + attn.qkv as a single launch
+ * (ivit_layernorm_linear_i8_qkv_ldv_planned: D = 192 or 384 with dh = 64; a D = 384 block only where it takes v row-major); the other
+ * blocks run the LayerNorm and the GEMM as two.  Decided by the rule the forward itself applies.                               */
+int ivit_vit_fused_qkv_blocks(ivit_vit m, int batch, int *blocks);
 /* *on = 1 when a forward of `batch` images runs the last block's attention, attn.proj, norm2 and Mlp on the class-token rows only
  * (B rows instead of B*T; the head reads no other row, vit_quant.py:271-281): models on the fused attention (dh == 64, T <= 640).
  * Same logits either way.  Decided by the rule the forward itself applies.                                                      */
