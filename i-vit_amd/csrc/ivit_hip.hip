@@ -1303,10 +1303,62 @@ int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in
     return IVIT_OK;
 }
 
+// Host restatement of the product shiftgelu_kernel forms (same fp32 sequence, IEEE division; -ffp-contract=off holds for
+// the host half too).  Q * sigmoid_int depends on (Q, row max) and the scale alone, so its extremes over the 32 896 pairs
+// with Q <= row max are the extremes over every possible input.  Below a scale of about 1.2e-3 the reference's clamp of
+// the exponential sum at 2^31 (quant_modules.py:437) lets sigmoid_int exceed 256 and the product leaves int16.
+static float host_shift_exp(float x, float x0, float nx0, int n) {
+    float t = x + floorf(x * 0.5f);
+    t = t - floorf(x * 0.0625f);
+    t = fmaxf(t, nx0);
+    const float q = floorf(t / x0);
+    const float r = t - x0 * q;
+    float e = r * 0.5f - x0;
+    e = floorf(ldexpf(e, n - (int)q));
+    return fmaxf(e, 0.0f);
+}
+
+static void shiftgelu_product_range(float s, int *lo, int *hi) {
+    static thread_local float cs = 0.f;      // the scale of a frozen layer repeats call after call
+    static thread_local int clo = 0, chi = 0;
+    if (s != cs) {
+        const float x0 = floorf(-1.0f / (s * 1.702f)), nx0 = 23.0f * x0;
+        float p[256];
+        for (int q = -128; q < 128; ++q) p[q + 128] = ((float)q * s) / s;
+        float mn = 0.f, mxv = 0.f;
+        for (int qmax = -128; qmax < 128; ++qmax) {
+            const float mx = p[qmax + 128];
+            const float emax = host_shift_exp(-mx, x0, nx0, 23);
+            for (int q = -128; q <= qmax; ++q) {
+                const float e = host_shift_exp(p[q + 128] - mx, x0, nx0, 23);
+                const float S = fminf(e + emax, 2147483648.0f);
+                const float F = floorf((1.0f / S) * 2147483648.0f);
+                const float sig = floorf((e * F) * 5.9604644775390625e-08f);
+                const float prod = rintf(p[q + 128] * sig);
+                mn = fminf(mn, prod);
+                mxv = fmaxf(mxv, prod);
+            }
+        }
+        clo = (int)fmaxf(mn, -2147483648.0f);
+        chi = (int)fminf(mxv, 2147483520.0f);
+        cs = s;
+    }
+    *lo = clo;
+    *hi = chi;
+}
+
 int ivit_shiftgelu(ivit_handle h, const int8_t *x, int64_t rows, int C, float scale, int16_t *out16) {
     CHECK_H(h);
     REQUIRE(h, x && out16 && rows > 0 && C > 0 && scale > 0.f, "bad arguments");
     REQUIRE(h, (C % 16) == 0, "C must be a multiple of 16");
+    int lo, hi;
+    shiftgelu_product_range(scale, &lo, &hi);
+    if (lo < -32768 || hi > 32767) {
+        snprintf(h->err, sizeof(h->err),
+                 "ivit_shiftgelu: at scale %.9g Q*sigmoid_int spans [%d, %d] and does not fit the 16-bit output; use "
+                 "ivit_shiftgelu_requant or the table form", (double)scale, lo, hi);
+        return IVIT_ERR_UNSUPPORTED;
+    }
     ivit_dyadic d = {0.0, 0.0};
     shiftgelu_kernel<false><<<(unsigned)((rows + 3) / 4), 256, 0, h->stream>>>(x, rows, C, scale, d, out16);
     LAUNCH_CHECK(h);

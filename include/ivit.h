@@ -302,7 +302,12 @@ int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in
                   int out_bits, uint16_t *out, int ld_out);
 
 /* ---- a6  IntGELU.forward (ShiftGELU)  (quant_modules.py:410-445).
- * x int8 [rows, C], per-tensor scale -> out16[i] = Q*sigmoid_int (scale s*2^-7).          */
+ * x int8 [rows, C], per-tensor scale -> out16[i] = Q*sigmoid_int (scale s*2^-7).
+ * Scale domain: sigmoid_int <= 256 and the product fits 16 bits only while the reference's clamp of the
+ * exponential sum at 2^31 (:437) does not bite, i.e. for scales above about 1.2e-3.  The entry point
+ * evaluates the extremes of Q*sigmoid_int over all (Q, row max) pairs on the host, from the scale alone,
+ * and returns IVIT_ERR_UNSUPPORTED (nothing launched, the message names the scale) when they leave int16.
+ * The 8-bit forms below carry the product in 32 bits and equal the reference at every positive scale.  */
 int ivit_shiftgelu(ivit_handle h, const int8_t *x, int64_t rows, int C, float scale,
                    int16_t *out16);
 /* a6 + a3 (layers_quant.py:146-147): ... -> clamp8(rq(Q*sigmoid_int, dy))               */

@@ -227,9 +227,22 @@ void ivit_ref_shiftmax(const int8_t *x, int64_t rows, int64_t n, int64_t ld_in, 
 }
 
 /* a6: IntGELU.forward (ShiftGELU)  quant_modules.py:425-445.
- * x int8 [rows, C], per-tensor scale s -> out[i] = Q * sigmoid_int (|.| <= 128*127,
- * int16), output scale s*2^-7.                                                  */
-void ivit_ref_shiftgelu(const int8_t *x, int64_t rows, int64_t C, float s, int16_t *out) {
+ * x int8 [rows, C], per-tensor scale s -> out[i] = Q * sigmoid_int, output scale s*2^-7.
+ * sigmoid_int <= 256 (|out| <= 128*256) only while the clamp of the sum at 2^31 (:437) does not
+ * bite; below a scale of about 1.2e-3 it does, sigmoid_int grows and the product leaves int16
+ * (75 264 at s = 5e-4).  The product is therefore carried in 32 bits.                          */
+static inline int32_t gelu_product(float p, float mx, float emax, float x0, float nx0) {
+    float e = iexp_shift(p - mx, x0, nx0, 23);
+    float S = e + emax;
+    S = S < 2147483648.0f ? S : 2147483648.0f;
+    float F = floorf((1.0f / S) * 2147483648.0f);
+    float sig = floorf((e * F) / 16777216.0f); /* 2^(31-8+1) */
+    float o = p * sig;
+    /* the next QuantAct takes round(fl(fl(o*sf)/sf)); see requant */
+    return (int32_t)rintf(o);
+}
+
+void ivit_ref_shiftgelu_i32(const int8_t *x, int64_t rows, int64_t C, float s, int32_t *out) {
     const float ssig = s * 1.702f;
     const float x0 = floorf(-1.0f / ssig);
     const float nx0 = 23.0f * x0;
@@ -247,18 +260,46 @@ void ivit_ref_shiftgelu(const int8_t *x, int64_t rows, int64_t C, float s, int16
             }
             const float emax = iexp_shift(-mx, x0, nx0, 23);
             for (int64_t j = 0; j < C; ++j) {
-                float e = iexp_shift(p[j] - mx, x0, nx0, 23);
-                float S = e + emax;
-                S = S < 2147483648.0f ? S : 2147483648.0f;
-                float F = floorf((1.0f / S) * 2147483648.0f);
-                float sig = floorf((e * F) / 16777216.0f); /* 2^(31-8+1) */
-                float o = p[j] * sig;
-                /* the next QuantAct takes round(fl(fl(o*sf)/sf)); see requant */
-                out[i * C + j] = (int16_t)rintf(o);
+                out[i * C + j] = gelu_product(p[j], mx, emax, x0, nx0);
             }
         }
         free(p);
     }
+}
+
+/* extremes of Q * sigmoid_int at scale s over every (Q, row max) pair with Q <= row max, i.e. over every
+ * possible input (a row's maximum is one of its elements and bounds the others).                        */
+void ivit_ref_shiftgelu_range(float s, int32_t *lo, int32_t *hi) {
+    const float x0 = floorf(-1.0f / (s * 1.702f));
+    const float nx0 = 23.0f * x0;
+    float p[256];
+    for (int q = -128; q < 128; ++q) {
+        float X = (float)q * s;
+        p[q + 128] = X / s;
+    }
+    *lo = 0;
+    *hi = 0;
+    for (int qmax = -128; qmax < 128; ++qmax) {
+        const float mx = p[qmax + 128];
+        const float emax = iexp_shift(-mx, x0, nx0, 23);
+        for (int Q = -128; Q <= qmax; ++Q) {
+            const int32_t o = gelu_product(p[Q + 128], mx, emax, x0, nx0);
+            *lo = o < *lo ? o : *lo;
+            *hi = o > *hi ? o : *hi;
+        }
+    }
+}
+
+/* 16-bit form: 0 when every product fits int16 at this scale (out written), 1 otherwise (out untouched) */
+int ivit_ref_shiftgelu(const int8_t *x, int64_t rows, int64_t C, float s, int16_t *out) {
+    int32_t lo, hi;
+    ivit_ref_shiftgelu_range(s, &lo, &hi);
+    if (lo < -32768 || hi > 32767) return 1;
+    int32_t *t = (int32_t *)malloc(sizeof(int32_t) * (size_t)(rows * C > 0 ? rows * C : 1));
+    ivit_ref_shiftgelu_i32(x, rows, C, s, t);
+    for (int64_t i = 0; i < rows * C; ++i) out[i] = (int16_t)t[i];
+    free(t);
+    return 0;
 }
 
 /* a7: IntLayerNorm.forward  quant_modules.py:353-386.

@@ -27,13 +27,15 @@ void ivit_ref_requant_i32(const int32_t *z, const ivit_dyadic *dy, int64_t nch, 
                           const ivit_dyadic *dy_id, int bits, int32_t *out, int64_t rows, int64_t C);
 void ivit_ref_shiftmax(const int8_t *x, int64_t rows, int64_t n, int64_t ld_in, float s, int out_bits, uint16_t *out,
                        int64_t ld_out);
-void ivit_ref_shiftgelu(const int8_t *x, int64_t rows, int64_t C, float s, int16_t *out);
+int ivit_ref_shiftgelu(const int8_t *x, int64_t rows, int64_t C, float s, int16_t *out);
+void ivit_ref_shiftgelu_i32(const int8_t *x, int64_t rows, int64_t C, float s, int32_t *out);
 void ivit_ref_layernorm(const int16_t *x, int64_t rows, int64_t C, float s, const float *bias_int, const float *sc,
                         float *z);
 void ivit_ref_im2col_patch(const int8_t *img, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t P, int8_t *out);
 
 #define TW_OK 0
 #define TW_INVALID 1
+#define TW_UNSUPPORTED 3
 #define TW_REQ(c) do { if (!(c)) return TW_INVALID; } while (0)
 
 static void *xmalloc(size_t n) { return malloc(n ? n : 1); }
@@ -297,32 +299,33 @@ int ivit_cpu_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int l
 int ivit_cpu_shiftgelu(ivit_handle h, const int8_t *x, int64_t rows, int C, float scale, int16_t *out16) {
     (void)h;
     TW_REQ(x && out16 && rows > 0 && C > 0 && scale > 0.f);
-    ivit_ref_shiftgelu(x, rows, C, scale, out16);
-    return TW_OK;
+    /* as ivit_shiftgelu: refused where Q*sigmoid_int can leave int16 at this scale (the bound depends on the scale alone) */
+    return ivit_ref_shiftgelu(x, rows, C, scale, out16) ? TW_UNSUPPORTED : TW_OK;
 }
 int ivit_cpu_shiftgelu_requant(ivit_handle h, const int8_t *x, int64_t rows, int C, float scale, ivit_dyadic dy,
                                int8_t *out8) {
     TW_REQ(x && out8 && rows > 0 && C > 0 && scale > 0.f);
-    int16_t *g = (int16_t *)xmalloc((size_t)rows * C * 2);
-    ivit_ref_shiftgelu(x, rows, C, scale, g);
-    const int rc = ivit_cpu_requant_i16(h, g, &dy, 1, NULL, NULL, 8, out8, rows, C);
+    int32_t *g = (int32_t *)xmalloc((size_t)rows * C * 4);       /* 32 bits: the product leaves int16 at small scales */
+    ivit_ref_shiftgelu_i32(x, rows, C, scale, g);
+    const int rc = ivit_cpu_requant_i32(h, g, &dy, 1, NULL, NULL, 8, out8, rows, C);
     free(g);
     return rc;
 }
 /* table[(qmax + 128) * 256 + (Q + 128)] for Q <= qmax (a row's maximum bounds its elements; the other half of the
- * table is never indexed and left 0): the two-element row {Q, qmax} has the same maximum, hence the same result */
+ * table is never indexed and left 0): the row {min(v, qmax) : v = -128..127} has maximum qmax and holds every Q <= qmax */
 int ivit_cpu_shiftgelu_build_table(ivit_handle h, float scale, ivit_dyadic dy, int8_t *table) {
     TW_REQ(table && scale > 0.f);
-    memset(table, 0, 65536);
+    int8_t *x = (int8_t *)xmalloc(65536), *o = (int8_t *)xmalloc(65536);
     for (int qmax = -128; qmax < 128; ++qmax)
-        for (int Q = -128; Q <= qmax; ++Q) {
-            const int8_t row[2] = {(int8_t)Q, (int8_t)qmax};
-            int8_t o[2];
-            const int rc = ivit_cpu_shiftgelu_requant(h, row, 1, 2, scale, dy, o);
-            if (rc) return rc;
-            table[(qmax + 128) * 256 + (Q + 128)] = o[0];
-        }
-    return TW_OK;
+        for (int v = -128; v < 128; ++v) x[(qmax + 128) * 256 + (v + 128)] = (int8_t)(v < qmax ? v : qmax);
+    const int rc = ivit_cpu_shiftgelu_requant(h, x, 256, 256, scale, dy, o);
+    memset(table, 0, 65536);
+    if (rc == TW_OK)
+        for (int qmax = -128; qmax < 128; ++qmax)
+            memcpy(table + (qmax + 128) * 256, o + (qmax + 128) * 256, (size_t)(qmax + 129));
+    free(x);
+    free(o);
+    return rc;
 }
 int ivit_cpu_shiftgelu_requant_lut(ivit_handle h, const int8_t *x, int64_t rows, int C, const int8_t *table,
                                    int8_t *out8) {
