@@ -1,5 +1,8 @@
 // ivit_hip.hip — C-ABI (include/ivit.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
+// The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
+// device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
+// range predicates rq_fast / rq_fast2 / attn_fast that choose instantiations and refuse calls.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdio.h>
@@ -9,6 +12,7 @@
 #include <dlfcn.h>
 #include <mutex>
 #include <atomic>
+#include <type_traits>
 #include "ivit_device.h"
 #include "ivit_elementwise.h"
 #include "ivit_layernorm.h"
@@ -56,6 +60,47 @@ struct ivit_device_guard {
 #define CHECK_H(h) if (!(h)) return IVIT_ERR_INVALID; ivit_device_guard ivit_dev_guard_; if (!ivit_dev_guard_.enter((h)->device)) return IVIT_ERR_HIP
 #define REQUIRE(h, cond, msg) do { if (!(cond)) { snprintf((h)->err, sizeof((h)->err), "%s: %s", __func__, msg); return IVIT_ERR_INVALID; } } while (0)
 #define LAUNCH_CHECK(h) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { snprintf((h)->err, sizeof((h)->err), "%s: %s", __func__, hipGetErrorString(e_)); return IVIT_ERR_HIP; } } while (0)
+
+// Launch `Kernel` with `lds` bytes of dynamic LDS.  Above 64 KB a launch needs hipFuncAttributeMaxDynamicSharedMemorySize: set once
+// per device and kernel for the largest size seen (the attribute is a maximum), so the eager single-stream modes pay no host call
+// per launch; a device ordinal outside the cache sets it every time.  Per DEVICE: ADVICE r5, one process-wide flag left the second
+// GPU of a process without it.  Returns the attribute's status; the caller checks the launch itself (LAUNCH_CHECK).
+template <auto Kernel, class... Args>
+static int launch_dyn(ivit_handle h, dim3 grid, dim3 block, size_t lds, const Args &...args) {
+    if (lds > 65536) {
+        static std::atomic<int> max_dev[IVIT_MAX_DEVICES];
+        const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
+        if (!cached || max_dev[h->device].load(std::memory_order_acquire) < (int)lds) {
+            hipError_t e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "hipFuncSetAttribute: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+            if (cached) max_dev[h->device].store((int)lds, std::memory_order_release);
+        }
+    }
+    Kernel<<<grid, block, lds, h->stream>>>(args...);
+    return IVIT_OK;
+}
+
+// f(std::true_type) or f(std::false_type): a launch site names a <bool FMA> (or <bool LN>) kernel pair once
+template <class F>
+static inline auto with_bool(bool on, F &&f) {
+    if (on) return f(std::true_type{});
+    return f(std::false_type{});
+}
+// the same for the two stage-0 widths of the token-order LayerNorm
+template <class F>
+static inline auto with_width(int C, F &&f) {
+    if (C == 96) return f(std::integral_constant<int, 96>{});
+    return f(std::integral_constant<int, 128>{});
+}
+
+// The range predicates: they choose which instantiation runs and which calls are refused, so each has ONE definition.
+// rq_fast: |m * 2^-e| below RQ_FAST_CLIM (ivit_device.h), where a 16-bit value times the multiplier is exact in the kernels' fast
+// requant.  attn_fast: both attention multipliers inside (-512, 512), the bound of attn_fused_kernel<FAST = true>.  It was
+// spelled `c < 512 && c > -512` at some sites and `fabs(c) < 512` at others: the two agree on every input, NaN included (every
+// comparison with a NaN is false, and fabs(NaN) is a NaN)
+static inline bool rq_fast(ivit_dyadic d) { return fabs(d.m * d.r) < RQ_FAST_CLIM; }
+static inline bool rq_fast2(ivit_dyadic a, ivit_dyadic b) { return rq_fast(a) && rq_fast(b); }
+static inline bool attn_fast(ivit_dyadic dy_qk, ivit_dyadic dy_pv) { return fabs(dy_qk.m * dy_qk.r) < 512.0 && fabs(dy_pv.m * dy_pv.r) < 512.0; }
 
 extern "C" {
 
@@ -164,11 +209,7 @@ static int launch_gemm(ivit_handle h, GemmArgs &a, int nb) {
     a.tiles_n = (a.N + GEMM_BN - 1) / GEMM_BN;
     dim3 grid((unsigned)(tm * a.tiles_n), (unsigned)nb, 1);
     gemm_nt_kernel<A16, EPI><<<grid, 256, 0, h->stream>>>(a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "gemm launch: %s", hipGetErrorString(e));
-        return IVIT_ERR_HIP;
-    }
+    LAUNCH_CHECK(h);
     return IVIT_OK;
 }
 
@@ -183,11 +224,7 @@ static int launch_gemm2(ivit_handle h, GemmArgs &a) {
     const long long c256 = ((t256 + s256 - 1) / s256) * 256, c128 = ((t128 + s128 - 1) / s128) * 128;
     if (c128 < c256) gemm_glds_kernel<EPI, 128><<<dim3((unsigned)t128), 256, 0, h->stream>>>(a);
     else gemm_glds_kernel<EPI, 256><<<dim3((unsigned)t256), 512, 0, h->stream>>>(a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "gemm2 launch: %s", hipGetErrorString(e));
-        return IVIT_ERR_HIP;
-    }
+    LAUNCH_CHECK(h);
     return IVIT_OK;
 }
 static inline bool use_gemm2(const GemmArgs &a) { return (a.K % 32) == 0 && a.K >= 64 && (a.lda % 16) == 0 && (a.ldb % 16) == 0; }
@@ -555,14 +592,14 @@ static inline bool qkv_ws_ok(const ivit_linear_plan_s *pl, int B, int T, int H, 
         return false;
     return ldv == 0 || (pl->K == Ws192Geo::K && ldv >= T && ldv % 16 == 0 && (long long)B * H * 64 * ldv < (1ll << 31));
 }
-template <class G, bool FMA, bool LN, int EPI, bool VT = false>
-static hipError_t ws_attr() {
-    return hipFuncSetAttribute((const void *)gemm_ws_qkv_kernel<G, FMA, LN, EPI, VT>, hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM);
-}
+// one workgroup per CU of the handle's share, each with a contiguous range of 32-token tiles
 template <class G, bool LN, int EPI, bool VT = false>
-static void ws_launch(bool fma, unsigned grid, hipStream_t st, const WsArgs &a) {
-    if (fma) gemm_ws_qkv_kernel<G, true, LN, EPI, VT><<<grid, WS_THREADS, G::SMEM, st>>>(a);
-    else gemm_ws_qkv_kernel<G, false, LN, EPI, VT><<<grid, WS_THREADS, G::SMEM, st>>>(a);
+static int ws_launch(ivit_handle h, const ivit_linear_plan_s *pl, const WsArgs &a) {
+    const int ntt = (a.M + 31) / 32;
+    const unsigned grid = (unsigned)(ntt < persistent_cus(h) ? ntt : persistent_cus(h));
+    return with_bool(pl->single_fma_ok, [&](auto FMA) {
+        return launch_dyn<gemm_ws_qkv_kernel<G, FMA(), LN, EPI, VT>>(h, grid, WS_THREADS, G::SMEM, a);
+    });
 }
 template <class G>
 static int launch_qkv_ws_g(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, const int16_t *x16, float ln_s,
@@ -575,46 +612,16 @@ static int launch_qkv_ws_g(ivit_handle h, const ivit_linear_plan_s *pl, const in
     a.M = B * T; a.N = pl->N; a.T = T; a.H = H; a.dummy = pl->dummy;
     a.x16 = x16; a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy;
     a.residual = nullptr; a.out16 = nullptr; a.cm = a.cr = 0.0; a.ln_out8 = nullptr; a.ldv = ldv;
-    static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
-    const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
-    if (!cached || !attr_dev[h->device].load(std::memory_order_acquire)) {
-        hipError_t e = ws_attr<G, true, true, WS_EPI_QKV8>();
-        if (e == hipSuccess) e = ws_attr<G, true, false, WS_EPI_QKV8>();
-        if (e == hipSuccess) e = ws_attr<G, false, true, WS_EPI_QKV8>();
-        if (e == hipSuccess) e = ws_attr<G, false, false, WS_EPI_QKV8>();
-        if (e == hipSuccess) e = ws_attr<G, true, true, WS_EPI_RQ8>();
-        if (e == hipSuccess) e = ws_attr<G, true, false, WS_EPI_RQ8>();
-        if (e == hipSuccess) e = ws_attr<G, false, true, WS_EPI_RQ8>();
-        if (e == hipSuccess) e = ws_attr<G, false, false, WS_EPI_RQ8>();
+    if (H == 0) { a.T = 1; a.H = 1; }      // plain 8-bit output [M][N] (q = out8; T = 1)
+    const int st = with_bool(x16 != nullptr, [&](auto LN) {
+        if (H == 0) return ws_launch<G, LN(), WS_EPI_RQ8>(h, pl, a);
         if constexpr (G::VT) {
-            if (e == hipSuccess) e = ws_attr<G, true, true, WS_EPI_QKV8, true>();
-            if (e == hipSuccess) e = ws_attr<G, true, false, WS_EPI_QKV8, true>();
-            if (e == hipSuccess) e = ws_attr<G, false, true, WS_EPI_QKV8, true>();
-            if (e == hipSuccess) e = ws_attr<G, false, false, WS_EPI_QKV8, true>();
+            if (ldv != 0) return ws_launch<G, LN(), WS_EPI_QKV8, true>(h, pl, a);
         }
-        if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "qkv attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-        if (cached) attr_dev[h->device].store(true, std::memory_order_release);
-    }
-    // one workgroup per CU, each with a contiguous range of 32-token tiles
-    const int ntt = (a.M + 31) / 32;
-    const unsigned grid = (unsigned)(ntt < persistent_cus(h) ? ntt : persistent_cus(h));
-    const bool fma = pl->single_fma_ok;
-    if (H == 0) {       // plain 8-bit output [M][N] (q = out8; T = 1)
-        a.T = 1; a.H = 1;
-        if (x16) ws_launch<G, true, WS_EPI_RQ8>(fma, grid, h->stream, a);
-        else ws_launch<G, false, WS_EPI_RQ8>(fma, grid, h->stream, a);
-    } else if (ldv != 0) {
-        if constexpr (G::VT) {
-            if (x16) ws_launch<G, true, WS_EPI_QKV8, true>(fma, grid, h->stream, a);
-            else ws_launch<G, false, WS_EPI_QKV8, true>(fma, grid, h->stream, a);
-        }
-    } else if (x16) {
-        ws_launch<G, true, WS_EPI_QKV8>(fma, grid, h->stream, a);
-    } else {
-        ws_launch<G, false, WS_EPI_QKV8>(fma, grid, h->stream, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "qkv launch: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+        return ws_launch<G, LN(), WS_EPI_QKV8>(h, pl, a);
+    });
+    if (st) return st;
+    LAUNCH_CHECK(h);
     return IVIT_OK;
 }
 static int launch_qkv_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, const int16_t *x16, float ln_s,
@@ -625,7 +632,7 @@ static int launch_qkv_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8
 }
 
 template <class G>
-static int launch_res_ws_g(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, double cm, double cr, const int16_t *residual,
+static int launch_res_ws_g(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual,
                            int16_t *out, int M, float ln_s, const float *ln_bias_int, const float *ln_sc, const ivit_dyadic *ln_dy,
                            int8_t *ln_out8) {
     constexpr bool TAIL = G::K == 384;      // norm2 in the launch's tail: built at 384 only
@@ -635,35 +642,19 @@ static int launch_res_ws_g(ivit_handle h, const ivit_linear_plan_s *pl, const in
     a.x = x8; a.wf = pl->wf; a.bias = pl->bias_eff; a.cq = pl->cq; a.q = a.k = a.v = nullptr;
     a.M = M; a.N = pl->N; a.T = 1; a.H = 1; a.dummy = pl->dummy;
     a.x16 = nullptr; a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy;
-    a.residual = residual; a.out16 = out; a.cm = cm; a.cr = cr; a.ln_out8 = ln_out8; a.ldv = 0;
-    static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
-    const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
-    if (!cached || !attr_dev[h->device].load(std::memory_order_acquire)) {
-        hipError_t e = ws_attr<G, true, false, WS_EPI_RES16>();
-        if (e == hipSuccess) e = ws_attr<G, false, false, WS_EPI_RES16>();
-        if constexpr (TAIL) {
-            if (e == hipSuccess) e = ws_attr<G, true, true, WS_EPI_RES16>();
-            if (e == hipSuccess) e = ws_attr<G, false, true, WS_EPI_RES16>();
-        }
-        if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "linear attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-        if (cached) attr_dev[h->device].store(true, std::memory_order_release);
-    }
-    const int ntt = (M + 31) / 32;
-    const unsigned grid = (unsigned)(ntt < persistent_cus(h) ? ntt : persistent_cus(h));
-    if (ln_out8) {
-        if constexpr (TAIL) ws_launch<G, true, WS_EPI_RES16>(pl->single_fma_ok, grid, h->stream, a);
-    } else {
-        ws_launch<G, false, WS_EPI_RES16>(pl->single_fma_ok, grid, h->stream, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "linear launch: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+    a.residual = residual; a.out16 = out; a.cm = dy_main.m * dy_main.r; a.cr = dy_res.m * dy_res.r; a.ln_out8 = ln_out8; a.ldv = 0;
+    int st = IVIT_OK;
+    if (!ln_out8) st = ws_launch<G, false, WS_EPI_RES16>(h, pl, a);
+    else if constexpr (TAIL) st = ws_launch<G, true, WS_EPI_RES16>(h, pl, a);
+    if (st) return st;
+    LAUNCH_CHECK(h);
     return IVIT_OK;
 }
-static int launch_res_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, double cm, double cr, const int16_t *residual,
+static int launch_res_ws(ivit_handle h, const ivit_linear_plan_s *pl, const int8_t *x8, ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual,
                          int16_t *out, int M, float ln_s = 0.f, const float *ln_bias_int = nullptr, const float *ln_sc = nullptr,
                          const ivit_dyadic *ln_dy = nullptr, int8_t *ln_out8 = nullptr) {
-    return pl->K == Ws192Geo::K ? launch_res_ws_g<Ws192Geo>(h, pl, x8, cm, cr, residual, out, M, ln_s, ln_bias_int, ln_sc, ln_dy, ln_out8)
-                                : launch_res_ws_g<Ws384Geo>(h, pl, x8, cm, cr, residual, out, M, ln_s, ln_bias_int, ln_sc, ln_dy, ln_out8);
+    return pl->K == Ws192Geo::K ? launch_res_ws_g<Ws192Geo>(h, pl, x8, dy_main, dy_res, residual, out, M, ln_s, ln_bias_int, ln_sc, ln_dy, ln_out8)
+                                : launch_res_ws_g<Ws384Geo>(h, pl, x8, dy_main, dy_res, residual, out, M, ln_s, ln_bias_int, ln_sc, ln_dy, ln_out8);
 }
 
 template <int EPI>
@@ -688,25 +679,17 @@ static int launch_gemm3(ivit_handle h, const ivit_linear_plan_s *pl, GemmArgs &a
         long long grid = h->num_cu;
         if (grid > nunits) grid = nunits;
         const dim3 g((unsigned)grid);
-        if (a.K == GA_BK * GA_NK) {
-            if (fma) gemm_as_kernel<EPI, false, true><<<g, 512, 0, h->stream>>>(a);
-            else gemm_as_kernel<EPI, false, false><<<g, 512, 0, h->stream>>>(a);
-        } else {
-            if (fma) gemm_as_kernel<EPI, true, true><<<g, 512, 0, h->stream>>>(a);
-            else gemm_as_kernel<EPI, true, false><<<g, 512, 0, h->stream>>>(a);
-        }
+        with_bool(fma, [&](auto FMA) {
+            if (a.K == GA_BK * GA_NK) gemm_as_kernel<EPI, false, FMA()><<<g, 512, 0, h->stream>>>(a);
+            else gemm_as_kernel<EPI, true, FMA()><<<g, 512, 0, h->stream>>>(a);
+        });
     } else {
         const long long nunits = (long long)((a.M + 127) / 128) * a.tiles_n;
         long long grid = (long long)h->num_cu * wg_per_cu;
         if (grid > nunits) grid = nunits;
-        if (fma) gemm_ps_kernel<EPI, true, false><<<dim3((unsigned)grid), 256, 0, h->stream>>>(a);
-        else gemm_ps_kernel<EPI, false, false><<<dim3((unsigned)grid), 256, 0, h->stream>>>(a);
+        with_bool(fma, [&](auto FMA) { gemm_ps_kernel<EPI, FMA(), false><<<dim3((unsigned)grid), 256, 0, h->stream>>>(a); });
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "gemm3 launch: %s", hipGetErrorString(e));
-        return IVIT_ERR_HIP;
-    }
+    LAUNCH_CHECK(h);
     return IVIT_OK;
 }
 
@@ -741,9 +724,8 @@ int ivit_linear_i8_requant_residual_planned(ivit_handle h, ivit_linear_plan pl, 
     REQUIRE(h, pl && x && out && residual && M > 0, "bad arguments");
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy; a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual;
-    const bool res_fast = fabs(dy_main.m * dy_main.r) < RQ_FAST_CLIM && fabs(dy_res.m * dy_res.r) < RQ_FAST_CLIM;
-    if (res_fast && ws_plan_ok(pl, M))
-        return launch_res_ws(h, pl, x, dy_main.m * dy_main.r, dy_res.m * dy_res.r, residual, out, M);
+    const bool res_fast = rq_fast2(dy_main, dy_res);
+    if (res_fast && ws_plan_ok(pl, M)) return launch_res_ws(h, pl, x, dy_main, dy_res, residual, out, M);
     if (use_gemm3(pl, a, 4) && res_fast) return launch_gemm3<EPI_RQ16_CH_RES>(h, pl, a);
     return ivit_linear_i8_requant_residual(h, x, pl->w, pl->bias, pl->dy, dy_main, dy_res, residual, out, M, pl->N, pl->K);
 }
@@ -754,12 +736,11 @@ int ivit_linear_i8_requant_residual_layernorm_planned(ivit_handle h, ivit_linear
                                                       int8_t *ln_out8) {
     CHECK_H(h);
     REQUIRE(h, pl && x && out && residual && M > 0 && ln_bias_int && ln_sc && ln_dy && ln_out8, "bad arguments");
-    const bool res_fast = fabs(dy_main.m * dy_main.r) < RQ_FAST_CLIM && fabs(dy_res.m * dy_res.r) < RQ_FAST_CLIM;
-    if (!(pl->wf && res_fast && pl->K == Ws384Geo::K && pl->N == Ws384Geo::K && M < (1 << 26))) {
+    if (!(pl->wf && rq_fast2(dy_main, dy_res) && pl->K == Ws384Geo::K && pl->N == Ws384Geo::K && M < (1 << 26))) {
         snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a 384 x 384 plan and residual multipliers in the fast range", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
-    return launch_res_ws(h, pl, x, dy_main.m * dy_main.r, dy_res.m * dy_res.r, residual, out, M, ln_scale, ln_bias_int, ln_sc, ln_dy, ln_out8);
+    return launch_res_ws(h, pl, x, dy_main, dy_res, residual, out, M, ln_scale, ln_bias_int, ln_sc, ln_dy, ln_out8);
 }
 
 int ivit_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, const int8_t *x, int8_t *q, int8_t *k, int8_t *vt,
@@ -801,14 +782,7 @@ int ivit_linear_plan_prepare_ws(ivit_handle h, ivit_linear_plan pl) {
 int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, const int16_t *x16, float scale, const float *bias_int,
                                          const float *sc, const ivit_dyadic *ln_dy, int8_t *q, int8_t *k, int8_t *v, int B, int T,
                                          int H, int dh) {
-    CHECK_H(h);
-    REQUIRE(h, pl && x16 && bias_int && sc && ln_dy && q && k && v && B > 0 && T > 0 && H > 0 && dh > 0, "bad arguments");
-    REQUIRE(h, pl->N == 3 * H * dh && pl->K == H * dh, "plan shape is not [3*H*dh, H*dh]");
-    if (!qkv_ws_ok(pl, B, T, H, dh)) {
-        snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 192 or 384, dh = 64 plan and B*H*T*64 < 2^31", __func__);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    return launch_qkv_ws(h, pl, nullptr, x16, scale, bias_int, sc, ln_dy, q, k, v, B, T, H);
+    return ivit_layernorm_linear_i8_qkv_ldv_planned(h, pl, x16, scale, bias_int, sc, ln_dy, q, k, v, B, T, H, dh, 0);     // v row-major
 }
 
 int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan pl, const int16_t *x16, float scale, const float *bias_int,
@@ -874,18 +848,6 @@ int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan f
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // plan creation is a build-time call
-    // the dynamic-LDS attributes of the kernels this plan will launch: once, here
-    const bool fma = fc1->single_fma_ok && fc2->single_fma_ok;
-    auto lds = [&](const void *fn, int bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-    if (w384) {
-        lds(fma ? (const void *)mlp384_kernel<true> : (const void *)mlp384_kernel<false>, Mlp384Geo::SMEM);
-        lds(fma ? (const void *)mlp384rs_kernel<true> : (const void *)mlp384rs_kernel<false>, RS_SMEM);
-        lds(fma ? (const void *)mlp384rs_kernel<true, 1> : (const void *)mlp384rs_kernel<false, 1>, RS_SMEM);
-    } else if (w256) {
-        lds(fma ? (const void *)mlp256_kernel<true> : (const void *)mlp256_kernel<false>, Mlp256Geo::SMEM);
-    } else {
-        lds(fma ? (const void *)mlp192_kernel<true> : (const void *)mlp192_kernel<false>, Mlp192Geo::SMEM);
-    }
     ivit_mlp_plan_s *p = e == hipSuccess ? new (std::nothrow) ivit_mlp_plan_s() : nullptr;
     if (!p) {
         (void)hipFree(dev);
@@ -894,7 +856,7 @@ int ivit_mlp_plan_create(ivit_handle h, ivit_linear_plan fc1, ivit_linear_plan f
     }
     p->fc1 = fc1; p->fc2 = fc2; p->width = fc1->K; p->w1f = (v4i *)dev; p->w2f = (v4i *)(dev + wbytes);
     p->w1r = w384 ? (v4i *)(dev + 2 * wbytes) : nullptr; p->w2r = w384 ? (v4i *)(dev + 3 * wbytes) : nullptr;
-    p->fma = fma;
+    p->fma = fc1->single_fma_ok && fc2->single_fma_ok;
     p->kernel = 0;
     p->device = h->device;
     *out = p;
@@ -925,7 +887,7 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
     a.x = x; a.w1f = p->w1f; a.w2f = p->w2f; a.b1 = p->fc1->bias_eff; a.b2 = p->fc2->bias_eff;
     a.cq1 = p->fc1->cq; a.cq2 = p->fc2->cq; a.tab = gelu_table; a.residual = residual; a.out = out;
     a.cm = dy_main.m * dy_main.r; a.cr = dy_res.m * dy_res.r; a.M = M;
-    if (!(fabs(a.cm) < RQ_FAST_CLIM && fabs(a.cr) < RQ_FAST_CLIM)) {
+    if (!rq_fast2(dy_main, dy_res)) {
         snprintf(h->err, sizeof(h->err), "%s: residual multipliers out of the fast range", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
@@ -938,11 +900,11 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
         const long long slots = (long long)(w256 ? Mlp256Geo::WG_PER_CU : Mlp192Geo::WG_PER_CU) * persistent_cus(h);
         const unsigned grid = (unsigned)(ntiles < slots ? ntiles : slots);
         a.balanced = 1;
-        if (w256) {
-            if (p->fma) mlp256_kernel<true><<<grid, Mlp256Geo::THREADS, Mlp256Geo::SMEM, h->stream>>>(a);
-            else mlp256_kernel<false><<<grid, Mlp256Geo::THREADS, Mlp256Geo::SMEM, h->stream>>>(a);
-        } else if (p->fma) mlp192_kernel<true><<<grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, h->stream>>>(a);
-        else mlp192_kernel<false><<<grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, h->stream>>>(a);
+        const int st = with_bool(p->fma, [&](auto FMA) {
+            return w256 ? launch_dyn<mlp256_kernel<FMA()>>(h, grid, Mlp256Geo::THREADS, Mlp256Geo::SMEM, a)
+                        : launch_dyn<mlp192_kernel<FMA()>>(h, grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, a);
+        });
+        if (st) return st;
         LAUNCH_CHECK(h);
         return IVIT_OK;
     }
@@ -960,15 +922,13 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
         snprintf(h->err, sizeof(h->err), "%s: the LayerNorm prologue exists in the role-split kernel only (two units per CU or more)", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
-    if (role_split) {
-        a.w1f = p->w1r; a.w2f = p->w2r;
-        if (ln_dy) {
-            if (p->fma) mlp384rs_kernel<true, 1><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
-            else mlp384rs_kernel<false, 1><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
-        } else if (p->fma) mlp384rs_kernel<true><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
-        else mlp384rs_kernel<false><<<grid, RS_THREADS, RS_SMEM, h->stream>>>(a);
-    } else if (p->fma) mlp384_kernel<true><<<grid, MLP_THREADS, MLP_SMEM, h->stream>>>(a);
-    else mlp384_kernel<false><<<grid, MLP_THREADS, MLP_SMEM, h->stream>>>(a);
+    if (role_split) { a.w1f = p->w1r; a.w2f = p->w2r; }
+    const int st = with_bool(p->fma, [&](auto FMA) {
+        if (!role_split) return launch_dyn<mlp384_kernel<FMA()>>(h, grid, MLP_THREADS, MLP_SMEM, a);
+        return ln_dy ? launch_dyn<mlp384rs_kernel<FMA(), 1>>(h, grid, RS_THREADS, RS_SMEM, a)
+                     : launch_dyn<mlp384rs_kernel<FMA()>>(h, grid, RS_THREADS, RS_SMEM, a);
+    });
+    if (st) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -984,22 +944,15 @@ static int mlp128_launch(ivit_handle h, const int8_t *x, const int8_t *w1, const
     a.cq1 = reinterpret_cast<const double *>(dy1); a.cq2 = reinterpret_cast<const double *>(dy2);
     a.tab = gelu_table; a.residual = residual; a.out = out;
     a.cm = dy_main.m * dy_main.r; a.cr = dy_res.m * dy_res.r; a.M = M; a.balanced = 1;
-    if (!(fabs(a.cm) < RQ_FAST_CLIM && fabs(a.cr) < RQ_FAST_CLIM)) {
+    if (!rq_fast2(dy_main, dy_res)) {
         snprintf(h->err, sizeof(h->err), "ivit_mlp_fused: residual multipliers out of the fast range at C = 128");
         return IVIT_ERR_UNSUPPORTED;
     }
     REQUIRE(h, (((uintptr_t)x | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)dy1 | (uintptr_t)dy2 | (uintptr_t)b1 | (uintptr_t)b2) & 15) == 0 &&
                    (((uintptr_t)residual | (uintptr_t)out) & 7) == 0,
             "C = 128: x, w1, w2, b1, b2, dy1, dy2 must be 16-byte aligned, residual and out 8-byte aligned");
-    static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
-    const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
-    if (!cached || !attr_dev[h->device].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)mlp128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Mlp128Geo::SMEM);
-        if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "mlp_fused attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-        if (cached) attr_dev[h->device].store(true, std::memory_order_release);
-    }
     const long long ntiles = (M + 15) / 16, slots = (long long)Mlp128Geo::WG_PER_CU * persistent_cus(h);
-    mlp128_kernel<<<(unsigned)(ntiles < slots ? ntiles : slots), Mlp128Geo::THREADS, Mlp128Geo::SMEM, h->stream>>>(a);
+    if (int st = launch_dyn<mlp128_kernel>(h, (unsigned)(ntiles < slots ? ntiles : slots), Mlp128Geo::THREADS, Mlp128Geo::SMEM, a)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1029,39 +982,22 @@ template <int NB, bool FAST, int TT = 0, int LUT = 0, bool VROW = false, bool CL
 static int launch_attn2(ivit_handle h, const AttnArgs &a, int BH) {
     const size_t lds = AttCfg<NB>::SMEM + (LUT == 2 ? (size_t)ATT_ROWLINE_BYTES
                                                    : (LUT == 1 ? (size_t)((a.t_count + 3) & ~3) * 4 + (size_t)a.nc * 512 + 256 : 0));
-    if (lds > 65536) {
-        // once per device and instantiation for the largest size seen (the attribute is a maximum): since round 6 every launch of
-        // the row-table form is above 64 KB, and the eager single-stream mode pays host calls
-        static std::atomic<int> set_dev[IVIT_MAX_DEVICES];
-        const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
-        if (!cached || set_dev[h->device].load(std::memory_order_acquire) < (int)lds) {
-            hipError_t e = hipFuncSetAttribute((const void *)attn_fused_kernel<NB, FAST, TT, LUT, VROW, CLS>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "attn attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-            if (cached) set_dev[h->device].store((int)lds, std::memory_order_release);
-        }
-    }
-    attn_fused_kernel<NB, FAST, TT, LUT, VROW, CLS><<<BH, ATT_WAVES * 64, lds, h->stream>>>(a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "attn launch: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+    // (since round 6 every launch of the row-table form is above 64 KB)
+    if (int st = launch_dyn<attn_fused_kernel<NB, FAST, TT, LUT, VROW, CLS>>(h, BH, ATT_WAVES * 64, lds, a)) return st;
+    LAUNCH_CHECK(h);
     return IVIT_OK;
 }
 
 template <int NB>
 static int launch_attn(ivit_handle h, const AttnArgs &a, int BH) {
-    const double cq = a.dy_qk.m * a.dy_qk.r, cp = a.dy_pv.m * a.dy_pv.r;
-    const bool fast = (cq < 512.0 && cq > -512.0 && cp < 512.0 && cp > -512.0);
+    const bool fast = attn_fast(a.dy_qk, a.dy_pv);
     const bool lut = a.aq && a.et && a.cls;
-    if (a.rowtab) {     // row-line tables (ivit_attention_fused_rowlut): the multipliers were checked by the caller
-        if (a.ldv == 0) {   // v row-major
-            if (NB == 4 && a.T == 197) return launch_attn2<NB, true, 197, 2, true>(h, a, BH);
-            if (NB == 10 && a.T == 577) return launch_attn2<NB, true, 577, 2, true>(h, a, BH);
-            return launch_attn2<NB, true, 0, 2, true>(h, a, BH);
-        }
-        if (NB == 4 && a.T == 197) return launch_attn2<NB, true, 197, 2>(h, a, BH);
-        if (NB == 10 && a.T == 577) return launch_attn2<NB, true, 577, 2>(h, a, BH);
-        return launch_attn2<NB, true, 0, 2>(h, a, BH);
-    }
+    if (a.rowtab)       // row-line tables (ivit_attention_fused_rowlut): the multipliers were checked by the caller
+        return with_bool(a.ldv == 0, [&](auto VROW) {       // v row-major, or v^T
+            if (NB == 4 && a.T == 197) return launch_attn2<NB, true, 197, 2, VROW()>(h, a, BH);
+            if (NB == 10 && a.T == 577) return launch_attn2<NB, true, 577, 2, VROW()>(h, a, BH);
+            return launch_attn2<NB, true, 0, 2, VROW()>(h, a, BH);
+        });
     if (fast) {
         if (NB == 4 && a.T == 197) return lut ? launch_attn2<NB, true, 197, true>(h, a, BH) : launch_attn2<NB, true, 197>(h, a, BH);
         if (NB == 10 && a.T == 577) return lut ? launch_attn2<NB, true, 577, true>(h, a, BH) : launch_attn2<NB, true, 577>(h, a, BH);
@@ -1074,10 +1010,9 @@ static int launch_attn(ivit_handle h, const AttnArgs &a, int BH) {
 // folded tile tests of the fixed-T instantiations have nothing to pay for)
 template <int NB>
 static int launch_attn_cls(ivit_handle h, const AttnArgs &a, int BH) {
-    const double cq = a.dy_qk.m * a.dy_qk.r, cp = a.dy_pv.m * a.dy_pv.r;
-    const bool fast = (cq < 512.0 && cq > -512.0 && cp < 512.0 && cp > -512.0);
+    const bool fast = attn_fast(a.dy_qk, a.dy_pv);
     const bool lut = a.aq && a.et && a.cls;
-    if (a.rowtab) return a.ldv == 0 ? launch_attn2<NB, true, 0, 2, true, true>(h, a, BH) : launch_attn2<NB, true, 0, 2, false, true>(h, a, BH);
+    if (a.rowtab) return with_bool(a.ldv == 0, [&](auto VROW) { return launch_attn2<NB, true, 0, 2, VROW(), true>(h, a, BH); });
     if (fast && lut) return launch_attn2<NB, true, 0, 1, false, true>(h, a, BH);
     return fast ? launch_attn2<NB, true, 0, 0, false, true>(h, a, BH) : launch_attn2<NB, false, 0, 0, false, true>(h, a, BH);
 }
@@ -1158,17 +1093,29 @@ extern "C" int ivit_shiftmax_rowtable(ivit_handle h, const uint16_t *exp_aq, con
     return IVIT_OK;
 }
 
+// the row-table entries, whole T (cls_out false) and class-token form: a table line holds 64 entries and the kernel is built with
+// FAST = true only
+static int attention_rowlut(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt, ivit_dyadic dy_qk, float s_softmax,
+                            const float *rowtab, int dmin, ivit_dyadic dy_pv, int8_t *ctx8, int B, int H, int T, int dh, int ldv,
+                            bool cls_out, const int16_t *x16, int16_t *x_cls) {
+    if (!h) return IVIT_ERR_INVALID;
+    const char *entry = cls_out ? "ivit_attention_fused_rowlut_cls" : "ivit_attention_fused_rowlut";
+    if (!(rowtab && ((uintptr_t)rowtab & 15) == 0 && dmin <= 0 && dmin >= -63)) {
+        snprintf(h->err, sizeof(h->err), "%s: bad row table (16-byte aligned, 1 - dmin <= 64)", entry);
+        return IVIT_ERR_INVALID;
+    }
+    if (!attn_fast(dy_qk, dy_pv)) {
+        snprintf(h->err, sizeof(h->err), "%s: requant multipliers out of the fast range (use ivit_attention_fused_lut%s)", entry, cls_out ? "_cls" : "");
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return attention_fused_impl(h, q, k, vt, dy_qk, s_softmax, dy_pv, ctx8, B, H, T, dh, ldv, nullptr, nullptr, nullptr, 0, 0, dmin, rowtab,
+                                cls_out, x16, x_cls);
+}
+
 extern "C" int ivit_attention_fused_rowlut(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                                            ivit_dyadic dy_qk, float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv,
                                            int8_t *ctx8, int B, int H, int T, int dh, int ldv) {
-    if (!h) return IVIT_ERR_INVALID;
-    REQUIRE(h, rowtab && ((uintptr_t)rowtab & 15) == 0 && dmin <= 0 && dmin >= -63, "bad row table (16-byte aligned, 1 - dmin <= 64)");
-    const double cq = dy_qk.m * dy_qk.r, cp = dy_pv.m * dy_pv.r;
-    if (!(cq < 512.0 && cq > -512.0 && cp < 512.0 && cp > -512.0)) {
-        snprintf(h->err, sizeof(h->err), "%s: requant multipliers out of the fast range (use ivit_attention_fused_lut)", __func__);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    return attention_fused_impl(h, q, k, vt, dy_qk, s_softmax, dy_pv, ctx8, B, H, T, dh, ldv, nullptr, nullptr, nullptr, 0, 0, dmin, rowtab);
+    return attention_rowlut(h, q, k, vt, dy_qk, s_softmax, rowtab, dmin, dy_pv, ctx8, B, H, T, dh, ldv, false, nullptr, nullptr);
 }
 
 // ---- the class-token forms: the context of token 0 of every image into ctx_cls [B, H*dh], its identity row of x16 into x_cls
@@ -1191,15 +1138,7 @@ extern "C" int ivit_attention_fused_lut_cls(ivit_handle h, const int8_t *q, cons
 extern "C" int ivit_attention_fused_rowlut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt, ivit_dyadic dy_qk,
                                                float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv, int8_t *ctx_cls,
                                                const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv) {
-    if (!h) return IVIT_ERR_INVALID;
-    REQUIRE(h, rowtab && ((uintptr_t)rowtab & 15) == 0 && dmin <= 0 && dmin >= -63, "bad row table (16-byte aligned, 1 - dmin <= 64)");
-    const double cq = dy_qk.m * dy_qk.r, cp = dy_pv.m * dy_pv.r;
-    if (!(cq < 512.0 && cq > -512.0 && cp < 512.0 && cp > -512.0)) {
-        snprintf(h->err, sizeof(h->err), "%s: requant multipliers out of the fast range (use ivit_attention_fused_lut_cls)", __func__);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    return attention_fused_impl(h, q, k, vt, dy_qk, s_softmax, dy_pv, ctx_cls, B, H, T, dh, ldv, nullptr, nullptr, nullptr, 0, 0, dmin,
-                                rowtab, true, x16, x_cls);
+    return attention_rowlut(h, q, k, vt, dy_qk, s_softmax, rowtab, dmin, dy_pv, ctx_cls, B, H, T, dh, ldv, true, x16, x_cls);
 }
 
 // out[r][:] = x[r * row_stride ...][:C]: `rows` rows of C 16-bit values, 16 bytes per thread (the stand-alone form of the identity-row
@@ -1278,16 +1217,6 @@ int ivit_requant_f32(ivit_handle h, const float *z, const ivit_dyadic *dy, int n
 }
 
 // ---------------------------------------------------------------- shift/norm kernels
-static int set_dyn_lds(ivit_handle h, const void *fn, size_t bytes) {
-    if (bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) {
-            snprintf(h->err, sizeof(h->err), "hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return IVIT_ERR_HIP;
-        }
-    }
-    return IVIT_OK;
-}
 
 int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in, float scale, int out_bits,
                   uint16_t *out, int ld_out) {
@@ -1296,9 +1225,7 @@ int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in
     REQUIRE(h, out_bits == 8 || out_bits == 16, "out_bits must be 8 or 16");
     const size_t lds = (size_t)4 * n * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "row too long for LDS staging");
-    int st = set_dyn_lds(h, (const void *)shiftmax_kernel, lds);
-    if (st) return st;
-    shiftmax_kernel<<<(unsigned)((rows + 3) / 4), 256, lds, h->stream>>>(x, rows, n, ld_in, scale, out_bits, out, ld_out);
+    if (int st = launch_dyn<shiftmax_kernel>(h, (unsigned)((rows + 3) / 4), 256, lds, x, rows, n, ld_in, scale, out_bits, out, ld_out)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1409,12 +1336,20 @@ int ivit_layernorm(ivit_handle h, const int16_t *x, int64_t rows, int C, float s
     REQUIRE(h, (C % 8) == 0, "C must be a multiple of 8");
     const size_t lds = (size_t)8 * C * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
-    int st = set_dyn_lds(h, (const void *)layernorm_kernel<false>, lds);
-    if (st) return st;
-    layernorm_kernel<false><<<(unsigned)((rows + 7) / 8), 256, lds, h->stream>>>(x, rows, C, C, scale, bias_int, sc, nullptr, z);
+    if (int st = launch_dyn<layernorm_kernel<false>>(h, (unsigned)((rows + 7) / 8), 256, lds, x, rows, C, C, scale, bias_int, sc, nullptr, z)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
+
+// layernorm_reg_kernel<CC, S, MERGE> on `rows` rows (x, scale, bias_int, sc, dy_ch, out8 of the enclosing entry), and out of the entry
+#define LNR_LAUNCH(CC, S, MERGE, row_stride, merge_R)                                                                     \
+    do {                                                                                                                  \
+        constexpr int rpb = (LNR_THREADS(S) / 64) * (64 / (4 * S));                                                       \
+        layernorm_reg_kernel<CC, S, MERGE><<<(unsigned)((rows + rpb - 1) / rpb), LNR_THREADS(S), 0, h->stream>>>(        \
+            x, rows, row_stride, scale, bias_int, sc, dy_ch, out8, merge_R);                                              \
+        LAUNCH_CHECK(h);                                                                                                  \
+        return IVIT_OK;                                                                                                   \
+    } while (0)
 
 int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C, int64_t row_stride, float scale,
                            const float *bias_int, const float *sc, const ivit_dyadic *dy_ch, int8_t *out8) {
@@ -1422,29 +1357,22 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
     REQUIRE(h, x && bias_int && sc && dy_ch && out8 && rows > 0 && C > 0 && scale > 0.f, "bad arguments");
     REQUIRE(h, (C % 8) == 0 && (row_stride % 8) == 0 && row_stride >= C, "C, row_stride multiples of 8");
     {   // production form: the row in registers, 4 S lanes per row (ivit_layernorm.h)
-#define LNR_LAUNCH(CC, S)                                                                                      \
-        do {                                                                                                    \
-            constexpr int rpb = (LNR_THREADS(S) / 64) * (64 / (4 * S));                                         \
-            layernorm_reg_kernel<CC, S><<<(unsigned)((rows + rpb - 1) / rpb), LNR_THREADS(S), 0, h->stream>>>( \
-                x, rows, row_stride, scale, bias_int, sc, dy_ch, out8);                                         \
-            LAUNCH_CHECK(h);                                                                                    \
-            return IVIT_OK;                                                                                     \
-        } while (0)
+#define LNR(CC, S) LNR_LAUNCH(CC, S, false, row_stride, 0)
         switch (C) {
             // lanes per row = 4 S (measured on DeiT-S b256: S = 1 23.2 us, S = 2 20.1, S = 4 20.2 — shorter per-wave instruction
             // chains and more waves per SIMD beat the cheaper quad-only reduction).  ivit_layernorm.h has the history of S = 1
-            case 96: LNR_LAUNCH(96, 2);        // Swin-T/S stage 0 (token-order sums use their own kernel)
-            case 128: LNR_LAUNCH(128, 2);      // Swin-B stage 0
-            case 192: LNR_LAUNCH(192, 2);      // DeiT-T, Swin stage 1
-            case 256: LNR_LAUNCH(256, 2);
-            case 384: LNR_LAUNCH(384, 2);      // DeiT-S, Swin stage 2, PatchMerging
-            case 512: LNR_LAUNCH(512, 4);
-            case 768: LNR_LAUNCH(768, 4);      // DeiT-B / ViT-B, Swin stage 3
-            case 1024: LNR_LAUNCH(1024, 4);    // ViT-L
-            case 1536: LNR_LAUNCH(1536, 4);    // Swin PatchMerging before stage 3
+            case 96: LNR(96, 2);        // Swin-T/S stage 0 (token-order sums use their own kernel)
+            case 128: LNR(128, 2);      // Swin-B stage 0
+            case 192: LNR(192, 2);      // DeiT-T, Swin stage 1
+            case 256: LNR(256, 2);
+            case 384: LNR(384, 2);      // DeiT-S, Swin stage 2, PatchMerging
+            case 512: LNR(512, 4);
+            case 768: LNR(768, 4);      // DeiT-B / ViT-B, Swin stage 3
+            case 1024: LNR(1024, 4);    // ViT-L
+            case 1536: LNR(1536, 4);    // Swin PatchMerging before stage 3
             default: break;
         }
-#undef LNR_LAUNCH
+#undef LNR
     }
     {   // other channel counts: 16 lanes per row, the row staged in LDS
         const size_t lds16 = (size_t)16 * (C + 16) * 4 + (size_t)C * 20;
@@ -1453,18 +1381,14 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
             riter = riter < 1 ? 1 : (riter > LN_RITER ? LN_RITER : riter);
             const long long per_block = 16 * riter;
             const unsigned grid = (unsigned)((rows + per_block - 1) / per_block);
-            int st16 = set_dyn_lds(h, (const void *)layernorm16_kernel<0>, lds16);
-            if (st16) return st16;
-            layernorm16_kernel<0><<<grid, 256, lds16, h->stream>>>(x, rows, C, row_stride, scale, bias_int, sc, dy_ch, out8, (int)riter);
+            if (int st = launch_dyn<layernorm16_kernel<0>>(h, grid, 256, lds16, x, rows, C, row_stride, scale, bias_int, sc, dy_ch, out8, (int)riter)) return st;
             LAUNCH_CHECK(h);
             return IVIT_OK;
         }
     }
     const size_t lds = (size_t)8 * C * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
-    int st = set_dyn_lds(h, (const void *)layernorm_kernel<true>, lds);
-    if (st) return st;
-    layernorm_kernel<true><<<(unsigned)((rows + 7) / 8), 256, lds, h->stream>>>(x, rows, C, row_stride, scale, bias_int, sc, dy_ch, out8);
+    if (int st = launch_dyn<layernorm_kernel<true>>(h, (unsigned)((rows + 7) / 8), 256, lds, x, rows, C, row_stride, scale, bias_int, sc, dy_ch, out8)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1476,23 +1400,17 @@ int ivit_patch_merge_layernorm_requant(ivit_handle h, const int16_t *x, int B, i
     CHECK_H(h);
     REQUIRE(h, x && bias_int && sc && dy_ch && out8 && B > 0 && R > 0 && (R % 2) == 0 && C > 0 && scale > 0.f, "bad arguments");
     const long long rows = (long long)B * (R / 2) * (R / 2);
-#define LNM_LAUNCH(CC, S)                                                                                                \
-    do {                                                                                                                 \
-        constexpr int rpb = (LNR_THREADS(S) / 64) * (64 / (4 * S));                                                      \
-        layernorm_reg_kernel<CC, S, true><<<(unsigned)((rows + rpb - 1) / rpb), LNR_THREADS(S), 0, h->stream>>>(        \
-            x, rows, 0, scale, bias_int, sc, dy_ch, out8, R);                                                            \
-        LAUNCH_CHECK(h);                                                                                                 \
-        return IVIT_OK;                                                                                                  \
-    } while (0)
+#define LNM(CC, S) LNR_LAUNCH(CC, S, true, 0, R)
     switch (4 * C) {
-        case 384: LNM_LAUNCH(384, 2);       // Swin-T/S: 96 -> 384
-        case 512: LNM_LAUNCH(512, 4);       // Swin-B: 128 -> 512
-        case 768: LNM_LAUNCH(768, 4);
-        case 1024: LNM_LAUNCH(1024, 4);
-        case 1536: LNM_LAUNCH(1536, 4);
+        case 384: LNM(384, 2);       // Swin-T/S: 96 -> 384
+        case 512: LNM(512, 4);       // Swin-B: 128 -> 512
+        case 768: LNM(768, 4);
+        case 1024: LNM(1024, 4);
+        case 1536: LNM(1536, 4);
         default: break;
     }
-#undef LNM_LAUNCH
+#undef LNM
+#undef LNR_LAUNCH
     snprintf(h->err, sizeof(h->err), "%s: built for C = 96, 128, 192, 256, 384 (use ivit_patch_merge_gather + ivit_layernorm_requant)", __func__);
     return IVIT_ERR_UNSUPPORTED;
 }
@@ -1506,10 +1424,9 @@ int ivit_shiftmax_masked(ivit_handle h, const int8_t *x, int64_t rows, int n, in
     REQUIRE(h, mask == nullptr || (nW > 0 && H > 0), "mask needs nW, H");
     const size_t lds = (size_t)4 * n * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "row too long for LDS staging");
-    int st = set_dyn_lds(h, (const void *)shiftmax_masked_kernel, lds);
-    if (st) return st;
-    shiftmax_masked_kernel<<<(unsigned)((rows + 3) / 4), 256, lds, h->stream>>>(x, rows, n, ld_in, scale, out_bits, mask,
-                                                                          nW > 0 ? nW : 1, H > 0 ? H : 1, out, ld_out);
+    if (int st = launch_dyn<shiftmax_masked_kernel>(h, (unsigned)((rows + 3) / 4), 256, lds, x, rows, n, ld_in, scale, out_bits, mask,
+                                                    nW > 0 ? nW : 1, H > 0 ? H : 1, out, ld_out))
+        return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1544,29 +1461,31 @@ int ivit_avgpool_requant_scaled(ivit_handle h, const int8_t *x, int B, int L, in
     return IVIT_OK;
 }
 
+// LDS bytes of layernorm_tokenorder_kernel at C channels; of layernorm_tokenorder8_kernel (C = 96 / 128), and its grid
+static inline size_t lnt_lds(int C) { return ((size_t)LNT_ROWS * (C + 1) + 3 * (size_t)C + 2 * LNT_ROWS + 2) * sizeof(float) + (size_t)C * sizeof(double); }
+static inline size_t lnt8_lds(int C) { return ((size_t)LNT8_ROWS * (C + 1) + C + 2 * LNT8_ROWS) * sizeof(float); }
+static inline unsigned lnt8_grid(int64_t rows) { return (unsigned)((rows + LNT8_ROWS - 1) / LNT8_ROWS); }
+
 int ivit_layernorm_tokenorder_requant(ivit_handle h, const int16_t *x, int64_t rows, int C, float scale,
                                       const float *bias_int, const float *sc, const ivit_dyadic *dy,
                                       int tokens_per_image, int8_t *out8) {
     CHECK_H(h);
     REQUIRE(h, x && bias_int && sc && dy && out8 && rows > 0 && C > 0 && scale > 0.f && tokens_per_image > 0, "bad arguments");
-    const size_t lds = ((size_t)LNT_ROWS * (C + 1) + 3 * (size_t)C + 2 * LNT_ROWS + 2) * sizeof(float) + (size_t)C * sizeof(double);
+    const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
+    int st;
     if (C == 96 || C == 128) {          // Swin-T/S and Swin-B stage 0
-        const size_t lds8 = ((size_t)LNT8_ROWS * (C + 1) + C + 2 * LNT8_ROWS) * sizeof(float);
-        const unsigned g8 = (unsigned)((rows + LNT8_ROWS - 1) / LNT8_ROWS);
         REQUIRE(h, (((uintptr_t)x | (uintptr_t)out8 | (uintptr_t)bias_int | (uintptr_t)sc) & 15) == 0,
                 "C = 96 / 128: x, out, bias_int, sc must be 16-byte aligned (vector loads)");
-        const void *fn = C == 96 ? (const void *)layernorm_tokenorder8_kernel<1, 96, int16_t> : (const void *)layernorm_tokenorder8_kernel<1, 128, int16_t>;
-        int st = set_dyn_lds(h, fn, lds8);
-        if (st) return st;
-        if (C == 96) layernorm_tokenorder8_kernel<1, 96, int16_t><<<g8, 96 / 8 * 16, lds8, h->stream>>>(x, rows, scale, bias_int, sc, dy, tokens_per_image, out8, ivit_dyadic{0.0, 0.0});
-        else layernorm_tokenorder8_kernel<1, 128, int16_t><<<g8, 128 / 8 * 16, lds8, h->stream>>>(x, rows, scale, bias_int, sc, dy, tokens_per_image, out8, ivit_dyadic{0.0, 0.0});
+        st = with_width(C, [&](auto W) {
+            return launch_dyn<layernorm_tokenorder8_kernel<1, W(), int16_t>>(h, lnt8_grid(rows), W() / 8 * 16, lnt8_lds(C), x, rows, scale, bias_int, sc, dy,
+                                                                             tokens_per_image, out8, ivit_dyadic{0.0, 0.0});
+        });
     } else {
-        int st = set_dyn_lds(h, (const void *)layernorm_tokenorder_kernel<1, 0>, lds);
-        if (st) return st;
-        layernorm_tokenorder_kernel<1, 0><<<(unsigned)((rows + LNT_ROWS - 1) / LNT_ROWS), 256, lds, h->stream>>>(
-            x, rows, C, scale, bias_int, sc, dy, tokens_per_image, out8);
+        st = launch_dyn<layernorm_tokenorder_kernel<1, 0>>(h, (unsigned)((rows + LNT_ROWS - 1) / LNT_ROWS), 256, lds, x, rows, C, scale, bias_int, sc, dy,
+                                                           tokens_per_image, out8, ivit_dyadic{0.0, 0.0});
     }
+    if (st) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1576,25 +1495,21 @@ int ivit_patch_norm_tokenorder(ivit_handle h, const int8_t *x8, int64_t rows, in
                                int16_t *out16) {
     CHECK_H(h);
     REQUIRE(h, x8 && bias_int && sc && dy_ch && out16 && rows > 0 && C > 0 && scale > 0.f && tokens_per_image > 0, "bad arguments");
-    const size_t lds = ((size_t)LNT_ROWS * (C + 1) + 3 * (size_t)C + 2 * LNT_ROWS + 2) * sizeof(float) + (size_t)C * sizeof(double);
+    const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
-    const unsigned grid = (unsigned)((rows + LNT_ROWS - 1) / LNT_ROWS);
+    int st;
     if (C == 96 || C == 128) {
-        const size_t lds8 = ((size_t)LNT8_ROWS * (C + 1) + C + 2 * LNT8_ROWS) * sizeof(float);
-        const unsigned g8 = (unsigned)((rows + LNT8_ROWS - 1) / LNT8_ROWS);
         REQUIRE(h, (((uintptr_t)x8 | (uintptr_t)out16 | (uintptr_t)bias_int | (uintptr_t)sc) & 15) == 0,
                 "C = 96 / 128: x, out, bias_int, sc must be 16-byte aligned (vector loads)");
-        const void *fn = C == 96 ? (const void *)layernorm_tokenorder8_kernel<2, 96, int8_t> : (const void *)layernorm_tokenorder8_kernel<2, 128, int8_t>;
-        int st = set_dyn_lds(h, fn, lds8);
-        if (st) return st;
-        if (C == 96) layernorm_tokenorder8_kernel<2, 96, int8_t><<<g8, 96 / 8 * 16, lds8, h->stream>>>(x8, rows, scale, bias_int, sc, dy_ch, tokens_per_image, out16, dy2);
-        else layernorm_tokenorder8_kernel<2, 128, int8_t><<<g8, 128 / 8 * 16, lds8, h->stream>>>(x8, rows, scale, bias_int, sc, dy_ch, tokens_per_image, out16, dy2);
+        st = with_width(C, [&](auto W) {
+            return launch_dyn<layernorm_tokenorder8_kernel<2, W(), int8_t>>(h, lnt8_grid(rows), W() / 8 * 16, lnt8_lds(C), x8, rows, scale, bias_int, sc, dy_ch,
+                                                                            tokens_per_image, out16, dy2);
+        });
     } else {
-        int st = set_dyn_lds(h, (const void *)layernorm_tokenorder_kernel<2, 0, int8_t>, lds);
-        if (st) return st;
-        layernorm_tokenorder_kernel<2, 0, int8_t><<<grid, 256, lds, h->stream>>>(x8, rows, C, scale, bias_int, sc, dy_ch,
-                                                                           tokens_per_image, out16, dy2);
+        st = launch_dyn<layernorm_tokenorder_kernel<2, 0, int8_t>>(h, (unsigned)((rows + LNT_ROWS - 1) / LNT_ROWS), 256, lds, x8, rows, C, scale, bias_int, sc,
+                                                                   dy_ch, tokens_per_image, out16, dy2);
     }
+    if (st) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1603,12 +1518,11 @@ int ivit_layernorm_tokenorder(ivit_handle h, const int16_t *x, int64_t rows, int
                               const float *bias_int, const float *sc, int tokens_per_image, float *z) {
     CHECK_H(h);
     REQUIRE(h, x && bias_int && sc && z && rows > 0 && C > 0 && scale > 0.f && tokens_per_image > 0, "bad arguments");
-    const size_t lds = ((size_t)LNT_ROWS * (C + 1) + 3 * (size_t)C + 2 * LNT_ROWS + 2) * sizeof(float) + (size_t)C * sizeof(double);
+    const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
-    int st = set_dyn_lds(h, (const void *)layernorm_tokenorder_kernel<0, 0>, lds);
-    if (st) return st;
-    layernorm_tokenorder_kernel<0, 0><<<(unsigned)((rows + LNT_ROWS - 1) / LNT_ROWS), 256, lds, h->stream>>>(
-        x, rows, C, scale, bias_int, sc, nullptr, tokens_per_image, z);
+    if (int st = launch_dyn<layernorm_tokenorder_kernel<0, 0>>(h, (unsigned)((rows + LNT_ROWS - 1) / LNT_ROWS), 256, lds, x, rows, C, scale, bias_int, sc,
+                                                               nullptr, tokens_per_image, z, ivit_dyadic{0.0, 0.0}))
+        return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1648,7 +1562,7 @@ int ivit_embed_finish(ivit_handle h, const int16_t *patch16, const int32_t *z_cl
     CHECK_H(h);
     REQUIRE(h, patch16 && z_cls && pos && x16 && B > 0 && T > 1 && D > 0 && (D % 8) == 0, "bad arguments (D must be a multiple of 8)");
     REQUIRE(h, (long long)T * D / 8 < (1 << 22) && B <= 65535, "T * D / 8 < 2^22, B < 2^16");
-    const int fast = fabs(dy_x.m * dy_x.r) < RQ_FAST_CLIM && fabs(dy_pos.m * dy_pos.r) < RQ_FAST_CLIM;
+    const int fast = rq_fast2(dy_x, dy_pos);
     embed_finish_kernel<<<dim3((unsigned)((T * (D / 8) + 255) / 256), (unsigned)B), 256, 0, h->stream>>>(
         patch16, z_cls, pos, dy_x, dy_pos, x16, T, D, 1.0f / (float)(D / 8), fast);
     LAUNCH_CHECK(h);
@@ -1661,7 +1575,7 @@ int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int C, int H, i
     CHECK_H(h);
     REQUIRE(h, images && w && dy_ch && z_cls && pos && x16 && B > 0 && C > 0 && H > 0 && W > 0 && P > 0 && D > 0, "bad arguments");
     const int gh = H / P, gw = W / P, np = gh * gw, K = C * P * P, T = np + 1;
-    const bool fast = fabs(dy_x.m * dy_x.r) < RQ_FAST_CLIM && fabs(dy_pos.m * dy_pos.r) < RQ_FAST_CLIM;
+    const bool fast = rq_fast2(dy_x, dy_pos);
     GemmArgs a = linear_args(images, w, bias, B * np, D, K);
     if (P != 16 || H % 16 || W % 16 || (D % 8) != 0 || (K % 64) != 0 || !fast || !use_gemm2(a) || (long long)B * np >= (1ll << 30) ||
         (long long)T * D / 8 >= (1 << 22) || B > 65535) {
@@ -1712,10 +1626,8 @@ static int window_attention12_launch(ivit_handle h, const int8_t *qkv, ivit_dyad
     int wpb = 8;
     while (wpb > 1 && ((nwin + wpb - 1) / wpb) * heads < 3 * slots) wpb >>= 1;
     a.wpb = wpb;
-    int st = set_dyn_lds(h, (const void *)window_attention12_kernel<12>, WA12_SMEM);
-    if (st) return st;
     const long long groups = (nwin + wpb - 1) / wpb;      // grid: whole groups of 8 window groups (see the kernel)
-    window_attention12_kernel<12><<<dim3((unsigned)(((groups + 7) / 8) * 8 * heads)), WA12_THREADS, WA12_SMEM, h->stream>>>(a);
+    if (int st = launch_dyn<window_attention12_kernel<12>>(h, (unsigned)(((groups + 7) / 8) * 8 * heads), WA12_THREADS, WA12_SMEM, a)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1754,10 +1666,8 @@ static int window_attention_impl(ivit_handle h, const int8_t *qkv, ivit_dyadic d
         while (wpw > 1 && ((nwin + 8LL * wpw - 1) / (8LL * wpw)) * heads < 3 * slots) wpw >>= 1;
         a.wpw = wpw;
         const size_t lds = WA_FIXED(8) + (size_t)((t_count + 3) & ~3) * 4 + (size_t)nc * 512 + 256;
-        int st = set_dyn_lds(h, (const void *)window_attention_kernel<true>, lds);
-        if (st) return st;
         const long long groups = (nwin + 8LL * wpw - 1) / (8LL * wpw);      // grid: whole groups of 8 window groups (see the kernel)
-        window_attention_kernel<true><<<dim3((unsigned)(((groups + 7) / 8) * 8 * heads)), 512, lds, h->stream>>>(a);
+        if (int st = launch_dyn<window_attention_kernel<true>>(h, (unsigned)(((groups + 7) / 8) * 8 * heads), 512, lds, a)) return st;
     } else {
         const long long groups = (nwin + 3) / 4;
         window_attention_kernel<false><<<dim3((unsigned)(((groups + 7) / 8) * 8 * heads)), 256, WA_FIXED(4), h->stream>>>(a);
@@ -1795,15 +1705,6 @@ int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32
                  __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
-    // the dynamic-LDS attribute is per device (one process-wide flag left the second GPU of a process without it)
-    static std::atomic<bool> attr_dev[IVIT_MAX_DEVICES];
-    const bool cached = h->device >= 0 && h->device < IVIT_MAX_DEVICES;
-    if (!cached || !attr_dev[h->device].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)swin_mlp_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MF_SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)swin_mlp_rs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SR_SMEM);
-        if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "mlp_fused attr: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-        if (cached) attr_dev[h->device].store(true, std::memory_order_release);
-    }
     MlpFusedArgs a;
     a.x = x; a.w1 = w1; a.b1 = b1; a.dy1 = dy1; a.tab = gelu_table; a.w2 = w2; a.b2 = b2; a.dy2 = dy2;
     a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual; a.out = out; a.M = M;
@@ -1811,8 +1712,9 @@ int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32
     const unsigned grid = (unsigned)(ntiles < h->num_cu ? ntiles : h->num_cu);
     // role-split form (ivit_swin_mlp_rs.h: producers on fc1 of tile i + 1 beside consumers on ShiftGELU / fc2 of tile i) when a
     // workgroup has at least two tiles to overlap; the phase-by-phase kernel otherwise
-    if (ntiles >= 2 * (long long)grid) swin_mlp_rs_kernel<<<grid, SR_THREADS, SR_SMEM, h->stream>>>(a);
-    else swin_mlp_fused_kernel<<<grid, MF_THREADS, MF_SMEM, h->stream>>>(a);
+    if (int st = ntiles >= 2 * (long long)grid ? launch_dyn<swin_mlp_rs_kernel>(h, grid, SR_THREADS, SR_SMEM, a)
+                                               : launch_dyn<swin_mlp_fused_kernel>(h, grid, MF_THREADS, MF_SMEM, a))
+        return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

@@ -1,9 +1,107 @@
-// ivit_model.h — native runner for the frozen integer DeiT/ViT forward (include/ivit.h,
-// "whole-model runner").  Chains the C-ABI entry points of ivit_hip.hip in the order of the
-// reference's VisionTransformer.forward (vit_quant.py:254-282); owns the ShiftGELU tables, the
-// slice streams/events and the optional hipGraph.  Included at the end of ivit_hip.hip.
+// ivit_model.h — native runners for the frozen integer DeiT/ViT and Swin forwards (include/ivit.h,
+// "whole-model runner").  Each chains the C-ABI entry points of ivit_hip.hip in the order of the
+// reference's forward (vit_quant.py:254-282, swin_quant.py) and owns its ShiftGELU tables and plans.
+// What is not about a model is written once, first: SliceRunner (the slice streams, events and
+// handles), fork_join, graph_capture, RUN / fused_or and gelu_table.  Included at the end of ivit_hip.hip.
 #pragma once
 #include <vector>
+
+struct ivit_graph_s {
+    ivit_handle h;
+    hipGraph_t graph;
+    hipGraphExec_t exec;
+};
+
+namespace {
+
+// the internal streams of a runner: one stream, "done" event and handle per slice, and the event the slices fork from
+struct SliceRunner {
+    std::vector<ivit_handle> slice_h;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> done;
+    hipEvent_t fork = nullptr;
+
+    // nothing for one slice.  Each resource is owned by the struct as soon as it exists, so destroy() after a failure releases it
+    bool create(ivit_handle h, int max_slices) {
+        if (max_slices <= 1) return true;
+        bool ok = hipEventCreateWithFlags(&fork, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; ok && i < max_slices; ++i) {
+            hipStream_t st = nullptr;
+            hipEvent_t ev = nullptr;
+            ivit_handle sh = nullptr;
+            ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
+            if (ok) streams.push_back(st);
+            ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+            if (ok) done.push_back(ev);
+            ok = ok && ivit_create(&sh, h->device, st) == IVIT_OK;
+            if (ok) slice_h.push_back(sh);
+        }
+        return ok;
+    }
+    void destroy() {
+        for (auto sh : slice_h) ivit_destroy(sh);
+        for (auto ev : done) (void)hipEventDestroy(ev);
+        for (auto st : streams) (void)hipStreamDestroy(st);
+        if (fork) (void)hipEventDestroy(fork);
+    }
+};
+
+inline int slice_begin(int batch, int nslices, int i) { return (int)(((long long)batch * i) / nslices); }
+inline int max_slice(int batch, int nslices) { return (batch + nslices - 1) / nslices; }
+
+// body(handle, slice index, first image, images) for each of `nslices` slices of `batch` images: on the caller's handle for one slice,
+// else on the internal streams, forked from and joined back into the caller's stream.  A failing slice's error text goes to `h`
+template <class Body>
+int fork_join(const SliceRunner &r, ivit_handle h, int batch, int nslices, Body &&body) {
+    if (nslices == 1) return body(h, 0, 0, batch);
+    if (hipEventRecord(r.fork, h->stream) != hipSuccess) return IVIT_ERR_HIP;
+    for (int i = 0; i < nslices; ++i) {
+        const int b0 = slice_begin(batch, nslices, i), b1 = slice_begin(batch, nslices, i + 1);
+        if (hipStreamWaitEvent(r.streams[i], r.fork, 0) != hipSuccess) return IVIT_ERR_HIP;
+        r.slice_h[i]->cu_share = std::max(1, persistent_cus(h) / nslices);      // a share of the caller's own share
+        const int rc = body(r.slice_h[i], i, b0, b1 - b0);
+        if (rc != IVIT_OK) { snprintf(h->err, sizeof(h->err), "%s", r.slice_h[i]->err); return rc; }
+        if (hipEventRecord(r.done[i], r.streams[i]) != hipSuccess) return IVIT_ERR_HIP;
+    }
+    for (int i = 0; i < nslices; ++i)
+        if (hipStreamWaitEvent(h->stream, r.done[i], 0) != hipSuccess) return IVIT_ERR_HIP;
+    return IVIT_OK;
+}
+
+// `forward()` captured on the handle's stream into an executable graph
+template <class Fwd>
+int graph_capture(ivit_handle h, ivit_graph *out, Fwd &&forward) {
+    REQUIRE(h, out, "null argument");
+    REQUIRE(h, h->stream != nullptr, "graph capture needs a non-default stream on the handle");
+    hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed);
+    if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "begin capture: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+    const int rc = forward();
+    hipGraph_t graph = nullptr;
+    e = hipStreamEndCapture(h->stream, &graph);
+    if (rc != IVIT_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (e != hipSuccess || !graph) { snprintf(h->err, sizeof(h->err), "end capture: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+    hipGraphExec_t exec = nullptr;
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) { (void)hipGraphDestroy(graph); snprintf(h->err, sizeof(h->err), "instantiate: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+    ivit_graph_s *g = new (std::nothrow) ivit_graph_s();
+    if (!g) { (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph); return IVIT_ERR_HIP; }
+    g->h = h; g->graph = graph; g->exec = exec;
+    *out = g;
+    return IVIT_OK;
+}
+
+// the slice bodies: a failing call ends the slice with its status
+#define RUN(call) do { const int rc_ = (call); if (rc_ != IVIT_OK) return rc_; } while (0)
+// a fused entry point where it takes the case (`fused`: its status, or IVIT_ERR_UNSUPPORTED without calling it), else the launches it
+// stands for; any other status of the fused entry is the slice's
+template <class Fallback>
+int fused_or(int fused, Fallback &&fallback) { return fused == IVIT_ERR_UNSUPPORTED ? fallback() : fused; }
+
+// block i's ShiftGELU table
+template <class Model>
+int8_t *gelu_table(const Model *m, int i) { return m->gelu_tab + (size_t)i * 65536; }
+
+}  // namespace
 
 struct ivit_vit_s {
     ivit_handle h;                    // the caller's handle (its stream is the parent stream)
@@ -18,16 +116,7 @@ struct ivit_vit_s {
     std::vector<ivit_linear_plan> plans;   // per block: qkv, proj, fc1, fc2 (frozen QuantLinear plans, ivit_linear_plan_create)
     std::vector<ivit_mlp_plan> mlp_plans;  // per block: fused Mlp plan (D = 384 or 192), or null -> fc1 / ShiftGELU / fc2 launches
     int max_slices;
-    std::vector<ivit_handle> slice_h; // one handle per internal stream
-    std::vector<hipStream_t> streams;
-    std::vector<hipEvent_t> done;
-    hipEvent_t fork;
-};
-
-struct ivit_graph_s {
-    ivit_handle h;
-    hipGraph_t graph;
-    hipGraphExec_t exec;
+    SliceRunner run;
 };
 
 namespace {
@@ -74,11 +163,8 @@ inline bool mlp_plan_shape(int C, int Hd) {
 // THE rule for "this block's Mlp is one ivit_mlp_fused_planned launch at M tokens": run_slice, swin_run_slice and the
 // ivit_*_fused_mlp_blocks queries all ask here.  No token-count threshold: at width 192 the fused launch measured faster than
 // the three-launch chain at every size tried, 197 tokens (DeiT-T batch 1: 15.8 against 20.0 us) to 200 704 (profiles/README.md)
-inline bool mlp_res_fast(ivit_dyadic res_main, ivit_dyadic res_res) {
-    return fabs(res_main.m * res_main.r) < RQ_FAST_CLIM && fabs(res_res.m * res_res.r) < RQ_FAST_CLIM;
-}
 inline bool mlp_plan_fuses(ivit_mlp_plan mp, ivit_dyadic res_main, ivit_dyadic res_res, long long /*M*/) {
-    return mp && mlp_res_fast(res_main, res_res);
+    return mp && rq_fast2(res_main, res_res);
 }
 
 // THE rule for "this block's norm1 + qkv is one ivit_layernorm_linear_i8_qkv_ldv_planned launch at B images": run_slice and
@@ -98,8 +184,26 @@ inline bool cls_tail(const ivit_vit_s *m) {
     return m->fused_attention && (size_t)m->num_patches * m->Kp >= (size_t)m->cfg.embed_dim;
 }
 
-inline int slice_begin(int batch, int nslices, int i) { return (int)(((long long)batch * i) / nslices); }
-inline int max_slice(int batch, int nslices) { return (batch + nslices - 1) / nslices; }
+// block i's attention on the fused kernel, in the Shiftmax form the block has tables for (v row-major, ldv = 0, with a row table; v^T
+// otherwise).  cls: the class-token form — the context of
+// token 0 of every image into `ctx` [B, D], its identity row of x16 into x_cls
+int vit_attention(const ivit_vit_s *m, ivit_handle h, int i, const int8_t *q, const int8_t *k, const int8_t *vt, int8_t *ctx, int B, int ldv,
+                  bool cls, const int16_t *x16, int16_t *x_cls) {
+    const ivit_vit_block &b = m->blocks[i];
+    const int T = m->T, H = m->cfg.num_heads, dh = m->cfg.embed_dim / H;
+    if (m->has_rowtab[i]) {      // one gather per score (round 6)
+        const float *rowtab = m->rowtab + (size_t)i * 256 * 64;
+        return cls ? ivit_attention_fused_rowlut_cls(h, q, k, vt, b.dy_qk, b.s_softmax, rowtab, b.exp_dmin, b.dy_pv, ctx, x16, x_cls, B, H, T, dh, ldv)
+                   : ivit_attention_fused_rowlut(h, q, k, vt, b.dy_qk, b.s_softmax, rowtab, b.exp_dmin, b.dy_pv, ctx, B, H, T, dh, ldv);
+    }
+    if (b.exp_aq)
+        return cls ? ivit_attention_fused_lut_cls(h, q, k, vt, b.dy_qk, b.s_softmax, b.exp_aq, b.exp_t, b.exp_cls, b.exp_nc, b.exp_tcount, b.exp_dmin,
+                                                  b.dy_pv, ctx, x16, x_cls, B, H, T, dh, ldv)
+                   : ivit_attention_fused_lut(h, q, k, vt, b.dy_qk, b.s_softmax, b.exp_aq, b.exp_t, b.exp_cls, b.exp_nc, b.exp_tcount, b.exp_dmin,
+                                              b.dy_pv, ctx, B, H, T, dh, ldv);
+    return cls ? ivit_attention_fused_cls(h, q, k, vt, b.dy_qk, b.s_softmax, b.dy_pv, ctx, x16, x_cls, B, H, T, dh, ldv)
+               : ivit_attention_fused(h, q, k, vt, b.dy_qk, b.s_softmax, b.dy_pv, ctx, B, H, T, dh, ldv);
+}
 
 // one slice on handle `h`
 // `Bmax`: images of the LARGEST slice of this forward — every slice uses that slice's buffer layout, so the regions
@@ -114,20 +218,16 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
            *k = (int8_t *)(ws + L.k), *vt = (int8_t *)(ws + L.vt), *ctx8 = (int8_t *)(ws + L.ctx8),
            *h8 = (int8_t *)(ws + L.h8), *g8 = (int8_t *)(ws + L.g8), *cls8 = (int8_t *)(ws + L.cls8);
     int16_t *patch16 = (int16_t *)(ws + L.patch16), *x = (int16_t *)(ws + L.xa), *y = (int16_t *)(ws + L.xb);
-    int rc;
-#define RUN(call) do { rc = (call); if (rc != IVIT_OK) { if (h != m->h) snprintf(m->h->err, sizeof(m->h->err), "%s", h->err); return rc; } } while (0)
     // PatchEmbed + class token + position embedding: one GEMM launch that gathers its A rows from the images and finishes the rows in its
     // epilogue (round 6), or im2col -> GEMM -> embed_finish where that form does not apply
-    rc = (m->Kp == c.in_chans * c.patch_size * c.patch_size)
-             ? ivit_patch_embed(h, images, B, c.in_chans, c.img_size, c.img_size, c.patch_size, P.pe_w, P.pe_b, P.pe_dy, P.z_cls, P.pos, P.dy_x, P.dy_pos, x, D)
-             : IVIT_ERR_UNSUPPORTED;
-    if (rc == IVIT_ERR_UNSUPPORTED) {
-        RUN(ivit_im2col_patch(h, images, B, c.in_chans, c.img_size, c.img_size, c.patch_size, patches));
-        RUN(ivit_linear_i8_requant(h, patches, P.pe_w, P.pe_b, P.pe_dy, 16, patch16, B * m->num_patches, D, m->Kp));
-        RUN(ivit_embed_finish(h, patch16, P.z_cls, P.pos, P.dy_x, P.dy_pos, x, B, T, D));
-    } else {
-        RUN(rc);
-    }
+    RUN(fused_or((m->Kp == c.in_chans * c.patch_size * c.patch_size)
+                     ? ivit_patch_embed(h, images, B, c.in_chans, c.img_size, c.img_size, c.patch_size, P.pe_w, P.pe_b, P.pe_dy, P.z_cls, P.pos, P.dy_x, P.dy_pos, x, D)
+                     : IVIT_ERR_UNSUPPORTED,
+                 [&] {
+                     RUN(ivit_im2col_patch(h, images, B, c.in_chans, c.img_size, c.img_size, c.patch_size, patches));
+                     RUN(ivit_linear_i8_requant(h, patches, P.pe_w, P.pe_b, P.pe_dy, 16, patch16, B * m->num_patches, D, m->Kp));
+                     return ivit_embed_finish(h, patch16, P.z_cls, P.pos, P.dy_x, P.dy_pos, x, B, T, D);
+                 }));
     for (int i = 0; i < c.depth; ++i) {
         const ivit_vit_block &b = m->blocks[i];
         // a layer on the row-table attention takes v ROW-major (ldv = 0: the qkv GEMM stores 16 bytes per lane instead of 16 byte
@@ -139,36 +239,19 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         const int Mb = tail ? B : M;      // rows behind the attention
         // norm1's 8-bit output has one consumer: where the qkv GEMM keeps a CU's tokens in LDS it is computed there (round 6; D = 192 too,
         // with v in either layout)
-        rc = qkv_plan_fuses(m, i, B) ? ivit_layernorm_linear_i8_qkv_ldv_planned(h, m->plans[4 * i], x, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy,
-                                                                                q, k, vt, B, T, H, dh, ldv)
-                                     : IVIT_ERR_UNSUPPORTED;
-        if (rc == IVIT_ERR_UNSUPPORTED) {
-            RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, a8));
-            RUN(ivit_linear_i8_qkv_planned(h, m->plans[4 * i], a8, q, k, vt, B, T, H, dh, ldv));
-        } else {
-            RUN(rc);
-        }
+        RUN(fused_or(qkv_plan_fuses(m, i, B) ? ivit_layernorm_linear_i8_qkv_ldv_planned(h, m->plans[4 * i], x, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy,
+                                                                                        q, k, vt, B, T, H, dh, ldv)
+                                             : IVIT_ERR_UNSUPPORTED,
+                     [&] {
+                         RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, a8));
+                         return ivit_linear_i8_qkv_planned(h, m->plans[4 * i], a8, q, k, vt, B, T, H, dh, ldv);
+                     }));
         if (tail) {
-            int8_t *ctxc = patches;
-            if (m->has_rowtab[i])
-                RUN(ivit_attention_fused_rowlut_cls(h, q, k, vt, b.dy_qk, b.s_softmax, m->rowtab + (size_t)i * 256 * 64, b.exp_dmin, b.dy_pv,
-                                                    ctxc, x, patch16, B, H, T, dh, ldv));
-            else if (b.exp_aq)
-                RUN(ivit_attention_fused_lut_cls(h, q, k, vt, b.dy_qk, b.s_softmax, b.exp_aq, b.exp_t, b.exp_cls, b.exp_nc,
-                                                 b.exp_tcount, b.exp_dmin, b.dy_pv, ctxc, x, patch16, B, H, T, dh, ld));
-            else
-                RUN(ivit_attention_fused_cls(h, q, k, vt, b.dy_qk, b.s_softmax, b.dy_pv, ctxc, x, patch16, B, H, T, dh, ld));
-            ctx8 = ctxc;
+            ctx8 = patches;
+            RUN(vit_attention(m, h, i, q, k, vt, ctx8, B, ldv, true, x, patch16));
             x = patch16;                // [B, D]; proj writes y, the Mlp writes patch16 again
         } else if (m->fused_attention) {
-            if (m->has_rowtab[i])      // one gather per score (round 6)
-                RUN(ivit_attention_fused_rowlut(h, q, k, vt, b.dy_qk, b.s_softmax, m->rowtab + (size_t)i * 256 * 64, b.exp_dmin, b.dy_pv,
-                                                ctx8, B, H, T, dh, ldv));
-            else if (b.exp_aq)
-                RUN(ivit_attention_fused_lut(h, q, k, vt, b.dy_qk, b.s_softmax, b.exp_aq, b.exp_t, b.exp_cls, b.exp_nc,
-                                             b.exp_tcount, b.exp_dmin, b.dy_pv, ctx8, B, H, T, dh, ld));
-            else
-                RUN(ivit_attention_fused(h, q, k, vt, b.dy_qk, b.s_softmax, b.dy_pv, ctx8, B, H, T, dh, ld));
+            RUN(vit_attention(m, h, i, q, k, vt, ctx8, B, ldv, false, nullptr, nullptr));
         } else {
             int8_t *s8 = (int8_t *)(ws + L.s8);
             uint16_t *p16 = (uint16_t *)(ws + L.p16);
@@ -182,28 +265,24 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         const bool mlp_fast = mlp_plan_fuses(m->mlp_plans[i], b.res2_main, b.res2_res, Mb);
         RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, Mb));
         { int16_t *t = x; x = y; y = t; }
-        rc = mlp_fast ? ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8,
-                                                         m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, y, Mb)
-                      : IVIT_ERR_UNSUPPORTED;
-        if (rc == IVIT_ERR_UNSUPPORTED) {
-            RUN(ivit_layernorm_requant(h, x, Mb, D, D, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8));
-            if (mlp_fast) {     // hidden tensor stays in LDS
-                RUN(ivit_mlp_fused_planned(h, m->mlp_plans[i], a8, m->gelu_tab + (size_t)i * 65536, b.res2_main, b.res2_res, x, y, Mb));
-            } else {
-                RUN(ivit_linear_i8_requant_planned(h, m->plans[4 * i + 2], a8, 8, h8, Mb));
-                RUN(ivit_shiftgelu_requant_lut(h, h8, Mb, Hd, m->gelu_tab + (size_t)i * 65536, g8));
-                RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, Mb));
-            }
-        } else {
-            RUN(rc);
-        }
+        const int8_t *tab = gelu_table(m, i);
+        RUN(fused_or(mlp_fast ? ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8, tab, b.res2_main,
+                                                                 b.res2_res, y, Mb)
+                              : IVIT_ERR_UNSUPPORTED,
+                     [&] {
+                         RUN(ivit_layernorm_requant(h, x, Mb, D, D, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8));
+                         if (mlp_fast)       // hidden tensor stays in LDS
+                             return ivit_mlp_fused_planned(h, m->mlp_plans[i], a8, tab, b.res2_main, b.res2_res, x, y, Mb);
+                         RUN(ivit_linear_i8_requant_planned(h, m->plans[4 * i + 2], a8, 8, h8, Mb));
+                         RUN(ivit_shiftgelu_requant_lut(h, h8, Mb, Hd, tab, g8));
+                         return ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, Mb);
+                     }));
         { int16_t *t = x; x = y; y = t; }
     }
     // final norm on the class-token rows only (row stride T*D; D where the last block left them compact), then the head's int32
     // accumulators
     RUN(ivit_layernorm_requant(h, x, B, D, cls_tail(m) ? (int64_t)D : (int64_t)T * D, P.s_ln, P.n_bias_int, P.n_sc, P.n_dy, cls8));
     RUN(ivit_linear_i8(h, cls8, P.head_w, P.head_b, logits, B, c.num_classes, D));
-#undef RUN
     return IVIT_OK;
 }
 
@@ -237,7 +316,6 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
     m->rowtab = nullptr;
     m->has_rowtab.assign(cfg->depth, 0);
     m->max_slices = max_slices;
-    m->fork = nullptr;
     hipError_t e = hipMalloc((void **)&m->gelu_tab, (size_t)cfg->depth * 65536);
     if (e == hipSuccess && m->fused_attention) e = hipMalloc((void **)&m->rowtab, (size_t)cfg->depth * 256 * 64 * sizeof(float));
     if (e != hipSuccess) {
@@ -246,11 +324,11 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
         return IVIT_ERR_HIP;
     }
     for (int i = 0; i < cfg->depth; ++i) {
-        int rc = ivit_shiftgelu_build_table(h, m->blocks[i].s_gelu, m->blocks[i].dy_gelu, m->gelu_tab + (size_t)i * 65536);
+        int rc = ivit_shiftgelu_build_table(h, m->blocks[i].s_gelu, m->blocks[i].dy_gelu, gelu_table(m, i));
         if (rc != IVIT_OK) { ivit_vit_destroy(m); return rc; }
         // frozen QuantLinear plans: per-channel multipliers and the exactness bounds of the pipelined GEMMs
         const ivit_vit_block &b = m->blocks[i];
-        if (m->rowtab && b.exp_aq && 1 - b.exp_dmin <= 64 && fabs(b.dy_qk.m * b.dy_qk.r) < 512.0 && fabs(b.dy_pv.m * b.dy_pv.r) < 512.0) {
+        if (m->rowtab && b.exp_aq && 1 - b.exp_dmin <= 64 && attn_fast(b.dy_qk, b.dy_pv)) {
             rc = ivit_shiftmax_rowtable(h, b.exp_aq, b.exp_t, b.exp_cls, b.exp_nc, b.exp_tcount, b.exp_dmin, m->rowtab + (size_t)i * 256 * 64);
             if (rc != IVIT_OK) { ivit_vit_destroy(m); return rc; }
             m->has_rowtab[i] = 1;
@@ -272,25 +350,10 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
         if (mlp_plan_shape(D, Hd) && ivit_mlp_plan_create(h, m->plans[4 * i + 2], m->plans[4 * i + 3], &mp) != IVIT_OK) mp = nullptr;
         m->mlp_plans.push_back(mp);
     }
-    if (max_slices > 1) {
-        bool ok = hipEventCreateWithFlags(&m->fork, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; ok && i < max_slices; ++i) {
-            // each resource is owned by `m` as soon as it exists, so the destroy on the error path releases it
-            hipStream_t st = nullptr;
-            hipEvent_t ev = nullptr;
-            ivit_handle sh = nullptr;
-            ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
-            if (ok) m->streams.push_back(st);
-            ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-            if (ok) m->done.push_back(ev);
-            ok = ok && ivit_create(&sh, h->device, st) == IVIT_OK;
-            if (ok) m->slice_h.push_back(sh);
-        }
-        if (!ok) {
-            snprintf(h->err, sizeof(h->err), "ivit_vit_create: stream/event creation failed");
-            ivit_vit_destroy(m);
-            return IVIT_ERR_HIP;
-        }
+    if (!m->run.create(h, max_slices)) {
+        snprintf(h->err, sizeof(h->err), "ivit_vit_create: stream/event creation failed");
+        ivit_vit_destroy(m);
+        return IVIT_ERR_HIP;
     }
     *out = m;
     return IVIT_OK;
@@ -298,10 +361,7 @@ int ivit_vit_create(ivit_handle h, const ivit_vit_config *cfg, const ivit_vit_pa
 
 int ivit_vit_destroy(ivit_vit m) {
     if (!m) return IVIT_ERR_INVALID;
-    for (auto sh : m->slice_h) ivit_destroy(sh);
-    for (auto ev : m->done) (void)hipEventDestroy(ev);
-    for (auto st : m->streams) (void)hipStreamDestroy(st);
-    if (m->fork) (void)hipEventDestroy(m->fork);
+    m->run.destroy();
     if (m->gelu_tab) (void)hipFree(m->gelu_tab);
     if (m->rowtab) (void)hipFree(m->rowtab);
     for (auto mp : m->mlp_plans) if (mp) (void)ivit_mlp_plan_destroy(mp);
@@ -374,44 +434,16 @@ int ivit_vit_forward(ivit_vit m, const int8_t *images, int batch, int nslices, v
     REQUIRE(h, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     const size_t stride = slice_layout(m, max_slice(batch, nslices)).total;
-    if (nslices == 1) return run_slice(m, h, images, batch, batch, (char *)workspace, logits);
-    if (hipEventRecord(m->fork, h->stream) != hipSuccess) return IVIT_ERR_HIP;
-    for (int i = 0; i < nslices; ++i) {
-        const int b0 = slice_begin(batch, nslices, i), b1 = slice_begin(batch, nslices, i + 1);
-        if (hipStreamWaitEvent(m->streams[i], m->fork, 0) != hipSuccess) return IVIT_ERR_HIP;
-        m->slice_h[i]->cu_share = std::max(1, persistent_cus(h) / nslices);      // a share of the caller's own share
-        rc = run_slice(m, m->slice_h[i], images + (size_t)b0 * img_bytes, b1 - b0, max_slice(batch, nslices),
-                       (char *)workspace + stride * (size_t)i,
-                       logits + (size_t)b0 * m->cfg.num_classes);
-        if (rc != IVIT_OK) return rc;
-        if (hipEventRecord(m->done[i], m->streams[i]) != hipSuccess) return IVIT_ERR_HIP;
-    }
-    for (int i = 0; i < nslices; ++i)
-        if (hipStreamWaitEvent(h->stream, m->done[i], 0) != hipSuccess) return IVIT_ERR_HIP;
-    return IVIT_OK;
+    return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
+        return run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, max_slice(batch, nslices), (char *)workspace + stride * (size_t)i,
+                         logits + (size_t)b0 * m->cfg.num_classes);
+    });
 }
 
 int ivit_vit_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
                           int32_t *logits, ivit_graph *out) {
     if (!m) return IVIT_ERR_INVALID;
-    ivit_handle h = m->h;
-    REQUIRE(h, out, "null argument");
-    REQUIRE(h, h->stream != nullptr, "graph capture needs a non-default stream on the handle");
-    hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed);
-    if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "begin capture: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    int rc = ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits);
-    hipGraph_t graph = nullptr;
-    e = hipStreamEndCapture(h->stream, &graph);
-    if (rc != IVIT_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess || !graph) { snprintf(h->err, sizeof(h->err), "end capture: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) { (void)hipGraphDestroy(graph); snprintf(h->err, sizeof(h->err), "instantiate: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    ivit_graph_s *g = new (std::nothrow) ivit_graph_s();
-    if (!g) { (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph); return IVIT_ERR_HIP; }
-    g->h = h; g->graph = graph; g->exec = exec;
-    *out = g;
-    return IVIT_OK;
+    return graph_capture(m->h, out, [&] { return ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits); });
 }
 
 int ivit_graph_launch(ivit_graph g) {
@@ -447,10 +479,7 @@ struct ivit_swin_s {
     std::vector<ivit_linear_plan> lin_plans; // per block: qkv, proj plans prepared for gemm_ws_qkv_kernel where C == 384, else null
     int8_t *gelu_tab;                 // [nblocks][65536]
     int max_slices;
-    std::vector<ivit_handle> slice_h;
-    std::vector<hipStream_t> streams;
-    std::vector<hipEvent_t> done;
-    hipEvent_t fork;
+    SliceRunner run;
 };
 
 namespace {
@@ -488,7 +517,7 @@ int swin_ln(const ivit_swin_s *m, ivit_handle h, const int16_t *x, long long M, 
 int swin_mlp_mode(const ivit_swin_s *m, int bi, int C, long long M) {
     if (C == 96 && m->cfg.mlp_ratio == 4 && m->fused_mlp) return 1;
     // C = 128 (Swin-B stage 0): the same entry, which at this width takes residual multipliers in the fast range only
-    if (C == Mlp128Geo::C && m->cfg.mlp_ratio == 4 && m->fused_mlp && mlp_res_fast(m->blocks[bi].res2_main, m->blocks[bi].res2_res)) return 1;
+    if (C == Mlp128Geo::C && m->cfg.mlp_ratio == 4 && m->fused_mlp && rq_fast2(m->blocks[bi].res2_main, m->blocks[bi].res2_res)) return 1;
     return mlp_plan_fuses(m->mlp_plans[bi], m->blocks[bi].res2_main, m->blocks[bi].res2_res, M) ? 2 : 0;
 }
 
@@ -505,8 +534,6 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
     int res = m->grid, L = res * res;
     long long M = (long long)B * L;
     const int Kp = c.in_chans * c.patch_size * c.patch_size;
-    int rc;
-#define RUN(call) do { rc = (call); if (rc != IVIT_OK) { if (h != m->h) snprintf(m->h->err, sizeof(m->h->err), "%s", h->err); return rc; } } while (0)
     // PatchEmbed: conv -> qact_before_norm(8) -> norm (token-order sums) -> qact(16) -> qact1(16)
     RUN(ivit_im2col_patch(h, images, B, c.in_chans, c.img_size, c.img_size, c.patch_size, patches));
     RUN(ivit_linear_i8_requant(h, patches, P.pe.w, P.pe.b, P.pe.dy, 8, a8, (int)M, E, Kp));
@@ -520,15 +547,13 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             const int wsz = res <= c.window_size ? res : c.window_size;     // SwinTransformerBlock.__init__
             const ivit_linear_plan *lp = &m->lin_plans[2 * bi];
             // norm1 inside the qkv launch where that layer runs on gemm_ws_qkv_kernel (C = 384, activations in natural token order)
-            rc = (lp[0] && li != 0) ? ivit_layernorm_linear_i8_requant_planned(h, lp[0], x, b.s_in, b.n1.bias_int, b.n1.sc, b.n1.dy, qkv, (int)M)
-                                    : IVIT_ERR_UNSUPPORTED;
-            if (rc == IVIT_ERR_UNSUPPORTED) {
-                RUN(swin_ln(m, h, x, M, C, b.s_in, b.n1, L, li == 0, a8));
-                if (lp[0]) RUN(ivit_linear_i8_requant_planned(h, lp[0], a8, 8, qkv, (int)M));
-                else RUN(ivit_linear_i8_requant(h, a8, b.qkv.w, b.qkv.b, b.qkv.dy, 8, qkv, (int)M, 3 * C, C));
-            } else {
-                RUN(rc);
-            }
+            RUN(fused_or((lp[0] && li != 0) ? ivit_layernorm_linear_i8_requant_planned(h, lp[0], x, b.s_in, b.n1.bias_int, b.n1.sc, b.n1.dy, qkv, (int)M)
+                                            : IVIT_ERR_UNSUPPORTED,
+                         [&] {
+                             RUN(swin_ln(m, h, x, M, C, b.s_in, b.n1, L, li == 0, a8));
+                             return lp[0] ? ivit_linear_i8_requant_planned(h, lp[0], a8, 8, qkv, (int)M)
+                                          : ivit_linear_i8_requant(h, a8, b.qkv.w, b.qkv.b, b.qkv.dy, 8, qkv, (int)M, 3 * C, C);
+                         }));
             if (b.exp_aq)
                 RUN(ivit_window_attention_fused_lut(h, qkv, b.dy_qk, b.dy_a, b.relb, b.s_softmax, b.exp_aq, b.exp_t, b.exp_cls,
                                                     b.exp_nc, b.exp_tcount, b.exp_dmin, b.dy_pv, ctx, B, res, wsz,
@@ -544,13 +569,13 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             // two slices, 4.76 against 4.70 ms same-box; the LayerNorm launch of one slice overlaps the other slice's kernels)
             RUN(swin_ln(m, h, x, M, C, b.s_mid, b.n2, L, li == 0, a8));
             if (mlp_mode == 1) {                                    // narrow stage: hidden tensor stays in LDS
-                RUN(ivit_mlp_fused(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, m->gelu_tab + (size_t)bi * 65536, b.fc2.w, b.fc2.b,
+                RUN(ivit_mlp_fused(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, gelu_table(m, bi), b.fc2.w, b.fc2.b,
                                    b.fc2.dy, b.res2_main, b.res2_res, x, y, M, C, 4 * C));
             } else if (mlp_mode == 2) {                             // C = 192, C = 256 and C = 384 stages: weights streamed, hidden tile in LDS
-                RUN(ivit_mlp_fused_planned(h, m->mlp_plans[bi], a8, m->gelu_tab + (size_t)bi * 65536, b.res2_main, b.res2_res, x, y, M));
+                RUN(ivit_mlp_fused_planned(h, m->mlp_plans[bi], a8, gelu_table(m, bi), b.res2_main, b.res2_res, x, y, M));
             } else {
                 RUN(ivit_linear_i8_requant(h, a8, b.fc1.w, b.fc1.b, b.fc1.dy, 8, h8, (int)M, c.mlp_ratio * C, C));
-                RUN(ivit_shiftgelu_requant_lut(h, h8, M, c.mlp_ratio * C, m->gelu_tab + (size_t)bi * 65536, g8));
+                RUN(ivit_shiftgelu_requant_lut(h, h8, M, c.mlp_ratio * C, gelu_table(m, bi), g8));
                 RUN(ivit_linear_i8_requant_residual(h, g8, b.fc2.w, b.fc2.b, b.fc2.dy, b.res2_main, b.res2_res, x, y, (int)M, C, c.mlp_ratio * C));
             }
             { int16_t *t = x; x = y; y = t; }
@@ -558,22 +583,19 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
         if (li < c.num_layers - 1) {     // PatchMerging: gather -> LN(4C) -> qact1(8) -> reduction -> qact2(8)
             const ivit_swin_merge &g = m->merges[li];
             // the 2 x 2 gather rides in the LayerNorm's loads (round 6: as a pass of its own it was 32 us per merge at Swin-T b256)
-            rc = ivit_patch_merge_layernorm_requant(h, x, B, res, C, g.s_in, g.n.bias_int, g.n.sc, g.n.dy, a8);
-            const bool merged = rc == IVIT_OK;
-            if (!merged && rc != IVIT_ERR_UNSUPPORTED) RUN(rc);
-            if (!merged) RUN(ivit_patch_merge_gather(h, x, 16, B, res, C, t16));
+            const int res_in = res;
             res /= 2;
             L = res * res;
             M = (long long)B * L;
-            if (!merged) RUN(swin_ln(m, h, t16, M, 4 * C, g.s_in, g.n, L, false, a8));
+            RUN(fused_or(ivit_patch_merge_layernorm_requant(h, x, B, res_in, C, g.s_in, g.n.bias_int, g.n.sc, g.n.dy, a8), [&] {
+                RUN(ivit_patch_merge_gather(h, x, 16, B, res_in, C, t16));
+                return swin_ln(m, h, t16, M, 4 * C, g.s_in, g.n, L, false, a8);
+            }));
             // reduction -> qact2(8), stored as the 16-bit stream the next stage reads (round 6: the widening pass was 16 us per merge)
-            rc = ivit_linear_i8_requant8_store16(h, a8, g.red.w, nullptr, g.red.dy, x, (int)M, 2 * C, 4 * C);
-            if (rc == IVIT_ERR_UNSUPPORTED) {
+            RUN(fused_or(ivit_linear_i8_requant8_store16(h, a8, g.red.w, nullptr, g.red.dy, x, (int)M, 2 * C, 4 * C), [&] {
                 RUN(ivit_linear_i8_requant(h, a8, g.red.w, nullptr, g.red.dy, 8, ctx, (int)M, 2 * C, 4 * C));
-                RUN(ivit_widen_i8_i16(h, ctx, x, M * 2 * C));
-            } else {
-                RUN(rc);
-            }
+                return ivit_widen_i8_i16(h, ctx, x, M * 2 * C);
+            }));
         }
     }
     const int C = E << (c.num_layers - 1);
@@ -581,7 +603,6 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
     RUN((L & 1) ? ivit_avgpool_requant(h, a8, B, L, C, P.dy_pool, pool)
                 : ivit_avgpool_requant_scaled(h, a8, B, L, C, P.s_pool, P.dy_pool, pool));
     RUN(ivit_linear_i8(h, pool, P.head_w, P.head_b, logits, B, c.num_classes, C));
-#undef RUN
     return IVIT_OK;
 }
 
@@ -591,10 +612,7 @@ extern "C" {
 
 int ivit_swin_destroy(ivit_swin m) {
     if (!m) return IVIT_ERR_INVALID;
-    for (auto sh : m->slice_h) ivit_destroy(sh);
-    for (auto ev : m->done) (void)hipEventDestroy(ev);
-    for (auto st : m->streams) (void)hipStreamDestroy(st);
-    if (m->fork) (void)hipEventDestroy(m->fork);
+    m->run.destroy();
     if (m->gelu_tab) (void)hipFree(m->gelu_tab);
     for (auto mp : m->mlp_plans) if (mp) (void)ivit_mlp_plan_destroy(mp);
     for (auto pl : m->mlp_lin) if (pl) (void)ivit_linear_plan_destroy(pl);
@@ -642,7 +660,7 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
     m->h = h; m->cfg = *cfg; m->prm = *params;
     m->blocks.assign(params->blocks_host, params->blocks_host + nb);
     if (cfg->num_layers > 1) m->merges.assign(params->merges_host, params->merges_host + cfg->num_layers - 1);
-    m->grid = grid; m->nblocks = nb; m->gelu_tab = nullptr; m->max_slices = max_slices; m->fork = nullptr;
+    m->grid = grid; m->nblocks = nb; m->gelu_tab = nullptr; m->max_slices = max_slices;
     m->fused_mlp = true;
     if (hipMemcpy(&m->dy_qact1_host, params->dy_qact1, sizeof(ivit_dyadic), hipMemcpyDeviceToHost) != hipSuccess) {
         snprintf(h->err, sizeof(h->err), "ivit_swin_create: cannot read dy_qact1");
@@ -655,7 +673,7 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
         return IVIT_ERR_HIP;
     }
     for (int i = 0; i < nb; ++i) {
-        int rc = ivit_shiftgelu_build_table(h, m->blocks[i].s_gelu, m->blocks[i].dy_gelu, m->gelu_tab + (size_t)i * 65536);
+        int rc = ivit_shiftgelu_build_table(h, m->blocks[i].s_gelu, m->blocks[i].dy_gelu, gelu_table(m, i));
         if (rc != IVIT_OK) { ivit_swin_destroy(m); return rc; }
     }
     {   // fused Mlp plans for the C = 192 (hidden 768), C = 256 (hidden 1024) and C = 384 (hidden 1536) stages
@@ -688,25 +706,10 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
                 m->lin_plans.push_back(q[1]);
             }
     }
-    if (max_slices > 1) {
-        bool ok = hipEventCreateWithFlags(&m->fork, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; ok && i < max_slices; ++i) {
-            // each resource is owned by `m` as soon as it exists, so the destroy on the error path releases it
-            hipStream_t st = nullptr;
-            hipEvent_t ev = nullptr;
-            ivit_handle sh = nullptr;
-            ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
-            if (ok) m->streams.push_back(st);
-            ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-            if (ok) m->done.push_back(ev);
-            ok = ok && ivit_create(&sh, h->device, st) == IVIT_OK;
-            if (ok) m->slice_h.push_back(sh);
-        }
-        if (!ok) {
-            snprintf(h->err, sizeof(h->err), "ivit_swin_create: stream/event creation failed");
-            ivit_swin_destroy(m);
-            return IVIT_ERR_HIP;
-        }
+    if (!m->run.create(h, max_slices)) {
+        snprintf(h->err, sizeof(h->err), "ivit_swin_create: stream/event creation failed");
+        ivit_swin_destroy(m);
+        return IVIT_ERR_HIP;
     }
     *out = m;
     return IVIT_OK;
@@ -744,43 +747,18 @@ int ivit_swin_forward(ivit_swin m, const int8_t *images, int batch, int nslices,
     REQUIRE(h, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     const size_t stride = swin_layout(m, max_slice(batch, nslices)).total;
-    if (nslices == 1) return swin_run_slice(m, h, images, batch, (char *)workspace, logits);
-    if (hipEventRecord(m->fork, h->stream) != hipSuccess) return IVIT_ERR_HIP;
-    for (int i = 0; i < nslices; ++i) {
-        const int b0 = slice_begin(batch, nslices, i), b1 = slice_begin(batch, nslices, i + 1);
-        if (hipStreamWaitEvent(m->streams[i], m->fork, 0) != hipSuccess) return IVIT_ERR_HIP;
-        m->slice_h[i]->cu_share = std::max(1, persistent_cus(h) / nslices);      // a share of the caller's own share
-        rc = swin_run_slice(m, m->slice_h[i], images + (size_t)b0 * img_bytes, b1 - b0, (char *)workspace + stride * (size_t)i,
-                            logits + (size_t)b0 * m->cfg.num_classes);
-        if (rc != IVIT_OK) return rc;
-        if (hipEventRecord(m->done[i], m->streams[i]) != hipSuccess) return IVIT_ERR_HIP;
-    }
-    for (int i = 0; i < nslices; ++i)
-        if (hipStreamWaitEvent(h->stream, m->done[i], 0) != hipSuccess) return IVIT_ERR_HIP;
-    return IVIT_OK;
+    return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
+        return swin_run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, (char *)workspace + stride * (size_t)i,
+                              logits + (size_t)b0 * m->cfg.num_classes);
+    });
 }
 
 int ivit_swin_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
                            int32_t *logits, ivit_graph *out) {
     if (!m) return IVIT_ERR_INVALID;
-    ivit_handle h = m->h;
-    REQUIRE(h, out, "null argument");
-    REQUIRE(h, h->stream != nullptr, "graph capture needs a non-default stream on the handle");
-    hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed);
-    if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "begin capture: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    int rc = ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits);
-    hipGraph_t graph = nullptr;
-    e = hipStreamEndCapture(h->stream, &graph);
-    if (rc != IVIT_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess || !graph) { snprintf(h->err, sizeof(h->err), "end capture: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) { (void)hipGraphDestroy(graph); snprintf(h->err, sizeof(h->err), "instantiate: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    ivit_graph_s *g = new (std::nothrow) ivit_graph_s();
-    if (!g) { (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph); return IVIT_ERR_HIP; }
-    g->h = h; g->graph = graph; g->exec = exec;
-    *out = g;
-    return IVIT_OK;
+    return graph_capture(m->h, out, [&] { return ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits); });
 }
 
 }  // extern "C"
+
+#undef RUN

@@ -202,6 +202,44 @@ def test_layernorm_requant_vs_oracle_ragged(H, C):
         assert len(np.unique(want)) > 50
 
 
+_LN_LDS_CASES = {}
+
+
+def _ln_lds_case(C):
+    """Eight rows of C channels (row 3 constant: zero variance), the LayerNorm constants and the oracle's fp32 result; computed once
+    per C and left unchanged."""
+    if C not in _LN_LDS_CASES:
+        from oracle import oracle as orc
+        rng = np.random.default_rng(C)
+        w = rng.normal(1.0, 0.4, C).astype(np.float32) * rng.choice([-1.0, 1.0], C).astype(np.float32)
+        bias_int, sc = iv.freeze.layernorm_constants(w, rng.normal(0.0, 0.5, C).astype(np.float32))
+        x = rng.integers(-26000, 26000, (8, C)).astype(np.int16)
+        x[:, : C // 2] //= 64                                         # small and large magnitudes in one row
+        x[3] = 1234
+        _LN_LDS_CASES[C] = (x, bias_int, sc, orc.layernorm(x, 7.3e-4, bias_int, sc))
+    return _LN_LDS_CASES[C]
+
+
+@pytest.mark.parametrize("device", [0, 1])
+def test_layernorm_dynamic_lds_attribute_cache(device):
+    """The dynamic-LDS attribute of a kernel is set once per device and kernel for the largest size seen (launch_dyn, ivit_hip.hip).
+    ivit_layernorm on 8 rows launches layernorm_kernel<false> with 8 * C * 4 bytes of LDS: C = 2056 (65 792 B, the first size above
+    64 KB: the attribute is set), 4096 (131 072 B: the request grows, set again), 2056 again (below the cached maximum: no host call,
+    and the launch must still be accepted), 512 (below 64 KB: the cache is not consulted).  Each result equals the oracle's bit for
+    bit.  Device 1 (after device 0, in the same process) repeats the first two steps: its cache entry is its own."""
+    if device >= torch.cuda.device_count():
+        pytest.skip("one visible GPU: the second-device half of the per-device attribute cache is not exercised")
+    with torch.cuda.device(device):
+        Hd = _lib.Handle(device, torch.cuda.current_stream().cuda_stream)
+        for C in (2056, 4096, 2056, 512) if device == 0 else (2056, 4096):
+            x, bias_int, sc, want = _ln_lds_case(C)
+            z = torch.zeros(8, C, dtype=torch.float32, device="cuda")
+            Hd.call("ivit_layernorm", P(dev(x)), 8, C, 7.3e-4, P(dev(bias_int)), P(dev(sc)), P(z))
+            got = z.cpu().numpy()
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (device, C, int((got != want).sum()))
+        Hd.close()
+
+
 @pytest.mark.parametrize("C,R,B", [(96, 56, 3), (192, 28, 5), (384, 14, 9), (128, 8, 2)])
 def test_patch_merge_layernorm_equals_gather_then_layernorm(H, C, R, B):
     """PatchMerging's 2 x 2 gather folded into the loads of the I-LayerNorm + QuantAct(8) that follows it (swin_quant.py:336-349,
