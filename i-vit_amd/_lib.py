@@ -171,6 +171,7 @@ SIGNATURES = {
     "ivit_mlp_plan_create": [_P, _P, _P, ctypes.POINTER(_P)],
     "ivit_mlp_fused_planned": [_P, _P, _P, _P, Dyadic, Dyadic, _P, _P, _L],
     "ivit_layernorm_mlp_fused_planned": [_P, _P, _P, _F, _P, _P, _P, _P, _P, Dyadic, Dyadic, _P, _L],
+    "ivit_layernorm_mlp_lockstep_planned": [_P, _P, _P, _F, _P, _P, _P, _P, Dyadic, Dyadic, _P, _L],
     "ivit_mlp_fused": [_P, _P, _P, _P, _P, _P, _P, _P, _P, Dyadic, Dyadic, _P, _P, _L, _I, _I],
     "ivit_patch_merge_gather": [_P, _P, _I, _I, _I, _I, _P],
     "ivit_widen_i8_i16": [_P, _P, _P, _L],
@@ -185,6 +186,7 @@ SIGNATURES = {
     "ivit_vit_destroy": [_P],
     "ivit_vit_workspace_bytes": [_P, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
     "ivit_vit_fused_mlp_blocks": [_P, _I, ctypes.POINTER(_I)],
+    "ivit_vit_fused_ln_mlp_blocks": [_P, _I, ctypes.POINTER(_I)],
     "ivit_vit_fused_qkv_blocks": [_P, _I, ctypes.POINTER(_I)],
     "ivit_vit_cls_tail": [_P, _I, ctypes.POINTER(_I)],
     "ivit_swin_fused_mlp_blocks": [_P, _I, ctypes.POINTER(_I * 4)],

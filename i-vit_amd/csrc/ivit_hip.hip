@@ -879,9 +879,36 @@ int ivit_mlp_plan_destroy(ivit_mlp_plan p) {
     return IVIT_OK;
 }
 
+// width 384: does ivit_mlp_fused_planned run (plan, M tokens) on the role-split kernel?  Two kernels, the same integers.  The
+// role-split one (producer waves on fc1 of unit u + 1 beside consumer waves on ShiftGELU / fc2 / epilogue of unit u) needs a second
+// unit per workgroup to overlap anything: with one unit per CU it only ties with the lock-step kernel (45.0 vs 44.6 us at
+// M = 20480), from two units on it wins (profiles/README.md, round 5)
+static bool mlp_role_split(const ivit_ctx *h, ivit_mlp_plan p, long long M) {
+    if (p->width != Mlp384Geo::C) return false;
+    const long long ntiles = (M + 15) / 16, nunits = (ntiles + MLP_TT - 2) / (MLP_TT - 1);
+    return p->kernel == 2 || (p->kernel == 0 && nunits > (long long)persistent_cus(h));
+}
+// what ivit_layernorm_mlp_lockstep_planned takes: a width the LayerNorm-headed lock-step kernel is built at (not 256: the Swin runner
+// keeps norm2 as its own launch by measurement) and residual multipliers in the fast range
+static bool ln_mlp_lockstep_ok(ivit_mlp_plan p, ivit_dyadic dy_main, ivit_dyadic dy_res) {
+    return p && (p->width == Mlp192Geo::C || p->width == Mlp384Geo::C) && rq_fast2(dy_main, dy_res);
+}
+// THE rule for "this block's norm2 + Mlp is ONE launch at M tokens on handle h", and through which entry: run_slice and
+// ivit_vit_fused_ln_mlp_blocks ask here.  The role-split kernel's LayerNorm head where ivit_mlp_fused_planned would run on that kernel
+// (width 384, two units per CU or more), else the lock-step kernel's (widths 192 and 384, every token count:
+// profiles/README.md, "Norm2 inside the lock-step fused Mlp launch")
+enum { LN_MLP_TWO_LAUNCHES = 0, LN_MLP_ROLE_SPLIT = 1, LN_MLP_LOCKSTEP = 2 };
+static int ln_mlp_plan_fuses(const ivit_ctx *h, ivit_mlp_plan p, ivit_dyadic dy_main, ivit_dyadic dy_res, long long M) {
+    if (!p || !rq_fast2(dy_main, dy_res)) return LN_MLP_TWO_LAUNCHES;
+    if (mlp_role_split(h, p, M)) return LN_MLP_ROLE_SPLIT;
+    return ln_mlp_lockstep_ok(p, dy_main, dy_res) ? LN_MLP_LOCKSTEP : LN_MLP_TWO_LAUNCHES;
+}
+
+// ln_lockstep: norm2 in the lock-step kernel's activation tiles (ivit_layernorm_mlp_lockstep_planned: x is null, `residual` the
+// LayerNorm's input too); the lock-step kernel whatever the plan is pinned to, same grids, same unit schedules
 static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, const int8_t *gelu_table, ivit_dyadic dy_main,
                             ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M, float ln_s, const float *ln_bias_int,
-                            const float *ln_sc, const ivit_dyadic *ln_dy) {
+                            const float *ln_sc, const ivit_dyadic *ln_dy, bool ln_lockstep = false) {
     MlpArgs a;
     a.ln_s = ln_s; a.ln_bias_int = ln_bias_int; a.ln_sc = ln_sc; a.ln_dy = ln_dy;
     a.x = x; a.w1f = p->w1f; a.w2f = p->w2f; a.b1 = p->fc1->bias_eff; a.b2 = p->fc2->bias_eff;
@@ -901,6 +928,7 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
         const unsigned grid = (unsigned)(ntiles < slots ? ntiles : slots);
         a.balanced = 1;
         const int st = with_bool(p->fma, [&](auto FMA) {
+            if (ln_lockstep) return launch_dyn<mlp192ln_kernel<FMA()>>(h, grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM_LN, a);
             return w256 ? launch_dyn<mlp256_kernel<FMA()>>(h, grid, Mlp256Geo::THREADS, Mlp256Geo::SMEM, a)
                         : launch_dyn<mlp192_kernel<FMA()>>(h, grid, Mlp192Geo::THREADS, Mlp192Geo::SMEM, a);
         });
@@ -914,16 +942,15 @@ static int mlp_fused_launch(ivit_handle h, ivit_mlp_plan p, const int8_t *x, con
     const unsigned grid = (unsigned)(nunits < persistent_cus(h) ? nunits : persistent_cus(h));
     const long long rounds_fixed = (nunits + grid - 1) / grid, rounds_bal = (ntiles + (long long)MLP_TT * grid - 1) / ((long long)MLP_TT * grid);
     a.balanced = rounds_bal < rounds_fixed;
-    // two kernels, the same integers.  The role-split one (producer waves on fc1 of unit u + 1 beside consumer waves on
-    // ShiftGELU / fc2 / epilogue of unit u) needs a second unit per workgroup to overlap anything: with one unit per CU it only
-    // ties with the lock-step kernel (45.0 vs 44.6 us at M = 20480), from two units on it wins (profiles/README.md, round 5)
-    const bool role_split = p->kernel == 2 || (p->kernel == 0 && nunits > (long long)grid);
-    if (ln_dy && !role_split) {
+    // two kernels, the same integers (mlp_role_split)
+    const bool role_split = !ln_lockstep && mlp_role_split(h, p, M);
+    if (ln_dy && !role_split && !ln_lockstep) {
         snprintf(h->err, sizeof(h->err), "%s: the LayerNorm prologue exists in the role-split kernel only (two units per CU or more)", __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
     if (role_split) { a.w1f = p->w1r; a.w2f = p->w2r; }
     const int st = with_bool(p->fma, [&](auto FMA) {
+        if (ln_lockstep) return launch_dyn<mlp384ln_kernel<FMA()>>(h, grid, MLP_THREADS, Mlp384Geo::SMEM_LN, a);
         if (!role_split) return launch_dyn<mlp384_kernel<FMA()>>(h, grid, MLP_THREADS, MLP_SMEM, a);
         return ln_dy ? launch_dyn<mlp384rs_kernel<FMA(), 1>>(h, grid, RS_THREADS, RS_SMEM, a)
                      : launch_dyn<mlp384rs_kernel<FMA()>>(h, grid, RS_THREADS, RS_SMEM, a);
@@ -974,6 +1001,21 @@ int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16
         return IVIT_ERR_UNSUPPORTED;
     }
     return mlp_fused_launch(h, p, scratch8, gelu_table, dy_main, dy_res, x16, out, M, scale, bias_int, sc, ln_dy);
+}
+
+int ivit_layernorm_mlp_lockstep_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int, const float *sc,
+                                        const ivit_dyadic *ln_dy, const int8_t *gelu_table, ivit_dyadic dy_main, ivit_dyadic dy_res,
+                                        int16_t *out, int64_t M) {
+    CHECK_H(h);
+    REQUIRE(h, p && x16 && bias_int && sc && ln_dy && gelu_table && out && M > 0, "bad arguments");
+    // every row of x16 is read twice, by different lanes at different times (LayerNorm one unit ahead, the identity branch in fc2's
+    // epilogue), and rows past M - 1 of a tile are row M - 1 again: in place is not a form this launch has
+    REQUIRE(h, out + (size_t)M * p->width <= x16 || x16 + (size_t)M * p->width <= out, "out must not overlap x16 (LayerNorm input and identity branch)");
+    if (!ln_mlp_lockstep_ok(p, dy_main, dy_res)) {
+        snprintf(h->err, sizeof(h->err), "%s: built at widths 192 and 384, for residual multipliers in the fast range", __func__);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return mlp_fused_launch(h, p, nullptr, gelu_table, dy_main, dy_res, x16, out, M, scale, bias_int, sc, ln_dy, true);
 }
 
 }  // extern "C"

@@ -114,7 +114,9 @@ struct LnGroup {
     // waves' by the barrier — in front of the output pass, the first reader
     // OP: int8_t * (the row's bytes go to op + 32 i, global memory), or a callable op(i, pk0, pk1) that places step i's
     // EPC bytes itself (ivit_gemm_ws.h: the consumer's LDS image)
-    template <typename DMA_SYNC = std::false_type, typename OP = int8_t *>
+    // LOCAL_Y: there is no cY table (ivit_mlp.h's LayerNorm head has 16 bytes of LDS per channel, not 20): 1 / sc is formed where it is
+    // consumed, by the same rcp_rn that fills the table elsewhere
+    template <typename DMA_SYNC = std::false_type, typename OP = int8_t *, bool LOCAL_Y = false>
     static __device__ __forceinline__ void run(float (&xv)[NSTEP][EPC], int j, int k, int cb0, bool fastrq, bool live,
                                                const double *cC, const float *cB, const float *cSc, const float *cY,
                                                OP op, DMA_SYNC = DMA_SYNC{}) {
@@ -168,12 +170,17 @@ struct LnGroup {
             double cv[EPC];
 #pragma unroll
             for (int e4 = 0; e4 < EPC; e4 += (EPC >= 4 ? 4 : 2)) {
-                if constexpr (EPC >= 4) {
+                if constexpr (EPC >= 4 && LOCAL_Y) {
+                    const v4f b4 = *reinterpret_cast<const v4f *>(cB + cb + e4), s4 = *reinterpret_cast<const v4f *>(cSc + cb + e4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { bi[e4 + e] = b4[e]; scv[e4 + e] = s4[e]; yv[e4 + e] = rcp_rn(s4[e]); }
+                } else if constexpr (EPC >= 4) {
                     const v4f b4 = *reinterpret_cast<const v4f *>(cB + cb + e4), s4 = *reinterpret_cast<const v4f *>(cSc + cb + e4),
                               y4 = *reinterpret_cast<const v4f *>(cY + cb + e4);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { bi[e4 + e] = b4[e]; scv[e4 + e] = s4[e]; yv[e4 + e] = y4[e]; }
                 } else {
+                    static_assert(!LOCAL_Y || EPC >= 4, "the table-less form is written for 8 lanes per row");
                     bi[0] = cB[cb]; bi[1] = cB[cb + 1]; scv[0] = cSc[cb]; scv[1] = cSc[cb + 1]; yv[0] = cY[cb]; yv[1] = cY[cb + 1];
                 }
             }
@@ -222,7 +229,10 @@ struct LnGroup {
 // roundings as the reference (quant_utils.py:229-231) in two fp64 operations instead of four, biased to 0..255 so the four
 // bytes of a dword pack without masks.  That needs |z * c| < 2^31: |y| <= 2^16 and k >= 2^16 / 2^10 after ten halvings at most
 // bound |o| by 2^40 + |bias|; a block with a channel where that bound fails keeps v_rndne_f64 + the saturating v_cvt_i32_f64.
-template <int CC, int THREADS>
+// WITH_Y = false (ivit_mlp.h's LayerNorm head, whose dynamic LDS is exactly what a CU has): no table of reciprocals
+// (LnGroup::run<.., LOCAL_Y = true>) — cY is instead ONE word of the caller's LDS through which the workgroup votes, because
+// __syncthreads_or keeps a static LDS slot of its own and the kernel would no longer fit
+template <int CC, int THREADS, bool WITH_Y = true>
 __device__ __forceinline__ bool ln_stage_constants(const float *__restrict__ bias_int, const float *__restrict__ sc,
                                                    const ivit_dyadic *__restrict__ dy, double *cC, float *cB, float *cSc, float *cY) {
     bool wide = false;
@@ -230,12 +240,20 @@ __device__ __forceinline__ bool ln_stage_constants(const float *__restrict__ bia
         const float scv = sc[c], bv = bias_int[c];
         const double cv = dy[c].m * dy[c].r;
         cSc[c] = scv;
-        cY[c] = rcp_rn(scv);
+        if constexpr (WITH_Y) cY[c] = rcp_rn(scv);
         cB[c] = bv;
         cC[c] = cv;
         wide |= !(fabs(cv) * (1.2e12 + 1.01 * fabs((double)bv)) < 2147483000.0);
     }
-    return !__syncthreads_or(wide);
+    if constexpr (!WITH_Y) {
+        volatile float *vote = cY;
+        if (threadIdx.x == 0) *vote = 0.f;
+        __syncthreads();
+        if (wide) *vote = 1.f;
+        __syncthreads();
+        return *vote == 0.f;
+    } else
+        return !__syncthreads_or(wide);
 }
 
 template <int EPC>

@@ -29,8 +29,8 @@
 // ShiftGELU phase or waits at a barrier.  One pass over both weight matrices is 288 KB (1.18 MB at width 384), i.e. 3.7 KB per
 // token of a full unit against 14.7 KB there.  fc2's 12 output-channel tiles split as 4 waves x 3 tiles, fc1's 48 as 4 waves x 4
 // chunks of 3: the register picture of a wave (3 channel tiles x 5 token tiles of accumulators) is the one mlp384_kernel has at
-// eight waves.  Units are always contiguous tile ranges.  No LayerNorm-headed form: that prologue lives in the role-split
-// kernel (ivit_mlp_rs.h), which needs two 80-token units per workgroup to overlap anything and exists at width 384 only.
+// eight waves.  Units are always contiguous tile ranges.  The LayerNorm-headed form is mlp192ln_kernel (below): norm2's constants
+// take the 3 KB that two workgroups leave of the CU's LDS.
 //
 // Width 256 (mlp256_kernel; Swin-B stage 1, hidden row 1024 B).  Eight waves, two channel tiles each (NJ = 2): fc1's 64 tiles are
 // 8 waves x 4 chunks of 2, fc2's 16 are 8 x 2.  Hidden 80 KB + activations 20 KB + table lines 4 KB = 104 KB: one workgroup per
@@ -52,6 +52,7 @@
 #pragma once
 #include <type_traits>
 #include "ivit_device.h"
+#include "ivit_layernorm.h"
 
 // The geometry of the lock-step kernel: everything follows from the width C and the wave count, except the five constants each
 // width states itself (below).
@@ -69,6 +70,8 @@ struct MlpGeo {
     static constexpr int SA = KS2 * KBLK;                   // activation tile [KS1][80][64 B]
     static constexpr int STAB = SA + KS1 * KBLK;            // one ShiftGELU table line (256 B) per half-wave
     static constexpr int SMEM = STAB + 2 * WAVES * 256;
+    static constexpr int SLN = SMEM;                        // LayerNorm-headed form: norm2's constants, 16 B per channel (c fp64, bias_int, sc)
+    static constexpr int SMEM_LN = SLN + 16 * C;            // 80 KB x 2 at width 192, 160 KB x 1 at 384: exactly a CU's LDS
     static constexpr int WD = 3;                            // weight fragments in flight ahead of the MFMAs that consume them
     static constexpr bool DIRECT = false;                   // operands as a plan prepared them (fragment-ordered weights, c = m * 2^-e, a bias)
 };
@@ -125,6 +128,8 @@ struct MlpArgs {
     int balanced;             // unit schedule: 0 = 64-token units dealt round-robin, 1 = contiguous tile ranges cut into units of <= 5 tiles
     // mlp384rs_kernel<FMA, LNH = true> (ivit_layernorm_mlp_fused_planned): norm2 + qact3 of this workgroup's rows first, from the block's 16-bit
     // stream (`residual` is that stream), into x (a scratch of M x 384 bytes that only this launch reads)
+    // mlp384ln_kernel / mlp192ln_kernel (ivit_layernorm_mlp_lockstep_planned), at both widths: the same operands, x unused — norm2's
+    // rows go straight into the unit's activation tile
     float ln_s;
     const float *ln_bias_int, *ln_sc;
     const ivit_dyadic *ln_dy;
@@ -213,16 +218,34 @@ __device__ __forceinline__ int mlp_rq(int z, double c) {
 template <bool FMA>
 __global__ __launch_bounds__(Mlp384Geo::THREADS, Mlp384Geo::WAVES * Mlp384Geo::WG_PER_CU / 4) void mlp384_kernel(MlpArgs p) {
     typedef Mlp384Geo G;
+    constexpr bool LNH = false;
 #include "ivit_mlp_body.h"
 }
 template <bool FMA>
 __global__ __launch_bounds__(Mlp192Geo::THREADS, Mlp192Geo::WAVES * Mlp192Geo::WG_PER_CU / 4) void mlp192_kernel(MlpArgs p) {
     typedef Mlp192Geo G;
+    constexpr bool LNH = false;
 #include "ivit_mlp_body.h"
 }
 template <bool FMA>
 __global__ __launch_bounds__(Mlp256Geo::THREADS, Mlp256Geo::WAVES * Mlp256Geo::WG_PER_CU / 4) void mlp256_kernel(MlpArgs p) {
     typedef Mlp256Geo G;
+    constexpr bool LNH = false;
+#include "ivit_mlp_body.h"
+}
+// The LayerNorm-headed form of the two ViT widths (ivit_mlp_body.h, LNH): norm2 + qact3 + the Mlp + the residual QuantAct
+// (vit_quant.py:139-142, layers_quant.py:144-153) in one launch.  Kernels of their own names, not a second template parameter of
+// the two above: those keep their symbols (profilers, bench tools and tests/test_mlp192_cpu.py find them by name)
+template <bool FMA>
+__global__ __launch_bounds__(Mlp384Geo::THREADS, Mlp384Geo::WAVES * Mlp384Geo::WG_PER_CU / 4) void mlp384ln_kernel(MlpArgs p) {
+    typedef Mlp384Geo G;
+    constexpr bool LNH = true;
+#include "ivit_mlp_body.h"
+}
+template <bool FMA>
+__global__ __launch_bounds__(Mlp192Geo::THREADS, Mlp192Geo::WAVES * Mlp192Geo::WG_PER_CU / 4) void mlp192ln_kernel(MlpArgs p) {
+    typedef Mlp192Geo G;
+    constexpr bool LNH = true;
 #include "ivit_mlp_body.h"
 }
 // width 128: the body once per requant form (FMA here is mlp_rq's RQ: 0 or 2), and the kernel that picks between them — every
@@ -231,6 +254,7 @@ __global__ __launch_bounds__(Mlp256Geo::THREADS, Mlp256Geo::WAVES * Mlp256Geo::W
 template <int FMA>
 __device__ __forceinline__ void mlp128_body(const MlpArgs &p) {
     typedef Mlp128Geo G;
+    constexpr bool LNH = false;
 #include "ivit_mlp_body.h"
 }
 __global__ __launch_bounds__(Mlp128Geo::THREADS, Mlp128Geo::WAVES * Mlp128Geo::WG_PER_CU / 4) void mlp128_kernel(MlpArgs p) {

@@ -1,6 +1,7 @@
 // ivit_mlp_body.h — the body of the lock-step fused-Mlp kernel (the scheme: ivit_mlp.h).  Not a header of its own: ivit_mlp.h includes it
-// once inside each entry point (mlp384_kernel, mlp256_kernel, mlp192_kernel, mlp128_body), which supplies `G` (the geometry), `FMA` (the
-// requant form: mlp_rq) and `p` (MlpArgs).  One
+// once inside each entry point (mlp384_kernel, mlp256_kernel, mlp192_kernel, mlp128_body and the LayerNorm-headed mlp384ln_kernel,
+// mlp192ln_kernel), which supplies `G` (the geometry), `FMA` (the requant form: mlp_rq), `LNH` (the activation tile of a unit is norm2 +
+// qact3 of its rows of the 16-bit stream, computed in place: below) and `p` (MlpArgs).  One
 // text, so that a change to the barriers, the prefetch distances or ShiftGELU reaches every width; included rather than called,
 // so that each entry point compiles exactly as if the body were written out in it.
     extern __shared__ __attribute__((aligned(256))) char sm[];
@@ -14,7 +15,7 @@
     // copied the current one into its accumulators — in the second, so the multipliers still come back first)
     static_assert(G::KS1 >= 2 && G::CQ_STEP <= G::BIAS_STEP && G::BIAS_STEP < G::KS1 - 1,
                   "the fc1 pipeline loads a chunk's multipliers, then the next bias, both before the chunk's last step");
-    static_assert(G::WG_PER_CU * G::SMEM <= 160 * 1024, "WG_PER_CU workgroups share a CU's LDS");
+    static_assert(G::WG_PER_CU * (LNH ? G::SMEM_LN : G::SMEM) <= 160 * 1024, "WG_PER_CU workgroups share a CU's LDS");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     typedef double v2d __attribute__((ext_vector_type(2)));
     // G::DIRECT: four channels' (m, 2^-e) pairs as the caller's table holds them -> their multipliers c = m * 2^-e
@@ -51,6 +52,60 @@
                 *reinterpret_cast<v4i *>(sm + G::SA + (c16 >> 2) * G::KBLK + row * 64 + mlp_phi(row, c16 & 3) * 16) = areg[i];
         }
     };
+
+    // LNH: the tile is not copied from p.x but computed — norm2 + qact3 (vit_quant.py:139-140) of the unit's rows of p.residual, the
+    // 16-bit stream that is LayerNorm input AND identity branch — so the LayerNorm's bytes never exist in HBM.  The arithmetic is
+    // LnGroup<C, 2> (8 lanes per row, 8 rows per wave and pass: layernorm_reg_kernel's, byte for byte); lane (k, h) of a row owns
+    // channels 32 i + 8 k + 4 h .. + 3 of step i, i.e. 4 bytes of chunk (i & 1) * 2 + (k >> 1) of K block i >> 1, stored where a_commit
+    // puts that (row, chunk).  Rows >= M are row M - 1 again (as a_fetch clamps them): the tile holds defined bytes.  The per-channel
+    // constants live behind the table lines at 16 B per channel (c fp64, bias_int, sc: what fits beside two workgroups per CU at
+    // width 192 and one at 384), so 1 / sc is formed per element (LnGroup::run<.., LOCAL_Y>).  ln_fetch requests the 16-bit rows of
+    // one pass (in front of ShiftGELU for a unit's first pass, one pass ahead after that), ln_rows normalises them into the tile
+    typedef LnGroup<G::C, 2> LG;
+    typedef typename LnRaw<4>::T ln_raw;
+    double *const cC = reinterpret_cast<double *>(sm + G::SLN);
+    float *const cB = reinterpret_cast<float *>(sm + G::SLN + G::C * 8), *const cSc = cB + G::C;
+    bool ln_fast = false;
+    // (the vote of ln_stage_constants goes through the first word of the table lines: nothing writes those before barrier B2 of unit 0)
+    if constexpr (LNH)
+        ln_fast = ln_stage_constants<G::C, G::THREADS, false>(p.ln_bias_int, p.ln_sc, p.ln_dy, cC, cB, cSc, reinterpret_cast<float *>(sm + G::STAB));
+    auto ln_fetch = [&](ln_raw (&raw)[LG::NSTEP], long long tile0, int r0) __attribute__((always_inline)) {
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        const int j = t & 7;
+        const long long grow = min(tile0 * 16 + r0 + ((t & 63) >> 3), p.M - 1);
+        const int16_t *xp = p.residual + grow * G::C + 4 * j;           // 8 k + 4 h with j = 2 k + h
+#pragma unroll
+        for (int i = 0; i < LG::NSTEP; ++i) raw[i] = *reinterpret_cast<const ln_raw *>(xp + 32 * i);
+    };
+    auto ln_rows = [&](const ln_raw (&raw)[LG::NSTEP], int r0) __attribute__((always_inline)) {
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        const int j = t & 7, k = j >> 1, row = r0 + ((t & 63) >> 3);
+        const float ys = rcp_rn(p.ln_s);
+        float xv[LG::NSTEP][LG::EPC];
+#pragma unroll
+        for (int i = 0; i < LG::NSTEP; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)raw[i][c], p.ln_s, ys);
+        char *const rowa = sm + G::SA + row * 64 + (k & 1) * 8 + 4 * (j & 1);
+        const int ph0 = mlp_phi(row, k >> 1) * 16, ph1 = mlp_phi(row, 2 + (k >> 1)) * 16;
+        auto place = [&](int i, unsigned pk0, unsigned) __attribute__((always_inline)) {
+            *reinterpret_cast<unsigned *>(rowa + (i >> 1) * G::KBLK + ((i & 1) ? ph1 : ph0)) = pk0;
+        };
+        LG::template run<std::false_type, decltype(place), true>(xv, j, k, 4 * j, ln_fast, true, cC, cB, cSc, nullptr, place);
+    };
+    // the passes of a unit's tile behind the first fetch: rows r0, r0 + 8 WAVES, ... of this wave
+    auto ln_tile = [&](ln_raw (&raw)[LG::NSTEP], long long tile0, int ntt) __attribute__((always_inline)) {
+        for (int r0 = wave * 8; r0 < ntt * 16; r0 += G::WAVES * 8) {
+            ln_raw cur[LG::NSTEP];
+#pragma unroll
+            for (int i = 0; i < LG::NSTEP; ++i) cur[i] = raw[i];
+            if (r0 + G::WAVES * 8 < ntt * 16) ln_fetch(raw, tile0, r0 + G::WAVES * 8);
+            ln_rows(cur, r0);
+        }
+    };
+    ln_raw lraw[LG::NSTEP];
 
     // ------------------------------------------------------------------------------------------------------------------
     // one unit of NTT token tiles starting at tile `tile0`; (next_tile0, next_ntt): the unit whose activations to prefetch
@@ -165,7 +220,9 @@
         // bytes are read once (NW dwords per lane) and stay in registers from the row maximum (packed byte maxima, then 5
         // shuffles) over the fetch of the maximum's 256-byte table line (global -> this half-wave's LDS slot) to the byte
         // gathers and the write-back.  No workgroup barrier inside.  The next unit's activations travel meanwhile.
-        if (next_ntt > 0) a_fetch(next_tile0, next_ntt);
+        if constexpr (LNH) {
+            if (wave * 8 < next_ntt * 16) ln_fetch(lraw, next_tile0, wave * 8);
+        } else if (next_ntt > 0) a_fetch(next_tile0, next_ntt);
         {
             const int hw = wave * 2 + (lane >> 5), l32 = lane & 31;
             typedef __attribute__((address_space(3))) const unsigned char lds_u8;
@@ -219,7 +276,8 @@
                 }
             }
         }
-        if (next_ntt > 0) a_commit(next_ntt);
+        if constexpr (LNH) ln_tile(lraw, next_tile0, next_ntt);
+        else if (next_ntt > 0) a_commit(next_ntt);
         __syncthreads();                                                    // B3
 
         // ---- fc2 + qact2 (16 bit) + qact4 with the identity branch (16 bit)
@@ -308,8 +366,13 @@
     };
 
     // ---- the unit stream
-    a_fetch(unit_tile0(0), unit_ntt(0));
-    a_commit(unit_ntt(0));
+    if constexpr (LNH) {
+        if (wave * 8 < unit_ntt(0) * 16) ln_fetch(lraw, unit_tile0(0), wave * 8);
+        ln_tile(lraw, unit_tile0(0), unit_ntt(0));
+    } else {
+        a_fetch(unit_tile0(0), unit_ntt(0));
+        a_commit(unit_ntt(0));
+    }
     __syncthreads();
     for (int i = 0; i < nu; ++i) {
         const long long tile0 = unit_tile0(i), tile1 = unit_tile0(i + 1);

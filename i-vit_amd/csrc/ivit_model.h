@@ -260,9 +260,11 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
             RUN(ivit_attn_pv_requant(h, p16, vt, b.dy_pv, ctx8, B, H, T, dh, ld, ld));
         }
         // attn.proj + qact2 with the identity branch, then norm2 + qact3 and the Mlp.  norm2 rides in the HEAD of the fused Mlp's launch
-        // (ivit_layernorm_mlp_fused_planned) where that kernel takes the shape; in the tail of the proj launch it measured slower
-        // (profiles/README.md)
+        // (ivit_layernorm_mlp_fused_planned) where the role-split kernel takes the shape, else in the activation tiles of the lock-step
+        // kernel (ivit_layernorm_mlp_lockstep_planned: D = 192, D = 384 below two units per CU, the class-token tail) where
+        // ln_mlp_plan_fuses says so; in the tail of the proj launch it measured slower (profiles/README.md)
         const bool mlp_fast = mlp_plan_fuses(m->mlp_plans[i], b.res2_main, b.res2_res, Mb);
+        const bool ln_lockstep = ln_mlp_plan_fuses(h, m->mlp_plans[i], b.res2_main, b.res2_res, Mb) == LN_MLP_LOCKSTEP;
         RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, Mb));
         { int16_t *t = x; x = y; y = t; }
         const int8_t *tab = gelu_table(m, i);
@@ -270,12 +272,17 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
                                                                  b.res2_res, y, Mb)
                               : IVIT_ERR_UNSUPPORTED,
                      [&] {
-                         RUN(ivit_layernorm_requant(h, x, Mb, D, D, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8));
-                         if (mlp_fast)       // hidden tensor stays in LDS
-                             return ivit_mlp_fused_planned(h, m->mlp_plans[i], a8, tab, b.res2_main, b.res2_res, x, y, Mb);
-                         RUN(ivit_linear_i8_requant_planned(h, m->plans[4 * i + 2], a8, 8, h8, Mb));
-                         RUN(ivit_shiftgelu_requant_lut(h, h8, Mb, Hd, tab, g8));
-                         return ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, Mb);
+                         return fused_or(ln_lockstep ? ivit_layernorm_mlp_lockstep_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc,
+                                                                                           b.n2_dy, tab, b.res2_main, b.res2_res, y, Mb)
+                                                     : IVIT_ERR_UNSUPPORTED,
+                                         [&] {
+                                             RUN(ivit_layernorm_requant(h, x, Mb, D, D, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8));
+                                             if (mlp_fast)       // hidden tensor stays in LDS
+                                                 return ivit_mlp_fused_planned(h, m->mlp_plans[i], a8, tab, b.res2_main, b.res2_res, x, y, Mb);
+                                             RUN(ivit_linear_i8_requant_planned(h, m->plans[4 * i + 2], a8, 8, h8, Mb));
+                                             RUN(ivit_shiftgelu_requant_lut(h, h8, Mb, Hd, tab, g8));
+                                             return ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, Mb);
+                                         });
                      }));
         { int16_t *t = x; x = y; y = t; }
     }
@@ -383,6 +390,19 @@ int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks) {
     int n = 0;
     for (int i = 0; i < m->cfg.depth; ++i)
         n += mlp_plan_fuses(m->mlp_plans[i], m->blocks[i].res2_main, m->blocks[i].res2_res, (long long)batch * m->T);
+    *blocks = n;
+    return IVIT_OK;
+}
+
+int ivit_vit_fused_ln_mlp_blocks(ivit_vit m, int batch, int *blocks) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, blocks && batch > 0, "bad arguments");
+    int n = 0;
+    for (int i = 0; i < m->cfg.depth; ++i) {
+        const bool tail = i == m->cfg.depth - 1 && cls_tail(m);
+        n += ln_mlp_plan_fuses(m->h, m->mlp_plans[i], m->blocks[i].res2_main, m->blocks[i].res2_res, tail ? batch : (long long)batch * m->T) !=
+             LN_MLP_TWO_LAUNCHES;
+    }
     *blocks = n;
     return IVIT_OK;
 }

@@ -127,6 +127,9 @@ class ViTEngine:
         self.v_row_major = True         # forward_ops: v row-major into the row-table attention (False: v^T as before)
         self.fuse_ln_qkv = True         # forward_ops: norm1 in the qkv GEMM's prologue where the plan is prepared (False: two launches)
         self.fuse_ln_mlp = True         # forward_ops: norm2 in the head of the fused Mlp's launch (False: two launches)
+        # forward_ops: norm2 in the lock-step fused Mlp's activation tiles (ivit_layernorm_mlp_lockstep_planned), tried where the launch above
+        # refuses.  Off by default: bench.py's --full accounting prices LayerNorm launches from the two LayerNorm-headed names it knows
+        self.fuse_ln_mlp_lockstep = False
         self.fuse_patch_embed = True    # forward_ops: ivit_patch_embed (False: im2col, GEMM, embed_finish)
         self._qkv_prepared = set()
         self.rowtab = {}
@@ -388,6 +391,9 @@ class ViTEngine:
             ln_mlp = fused and self.fuse_ln_mlp and self.h.try_call(
                 "ivit_layernorm_mlp_fused_planned", self._mlp_plans[i], P(x), f32[p + "ln2.s"], self.ptr(p + "norm2.bias_int"), self.ptr(p + "norm2.sc"),
                 self.ptr(p + "norm2.dy"), P(ws["a8"]), _P(self.gelu_tab[i].data_ptr()), _dy(dm), _dy(dr), P(y), M)
+            ln_mlp = ln_mlp or (fused and self.fuse_ln_mlp_lockstep and self.h.try_call(
+                "ivit_layernorm_mlp_lockstep_planned", self._mlp_plans[i], P(x), f32[p + "ln2.s"], self.ptr(p + "norm2.bias_int"), self.ptr(p + "norm2.sc"),
+                self.ptr(p + "norm2.dy"), _P(self.gelu_tab[i].data_ptr()), _dy(dm), _dy(dr), P(y), M))
             if not ln_mlp:
                 call("ivit_layernorm_requant", P(x), M, D, D, f32[p + "ln2.s"], self.ptr(p + "norm2.bias_int"),
                      self.ptr(p + "norm2.sc"), self.ptr(p + "norm2.dy"), P(ws["a8"]))

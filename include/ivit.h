@@ -48,7 +48,10 @@ enum {
     IVIT_ERR_NO_DEVICE = 4
 };
 
-/* 100 * major + minor.  110: ivit_linear_plan_prepare_ws also takes K = 192 plans, and every entry that runs on a prepared plan takes
+/* 100 * major + minor.  111: ivit_layernorm_mlp_lockstep_planned, ivit_vit_fused_ln_mlp_blocks (additions only): ivit_vit_forward
+ * runs norm2 + the Mlp of a D = 192 block, and of a D = 384 block below two units per CU (small batches, the class-token tail), as
+ * one launch.
+ * 110: ivit_linear_plan_prepare_ws also takes K = 192 plans, and every entry that runs on a prepared plan takes
  * them (ivit_linear_i8_qkv_planned also with v^T there); ivit_layernorm_linear_i8_qkv_ldv_planned, ivit_vit_fused_qkv_blocks
  * (additions only): ivit_vit_forward runs norm1 + qkv of a D = 192, dh = 64 block as one launch and its attn.proj on the same kernel.
  * 109: the class-token forms of the fused attention (ivit_attention_fused_cls, ivit_attention_fused_lut_cls,
@@ -71,7 +74,7 @@ enum {
  * fields exp_* at their END (added in 100 without a bump: a caller compiled against an older layout must be rebuilt).
  * Parameter structs are read field by field: ZERO-INITIALISE them (memset / = {0}) before filling — exp_aq == NULL (and
  * exp_nc == exp_tcount == exp_dmin == 0) selects the arithmetic Shiftmax, anything else is taken as device pointers.        */
-#define IVIT_VERSION 110
+#define IVIT_VERSION 111
 int ivit_version(void);
 const char *ivit_status_string(int status);
 
@@ -404,6 +407,11 @@ int ivit_vit_workspace_bytes(ivit_vit m, int batch, int nslices, size_t *bytes);
 /* How many blocks of a forward of `batch` images in ONE slice issue their Mlp as a single launch (the fused kernels of
  * ivit_mlp_plan_create); the other blocks run fc1 / ShiftGELU / fc2 as three.  Decided by the rule the forward itself applies. */
 int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks);
+/* How many blocks of a forward of `batch` images in ONE slice issue norm2 + qact3 + the Mlp + the residual QuantAct as a single launch,
+ * through either LayerNorm-headed entry (ivit_layernorm_mlp_fused_planned, ivit_layernorm_mlp_lockstep_planned); the other blocks run
+ * the LayerNorm as a launch of its own.  The last block is counted at the row count of its class-token tail (ivit_vit_cls_tail).
+ * Decided by the rule the forward itself applies.                                                                                */
+int ivit_vit_fused_ln_mlp_blocks(ivit_vit m, int batch, int *blocks);
 /* How many blocks of a forward of `batch` images in ONE slice issue norm1 + qact1 + attn.qkv as a single launch
  * (ivit_layernorm_linear_i8_qkv_ldv_planned: D = 192 or 384 with dh = 64; a D = 384 block only where it takes v row-major); the other
  * blocks run the LayerNorm and the GEMM as two.  Decided by the rule the forward itself applies.                               */
@@ -584,6 +592,17 @@ int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, cons
 int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int,
                                      const float *sc, const ivit_dyadic *ln_dy, int8_t *scratch8, const int8_t *gelu_table,
                                      ivit_dyadic dy_main, ivit_dyadic dy_res, int16_t *out, int64_t M);
+/* The same block tail — norm2 + qact3, Mlp.forward and the residual QuantAct (vit_quant.py:139-142 around layers_quant.py:144-153) — in
+ * ONE launch of the LOCK-STEP kernel, at widths 192 and 384 and every token count: a workgroup computes the LayerNorm of a unit's rows
+ * (x16 [M, C], the block's 16-bit stream, which is also the identity branch; scale / bias_int / sc / ln_dy as for
+ * ivit_layernorm_requant) straight into the unit's activation tile in LDS, one unit ahead of the GEMMs, so norm2's 8-bit rows never
+ * exist in memory and there is no scratch argument.  out == ivit_layernorm_requant followed by ivit_mlp_fused_planned.  Always the
+ * lock-step kernel, whatever ivit_mlp_plan_select says; grids and unit schedules are those of ivit_mlp_fused_planned on that kernel
+ * (ivit_set_cu_share included).  out overlapping x16 is IVIT_ERR_INVALID.  IVIT_ERR_UNSUPPORTED (nothing launched) on a plan of
+ * another width (256) and for residual multipliers outside the fast range.                                                       */
+int ivit_layernorm_mlp_lockstep_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int,
+                                        const float *sc, const ivit_dyadic *ln_dy, const int8_t *gelu_table, ivit_dyadic dy_main,
+                                        ivit_dyadic dy_res, int16_t *out, int64_t M);
 /* PatchMerging's 2x2 gather (swin_quant.py:336-342): x [B,R,R,C] (in_bits 8 or 16) ->
  * int16 [B, (R/2)^2, 4C], channel blocks in the reference's torch.cat order.                  */
 int ivit_patch_merge_gather(ivit_handle h, const void *x, int in_bits, int B, int R, int C, int16_t *out);
