@@ -28,6 +28,7 @@ _LAZY = {
     "swin_base_patch4_window12_384": ("swin_quant", "swin_base_patch4_window12_384"),
     "SwinEngine": ("swin_engine", "SwinEngine"),
     "load_reference_state_dict": ("checkpoint", "load_reference_state_dict"),
+    "topk_reference": ("predict", "topk_reference"), "evaluate": ("predict", "evaluate"),
 }
 
 

@@ -241,6 +241,11 @@ SIGNATURES = {
     "ivit_im2col_patch": [_P, _P, _I, _I, _I, _I, _I, _P],
     "ivit_embed_finish": [_P, _P, _P, _P, Dyadic, Dyadic, _P, _I, _I, _I],
     "ivit_patch_embed": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, Dyadic, Dyadic, _P, _I],
+    "ivit_logits_topk": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "ivit_vit_predict": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P, _P, _I, _P, _P],
+    "ivit_swin_predict": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P, _P, _I, _P, _P],
+    "ivit_vit_predict_graph_create": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P, _P, _I, _P, _P, ctypes.POINTER(_P)],
+    "ivit_swin_predict_graph_create": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P, _P, _I, _P, _P, ctypes.POINTER(_P)],
 }
 OTHER_SYMBOLS = ["ivit_version", "ivit_status_string", "ivit_last_error", "ivit_linear_plan_destroy", "ivit_mlp_plan_destroy", "ivit_linear_plan_query", "ivit_mlp_plan_select"]
 

@@ -27,6 +27,7 @@
 #include "ivit_swin_mlp_rs.h"
 #include "ivit_gemm_ws.h"
 #include "ivit_swin12.h"
+#include "ivit_topk.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -1777,6 +1778,19 @@ int ivit_widen_i8_i16(ivit_handle h, const int8_t *x, int16_t *out, int64_t n) {
     REQUIRE(h, x && out && n >= 0, "bad arguments");
     if (n == 0) return IVIT_OK;
     widen_i8_i16_kernel<<<grid_for(h, n, 1024), 256, 0, h->stream>>>(x, out, n);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+int ivit_logits_topk(ivit_handle h, const int32_t *logits, const float *scale, int batch, int num_classes, int k, int32_t *idx,
+                     float *val) {
+    CHECK_H(h);
+    REQUIRE(h, logits && scale && idx && batch >= 0 && num_classes >= 1, "bad arguments");
+    REQUIRE(h, k >= 1 && k <= TOPK_MAX_K && k <= num_classes, "k must be in 1 .. min(16, num_classes)");
+    if (batch == 0) return IVIT_OK;
+    const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per image; 64-bit sum: no overflow near INT_MAX
+    if (num_classes <= TOPK_REG_CLASSES) logits_topk_kernel<true><<<grid, 256, 0, h->stream>>>(logits, scale, batch, num_classes, k, idx, val);
+    else logits_topk_kernel<false><<<grid, 256, 0, h->stream>>>(logits, scale, batch, num_classes, k, idx, val);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

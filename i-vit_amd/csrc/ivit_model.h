@@ -466,6 +466,21 @@ int ivit_vit_graph_create(ivit_vit m, const int8_t *images, int batch, int nslic
     return graph_capture(m->h, out, [&] { return ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits); });
 }
 
+// the forward, then the top-k of its logits on the handle's stream: behind the slices' join, so inside a capture it is one more node
+int ivit_vit_predict(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                     const float *head_scale, int k, int32_t *idx, float *val) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, head_scale && idx && k >= 1 && k <= TOPK_MAX_K && k <= m->cfg.num_classes, "head_scale / idx null or k outside 1 .. min(16, num_classes)");
+    RUN(ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits));
+    return ivit_logits_topk(m->h, logits, head_scale, batch, m->cfg.num_classes, k, idx, val);
+}
+
+int ivit_vit_predict_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                                  int32_t *logits, const float *head_scale, int k, int32_t *idx, float *val, ivit_graph *out) {
+    if (!m) return IVIT_ERR_INVALID;
+    return graph_capture(m->h, out, [&] { return ivit_vit_predict(m, images, batch, nslices, workspace, bytes, logits, head_scale, k, idx, val); });
+}
+
 int ivit_graph_launch(ivit_graph g) {
     if (!g) return IVIT_ERR_INVALID;
     hipError_t e = hipGraphLaunch(g->exec, g->h->stream);
@@ -777,6 +792,20 @@ int ivit_swin_graph_create(ivit_swin m, const int8_t *images, int batch, int nsl
                            int32_t *logits, ivit_graph *out) {
     if (!m) return IVIT_ERR_INVALID;
     return graph_capture(m->h, out, [&] { return ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits); });
+}
+
+int ivit_swin_predict(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                     const float *head_scale, int k, int32_t *idx, float *val) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, head_scale && idx && k >= 1 && k <= TOPK_MAX_K && k <= m->cfg.num_classes, "head_scale / idx null or k outside 1 .. min(16, num_classes)");
+    RUN(ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits));
+    return ivit_logits_topk(m->h, logits, head_scale, batch, m->cfg.num_classes, k, idx, val);
+}
+
+int ivit_swin_predict_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                                  int32_t *logits, const float *head_scale, int k, int32_t *idx, float *val, ivit_graph *out) {
+    if (!m) return IVIT_ERR_INVALID;
+    return graph_capture(m->h, out, [&] { return ivit_swin_predict(m, images, batch, nslices, workspace, bytes, logits, head_scale, k, idx, val); });
 }
 
 }  // extern "C"

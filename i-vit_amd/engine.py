@@ -2,6 +2,8 @@
 
 `forward` / `capture` hand the whole batch to the native runner (`ivit_vit_forward`,
 csrc/ivit_model.h): one C call per batch, slices on internal HIP streams, optional hipGraph.
+`predict` / `capture_predict` (ivit_amd.predict.PredictMixin) are the same with the top-k of the
+dequantised logits behind them (`ivit_vit_predict`).
 `forward_ops` issues the same kernels one C-ABI call at a time from Python (used by the
 per-operator timing in bench.py and by the parity tests of the unfused attention path).
 Both follow the call order of the reference `VisionTransformer.forward`
@@ -17,6 +19,7 @@ import torch
 
 from . import _lib
 from .freeze import freeze_vit
+from .predict import PredictMixin
 
 _P = ctypes.c_void_p
 
@@ -90,7 +93,9 @@ def vit_native_params(cfg, table, f32, host, base):
     return c, prm, blocks
 
 
-class ViTEngine:
+class ViTEngine(PredictMixin):
+    _PREDICT, _PREDICT_GRAPH = "ivit_vit_predict", "ivit_vit_predict_graph_create"     # PredictMixin: predict / capture_predict
+
     def __init__(self, cfg, consts, f32, device="cuda:0", blob=None, table=None):
         """consts/f32 from freeze.freeze_vit (rank 0) — or a pre-packed (blob, table)
         received from a broadcast (then `consts` may be None)."""

@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from .engine import pack_constants
 from .freeze import dyadic, layernorm_constants, quantize, quantize_bias, quantize_weight, shiftmax_tables
+from .predict import PredictMixin
 
 _P = ctypes.c_void_p
 
@@ -210,7 +211,9 @@ def check_swin_windows(cfg):
                                  f"resolution {res} and window {wsz}")
 
 
-class SwinEngine:
+class SwinEngine(PredictMixin):
+    _PREDICT, _PREDICT_GRAPH = "ivit_swin_predict", "ivit_swin_predict_graph_create"   # PredictMixin: predict / capture_predict
+
     def __init__(self, cfg, weights, scales, device="cuda:0", packed=None, exp_tables=False):
         """weights/scales: freeze here (rank 0) — or `packed` = (blob, table, host) received from a broadcast.
         exp_tables: see freeze_swin."""

@@ -619,6 +619,32 @@ int ivit_widen_i8_i16(ivit_handle h, const int8_t *x, int16_t *out, int64_t n);
 int ivit_linear_i8_requant8_store16(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias, const ivit_dyadic *dy_ch,
                                     int16_t *out16, int M, int N, int K);
 
+/* ---- a13  predictions: what validate() does with the model's output (quant_train.py:314-351: output = model(data) at :334, then
+ * accuracy(output, target, topk=(1, 5)) at :338, i.e. a top-k of every output row compared with the label), on the device.
+ * The output is the head's accumulators times the per-class head scale (quant_modules.py:96-97: F.linear(x_int, weight_integer,
+ * bias_integer) * bias_scaling_factor, returned unchanged by vit_quant.py:278-282 / swin_quant.py:560-564):
+ *   v[b, c] = fl32(fl32(logits[b, c]) * scale[c])      (int -> fp32 conversion RNE, one multiply, nothing contracted)
+ * logits int32 [batch, num_classes], scale float [num_classes] -> idx int32 [batch, k], val float [batch, k] (val may be NULL:
+ * indices only).  The ORDER is part of the contract, which torch.topk's is not: descending by value, -0.0 and +0.0 equal, equal values
+ * by ascending class index — row b of idx is the first k entries of np.lexsort((arange(num_classes), -(v[b] + 0.0))); val holds the
+ * bits of v, -0.0 included.  Non-finite scale entries are OUTSIDE the contract (no frozen model has one).
+ * 1 <= k <= min(16, num_classes), IVIT_ERR_INVALID otherwise (nothing launched).  One launch (csrc/ivit_topk.h).                    */
+int ivit_logits_topk(ivit_handle h, const int32_t *logits, const float *scale, int batch, int num_classes, int k, int32_t *idx,
+                     float *val);
+/* validate()'s `output = model(images)` + `output.topk(...)` (quant_train.py:334, :338) as one call: ivit_vit_forward /
+ * ivit_swin_forward of the same arguments (logits is written, with the same integers), then ivit_logits_topk of those logits with
+ * `head_scale` (float [num_classes], device: the model's bias_scaling_factor of the head, "head.scale" of the constants blob) on the
+ * handle's stream, behind the slices' join.  k is checked before anything is launched.  The *_graph_create forms capture both
+ * (replay: ivit_graph_launch).                                                                                                      */
+int ivit_vit_predict(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                     const float *head_scale, int k, int32_t *idx, float *val);
+int ivit_swin_predict(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                      const float *head_scale, int k, int32_t *idx, float *val);
+int ivit_vit_predict_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                                  int32_t *logits, const float *head_scale, int k, int32_t *idx, float *val, ivit_graph *out);
+int ivit_swin_predict_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                                   int32_t *logits, const float *head_scale, int k, int32_t *idx, float *val, ivit_graph *out);
+
 /* ---- diagnostics (used by the parity tests only) ------------------------------------
  * q_ieee = n / d (compiler's correctly-rounded division) and q_lean = the hoisted-reciprocal
  * FMA sequence the kernels use for constant divisors; must agree bit for bit.            */
