@@ -8,42 +8,8 @@ import torch
 import torch.distributed as dist
 
 from .engine import ViTEngine, pack_constants
-from .freeze import freeze_vit
-
-
-def broadcast_constants(consts, f32, rank, world, device):
-    """rank 0 passes (consts, f32); other ranks pass (None, None).
-    Returns (blob tensor on `device`, table, f32) on every rank."""
-    if world == 1:
-        blob, table = pack_constants(consts)
-        return torch.from_numpy(blob).to(device), table, f32
-    meta = [None]
-    blob_t = None
-    if rank == 0:
-        blob, table = pack_constants(consts)
-        meta = [(table, {k: float(np.float32(v)) for k, v in f32.items()}, int(blob.size))]
-        blob_t = torch.from_numpy(blob).to(device)
-    dist.broadcast_object_list(meta, src=0)
-    table, f32, nbytes = meta[0]
-    if rank != 0:
-        blob_t = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    dist.broadcast(blob_t, src=0)   # RCCL: one large message, ring over xGMI links
-    return blob_t, table, f32
-
-
-def shard_range(total, rank, world):
-    """contiguous, balanced split of `total` images over `world` ranks."""
-    base, rem = divmod(total, world)
-    lo = rank * base + min(rank, rem)
-    return lo, lo + base + (1 if rank < rem else 0)
-
-
-def build_engine_broadcast(cfg, weights, scales, device, rank, world):
-    consts = f32 = None
-    if rank == 0:
-        consts, f32 = freeze_vit(cfg, weights, scales)
-    blob, table, f32 = broadcast_constants(consts, f32, rank, world, device)
-    return ViTEngine(cfg, None, f32, device=device, blob=blob, table=table)
+from .freeze import freeze_swin, freeze_vit
+from .swin_engine import SwinEngine, pack_swin_constants
 
 
 def broadcast_packed(packed, rank, world, device):
@@ -65,8 +31,29 @@ def broadcast_packed(packed, rank, world, device):
     return blob_t, table, host
 
 
+def broadcast_constants(consts, f32, rank, world, device):
+    """rank 0 passes (consts, f32); other ranks pass (None, None).
+    Returns (blob tensor on `device`, table, f32) on every rank."""
+    packed = pack_constants(consts) + ({k: float(np.float32(v)) for k, v in f32.items()},) if rank == 0 else None
+    return broadcast_packed(packed, rank, world, device)
+
+
+def shard_range(total, rank, world):
+    """contiguous, balanced split of `total` images over `world` ranks."""
+    base, rem = divmod(total, world)
+    lo = rank * base + min(rank, rem)
+    return lo, lo + base + (1 if rank < rem else 0)
+
+
+def build_engine_broadcast(cfg, weights, scales, device, rank, world):
+    consts = f32 = None
+    if rank == 0:
+        consts, f32 = freeze_vit(cfg, weights, scales)
+    blob, table, f32 = broadcast_constants(consts, f32, rank, world, device)
+    return ViTEngine(cfg, None, f32, device=device, blob=blob, table=table)
+
+
 def build_swin_engine_broadcast(cfg, weights, scales, device, rank, world):
-    from .swin_engine import SwinEngine, freeze_swin, pack_swin_constants
     packed = pack_swin_constants(freeze_swin(cfg, weights, scales)) if rank == 0 else None
     return SwinEngine(cfg, None, None, device=device, packed=broadcast_packed(packed, rank, world, device))
 

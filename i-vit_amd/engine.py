@@ -1,9 +1,7 @@
 """ViTEngine — frozen integer DeiT/ViT forward on one MI355X through the C-ABI.
 
-`forward` / `capture` hand the whole batch to the native runner (`ivit_vit_forward`,
-csrc/ivit_model.h): one C call per batch, slices on internal HIP streams, optional hipGraph.
-`predict` / `capture_predict` (ivit_amd.predict.PredictMixin) are the same with the top-k of the
-dequantised logits behind them (`ivit_vit_predict`).
+`forward` / `capture` / `predict` / `capture_predict` are NativeEngine's (ivit_amd.native): the whole
+batch goes to the native runner (`ivit_vit_forward`, csrc/ivit_model.h) in one C call.
 `forward_ops` issues the same kernels one C-ABI call at a time from Python (used by the
 per-operator timing in bench.py and by the parity tests of the unfused attention path).
 Both follow the call order of the reference `VisionTransformer.forward`
@@ -19,7 +17,7 @@ import torch
 
 from . import _lib
 from .freeze import freeze_vit
-from .predict import PredictMixin
+from .native import NativeEngine
 
 _P = ctypes.c_void_p
 
@@ -93,29 +91,20 @@ def vit_native_params(cfg, table, f32, host, base):
     return c, prm, blocks
 
 
-class ViTEngine(PredictMixin):
-    _PREDICT, _PREDICT_GRAPH = "ivit_vit_predict", "ivit_vit_predict_graph_create"     # PredictMixin: predict / capture_predict
+class ViTEngine(NativeEngine):
+    PREFIX = "ivit_vit"
 
     def __init__(self, cfg, consts, f32, device="cuda:0", blob=None, table=None):
         """consts/f32 from freeze.freeze_vit (rank 0) — or a pre-packed (blob, table)
         received from a broadcast (then `consts` may be None)."""
-        self.cfg = cfg
-        self.device = torch.device(device)
-        if not torch.cuda.is_available():
-            raise _lib.IvitError("ViTEngine needs a HIP device; the product path has no CPU fallback")
-        torch.cuda.set_device(self.device)
+        self._plans, self._mlp_plans = {}, {}       # before anything can raise: __del__ reads them
+        super().__init__(cfg, device)
         if blob is None:
             blob, table = pack_constants(consts)
-        self.table = table
         self.f32 = {k: float(np.float32(v)) for k, v in f32.items()}
-        if isinstance(blob, np.ndarray):
-            self.blob = torch.from_numpy(blob).to(self.device)
-        else:
-            self.blob = blob  # already a device uint8 tensor
+        self._load(blob, table)
         # scalar dyadics are passed by value: keep host copies
         self.host = host_scalars(blob if isinstance(blob, np.ndarray) else self.blob.cpu().numpy(), table)
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.h = _lib.Handle(dev_index, torch.cuda.current_stream(self.device).cuda_stream)
         self._ws = {}
         self.fused_attention = (cfg.head_dim == 64 and cfg.num_tokens <= 640)
         self.use_exp_tables = True      # forward_ops only: False issues the arithmetic Shiftmax (cross-check)
@@ -157,11 +146,7 @@ class ViTEngine(PredictMixin):
         # copy of the fragment-ordered Mlp weights (14 MB for DeiT-S).  use_plans = False issues the unplanned kernels
         self.use_plans = True
         self.use_fused_mlp = True       # forward_ops: ivit_mlp_fused_planned where a fused plan exists (D = 384 or 192)
-        self._plans = {}
-        self._mlp_plans = {}
         self._build_native()
-
-    MAX_SLICES = 8
 
     def build_op_plans(self):
         """ivit_linear_plan_create / ivit_mlp_plan_create for every block (idempotent)."""
@@ -187,104 +172,30 @@ class ViTEngine(PredictMixin):
         self.build_op_plans()
         return self._plans[prefix].p
 
-    def _build_native(self):
-        """ivit_vit_create: hand the runner device pointers into the blob + host scalars."""
-        c, prm, self._native_keep = vit_native_params(self.cfg, self.table, self.f32, self.host, self.blob.data_ptr())
-        self.model = _P()
-        self.h._check(self.h.lib.ivit_vit_create(self.h.h, ctypes.byref(c), ctypes.byref(prm), self.MAX_SLICES,
-                                                 ctypes.byref(self.model)), "ivit_vit_create")
-        self._native_ws = {}
+    def _native_params(self):
+        return vit_native_params(self.cfg, self.table, self.f32, self.host, self.blob.data_ptr())
+
+    def _workspace_init(self, ws, B, nslices):
+        self._entry("_workspace_init", self.model, _P(ws.data_ptr()), ws.numel(), B, nslices)
 
     def __del__(self):
+        super().__del__()
         try:
-            if getattr(self, "model", None):
-                self.h.lib.ivit_vit_destroy(self.model)
-                self.model = None
-            for mp in getattr(self, "_mlp_plans", {}).values():
+            for mp in self._mlp_plans.values():
                 self.h.lib.ivit_mlp_plan_destroy(mp)
             self._mlp_plans = {}
-            for pl in getattr(self, "_plans", {}).values():
+            for pl in self._plans.values():
                 pl.close()
         except Exception:
             pass
-
-    def _native_buffers(self, B, nslices):
-        key = (B, nslices)
-        if key not in self._native_ws:
-            # bounded: at most 4 (batch, slices) shapes that no captured graph refers to stay resident.  A graph has its
-            # workspace pointer baked in: those entries are pinned (self._graph_keys) and never evicted
-            free = [k for k in self._native_ws if k not in getattr(self, "_graph_keys", set())]
-            if len(free) >= 4:
-                self._native_ws.pop(free[0])
-        if key not in self._native_ws:
-            n = ctypes.c_size_t()
-            self.h._check(self.h.lib.ivit_vit_workspace_bytes(self.model, B, nslices, ctypes.byref(n)), "ivit_vit_workspace_bytes")
-            ws = torch.empty(n.value, dtype=torch.uint8, device=self.device)
-            logits = torch.empty(B, self.cfg.num_classes, dtype=torch.int32, device=self.device)
-            self.h._check(self.h.lib.ivit_vit_workspace_init(self.model, _P(ws.data_ptr()), n.value, B, nslices), "ivit_vit_workspace_init")
-            self._native_ws[key] = (ws, logits)
-        return self._native_ws[key]
-
-    def forward(self, images, nslices=1, copy=False):
-        """images: int8 device tensor [B, C, H, W] (already quantised, scale s_in) -> int32 logits
-        [B, num_classes] (head accumulators).  One native call; nslices > 1 cuts the batch into slices
-        on the runner's internal HIP streams (VALU-bound kernels of one slice share the chip with the
-        MFMA-bound GEMMs of another).  Same integers for every nslices.
-
-        The returned tensor is the engine's OWN output buffer for this (batch, nslices): the next forward /
-        graph replay of the same shape overwrites it (nothing is allocated per call).  Pass copy=True — or
-        clone it — when results of several batches are kept (an eval loop collecting logits)."""
-        assert images.dtype == torch.int8 and images.is_contiguous() and images.device == self.device
-        self.h.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-        B = images.shape[0]
-        nslices = max(1, min(int(nslices), B, self.MAX_SLICES))
-        ws, logits = self._native_buffers(B, nslices)
-        self.h._check(self.h.lib.ivit_vit_forward(self.model, _P(images.data_ptr()), B, nslices, _P(ws.data_ptr()),
-                                                  ws.numel(), _P(logits.data_ptr())), "ivit_vit_forward")
-        return logits.clone() if copy else logits
-
-    def forward_streams(self, images, nstreams=2):
-        return self.forward(images, nslices=nstreams)
-
-    def capture(self, images, nstreams=1):
-        """hipGraph of one forward on fixed buffers (ivit_vit_graph_create).  Returns a callable that
-        replays it and returns the logits tensor."""
-        B = images.shape[0]
-        nslices = max(1, min(int(nstreams), B, self.MAX_SLICES))
-        ws, logits = self._native_buffers(B, nslices)
-        if not hasattr(self, "_gstream"):
-            self._gstream = torch.cuda.Stream(self.device)
-        torch.cuda.synchronize(self.device)
-        self.h.set_stream(self._gstream.cuda_stream)
-        g = _P()
-        self.h._check(self.h.lib.ivit_vit_graph_create(self.model, _P(images.data_ptr()), B, nslices, _P(ws.data_ptr()),
-                                                       ws.numel(), _P(logits.data_ptr()), ctypes.byref(g)), "ivit_vit_graph_create")
-        # the graph replays on `ws` / `logits` / `images`: all three live as long as the replay closure does, and the
-        # workspace entry is pinned against eviction
-        self._graphs = getattr(self, "_graphs", []) + [(g, ws, logits, images)]
-        self._graph_keys = getattr(self, "_graph_keys", set()) | {(B, nslices)}
-        lib, gs, dev = self.h.lib, self._gstream, self.device
-
-        def replay(_keep=(ws, logits, images)):
-            cur = torch.cuda.current_stream(dev)
-            gs.wait_stream(cur)
-            self.h.set_stream(gs.cuda_stream)
-            self.h._check(lib.ivit_graph_launch(g), "ivit_graph_launch")
-            cur.wait_stream(gs)
-            return logits
-        return replay
 
     @classmethod
     def from_float(cls, cfg, weights, scales, device="cuda:0"):
         consts, f32 = freeze_vit(cfg, weights, scales)
         return cls(cfg, consts, f32, device)
 
-    def ptr(self, name):
-        return _P(self.blob.data_ptr() + self.table[name][0])
-
     def head_scale(self):
-        o, dt, shp = self.table["head.scale"]
-        return self.blob[o:o + 4 * shp[0]].cpu().numpy().view(np.float32).copy()
+        return self.head_scale_host()
 
     def workspace(self, B, key=None):
         wkey = (B, key)

@@ -75,29 +75,35 @@ def layernorm_constants(weight, bias):
     return bias_int, (sf * w).astype(np.float32)
 
 
+def _emitters(weights, s, c):
+    """linear(prefix, s_in, s_out_site) and norm(prefix, s_out_site) of both freezers: the constants of one QuantLinear
+    (-> QuantAct at the site s_out_site, if any; returns the bias scale) and of one IntLayerNorm -> QuantAct, written into c"""
+    def linear(prefix, s_in, s_out_site):
+        wq, s_w = quantize_weight(weights[prefix + ".weight"])
+        c[prefix + ".w"] = np.ascontiguousarray(wq.reshape(wq.shape[0], -1))
+        if prefix + ".bias" in weights:
+            c[prefix + ".b"], s_b = quantize_bias(weights[prefix + ".bias"], s_w, s_in)
+        else:                                       # Swin's PatchMerging reduction
+            s_b = (s_w * np.float32(s_in)).astype(np.float32)
+        if s_out_site is not None:
+            c[prefix + ".dy"] = dyadic(s_b, s[s_out_site])
+        return s_b
+
+    def norm(prefix, s_out_site):
+        bi, sc = layernorm_constants(weights[prefix + ".weight"], weights[prefix + ".bias"])
+        c[prefix + ".bias_int"], c[prefix + ".sc"] = bi, sc
+        c[prefix + ".dy"] = dyadic(sc, s[s_out_site])
+
+    return linear, norm
+
+
 def freeze_vit(cfg, weights, scales):
     """All integer constants of a frozen DeiT/ViT (reference models/vit_quant.py).
     Returns a flat dict name -> numpy array (int8/int32/int16/float32/float64[.,2])."""
     s = {k: np.float32(v) for k, v in scales.items()}
     D = cfg.embed_dim
     c = {}
-
-    def linear(prefix, s_in, s_out_site, store=None):
-        wq, s_w = quantize_weight(weights[prefix + ".weight"])
-        bq, s_b = quantize_bias(weights[prefix + ".bias"], s_w, s_in)
-        store = store or prefix
-        c[store + ".w"] = wq.reshape(wq.shape[0], -1)
-        c[store + ".b"] = bq
-        if s_out_site is not None:
-            c[store + ".dy"] = dyadic(s_b, s[s_out_site])
-        return s_b
-
-    def norm(prefix, s_out_site):
-        bi, sc = layernorm_constants(weights[prefix + ".weight"], weights[prefix + ".bias"])
-        c[prefix + ".bias_int"] = bi
-        c[prefix + ".sc"] = sc
-        c[prefix + ".dy"] = dyadic(sc, s[s_out_site])
-
+    linear, norm = _emitters(weights, s, c)
     linear("patch_embed.proj", s["qact_input"], "patch_embed.qact")
     cls = weights["cls_token"].reshape(-1).astype(np.float32)
     c["z_cls"] = np.rint((cls / s["patch_embed.qact"]).astype(np.float32)).astype(np.int32)
@@ -137,6 +143,90 @@ def freeze_vit(cfg, weights, scales):
     norm("norm", "qact2")
     c["head.scale"] = linear("head", s["qact2"], None)
     return c, f32
+
+
+def _rel_index(ws):
+    """relative_position_index (swin_quant.py:80-94)"""
+    coords = np.stack(np.meshgrid(np.arange(ws), np.arange(ws), indexing="ij")).reshape(2, -1)
+    rel = (coords[:, :, None] - coords[:, None, :]).transpose(1, 2, 0).copy()
+    rel[:, :, 0] += ws - 1
+    rel[:, :, 1] += ws - 1
+    rel[:, :, 0] *= 2 * ws - 1
+    return rel.sum(-1)
+
+
+def _rne_times(z, dy):
+    """rne((double(z) * m) * 2^-e) for an integer array and one dyadic pair"""
+    return np.rint(z.astype(np.float64) * dy[0, 0] * dy[0, 1])
+
+
+def freeze_swin(cfg, weights, scales, exp_tables=False):
+    """name -> numpy array / python scalar for every constant of the frozen Swin.
+    exp_tables: also build the Shiftmax tables of every layer, which routes the windowed attention to
+    ivit_window_attention_fused_lut.  Off by default: measured on MI355X the table form is not faster than the
+    arithmetic one in this kernel (profiles/README.md, round 4) — the switch keeps the path exercised by the tests."""
+    s = {k: np.float32(v) for k, v in scales.items()}
+    c = {}
+    linear, norm = _emitters(weights, s, c)
+    linear("patch_embed.proj", s["qact_input"], "patch_embed.qact_before_norm")
+    c["patch_embed.s_bn"] = s["patch_embed.qact_before_norm"]
+    norm("patch_embed.norm", "patch_embed.qact")
+    c["dy_qact1"] = dyadic(s["patch_embed.qact"], s["qact1"])
+    s_x = s["qact1"]
+    res = cfg.grid
+    for li, (depth, heads) in enumerate(zip(cfg.depths, cfg.num_heads)):
+        C = cfg.embed_dim * 2 ** li
+        dh = C // heads
+        ws = min(cfg.window_size, res)
+        for bj in range(depth):
+            p = f"layers.{li}.blocks.{bj}."
+            c[p + "s_in"] = s_x
+            norm(p + "norm1", p + "qact1")
+            linear(p + "attn.qkv", s[p + "qact1"], p + "attn.qact1")
+            s1 = s[p + "attn.qact1"]
+            s_qk = np.float32(np.float32(s1 * s1) * np.float32(dh ** -0.5))       # swin_quant.py:133-135
+            c[p + "attn.dy_qk"] = dyadic(s_qk, s[p + "attn.qact_attn1"])
+            c[p + "attn.dy_a"] = dyadic(s[p + "attn.qact_attn1"], s[p + "attn.qact2"])
+            # relative position bias: table -> 8 bit (QuantAct input branch), gathered, then its half of
+            # the identity requant of qact2 (swin_quant.py:142-149) — a constant of the layer
+            tab = quantize(weights[p + "attn.relative_position_bias_table"], s[p + "attn.qact_table"], 8, False)
+            N = ws * ws
+            bias = tab[_rel_index(ws).reshape(-1)].reshape(N, N, heads).transpose(2, 0, 1)
+            c[p + "attn.relb"] = np.ascontiguousarray(
+                _rne_times(bias, dyadic(s[p + "attn.qact_table"], s[p + "attn.qact2"]))).astype(np.int16)
+            c[p + "attn.s_softmax"] = s[p + "attn.qact2"]
+            # exp_int by table where no shift mask applies; the table form is built for window 7 only (window 12: arithmetic)
+            tabs = shiftmax_tables(s[p + "attn.qact2"]) if exp_tables and ws == 7 else None
+            if tabs is not None:                               # else: the kernel's arithmetic path for this layer
+                c[p + "attn.exp_aq"], c[p + "attn.exp_t"], c[p + "attn.exp_cls"] = tabs["aq"], tabs["t"], tabs["cls"]
+                # three small integers, carried with the fp32 host scalars (exact: t_count <= 16384)
+                c[p + "attn.exp_nc"], c[p + "attn.exp_tcount"], c[p + "attn.exp_dmin"] = tabs["NC"], tabs["t"].size, tabs["dmin"]
+            c[p + "attn.dy_pv"] = dyadic(np.float32(np.float32(2.0 ** -7) * s1), s[p + "attn.qact3"])
+            linear(p + "attn.proj", s[p + "attn.qact3"], p + "attn.qact4")
+            c[p + "res1.dy_main"] = dyadic(s[p + "attn.qact4"], s[p + "qact2"])
+            c[p + "res1.dy_res"] = dyadic(s_x, s[p + "qact2"])
+            c[p + "s_mid"] = s[p + "qact2"]
+            norm(p + "norm2", p + "qact3")
+            linear(p + "mlp.fc1", s[p + "qact3"], p + "mlp.qact_gelu")
+            c[p + "mlp.s_gelu"] = s[p + "mlp.qact_gelu"]
+            c[p + "mlp.dy_gelu"] = dyadic(np.float32(s[p + "mlp.qact_gelu"] * np.float32(2.0 ** -7)), s[p + "mlp.qact1"])
+            linear(p + "mlp.fc2", s[p + "mlp.qact1"], p + "mlp.qact2")
+            c[p + "res2.dy_main"] = dyadic(s[p + "mlp.qact2"], s[p + "qact4"])
+            c[p + "res2.dy_res"] = dyadic(s[p + "qact2"], s[p + "qact4"])
+            s_x = s[p + "qact4"]
+        if li < cfg.num_layers - 1:
+            p = f"layers.{li}.downsample."
+            c[p + "s_in"] = s_x
+            norm(p + "norm", p + "qact1")
+            linear(p + "reduction", s[p + "qact1"], p + "qact2")
+            s_x = s[p + "qact2"]
+            res //= 2
+    c["norm.s_in"] = s_x
+    norm("norm", "qact2")
+    c["dy_pool"] = dyadic(s["qact2"], s["qact3"])
+    c["pool.s_in"] = s["qact2"]
+    c["head.scale"] = linear("head", s["qact3"], None)
+    return c
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -1,0 +1,220 @@
+"""NativeEngine — what ViTEngine and SwinEngine share: one frozen model behind the C runners of csrc/ivit_model.h.
+
+The base owns the device and handle, the constants blob, the workspace cache and the four ways into a runner:
+`forward` / `capture` (ivit_<model>_forward, one C call per batch, or its hipGraph) and `predict` / `capture_predict` (the same
+with the top-k of the dequantised logits behind them, ivit_<model>_predict).  A subclass names its C prefix, builds its
+parameter structs (`_native_params`) and keeps its `forward_ops`.  torch is used for device memory and streams only.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+_P = ctypes.c_void_p
+
+
+def _ptr(t):
+    return _P(t.data_ptr())
+
+
+class ShapeCache:
+    """key -> make(*key), bounded: at most `limit` keys that are not pinned stay resident, the oldest of them leaves first;
+    a pinned key never leaves and does not count toward the limit."""
+
+    def __init__(self, make, limit=4):
+        self.make, self.limit = make, limit
+        self.items, self.pinned = {}, set()
+
+    def __contains__(self, key):
+        return key in self.items
+
+    def unpinned(self):
+        return [k for k in self.items if k not in self.pinned]
+
+    def pin(self, key):
+        self.pinned.add(key)
+
+    def get(self, key):
+        if key not in self.items:
+            free = self.unpinned()
+            if len(free) >= self.limit:
+                del self.items[free[0]]
+            self.items[key] = self.make(*key)
+        return self.items[key]
+
+
+class NativeEngine:
+    # "ivit_vit" / "ivit_swin": the entries are PREFIX + _create, _destroy, _workspace_bytes, _forward, _graph_create, _predict and
+    # _predict_graph_create
+    PREFIX = None
+    MAX_SLICES = 8
+
+    def __init__(self, cfg, device):
+        """refuses without a device; `_load` brings the constants, `_build_native` the model"""
+        self.model = None
+        if not torch.cuda.is_available():
+            raise _lib.IvitError(f"{type(self).__name__} needs a HIP device; the product path has no CPU fallback")
+        self.cfg, self.device = cfg, torch.device(device)
+        torch.cuda.set_device(self.device)
+        # a graph has its buffers baked in: the (batch, slices) shapes one refers to are pinned in the cache (_graph_keys), and
+        # _graphs keeps every graph's buffers alive
+        self._native_ws = ShapeCache(self._make_buffers)
+        self._graph_keys = self._native_ws.pinned
+        self._graphs = []
+        self._predict_out = {}
+        self._gstream = None                    # the stream graphs are captured and replayed on, made by the first capture
+        self._head_scale_host = None
+        self.last_logits = None
+
+    def _load(self, blob, table):
+        """the packed constants (host numpy blob, or a uint8 tensor from a broadcast) onto the device, and the handle on the
+        current stream"""
+        self.table = table
+        self.blob = torch.from_numpy(blob).to(self.device) if isinstance(blob, np.ndarray) else blob.to(self.device)
+        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.h = _lib.Handle(dev_index, torch.cuda.current_stream(self.device).cuda_stream)
+
+    def ptr(self, name):
+        return _P(self.blob.data_ptr() + self.table[name][0])
+
+    def head_scale_host(self):
+        """host float32 copy [num_classes] of the head's scale (the reference's head.bias_scaling_factor), read from the device
+        once; every call returns a fresh array, the caller's to change."""
+        if self._head_scale_host is None:
+            o, _, shp = self.table["head.scale"]
+            self._head_scale_host = self.blob[o:o + 4 * int(np.prod(shp))].cpu().numpy().view(np.float32).copy()
+        return self._head_scale_host.copy()
+
+    def _entry(self, suffix, *args):
+        name = self.PREFIX + suffix
+        self.h._check(getattr(self.h.lib, name)(*args), name)
+
+    def _native_params(self):
+        """(config struct, params struct, keep-alive) of PREFIX_create"""
+        raise NotImplementedError
+
+    def _build_native(self):
+        """PREFIX_create: hand the runner device pointers into the blob + host scalars."""
+        c, prm, self._native_keep = self._native_params()
+        model = _P()
+        self._entry("_create", self.h.h, ctypes.byref(c), ctypes.byref(prm), self.MAX_SLICES, ctypes.byref(model))
+        self.model = model
+
+    def __del__(self):
+        try:
+            if self.model:
+                getattr(self.h.lib, self.PREFIX + "_destroy")(self.model)
+                self.model = None
+        except Exception:
+            pass
+
+    def _workspace_init(self, ws, B, nslices):
+        """what a fresh workspace needs before its first forward: nothing, unless the subclass says"""
+
+    def _make_buffers(self, B, nslices):
+        n = ctypes.c_size_t()
+        self._entry("_workspace_bytes", self.model, B, nslices, ctypes.byref(n))
+        ws = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+        logits = torch.empty(B, self.cfg.num_classes, dtype=torch.int32, device=self.device)
+        self._workspace_init(ws, B, nslices)
+        return ws, logits
+
+    def _native_buffers(self, B, nslices):
+        """(workspace, logits) of one (batch, slices), the engine's own: see ShapeCache"""
+        return self._native_ws.get((B, nslices))
+
+    def _predict_buffers(self, logits, key):
+        """(idx, val) of one (batch, slices, k): they live beside the logits buffer and follow its rule — the engine's own,
+        overwritten by the next call of the same shape, pinned while a captured graph refers to them"""
+        outs = self._predict_out
+        hit = outs.get(key)
+        if hit is None or hit[0] is not logits:          # first use, or the logits buffer of this shape was evicted and rebuilt
+            for old in [q for q, v in outs.items() if not v[3] and q[:2] not in self._native_ws]:
+                del outs[old]
+            hit = outs[key] = [logits, torch.empty(key[0], key[2], dtype=torch.int32, device=self.device),
+                               torch.empty(key[0], key[2], dtype=torch.float32, device=self.device), False]
+        return hit[1], hit[2]
+
+    def _check_images(self, images):
+        assert images.dtype == torch.int8 and images.is_contiguous() and images.device == self.device
+
+    def _use_current_stream(self):
+        self.h.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _args(self, images, nslices, k=None):
+        """(arguments of the forward entries — of the predict entries with k —, cache key, buffers) for one batch"""
+        B = images.shape[0]
+        nslices = max(1, min(int(nslices), B, self.MAX_SLICES))
+        ws, logits = bufs = self._native_buffers(B, nslices)
+        args = (self.model, _ptr(images), B, nslices, _ptr(ws), ws.numel(), _ptr(logits))
+        if k is None:
+            return args, (B, nslices), bufs
+        idx, val = self._predict_buffers(logits, (B, nslices, int(k)))
+        return args + (self.ptr("head.scale"), int(k), _ptr(idx), _ptr(val)), (B, nslices, int(k)), bufs + (idx, val)
+
+    def forward(self, images, nslices=1, copy=False):
+        """images: int8 device tensor [B, C, H, W] (already quantised, scale s_in) -> int32 logits
+        [B, num_classes] (head accumulators).  One native call; nslices > 1 cuts the batch into slices
+        on the runner's internal HIP streams (VALU-bound kernels of one slice share the chip with the
+        MFMA-bound GEMMs of another).  Same integers for every nslices.
+
+        The returned tensor is the engine's OWN output buffer for this (batch, nslices): the next forward /
+        graph replay of the same shape overwrites it (nothing is allocated per call).  Pass copy=True — or
+        clone it — when results of several batches are kept (an eval loop collecting logits)."""
+        self._check_images(images)
+        self._use_current_stream()
+        args, _, (_, logits) = self._args(images, nslices)
+        self._entry("_forward", *args)
+        return logits.clone() if copy else logits
+
+    def predict(self, images, k=5, nslices=1, copy=False):
+        """images int8 [B, C, H, W] -> (idx int32 [B, k], val float32 [B, k]) device tensors: the k best classes of every image in
+        the order of `predict.topk_reference`, and their dequantised head outputs.  One native call (the forward, then the top-k
+        launch behind the slices' join); the head scale is read where it lies in the constants blob.  The int32 logits of the same
+        call are in `last_logits`.  Like forward(), the results are the engine's own buffers for this (batch, nslices, k):
+        copy=True (or clone) to keep them across calls.  1 <= k <= min(16, num_classes)."""
+        self._use_current_stream()
+        self._check_images(images)
+        args, _, (_, logits, idx, val) = self._args(images, nslices, k)
+        self._entry("_predict", *args)
+        self.last_logits = logits
+        return (idx.clone(), val.clone()) if copy else (idx, val)
+
+    def _capture(self, suffix, images, args, key, bufs, out):
+        """hipGraph of the entry PREFIX + suffix on fixed buffers; returns a callable that replays it and returns `out`"""
+        if self._gstream is None:
+            self._gstream = torch.cuda.Stream(self.device)
+        torch.cuda.synchronize(self.device)
+        self.h.set_stream(self._gstream.cuda_stream)
+        g = _P()
+        self._entry(suffix, *args, ctypes.byref(g))
+        # the graph replays on its buffers and on `images`: all live as long as the replay closure does, and the workspace
+        # entry is pinned against eviction
+        self._graphs.append((g,) + bufs + (images,))
+        self._native_ws.pin(key[:2])
+        lib, gs, dev = self.h.lib, self._gstream, self.device
+
+        def replay(_keep=bufs + (images,)):
+            cur = torch.cuda.current_stream(dev)
+            gs.wait_stream(cur)
+            self.h.set_stream(gs.cuda_stream)
+            self.h._check(lib.ivit_graph_launch(g), "ivit_graph_launch")
+            cur.wait_stream(gs)
+            return out
+        return replay
+
+    def capture(self, images, nstreams=1):
+        """hipGraph of one forward on fixed buffers (PREFIX_graph_create).  Returns a callable that
+        replays it and returns the logits tensor."""
+        args, key, bufs = self._args(images, nstreams)
+        return self._capture("_graph_create", images, args, key, bufs, bufs[1])
+
+    def capture_predict(self, images, k=5, nstreams=1):
+        """hipGraph of one predict on fixed buffers; returns a callable that replays it and returns (idx, val)."""
+        self._check_images(images)
+        args, key, bufs = self._args(images, nstreams, k)
+        replay = self._capture("_predict_graph_create", images, args, key, bufs, bufs[2:])
+        self._predict_out[key][3] = True
+        return replay
