@@ -60,6 +60,10 @@ struct ivit_device_guard {
 };
 #define CHECK_H(h) if (!(h)) return IVIT_ERR_INVALID; ivit_device_guard ivit_dev_guard_; if (!ivit_dev_guard_.enter((h)->device)) return IVIT_ERR_HIP
 #define REQUIRE(h, cond, msg) do { if (!(cond)) { snprintf((h)->err, sizeof((h)->err), "%s: %s", __func__, msg); return IVIT_ERR_INVALID; } } while (0)
+// An activation or output pointer that a kernel touches through vector accesses wider than its element (include/ivit.h, Conventions):
+// refused unless aligned to that width, before anything is launched.  `name` is the argument as the header spells it.
+#define REQUIRE_ALIGNED(h, p, name, bytes) REQUIRE(h, ((uintptr_t)(p) & ((bytes) - 1)) == 0, name " must be " #bytes "-byte aligned")
+#define REQUIRE_A16(h, p, name) REQUIRE_ALIGNED(h, p, name, 16)
 #define LAUNCH_CHECK(h) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { snprintf((h)->err, sizeof((h)->err), "%s: %s", __func__, hipGetErrorString(e_)); return IVIT_ERR_HIP; } } while (0)
 
 // Launch `Kernel` with `lds` bytes of dynamic LDS.  Above 64 KB a launch needs hipFuncAttributeMaxDynamicSharedMemorySize: set once
@@ -167,6 +171,8 @@ static inline int grid_for(ivit_handle h, long long work_items, int per_block) {
 int ivit_quantize_input_f32(ivit_handle h, const float *x, float scale, int8_t *q, int64_t n) {
     CHECK_H(h);
     REQUIRE(h, x && q && n >= 0 && scale > 0.f, "bad arguments");
+    REQUIRE_A16(h, x, "x");                 // four floats per load, four packed bytes per store
+    REQUIRE_ALIGNED(h, q, "q", 4);
     if (n == 0) return IVIT_OK;
     quantize_input_kernel<<<grid_for(h, n, 1024), 256, 0, h->stream>>>(x, scale, q, n);
     LAUNCH_CHECK(h);
@@ -282,6 +288,7 @@ int ivit_linear_i8(ivit_handle h, const int8_t *x, const int8_t *w, const int32_
     CHECK_H(h);
     REQUIRE(h, x && w && acc && M > 0 && N > 0 && K > 0, "bad arguments");
     REQUIRE(h, (K % 16) == 0, "K must be a multiple of 16");
+    REQUIRE_A16(h, x, "x");                 // acc: 32-bit scalar stores (gemm_nt_kernel, EPI_RAW32)
     GemmArgs a = linear_args(x, w, bias, M, N, K);
     a.out = acc;
     return launch_gemm<false, EPI_RAW32>(h, a, 1);
@@ -293,6 +300,8 @@ int ivit_linear_i8_requant(ivit_handle h, const int8_t *x, const int8_t *w, cons
     REQUIRE(h, x && w && out && dy_ch && M > 0 && N > 0 && K > 0, "bad arguments");
     REQUIRE(h, (K % 16) == 0, "K must be a multiple of 16");
     REQUIRE(h, bits == 8 || bits == 16, "bits must be 8 or 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, out, "out");
     GemmArgs a = linear_args(x, w, bias, M, N, K);
     a.out = out; a.dy_ch = dy_ch;
     if (const int nct = wreg_nct(a)) return bits == 8 ? launch_wreg<EPI_RQ8_CH>(h, a, nct) : launch_wreg<EPI_RQ16_CH>(h, a, nct);
@@ -307,6 +316,8 @@ int ivit_linear_i8_requant8_store16(ivit_handle h, const int8_t *x, const int8_t
     CHECK_H(h);
     REQUIRE(h, x && w && out && dy_ch && M > 0 && N > 0 && K > 0, "bad arguments");
     REQUIRE(h, (K % 16) == 0, "K must be a multiple of 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, out, "out16");
     GemmArgs a = linear_args(x, w, bias, M, N, K);
     a.out = out; a.dy_ch = dy_ch;
     if (wreg_nct(a) || !use_gemm2(a)) {
@@ -322,6 +333,9 @@ int ivit_linear_i8_requant_residual(ivit_handle h, const int8_t *x, const int8_t
     CHECK_H(h);
     REQUIRE(h, x && w && out && dy_ch && residual && M > 0 && N > 0 && K > 0, "bad arguments");
     REQUIRE(h, (K % 16) == 0, "K must be a multiple of 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, residual, "residual");
+    REQUIRE_A16(h, out, "out");
     GemmArgs a = linear_args(x, w, bias, M, N, K);
     a.out = out; a.dy_ch = dy_ch; a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual;
     if (const int nct = wreg_nct(a)) return launch_wreg<EPI_RQ16_CH_RES>(h, a, nct);
@@ -335,6 +349,10 @@ int ivit_linear_i8_qkv(ivit_handle h, const int8_t *x, const int8_t *w, const in
     CHECK_H(h);
     REQUIRE(h, x && w && dy_ch && q && k && vt && B > 0 && T > 0 && H > 0 && dh > 0, "bad arguments");
     REQUIRE(h, (dh % 16) == 0, "head dim must be a multiple of 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, q, "q");
+    REQUIRE_A16(h, k, "k");
+    REQUIRE_A16(h, vt, "vt");
     REQUIRE(h, ldv == 0 || ldv >= T, "ldv < T (0 = v row-major [B*H, T, dh])");
     const int D = H * dh;
     GemmArgs a = linear_args(x, w, bias, B * T, 3 * D, D);
@@ -351,6 +369,8 @@ int ivit_bmm_nt_i8(ivit_handle h, const int8_t *A, const int8_t *B, int32_t *C, 
     REQUIRE(h, A && B && C && nb > 0 && M > 0 && N > 0 && K > 0, "bad arguments");
     REQUIRE(h, (lda % 16) == 0 && (ldb % 16) == 0 && (strideA % 16) == 0 && (strideB % 16) == 0,
             "lda/ldb/strides must be multiples of 16");
+    REQUIRE_A16(h, A, "A");                 // C: 32-bit scalar stores (gemm_nt_kernel, EPI_RAW32)
+    REQUIRE_A16(h, B, "B");
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
@@ -364,6 +384,8 @@ int ivit_bmm_nt_u16i8(ivit_handle h, const uint16_t *A, const int8_t *B, int32_t
     REQUIRE(h, A && B && C && nb > 0 && M > 0 && N > 0 && K > 0, "bad arguments");
     REQUIRE(h, (lda % 8) == 0 && (ldb % 16) == 0 && (strideA % 8) == 0 && (strideB % 16) == 0,
             "lda must be a multiple of 8, ldb of 16");
+    REQUIRE_A16(h, A, "A");
+    REQUIRE_A16(h, B, "B");
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
@@ -376,6 +398,9 @@ int ivit_attn_qk_requant(ivit_handle h, const int8_t *q, const int8_t *k, ivit_d
     CHECK_H(h);
     REQUIRE(h, q && k && scores8 && BH > 0 && T > 0 && dh > 0, "bad arguments");
     REQUIRE(h, (dh % 16) == 0 && lds >= T, "dh %16, lds >= T");
+    REQUIRE_A16(h, q, "q");
+    REQUIRE_A16(h, k, "k");
+    REQUIRE_A16(h, scores8, "scores8");
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = q; a.B = k; a.M = T; a.N = T; a.K = dh; a.lda = dh; a.ldb = dh; a.ldc = lds;
@@ -389,6 +414,9 @@ int ivit_attn_pv_requant(ivit_handle h, const uint16_t *p, const int8_t *vt, ivi
     CHECK_H(h);
     REQUIRE(h, p && vt && ctx8 && B > 0 && H > 0 && T > 0 && dh > 0, "bad arguments");
     REQUIRE(h, (ldp % 8) == 0 && (ldv % 16) == 0 && ldp >= T && ldv >= T, "ldp %8, ldv %16, >= T");
+    REQUIRE_A16(h, p, "p");
+    REQUIRE_A16(h, vt, "vt");
+    REQUIRE_A16(h, ctx8, "ctx8");
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = p; a.B = vt; a.M = T; a.N = dh; a.K = T; a.lda = ldp; a.ldb = ldv; a.ldc = H * dh;
@@ -700,6 +728,8 @@ int ivit_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan pl, const int
     CHECK_H(h);
     REQUIRE(h, pl && x && out && M > 0, "bad arguments");
     REQUIRE(h, bits == 8 || bits == 16, "bits must be 8 or 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, out, "out");
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy;
     if (bits == 8 && ws_plan_ok(pl, M))      // prepared plan: tokens of a CU in LDS, weight slabs in registers
@@ -712,6 +742,8 @@ int ivit_layernorm_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan pl,
                                              const float *sc, const ivit_dyadic *ln_dy, int8_t *out8, int M) {
     CHECK_H(h);
     REQUIRE(h, pl && x16 && bias_int && sc && ln_dy && out8 && M > 0, "bad arguments");
+    REQUIRE_A16(h, x16, "x16");
+    REQUIRE_A16(h, out8, "out8");
     if (!ws_plan_ok(pl, M)) {
         snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 192 or 384 plan", __func__);
         return IVIT_ERR_UNSUPPORTED;
@@ -723,6 +755,9 @@ int ivit_linear_i8_requant_residual_planned(ivit_handle h, ivit_linear_plan pl, 
                                             ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int M) {
     CHECK_H(h);
     REQUIRE(h, pl && x && out && residual && M > 0, "bad arguments");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, residual, "residual");
+    REQUIRE_A16(h, out, "out");
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy; a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual;
     const bool res_fast = rq_fast2(dy_main, dy_res);
@@ -737,6 +772,10 @@ int ivit_linear_i8_requant_residual_layernorm_planned(ivit_handle h, ivit_linear
                                                       int8_t *ln_out8) {
     CHECK_H(h);
     REQUIRE(h, pl && x && out && residual && M > 0 && ln_bias_int && ln_sc && ln_dy && ln_out8, "bad arguments");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, residual, "residual");
+    REQUIRE_A16(h, out, "out");
+    REQUIRE_A16(h, ln_out8, "ln_out8");
     if (!(pl->wf && rq_fast2(dy_main, dy_res) && pl->K == Ws384Geo::K && pl->N == Ws384Geo::K && M < (1 << 26))) {
         snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a 384 x 384 plan and residual multipliers in the fast range", __func__);
         return IVIT_ERR_UNSUPPORTED;
@@ -749,6 +788,10 @@ int ivit_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, const int8_t 
     CHECK_H(h);
     REQUIRE(h, pl && x && q && k && vt && B > 0 && T > 0 && H > 0 && dh > 0, "bad arguments");
     REQUIRE(h, (dh % 16) == 0, "head dim must be a multiple of 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, q, "q");
+    REQUIRE_A16(h, k, "k");
+    REQUIRE_A16(h, vt, "vt");
     REQUIRE(h, ldv == 0 || ldv >= T, "ldv < T (0 = v row-major [B*H, T, dh])");
     const int D = H * dh;
     REQUIRE(h, pl->N == 3 * D && pl->K == D, "plan shape is not [3*H*dh, H*dh]");
@@ -791,6 +834,10 @@ int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan pl,
                                              int H, int dh, int ldv) {
     CHECK_H(h);
     REQUIRE(h, pl && x16 && bias_int && sc && ln_dy && q && k && vt && B > 0 && T > 0 && H > 0 && dh > 0, "bad arguments");
+    REQUIRE_A16(h, x16, "x16");
+    REQUIRE_A16(h, q, "q");
+    REQUIRE_A16(h, k, "k");
+    REQUIRE_A16(h, vt, "vt");
     REQUIRE(h, pl->N == 3 * H * dh && pl->K == H * dh, "plan shape is not [3*H*dh, H*dh]");
     REQUIRE(h, ldv == 0 || (ldv >= T && ldv % 16 == 0), "ldv: 0 (v row-major [B*H, T, dh]) or a multiple of 16 >= T (v^T)");
     if (!qkv_ws_ok(pl, B, T, H, dh, ldv)) {
@@ -976,9 +1023,11 @@ static int mlp128_launch(ivit_handle h, const int8_t *x, const int8_t *w1, const
         snprintf(h->err, sizeof(h->err), "ivit_mlp_fused: residual multipliers out of the fast range at C = 128");
         return IVIT_ERR_UNSUPPORTED;
     }
-    REQUIRE(h, (((uintptr_t)x | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)dy1 | (uintptr_t)dy2 | (uintptr_t)b1 | (uintptr_t)b2) & 15) == 0 &&
-                   (((uintptr_t)residual | (uintptr_t)out) & 7) == 0,
-            "C = 128: x, w1, w2, b1, b2, dy1, dy2 must be 16-byte aligned, residual and out 8-byte aligned");
+    REQUIRE(h, (((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)dy1 | (uintptr_t)dy2 | (uintptr_t)b1 | (uintptr_t)b2) & 15) == 0,
+            "C = 128: w1, w2, b1, b2, dy1, dy2 must be 16-byte aligned");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_ALIGNED(h, residual, "residual", 8);
+    REQUIRE_ALIGNED(h, out, "out", 8);
     const long long ntiles = (M + 15) / 16, slots = (long long)Mlp128Geo::WG_PER_CU * persistent_cus(h);
     if (int st = launch_dyn<mlp128_kernel>(h, (unsigned)(ntiles < slots ? ntiles : slots), Mlp128Geo::THREADS, Mlp128Geo::SMEM, a)) return st;
     LAUNCH_CHECK(h);
@@ -989,6 +1038,9 @@ int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, cons
                            ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M) {
     CHECK_H(h);
     REQUIRE(h, p && x && gelu_table && residual && out && M > 0, "bad arguments");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, residual, "residual");
+    REQUIRE_A16(h, out, "out");
     return mlp_fused_launch(h, p, x, gelu_table, dy_main, dy_res, residual, out, M, 0.f, nullptr, nullptr, nullptr);
 }
 
@@ -997,6 +1049,9 @@ int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16
                                      ivit_dyadic dy_res, int16_t *out, int64_t M) {
     CHECK_H(h);
     REQUIRE(h, p && x16 && bias_int && sc && ln_dy && scratch8 && gelu_table && out && M > 0, "bad arguments");
+    REQUIRE_A16(h, x16, "x16");
+    REQUIRE_A16(h, scratch8, "scratch8");
+    REQUIRE_A16(h, out, "out");
     if (p->width != MLP_C) {
         snprintf(h->err, sizeof(h->err), "%s: the LayerNorm prologue exists at width 384 only", __func__);      // not at 192, not at 256
         return IVIT_ERR_UNSUPPORTED;
@@ -1009,6 +1064,8 @@ int ivit_layernorm_mlp_lockstep_planned(ivit_handle h, ivit_mlp_plan p, const in
                                         int16_t *out, int64_t M) {
     CHECK_H(h);
     REQUIRE(h, p && x16 && bias_int && sc && ln_dy && gelu_table && out && M > 0, "bad arguments");
+    REQUIRE_A16(h, x16, "x16");
+    REQUIRE_A16(h, out, "out");
     // every row of x16 is read twice, by different lanes at different times (LayerNorm one unit ahead, the identity branch in fc2's
     // epilogue), and rows past M - 1 of a tile are row M - 1 again: in place is not a form this launch has
     REQUIRE(h, out + (size_t)M * p->width <= x16 || x16 + (size_t)M * p->width <= out, "out must not overlap x16 (LayerNorm input and identity branch)");
@@ -1069,6 +1126,10 @@ static int attention_fused_impl(ivit_handle h, const int8_t *q, const int8_t *k,
     REQUIRE(h, q && k && vt && ctx8 && B > 0 && H > 0 && T > 0 && s_softmax > 0.f, "bad arguments");
     REQUIRE(h, (x16 == nullptr) == (x_cls == nullptr) && (cls_out || !x16), "x16 and x_cls go together (both null: no identity rows)");
     REQUIRE(h, !cls_out || (((uintptr_t)x16 | (uintptr_t)x_cls | (uintptr_t)ctx8) & 15) == 0, "ctx_cls, x16 and x_cls must be 16-byte aligned");
+    REQUIRE_A16(h, q, "q");
+    REQUIRE_A16(h, k, "k");
+    REQUIRE_A16(h, vt, "vt");
+    REQUIRE_A16(h, ctx8, "ctx8");
     REQUIRE(h, ((ldv % 16) == 0 && ldv >= T) || (ldv == 0 && rowtab), "ldv must be a multiple of 16 and >= T (0 = v row-major: ivit_attention_fused_rowlut only)");
     if (dh != 64 || T > 640) {
         snprintf(h->err, sizeof(h->err), "ivit_attention_fused: built for dh == 64, T <= 640");
@@ -1211,7 +1272,9 @@ template <typename ZT>
 static int requant_any(ivit_handle h, const ZT *z, const ivit_dyadic *dy, int nch, const int32_t *z_id,
                        const ivit_dyadic *dy_id, int bits, void *out, int64_t rows, int C) {
     const long long total = (long long)rows * C;
-    if ((C % 8) == 0 && nch == 1) {   // per-channel tables keep the element-per-lane form (coalesced constant loads)
+    // per-channel tables keep the element-per-lane form (coalesced constant loads), and so does an output that is not 16-byte aligned:
+    // requant_vec8_kernel stores 8 (8-bit) or 16 (16-bit) bytes at once, requant_kernel one element.  Same integers
+    if ((C % 8) == 0 && nch == 1 && ((uintptr_t)out & 15) == 0) {
         const int g8 = grid_for(h, total / 8, 256 * 2);
         if (bits == 8) requant_vec8_kernel<ZT, 8><<<g8, 256, 0, h->stream>>>(z, dy, nch, z_id, dy_id, out, total / 8, C / 8);
         else if (bits == 16) requant_vec8_kernel<ZT, 16><<<g8, 256, 0, h->stream>>>(z, dy, nch, z_id, dy_id, out, total / 8, C / 8);
@@ -1321,6 +1384,8 @@ int ivit_shiftgelu(ivit_handle h, const int8_t *x, int64_t rows, int C, float sc
     CHECK_H(h);
     REQUIRE(h, x && out16 && rows > 0 && C > 0 && scale > 0.f, "bad arguments");
     REQUIRE(h, (C % 16) == 0, "C must be a multiple of 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, out16, "out16");
     int lo, hi;
     shiftgelu_product_range(scale, &lo, &hi);
     if (lo < -32768 || hi > 32767) {
@@ -1340,6 +1405,8 @@ int ivit_shiftgelu_requant(ivit_handle h, const int8_t *x, int64_t rows, int C, 
     CHECK_H(h);
     REQUIRE(h, x && out8 && rows > 0 && C > 0 && scale > 0.f, "bad arguments");
     REQUIRE(h, (C % 16) == 0, "C must be a multiple of 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, out8, "out8");
     shiftgelu_kernel<true><<<(unsigned)((rows + 3) / 4), 256, 0, h->stream>>>(x, rows, C, scale, dy, out8);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1358,6 +1425,8 @@ int ivit_shiftgelu_requant_lut(ivit_handle h, const int8_t *x, int64_t rows, int
     CHECK_H(h);
     REQUIRE(h, x && out8 && table && rows > 0 && C > 0, "bad arguments");
     REQUIRE(h, (C % 16) == 0, "C must be a multiple of 16");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, out8, "out8");
     // half a wavefront per row, row in registers: ITER = ceil(C / 512) chunks of 16 bytes per lane
     constexpr bool lut_old = false;
     const int iter = (C / 16 + 31) / 32;
@@ -1377,6 +1446,8 @@ int ivit_layernorm(ivit_handle h, const int16_t *x, int64_t rows, int C, float s
     CHECK_H(h);
     REQUIRE(h, x && bias_int && sc && z && rows > 0 && C > 0 && scale > 0.f, "bad arguments");
     REQUIRE(h, (C % 8) == 0, "C must be a multiple of 8");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, z, "z");
     const size_t lds = (size_t)8 * C * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
     if (int st = launch_dyn<layernorm_kernel<false>>(h, (unsigned)((rows + 7) / 8), 256, lds, x, rows, C, C, scale, bias_int, sc, nullptr, z)) return st;
@@ -1399,6 +1470,8 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
     CHECK_H(h);
     REQUIRE(h, x && bias_int && sc && dy_ch && out8 && rows > 0 && C > 0 && scale > 0.f, "bad arguments");
     REQUIRE(h, (C % 8) == 0 && (row_stride % 8) == 0 && row_stride >= C, "C, row_stride multiples of 8");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, out8, "out8");
     {   // production form: the row in registers, 4 S lanes per row (ivit_layernorm.h)
 #define LNR(CC, S) LNR_LAUNCH(CC, S, false, row_stride, 0)
         switch (C) {
@@ -1442,6 +1515,8 @@ int ivit_patch_merge_layernorm_requant(ivit_handle h, const int16_t *x, int B, i
                                        const float *sc, const ivit_dyadic *dy_ch, int8_t *out8) {
     CHECK_H(h);
     REQUIRE(h, x && bias_int && sc && dy_ch && out8 && B > 0 && R > 0 && (R % 2) == 0 && C > 0 && scale > 0.f, "bad arguments");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, out8, "out8");
     const long long rows = (long long)B * (R / 2) * (R / 2);
 #define LNM(CC, S) LNR_LAUNCH(CC, S, true, 0, R)
     switch (4 * C) {
@@ -1590,6 +1665,8 @@ int ivit_im2col_patch(ivit_handle h, const int8_t *img, int B, int Cin, int H, i
     CHECK_H(h);
     REQUIRE(h, img && rows && B > 0 && Cin > 0 && P > 0, "bad arguments");
     REQUIRE(h, (H % P) == 0 && (W % P) == 0 && (P % 4) == 0 && (W % 4) == 0, "H,W multiples of P; P,W multiples of 4");
+    REQUIRE_A16(h, img, "img");
+    REQUIRE_A16(h, rows, "rows");
     const size_t lds = (size_t)Cin * P * W;
     REQUIRE(h, lds <= 64 * 1024, "patch strip too large for LDS staging");
     if (P == 16 && Cin == 3 && (W % 16) == 0 && B <= 65535)
@@ -1605,6 +1682,8 @@ int ivit_embed_finish(ivit_handle h, const int16_t *patch16, const int32_t *z_cl
     CHECK_H(h);
     REQUIRE(h, patch16 && z_cls && pos && x16 && B > 0 && T > 1 && D > 0 && (D % 8) == 0, "bad arguments (D must be a multiple of 8)");
     REQUIRE(h, (long long)T * D / 8 < (1 << 22) && B <= 65535, "T * D / 8 < 2^22, B < 2^16");
+    REQUIRE_A16(h, patch16, "patch16");
+    REQUIRE_A16(h, x16, "x16");
     const int fast = rq_fast2(dy_x, dy_pos);
     embed_finish_kernel<<<dim3((unsigned)((T * (D / 8) + 255) / 256), (unsigned)B), 256, 0, h->stream>>>(
         patch16, z_cls, pos, dy_x, dy_pos, x16, T, D, 1.0f / (float)(D / 8), fast);
@@ -1617,6 +1696,8 @@ int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int C, int H, i
                      int16_t *x16, int D) {
     CHECK_H(h);
     REQUIRE(h, images && w && dy_ch && z_cls && pos && x16 && B > 0 && C > 0 && H > 0 && W > 0 && P > 0 && D > 0, "bad arguments");
+    REQUIRE_A16(h, images, "images");
+    REQUIRE_A16(h, x16, "x16");
     const int gh = H / P, gw = W / P, np = gh * gw, K = C * P * P, T = np + 1;
     const bool fast = rq_fast2(dy_x, dy_pos);
     GemmArgs a = linear_args(images, w, bias, B * np, D, K);
@@ -1681,6 +1762,8 @@ static int window_attention_impl(ivit_handle h, const int8_t *qkv, ivit_dyadic d
                                  int window, int shift, int heads, int dh) {
     CHECK_H(h);
     REQUIRE(h, qkv && relb && ctx && B > 0 && R > 0 && heads > 0, "bad arguments");
+    REQUIRE_A16(h, qkv, "qkv");
+    REQUIRE_A16(h, ctx, "ctx");
     if (window == 12) return window_attention12_launch(h, qkv, dy_qk, dy_a, relb, s_softmax, aq != nullptr, dy_pv, ctx, B, R,
                                                        shift, heads, dh);
     if (window != 7 || dh != 32 || (R % 7) != 0) {
@@ -1748,6 +1831,9 @@ int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32
                  __func__);
         return IVIT_ERR_UNSUPPORTED;
     }
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, residual, "residual");
+    REQUIRE_A16(h, out, "out");
     MlpFusedArgs a;
     a.x = x; a.w1 = w1; a.b1 = b1; a.dy1 = dy1; a.tab = gelu_table; a.w2 = w2; a.b2 = b2; a.dy2 = dy2;
     a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual; a.out = out; a.M = M;
@@ -1766,6 +1852,9 @@ int ivit_patch_merge_gather(ivit_handle h, const void *x, int in_bits, int B, in
     CHECK_H(h);
     REQUIRE(h, x && out && B > 0 && R > 0 && (R % 2) == 0 && C > 0 && (C % 8) == 0, "bad arguments (C must be a multiple of 8)");
     REQUIRE(h, in_bits == 8 || in_bits == 16, "in_bits must be 8 or 16");
+    if (in_bits == 16) REQUIRE_A16(h, x, "x");
+    else REQUIRE_ALIGNED(h, x, "x", 8);
+    REQUIRE_A16(h, out, "out");
     const long long total = (long long)B * R * R * C / 8;
     if (in_bits == 8) patch_merge_gather_kernel<int8_t><<<grid_for(h, total, 1024), 256, 0, h->stream>>>((const int8_t *)x, B, R, C, out);
     else patch_merge_gather_kernel<int16_t><<<grid_for(h, total, 1024), 256, 0, h->stream>>>((const int16_t *)x, B, R, C, out);

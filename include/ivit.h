@@ -14,6 +14,13 @@
  *   - every call is asynchronous on the handle's HIP stream, allocates nothing,
  *     synchronises nothing and is hipGraph-capturable;
  *   - return value: IVIT_OK or an error code (no exceptions, no aborts);
+ *   - alignment: an activation or output pointer that a kernel touches through vector accesses wider than its element must be
+ *     aligned to that width, 16 bytes unless stated: a misaligned one is refused with IVIT_ERR_INVALID before anything is
+ *     launched, and ivit_last_error names the argument.  The "Alignment:" line in front of an entry lists the pointers this
+ *     applies to; an activation or output pointer it does not list (and every one of an entry without such a line) takes any
+ *     address aligned to its element — a row sub-view with an odd pitch, a slice of a batch.  Weights, biases, dyadic tables,
+ *     LayerNorm constants and Shiftmax tables are read in 16-byte pieces throughout: keep them 16-byte aligned (a
+ *     256-byte-aligned constants blob does);
  *   - activations are carried as INTEGERS plus an fp32 scale held by the caller
  *     (the reference carries fp32 "integer*scale" tensors; X = fl(Q*s) is
  *     re-derived inside the kernels where its rounding matters).
@@ -93,6 +100,7 @@ const char *ivit_last_error(ivit_handle h);
 
 /* ---- a4  QuantAct.forward, input branch  (quant_modules.py:194-196 ->
  * quant_utils.py:77-96, 12-48):  q = clamp(rne(fl(fl(1/s)*x)), -128, 127)            */
+/* Alignment: x 16-byte aligned, q 4-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_quantize_input_f32(ivit_handle h, const float *x, float scale, int8_t *q, int64_t n);
 /* ToTensor -> Normalize(mean, std) -> the same input QuantAct, from uint8 pixels on the device
  * (utils/data_utils.py:89-91: transforms.ToTensor, transforms.Normalize; then vit_quant.py:257):
@@ -111,17 +119,20 @@ int ivit_resize_center_crop_u8(ivit_handle h, const uint8_t *hwc, int B, int H0,
 
 /* ---- a1  QuantLinear.forward  (quant_modules.py:67-97) — integer accumulators.
  * acc[i,j] = sum_k x[i,k]*w[j,k] + bias[j];  x int8 [M,K], w int8 [N,K], K % 16 == 0. */
+/* Alignment: x 16-byte aligned; acc takes any int32 address (a slice of a batch's logits); IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias,
                    int32_t *acc, int M, int N, int K);
 
 /* a1 + a3: the QuantLinear -> QuantAct pairs of the reference, fused.
  * out = clamp_bits(rq(acc[i,j], dy_ch[j]));  bits = 8 (int8 out) or 16 (int16 out).    */
+/* Alignment: x and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8_requant(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias,
                            const ivit_dyadic *dy_ch, int bits, void *out, int M, int N, int K);
 
 /* a1 + a3 + a3(identity): proj/fc2 -> QuantAct(16) -> Block.qact2/qact4 residual add
  * (vit_quant.py:84-85,135,141; layers_quant.py:150-151):
  * t = clamp16(rq(acc, dy_ch[j])); out = clamp16(rq(t, dy_main) + rq(residual, dy_res)). */
+/* Alignment: x, residual and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8_requant_residual(ivit_handle h, const int8_t *x, const int8_t *w,
                                     const int32_t *bias, const ivit_dyadic *dy_ch,
                                     ivit_dyadic dy_main, ivit_dyadic dy_res,
@@ -130,7 +141,10 @@ int ivit_linear_i8_requant_residual(ivit_handle h, const int8_t *x, const int8_t
 /* a1 + a3 + head split (vit_quant.py:61-69): qkv Linear -> QuantAct(8) -> q,k as
  * [B,H,T,dh] and v TRANSPOSED as [B,H,dh,ldv] (token dim contiguous, ldv % 16 == 0,
  * ldv >= T) — the layout the MFMA attn·v operand wants.  x is [B*T, D], w [3D, D].
- * ldv == 0 (round 6): v ROW-major [B,H,T,dh] like q and k, for ivit_attention_fused_rowlut(ldv = 0). */
+ * ldv == 0 (round 6): v ROW-major [B,H,T,dh] like q and k, for ivit_attention_fused_rowlut(ldv = 0).
+ * Columns t >= T of v^T are not written (by the _planned form neither), and no entry that takes v^T or a padded uint16 p
+ * (ivit_bmm_nt_u16i8, ivit_attn_pv_requant, ivit_attention_fused*) reads them: they need not be zero. */
+/* Alignment: x, q, k and vt 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8_qkv(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias,
                        const ivit_dyadic *dy_ch, int8_t *q, int8_t *k, int8_t *vt, int B, int T,
                        int H, int dh, int ldv);
@@ -159,9 +173,12 @@ int ivit_linear_plan_create(ivit_handle h, const int8_t *w, const int32_t *bias,
 int ivit_linear_plan_destroy(ivit_linear_plan p);
 /* pipelined_ok: the persistent kernel may be used; single_fma_ok: its one-FMA requant form is exact.        */
 int ivit_linear_plan_query(ivit_linear_plan p, int *pipelined_ok, int *single_fma_ok);
+/* Alignment: x and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, int bits, void *out, int M);
+/* Alignment: x, residual and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8_requant_residual_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, ivit_dyadic dy_main,
                                             ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int M);
+/* Alignment: x, q, k and vt 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, int8_t *q, int8_t *k, int8_t *vt,
                                int B, int T, int H, int dh, int ldv);
 /* Round 6: K = 384 layers on the kernel that keeps a CU's tokens in LDS and a 64-channel slab of weights in registers
@@ -180,6 +197,7 @@ int ivit_linear_plan_prepare_ws(ivit_handle h, ivit_linear_plan p);
  * C = 384 block, activations in natural token order): out8 == ivit_layernorm_requant followed by ivit_linear_i8_requant_planned(bits = 8).
  * IVIT_ERR_UNSUPPORTED (nothing launched) unless the plan is a prepared K = 384 one.  On a prepared plan
  * ivit_linear_i8_requant_planned(bits = 8) runs on the same kernel.                                                            */
+/* Alignment: x16 and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_layernorm_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan p, const int16_t *x16, float scale,
                                              const float *bias_int, const float *sc, const ivit_dyadic *ln_dy, int8_t *out8, int M);
 /* attn.proj + qact2 with the identity branch + norm2 + qact3 of a D = 384 block in ONE launch (vit_quant.py:137-140):
@@ -187,10 +205,12 @@ int ivit_layernorm_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan p, 
  * ln_bias_int, ln_sc, ln_dy) — the workgroup that produced a row normalises it.  IVIT_ERR_UNSUPPORTED (nothing launched) unless
  * the plan is a prepared 384 x 384 one and both residual multipliers are in the fast range (|m * 2^-e| < 2^9).  Measured SLOWER
  * than the two launches in the DeiT-S forward (profiles/README.md, round 6): the native runner does not use it.            */
+/* Alignment: x, residual, out and ln_out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8_requant_residual_layernorm_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, ivit_dyadic dy_main,
                                                       ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int M,
                                                       float ln_scale, const float *ln_bias_int, const float *ln_sc,
                                                       const ivit_dyadic *ln_dy, int8_t *ln_out8);
+/* Alignment: x16, q, k and v 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan p, const int16_t *x16, float scale,
                                          const float *bias_int, const float *sc, const ivit_dyadic *ln_dy, int8_t *q,
                                          int8_t *k, int8_t *v, int B, int T, int H, int dh);
@@ -201,6 +221,7 @@ int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan p, cons
  * entry; ldv >= T with ldv % 16 == 0 stores v TRANSPOSED, element (b, h, t, ch) at vt[((b * H + h) * 64 + ch) * ldv + t], the layout of
  * ivit_linear_i8_qkv.  Columns t >= T of v^T are not written.  IVIT_ERR_UNSUPPORTED (nothing launched) where the ldv == 0 entry returns
  * it, and for v^T on a K = 384 plan or with B*H*64*ldv >= 2^31.                                                               */
+/* Alignment: x16, q, k and vt 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan p, const int16_t *x16, float scale,
                                              const float *bias_int, const float *sc, const ivit_dyadic *ln_dy, int8_t *q,
                                              int8_t *k, int8_t *vt, int B, int T, int H, int dh, int ldv);
@@ -208,21 +229,25 @@ int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan p, 
 /* ---- a2  QuantMatMul.forward  (quant_modules.py:223-228), batched, "NT" form:
  * C[b] = A[b] (M x K) * B[b]^T (B[b] is N x K), int32.  q·kᵀ: A=q, B=k.
  * lda/ldb/ldc in elements, strides per batch in elements; lda,ldb % 16 == 0.            */
+/* Alignment: A and B 16-byte aligned; C takes any int32 address; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_bmm_nt_i8(ivit_handle h, const int8_t *A, const int8_t *B, int32_t *C, int nb, int M,
                    int N, int K, int lda, int ldb, int ldc, int64_t strideA, int64_t strideB,
                    int64_t strideC);
 /* attn·v with the 16-bit Shiftmax output as A (values 0..32768): exact, two int8 MFMA
  * passes (a-16384 = 256*hi + lo) + 16384*colsum(B).  B = vᵀ [N=dh, K=T].                */
+/* Alignment: A and B 16-byte aligned; C takes any int32 address; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_bmm_nt_u16i8(ivit_handle h, const uint16_t *A, const int8_t *B, int32_t *C, int nb,
                       int M, int N, int K, int lda, int ldb, int ldc, int64_t strideA,
                       int64_t strideB, int64_t strideC);
 
 /* a2 + a3, attention-shaped (vit_quant.py:70-74, 79-83):
- * scores8[bh,i,j] = clamp8(rq(q[bh,i,:]·k[bh,j,:], dy));  scores8 is [B*H, T, lds].       */
+ * scores8[bh,i,j] = clamp8(rq(q[bh,i,:]·k[bh,j,:], dy));  scores8 is [B*H, T, lds]; columns j >= T of a row are not written. */
+/* Alignment: q, k and scores8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_attn_qk_requant(ivit_handle h, const int8_t *q, const int8_t *k, ivit_dyadic dy,
                          int8_t *scores8, int BH, int T, int dh, int lds);
 /* ctx8[b,i,h*dh+d] = clamp8(rq(sum_j p[bh,i,j]*v[bh,j,d], dy));  p is [B*H,T,ldp] uint16,
  * vt is [B*H,dh,ldv];  ctx8 is [B,T,H*dh] (heads merged, vit_quant.py:81).               */
+/* Alignment: p, vt and ctx8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_attn_pv_requant(ivit_handle h, const uint16_t *p, const int8_t *vt, ivit_dyadic dy,
                          int8_t *ctx8, int B, int H, int T, int dh, int ldp, int ldv);
 
@@ -231,6 +256,7 @@ int ivit_attn_pv_requant(ivit_handle h, const uint16_t *p, const int8_t *vt, ivi
  * registers.  Bit-identical to ivit_attn_qk_requant + ivit_shiftmax + ivit_attn_pv_requant.
  * q,k [B*H,T,dh], vt [B*H,dh,ldv] (as written by ivit_linear_i8_qkv), ctx8 [B,T,H*dh].
  * Built for dh == 64 and T <= 640 (DeiT/ViT at 224 and 384); else IVIT_ERR_UNSUPPORTED.   */
+/* Alignment: q, k, vt and ctx8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_attention_fused(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                          ivit_dyadic dy_qk, float s_softmax, ivit_dyadic dy_pv, int8_t *ctx8,
                          int B, int H, int T, int dh, int ldv);
@@ -240,6 +266,7 @@ int ivit_attention_fused(ivit_handle h, const int8_t *q, const int8_t *k, const 
  * exp_int = exp_t[exp_aq[exp_cls[vmax]][v] + max(v - vmax, dmin) - dmin].  exp_aq uint16 [nclass][256],
  * exp_t float [t_count], exp_cls uint8 [256] (device; exp_aq and exp_t 16-byte aligned, exp_cls 4-byte aligned — they are
  * copied into LDS in 16-byte pieces; IVIT_ERR_INVALID otherwise).  Same integers as ivit_attention_fused.        */
+/* Alignment: q, k, vt and ctx8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_attention_fused_lut(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                              ivit_dyadic dy_qk, float s_softmax, const uint16_t *exp_aq, const float *exp_t,
                              const uint8_t *exp_cls, int nclass, int t_count, int dmin, ivit_dyadic dy_pv,
@@ -258,6 +285,7 @@ int ivit_attention_fused_lut(ivit_handle h, const int8_t *q, const int8_t *k, co
  * (one 16-byte store per token and head instead of sixteen byte stores); the kernel transposes on its way into the LDS.      */
 int ivit_shiftmax_rowtable(ivit_handle h, const uint16_t *exp_aq, const float *exp_t, const uint8_t *exp_cls,
                            int nclass, int t_count, int dmin, float *rowtab);
+/* Alignment: q, k, vt and ctx8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_attention_fused_rowlut(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                                 ivit_dyadic dy_qk, float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv,
                                 int8_t *ctx8, int B, int H, int T, int dh, int ldv);
@@ -268,18 +296,22 @@ int ivit_attention_fused_rowlut(ivit_handle h, const int8_t *q, const int8_t *k,
  * integers.  x16 / x_cls (both NULL: skipped): row b*T of the 16-bit stream x16 [B*T, H*dh] is copied to x_cls [B, H*dh] on the side
  * — the identity rows of the attn.proj that follows (vit_quant.py:135).  ctx_cls, x16 and x_cls 16-byte aligned; otherwise the
  * arguments, limits and status codes of the whole-T entry of the same Shiftmax form.                                               */
+/* Alignment: q, k and vt 16-byte aligned, like ctx_cls, x16 and x_cls; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_attention_fused_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                              ivit_dyadic dy_qk, float s_softmax, ivit_dyadic dy_pv, int8_t *ctx_cls,
                              const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
+/* Alignment: q, k and vt 16-byte aligned, like ctx_cls, x16 and x_cls; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_attention_fused_lut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                                  ivit_dyadic dy_qk, float s_softmax, const uint16_t *exp_aq, const float *exp_t,
                                  const uint8_t *exp_cls, int nclass, int t_count, int dmin, ivit_dyadic dy_pv,
                                  int8_t *ctx_cls, const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
+/* Alignment: q, k and vt 16-byte aligned, like ctx_cls, x16 and x_cls; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_attention_fused_rowlut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                                     ivit_dyadic dy_qk, float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv,
                                     int8_t *ctx_cls, const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
 /* out[r, :] = x[r * row_stride : r * row_stride + C] for r < rows (16-bit values; x[:, 0] of vit_quant.py:272 with
  * row_stride = T * C): the identity-row copy above as a launch of its own.  C and row_stride multiples of 8, 16-byte aligned.    */
+/* Alignment: x and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_gather_rows_i16(ivit_handle h, const int16_t *x, int64_t rows, int C, int64_t row_stride, int16_t *out);
 
 /* ---- a3  QuantAct.forward with a previous scale -> fixedpoint_mul.forward
@@ -311,9 +343,11 @@ int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in
  * evaluates the extremes of Q*sigmoid_int over all (Q, row max) pairs on the host, from the scale alone,
  * and returns IVIT_ERR_UNSUPPORTED (nothing launched, the message names the scale) when they leave int16.
  * The 8-bit forms below carry the product in 32 bits and equal the reference at every positive scale.  */
+/* Alignment: x and out16 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_shiftgelu(ivit_handle h, const int8_t *x, int64_t rows, int C, float scale,
                    int16_t *out16);
 /* a6 + a3 (layers_quant.py:146-147): ... -> clamp8(rq(Q*sigmoid_int, dy))               */
+/* Alignment: x and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_shiftgelu_requant(ivit_handle h, const int8_t *x, int64_t rows, int C, float scale,
                            ivit_dyadic dy, int8_t *out8);
 
@@ -322,6 +356,7 @@ int ivit_shiftgelu_requant(ivit_handle h, const int8_t *x, int64_t rows, int C, 
  * (Q+128)] (65536 bytes) once with the same device arithmetic; the per-token call is then
  * a row max plus byte gathers (HBM-bound instead of VALU-bound).                          */
 int ivit_shiftgelu_build_table(ivit_handle h, float scale, ivit_dyadic dy, int8_t *table);
+/* Alignment: x and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_shiftgelu_requant_lut(ivit_handle h, const int8_t *x, int64_t rows, int C,
                                const int8_t *table, int8_t *out8);
 
@@ -329,10 +364,12 @@ int ivit_shiftgelu_requant_lut(ivit_handle h, const int8_t *x, int64_t rows, int
  * x int16 [rows, C] with per-tensor scale; bias_int[c] = floor(fl(fl(b/w)/sf)) and
  * sc[c] = fl(sf*w[c]) from the host.  z[i,c] = rne(fl(fl(out*sc)/sc)) as float — the
  * integer the following QuantAct derives (quant_utils.py:220).                           */
+/* Alignment: x and z 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_layernorm(ivit_handle h, const int16_t *x, int64_t rows, int C, float scale,
                    const float *bias_int, const float *sc, float *z);
 /* a7 + a3 (vit_quant.py:131-132): ... -> clamp8(rq(z, dy_ch[c])).  row_stride in
  * elements lets the final norm read only the class-token rows (vit_quant.py:271-272).    */
+/* Alignment: x and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
                            int64_t row_stride, float scale, const float *bias_int,
                            const float *sc, const ivit_dyadic *dy_ch, int8_t *out8);
@@ -341,10 +378,12 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
  * (layers_quant.py:184-196, quant_modules.py:297-330), then class token + position
  * embedding (vit_quant.py:259-265).
  * ivit_im2col_patch: NCHW int8 image -> [B*gh*gw, Cin*P*P] rows in conv-weight order.    */
+/* Alignment: img and rows 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_im2col_patch(ivit_handle h, const int8_t *img, int B, int Cin, int H, int W, int P,
                       int8_t *rows);
 /* x16[b,0,:]  = clamp16(rq(z_cls[:], dy_x) + rq(pos[0,:], dy_pos))
  * x16[b,1+i,:] = clamp16(rq(patch16[b,i,:], dy_x) + rq(pos[1+i,:], dy_pos))             */
+/* Alignment: patch16 and x16 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_embed_finish(ivit_handle h, const int16_t *patch16, const int32_t *z_cls,
                       const int16_t *pos, ivit_dyadic dy_x, ivit_dyadic dy_pos, int16_t *x16,
                       int B, int T, int D);
@@ -353,6 +392,7 @@ int ivit_embed_finish(ivit_handle h, const int16_t *patch16, const int32_t *z_cl
  * patch's position embedding and writes row 1 + i of its image.  w [D, Cin*P*P] in conv-weight order, bias int32 [D] or NULL,
  * dy_ch [D] as for ivit_linear_i8_requant(bits = 16).  x16 == ivit_im2col_patch -> ivit_linear_i8_requant(16) -> ivit_embed_finish.
  * IVIT_ERR_UNSUPPORTED (nothing launched) unless P == 16, H and W multiples of 16, Cin*P*P a multiple of 64 and |dy_x|, |dy_pos| < 2^9. */
+/* Alignment: images and x16 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int Cin, int H, int W, int P, const int8_t *w,
                      const int32_t *bias, const ivit_dyadic *dy_ch, const int32_t *z_cls, const int16_t *pos,
                      ivit_dyadic dy_x, ivit_dyadic dy_pos, int16_t *x16, int D);
@@ -524,11 +564,13 @@ int ivit_layernorm_tokenorder(ivit_handle h, const int16_t *x, int64_t rows, int
 /* the same with the per-channel QuantAct(8) that follows fused in (out8 int8 [rows, C]).  For C = 96 / 128 (the
  * vectorised kernel) x, out8, bias_int and sc must be 16-byte aligned: IVIT_ERR_INVALID otherwise; the same holds for
  * ivit_patch_norm_tokenorder below.                                                              */
+/* Alignment: at C = 96 / 128 x and out8 16-byte aligned (the other widths take any element-aligned address); IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_layernorm_tokenorder_requant(ivit_handle h, const int16_t *x, int64_t rows, int C, float scale,
                                       const float *bias_int, const float *sc, const ivit_dyadic *dy,
                                       int tokens_per_image, int8_t *out8);
 /* PatchEmbed's tail in one pass (layers_quant.py:193-195, swin_quant.py:543): int8 conv output ->
  * norm (token-order sums) -> qact (16 bit, per-channel dy_ch) -> qact1 (16 bit, per-tensor dy2).          */
+/* Alignment: at C = 96 / 128 x8 and out16 16-byte aligned (the other widths take any element-aligned address); IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_patch_norm_tokenorder(ivit_handle h, const int8_t *x8, int64_t rows, int C, float scale,
                                const float *bias_int, const float *sc, const ivit_dyadic *dy_ch,
                                ivit_dyadic dy2, int tokens_per_image, int16_t *out16);
@@ -540,6 +582,7 @@ int ivit_patch_norm_tokenorder(ivit_handle h, const int8_t *x8, int64_t rows, in
  * relb int16 [heads, N, N] (N = window^2) = rq(quantised bias table gathered by
  * relative_position_index, dy(qact_table -> qact2)); dy_a = dy(qact_attn1 -> qact2).
  * Built for window 7 (R % 7 == 0) and window 12 (R % 12 == 0, relb 16-byte aligned), dh 32.  */
+/* Alignment: qkv and ctx 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_window_attention_fused(ivit_handle h, const int8_t *qkv, ivit_dyadic dy_qk, ivit_dyadic dy_a,
                                 const int16_t *relb, float s_softmax, ivit_dyadic dy_pv, int8_t *ctx,
                                 int B, int R, int window, int shift, int heads, int dh);
@@ -548,6 +591,7 @@ int ivit_window_attention_fused(ivit_handle h, const int8_t *qkv, ivit_dyadic dy
  * errors) in the windows that carry no shift mask; windows under the mask (swin_quant.py:151-156) keep the arithmetic
  * form, because the float -100 enters between the requotient's multiply and divide.  Same integers as the entry above.
  * Window 7 only (IVIT_ERR_UNSUPPORTED at window 12).                                                                  */
+/* Alignment: qkv and ctx 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_window_attention_fused_lut(ivit_handle h, const int8_t *qkv, ivit_dyadic dy_qk, ivit_dyadic dy_a,
                                     const int16_t *relb, float s_softmax, const uint16_t *exp_aq, const float *exp_t,
                                     const uint8_t *exp_cls, int nclass, int t_count, int dmin, ivit_dyadic dy_pv,
@@ -560,6 +604,7 @@ int ivit_window_attention_fused_lut(ivit_handle h, const int8_t *qkv, ivit_dyadi
  * hidden = 512 (Swin-B stage 0: the lock-step kernel of csrc/ivit_mlp.h reading w1 / w2 row-major from L2; there x, w1, w2, b1, b2,
  * dy1, dy2 must be 16-byte aligned, and residual multipliers >= 2^9 are IVIT_ERR_UNSUPPORTED with nothing launched);
  * other shapes: IVIT_ERR_UNSUPPORTED.                                                                   */
+/* Alignment: x, residual and out 16-byte aligned (C = 128: residual and out 8-byte aligned); IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32_t *b1, const ivit_dyadic *dy1,
                    const int8_t *gelu_table, const int8_t *w2, const int32_t *b2, const ivit_dyadic *dy2,
                    ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M,
@@ -581,6 +626,7 @@ int ivit_mlp_plan_destroy(ivit_mlp_plan p);
  * while another thread or stream is inside ivit_mlp_fused_planned on the same plan: it rewrites a field the launch reads.
  * A width-192 or width-256 plan has the lock-step kernel only: 0 and 1 succeed, 2 returns IVIT_ERR_UNSUPPORTED and changes nothing.  */
 int ivit_mlp_plan_select(ivit_mlp_plan p, int kernel);
+/* Alignment: x, residual and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, const int8_t *gelu_table,
                            ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual, int16_t *out,
                            int64_t M);
@@ -589,6 +635,7 @@ int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, cons
  * bias_int / sc / ln_dy as for ivit_layernorm_requant) into scratch8 [M, 384] and reads its activation tiles from there.  out ==
  * ivit_layernorm_requant followed by ivit_mlp_fused_planned.  IVIT_ERR_UNSUPPORTED (nothing launched) where ivit_mlp_fused_planned is,
  * where the launch would run on the lock-step kernel (fewer than two units per CU), and on a width-192 or width-256 plan.         */
+/* Alignment: x16, scratch8 and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int,
                                      const float *sc, const ivit_dyadic *ln_dy, int8_t *scratch8, const int8_t *gelu_table,
                                      ivit_dyadic dy_main, ivit_dyadic dy_res, int16_t *out, int64_t M);
@@ -600,15 +647,18 @@ int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16
  * lock-step kernel, whatever ivit_mlp_plan_select says; grids and unit schedules are those of ivit_mlp_fused_planned on that kernel
  * (ivit_set_cu_share included).  out overlapping x16 is IVIT_ERR_INVALID.  IVIT_ERR_UNSUPPORTED (nothing launched) on a plan of
  * another width (256) and for residual multipliers outside the fast range.                                                       */
+/* Alignment: x16 and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_layernorm_mlp_lockstep_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int,
                                         const float *sc, const ivit_dyadic *ln_dy, const int8_t *gelu_table, ivit_dyadic dy_main,
                                         ivit_dyadic dy_res, int16_t *out, int64_t M);
 /* PatchMerging's 2x2 gather (swin_quant.py:336-342): x [B,R,R,C] (in_bits 8 or 16) ->
  * int16 [B, (R/2)^2, 4C], channel blocks in the reference's torch.cat order.                  */
+/* Alignment: x 16-byte aligned (8-byte at in_bits = 8), out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_patch_merge_gather(ivit_handle h, const void *x, int in_bits, int B, int R, int C, int16_t *out);
 /* The same gather folded into the I-LayerNorm + QuantAct(8) that follows it in PatchMerging.forward (swin_quant.py:336-349:
  * gather, self.norm over 4C, qact1) — x int16 [B,R,R,C] -> out8 int8 [B (R/2)^2, 4C]; the gathered tensor never exists.  Same
  * integers as ivit_patch_merge_gather + ivit_layernorm_requant.  C in {96, 128, 192, 256, 384}; else IVIT_ERR_UNSUPPORTED.      */
+/* Alignment: x and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_patch_merge_layernorm_requant(ivit_handle h, const int16_t *x, int B, int R, int C, float scale,
                                        const float *bias_int, const float *sc, const ivit_dyadic *dy_ch, int8_t *out8);
 int ivit_widen_i8_i16(ivit_handle h, const int8_t *x, int16_t *out, int64_t n);
@@ -616,6 +666,7 @@ int ivit_widen_i8_i16(ivit_handle h, const int8_t *x, int16_t *out, int64_t n);
  * next stage's 16-bit stream: out16 = clamp8(rq(acc + bias, dy_ch[n])) stored as int16 [M][N] — ivit_linear_i8_requant(bits = 8) followed by
  * ivit_widen_i8_i16 in one launch, same integers.  gemm_glds_kernel's shapes only (K % 32 == 0, K >= 64, not the short-K streaming kernel's):
  * IVIT_ERR_UNSUPPORTED otherwise, nothing launched.                                                                                  */
+/* Alignment: x and out16 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 int ivit_linear_i8_requant8_store16(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias, const ivit_dyadic *dy_ch,
                                     int16_t *out16, int M, int N, int K);
 

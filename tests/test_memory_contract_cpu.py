@@ -1,0 +1,145 @@
+"""The memory contract of the C-ABI on the CPU twin (oracle/ivit_twin.c), which half of the GPU suite trusts as its reference: every
+twinned entry point of tests/abi_cases.py::_cases runs with each array inside its own [1 MiB guard | payload | 1 MiB guard] numpy
+arena and must (1) write nothing outside its outputs, (2) give the same bytes whatever lies around its inputs, (3) give the bytes of
+the same call on plain arrays.  The harness itself is tested with two planted entries that break rules 1 and 2."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import abi_cases as A
+
+
+@pytest.fixture(scope="module")
+def twin():
+    return A.load_twin()
+
+
+@functools.lru_cache(maxsize=None)
+def twin_cases(variant):
+    """the table, built once per variant and left unchanged (the arenas copy from it)"""
+    return A._cases(np.random.default_rng(77 + variant), variant)
+
+
+NAMES = sorted(A.table_names()[0])
+
+
+def test_every_entry_point_is_in_a_table_or_excluded():
+    """a new entry point fails here until someone adds a case for it"""
+    missing, stale = A.uncovered_entry_points()
+    assert not missing, f"entry points without a case in tests/abi_cases.py: {missing}"
+    assert not stale, f"exclusions that name no entry point, or one that has a case: {stale}"
+
+
+def test_alignment_table_covers_every_entry_with_arrays():
+    """check 4 of the device tests reads abi_cases.ALIGN: an entry that gains a case with array arguments but no record there (or in
+    TABLES_ONLY) would skip it silently; and every record names array arguments of every case of its entry"""
+    missing, wrong = A.alignment_table_gaps()
+    assert not missing, f"entries with array arguments and no record in abi_cases.ALIGN: {missing}"
+    assert not wrong, f"records of abi_cases.ALIGN that name no array argument: {wrong}"
+
+
+def test_glds_256_row_tile_is_unreachable():
+    """gemm_glds_kernel has a 256-row instantiation that no call can select, which is why the tables hold no case for it: launch_gemm2
+    estimates ceil(tiles / slots) * rows with 2 slots per CU for 256-row tiles and, at G2_NSTAGE128 == 2, 4 per CU for 128-row tiles;
+    128-row tiles are at most twice as many, so they never need more rounds, and at half the rows per round they always cost less
+    (ties go to 256 rows, and there are none).  The rule is restated from csrc/ivit_hip.hip and searched over M, the column tiles and
+    CU counts; if the constant or the rule changes this fails, and the tables then need cases on the 256-row side."""
+    import os
+    import re
+    from conftest import ROOT
+    csrc = os.path.join(ROOT, "i-vit_amd", "csrc")
+    assert re.search(r"#define G2_NSTAGE128 2\b", open(os.path.join(csrc, "ivit_gemm2.h")).read())
+    hip = open(os.path.join(csrc, "ivit_hip.hip")).read()
+    assert "s256 = 2LL * h->num_cu, s128 = (G2_NSTAGE128 == 2 ? 4LL : 3LL) * h->num_cu;" in hip
+    assert "c256 = ((t256 + s256 - 1) / s256) * 256, c128 = ((t128 + s128 - 1) / s128) * 128;" in hip
+    assert "if (c128 < c256) gemm_glds_kernel<EPI, 128>" in hip
+    M = np.arange(1, 1 << 20, dtype=np.int64)
+    for cus in (1, 64, 256, 304):
+        for tiles_n in range(1, 13):
+            t256, t128 = (M + 255) // 256 * tiles_n, (M + 127) // 128 * tiles_n
+            c256, c128 = (t256 + 2 * cus - 1) // (2 * cus) * 256, (t128 + 4 * cus - 1) // (4 * cus) * 128
+            assert (c128 < c256).all(), (cus, tiles_n)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_twin_memory_contract(twin, name):
+    mem = A.NumpyMem()
+    fn = getattr(twin, "ivit_cpu_" + name)
+    ran = 0
+    for variant in (0, 1):
+        for i, (n, args) in enumerate(twin_cases(variant)):
+            if n != name:
+                continue
+            what = f"ivit_cpu_{name} (variant {variant}, case {i})"
+            got = A.check_contract(fn, None, args, mem, what=what)
+            want = A.plain_outputs(fn, None, args, mem)
+            for j, (g, w) in enumerate(zip(got, want)):
+                assert np.array_equal(g, w), (what, j, int((g != w).sum()))
+            ran += 1
+    assert ran
+
+
+# ---------------------------------------------------------------- the harness on two planted bugs
+def _view(ptr, n, dtype, offset=0):
+    """n elements at ptr + offset elements, as the entry itself would address them"""
+    dt = np.dtype(dtype)
+    raw = (ctypes.c_uint8 * (n * dt.itemsize)).from_address(ptr.value + offset * dt.itemsize)
+    return np.frombuffer(raw, dt)
+
+
+def _good(h, x, out, n):
+    _view(out, n, np.int16)[:] = _view(x, n, np.int16) + 1
+    return 0
+
+
+def _writes_in_front(h, x, out, n):
+    _good(h, x, out, n)
+    _view(out, 1, np.int16, offset=-1)[:] = 7                 # one element in front of its output
+    return 0
+
+
+def _reads_behind(h, x, out, n):
+    _good(h, x, out, n)
+    _view(out, 1, np.int16)[:] += _view(x, 1, np.int8, offset=2 * n).astype(np.int16)     # the byte behind its input
+    return 0
+
+
+def _skips_last(h, x, out, n):
+    _view(out, n - 1, np.int16)[:] = _view(x, n - 1, np.int16) + 1
+    return 0
+
+
+def test_harness_catches_planted_bugs():
+    """check 1 fails on the entry that writes in front of its output and check 2 on the one that reads behind its input, each with its
+    own message, and neither on the other; an entry that leaves an output element unwritten is caught too; the sound entry passes"""
+    mem = A.NumpyMem()
+    x = np.arange(-500, 500, dtype=np.int16)
+    args = [("in", x), ("out", np.zeros(1000, np.int16)), 1000]
+    want = (x + 1).view(np.uint8)
+    assert np.array_equal(A.check_contract(_good, None, args, mem)[0], want)
+    assert np.array_equal(A.plain_outputs(_good, None, args, mem)[0], want)
+    with pytest.raises(A.ContractError, match="2 bytes written IN FRONT of the output"):
+        A.check_contract(_writes_in_front, None, args, mem)
+    with pytest.raises(A.ContractError, match="depend on what lies around the inputs"):
+        A.check_contract(_reads_behind, None, args, mem)
+    with pytest.raises(A.ContractError, match="2 bytes of the output never written"):
+        A.check_contract(_skips_last, None, args, mem)
+    # pad columns: an input's are filled like the guards, an output's must keep the fill
+    xp = np.zeros((4, 8), np.int16)
+    xp[:, :5] = 3
+
+    def rowsum(h, x, out, rows, n, ld):
+        _view(out, rows, np.int16)[:] = _view(x, rows * ld, np.int16).reshape(rows, ld)[:, :n].sum(axis=1)
+        return 0
+
+    def rowsum_unmasked(h, x, out, rows, n, ld):
+        _view(out, rows, np.int16)[:] = _view(x, rows * ld, np.int16).reshape(rows, ld).sum(axis=1)
+        return 0
+    pargs = [("in", xp, 5), ("out", np.zeros(4, np.int16)), 4, 5, 8]
+    assert np.array_equal(A.check_contract(rowsum, None, pargs, mem)[0].view(np.int16), np.full(4, 15, np.int16))
+    with pytest.raises(A.ContractError, match="depend on what lies around the inputs"):
+        A.check_contract(rowsum_unmasked, None, pargs, mem)
+    zargs = [("in", xp, ("zero", 5)), ("out", np.zeros(4, np.int16)), 4, 5, 8]      # a pad the header demands to be zero stays zero
+    assert np.array_equal(A.check_contract(rowsum_unmasked, None, zargs, mem)[0].view(np.int16), np.full(4, 15, np.int16))

@@ -6,7 +6,6 @@ bit for bit."""
 import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,38 +16,14 @@ import ivit_amd as iv
 from conftest import golden_scales
 from ivit_amd import _lib
 
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import gen_twin_header  # noqa: E402
+from abi_cases import _EXTRA, _cases, _run, _sig, dyv, gen_twin_header, hp, load_twin  # noqa: E402
 
 _P = ctypes.c_void_p
 
 
 @pytest.fixture(scope="module")
 def twin():
-    from oracle import oracle as orc
-    lib = ctypes.CDLL(orc.build())
-    for name in gen_twin_header.TWIN:
-        fn = getattr(lib, "ivit_cpu_" + name)           # AttributeError = a declared twin is not exported
-        fn.argtypes = _sig(name)                        # the C-ABI's own ctypes signature, unchanged
-        fn.restype = ctypes.c_int
-    return lib
-
-
-# the two plan calls without a handle argument are declared outside _lib.SIGNATURES (which prepends nothing, but whose
-# Handle.call wrapper does): same argtypes as _lib.load() sets
-_EXTRA = {"linear_plan_destroy": [_P], "mlp_plan_destroy": [_P], "linear_plan_query": [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]}
-
-
-def _sig(name):
-    return _EXTRA.get(name) or _lib.SIGNATURES["ivit_" + name]
-
-
-def hp(a):
-    return a.ctypes.data_as(_P)
-
-
-def dyv(d):
-    return _lib.Dyadic(float(d[0, 0]), float(d[0, 1]))
+    return load_twin()
 
 
 def test_twin_header_is_generated_from_the_c_abi():
@@ -103,154 +78,7 @@ def test_twin_rejects_bad_arguments(twin):
     assert twin.ivit_cpu_linear_i8_requant(None, hp(x), hp(x), None, None, 8, hp(x), 4, 4, 16) == 1          # no dyadics
 
 
-# ---------------------------------------------------------------- the same calls through both libraries
-def _cases(rng, variant=0):
-    """-> list of (entry point, args); an argument is a scalar / Dyadic, ("in", array), ("out", array) or None.
-    variant 1 is a second argument list per entry point: ragged row counts, other channel / token counts, other scales."""
-    I, O = (lambda a: ("in", np.ascontiguousarray(a))), (lambda a: ("out", a))
-    cs = []
-    V = variant
-    M, N, K = ((300, 96, 64), (173, 160, 128))[V]
-    x = rng.integers(-128, 128, (M, K), dtype=np.int8)
-    w = np.rint(rng.normal(0, 40, (N, K)).clip(-127, 127)).astype(np.int8)
-    b = rng.integers(-3000, 3000, N).astype(np.int32)
-    s_pre = (10 ** rng.uniform(*((-5.5, -4.5), (-5.1, -4.2))[V], N)).astype(np.float32)
-    d8, d16 = iv.freeze.dyadic(s_pre, np.float32((2e-2, 3.1e-2)[V])), iv.freeze.dyadic(s_pre, np.float32((1e-4, 1.7e-4)[V]))
-    dm, dr = iv.freeze.dyadic(np.float32(1e-4), np.float32(2e-4)), iv.freeze.dyadic(np.float32(3e-4), np.float32(2e-4))
-    res = rng.integers(-20000, 20000, (M, N)).astype(np.int16)
-    cs.append(("quantize_input_f32", [I(rng.normal(0, 1, 5000).astype(np.float32)), 0.02, O(np.zeros(5000, np.int8)), 5000]))
-    cs.append(("linear_i8", [I(x), I(w), I(b), O(np.zeros((M, N), np.int32)), M, N, K]))
-    cs.append(("linear_i8_requant", [I(x), I(w), I(b), I(d8), 8, O(np.zeros((M, N), np.int8)), M, N, K]))
-    cs.append(("linear_i8_requant", [I(x), I(w), I(b), I(d16), 16, O(np.zeros((M, N), np.int16)), M, N, K]))
-    cs.append(("linear_i8_requant_residual", [I(x), I(w), I(b), I(d16), dyv(dm), dyv(dr), I(res), O(np.zeros((M, N), np.int16)), M, N, K]))
-    # attention-shaped entry points: B = 2, H = 2, T = 50, dh = 64
-    B, Hh, T, dh, ld = ((2, 2, 50, 64, 64), (3, 1, 37, 64, 48))[V]
-    D = Hh * dh
-    xq = rng.integers(-128, 128, (B * T, D), dtype=np.int8)
-    wq = np.rint(rng.normal(0, 30, (3 * D, D)).clip(-127, 127)).astype(np.int8)
-    bq = rng.integers(-3000, 3000, 3 * D).astype(np.int32)
-    dq = iv.freeze.dyadic((10 ** rng.uniform(-5.5, -5.0, 3 * D)).astype(np.float32), np.float32(4e-2))
-    q = rng.integers(-128, 128, (B * Hh, T, dh), dtype=np.int8)
-    k = rng.integers(-128, 128, (B * Hh, T, dh), dtype=np.int8)
-    vt = np.zeros((B * Hh, dh, ld), np.int8)
-    vt[:, :, :T] = rng.integers(-128, 128, (B * Hh, dh, T), dtype=np.int8)
-    dqk, dpv = iv.freeze.dyadic(np.float32(2e-4), np.float32(6e-2)), iv.freeze.dyadic(np.float32(3e-6), np.float32(9e-3))
-    cs.append(("linear_i8_qkv", [I(xq), I(wq), I(bq), I(dq), O(np.zeros((B * Hh, T, dh), np.int8)), O(np.zeros((B * Hh, T, dh), np.int8)),
-                                 O(np.zeros((B * Hh, dh, ld), np.int8)), B, T, Hh, dh, ld]))
-    cs.append(("bmm_nt_i8", [I(q), I(k), O(np.zeros((B * Hh, T, T), np.int32)), B * Hh, T, T, dh, dh, dh, T, T * dh, T * dh, T * T]))
-    p16 = np.zeros((B * Hh, T, ld), np.uint16)
-    p16[:, :, :T] = rng.integers(0, 32769, (B * Hh, T, T)).astype(np.uint16)
-    cs.append(("bmm_nt_u16i8", [I(p16), I(vt), O(np.zeros((B * Hh, T, dh), np.int32)), B * Hh, T, dh, T, ld, ld, dh, T * ld, dh * ld, T * dh]))
-    cs.append(("attn_qk_requant", [I(q), I(k), dyv(dqk), O(np.zeros((B * Hh, T, ld), np.int8)), B * Hh, T, dh, ld]))
-    cs.append(("attn_pv_requant", [I(p16), I(vt), dyv(dpv), O(np.zeros((B, T, D), np.int8)), B, Hh, T, dh, ld, ld]))
-    cs.append(("attention_fused", [I(q), I(k), I(vt), dyv(dqk), 0.06, dyv(dpv), O(np.zeros((B, T, D), np.int8)), B, Hh, T, dh, ld]))
-    # requant flavours
-    z32 = rng.integers(-2 ** 20, 2 ** 20, (M, N)).astype(np.int32)
-    zid = rng.integers(-30000, 30000, (M, N)).astype(np.int32)
-    cs.append(("requant_i32", [I(z32), I(d8), N, None, None, 8, O(np.zeros((M, N), np.int8)), M, N]))
-    cs.append(("requant_i32", [I(z32), I(dm), 1, I(zid), I(dr), 16, O(np.zeros((M, N), np.int16)), M, N]))
-    cs.append(("requant_i16", [I(res), I(dm), 1, None, None, 16, O(np.zeros((M, N), np.int16)), M, N]))
-    cs.append(("requant_f32", [I(z32.astype(np.float32) * 4096.0), I(iv.freeze.dyadic(s_pre * np.float32(1e-3), np.float32(2e-2))), N,
-                               None, None, 8, O(np.zeros((M, N), np.int8)), M, N]))
-    # elementwise operators
-    R8 = (64, 61)[V]
-    s8 = rng.integers(-128, 128, (R8, 197), dtype=np.int8)
-    s8[3] = -128; s8[4] = 127; s8[5, :] = -100; s8[5, 17] = 90                       # flat, saturated and peaky rows
-    cs.append(("shiftmax", [I(s8), R8, 197, 197, (0.07, 0.093)[V], 16, O(np.zeros((R8, 197), np.uint16)), 197]))
-    cs.append(("shiftmax", [I(s8), R8, 197, 197, (0.11, 0.157)[V], 8, O(np.zeros((R8, 197), np.uint16)), 197]))
-    Rg, Cg, sg = ((40, 384, 0.03), (37, 768, 0.045))[V]
-    g8 = rng.integers(-128, 128, (Rg, Cg), dtype=np.int8)
-    g8[2] = rng.integers(-128, -60, Cg, dtype=np.int8)                                # an all-negative row
-    dg = iv.freeze.dyadic(np.float32(sg * 2.0 ** -7), np.float32((0.025, 0.033)[V]))
-    tab = np.zeros(65536, np.int8)
-    cs.append(("shiftgelu", [I(g8), Rg, Cg, sg, O(np.zeros((Rg, Cg), np.int16))]))
-    cs.append(("shiftgelu_requant", [I(g8), Rg, Cg, sg, dyv(dg), O(np.zeros((Rg, Cg), np.int8))]))
-    cs.append(("shiftgelu_build_table", [sg, dyv(dg), O(tab)]))
-    C = (192, 384)[V]
-    Rl = (48, 50)[V]
-    xl = rng.integers(-9000, 9000, (Rl, C)).astype(np.int16)
-    xl[1] = 1234                                                                       # a zero-variance row
-    wl, bl = rng.uniform(0.4, 1.6, C).astype(np.float32), rng.normal(0, 0.3, C).astype(np.float32)
-    wl[5] = -0.7
-    bias_int, sc = iv.freeze.layernorm_constants(wl, bl)
-    dl = iv.freeze.dyadic(sc, np.float32(0.03))
-    sl = (2.5e-4, 3.3e-4)[V]
-    cs.append(("layernorm", [I(xl), Rl, C, sl, I(bias_int), I(sc), O(np.zeros((Rl, C), np.float32))]))
-    cs.append(("layernorm_requant", [I(xl), Rl, C, C, sl, I(bias_int), I(sc), I(dl), O(np.zeros((Rl, C), np.int8))]))
-    # one channel with a multiplier far above the |z * c| < 2^31 bound: the block takes the v_rndne_f64 / saturating form of the
-    # 8-bit requant (ivit_layernorm.h) instead of the magic-number one
-    dl_wide = dl.copy()
-    dl_wide[3:4] = iv.freeze.dyadic(sc[3:4], np.float32(1e-13))
-    cs.append(("layernorm_requant", [I(xl), Rl, C, C, sl, I(bias_int), I(sc), I(dl_wide), O(np.zeros((Rl, C), np.int8))]))
-    img = rng.integers(-128, 128, (2, 3, 32, 32), dtype=np.int8)
-    cs.append(("im2col_patch", [I(img), 2, 3, 32, 32, 8, O(np.zeros((2 * 16, 3 * 64), np.int8))]))
-    Te, De = ((17, 64), (10, 128))[V]
-    cs.append(("embed_finish", [I(rng.integers(-20000, 20000, (2, Te - 1, De)).astype(np.int16)), I(rng.integers(-10 ** 6, 10 ** 6, De).astype(np.int32)),
-                                I(rng.integers(-20000, 20000, (Te, De)).astype(np.int16)), dyv(dm), dyv(dr), O(np.zeros((2, Te, De), np.int16)), 2, Te, De]))
-    # ---- round 3: Swin-specific operators
-    a49 = rng.integers(-128, 128, (8 * 3 * 49, 49), dtype=np.int8)                     # [B_ = 8, H = 3, 49] rows
-    mk = np.where(rng.random((4, 49, 49)) < 0.3, np.float32(-100.0), np.float32(0.0)).astype(np.float32)
-    cs.append(("shiftmax_masked", [I(a49), 8 * 3 * 49, 49, 49, 0.05, 8, I(mk), 4, 3, O(np.zeros((8 * 3 * 49, 49), np.uint16)), 49]))
-    cs.append(("shiftmax_masked", [I(a49), 8 * 3 * 49, 49, 49, 0.05, 8, None, 0, 0, O(np.zeros((8 * 3 * 49, 49), np.uint16)), 49]))
-    zb = rng.integers(-128, 128, 6 * 3 * 2401).astype(np.int32)
-    zi = rng.integers(-128, 128, 3 * 2401).astype(np.int32)
-    da, db = iv.freeze.dyadic(np.float32(0.04), np.float32(0.05)), iv.freeze.dyadic(np.float32(0.01), np.float32(0.05))
-    cs.append(("requant_i32_bcast", [I(zb), dyv(da), I(zi), 3 * 2401, dyv(db), 8, O(np.zeros(6 * 3 * 2401, np.int8)), 6 * 3 * 2401]))
-    cs.append(("avgpool_requant", [I(rng.integers(-128, 128, (3, 49, 96), dtype=np.int8)), 3, 49, 96, dyv(iv.freeze.dyadic(np.float32(0.03), np.float32(0.02))),
-                                   O(np.zeros((3, 96), np.int8))]))
-    Ct, Lt = ((96, 64), (128, 49))[V]                                                   # token-order sums: 2 images of Lt tokens
-    xt = rng.integers(-9000, 9000, (2 * Lt, Ct)).astype(np.int16)
-    wt, bt = rng.uniform(0.4, 1.6, Ct).astype(np.float32), rng.normal(0, 0.3, Ct).astype(np.float32)
-    bit, sct = iv.freeze.layernorm_constants(wt, bt)
-    dt8, dt16 = iv.freeze.dyadic(sct, np.float32(0.03)), iv.freeze.dyadic(sct, np.float32(2e-4))
-    cs.append(("layernorm_tokenorder", [I(xt), 2 * Lt, Ct, 2.5e-4, I(bit), I(sct), Lt, O(np.zeros((2 * Lt, Ct), np.float32))]))
-    cs.append(("layernorm_tokenorder_requant", [I(xt), 2 * Lt, Ct, 2.5e-4, I(bit), I(sct), I(dt8), Lt, O(np.zeros((2 * Lt, Ct), np.int8))]))
-    cs.append(("patch_norm_tokenorder", [I(rng.integers(-128, 128, (2 * Lt, Ct), dtype=np.int8)), 2 * Lt, Ct, 0.02, I(bit), I(sct), I(dt16),
-                                         dyv(iv.freeze.dyadic(np.float32(2e-4), np.float32(2.5e-4))), Lt, O(np.zeros((2 * Lt, Ct), np.int16))]))
-    pm = rng.integers(-20000, 20000, (2, 14, 14, 96)).astype(np.int16)
-    cs.append(("patch_merge_gather", [I(pm), 16, 2, 14, 96, O(np.zeros((2, 49, 384), np.int16))]))
-    cs.append(("patch_merge_gather", [I(rng.integers(-128, 128, (2, 14, 14, 96), dtype=np.int8)), 8, 2, 14, 96, O(np.zeros((2, 49, 384), np.int16))]))
-    cs.append(("widen_i8_i16", [I(rng.integers(-128, 128, 5000, dtype=np.int8)), O(np.zeros(5000, np.int16)), 5000]))
-    # windowed attention: 2 images of 14 x 14 tokens (2 x 2 windows), 3 heads, with and without the cyclic shift
-    Bw, Rw, Hw = ((2, 14, 3), (1, 21, 2))[V]
-    qkvw = rng.integers(-128, 128, (Bw, Rw, Rw, 3 * Hw * 32), dtype=np.int8)
-    relb = rng.integers(-60, 60, (Hw, 49, 49)).astype(np.int16)
-    dwq, dwa, dwp = (iv.freeze.dyadic(np.float32(a), np.float32(b)) for a, b in (((3e-4, 0.05), (0.05, 0.06), (4e-4, 0.03)), ((2.2e-4, 0.043), (0.043, 0.071), (5e-4, 0.026)))[V])
-    for sh in (0, 3):
-        cs.append(("window_attention_fused", [I(qkvw), dyv(dwq), dyv(dwa), I(relb), (0.06, 0.071)[V], dyv(dwp), O(np.zeros((Bw, Rw * Rw, Hw * 32), np.int8)),
-                                              Bw, Rw, 7, sh, Hw, 32]))
-    wtab = iv.freeze.shiftmax_tables(np.float32((0.06, 0.071)[V]))
-    for sh in (0, 3):
-        cs.append(("window_attention_fused_lut", [I(qkvw), dyv(dwq), dyv(dwa), I(relb), (0.06, 0.071)[V], I(wtab["aq"]), I(wtab["t"]), I(wtab["cls"]),
-                                                  int(wtab["NC"]), int(wtab["t"].size), int(wtab["dmin"]), dyv(dwp),
-                                                  O(np.zeros((Bw, Rw * Rw, Hw * 32), np.int8)), Bw, Rw, 7, sh, Hw, 32]))
-    # ---- the uint8 front end (N3): ToTensor -> Normalize -> input QuantAct; antialiased bicubic resize + centre crop
-    u8 = rng.integers(0, 256, (2, 37, 53, 3), dtype=np.uint8)
-    u8.reshape(-1)[:256] = np.arange(256, dtype=np.uint8)
-    mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
-    cs.append(("normalize_quantize_u8", [I(u8), 2, 37, 53, ("host", mean), ("host", std), 0.0207, O(np.zeros((2, 3, 37, 53), np.int8))]))
-    big = rng.integers(0, 256, (2, 60, 83, 3), dtype=np.uint8)
-    cs.append(("resize_center_crop_u8", [I(big), 2, 60, 83, 40, 32, O(np.zeros((2, 60, 32, 3), np.float32)), O(np.zeros((2, 32, 32, 3), np.uint8))]))
-    tall = rng.integers(0, 256, (1, 75, 50, 3), dtype=np.uint8)                        # portrait, upscaling
-    cs.append(("resize_center_crop_u8", [I(tall), 1, 75, 50, 64, 56, O(np.zeros((1, 75, 56, 3), np.float32)), O(np.zeros((1, 56, 56, 3), np.uint8))]))
-    return cs
-
-
-def _run(fn, handle, args, to_ptr):
-    outs, call = [], [handle]
-    for a in args:
-        if isinstance(a, tuple) and a[0] == "host":          # a HOST array on both sides (mean / std of the normalisation)
-            call.append(a[1].ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
-        elif isinstance(a, tuple):
-            buf = to_ptr(a[1], a[0] == "out")
-            call.append(buf[0])
-            if a[0] == "out":
-                outs.append(buf[1])
-        else:
-            call.append(a)
-    st = fn(*call)
-    assert st == 0, st
-    return outs
+# ---------------------------------------------------------------- the same calls through both libraries (tests/abi_cases.py)
 
 
 @pytest.mark.gpu
