@@ -247,6 +247,22 @@ SIGNATURES = {
     "ivit_vit_predict_graph_create": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P, _P, _I, _P, _P, ctypes.POINTER(_P)],
     "ivit_swin_predict_graph_create": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P, _P, _I, _P, _P, ctypes.POINTER(_P)],
 }
+
+
+class ImageDesc(ctypes.Structure):
+    """struct ivit_image_desc: image i of a ragged batch is h * w * 3 bytes at pixels + offset, uint8 HWC"""
+    _fields_ = [("offset", ctypes.c_int64), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+# The PIL-pinned ragged front end (include/ivit.h; csrc/ivit_preprocess.h), bound like SIGNATURES and walked by load() in the same
+# way.  A table of its own: tests/abi_cases.py holds one case per name of SIGNATURES in the shape its twin tables know, and these
+# entries take a host AND a device descriptor table; their memory contract is tested in tests/test_pil_resize_gpu.py on the same
+# arena harness.
+_D = ctypes.POINTER(ImageDesc)
+FRONT_END_SIGNATURES = {
+    "ivit_resize_center_crop_u8_pil": [_P, _P, ctypes.c_size_t, _D, _P, _I, _I, _I, _P],
+    "ivit_eval_transform_u8": [_P, _P, ctypes.c_size_t, _D, _P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _P],
+}
 OTHER_SYMBOLS = ["ivit_version", "ivit_status_string", "ivit_last_error", "ivit_linear_plan_destroy", "ivit_mlp_plan_destroy", "ivit_linear_plan_query", "ivit_mlp_plan_select"]
 
 _lib = None
@@ -261,10 +277,11 @@ def load():
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
     lib = ctypes.CDLL(SO_PATH)
-    for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = ctypes.c_int
+    for table in (SIGNATURES, FRONT_END_SIGNATURES):
+        for name, args in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes = args
+            fn.restype = ctypes.c_int
     lib.ivit_version.restype = ctypes.c_int
     lib.ivit_status_string.restype = ctypes.c_char_p
     lib.ivit_status_string.argtypes = [ctypes.c_int]

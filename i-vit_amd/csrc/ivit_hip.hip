@@ -28,6 +28,7 @@
 #include "ivit_gemm_ws.h"
 #include "ivit_swin12.h"
 #include "ivit_topk.h"
+#include "ivit_preprocess.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -205,6 +206,63 @@ int ivit_normalize_quantize_u8(ivit_handle h, const uint8_t *hwc, int B, int H, 
         hwc, B, H, W, mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], scale, nchw);
     LAUNCH_CHECK(h);
     return IVIT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the PIL-pinned ragged front end (ivit_preprocess.h)
+// The checks of the host descriptor table, then ONE launch over the device table: ceil(crop / PIL_BAND) x B workgroups, a function of
+// B and crop only.  `fn` names the entry in ivit_last_error.
+template <bool NCHW>
+static int launch_pil_eval(ivit_handle h, const char *fn, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *desc_host,
+                           const ivit_image_desc *desc_dev, int B, int size, int crop, const float *mean, const float *std_, float scale,
+                           void *out) {
+    auto fail = [&](const char *msg, int i) {
+        if (i >= 0) snprintf(h->err, sizeof(h->err), "%s: image %d: %s", fn, i, msg);
+        else snprintf(h->err, sizeof(h->err), "%s: %s", fn, msg);
+        return IVIT_ERR_INVALID;
+    };
+    if (!(pixels && desc_host && desc_dev && out && B > 0 && size > 0 && crop > 0)) return fail("bad arguments", -1);
+    if (NCHW) {
+        if (!(mean && std_ && scale > 0.f)) return fail("bad arguments", -1);
+        if (!(std_[0] != 0.f && std_[1] != 0.f && std_[2] != 0.f)) return fail("zero std", -1);
+    }
+    const int nbands = (crop + PIL_BAND - 1) / PIL_BAND;
+    if ((long long)nbands * B > 0x7fffffffLL) return fail("B * ceil(crop / 32) exceeds the grid", -1);
+    for (int i = 0; i < B; ++i) {
+        const ivit_image_desc &d = desc_host[i];
+        if (d.h <= 0 || d.w <= 0) return fail("non-positive side", i);
+        if (d.offset < 0) return fail("negative offset", i);
+        const unsigned __int128 end = (unsigned __int128)d.offset + (unsigned __int128)d.h * (unsigned __int128)d.w * 3u;
+        if (end > (unsigned __int128)pixels_bytes) return fail("reaches past pixels_bytes", i);
+        long long Hr, Wr;                  // torchvision Resize(int), as in ivit_resize_center_crop_u8 and pil_eval_kernel
+        if (d.h <= d.w) { Hr = size; Wr = (long long)size * d.w / d.h; }
+        else { Wr = size; Hr = (long long)size * d.h / d.w; }
+        if (crop > Hr || crop > Wr) return fail("crop larger than the resized image", i);
+    }
+    const float z = 0.f;
+    const int st = launch_dyn<pil_eval_kernel<NCHW>>(h, dim3((unsigned)(nbands * B)), dim3(PIL_THREADS), (size_t)PIL_LDS_BYTES,
+                                                      (const unsigned char *)pixels, desc_dev, size, crop, nbands, NCHW ? mean[0] : z,
+                                                      NCHW ? mean[1] : z, NCHW ? mean[2] : z, NCHW ? std_[0] : z, NCHW ? std_[1] : z,
+                                                      NCHW ? std_[2] : z, NCHW ? scale : z, (unsigned char *)out);
+    if (st != IVIT_OK) return st;
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" {
+
+int ivit_resize_center_crop_u8_pil(ivit_handle h, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *desc_host,
+                                   const ivit_image_desc *desc_dev, int B, int size, int crop, uint8_t *out_hwc) {
+    CHECK_H(h);
+    return launch_pil_eval<false>(h, __func__, pixels, pixels_bytes, desc_host, desc_dev, B, size, crop, nullptr, nullptr, 0.f, out_hwc);
+}
+
+int ivit_eval_transform_u8(ivit_handle h, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *desc_host,
+                           const ivit_image_desc *desc_dev, int B, int size, int crop, const float mean[3], const float std_[3],
+                           float scale, int8_t *nchw) {
+    CHECK_H(h);
+    return launch_pil_eval<true>(h, __func__, pixels, pixels_bytes, desc_host, desc_dev, B, size, crop, mean, std_, scale, nchw);
 }
 
 }  // extern "C"

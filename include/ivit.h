@@ -112,10 +112,50 @@ int ivit_normalize_quantize_u8(ivit_handle h, const uint8_t *hwc, int B, int H, 
 /* Resize(size, interpolation=bicubic) + CenterCrop(crop) of the same eval transform (utils/data_utils.py:82-88) on the
  * device: hwc uint8 [B, H0, W0, 3] -> out_hwc uint8 [B, crop, crop, 3] (feed it to ivit_normalize_quantize_u8).  The
  * shorter side is resized to `size` (the longer to int(size * long / short)), antialiased separable bicubic (a = -0.5)
- * in fp32, rne, clamp; then the centre crop.  workspace: B * H0 * crop * 3 floats (caller-owned).  The reference resizes
- * with PIL, which this image does not have: the pin is torch's antialiased bicubic (tests/golden/resize.npz).       */
+ * in fp32, rne, clamp; then the centre crop.  workspace: B * H0 * crop * 3 floats (caller-owned).
+ * Two front ends restate that transform, and they are pinned to different things:
+ *   - this entry is pinned to TORCH's antialiased bicubic (tests/golden/resize.npz, within 1 LSB on < 1e-3 of the pixels).  It
+ *     is not what the reference computes: the reference resizes PIL images, and PIL's filter differs from torch's by more than
+ *     rounding (22-bit fixed point, a uint8 intermediate between the two passes);
+ *   - ivit_resize_center_crop_u8_pil and ivit_eval_transform_u8 below are pinned to PIL's own bytes
+ *     (tests/golden/pil_resize.npz) and take images of different sizes in one call.  A count that is to equal the
+ *     reference's `quant_train.py --evaluate` goes through those.                                                         */
 int ivit_resize_center_crop_u8(ivit_handle h, const uint8_t *hwc, int B, int H0, int W0, int size, int crop,
                                float *workspace, uint8_t *out_hwc);
+
+/* One image of a ragged batch: h * w * 3 bytes at pixels + offset, uint8 HWC, dense.  No alignment requirement on offset. */
+typedef struct ivit_image_desc {
+    int64_t offset;
+    int32_t h, w;
+} ivit_image_desc;
+
+/* Resize(size, interpolation=3) + CenterCrop(crop) of the reference's eval transform (utils/data_utils.py:82-92:
+ * transforms.Resize on PIL images, then transforms.CenterCrop) for B images of DIFFERENT sizes, in one launch, bit-exact with
+ * PIL: the pin is PIL's own output, Image.resize((Wr, Hr), Image.BICUBIC) then the crop (tests/golden/pil_resize.npz; every byte,
+ * no tolerance).  Sizes and crop offsets follow torchvision, as in ivit_resize_center_crop_u8: the shorter side becomes `size`,
+ * the longer int(size * long / short) in integers; offsets rint((dim - crop) / 2.0), ties to even.  The arithmetic is PIL's:
+ * coefficients in double, 22-bit fixed point, horizontal pass into uint8, then vertical; an axis whose length does not change
+ * is copied (csrc/ivit_preprocess.h states it line by line, ivit_amd.preprocess.pil_resize_center_crop_reference in numpy).
+ * out_hwc uint8 [B, crop, crop, 3].
+ * desc_host and desc_dev are the SAME B records, on the host and on the device (the caller places the device copy, as it places
+ * every other constant).  The call validates the host copy — h, w > 0; offset >= 0; offset + h * w * 3 <= pixels_bytes; crop <=
+ * both resized sides — and on a failed check returns IVIT_ERR_INVALID with the image's index in ivit_last_error, nothing
+ * launched.  The kernel reads ONLY the device copy: a replay of a captured graph reads the device table again, so whatever it
+ * holds then must describe images for which the captured call's checks hold (inside pixels_bytes, crop inside the resized image).
+ * Every image that ivit_resize_center_crop_u8 accepts is accepted.  No workspace.  pixels, the offsets and the output take any
+ * address (byte accesses only).                                                                                          */
+int ivit_resize_center_crop_u8_pil(ivit_handle h, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *desc_host,
+                                   const ivit_image_desc *desc_dev, int B, int size, int crop, uint8_t *out_hwc);
+
+/* The whole eval transform of the reference (utils/data_utils.py:82-92: Resize, CenterCrop, ToTensor, Normalize; then the input
+ * QuantAct, vit_quant.py:257) on a ragged batch in one launch: the bytes of ivit_resize_center_crop_u8_pil taken through the
+ * 3 x 256 table of ivit_normalize_quantize_u8 with the HWC -> CHW transpose, nchw int8 [B, 3, crop, crop]; the cropped uint8
+ * image is never written.  Equal, byte for byte, to ivit_normalize_quantize_u8 on PIL's bytes: the pin is PIL
+ * (tests/golden/pil_resize.npz).  Descriptors, checks, graph replay and alignment as above; mean_host / std_host are HOST
+ * arrays of 3 floats.                                                                                                     */
+int ivit_eval_transform_u8(ivit_handle h, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *desc_host,
+                           const ivit_image_desc *desc_dev, int B, int size, int crop, const float mean_host[3],
+                           const float std_host[3], float scale, int8_t *nchw);
 
 /* ---- a1  QuantLinear.forward  (quant_modules.py:67-97) — integer accumulators.
  * acc[i,j] = sum_k x[i,k]*w[j,k] + bias[j];  x int8 [M,K], w int8 [N,K], K % 16 == 0. */

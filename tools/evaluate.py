@@ -4,9 +4,15 @@
     python tools/evaluate.py data.npz --model deit_tiny --golden tests/golden/deit_tiny_b1.npz
     python tools/evaluate.py data.npz --model deit_small --state-dict checkpoint.pth.tar --batch 128 --topk 1 5
 
-data.npz holds `images` and `labels` [N].  images uint8 [N, H, W, 3]: raw pixels, taken through the reference's eval transform on
-the device (resize --resize, centre crop to the model's input, normalise, input QuantAct).  images int8 [N, C, S, S]: already
-quantised at the model's input scale, fed as they are.
+data.npz holds `labels` [N] and the images in one of three forms:
+  images uint8 [N, H, W, 3]   raw pixels of one size, taken through the reference's eval transform on the device (resize --resize,
+                              centre crop to the model's input, normalise, input QuantAct).  --resample torch (the default) is the
+                              torch-pinned transform (ivit_amd.preprocess.eval_transform), --resample pil the PIL-exact one;
+  pixels uint8 [total], offsets int64 [N], shapes int32 [N, 2]
+                              raw pixels of DIFFERENT sizes, image i = shapes[i] = (h, w) HWC at pixels[offsets[i]:].  The buffer
+                              is uploaded once per rank and every batch is one launch of eval_transform_pil: the bytes PIL hands
+                              the reference (utils/data_utils.py:82-92), so the count is the one `quant_train.py --evaluate` gives;
+  images int8 [N, C, S, S]    already quantised at the model's input scale, fed as they are.
 The model is a name from ivit_amd.CONFIGS / SWIN_CONFIGS with either
   --golden F      the seeded synthetic weights and the calibrated scales recorded in a tests/golden fixture, or
   --state-dict F  a reference state dict / checkpoint (float parameters and act_scaling_factor buffers; ivit_amd.checkpoint).
@@ -55,6 +61,8 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--topk", type=int, nargs="+", default=[1, 5])
     ap.add_argument("--resize", type=int, default=0, help="shorter side before the centre crop (default: int(crop / 0.875))")
+    ap.add_argument("--resample", choices=("torch", "pil"), default="torch",
+                    help="uint8 [N, H, W, 3] images: the torch-pinned resize (default) or the PIL-exact one; ragged files are always pil")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/evaluate.py needs a HIP device; the product path has no CPU fallback")
@@ -67,20 +75,45 @@ def main():
         dist.init_process_group(os.environ.get("IVIT_DIST_BACKEND", "nccl"), rank=rank, world_size=world)
     cfg, eng, s_in = build_engine(args, device)
     d = np.load(args.data)
-    images, labels = d["images"], d["labels"].astype(np.int64).reshape(-1)
-    if len(images) != len(labels):
-        raise SystemExit(f"{len(images)} images but {len(labels)} labels")
-    transform = None
-    if images.dtype == np.uint8 and images.ndim == 4 and images.shape[-1] == 3:
-        from ivit_amd.preprocess import eval_transform
-        size = args.resize or int(cfg.img_size / 0.875)
-        transform = lambda u8: eval_transform(u8, s_in, size, cfg.img_size)      # noqa: E731
-    elif not (images.dtype == np.int8 and images.shape[1:] == (cfg.in_chans, cfg.img_size, cfg.img_size)):
-        raise SystemExit(f"images must be uint8 [N, H, W, 3] or int8 [N, {cfg.in_chans}, {cfg.img_size}, {cfg.img_size}]; "
-                         f"got {images.dtype} {images.shape}")
+    labels = d["labels"].astype(np.int64).reshape(-1)
+    size = args.resize or int(cfg.img_size / 0.875)
     lo, hi = ivdist.shard_range(len(labels), rank, world)
-    mine = torch.from_numpy(np.ascontiguousarray(images[lo:hi])).to(device)      # this rank's share only
     share = torch.from_numpy(labels[lo:hi]).to(device)                           # once: no copy inside evaluate's loop
+    transform = None
+    if "pixels" in d.files or (args.resample == "pil" and d["images"].dtype == np.uint8):
+        from ivit_amd.preprocess import DESC_DTYPE, RaggedImages, eval_transform_pil
+        if "pixels" in d.files:
+            pixels, offsets, shapes = d["pixels"], d["offsets"].astype(np.int64).reshape(-1), d["shapes"].astype(np.int64).reshape(-1, 2)
+        else:                                                                    # equal sizes, described as a ragged batch
+            images = d["images"]
+            if images.ndim != 4 or images.shape[-1] != 3:
+                raise SystemExit(f"images must be uint8 [N, H, W, 3]; got {images.shape}")
+            pixels = images.reshape(-1)
+            shapes = np.tile(np.array(images.shape[1:3], np.int64), (len(images), 1))
+            offsets = np.arange(len(images), dtype=np.int64) * int(np.prod(images.shape[1:]))
+        if pixels.dtype != np.uint8 or not (len(offsets) == len(shapes) == len(labels)):
+            raise SystemExit(f"pixels must be uint8 and offsets, shapes, labels of one length; got {pixels.dtype}, "
+                             f"{len(offsets)}, {len(shapes)}, {len(labels)}")
+        ends = offsets + shapes[:, 0] * shapes[:, 1] * 3
+        if (shapes < 1).any() or (offsets < 0).any() or (ends > pixels.size).any():
+            raise SystemExit("an image record lies outside `pixels`")
+        # this rank's share of the packed buffer only, uploaded once; offsets relative to it
+        first, last = (int(offsets[lo:hi].min()), int(ends[lo:hi].max())) if hi > lo else (0, 0)
+        desc = np.zeros(hi - lo, DESC_DTYPE)
+        desc["offset"], desc["h"], desc["w"] = offsets[lo:hi] - first, shapes[lo:hi, 0], shapes[lo:hi, 1]
+        mine = RaggedImages(torch.from_numpy(np.ascontiguousarray(pixels[first:last])).to(device), desc)
+        transform = lambda rag: eval_transform_pil(rag, s_in, size, cfg.img_size)      # noqa: E731
+    else:
+        images = d["images"]
+        if len(images) != len(labels):
+            raise SystemExit(f"{len(images)} images but {len(labels)} labels")
+        if images.dtype == np.uint8 and images.ndim == 4 and images.shape[-1] == 3:
+            from ivit_amd.preprocess import eval_transform
+            transform = lambda u8: eval_transform(u8, s_in, size, cfg.img_size)      # noqa: E731
+        elif not (images.dtype == np.int8 and images.shape[1:] == (cfg.in_chans, cfg.img_size, cfg.img_size)):
+            raise SystemExit(f"images must be uint8 [N, H, W, 3] or int8 [N, {cfg.in_chans}, {cfg.img_size}, {cfg.img_size}]; "
+                             f"got {images.dtype} {images.shape}")
+        mine = torch.from_numpy(np.ascontiguousarray(images[lo:hi])).to(device)      # this rank's share only
     batches = ((mine[a:a + args.batch], share[a:a + args.batch]) for a in range(0, hi - lo, args.batch))
     out = evaluate(eng, batches, topk=args.topk, transform=transform, rank=rank, world=world)       # ends with the one all_reduce
     if rank == 0:
