@@ -83,7 +83,7 @@ def vit_native_params(cfg, table, f32, host, base):
     prm = L.VitParams()
     prm.pe_w, prm.pe_b, prm.pe_dy = ptr("patch_embed.proj.w"), ptr("patch_embed.proj.b"), ptr("patch_embed.proj.dy")
     prm.z_cls, prm.pos, prm.dy_x, prm.dy_pos = ptr("z_cls"), ptr("pos"), dy("embed.dy_x"), dy("embed.dy_pos")
-    prm.blocks_host = ctypes.cast(blocks, ctypes.POINTER(L.VitBlock))
+    prm.blocks_host = ctypes.addressof(blocks)
     prm.s_ln, prm.n_bias_int, prm.n_sc, prm.n_dy = f32["ln.s"], ptr("norm.bias_int"), ptr("norm.sc"), ptr("norm.dy")
     prm.head_w, prm.head_b = ptr("head.w"), ptr("head.b")
     c = L.VitConfig(cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads,

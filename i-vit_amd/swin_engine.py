@@ -84,8 +84,8 @@ def swin_native_params(cfg, table, f, dy, base):
             g.s_in, g.n, g.red = f[p + "s_in"], ln(p + "norm"), lin(p + "reduction")
     prm = L.SwinParams()
     prm.pe, prm.s_bn, prm.pn, prm.dy_qact1 = lin("patch_embed.proj"), f["patch_embed.s_bn"], ln("patch_embed.norm"), a("dy_qact1")
-    prm.blocks_host = ctypes.cast(blocks, ctypes.POINTER(L.SwinBlock))
-    prm.merges_host = ctypes.cast(merges, ctypes.POINTER(L.SwinMerge))
+    prm.blocks_host = ctypes.addressof(blocks)
+    prm.merges_host = ctypes.addressof(merges)
     prm.s_norm_in, prm.n, prm.dy_pool = f["norm.s_in"], ln("norm"), dy["dy_pool"]
     prm.head_w, prm.head_b = a("head.w"), a("head.b")
     prm.s_pool = f["pool.s_in"]

@@ -27,15 +27,6 @@ import gen_twin_header  # noqa: E402
 
 _P = ctypes.c_void_p
 
-# the two plan calls without a handle argument are declared outside _lib.SIGNATURES (which prepends nothing, but whose
-# Handle.call wrapper does): same argtypes as _lib.load() sets
-_EXTRA = {"linear_plan_destroy": [_P], "mlp_plan_destroy": [_P], "linear_plan_query": [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]}
-
-
-def _sig(name):
-    return _EXTRA.get(name) or _lib.SIGNATURES["ivit_" + name]
-
-
 def hp(a):
     return a.ctypes.data_as(_P)
 
@@ -47,12 +38,7 @@ def dyv(d):
 def load_twin():
     """the CPU twin (oracle/libivit_oracle.so, built on demand) with the C-ABI's own ctypes signatures"""
     from oracle import oracle as orc
-    lib = ctypes.CDLL(orc.build())
-    for name in gen_twin_header.TWIN:
-        fn = getattr(lib, "ivit_cpu_" + name)           # AttributeError = a declared twin is not exported
-        fn.argtypes = _sig(name)                        # the C-ABI's own ctypes signature, unchanged
-        fn.restype = ctypes.c_int
-    return lib
+    return _lib.bind(ctypes.CDLL(orc.build()), gen_twin_header.TWIN, prefix="ivit_cpu_")     # AttributeError = a declared twin is not exported
 
 
 def _io():
@@ -465,8 +451,15 @@ def hip_cases(H, rng):
     return cs
 
 
-# every entry of _lib.SIGNATURES is in one of the two tables, or here with its reason
+# every prototype of include/ivit.h is in one of the two tables, or here with its reason
 EXCLUDED = {
+    "version": "returns IVIT_VERSION: no argument",
+    "status_string": "status code -> static string: no tensor argument",
+    "last_error": "returns the handle's message buffer: no tensor argument",
+    "mlp_plan_select": "tuning switch of a plan, a host field: part of the setup of the mlp_fused_planned cases",
+    **{n: "tests/test_pil_resize_gpu.py runs them on the arena harness" for n in ("resize_center_crop_u8_pil", "eval_transform_u8")},
+    **{n: "plan life cycle, no handle and no tensor argument: the teardown of the planned cases" for n in ("linear_plan_destroy", "mlp_plan_destroy")},
+    "linear_plan_query": "query of a plan: writes two host ints",
     **{n: "handle life cycle and settings: no tensor argument" for n in ("create", "destroy", "set_stream", "set_cu_share")},
     **{n: "build-time plan call (allocates, synchronises): the setup of the planned cases" for n in
        ("linear_plan_create", "linear_plan_prepare_ws", "mlp_plan_create")},
@@ -490,9 +483,9 @@ def table_names():
 
 
 def uncovered_entry_points():
-    """names of _lib.SIGNATURES that are in neither table and not excluded, and stale exclusions: both must be empty"""
+    """prototypes of include/ivit.h that are in neither table and not excluded, and stale exclusions: both must be empty"""
     twinned, hip = table_names()
-    every = {n[len("ivit_"):] for n in _lib.SIGNATURES}
+    every = {n[len("ivit_"):] for n in _lib.ABI.functions}
     return sorted(every - twinned - hip - set(EXCLUDED)), sorted((set(EXCLUDED) - every) | (set(EXCLUDED) & (twinned | hip)))
 
 

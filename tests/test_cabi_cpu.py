@@ -1,9 +1,13 @@
-"""CPU: the C-ABI library builds/loads and exports every symbol include/ivit.h declares;
+"""CPU: the C-ABI library builds/loads and exports every symbol include/ivit.h declares, the binding derived from the header
+(ivit_amd/_abi.py) has the C compiler's struct layouts and binds every prototype;
 host-side freeze logic agrees with the oracle's independent restatement."""
+import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
+import pytest
 
 from conftest import ROOT, load_golden, golden_scales
 import ivit_amd as iv
@@ -22,6 +26,130 @@ def test_library_exports_header_symbols():
         assert n in names, f"{n} bound in python but not declared in ivit.h"
     assert lib.ivit_version() >= 100
     assert lib.ivit_status_string(1) == b"invalid argument"
+
+
+def test_struct_layouts_are_the_c_compilers(tmp_path):
+    """sizeof and every offsetof of every struct of include/ivit.h, printed by a C program that includes the real header, equal those
+    of the generated Structures: independent of the parser, which must not drop, reorder or mistype a field"""
+    structs = _lib.ABI.structs
+    assert len(structs) == 11 and set(structs) == set(_lib.STRUCT_NAMES)
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "ivit.h"', "int main(void) {"]
+    for name, fields in structs.items():
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name}.{d.name} %zu\\n", offsetof({name}, {d.name}));' for d in fields]
+    (tmp_path / "layout.c").write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    subprocess.run(["cc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
+    want = dict(line.split() for line in subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.splitlines())
+    got = {}
+    for name, fields in structs.items():
+        cls = getattr(_lib, _lib.STRUCT_NAMES[name])
+        assert [f[0] for f in cls._fields_] == [d.name for d in fields]
+        got[name] = str(ctypes.sizeof(cls))
+        got.update({f"{name}.{d.name}": str(getattr(cls, d.name).offset) for d in fields})
+    assert got == want, sorted(k for k in want if got.get(k) != want[k])
+    assert len(want) == 11 + sum(len(f) for f in structs.values()) and len(structs["ivit_vit_block"]) == 35 and len(structs["ivit_swin_block"]) == 25
+
+
+def test_every_prototype_of_the_header_is_bound():
+    """after load(), every prototype has argtypes of the header's parameter count and the mapped restype"""
+    iv.build()
+    lib = _lib.load()
+    fns = _lib.ABI.functions
+    assert len(fns) == 99 and set(fns) == set(_lib.SIGNATURES) == set(_lib.RESTYPES)
+    assert _lib.IVIT_VERSION == 111 == lib.ivit_version()
+    for name, fn in fns.items():
+        bound = getattr(lib, name)
+        assert len(bound.argtypes) == len(fn.params), name
+        assert bound.argtypes == _lib.SIGNATURES[name], name
+        assert bound.restype is (ctypes.c_char_p if fn.ret.type == "const char *" else ctypes.c_int), name
+    assert lib.ivit_status_string(1) == b"invalid argument"
+    # the rule at one prototype of each kind: by-value struct, int64_t, size_t, typed pointers, array parameters, handles
+    P, I = ctypes.c_void_p, ctypes.c_int
+    assert _lib.SIGNATURES["ivit_requant_i32_bcast"] == [P, P, _lib.Dyadic, P, ctypes.c_int64, _lib.Dyadic, I, P, ctypes.c_int64]
+    assert _lib.SIGNATURES["ivit_eval_transform_u8"] == [P, P, ctypes.c_size_t, P, P, I, I, I, P, P, ctypes.c_float, P]
+    assert _lib.SIGNATURES["ivit_swin_fused_mlp_blocks"] == [P, I, P] and _lib.SIGNATURES["ivit_version"] == []
+    assert (_lib.IVIT_OK, _lib.IVIT_ERR_INVALID, _lib.IVIT_ERR_HIP, _lib.IVIT_ERR_UNSUPPORTED, _lib.IVIT_ERR_NO_DEVICE) == (0, 1, 2, 3, 4)
+
+
+_SNIPPET = """
+/* every construct of include/ivit.h
+   in a few lines */
+#ifndef X_H
+#define X_H
+#define X_VERSION 7
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef struct x_ctx *x_handle;
+typedef struct x_pair { double m; /* a */ double r; } x_pair;
+enum { X_OK = 0, X_BAD = 1 };
+typedef struct x_desc {
+    int64_t offset;
+    int32_t h, w; const x_pair *tab; x_pair a, b;
+    int depths[4];
+    x_handle owner;
+} x_desc;
+int x_version(void);
+const char *x_name(int status);
+int x_run(x_handle h, const uint8_t *px, size_t bytes, const x_desc *desc_host, x_pair p, const float mean[3],
+          int64_t n, void **out);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_parser_reads_every_construct_the_header_uses():
+    from ivit_amd import _abi
+    D = _abi.Decl
+    abi = _abi.parse(_SNIPPET)
+    assert abi.handles == ["x_handle"] and dict(abi.constants) == {"X_VERSION": 7, "X_OK": 0, "X_BAD": 1}
+    assert list(abi.structs) == ["x_pair", "x_desc"]
+    assert abi.structs["x_pair"] == [D("m", "double", 0, None, "double"), D("r", "double", 0, None, "double")]
+    assert abi.structs["x_desc"] == [
+        D("offset", "int64_t", 0, None, "int64_t"), D("h", "int32_t", 0, None, "int32_t"), D("w", "int32_t", 0, None, "int32_t"),
+        D("tab", "x_pair", 1, None, "const x_pair *"), D("a", "x_pair", 0, None, "x_pair"), D("b", "x_pair", 0, None, "x_pair"),
+        D("depths", "int", 0, 4, "int [4]"), D("owner", "x_handle", 0, None, "x_handle")]
+    assert list(abi.functions) == ["x_version", "x_name", "x_run"]
+    assert abi.functions["x_version"].params == [] and abi.functions["x_version"].text == "void"
+    assert abi.functions["x_name"].ret.type == "const char *"
+    run = abi.functions["x_run"]
+    assert [(p.type, p.name) for p in run.params] == [
+        ("x_handle", "h"), ("const uint8_t *", "px"), ("size_t", "bytes"), ("const x_desc *", "desc_host"), ("x_pair", "p"),
+        ("const float [3]", "mean"), ("int64_t", "n"), ("void **", "out")]
+    assert run.text == ("x_handle h, const uint8_t *px, size_t bytes, const x_desc *desc_host, x_pair p, const float mean[3], "
+                        "int64_t n, void **out")
+    S = _abi.structures(abi)
+    P = ctypes.c_void_p
+    assert S["x_desc"]._fields_ == [("offset", ctypes.c_int64), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("tab", P),
+                                    ("a", S["x_pair"]), ("b", S["x_pair"]), ("depths", ctypes.c_int * 4), ("owner", P)]
+    sig = _abi.signatures(abi, S)
+    assert sig["x_run"] == (ctypes.c_int, [P, P, ctypes.c_size_t, P, S["x_pair"], P, ctypes.c_int64, P])
+    assert sig["x_name"] == (ctypes.c_char_p, [ctypes.c_int]) and sig["x_version"] == (ctypes.c_int, [])
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int f(uint24_t x);", "uint24_t x"),                                           # an unknown type
+    ("typedef struct s { unsigned int a; } s;", "unsigned int a"),
+    ("int f(int n, int (*cb)(int));", "int (*cb)(int)"),                           # a function-pointer parameter
+    ("typedef struct s { void (*cb)(void); } s;", "void (*cb)(void)"),
+    ("typedef struct s { int a : 3; } s;", "int a : 3"),                            # a bit-field
+    ("typedef union u { int a; float b; } u;", "typedef union u"),                  # a union
+    ("typedef struct s { int k; union { int a; float b; } v; } s;", "typedef struct s"),
+    ("int f(int a);\ntypedef struct s { int a; int b;\nint g(int a);", "typedef struct s { int a; int b;"),   # an unterminated struct
+    ("int f(int);", "int"),                                                         # a parameter without a name
+    ("int f(void v);", "void v"),
+    ("enum { A, B };", "A"),                                                        # implicit enumerator values
+    ("#define SQ(x) ((x) * (x))\nint f(int a);", "#define SQ(x)"),                  # a macro
+    ("int f(int a); /* never closed", "never closed"),
+    ("struct s *f(int a);", "struct s *f"),
+])
+def test_parser_refuses_what_it_does_not_know(text, names):
+    from ivit_amd import _abi
+    with pytest.raises(_abi.AbiError) as e:
+        _abi.parse(text)
+    assert names in str(e.value), str(e.value)
 
 
 def _device_code_object(so_path):

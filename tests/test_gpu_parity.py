@@ -705,16 +705,10 @@ def mlp_production_case():
     (oracle/ivit_twin.c chains the restated operators: layers_quant.py:144-153 + vit_quant.py:141-142).  The operator is
     row-wise, so the oracle's first M rows are the oracle's answer for the first M rows alone: one 50432-row CPU run (~20 s on
     the GPU box's host) serves every row count below."""
-    import os
-    import subprocess
-    from conftest import ROOT
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s"])
-    twin = ctypes.CDLL(os.path.join(ROOT, "oracle", "libivit_oracle.so"))
+    from abi_cases import load_twin
+    twin = load_twin()
     hp = lambda a: a.ctypes.data_as(_P)
     dyv = lambda d: _lib.Dyadic(float(d[0, 0]), float(d[0, 1]))
-    for name in ("linear_plan_create", "mlp_plan_create", "mlp_fused_planned", "shiftgelu_build_table", "mlp_plan_destroy", "linear_plan_destroy"):
-        getattr(twin, "ivit_cpu_" + name).argtypes = _lib.SIGNATURES.get("ivit_" + name, [_P])     # the destroy calls take the plan only
-        getattr(twin, "ivit_cpu_" + name).restype = ctypes.c_int
     M = 50432
     rng = np.random.default_rng(M)
     C, Hd = 384, 1536

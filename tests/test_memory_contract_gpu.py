@@ -65,7 +65,6 @@ NAMES = sorted(A.table_names()[0] | A.table_names()[1])
 def test_memory_contract(H, twin, name):
     mem, host = A.TorchMem(), A.NumpyMem()
     fn = getattr(H.lib, "ivit_" + name)
-    fn.argtypes = A._sig(name)
     todo = cases_of(H, name)
     assert todo
     for label, args, setup, twinned in todo:

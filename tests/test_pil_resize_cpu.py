@@ -109,9 +109,9 @@ def test_new_entries_are_declared_exported_and_bound():
     assert "typedef struct ivit_image_desc" in hdr
     for name in NEW:
         assert re.search(r"\bint\s+%s\s*\(" % name, hdr), name
-        assert hasattr(lib, name) and name in _lib.FRONT_END_SIGNATURES and name not in _lib.SIGNATURES
-        assert getattr(lib, name).argtypes == _lib.FRONT_END_SIGNATURES[name]
-    assert len(_lib.FRONT_END_SIGNATURES[NEW[0]]) == 9 and len(_lib.FRONT_END_SIGNATURES[NEW[1]]) == 12
+        assert hasattr(lib, name) and name in _lib.SIGNATURES
+        assert getattr(lib, name).argtypes == _lib.SIGNATURES[name]
+    assert len(_lib.SIGNATURES[NEW[0]]) == 9 and len(_lib.SIGNATURES[NEW[1]]) == 12
     assert ctypes.sizeof(_lib.ImageDesc) == 16 == pp.DESC_DTYPE.itemsize
     assert [pp.DESC_DTYPE.fields[n][1] for n in ("offset", "h", "w")] == [_lib.ImageDesc.offset.offset, _lib.ImageDesc.h.offset, _lib.ImageDesc.w.offset]
     # each declaration cites the reference's transform and names its pin

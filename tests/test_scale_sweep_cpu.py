@@ -4,21 +4,17 @@ modules).  tests/golden/ops.npz pins each operator at a handful of scales with r
 sequence depends on the scale runs at about 150 scales (48 for I-LayerNorm, 63 for the attention tables) on input blocks
 that cover its domain.  CPU only; tests/test_scale_sweep_gpu.py runs the HIP library over the same fixture."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 import ivit_amd as iv
 from ivit_amd import _lib
 from oracle import oracle as orc
 import scale_sweep as sw
-
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import gen_twin_header  # noqa: E402
+from abi_cases import load_twin
 
 _P = ctypes.c_void_p
 UNSUPPORTED = _lib.IVIT_ERR_UNSUPPORTED
@@ -32,13 +28,7 @@ def g():
 
 @pytest.fixture(scope="module")
 def twin():
-    lib = ctypes.CDLL(orc.build())
-    for name in gen_twin_header.TWIN:
-        if "ivit_" + name in _lib.SIGNATURES:
-            fn = getattr(lib, "ivit_cpu_" + name)
-            fn.argtypes = _lib.SIGNATURES["ivit_" + name]
-            fn.restype = ctypes.c_int
-    return lib
+    return load_twin()
 
 
 def hp(a):

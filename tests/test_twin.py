@@ -16,7 +16,7 @@ import ivit_amd as iv
 from conftest import golden_scales
 from ivit_amd import _lib
 
-from abi_cases import _EXTRA, _cases, _run, _sig, dyv, gen_twin_header, hp, load_twin  # noqa: E402
+from abi_cases import _cases, _run, dyv, gen_twin_header, hp, load_twin  # noqa: E402
 
 _P = ctypes.c_void_p
 
@@ -30,7 +30,7 @@ def test_twin_header_is_generated_from_the_c_abi():
     """oracle/ivit_twin.h == tools/gen_twin_header.py(include/ivit.h): same parameter lists by construction; ivit_twin.c
     includes it, so a drifting definition does not compile"""
     assert open(os.path.join(ROOT, "oracle", "ivit_twin.h")).read() == gen_twin_header.render()
-    assert set("ivit_" + n for n in gen_twin_header.TWIN) <= set(_lib.SIGNATURES) | set("ivit_" + n for n in _EXTRA)
+    assert set("ivit_" + n for n in gen_twin_header.TWIN) <= set(_lib.SIGNATURES)
 
 
 def test_twin_exports_every_declared_symbol(twin):
@@ -102,9 +102,7 @@ def test_every_twinned_entry_point_agrees_with_the_hip_library(twin, variant):
     seen = set()
     for name, args in cases:
         seen.add(name)
-        gfn = getattr(H.lib, "ivit_" + name)
-        gfn.argtypes = _sig(name)
-        gout = _run(gfn, H.h, args, to_dev)
+        gout = _run(getattr(H.lib, "ivit_" + name), H.h, args, to_dev)
         cout = _run(getattr(twin, "ivit_cpu_" + name), None, args, to_host)
         torch.cuda.synchronize()
         for i, (g, c) in enumerate(zip(gout, cout)):
@@ -138,7 +136,7 @@ def test_every_twinned_entry_point_agrees_with_the_hip_library(twin, variant):
     assert f(H.h, pg, _P(xd.data_ptr()), 8, _P(og.data_ptr()), M) == 0
     assert twin.ivit_cpu_linear_i8_requant_planned(None, pc, hp(x), 8, hp(oc), M) == 0
     assert np.array_equal(og.cpu().numpy(), oc)
-    H.lib.ivit_linear_plan_destroy.argtypes = [_P]
+    H.lib.ivit_linear_plan_destroy.argtypes = _lib.SIGNATURES["ivit_linear_plan_destroy"]
     assert H.lib.ivit_linear_plan_destroy(pg) == 0 and twin.ivit_cpu_linear_plan_destroy(pc) == 0
     # planned fused Mlp (D = 384): linear plans -> Mlp plan -> one call, on both sides
     Mm, Cm, Hm = (333, 2051)[variant], 384, 1536       # 2051 = 128 full tiles + 3 rows: several units per workgroup shape
