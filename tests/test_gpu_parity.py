@@ -1515,8 +1515,14 @@ def test_linear_plan_bounds_and_fallback(H):
     d2 = dev(iv.freeze.dyadic(np.full(N, 1e-6, np.float32), np.float32(0.05)))
     p2 = H.linear_plan(P(dev(w2)), P(bd), P(d2), N, K2)
     assert p2.pipelined_ok
-    fma2 = p2.single_fma_ok
-    out2 = torch.zeros(M, N, dtype=torch.int8, device="cuda")
+    # which form: the one-FMA requant exactly when NO z within the plan's bound 128 * sum|w| + |bias| of any channel rounds
+    # differently once and twice (tests/two_roundings.py enumerates those z exactly; tests/test_requant_two_roundings_gpu.py
+    # pins the decision where such a z exists).  Here (m = 1407374859, e = 46) there is none: the proof must succeed
+    import two_roundings as tr
+    m2, r2 = iv.freeze.dyadic(np.float32(1e-6), np.float32(0.05))[0]
+    zs = tr.differing(int(m2), int(round(-np.log2(r2))), 128 * 127 * K2 + int(np.abs(b).max()))
+    assert p2.single_fma_ok == (not zs) and p2.single_fma_ok, zs
+    out2 =torch.zeros(M, N, dtype=torch.int8, device="cuda")
     H.call("ivit_linear_i8_requant_planned", p2.p, P(dev(x2)), 8, P(out2), M)
     ref2 = orc.requant(orc.linear_i8(x2, w2, b), orc.dyadic(np.full(N, 1e-6, np.float32), np.float32(0.05)), 8)
     assert np.array_equal(out2.cpu().numpy().astype(np.int32), ref2)

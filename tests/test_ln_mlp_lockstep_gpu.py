@@ -41,12 +41,18 @@ class Case:
     that the hidden range is reached from LayerNorm's narrower rows); the LayerNorm's those of
     test_gpu_parity.py::test_layernorm_mlp_fused_equals_two_launches: half the channels of x16 divided by 64, weights of both signs, and
     (from 3 rows on) one all-constant row and one row at +-32767.  wide_ln: one channel's multiplier so large that the LayerNorm's
-    two-operation 8-bit requant is not provable (|c| (1.2e12 + 1.01 |bias_int|) >= 2^31) and the kernel takes its v_rndne_f64 form."""
+    two-operation 8-bit requant is not provable (|c| (1.2e12 + 1.01 |bias_int|) >= 2^31) and the kernel takes its v_rndne_f64 form.
+    tweak: called with the case once its host operands are drawn and before anything is uploaded; it may change them and may put
+    (m, e) into rows1 / rows2, rows of fc1's / fc2's per-channel multiplier table written as (m, 2^-e) directly."""
 
-    def __init__(self, H, C, M, seed, wide_ln=False):
+    def __init__(self, H, C, M, seed, wide_ln=False, tweak=None):
         self.H = H
+        self.rows1, self.rows2 = {}, {}
         self.host(C, M, seed, wide_ln)
-        self.upload()
+        if tweak is not None:
+            tweak(self)
+        if H is not None:               # H = None: the host operands and the oracle only (the CPU side of tests/test_mlp_rolesplit_gpu.py)
+            self.upload()
 
     def host(self, C, M, seed, wide_ln):
         rng = np.random.default_rng(seed)
@@ -78,8 +84,8 @@ class Case:
         H, C, HD = self.H, self.C, self.HD
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
         self.d = {k: up(getattr(self, k)) for k in ("w1", "b1", "w2", "b2", "x16", "bias_int", "sc")}
-        self.d["d1"] = up(iv.freeze.dyadic(self.s1, S_FC1_OUT))
-        self.d["d2"] = up(iv.freeze.dyadic(self.s2, S_FC2_OUT))
+        self.d["d1"] = up(self.table(iv.freeze.dyadic(self.s1, S_FC1_OUT), self.rows1))
+        self.d["d2"] = up(self.table(iv.freeze.dyadic(self.s2, S_FC2_OUT), self.rows2))
         self.d["dln"] = up(iv.freeze.dyadic(self.s_pre, S_LN_OUT))
         self.tab = torch.empty(65536, dtype=torch.int8, device="cuda")
         H.call("ivit_shiftgelu_build_table", float(S_GELU), dyv(iv.freeze.dyadic(np.float32(S_GELU * 2.0 ** -7), S_G_OUT)), P(self.tab))
@@ -87,6 +93,16 @@ class Case:
         H.call("ivit_linear_plan_create", P(self.d["w1"]), P(self.d["b1"]), P(self.d["d1"]), HD, C, ctypes.byref(self.p1))
         H.call("ivit_linear_plan_create", P(self.d["w2"]), P(self.d["b2"]), P(self.d["d2"]), C, HD, ctypes.byref(self.p2))
         H.call("ivit_mlp_plan_create", self.p1, self.p2, ctypes.byref(self.mp))
+
+    @staticmethod
+    def table(t, rows):
+        """a per-channel multiplier table (the library's [n, 2] array or the oracle's) with the rows written directly put in"""
+        for ch, (m, e) in rows.items():
+            if isinstance(t, np.ndarray):
+                t[ch] = (float(m), 2.0 ** -e)
+            else:
+                t[ch].m, t[ch].r = float(m), 2.0 ** -e
+        return t
 
     def args(self, out, dm=None, dr=None, x16=None):
         d = self.d
@@ -116,15 +132,32 @@ class Case:
 
     def oracle(self):
         """The CPU oracle's operators, every row: (norm2's 8-bit rows, hidden int8, out int32)."""
+        c = self.chain()
+        return c["a"], c["h"], c["o"]
+
+    def chain(self):
+        """oracle() with every intermediate: a (norm2's 8-bit rows), h (hidden), g (ShiftGELU + qact1), acc2 (fc2's accumulators
+        with the bias), t (qact2, 16 bit), o (the residual QuantAct)."""
         from oracle import oracle as orc
         z = orc.layernorm(self.x16, S_IN, self.bias_int, self.sc)
         a = orc.requant(z, orc.dyadic(self.s_pre, S_LN_OUT), 8)
-        h = orc.requant(orc.linear_i8(a.astype(np.int8), self.w1, self.b1), orc.dyadic(self.s1, S_FC1_OUT), 8)
+        h = orc.requant(orc.linear_i8(a.astype(np.int8), self.w1, self.b1), self.table(orc.dyadic(self.s1, S_FC1_OUT), self.rows1), 8)
+        return dict(a=a, h=h, **self.from_hidden(h, self.x16))
+
+    def from_hidden(self, h, x16):
+        """the chain behind fc1's QuantAct for hidden rows h and their identity rows x16: g, acc2, t, o"""
+        from oracle import oracle as orc
         g = orc.requant(orc.shiftgelu(h.astype(np.int8), S_GELU).astype(np.int32), orc.dyadic(np.float32(S_GELU * 2.0 ** -7), S_G_OUT), 8)
-        t = orc.requant(orc.linear_i8(g.astype(np.int8), self.w2, self.b2), orc.dyadic(self.s2, S_FC2_OUT), 16)
-        o = orc.requant(t, orc.dyadic(np.float32(2e-4), np.float32(3.1e-4)), 16, z_id=self.x16.astype(np.int32),
-                        dy_id=orc.dyadic(np.float32(2.7e-4), np.float32(3.1e-4)))
-        return a, h, o
+        acc2 = orc.linear_i8(g.astype(np.int8), self.w2, self.b2)
+        t = orc.requant(acc2, self.table(orc.dyadic(self.s2, S_FC2_OUT), self.rows2), 16)
+        return dict(g=g, acc2=acc2, t=t, o=self.residual_act(t, x16))
+
+    @staticmethod
+    def residual_act(t, x16):
+        """the oracle's residual QuantAct of qact2's rows t with the identity rows x16"""
+        from oracle import oracle as orc
+        return orc.requant(np.ascontiguousarray(t, np.int32), orc.dyadic(np.float32(2e-4), np.float32(3.1e-4)), 16,
+                           z_id=np.ascontiguousarray(x16).astype(np.int32), dy_id=orc.dyadic(np.float32(2.7e-4), np.float32(3.1e-4)))
 
     def close(self):
         self.H.lib.ivit_mlp_plan_destroy(self.mp)

@@ -71,11 +71,11 @@ def tokens(M):
 
 
 @functools.lru_cache(maxsize=None)
-def layer(N, bits, fma):
-    """A frozen QuantLinear 192 -> N with an 8- or 16-bit QuantAct behind it.  The output scale puts the accumulators' standard deviation at
-    0.4 of the output range, so that both clamps are reached.  fma = False: channel 5 gets a negative multiplier and a bias of 9.5e6, so
+def layer(N, bits, fma, K=K):
+    """A frozen QuantLinear K -> N (192 here; tests/test_requant_two_roundings_gpu.py takes the recipe to K = 384 and 1536) with an 8- or
+    16-bit QuantAct behind it.  The output scale puts the accumulators' standard deviation at 0.4 of the output range, so that both clamps are reached.  fma = False: channel 5 gets a negative multiplier and a bias of 9.5e6, so
     that |m| * (128 * sum|w| + |bias|) >= 2^53 and the plan cannot take the one-FMA requant (linear_plan_fma_kernel refuses c <= 0)."""
-    rng = np.random.default_rng(N * 4 + bits + (0 if fma else 1))
+    rng = np.random.default_rng(N * 4 + bits + (0 if fma else 1) + (0 if K == 192 else K))
     w = np.rint(rng.normal(0, 45, (N, K)).clip(-128, 127)).astype(np.int8)
     b = rng.integers(-2 ** 14, 2 ** 14, N).astype(np.int32)
     s_pre = (10 ** rng.uniform(-5.5, -5, N)).astype(np.float32)
