@@ -269,7 +269,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 1) void attn_fused_kernel(AttnArgs 
                 acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qf, acc, 0, 0, 0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    int v = FAST ? min(max(__double2loint(__builtin_fma((double)acc[r], c_qk, 6755399441055744.0 + VB)), VB - 128), VB + 127)
+                    int v = FAST ? min(max(__double2loint(__builtin_fma((double)acc[r], c_qk, RQ_MAGIC + VB)), VB - 128), VB + 127)
                                  : rq_c((double)acc[r], c_qk, -128, 127) + VB;
                     f[j][r] = LUT ? __int_as_float(v) : sXq[v + 128];      // LUT: the (biased) integer itself waits for vmax
                     if (j * 16 + 15 < T || j * 16 + g * 4 + r < T) qmax = max(qmax, v);
@@ -288,8 +288,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 1) void attn_fused_kernel(AttnArgs 
         const int rowbase2 = LUT == 1 ? ((int)sCls[qmax + 128 - VB] * 256 + 128 - VB) * 2 : 0;
         // LDS address of this query row's table line, once per row: the first gather's address is then ONE v_lshl_add_u32 per
         // score (round 4: left to the compiler it was a shift plus a three-input add on the run-time table base, 1.4 + 1.3 per score)
-        typedef __attribute__((address_space(3))) const char att_lds_c;
-        const unsigned aqrow = (unsigned)(size_t)((att_lds_c *)sAQ) + (unsigned)rowbase2;
+        const unsigned aqrow = (unsigned)(size_t)((lds_cc *)sAQ) + (unsigned)rowbase2;
 
         // ---- shift-exp; keys >= T contribute exactly 0
         if (LUT == 2) {
@@ -300,8 +299,6 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 1) void attn_fused_kernel(AttnArgs 
                 v4f l[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) l[u] = src[u];
-                typedef float v2f __attribute__((ext_vector_type(2)));
-                typedef __attribute__((address_space(3))) v2f lds_v2f;
                 const unsigned dst = lines + (unsigned)qi * ATT_LINE_PITCH + (unsigned)g * 64;
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -360,7 +357,7 @@ __global__ __launch_bounds__(ATT_WAVES * 64, 1) void attn_fused_kernel(AttnArgs 
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const float e = *reinterpret_cast<__attribute__((address_space(3))) const float *>(
-                                (att_lds_c *)(size_t)(unsigned)C::SMEM + (unsigned)e1[jj][r]);
+                                (lds_cc *)(size_t)(unsigned)C::SMEM + (unsigned)e1[jj][r]);
                             f[j][r] = (j * 16 + 15 < T || j * 16 + g * 4 + r < T) ? e : 0.f;
                         }
                     }

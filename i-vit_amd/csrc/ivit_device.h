@@ -17,6 +17,21 @@ typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef short v8s __attribute__((ext_vector_type(8)));
+typedef double v2d __attribute__((ext_vector_type(2)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// LDS (address space 3) views: `*(lds_v4i *)(size_t)addr` is a DS access at the 32-bit LDS byte address `addr` (one base register
+// + an immediate offset), `(unsigned)(size_t)(lds_c *)ptr` the LDS byte address of a __shared__ object
+typedef __attribute__((address_space(3))) char lds_c;
+typedef __attribute__((address_space(3))) const char lds_cc;
+typedef __attribute__((address_space(3))) const unsigned char lds_u8;
+typedef __attribute__((address_space(3))) int lds_i32;
+typedef __attribute__((address_space(3))) unsigned lds_u32;
+typedef __attribute__((address_space(3))) v2i lds_v2i;
+typedef __attribute__((address_space(3))) v4i lds_v4i;
+typedef __attribute__((address_space(3))) const v4i lds_cv4i;
+typedef __attribute__((address_space(3))) v2f lds_v2f;
+typedef __attribute__((address_space(3))) v2d lds_v2d;
 
 #define IVIT_WAVE 64
 
@@ -62,8 +77,28 @@ __device__ __forceinline__ int rq_c(double z, double c, int lo, int hi) {
 // so the low dword does not wrap where v_cvt_i32_f64 would saturate.  Callers check both.
 #define RQ_FAST_ZLIM (1 << 22)
 #define RQ_FAST_CLIM 512.0
+#define RQ_MAGIC 6755399441055744.0              // 1.5 * 2^52: the one magic number of every requant below and in the kernels
 __device__ __forceinline__ int rq_fast(int z, double c) {
-    return __double2loint(__builtin_fma((double)z, c, 6755399441055744.0));
+    return __double2loint(__builtin_fma((double)z, c, RQ_MAGIC));
+}
+// requant of an accumulator, before the clamp.  RQ 1: one FMA onto the magic number (the plan proved it equal to the reference's
+// two roundings); 0: multiply, then add the magic number; both need |z c| < 2^31.  2: v_rndne_f64 + saturating convert, any c.
+template <int RQ>
+__device__ __forceinline__ int rq_magic(int z, double c) {
+    if constexpr (RQ == 2) return rint_sat_i32((double)z * c);
+    const double t = RQ ? __builtin_fma((double)z, c, RQ_MAGIC) : ((double)z * c + RQ_MAGIC);
+    return __double2loint(t);
+}
+// Magic-number rounding of z * c is safe — the low dword of z * c + RQ_MAGIC does not wrap — for every |z| <= zmax: |c| zmax < 2^31,
+// with the margin that absorbs the roundings of the bound itself.  The callers' zmax expressions are the proofs (K * 2^14 + |bias|
+// for an int8 x int8 contraction of length K, 128 * sum |W| + |bias| in the plans, LayerNorm's own bound); only the comparison is
+// shared.  NaN-proof: a multiplier that is not a number is not safe.
+__host__ __device__ __forceinline__ bool rq_magic_safe(double c, double zmax) { return fabs(c) * zmax < 2147483000.0; }
+// t = fl64(z * c) -> clamp(rne(t), -128, 127) + 128, a BIASED byte: the low dword of t + (RQ_MAGIC + 128) where rq_magic_safe holds
+// for the channel (FAST; the saturating packs of the consumer clamp), v_rndne_f64 + the saturating convert otherwise
+template <bool FAST>
+__device__ __forceinline__ int rq_biased_byte(double t) {
+    return FAST ? __double2loint(t + (RQ_MAGIC + 128.0)) : min(max(rint_sat_i32(t), -128), 127) + 128;
 }
 
 // ---- correctly-rounded fp32 division by a loop-invariant divisor --------------

@@ -710,7 +710,6 @@ __global__ __launch_bounds__(256) void shiftgelu_lut2_kernel(const int8_t *__res
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     const unsigned base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)lut[slot];
-    typedef __attribute__((address_space(3))) const unsigned char lds_u8;
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int c = l32 + it * 32;

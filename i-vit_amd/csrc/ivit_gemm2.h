@@ -130,7 +130,7 @@ __global__ __launch_bounds__(BM * 2, BM == 256 ? 4 : (G2_NSTAGE128 == 2 ? 4 : 3)
         sC[tid] = cv;
         sBias[tid] = bs;
         // magic-number rounding in the epilogue needs |(acc + bias) * c| < 2^31; |acc| <= K * 2^14
-        sUnsafe[tid] = !(fabs(cv) * ((double)Kdim * 16384.0 + fabs((double)bs)) < 2147483000.0);
+        sUnsafe[tid] = !rq_magic_safe(cv, (double)Kdim * 16384.0 + fabs((double)bs));
     }
 
     // acc[i][j]: C^T sub-tiles — lane holds token (lane&31) of m-tile i and, per register
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(BM * 2, BM == 256 ? 4 : (G2_NSTAGE128 == 2 ? 4 : 3)
                     for (int e = 0; e < 4; ++e) {
                         const int z = acc[i][j][g * 4 + e] + bs[e];
                         const double t = (double)z * c[e];
-                        const int v = decltype(use_fast)::value ? __double2loint(t + 6755399441055744.0) : rint_sat_i32(t);
+                        const int v = decltype(use_fast)::value ? __double2loint(t + RQ_MAGIC) : rint_sat_i32(t);
                         o[e] = min(max(v, OLO), OHI);
                     }
                     if (OUT8) {

@@ -30,7 +30,6 @@
 #define G3_NS 3
 #define G3_STG_LD 136
 #define G3_CONST_BYTES 1536
-#define G3_MAGIC 6755399441055744.0
 #define G3_MAXNK_ASTAT 6                 // panel slices that fit: K <= 384
 
 template <bool ASTAT> struct G3Cfg {
@@ -74,7 +73,7 @@ __device__ __forceinline__ void g3_requant_subtile(const v16i &acc, const char *
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int z = acc[g * 4 + e];
-            const double t = FMA ? __builtin_fma((double)z, cp[e], G3_MAGIC) : ((double)z * cp[e] + G3_MAGIC);
+            const double t = FMA ? __builtin_fma((double)z, cp[e], RQ_MAGIC) : ((double)z * cp[e] + RQ_MAGIC);
             const int v = __double2loint(t);
             o[e] = OUT8 ? min(max(v, -128), 127) : min(max(v, -32768), 32767);
         }
@@ -549,8 +548,7 @@ __device__ __forceinline__ void ga_wait_vm_fast(int n) {
 
 // 16-byte LDS read at an explicit LDS byte address (one base register + immediate offset)
 __device__ __forceinline__ v4i ga_lds_read16(unsigned lds_addr) {
-    typedef __attribute__((address_space(3))) const v4i lds_v4i_t;
-    return *(lds_v4i_t *)(size_t)(lds_addr);
+    return *(lds_cv4i *)(size_t)(lds_addr);
 }
 
 // swap the upper-half lanes of `a` with the lower-half lanes of `b`
@@ -567,7 +565,7 @@ __device__ __forceinline__ void ga_swap32(int &a, int &b) {
 template <bool FMA>
 __device__ __forceinline__ void ga_rq4(const int (&z)[4], double c0, double c1, double c2, double c3, int (&o)[4]) {
     double t0, t1, t2, t3;
-    const double mg = G3_MAGIC;
+    const double mg = RQ_MAGIC;
     if (FMA) {
         asm volatile("v_cvt_f64_i32 %0, %4\n\tv_cvt_f64_i32 %1, %5\n\tv_cvt_f64_i32 %2, %6\n\tv_cvt_f64_i32 %3, %7\n\t"
             "v_fma_f64 %0, %0, %8, %12\n\tv_fma_f64 %1, %1, %9, %12\n\tv_fma_f64 %2, %2, %10, %12\n\tv_fma_f64 %3, %3, %11, %12"
@@ -711,7 +709,6 @@ __global__ __launch_bounds__(512, 2) void gemm_as_kernel(GemmArgs p) {
     const float rcpT = 1.0f / (float)(p.T > 0 ? p.T : 1);
     v4i resv[8];          // residual pieces in flight / waiting for their sub-tile's epilogue: [(j*2 + i)*2 + piece]
     (void)resv;
-    typedef double v2d __attribute__((ext_vector_type(2)));
     v2d cqv[2][2];        // multipliers of the next epilogue work: [quad slot][c01 | c23], requested at the END of the
                           // section before (after their previous contents were consumed)
     v4i fa[2][2], fb[2][2];   // MFMA fragments of section G: [G & 1][i | j]

@@ -11,7 +11,7 @@
 //   * the four waves of a workgroup take the four 32-token tiles of a 128-token row tile; the activation tile travels
 //     global -> LDS by DMA one row tile ahead (two buffers, one workgroup barrier per row tile);
 //   * v_mfma_i32_32x32x32_i8 with the weights as the A operand and the MFMA rows placed so that accumulator register v of
-//     lane (token, h) is channel 16 h + v of the tile (the trick of ivit_mlp_rs.h): 16 consecutive output channels per lane,
+//     lane (token, h) is channel 16 h + v of the tile (ivit_wa.h): 16 consecutive output channels per lane,
 //     stored straight from registers as one (8 bit) or two (16 bit) 16-byte global stores per tile — no staging pass;
 //   * workgroups are persistent and small (2 - 4 per CU, bounded by registers): the other workgroups' loads, MFMAs and
 //     stores fill a workgroup's waits, which is what the big-tile kernels try to do inside one workgroup.  (Measured and
@@ -25,6 +25,7 @@
 #pragma once
 #include "ivit_gemm.h"
 #include "ivit_gemm2.h"
+#include "ivit_wa.h"
 
 #define GW_BM 128
 #define GW_THREADS 256
@@ -32,17 +33,12 @@
 // accumulators 16 + multipliers 32 (+ 8 identity): 4 at K = 96 without the residual, 3 with it or at NCT KS <= 12, else 2
 #define GW_MINW(EPI, KS, NCT) ((NCT) * (KS) <= 9 ? ((EPI) == EPI_RQ16_CH_RES ? 3 : 4) : ((NCT) * (KS) <= 12 && (EPI) != EPI_RQ16_CH_RES ? 3 : 2))
 
-__device__ __forceinline__ int gw_chan_of_row(int rho) { return ((rho >> 2) & 1) * 16 + (rho >> 3) * 4 + (rho & 3); }
-
 // KS = K / 32 k-steps, NCT = 32-channel tiles per workgroup (its channel group)
 template <int EPI, int KS, int NCT>
 __global__ __launch_bounds__(GW_THREADS, GW_MINW(EPI, KS, NCT)) void gemm_wreg_kernel(GemmArgs p) {
     static_assert(EPI == EPI_RQ8_CH || EPI == EPI_RQ16_CH || EPI == EPI_RQ16_CH_RES, "per-channel requant epilogues");
     constexpr int K = KS * 32, NC = NCT * 32, ABUF = GW_BM * K;
     constexpr bool OUT8 = EPI == EPI_RQ8_CH;
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    typedef __attribute__((address_space(3))) char lds_c;
-    typedef __attribute__((address_space(3))) v4i lds_v4i;
     __shared__ __attribute__((aligned(256))) char sA[2 * ABUF];
     __shared__ __attribute__((aligned(16))) double sC[NC];
     __shared__ __attribute__((aligned(16))) int sBias[NC];
@@ -64,7 +60,7 @@ __global__ __launch_bounds__(GW_THREADS, GW_MINW(EPI, KS, NCT)) void gemm_wreg_k
     for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-            wf[ct][ks] = *reinterpret_cast<const v4i *>(p.B + (size_t)(chbase + 32 * ct + gw_chan_of_row(tok)) * K + 32 * ks + 16 * kh);
+            wf[ct][ks] = *reinterpret_cast<const v4i *>(p.B + (size_t)(chbase + 32 * ct + wa_chan_of_row(tok)) * K + 32 * ks + 16 * kh);
     if (tid == 0) sUnsafe = 0;
     __syncthreads();
     if (tid < NC) {
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(GW_THREADS, GW_MINW(EPI, KS, NCT)) void gemm_wreg_k
         sC[tid] = cv;
         sBias[tid] = bs;
         // magic-number rounding needs |(acc + bias) * c| < 2^31; |acc| <= K * 2^14
-        if (!(fabs(cv) * ((double)K * 16384.0 + fabs((double)bs)) < 2147483000.0)) sUnsafe = 1;
+        if (!rq_magic_safe(cv, (double)K * 16384.0 + fabs((double)bs))) sUnsafe = 1;
     }
 
     // activation row tile -> LDS by DMA: [k-step][token][2 x 16 B], the chunk of (token, h) at position h ^ (token >> 4 & 1)
@@ -130,11 +126,7 @@ __global__ __launch_bounds__(GW_THREADS, GW_MINW(EPI, KS, NCT)) void gemm_wreg_k
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
                 v16i acc;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const v4i b4 = *reinterpret_cast<const v4i *>(sBias + 32 * ct + 16 * kh + 4 * q);
-                    acc[4 * q] = b4[0]; acc[4 * q + 1] = b4[1]; acc[4 * q + 2] = b4[2]; acc[4 * q + 3] = b4[3];
-                }
+                WA_ACC_BIAS(acc, *reinterpret_cast<const v4i *>(sBias + 32 * ct + 16 * kh + 4 * q));
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[ct][ks], af[ks], acc, 0, 0, 0);
                 const int ch0 = chbase + 32 * ct + 16 * kh;
@@ -146,23 +138,15 @@ __global__ __launch_bounds__(GW_THREADS, GW_MINW(EPI, KS, NCT)) void gemm_wreg_k
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
                         const double t = (double)acc[v + e] * c2[e];
-                        if (decltype(use_fast)::value) o[v + e] = __double2loint(t + (6755399441055744.0 + (OUT8 ? 128.0 : 0.0)));
-                        else o[v + e] = min(max(rint_sat_i32(t), OUT8 ? -128 : -32768), OUT8 ? 127 : 32767) + (OUT8 ? 128 : 0);
+                        if (OUT8) o[v + e] = rq_biased_byte<decltype(use_fast)::value>(t);
+                        else o[v + e] = decltype(use_fast)::value ? __double2loint(t + RQ_MAGIC) : min(max(rint_sat_i32(t), -32768), 32767);
                     }
                 }
                 if (OUT8) {
-                    // biased to 0 .. 255: v_cvt_pk_i16_i32 + v_sat_pk_u8_i16 clamp while packing; one xor per dword takes the bias out
+                    // biased to 0 .. 255 and clamped while packing; one xor per dword takes the bias out
                     v4i w;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        unsigned p01, p23, b01, b23;
-                        const int s0 = o[4 * q], s1 = o[4 * q + 1], s2 = o[4 * q + 2], s3 = o[4 * q + 3];
-                        asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p01) : "v"(s0), "v"(s1));
-                        asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p23) : "v"(s2), "v"(s3));
-                        asm("v_sat_pk_u8_i16 %0, %1" : "=v"(b01) : "v"(p01));
-                        asm("v_sat_pk_u8_i16 %0, %1" : "=v"(b23) : "v"(p23));
-                        w[q] = (int)(__builtin_amdgcn_perm(b23, b01, 0x05040100u) ^ 0x80808080u);
-                    }
+                    for (int q = 0; q < 4; ++q) w[q] = (int)(wa_pack_biased(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]) ^ 0x80808080u);
                     if (live) *reinterpret_cast<v4i *>(reinterpret_cast<int8_t *>(p.out) + row * p.ldc + ch0) = w;
                 } else {
                     v4i w0, w1;
@@ -172,7 +156,9 @@ __global__ __launch_bounds__(GW_THREADS, GW_MINW(EPI, KS, NCT)) void gemm_wreg_k
                         if (EPI == EPI_RQ16_CH_RES) {
                             const int rw = d < 4 ? r0[d] : r1[d - 4];
                             const int ra = (int)(short)(rw & 0xffff), rb = rw >> 16;
-                            // both terms are integers < 2^31: the sum is the reference's fp64 sum (quant_utils.py:238-244)
+                            // both terms are integers < 2^31: the sum is the reference's fp64 sum (quant_utils.py:238-244).  (Written out,
+                            // not ivit_wa.h's wa_res_pair: this site branches on res_fast around both halves of a dword where the helper
+                            // selects per element, and through the helper the whole epilogue is scheduled differently)
                             if (__builtin_expect(res_fast, 1)) { t0 = rq_fast(ra, cr) + rq_fast(t0, cm); t1 = rq_fast(rb, cr) + rq_fast(t1, cm); }
                             else { t0 = rq_lean_wide(ra, cr) + rq_lean_wide(t0, cm); t1 = rq_lean_wide(rb, cr) + rq_lean_wide(t1, cm); }
                         }

@@ -4,7 +4,7 @@
 // block's first LayerNorm never exist in HBM (vit_quant.py:136-140: norm1's output has one consumer, attn.qkv).
 //
 //   * a workgroup (8 waves, one per CU) owns a contiguous range of 32-token tiles (<= WS_MAXT per panel: 7 x 32 x 384 B = 86 KB),
-//     laid out [64-column block][token][64 B] with the chunk permutation of ivit_mlp_rs.h (conflict-free ds_read_b128
+//     laid out [64-column block][token][64 B] with the chunk permutation wa_g of ivit_wa.h (conflict-free ds_read_b128
 //     B fragments).  LN = false: filled by DMA from the 8-bit activations.  LN = true: every wave normalises 8 rows at a time
 //     (ivit_layernorm.h::LnGroup<384, 2>, the same arithmetic as layernorm_reg_kernel, byte for byte) and writes the bytes there;
 //   * a wave's task is (64-channel slab = one head of q, k or v; one half of the panel's token tiles): the 2 x 12 16-byte A
@@ -24,6 +24,7 @@
 // of the qkv epilogue (VT).  Measured: profiles/README.md, "Width 192 on the weights-in-registers GEMM".
 #pragma once
 #include "ivit_layernorm.h"
+#include "ivit_wa.h"
 #include <type_traits>
 
 // One source, two widths.  K = 384: 7 tiles x 32 tokens x 384 B = 86 KB per panel, 96 weight registers per slab.  K = 192: a tile is
@@ -55,7 +56,6 @@ typedef WsGeo<192, 14, true> Ws192Geo;
 #define WS_MAXN 1536
 inline bool ws_width(int K) { return K == Ws384Geo::K || K == Ws192Geo::K; }
 #define WS_THREADS 512
-#define WS_MAGIC 6755399441055744.0
 
 struct WsArgs {
     const int8_t *x;          // [M][K] 8-bit activations (LN = false)
@@ -82,15 +82,12 @@ struct WsArgs {
 #define WS_EPI_RES16 1
 #define WS_EPI_RQ8 2                             // plain QuantLinear -> QuantAct(8): q = out8 [M][N] row-major (Swin's qkv layer)
 
-__device__ __forceinline__ int ws_chan_of_row(int rho) { return ((rho >> 2) & 1) * 16 + (rho >> 3) * 4 + (rho & 3); }
-__device__ __forceinline__ int ws_g(int tok) { return ((tok >> 1) & 3) ^ ((tok >> 3) & 3) ^ ((tok >> 4) & 1); }
-
 // weights [N][K] -> fragments of 64 lanes x 16 B: fragment ct * (K / 32) + ks, lane l = (row l & 31, k half l >> 5)
 __global__ __launch_bounds__(256) void ws_swizzle_kernel(const int8_t *__restrict__ w, v4i *__restrict__ wf, int N, int K) {
     const int nks = K / 32, nfrag = N / 32 * nks;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nfrag * 64; i += gridDim.x * 256) {
         const int l = i & 63, f = i >> 6, ct = f / nks, ks = f - ct * nks;
-        const int ch = 32 * ct + ws_chan_of_row(l & 31);
+        const int ch = 32 * ct + wa_chan_of_row(l & 31);
         wf[i] = *reinterpret_cast<const v4i *>(w + (size_t)ch * K + 32 * ks + 16 * (l >> 5));
     }
 }
@@ -100,17 +97,11 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
     static_assert(!VT || (G::VT && EPI == WS_EPI_QKV8), "the v^T store form belongs to the qkv scatter of a geometry that keeps its table");
     static_assert(!(LN && EPI == WS_EPI_RES16) || G::K == 384, "norm2 in the proj launch is built at 384 only");
     extern __shared__ __attribute__((aligned(256))) char sm[];
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    typedef __attribute__((address_space(3))) char lds_c;
-    typedef __attribute__((address_space(3))) v4i lds_v4i;
-    typedef __attribute__((address_space(3))) int lds_i32;
-    typedef __attribute__((address_space(3))) unsigned lds_u32;
-    typedef __attribute__((address_space(3))) v2d lds_v2d;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned sm_lds = (unsigned)(size_t)(lds_c *)sm;
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
-    const int lane = tid & 63, tok = lane & 31, kh = lane >> 5, e = kh ^ ws_g(tok);
+    const int lane = tid & 63, tok = lane & 31, kh = lane >> 5, e = kh ^ wa_g(tok);
 
     const int ntt = (p.M + 31) >> 5;
     const int t_beg = (int)((long long)ntt * blockIdx.x / gridDim.x), t_end = (int)((long long)ntt * (blockIdx.x + 1) / gridDim.x);
@@ -143,31 +134,16 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                 const bool live = row_raw < p.M;
                 const int16_t *xp = p.x16 + (live ? row_raw : (long long)p.M - 1) * G::K + 8 * k + 4 * hh;
                 float xv[LG::NSTEP][LG::EPC];
-#pragma unroll
-                for (int i = 0; i < LG::NSTEP; ++i) {
-                    const LnRaw<4>::T t = *reinterpret_cast<const LnRaw<4>::T *>(xp + 32 * i);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)t[c], p.ln_s, ys);
-                }
-                const unsigned rowa = sm_lds + tokl * 64 + (k & 1) * 8 + 4 * hh, gk = (unsigned)((k >> 1) ^ ws_g(tokl));
+                LN_ROW_X(LG, xv, LG::raw_at(xp + 32 * i), p.ln_s, ys);
+                const unsigned rowa = sm_lds + tokl * 64 + (k & 1) * 8 + 4 * hh, gk = (unsigned)((k >> 1) ^ wa_g(tokl));
                 LG::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY,
                        [&](int i, unsigned pk0, unsigned) __attribute__((always_inline)) {
                            *(lds_u32 *)(size_t)(rowa + (i >> 1) * G::KBLK + ((gk ^ ((i & 1) * 2)) << 4)) = pk0;
                        });
             }
         } else {
-            // ---- the panel's tokens: global -> LDS by DMA, 16 tokens x 4 chunk slots per instruction (source chunk = slot ^ g)
-            for (int tg = wave; tg < n_own * 2; tg += 8) {
-                const int tokl = tg * 16 + (lane >> 2), c = (lane & 3) ^ ws_g(tokl);
-                const long long grow = min((long long)t0 * 32 + tokl, (long long)p.M - 1);
-                const int8_t *src = p.x + grow * G::K + c * 16;
-#pragma unroll
-                for (int kb = 0; kb < G::KB; ++kb) {
-                    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(kb * G::KBLK + tg * 1024));
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + kb * 64),
-                                                     (__attribute__((address_space(3))) void *)(sm + dst), 16, 0, 0);
-                }
-            }
+            // ---- the panel's tokens: global -> LDS by DMA, one token group of 16 per wave at a time
+            for (int tg = wave; tg < n_own * 2; tg += 8) WA_DMA16(G::KB, G::KBLK, sm, 0, tg, lane, p.x, (long long)t0 * 32, p.M)
         }
         // output row offset of every token of the panel: (b * H * T + t_in_image) * 64
         if (tid < G::TOK) {
@@ -232,13 +208,11 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                         }
                 }
 #pragma unroll
-                for (int c = 0; c < 2; ++c)
+                for (int c = 0; c < 2; ++c) {
+                    WA_ACC_BIAS(acc[c][0], *(lds_v4i *)(size_t)(sm_lds + G::SBIAS + (chb + 32 * c + 4 * q) * 4));
 #pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) {
-                        const v4i b4 = *(lds_v4i *)(size_t)(sm_lds + G::SBIAS + (chb + 32 * c + 4 * q4) * 4);
-#pragma unroll
-                        for (int t = 0; t < NT; ++t) { acc[c][t][4 * q4] = b4[0]; acc[c][t][4 * q4 + 1] = b4[1]; acc[c][t][4 * q4 + 2] = b4[2]; acc[c][t][4 * q4 + 3] = b4[3]; }
-                    }
+                    for (int t = 1; t < NT; ++t) acc[c][t] = acc[c][0];
+                }
 #pragma unroll
                 for (int ks = 0; ks < G::KS; ++ks) {
                     __builtin_amdgcn_sched_barrier(0);
@@ -250,8 +224,8 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                         for (int t = 0; t < NT; ++t)
                             acc[c][t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(W[c][ks], bf[ks & 1][t], acc[c][t], 0, 0, 0);
                 }
-                // requant to 8 bits: fma(z, c, magic + 128) leaves Q + 128 in the low dword; the two packs saturate to [0, 255]
-                // = clamp(Q, -128, 127) + 128; the xor takes the bias off again.  One (channel tile, token tile) at a time:
+                // requant to 8 bits: fma(z, c, magic + 128) leaves Q + 128 in the low dword, wa_pack_biased clamps while packing,
+                // the xor takes the bias off again.  One (channel tile, token tile) at a time:
                 // sixteen channels of a token per lane, one 16-byte store
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -261,24 +235,12 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         if constexpr (EPI == WS_EPI_RES16) {
-                            // 16-bit requant, then the residual QuantAct: both terms are integers < 2^31 / 2, their sum is the
-                            // reference's fp64 sum; v_cvt_pk_i16_i32 clamps to 16 bits while packing
+                            // 16-bit requant, then the residual QuantAct
                             v4i o0, o1;
 #pragma unroll
                             for (int d = 0; d < 8; ++d) {
-                                const unsigned rw = (unsigned)(d < 4 ? idr[c][t][0][d] : idr[c][t][1][d - 4]);
-                                int o[2];
-#pragma unroll
-                                for (int h2 = 0; h2 < 2; ++h2) {
-                                    const int v = 2 * d + h2;
-                                    const double m = cqv[v >> 1][v & 1];
-                                    const double tq = FMA ? __builtin_fma((double)acc[c][t][v], m, WS_MAGIC) : ((double)acc[c][t][v] * m + WS_MAGIC);
-                                    const int t16 = min(max(__double2loint(tq), -32768), 32767);
-                                    const int r = h2 ? ((int)rw >> 16) : (int)(short)(rw & 0xffffu);
-                                    o[h2] = rq_fast(r, p.cr) + rq_fast(t16, p.cm);
-                                }
-                                int pk;
-                                asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(pk) : "v"(o[0]), "v"(o[1]));
+                                const int pk = wa_res_pair<FMA>(acc[c][t][2 * d], acc[c][t][2 * d + 1], cqv[d], d < 4 ? idr[c][t][0][d] : idr[c][t][1][d - 4],
+                                                                p.cm, p.cr, std::true_type{});
                                 if (d < 4) o0[d] = pk; else o1[d - 4] = pk;
                             }
                             asm volatile("" : "+v"(o0), "+v"(o1));
@@ -297,16 +259,11 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
 #pragma unroll
                             for (int i = 0; i < 4; ++i) {
                                 const double m = cqv[2 * q4 + (i >> 1)][i & 1];
-                                const double tq = FMA ? __builtin_fma((double)acc[c][t][4 * q4 + i], m, WS_MAGIC + 128.0)
-                                                      : ((double)acc[c][t][4 * q4 + i] * m + (WS_MAGIC + 128.0));
+                                const double tq = FMA ? __builtin_fma((double)acc[c][t][4 * q4 + i], m, RQ_MAGIC + 128.0)
+                                                      : ((double)acc[c][t][4 * q4 + i] * m + (RQ_MAGIC + 128.0));
                                 o[i] = __double2loint(tq);
                             }
-                            unsigned p01, p23, b01, b23;
-                            asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p01) : "v"(o[0]), "v"(o[1]));
-                            asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p23) : "v"(o[2]), "v"(o[3]));
-                            asm("v_sat_pk_u8_i16 %0, %1" : "=v"(b01) : "v"(p01));
-                            asm("v_sat_pk_u8_i16 %0, %1" : "=v"(b23) : "v"(p23));
-                            int hq = (int)(__builtin_amdgcn_perm(b23, b01, 0x05040100u) ^ 0x80808080u);
+                            int hq = (int)(wa_pack_biased(o[0], o[1], o[2], o[3]) ^ 0x80808080u);
                             asm volatile("" : "+v"(hq));       // pinned: left alone, the optimiser converts every accumulator first
                             o4[q4] = hq;
                         }
@@ -356,12 +313,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void gemm_ws_qkv_kernel(WsArgs p) {
                 const long long row = live ? row_raw : (long long)p.M - 1;
                 const int16_t *xp = p.out16 + row * G::K + 8 * k + 4 * hh;
                 float xv[LG::NSTEP][LG::EPC];
-#pragma unroll
-                for (int i = 0; i < LG::NSTEP; ++i) {
-                    const LnRaw<4>::T t = *reinterpret_cast<const LnRaw<4>::T *>(xp + 32 * i);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)t[c], p.ln_s, ys);
-                }
+                LN_ROW_X(LG, xv, LG::raw_at(xp + 32 * i), p.ln_s, ys);
                 LG::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, p.ln_out8 + row * G::K + 8 * k + 4 * hh);
             }
         }

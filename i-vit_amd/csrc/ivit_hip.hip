@@ -538,7 +538,7 @@ __global__ __launch_bounds__(256) void linear_plan_kernel(const int8_t *__restri
         cq[n] = c;
         const double zmax = 128.0 * (double)l1 + fabs((double)(bias ? bias[n] : 0));
         int b = 0;
-        if (!(fabs(c) * zmax < 2147483000.0)) b |= 1;
+        if (!rq_magic_safe(c, zmax)) b |= 1;
         if (!(fabs(dy[n].m) * zmax < 9007199254740992.0)) b |= 4;      // bound fails: linear_plan_fma_kernel decides
         if (b) atomicOr(bad, b);
     }
@@ -563,8 +563,8 @@ __global__ __launch_bounds__(256) void linear_plan_fma_kernel(const int8_t *__re
     const double m = dy[n].m, r = dy[n].r, c = m * r;
     const double zmax = 128.0 * (double)s_l1 + fabs((double)(bias ? bias[n] : 0));
     if (fabs(m) * zmax < 9007199254740992.0) return;               // exact products: nothing to prove
-    if (!(c > 0.0) || !(zmax < 2147483000.0)) { if (tid == 0) atomicOr(bad, 2); return; }
-    auto f1 = [&](double z) { return __double2loint(__builtin_fma(z, c, 6755399441055744.0)); };
+    if (!(c > 0.0) || !rq_magic_safe(1.0, zmax)) { if (tid == 0) atomicOr(bad, 2); return; }      // (|z| itself must fit the bound)
+    auto f1 = [&](double z) { return __double2loint(__builtin_fma(z, c, RQ_MAGIC)); };
     auto f2 = [&](double z) { return (int)__builtin_rint((z * m) * r); };
     bool fail = false;
     for (int i = 0; i < 256 && !fail; ++i) {

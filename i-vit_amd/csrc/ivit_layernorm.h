@@ -61,11 +61,20 @@ __device__ __forceinline__ float ln_dpp(float v) {
 // Everything after the row is in registers as x = fl(fl(Q*s)/s): both torch-order sums, the integer Newton iteration, the
 // output pass with the per-channel constants of the block's LDS copy, the store.  Shared by the one-shot kernel and the
 // pipelined one below.
+template <int EPC>
+struct LnRaw;
+template <> struct LnRaw<8> { typedef short T __attribute__((ext_vector_type(8))); };
+template <> struct LnRaw<4> { typedef short T __attribute__((ext_vector_type(4))); };
+template <> struct LnRaw<2> { typedef short T __attribute__((ext_vector_type(2))); };
+
 template <int CC, int S>
 struct LnGroup {
     static constexpr int LPR = 4 * S, EPC = 8 / S, NSTEP = CC / 32, RPW = 64 / LPR;
     static_assert(CC % 32 == 0 && NSTEP < 256, "whole 32-element steps, at most one cascade level above the first");
     static_assert(S == 2 || S == 4, "8 or 16 lanes per row (the 4-lanes-per-row form is not built: see the note above)");
+    typedef typename LnRaw<EPC>::T Raw;             // a lane's EPC 16-bit values of one 32-element step
+
+    static __device__ __forceinline__ Raw raw_at(const int16_t *p) { return *reinterpret_cast<const Raw *>(p); }
 
     // ((g0 + g1) + g2) + g3 over the accumulator groups, then vector lanes 0..7 in order; every lane of the row gets it.
     // Lane j = S k + h of a row: group k + 1 is S lanes up (DPP row shifts; a row's 4 S lanes never straddle a DPP row of
@@ -186,7 +195,6 @@ struct LnGroup {
             }
 #pragma unroll
             for (int e = 0; e < EPC; e += 2) {
-                typedef double v2d __attribute__((ext_vector_type(2)));
                 const v2d c2 = *reinterpret_cast<const v2d *>(cC + cb + e);
                 cv[e] = c2[0]; cv[e + 1] = c2[1];
             }
@@ -196,7 +204,7 @@ struct LnGroup {
                 for (int e = 0; e < EPC; ++e) {
                     const float o = floorf(xv[i][e] * Fh) + bi[e];
                     const float zz = rintf(requotient_m(o, scv[e], yv[e]));
-                    const int v = __double2loint((double)zz * cv[e] + (6755399441055744.0 + 128.0));
+                    const int v = __double2loint((double)zz * cv[e] + (RQ_MAGIC + 128.0));
                     pk[e >> 2] |= (unsigned)min(max(v, 0), 255) << (8 * (e & 3));
                 }
                 pk[0] ^= 0x80808080u; pk[1] ^= 0x80808080u;
@@ -224,6 +232,17 @@ struct LnGroup {
     }
 };
 
+// The row as LnGroup::run wants it, xv[i][e] = fl(fl(Q*s)/s) of this lane's EPC values of every 32-element step i, with ys = rcp_rn(s).
+// RAW_I: the step's raw values (G::Raw) as an expression in `i` — G::raw_at(xp + 32 * i) for a contiguous row whose first channel of
+// this lane is at xp, or a register the caller requested earlier.  A macro, not a member of LnGroup: taking xv by reference, the
+// force-inlined function reaches the back end with the operands of two adds of LnGroup::finish swapped (and, at other widths, the
+// output pass re-ordered), while this text compiles to the instruction streams the kernels had with the loop written out in each.
+#define LN_ROW_X(G, xv, RAW_I, s, ys)                                                                           \
+    _Pragma("unroll") for (int i = 0; i < G::NSTEP; ++i) {                                                      \
+        const typename G::Raw t_ = RAW_I;                                                                       \
+        _Pragma("unroll") for (int e_ = 0; e_ < G::EPC; ++e_) xv[i][e_] = requotient_m((float)t_[e_], s, ys);   \
+    }
+
 // per-channel constants of one LayerNorm -> the block's LDS copy; returns whether every channel admits the two-operation
 // 8-bit requant.  The requant rne(fl64(z * c)) is taken as the low dword of fl64(z * c) + (1.5 * 2^52 + 128) — the same two
 // roundings as the reference (quant_utils.py:229-231) in two fp64 operations instead of four, biased to 0..255 so the four
@@ -243,7 +262,7 @@ __device__ __forceinline__ bool ln_stage_constants(const float *__restrict__ bia
         if constexpr (WITH_Y) cY[c] = rcp_rn(scv);
         cB[c] = bv;
         cC[c] = cv;
-        wide |= !(fabs(cv) * (1.2e12 + 1.01 * fabs((double)bv)) < 2147483000.0);
+        wide |= !rq_magic_safe(cv, 1.2e12 + 1.01 * fabs((double)bv));
     }
     if constexpr (!WITH_Y) {
         volatile float *vote = cY;
@@ -255,12 +274,6 @@ __device__ __forceinline__ bool ln_stage_constants(const float *__restrict__ bia
     } else
         return !__syncthreads_or(wide);
 }
-
-template <int EPC>
-struct LnRaw;
-template <> struct LnRaw<8> { typedef short T __attribute__((ext_vector_type(8))); };
-template <> struct LnRaw<4> { typedef short T __attribute__((ext_vector_type(4))); };
-template <> struct LnRaw<2> { typedef short T __attribute__((ext_vector_type(2))); };
 
 // MERGE_R > 0 (round 6): the row is PatchMerging's 2 x 2 gather (swin_quant.py:336-342) of x [B, R, R, CC / 4] done in the load —
 // merged row (b, yo, xo) = the four tokens (2 yo + (q & 1), 2 xo + (q >> 1)), q = 0..3, side by side in the reference's
@@ -299,13 +312,7 @@ __global__ __launch_bounds__(LNR_THREADS(S), LNR_MIN_WAVES(CC, S)) void layernor
 
     // ---- load, x = fl(fl(Q*s)/s)
     float xv[NSTEP][EPC];
-#pragma unroll
-    for (int i = 0; i < NSTEP; ++i) {
-        const int16_t *src = MERGE ? xq[(32 * i) / (CC / 4)] + (32 * i) % (CC / 4) : xp + 32 * i;
-        const typename LnRaw<EPC>::T t = *reinterpret_cast<const typename LnRaw<EPC>::T *>(src);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) xv[i][e] = requotient_m((float)t[e], s, ys);
-    }
+    LN_ROW_X(G, xv, G::raw_at(MERGE ? xq[(32 * i) / (CC / 4)] + (32 * i) % (CC / 4) : xp + 32 * i), s, ys);
     G::run(xv, j, k, 8 * k + EPC * hh, fastrq, live, cC, cB, cSc, cY, out + row * CC + 8 * k + EPC * hh);
 }
 

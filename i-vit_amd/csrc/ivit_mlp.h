@@ -110,7 +110,6 @@ struct Mlp128Geo : MlpGeo<128, 4> {
 #define MLP_KS1 Mlp384Geo::KS1
 #define MLP_KS2 Mlp384Geo::KS2
 #define MLP_SMEM Mlp384Geo::SMEM
-#define MLP_MAGIC 6755399441055744.0
 
 struct MlpArgs {
     const int8_t *x;          // [M, C] int8 (LayerNorm + requant output)
@@ -161,15 +160,6 @@ __device__ __forceinline__ int mlp_phi(int tok, int chunk) {
 MLP_SWIZZLE_KERNEL(mlp_swizzle_kernel, Mlp384Geo)
 MLP_SWIZZLE_KERNEL(mlp192_swizzle_kernel, Mlp192Geo)
 MLP_SWIZZLE_KERNEL(mlp256_swizzle_kernel, Mlp256Geo)
-
-// requant of an accumulator, before the clamp.  RQ 1: one FMA onto the magic number (the plan proved it equal to the reference's
-// two roundings); 0: multiply, then add the magic number; both need |z c| < 2^31.  2: v_rndne_f64 + saturating convert, any c.
-template <int RQ>
-__device__ __forceinline__ int mlp_rq(int z, double c) {
-    if constexpr (RQ == 2) return rint_sat_i32((double)z * c);
-    const double t = RQ ? __builtin_fma((double)z, c, MLP_MAGIC) : ((double)z * c + MLP_MAGIC);
-    return __double2loint(t);
-}
 
 // This workgroup's units, from (p.M, p.balanced, blockIdx, gridDim): declares `nu` (units of this workgroup; returns from the
 // kernel if none), unit_tile0(i) (first tile of unit i) and unit_ntt(i) (its tiles, 0 past the last unit).  TT: the most tiles
@@ -248,7 +238,7 @@ __global__ __launch_bounds__(Mlp192Geo::THREADS, Mlp192Geo::WAVES * Mlp192Geo::W
     constexpr bool LNH = true;
 #include "ivit_mlp_body.h"
 }
-// width 128: the body once per requant form (FMA here is mlp_rq's RQ: 0 or 2), and the kernel that picks between them — every
+// width 128: the body once per requant form (FMA here is rq_magic's RQ: 0 or 2), and the kernel that picks between them — every
 // workgroup reads the 640 multipliers and biases once and asks whether |z c| < 2^31 holds for all of them, with |z| <= K * 2^14
 // + |bias| (the bound swin_mlp_rs_kernel uses)
 template <int FMA>
@@ -266,7 +256,7 @@ __global__ __launch_bounds__(Mlp128Geo::THREADS, Mlp128Geo::WAVES * Mlp128Geo::W
         const ivit_dyadic d = reinterpret_cast<const ivit_dyadic *>(first ? p.cq1 : p.cq2)[n];
         const int32_t *b = first ? p.b1 : p.b2;
         const double zmax = (double)(first ? G::C : G::HD) * 16384.0 + fabs((double)(b ? b[n] : 0));
-        wide |= !(fabs(d.m * d.r) * zmax < 2147483000.0);
+        wide |= !rq_magic_safe(d.m * d.r, zmax);
     }
     if (__syncthreads_or(wide)) mlp128_body<2>(p);
     else mlp128_body<0>(p);

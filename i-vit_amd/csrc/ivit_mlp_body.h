@@ -1,6 +1,6 @@
 // ivit_mlp_body.h — the body of the lock-step fused-Mlp kernel (the scheme: ivit_mlp.h).  Not a header of its own: ivit_mlp.h includes it
 // once inside each entry point (mlp384_kernel, mlp256_kernel, mlp192_kernel, mlp128_body and the LayerNorm-headed mlp384ln_kernel,
-// mlp192ln_kernel), which supplies `G` (the geometry), `FMA` (the requant form: mlp_rq), `LNH` (the activation tile of a unit is norm2 +
+// mlp192ln_kernel), which supplies `G` (the geometry), `FMA` (the requant form: rq_magic), `LNH` (the activation tile of a unit is norm2 +
 // qact3 of its rows of the 16-bit stream, computed in place: below) and `p` (MlpArgs).  One
 // text, so that a change to the barriers, the prefetch distances or ShiftGELU reaches every width; included rather than called,
 // so that each entry point compiles exactly as if the body were written out in it.
@@ -17,7 +17,6 @@
                   "the fc1 pipeline loads a chunk's multipliers, then the next bias, both before the chunk's last step");
     static_assert(G::WG_PER_CU * (LNH ? G::SMEM_LN : G::SMEM) <= 160 * 1024, "WG_PER_CU workgroups share a CU's LDS");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    typedef double v2d __attribute__((ext_vector_type(2)));
     // G::DIRECT: four channels' (m, 2^-e) pairs as the caller's table holds them -> their multipliers c = m * 2^-e
     auto dy_c = [](const v2d (&d)[4], v2d (&c)[2]) __attribute__((always_inline)) {
         c[0] = v2d{d[0][0] * d[0][1], d[1][0] * d[1][1]};
@@ -62,7 +61,7 @@
     // width 192 and one at 384), so 1 / sc is formed per element (LnGroup::run<.., LOCAL_Y>).  ln_fetch requests the 16-bit rows of
     // one pass (in front of ShiftGELU for a unit's first pass, one pass ahead after that), ln_rows normalises them into the tile
     typedef LnGroup<G::C, 2> LG;
-    typedef typename LnRaw<4>::T ln_raw;
+    typedef typename LG::Raw ln_raw;
     double *const cC = reinterpret_cast<double *>(sm + G::SLN);
     float *const cB = reinterpret_cast<float *>(sm + G::SLN + G::C * 8), *const cSc = cB + G::C;
     bool ln_fast = false;
@@ -84,10 +83,7 @@
         const int j = t & 7, k = j >> 1, row = r0 + ((t & 63) >> 3);
         const float ys = rcp_rn(p.ln_s);
         float xv[LG::NSTEP][LG::EPC];
-#pragma unroll
-        for (int i = 0; i < LG::NSTEP; ++i)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)raw[i][c], p.ln_s, ys);
+        LN_ROW_X(LG, xv, raw[i], p.ln_s, ys);
         char *const rowa = sm + G::SA + row * 64 + (k & 1) * 8 + 4 * (j & 1);
         const int ph0 = mlp_phi(row, k >> 1) * 16, ph1 = mlp_phi(row, 2 + (k >> 1)) * 16;
         auto place = [&](int i, unsigned pk0, unsigned) __attribute__((always_inline)) {
@@ -198,10 +194,10 @@
 #pragma unroll
                         for (int tt = 0; tt < NTT; ++tt) {
                             int o[4];
-                            o[0] = mlp_rq<FMA>(acc[j][tt][0], cq[j][0][0]);
-                            o[1] = mlp_rq<FMA>(acc[j][tt][1], cq[j][0][1]);
-                            o[2] = mlp_rq<FMA>(acc[j][tt][2], cq[j][1][0]);
-                            o[3] = mlp_rq<FMA>(acc[j][tt][3], cq[j][1][1]);
+                            o[0] = rq_magic<FMA>(acc[j][tt][0], cq[j][0][0]);
+                            o[1] = rq_magic<FMA>(acc[j][tt][1], cq[j][0][1]);
+                            o[2] = rq_magic<FMA>(acc[j][tt][2], cq[j][1][0]);
+                            o[3] = rq_magic<FMA>(acc[j][tt][3], cq[j][1][1]);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) o[e] = min(max(o[e], -128), 127);
                             const unsigned w01 = __builtin_amdgcn_perm((unsigned)o[1], (unsigned)o[0], 0x0c0c0400u);
@@ -225,7 +221,6 @@
         } else if (next_ntt > 0) a_fetch(next_tile0, next_ntt);
         {
             const int hw = wave * 2 + (lane >> 5), l32 = lane & 31;
-            typedef __attribute__((address_space(3))) const unsigned char lds_u8;
             typedef unsigned short v2us __attribute__((ext_vector_type(2)));
             const unsigned sm_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char *)sm;
             const unsigned base = sm_lds + G::STAB + hw * 256;           // 256-byte aligned: byte | base is the address
@@ -343,10 +338,10 @@
 #pragma unroll
                 for (int tt = 0; tt < NTT; ++tt) {
                     int t16[4];
-                    t16[0] = mlp_rq<FMA>(acc[j][tt][0], c2[j][0][0]);
-                    t16[1] = mlp_rq<FMA>(acc[j][tt][1], c2[j][0][1]);
-                    t16[2] = mlp_rq<FMA>(acc[j][tt][2], c2[j][1][0]);
-                    t16[3] = mlp_rq<FMA>(acc[j][tt][3], c2[j][1][1]);
+                    t16[0] = rq_magic<FMA>(acc[j][tt][0], c2[j][0][0]);
+                    t16[1] = rq_magic<FMA>(acc[j][tt][1], c2[j][0][1]);
+                    t16[2] = rq_magic<FMA>(acc[j][tt][2], c2[j][1][0]);
+                    t16[3] = rq_magic<FMA>(acc[j][tt][3], c2[j][1][1]);
                     int o[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {

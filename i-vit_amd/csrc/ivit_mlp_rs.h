@@ -9,27 +9,22 @@
 // mlp384_kernel all eight waves are in the same phase: the matrix pipe idles through ShiftGELU and both epilogues.
 //
 // v_mfma_i32_32x32x32_i8 throughout (a lone wave issues it at the full rate; a lone wave reaches half the rate with 16x16x64),
-// weights as the A operand (rows = channels), 32 tokens as the B operand (a lane = a token).  The rows of a weight fragment are
-// placed at plan time so that MFMA row q*8 + h*4 + i is channel h*16 + q*4 + i of the 32-channel tile: accumulator register v of
-// lane (token, h) is then channel 16 h + v — sixteen CONSECUTIVE channels per lane: one ds_write_b128 per token tile into the
-// hidden tile, two 16-byte global stores per token tile in fc2's epilogue.
+// weights as the A operand, sixteen CONSECUTIVE channels per lane (the scheme and its shared pieces: ivit_wa.h): one ds_write_b128
+// per token tile into the hidden tile, two 16-byte global stores per token tile in fc2's epilogue.
 //
 // One hidden tile (<= 80 tokens x 1536 B = 120 KB; two do not fit and smaller units pay the 1.18 MB weight sweep more often),
 // so a producer may only overwrite the 128-channel slice r of the hidden tile once every consumer is past it in fc2's K loop of
 // the PREVIOUS unit: the producer parks up to RS_HD requantised rounds in registers (4 dwords per token tile and round) and
 // writes round r - RS_HD behind the K loop of round r.  Hand-over by monotonically increasing LDS counters (no workgroup barrier
 // after the prologue): F_H hidden tile of unit u complete (4 producers), F_G ShiftGELU of unit u complete (4 consumers),
-// F_R[r] consumers past slice r in fc2 of unit u, F_A producers done with the activation tile, F_D next activation tile landed.
-// An LDS instruction stream of one wave executes in order, so "data accesses, then ds_add" / "ds_read counter, then data
-// accesses" need no fences beyond keeping the compiler from reordering them (asm volatile + memory clobber).
+// F_R[r] consumers past slice r in fc2 of unit u, F_A producers done with the activation tile, F_D next activation tile landed
+// (rs_signal / rs_wait: ivit_wa.h).
 //
-// LDS images: [64-column block][token][64 B]; the four 16-byte chunks of a token's 64 B are permuted by
-// g(token) = ((token >> 1) & 3) ^ gray((token >> 3) & 3): conflict-free both for the B-fragment ds_read_b128 (lane groups
-// {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and their upper-half twins: MI355X_MICROARCH.md, LDS) and for the producers'
-// ds_write_b128 (eight consecutive tokens per group, 32 banks).
+// LDS images: [64-column block][token][64 B], the four 16-byte chunks of a token's 64 B permuted by wa_g(token) (ivit_wa.h).
 #pragma once
 #include "ivit_mlp.h"
 #include "ivit_layernorm.h"
+#include "ivit_wa.h"
 
 #define RS_T 80                                  // token rows of a unit in LDS (5 tiles of 16)
 #define RS_KBLK (RS_T * 64)
@@ -50,15 +45,12 @@
 #define RS_HD 6                                  // producer: requantised rounds parked in registers; divides 12
 #define RS_WD2 3                                 // consumer: k-steps of weight fragments in flight (3 fragments each)
 
-__device__ __forceinline__ int rs_chan_of_row(int rho) { return ((rho >> 2) & 1) * 16 + (rho >> 3) * 4 + (rho & 3); }
-__device__ __forceinline__ int rs_g(int tok) { return ((tok >> 1) & 3) ^ ((tok >> 3) & 3) ^ ((tok >> 4) & 1); }
-
 // fc1 weights [1536][384] -> fragments of 64 lanes x 16 B in consumption order: fragment (r * 12 + ks) * 4 + w is what
 // producer w multiplies in k-step ks (32 columns) of round r (channels 128 r + 32 w ...): one contiguous 4 KB window per step
 __global__ __launch_bounds__(256) void rs_swizzle_w1_kernel(const int8_t *__restrict__ w, v4i *__restrict__ wf) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < 144 * 4 * 64; i += gridDim.x * 256) {
         const int l = i & 63, f = i >> 6, pw = f & 3, s = f >> 2, r = s / 12, ks = s - r * 12;
-        const int ch = 128 * r + 32 * pw + rs_chan_of_row(l & 31);
+        const int ch = 128 * r + 32 * pw + wa_chan_of_row(l & 31);
         wf[i] = *reinterpret_cast<const v4i *>(w + (size_t)ch * MLP_C + 32 * ks + 16 * (l >> 5));
     }
 }
@@ -66,50 +58,15 @@ __global__ __launch_bounds__(256) void rs_swizzle_w1_kernel(const int8_t *__rest
 __global__ __launch_bounds__(256) void rs_swizzle_w2_kernel(const int8_t *__restrict__ w, v4i *__restrict__ wf) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < 48 * 12 * 64; i += gridDim.x * 256) {
         const int l = i & 63, f = i >> 6, ct = f % 3, j = (f / 3) & 3, ks = f / 12;
-        const int ch = 96 * j + 32 * ct + rs_chan_of_row(l & 31);
+        const int ch = 96 * j + 32 * ct + wa_chan_of_row(l & 31);
         wf[i] = *reinterpret_cast<const v4i *>(w + (size_t)ch * MLP_HD + 32 * ks + 16 * (l >> 5));
     }
-}
-
-// Both hand-over primitives are single asm blocks: straight-line code for the register allocator (as C++ the spin loop was
-// unrolled nine times and every `if (lane == 0)` split a basic block: 1.4 K spilled registers in the producers).
-__device__ __forceinline__ void rs_signal(unsigned flag_addr) {            // lane 0 adds 1 (flag_addr is wave-uniform)
-    unsigned long long save;
-    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_add_u32 %1, %2\n\ts_mov_b64 exec, %0"
-                 : "=&s"(save) : "v"(flag_addr), "v"(1u) : "memory");
-}
-// spin until the LDS counter reaches `target` (the counters only grow).  A hand-over that never comes is a bug: trap loudly —
-// after 2^28 polls of >= 64 cycles each (~10 s: far beyond any stall a debugger, a profiler or throttled clocks produce, short
-// enough that a real deadlock ends the launch instead of wedging the queue)
-__device__ __forceinline__ void rs_wait(unsigned flag_addr, unsigned target) {
-    unsigned v, cnt, tmp;
-    asm volatile("s_mov_b32 %1, 0\n"
-                 ".Lrsw%=:\n\t"
-                 "ds_read_b32 %0, %3\n\t"
-                 "s_waitcnt lgkmcnt(0)\n\t"
-                 "v_readfirstlane_b32 %2, %0\n\t"
-                 "s_sub_i32 %2, %2, %4\n\t"
-                 "s_cmp_ge_i32 %2, 0\n\t"
-                 "s_cbranch_scc1 .Lrsd%=\n\t"
-                 "s_sleep 1\n\t"
-                 "s_add_u32 %1, %1, 1\n\t"
-                 "s_cmp_lt_u32 %1, 0x10000000\n\t"
-                 "s_cbranch_scc1 .Lrsw%=\n\t"
-                 "s_trap 2\n"
-                 ".Lrsd%=:"
-                 : "=&v"(v), "=&s"(cnt), "=&s"(tmp) : "v"(flag_addr), "s"(target) : "memory", "scc");
 }
 
 // LNH: 0 = the activations are 8-bit (p.x); 1 = norm2 of every row of the workgroup first, by all eight waves
 template <bool FMA, int LNH = 0>
 __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
     extern __shared__ __attribute__((aligned(256))) char sm[];
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    typedef __attribute__((address_space(3))) char lds_c;
-    typedef __attribute__((address_space(3))) v4i lds_v4i;
-    typedef __attribute__((address_space(3))) unsigned lds_u32;
-    typedef __attribute__((address_space(3))) int lds_i32;
-    typedef __attribute__((address_space(3))) v2i lds_v2i;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned sm_lds = (unsigned)(size_t)(lds_c *)sm;
     const unsigned fl = sm_lds + RS_SFLAG;
@@ -141,12 +98,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
             const long long row = live ? row_raw : r_end - 1;
             const int16_t *xp = p.residual + row * MLP_C + 8 * k + 4 * hh;
             float xv[LG::NSTEP][LG::EPC];
-#pragma unroll
-            for (int i = 0; i < LG::NSTEP; ++i) {
-                const LnRaw<4>::T t = *reinterpret_cast<const LnRaw<4>::T *>(xp + 32 * i);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) xv[i][c] = requotient_m((float)t[c], p.ln_s, ys);
-            }
+            LN_ROW_X(LG, xv, LG::raw_at(xp + 32 * i), p.ln_s, ys);
             LG::run(xv, j, k, 8 * k + 4 * hh, ln_fast, live, cC, cB, cSc, cY, a8 + row * MLP_C + 8 * k + 4 * hh);
         }
     };
@@ -166,21 +118,10 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
     }
     __syncthreads();
 
-    // activation tile of a unit: global -> LDS by DMA, 16 tokens x 4 chunk slots per instruction; the source chunk of a
-    // slot is slot ^ g(token) (the permutation is applied on the source side; the LDS side of a DMA is lane-linear)
+    // activation tile of a unit: global -> LDS by DMA, one token group of 16 at a time
     auto a_dma = [&](long long tile0, int ntt) __attribute__((always_inline)) {
         const int lane = threadIdx.x & 63;
-        for (int tg = 0; tg < ntt; ++tg) {
-            const int tokl = tg * 16 + (lane >> 2), c = (lane & 3) ^ rs_g(tokl);
-            const long long grow = min(tile0 * 16 + tokl, p.M - 1);
-            const int8_t *src = p.x + grow * MLP_C + c * 16;
-#pragma unroll
-            for (int kb = 0; kb < MLP_KS1; ++kb) {
-                const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(RS_SA + kb * RS_KBLK + tg * 1024));
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + kb * 64),
-                                                 (__attribute__((address_space(3))) void *)(sm + dst), 16, 0, 0);
-            }
-        }
+        for (int tg = 0; tg < ntt; ++tg) WA_DMA16(MLP_KS1, RS_KBLK, sm, RS_SA, tg, lane, p.x, tile0 * 16, p.M)
     };
 
     // ------------------------------------------------------------------------------------------------------------------------
@@ -194,7 +135,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
         static_assert(SPI % RS_WR == 0 && 12 % RS_HD == 0, "ring slots must be static across iterations");
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
-        const int lane = tid & 63, tok = lane & 31, kh = lane >> 5, e = kh ^ rs_g(tok);
+        const int lane = tid & 63, tok = lane & 31, kh = lane >> 5, e = kh ^ wa_g(tok);
         // LDS addresses as integers (per-lane base + immediates): through `sm + ...` every access costs an address register
         const unsigned fa0 = sm_lds + RS_SA + tok * 64 + e * 16, fa1 = sm_lds + RS_SA + tok * 64 + (e ^ 2) * 16;
         const unsigned hwo = sm_lds + RS_SH + (pw >> 1) * RS_KBLK + tok * 64 + ((((pw & 1) * 2) ^ e) * 16);
@@ -220,11 +161,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
         };
         v16i bias;
         auto load_bias = [&](int r) __attribute__((always_inline)) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const v4i b4 = *reinterpret_cast<const v4i *>(p.b1 + 128 * r + 32 * pw + 16 * kh + 4 * q);
-                bias[4 * q] = b4[0]; bias[4 * q + 1] = b4[1]; bias[4 * q + 2] = b4[2]; bias[4 * q + 3] = b4[3];
-            }
+            WA_ACC_BIAS(bias, *reinterpret_cast<const v4i *>(p.b1 + 128 * r + 32 * pw + 16 * kh + 4 * q));
         };
         load_bias(it0 * RS_HD);
         rs_wait(fl + 4 * RS_F_D, (unsigned)u + 1);
@@ -255,9 +192,8 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (it > it0) flush(rr, r - RS_HD);
                 if (r + 1 < 12) load_bias(r + 1);       // consumed by the next round's first MFMAs, behind this requant
-                // requant: accumulator register v is channel chb + v.  fma(z, c, magic + 128) leaves Q + 128 in the low dword;
-                // v_cvt_pk_i16_i32 and v_sat_pk_u8_i16 saturate to [0, 255] = clamp(Q, -128, 127) + 128 while packing: the hidden
-                // tile holds BIASED bytes, which is what ShiftGELU's table is indexed by
+                // requant: accumulator register v is channel chb + v.  fma(z, c, magic + 128) leaves Q + 128 in the low dword; the
+                // hidden tile holds BIASED bytes (wa_pack_biased), which is what ShiftGELU's table is indexed by
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -266,19 +202,14 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
                             const double c = cq[2 * q + (i >> 1)][i & 1];
-                            const double tq = FMA ? __builtin_fma((double)acc[t][4 * q + i], c, MLP_MAGIC + 128.0)
-                                                  : ((double)acc[t][4 * q + i] * c + (MLP_MAGIC + 128.0));
+                            const double tq = FMA ? __builtin_fma((double)acc[t][4 * q + i], c, RQ_MAGIC + 128.0)
+                                                  : ((double)acc[t][4 * q + i] * c + (RQ_MAGIC + 128.0));
                             o[i] = __double2loint(tq);
                         }
                         mx[t] = max(max(mx[t], o[0]), o[1]);
                         mx[t] = max(max(mx[t], o[2]), o[3]);
                         asm volatile("" : "+v"(mx[t]));
-                        unsigned p01, p23, b01, b23;
-                        asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p01) : "v"(o[0]), "v"(o[1]));
-                        asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p23) : "v"(o[2]), "v"(o[3]));
-                        asm("v_sat_pk_u8_i16 %0, %1" : "=v"(b01) : "v"(p01));
-                        asm("v_sat_pk_u8_i16 %0, %1" : "=v"(b23) : "v"(p23));
-                        int hq = (int)__builtin_amdgcn_perm(b23, b01, 0x05040100u);
+                        int hq = (int)wa_pack_biased(o[0], o[1], o[2], o[3]);
                         asm volatile("" : "+v"(hq));       // pinned here: left alone, the optimiser sinks the whole requant
                         hold[rr][t][q] = hq;               // of all RS_HD rounds to the flush that first reads it (and spills)
                     }
@@ -309,8 +240,8 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
     // ------------------------------------------------------------------------------------------------------------------------
     // ShiftGELU (+ qact1) of a unit in place, half a wavefront per token: half-wave `hwid` of the sixteen takes tokens hwid + 16 i.
     // The row maximum comes from the producers (RS_SMAX, reset here); per token: its 256-byte table line global -> one of this
-    // half-wave's two LDS slots, the row's 12 dwords per lane, 48 byte gathers, write-back.  Gathers are issued three dwords
-    // (12 gathers) ahead of the merge that consumes them (lgkmcnt counts 15 at most), their addresses are one SDWA each.
+    // half-wave's two LDS slots, the row's 12 dwords per lane, 48 byte gathers (wa_gelu_issue), write-back (wa_gelu_merge).  Gathers
+    // are issued three dwords (12 gathers) ahead of the merge that consumes them (lgkmcnt counts 15 at most).
     auto gelu = [&](auto nt_c, const int nvalid) __attribute__((always_inline)) {
         constexpr int NT = decltype(nt_c)::value, NHW = 16;
         constexpr int NTK = (NT == 3 ? 80 : 64) / NHW;                                   // tokens per half-wave
@@ -341,28 +272,14 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
                 for (int c = 0; c <= 4; ++c) {
                     if (c < 4) {
 #pragma unroll
-                        for (int m = 3 * c; m < 3 * c + 3; ++m) {
-                            unsigned a0, a1, a2, a3;
-                            asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(a0) : "v"(w[m]), "v"(base));
-                            asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(a1) : "v"(w[m]), "v"(base));
-                            asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(a2) : "v"(w[m]), "v"(base));
-                            asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(a3) : "v"(w[m]), "v"(base));
-                            asm volatile("ds_read_u8 %0, %1" : "=v"(g[m][0]) : "v"(a0) : "memory");
-                            asm volatile("ds_read_u8 %0, %1" : "=v"(g[m][1]) : "v"(a1) : "memory");
-                            asm volatile("ds_read_u8_d16_hi %0, %1" : "=v"(g[m][2]) : "v"(a2) : "memory");     // byte << 16, low half zeroed (SRAM-ECC d16 semantics)
-                            asm volatile("ds_read_u8_d16_hi %0, %1" : "=v"(g[m][3]) : "v"(a3) : "memory");
-                        }
+                        for (int m = 3 * c; m < 3 * c + 3; ++m) wa_gelu_issue(w[m], base, g[m]);
                     }
                     if (c > 0) {
                         if (c < 4) asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
                         else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-                        for (int m = 3 * c - 3; m < 3 * c; ++m) {
-                            unsigned o, t13;
-                            asm volatile("v_or_b32 %0, %1, %2" : "=v"(t13) : "v"(g[m][1]), "v"(g[m][3]));      // behind the wait
-                            asm volatile("v_or3_b32 %0, %1, %2, %3" : "=v"(o) : "v"(g[m][0]), "v"(g[m][2]), "v"(t13 << 8));
-                            *(lds_u32 *)(size_t)((m < 6 ? rowa : rowb) + i * NHW * 64 + (m % 6) * 2 * RS_KBLK) = o;
-                        }
+                        for (int m = 3 * c - 3; m < 3 * c; ++m)
+                            *(lds_u32 *)(size_t)((m < 6 ? rowa : rowb) + i * NHW * 64 + (m % 6) * 2 * RS_KBLK) = wa_gelu_merge(g[m]);
                     }
                 }
             }
@@ -418,7 +335,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
             constexpr int NT = decltype(nt_c)::value;
             int tid = threadIdx.x;
             asm volatile("" : "+v"(tid));
-            const int lane = tid & 63, tok = lane & 31, kh = lane >> 5, e = kh ^ rs_g(tok);
+            const int lane = tid & 63, tok = lane & 31, kh = lane >> 5, e = kh ^ wa_g(tok);
             const unsigned fh0 = sm_lds + RS_SH + tok * 64 + e * 16, fh1 = sm_lds + RS_SH + tok * 64 + (e ^ 2) * 16;
             const unsigned fh2 = fh0 + 12 * RS_KBLK, fh3 = fh1 + 12 * RS_KBLK;       // the DS offset field holds 16 bits
             const int nvalid = ntt * 16;
@@ -443,12 +360,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
             {
                 v16i bias[3];
 #pragma unroll
-                for (int ct = 0; ct < 3; ++ct)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const v4i b4 = *reinterpret_cast<const v4i *>(p.b2 + 96 * j + 32 * ct + 16 * kh + 4 * q);
-                        bias[ct][4 * q] = b4[0]; bias[ct][4 * q + 1] = b4[1]; bias[ct][4 * q + 2] = b4[2]; bias[ct][4 * q + 3] = b4[3];
-                    }
+                for (int ct = 0; ct < 3; ++ct) WA_ACC_BIAS(bias[ct], *reinterpret_cast<const v4i *>(p.b2 + 96 * j + 32 * ct + 16 * kh + 4 * q));
                 load_b(0, 0);
 #pragma unroll
                 for (int ks = 0; ks < 48; ++ks) {
@@ -494,6 +406,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
                 const int tl = t * 32 + tok;
                 const long long row = tok0 + tl;
                 v4i o0, o1;
+                // (written out, not wa_res_pair: through the helper, the two terms of six of this kernel's residual adds swap places)
 #pragma unroll
                 for (int d = 0; d < 8; ++d) {
                     const unsigned rw = (unsigned)(d < 4 ? idr[n % 3][0][d] : idr[n % 3][1][d - 4]);
@@ -501,7 +414,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void mlp384rs_kernel(MlpArgs p) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int v = 2 * d + h;
-                        const int t16 = min(max(mlp_rq<FMA>(acc[ct][t][v], c2[ct & 1][v >> 1][v & 1]), -32768), 32767);
+                        const int t16 = min(max(rq_magic<FMA>(acc[ct][t][v], c2[ct & 1][v >> 1][v & 1]), -32768), 32767);
                         const int r = h ? ((int)rw >> 16) : (int)(short)(rw & 0xffffu);
                         o[h] = rq_fast(r, p.cr) + rq_fast(t16, p.cm);         // both terms < 2^31 / 2: the sum is the reference's fp64 sum
                     }

@@ -524,7 +524,7 @@ __global__ __launch_bounds__(LUT ? 512 : 256, LUT ? 4 : WA_MINW) void window_att
             const int key = 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * half;      // < 49 except i == 24 on half 1
             kk = (i == 24 && half) ? 48 : key;
             const int z = kt ? acc1[r] : acc0[r];
-            const int v = min(max(__double2loint((double)z * c_qk + 6755399441055744.0), -128), 127);
+            const int v = min(max(__double2loint((double)z * c_qk + RQ_MAGIC), -128), 127);
             return min(max((int)sTa[v + 128] + (int)sRel[qq * 49 + kk], -128), 127);
         };
         if (LUT && !masked) {
@@ -539,9 +539,8 @@ __global__ __launch_bounds__(LUT ? 512 : 256, LUT ? 4 : WA_MINW) void window_att
                 if (i == 8 || i == 16) __builtin_amdgcn_sched_barrier(0);     // three batches of gathers: bounded live registers
             }
             amax = max(amax, __shfl_xor(amax, 32));
-            typedef __attribute__((address_space(3))) const char wa_lds_c;
-            const unsigned aqrow = (unsigned)(size_t)((wa_lds_c *)sAQ) + ((unsigned)sCls[amax + 128] * 256u + 128u) * 2u;
-            const unsigned tb = (unsigned)(size_t)((wa_lds_c *)sT);
+            const unsigned aqrow = (unsigned)(size_t)((lds_cc *)sAQ) + ((unsigned)sCls[amax + 128] * 256u + 128u) * 2u;
+            const unsigned tb = (unsigned)(size_t)((lds_cc *)sT);
             const int qd = amax + p.dmin;
 #pragma unroll
             for (int c0 = 0; c0 < 25; c0 += 13) {
@@ -617,7 +616,7 @@ __global__ __launch_bounds__(LUT ? 512 : 256, LUT ? 4 : WA_MINW) void window_att
             int ob[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                ob[e] = min(max(__double2loint((double)o[g * 4 + e] * c_pv + 6755399441055744.0), -128), 127);
+                ob[e] = min(max(__double2loint((double)o[g * 4 + e] * c_pv + RQ_MAGIC), -128), 127);
             unsigned w01 = __builtin_amdgcn_perm((unsigned)ob[1], (unsigned)ob[0], 0x0c0c0400u);
             unsigned w23 = __builtin_amdgcn_perm((unsigned)ob[3], (unsigned)ob[2], 0x0c0c0400u);
             W[g] = __builtin_amdgcn_perm(w23, w01, 0x05040100u);

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(WA12_THREADS, 3) void window_attention12_kernel(Win
         for (int i = 0; i < 72; ++i) {
             const int kt = i >> 4, r = i & 15;
             const int key = 32 * kt + 8 * (r >> 2) + 4 * half + (r & 3);
-            const int v = min(max(__double2loint((double)acc[kt][r] * c_qk + 6755399441055744.0), -128), 127);
+            const int v = min(max(__double2loint((double)acc[kt][r] * c_qk + RQ_MAGIC), -128), 127);
             const int a = min(max((int)sTa[v + 128] + (int)relq[key], -128), 127);
             float xt;
             if (masked) {
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(WA12_THREADS, 3) void window_attention12_kernel(Win
             int ob[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                ob[e] = min(max(__double2loint((double)o[g * 4 + e] * c_pv + 6755399441055744.0), -128), 127);
+                ob[e] = min(max(__double2loint((double)o[g * 4 + e] * c_pv + RQ_MAGIC), -128), 127);
             unsigned w01 = __builtin_amdgcn_perm((unsigned)ob[1], (unsigned)ob[0], 0x0c0c0400u);
             unsigned w23 = __builtin_amdgcn_perm((unsigned)ob[3], (unsigned)ob[2], 0x0c0c0400u);
             W[g] = __builtin_amdgcn_perm(w23, w01, 0x05040100u);

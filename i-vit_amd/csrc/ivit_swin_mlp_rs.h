@@ -7,15 +7,15 @@
 // (2 x 24 KB — at this width two tiles fit, the structure the round-4 review asked for) and the sixteen waves split by role:
 //   waves 0-7,  producers: fc1 + qact_gelu (8 bit) of tile i + 1 into hidden buffer (i + 1) & 1, row maxima by ds_max
 //   waves 8-15, consumers: ShiftGELU (+ qact1) by table, fc2 + qact2 (16 bit) + qact4 with the identity branch of tile i
-// hand-over by monotone LDS counters (rs_signal / rs_wait of ivit_mlp_rs.h): no workgroup barrier after the prologue, the
+// hand-over by monotone LDS counters (rs_signal / rs_wait: ivit_wa.h): no workgroup barrier after the prologue, the
 // producers' requant VALU runs beside the consumers' gathers and MFMAs.  MFMA rows of both weight matrices are placed so that a
-// lane owns 16 consecutive output channels (one ds_write_b128 into the hidden tile, two 16-byte global stores in the epilogue,
-// no permlane exchange); the requants use the magic-number form with saturating packs where |z c| < 2^31 is provable for every
+// lane owns 16 consecutive output channels (ivit_wa.h: one ds_write_b128 into the hidden tile, two 16-byte global stores in the
+// epilogue, no permlane exchange); the requants use the magic-number form with saturating packs where |z c| < 2^31 is provable for every
 // channel (checked once per workgroup), the v_rndne_f64 form otherwise.
 #pragma once
 #include "ivit_gemm2.h"
 #include "ivit_swin.h"
-#include "ivit_mlp_rs.h"
+#include "ivit_wa.h"
 
 #define SR_X 0                                       // 2 x 6 144, [k-step 3][token tile 2][32 tokens][32 B]
 #define SR_H (SR_X + 2 * MF_BM * MF_C)               // 2 x 24 576, [k-step 12][64 tokens][32 B]
@@ -40,12 +40,6 @@
 
 __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p) {
     extern __shared__ __attribute__((aligned(256))) char sm[];
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    typedef __attribute__((address_space(3))) char lds_c;
-    typedef __attribute__((address_space(3))) v4i lds_v4i;
-    typedef __attribute__((address_space(3))) v2i lds_v2i;
-    typedef __attribute__((address_space(3))) unsigned lds_u32;
-    typedef __attribute__((address_space(3))) int lds_i32;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), half = lane >> 5, l31 = lane & 31;
     const unsigned sm_lds = (unsigned)(size_t)(lds_c *)sm, fl = sm_lds + SR_FLAG;
     double *sC1 = reinterpret_cast<double *>(sm + SR_C1), *sC2 = reinterpret_cast<double *>(sm + SR_C2);
@@ -60,13 +54,13 @@ __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p)
         const double cv = p.dy1[tid].m * p.dy1[tid].r;
         const int bs = p.b1 ? p.b1[tid] : 0;
         sC1[tid] = cv; sB1[tid] = bs;
-        wide |= !(fabs(cv) * ((double)MF_C * 16384.0 + fabs((double)bs)) < 2147483000.0);      // magic-number rounding needs |z c| < 2^31
+        wide |= !rq_magic_safe(cv, (double)MF_C * 16384.0 + fabs((double)bs));
     }
     if (tid < MF_C) {
         const double cv = p.dy2[tid].m * p.dy2[tid].r;
         const int bs = p.b2 ? p.b2[tid] : 0;
         sC2[tid] = cv; sB2[tid] = bs;
-        wide |= !(fabs(cv) * ((double)MF_HD * 16384.0 + fabs((double)bs)) < 2147483000.0);
+        wide |= !rq_magic_safe(cv, (double)MF_HD * 16384.0 + fabs((double)bs));
     }
     if (tid < 16) reinterpret_cast<unsigned *>(sm + SR_FLAG)[tid] = 0;
     if (tid < 2 * MF_BM) reinterpret_cast<int *>(sm + SR_MAX)[tid] = (int)0x80000000;
@@ -102,7 +96,7 @@ __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p)
         for (int k3 = 0; k3 < 3; ++k3)
 #pragma unroll
             for (int kc = 0; kc < 3; ++kc)
-                w1f[k3][kc] = *reinterpret_cast<const v4i *>(p.w1 + (size_t)(((wave + 8 * k3) >> 1) * 32 + rs_chan_of_row(l31)) * MF_C + kc * 32 + half * 16);
+                w1f[k3][kc] = *reinterpret_cast<const v4i *>(p.w1 + (size_t)(((wave + 8 * k3) >> 1) * 32 + wa_chan_of_row(l31)) * MF_C + kc * 32 + half * 16);
         auto produce = [&](auto use_fast) __attribute__((always_inline)) {
             for (int i = 0; i < nmine; ++i) {
                 const int b = i & 1;
@@ -119,11 +113,7 @@ __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p)
                 for (int k3 = 0; k3 < 3; ++k3) {
                     const int unit = wave + 8 * k3, nt = unit >> 1, mt = unit & 1;      // 24 (channel tile, token tile) units over 8 waves
                     v16i acc;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const v4i b4 = *reinterpret_cast<const v4i *>(sB1 + nt * 32 + half * 16 + q * 4);
-                        acc[4 * q] = b4[0]; acc[4 * q + 1] = b4[1]; acc[4 * q + 2] = b4[2]; acc[4 * q + 3] = b4[3];
-                    }
+                    WA_ACC_BIAS(acc, *reinterpret_cast<const v4i *>(sB1 + nt * 32 + half * 16 + q * 4));
 #pragma unroll
                     for (int kc = 0; kc < 3; ++kc) {
                         const v4i xf = *(lds_v4i *)(size_t)(xa + (kc * 2 + mt) * 1024);
@@ -139,20 +129,11 @@ __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p)
                         for (int e = 0; e < 4; e += 2) {
                             const v2d c2 = *reinterpret_cast<const v2d *>(sC1 + nt * 32 + half * 16 + q * 4 + e);
 #pragma unroll
-                            for (int f = 0; f < 2; ++f) {
-                                const double t = (double)acc[4 * q + e + f] * c2[f];
-                                o[e + f] = decltype(use_fast)::value ? __double2loint(t + (6755399441055744.0 + 128.0))
-                                                                     : min(max(rint_sat_i32(t), -128), 127) + 128;
-                            }
+                            for (int f = 0; f < 2; ++f) o[e + f] = rq_biased_byte<decltype(use_fast)::value>((double)acc[4 * q + e + f] * c2[f]);
                         }
                         mx = max(max(mx, o[0]), o[1]);
                         mx = max(max(mx, o[2]), o[3]);
-                        unsigned p01, p23, b01, b23;
-                        asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p01) : "v"(o[0]), "v"(o[1]));
-                        asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p23) : "v"(o[2]), "v"(o[3]));
-                        asm("v_sat_pk_u8_i16 %0, %1" : "=v"(b01) : "v"(p01));
-                        asm("v_sat_pk_u8_i16 %0, %1" : "=v"(b23) : "v"(p23));
-                        hw[q] = (int)__builtin_amdgcn_perm(b23, b01, 0x05040100u);
+                        hw[q] = (int)wa_pack_biased(o[0], o[1], o[2], o[3]);
                     }
                     *(lds_v4i *)(size_t)(ha + nt * (MF_BM * 32) + mt * 1024) = hw;
                     asm volatile("ds_max_i32 %0, %1" ::"v"(sm_lds + SR_MAX + (b * MF_BM + mt * 32 + l31) * 4), "v"(min(mx, 255)) : "memory");
@@ -175,7 +156,7 @@ __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p)
         v4i w2f[12];                                    // fc2: this wave's channel tile (cw >> 1), all of K
 #pragma unroll
         for (int kc = 0; kc < 12; ++kc)
-            w2f[kc] = *reinterpret_cast<const v4i *>(p.w2 + (size_t)((cw < 6 ? cw >> 1 : 0) * 32 + rs_chan_of_row(l31)) * MF_HD + kc * 32 + half * 16);
+            w2f[kc] = *reinterpret_cast<const v4i *>(p.w2 + (size_t)((cw < 6 ? cw >> 1 : 0) * 32 + wa_chan_of_row(l31)) * MF_HD + kc * 32 + half * 16);
         auto consume = [&](auto use_fast) __attribute__((always_inline)) {
             for (int i = 0; i < nmine; ++i) {
                 const int b = i & 1;
@@ -209,25 +190,10 @@ __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p)
 #pragma unroll
                         for (int m = 0; m < 3; ++m) w[m] = *(lds_u32 *)(size_t)(ra + m * 4 * (MF_BM * 32));
 #pragma unroll
-                        for (int m = 0; m < 3; ++m) {
-                            unsigned a0, a1, a2, a3;
-                            asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(a0) : "v"(w[m]), "v"(base));
-                            asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(a1) : "v"(w[m]), "v"(base));
-                            asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(a2) : "v"(w[m]), "v"(base));
-                            asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(a3) : "v"(w[m]), "v"(base));
-                            asm volatile("ds_read_u8 %0, %1" : "=v"(g[m][0]) : "v"(a0) : "memory");
-                            asm volatile("ds_read_u8 %0, %1" : "=v"(g[m][1]) : "v"(a1) : "memory");
-                            asm volatile("ds_read_u8_d16_hi %0, %1" : "=v"(g[m][2]) : "v"(a2) : "memory");     // byte << 16, low half zeroed (SRAM-ECC d16)
-                            asm volatile("ds_read_u8_d16_hi %0, %1" : "=v"(g[m][3]) : "v"(a3) : "memory");
-                        }
+                        for (int m = 0; m < 3; ++m) wa_gelu_issue(w[m], base, g[m]);
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-                        for (int m = 0; m < 3; ++m) {
-                            unsigned o, t13;
-                            asm volatile("v_or_b32 %0, %1, %2" : "=v"(t13) : "v"(g[m][1]), "v"(g[m][3]));      // behind the wait
-                            asm volatile("v_or3_b32 %0, %1, %2, %3" : "=v"(o) : "v"(g[m][0]), "v"(g[m][2]), "v"(t13 << 8));
-                            *(lds_u32 *)(size_t)(ra + m * 4 * (MF_BM * 32)) = o;
-                        }
+                        for (int m = 0; m < 3; ++m) *(lds_u32 *)(size_t)(ra + m * 4 * (MF_BM * 32)) = wa_gelu_merge(g[m]);
                     }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -235,12 +201,9 @@ __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p)
                 rs_wait(fl + 4 * SR_F_G, 8u * (unsigned)(i + 1));
                 if (cw >= 6) { rs_signal(fl + 4 * SR_F_F); continue; }
                 // ---- fc2 + qact2 (16 bit) + qact4 with the identity branch: channels 32 nt + 16 half + v of token tok
-                v16i acc;                 // (two accumulator chains over even / odd k-steps measured slower: 280 vs 264 us, and spilled)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const v4i b4 = *reinterpret_cast<const v4i *>(sB2 + nt * 32 + half * 16 + q * 4);
-                    acc[4 * q] = b4[0]; acc[4 * q + 1] = b4[1]; acc[4 * q + 2] = b4[2]; acc[4 * q + 3] = b4[3];
-                }
+                // (two accumulator chains over even / odd k-steps measured slower: 280 vs 264 us, and spilled)
+                v16i acc;
+                WA_ACC_BIAS(acc, *reinterpret_cast<const v4i *>(sB2 + nt * 32 + half * 16 + q * 4));
                 const unsigned ga = sm_lds + SR_H + b * (MF_BM * MF_HD) + (mt * 32 + l31) * 32 + half * 16;
 #pragma unroll
                 for (int kc = 0; kc < 12; ++kc) {
@@ -252,19 +215,8 @@ __global__ __launch_bounds__(SR_THREADS) void swin_mlp_rs_kernel(MlpFusedArgs p)
                 v4i o0, o1;
 #pragma unroll
                 for (int d = 0; d < 8; ++d) {
-                    const v2d c2 = *reinterpret_cast<const v2d *>(sC2 + nt * 32 + half * 16 + 2 * d);
-                    const int rw = d < 4 ? r0[d] : r1[d - 4];
-                    int o[2];
-#pragma unroll
-                    for (int f = 0; f < 2; ++f) {
-                        const double t = (double)acc[2 * d + f] * c2[f];
-                        const int t16 = min(max(decltype(use_fast)::value ? __double2loint(t + 6755399441055744.0) : rint_sat_i32(t), -32768), 32767);
-                        const int r = f ? (rw >> 16) : (int)(short)(rw & 0xffff);
-                        // both terms are integers < 2^31: the sum is the reference's fp64 sum (quant_utils.py:238-244)
-                        o[f] = res_fast ? rq_fast(r, cr) + rq_fast(t16, cm) : rq_lean_wide(r, cr) + rq_lean_wide(t16, cm);
-                    }
-                    int pk;
-                    asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(pk) : "v"(o[0]), "v"(o[1]));      // clamp to 16 bits and pack
+                    const int pk = wa_res_pair<decltype(use_fast)::value ? 0 : 2>(acc[2 * d], acc[2 * d + 1], *reinterpret_cast<const v2d *>(sC2 + nt * 32 + half * 16 + 2 * d),
+                                                                                 d < 4 ? r0[d] : r1[d - 4], cm, cr, res_fast);
                     if (d < 4) o0[d] = pk; else o1[d - 4] = pk;
                 }
                 if (tok < p.M) {

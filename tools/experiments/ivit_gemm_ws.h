@@ -7,7 +7,7 @@
 // models/vit_quant.py:65-74) with the WEIGHTS of a 32-channel tile resident in registers and the tokens of a whole CU in LDS:
 //
 //   * a workgroup (8 waves, one per CU) owns a contiguous range of 32-token tiles (<= WS_MAXT: 7 x 32 x 384 B = 86 KB of LDS,
-//     loaded once by DMA, [64-column block][token][64 B] with the chunk permutation of ivit_mlp_rs.h);
+//     loaded once by DMA, [64-column block][token][64 B] with the chunk permutation of ivit_wa.h);
 //   * a wave's task is (64-channel slab = one head of q, k or v; one half of the CU's token tiles); the 2 x 12 16-byte A
 //     fragments of the slab (24 KB) stay in 96 registers while the wave sweeps its token tiles two at a time (tokens are the
 //     B operand, a lane = a token; each B fragment read from LDS feeds two MFMAs — with one channel tile per wave the LDS read
