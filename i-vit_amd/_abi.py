@@ -1,4 +1,4 @@
-"""include/ivit.h, parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from it,
+"""include/ivit.h and include/ivit_eval.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
 tools/gen_twin_header.py prints the CPU twin's prototypes from it, the tests bind the twin and walk the entry points through it.
 Standard library only, so a tool loads this file without the package (and without torch).
 
@@ -7,6 +7,8 @@ Standard library only, so a tool loads this file without the package (and withou
     ABI.structs     name -> [Decl, ...] in declaration order
     ABI.handles     names of the opaque handles (typedef struct X *name;)
     ABI.constants   the enum's values and the integer #defines (IVIT_VERSION)
+    EVAL_ABI        the same of include/ivit_eval.h, the second public header: ITS functions and constants (IVIT_EVAL_VERSION), with
+                    the handles and structs of ivit.h, which it includes, known to it
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -25,6 +27,7 @@ import os
 import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ivit.h")
+EVAL_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_eval.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -78,12 +81,15 @@ def _function(decl, abi):
     return Function(ret, params, text)
 
 
-def parse(text):
-    """the declarations of a header in the dialect of include/ivit.h -> Abi"""
+def parse(text, base=None):
+    """the declarations of a header in the dialect of include/ivit.h -> Abi.  `base`: the Abi of a header this one includes — its
+    handles and structs are known types here (and listed in the result, so that ctype() maps them); functions and constants are
+    this header's own"""
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     if "/*" in text:
         raise AbiError(f"include/ivit.h: unterminated comment `{text[text.index('/*'):][:80]}`")
-    abi = Abi(collections.OrderedDict(), collections.OrderedDict(), [], collections.OrderedDict())
+    abi = Abi(collections.OrderedDict(), collections.OrderedDict(base.structs if base else ()), list(base.handles if base else ()),
+              collections.OrderedDict())
     lines = []
     for line in text.split("\n"):
         if line.lstrip().startswith("#"):                    # preprocessor: an integer #define is a constant, a macro is refused
@@ -159,3 +165,5 @@ def signatures(abi, structs):
 
 with open(HEADER) as _f:
     ABI = parse(_f.read())
+with open(EVAL_HEADER) as _f:
+    EVAL_ABI = parse(_f.read(), base=ABI)

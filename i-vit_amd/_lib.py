@@ -1,5 +1,7 @@
-"""ctypes binding of the C-ABI in include/ivit.h (libivit_hip.so, built in-tree).  Nothing of the ABI is restated here: the
-Structures, the status codes and every argtypes / restype are derived from the header by _abi.py (the mapping rule is stated there).
+"""ctypes binding of the C-ABI in include/ivit.h and include/ivit_eval.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
+restated here: the Structures, the status codes and every argtypes / restype are derived from the headers by _abi.py (the mapping
+rule is stated there).  ivit.h is frozen at IVIT_VERSION 111: ABI / SIGNATURES / RESTYPES are its prototypes and stay what they are;
+the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -51,6 +53,14 @@ _signatures = _abi.signatures(ABI, _structs)
 RESTYPES = {name: ret for name, (ret, args) in _signatures.items()}        # prototype of the header -> restype
 SIGNATURES = {name: args for name, (ret, args) in _signatures.items()}      # prototype of the header -> argtypes
 
+# include/ivit_eval.h, by the same rule (it declares no struct of its own: the Structures are those of ivit.h)
+EVAL_ABI = _abi.EVAL_ABI
+IVIT_EVAL_VERSION = EVAL_ABI.constants["IVIT_EVAL_VERSION"]
+assert set(EVAL_ABI.structs) == set(ABI.structs) and not set(EVAL_ABI.functions) & set(ABI.functions)
+_eval_signatures = _abi.signatures(EVAL_ABI, _structs)
+EVAL_RESTYPES = {name: ret for name, (ret, args) in _eval_signatures.items()}
+EVAL_SIGNATURES = {name: args for name, (ret, args) in _eval_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -59,7 +69,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -97,6 +107,14 @@ def bind(lib, names=None, prefix="ivit_"):
     return lib
 
 
+def bind_eval(lib):
+    """the same for every prototype of include/ivit_eval.h"""
+    for name, args in EVAL_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, EVAL_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -108,7 +126,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind(ctypes.CDLL(SO_PATH))
+    _lib = bind_eval(bind(ctypes.CDLL(SO_PATH)))
     return _lib
 
 

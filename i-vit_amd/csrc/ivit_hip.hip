@@ -1,4 +1,4 @@
-// ivit_hip.hip — C-ABI (include/ivit.h) over the gfx950 kernels.
+// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -28,6 +28,7 @@
 #include "ivit_gemm_ws.h"
 #include "ivit_swin12.h"
 #include "ivit_topk.h"
+#include "ivit_score.h"
 #include "ivit_preprocess.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
@@ -1938,6 +1939,20 @@ int ivit_logits_topk(ivit_handle h, const int32_t *logits, const float *scale, i
     const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per image; 64-bit sum: no overflow near INT_MAX
     if (num_classes <= TOPK_REG_CLASSES) logits_topk_kernel<true><<<grid, 256, 0, h->stream>>>(logits, scale, batch, num_classes, k, idx, val);
     else logits_topk_kernel<false><<<grid, 256, 0, h->stream>>>(logits, scale, batch, num_classes, k, idx, val);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+int ivit_logits_score(ivit_handle h, const int32_t *logits, const float *scale, const int64_t *labels, int batch, int num_classes,
+                      int32_t *rank, double *nll) {
+    CHECK_H(h);
+    REQUIRE(h, logits && scale && labels && batch >= 0 && num_classes >= 1, "bad arguments");
+    REQUIRE(h, rank || nll, "rank and nll are both null");
+    if (batch == 0) return IVIT_OK;
+    const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per image, as ivit_logits_topk
+    const long long *lab = (const long long *)labels;
+    if (num_classes <= TOPK_REG_CLASSES) logits_score_kernel<true><<<grid, 256, 0, h->stream>>>(logits, scale, lab, batch, num_classes, rank, nll);
+    else logits_score_kernel<false><<<grid, 256, 0, h->stream>>>(logits, scale, lab, batch, num_classes, rank, nll);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

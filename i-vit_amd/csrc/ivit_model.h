@@ -481,6 +481,22 @@ int ivit_vit_predict_graph_create(ivit_vit m, const int8_t *images, int batch, i
     return graph_capture(m->h, out, [&] { return ivit_vit_predict(m, images, batch, nslices, workspace, bytes, logits, head_scale, k, idx, val); });
 }
 
+// the forward, then rank and nll of the labels among its logits (include/ivit_eval.h): the same place behind the slices' join
+int ivit_vit_score(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                   const float *head_scale, const int64_t *labels, int32_t *rank, double *nll) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, head_scale && labels && (rank || nll), "head_scale / labels null, or rank and nll both null");
+    RUN(ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits));
+    return ivit_logits_score(m->h, logits, head_scale, labels, batch, m->cfg.num_classes, rank, nll);
+}
+
+int ivit_vit_score_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                                int32_t *logits, const float *head_scale, const int64_t *labels, int32_t *rank, double *nll,
+                                ivit_graph *out) {
+    if (!m) return IVIT_ERR_INVALID;
+    return graph_capture(m->h, out, [&] { return ivit_vit_score(m, images, batch, nslices, workspace, bytes, logits, head_scale, labels, rank, nll); });
+}
+
 int ivit_graph_launch(ivit_graph g) {
     if (!g) return IVIT_ERR_INVALID;
     hipError_t e = hipGraphLaunch(g->exec, g->h->stream);
@@ -806,6 +822,22 @@ int ivit_swin_predict_graph_create(ivit_swin m, const int8_t *images, int batch,
                                   int32_t *logits, const float *head_scale, int k, int32_t *idx, float *val, ivit_graph *out) {
     if (!m) return IVIT_ERR_INVALID;
     return graph_capture(m->h, out, [&] { return ivit_swin_predict(m, images, batch, nslices, workspace, bytes, logits, head_scale, k, idx, val); });
+}
+
+// the forward, then rank and nll of the labels among its logits (include/ivit_eval.h): the same place behind the slices' join
+int ivit_swin_score(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                    const float *head_scale, const int64_t *labels, int32_t *rank, double *nll) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, head_scale && labels && (rank || nll), "head_scale / labels null, or rank and nll both null");
+    RUN(ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits));
+    return ivit_logits_score(m->h, logits, head_scale, labels, batch, m->cfg.num_classes, rank, nll);
+}
+
+int ivit_swin_score_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                                 int32_t *logits, const float *head_scale, const int64_t *labels, int32_t *rank, double *nll,
+                                 ivit_graph *out) {
+    if (!m) return IVIT_ERR_INVALID;
+    return graph_capture(m->h, out, [&] { return ivit_swin_score(m, images, batch, nslices, workspace, bytes, logits, head_scale, labels, rank, nll); });
 }
 
 }  // extern "C"

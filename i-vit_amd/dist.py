@@ -58,14 +58,15 @@ def build_swin_engine_broadcast(cfg, weights, scales, device, rank, world):
     return SwinEngine(cfg, None, None, device=device, packed=broadcast_packed(packed, rank, world, device))
 
 
-def evaluate_sharded(engine, images, labels, batch, rank, world, topk=(1, 5), transform=None):
+def evaluate_sharded(engine, images, labels, batch, rank, world, topk=(1, 5), transform=None, loss=False):
     """ivit_amd.predict.evaluate over THIS rank's contiguous share (shard_range) of `images` / `labels`, in batches of `batch`:
     every rank predicts its own images, its labels are uploaded once, and the hit counts meet in the one all_reduce that ends
-    evaluate — no collective and no host-device copy per step.  Returns the reduced result on every rank."""
+    evaluate — no collective and no host-device copy per step.  loss=True adds the reference's `Loss` (evaluate's loss=True).
+    Returns the reduced result on every rank."""
     from .predict import evaluate
     lo, hi = shard_range(len(labels), rank, world)
     if getattr(engine, "device", None) is not None:      # this rank's labels go up once: no copy inside evaluate's loop
         labels = torch.as_tensor(labels)[lo:hi].to(engine.device)
         lo, hi, images = 0, hi - lo, images[lo:hi]
     batches = ((images[a:min(a + batch, hi)], labels[a:min(a + batch, hi)]) for a in range(lo, hi, batch))
-    return evaluate(engine, batches, topk=topk, transform=transform, rank=rank, world=world)
+    return evaluate(engine, batches, topk=topk, transform=transform, rank=rank, world=world, loss=loss)

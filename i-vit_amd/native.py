@@ -1,8 +1,9 @@
 """NativeEngine — what ViTEngine and SwinEngine share: one frozen model behind the C runners of csrc/ivit_model.h.
 
 The base owns the device and handle, the constants blob, the workspace cache and the four ways into a runner:
-`forward` / `capture` (ivit_<model>_forward, one C call per batch, or its hipGraph) and `predict` / `capture_predict` (the same
-with the top-k of the dequantised logits behind them, ivit_<model>_predict).  A subclass names its C prefix, builds its
+`forward` / `capture` (ivit_<model>_forward, one C call per batch, or its hipGraph), `predict` / `capture_predict` (the same
+with the top-k of the dequantised logits behind them, ivit_<model>_predict) and `score` / `capture_score` (with the labels' rank and
+negative log-likelihood behind them instead, ivit_<model>_score of include/ivit_eval.h).  A subclass names its C prefix, builds its
 parameter structs (`_native_params`) and keeps its `forward_ops`.  torch is used for device memory and streams only.
 """
 import ctypes
@@ -46,8 +47,8 @@ class ShapeCache:
 
 
 class NativeEngine:
-    # "ivit_vit" / "ivit_swin": the entries are PREFIX + _create, _destroy, _workspace_bytes, _forward, _graph_create, _predict and
-    # _predict_graph_create
+    # "ivit_vit" / "ivit_swin": the entries are PREFIX + _create, _destroy, _workspace_bytes, _forward, _graph_create, _predict,
+    # _predict_graph_create, _score and _score_graph_create
     PREFIX = None
     MAX_SLICES = 8
 
@@ -64,6 +65,7 @@ class NativeEngine:
         self._graph_keys = self._native_ws.pinned
         self._graphs = []
         self._predict_out = {}
+        self._score_out = {}
         self._gstream = None                    # the stream graphs are captured and replayed on, made by the first capture
         self._head_scale_host = None
         self.last_logits = None
@@ -137,6 +139,28 @@ class NativeEngine:
                                torch.empty(key[0], key[2], dtype=torch.float32, device=self.device), False]
         return hit[1], hit[2]
 
+    def _score_buffers(self, logits, key):
+        """(rank, nll) of one (batch, slices): the rule of _predict_buffers"""
+        outs = self._score_out
+        hit = outs.get(key)
+        if hit is None or hit[0] is not logits:
+            for old in [q for q, v in outs.items() if not v[3] and q not in self._native_ws]:
+                del outs[old]
+            hit = outs[key] = [logits, torch.empty(key[0], dtype=torch.int32, device=self.device),
+                               torch.empty(key[0], dtype=torch.float64, device=self.device), False]
+        return hit[1], hit[2]
+
+    def _check_labels(self, labels, B):
+        assert isinstance(labels, torch.Tensor) and labels.dtype == torch.int64 and labels.device == self.device, "labels: int64 device tensor"
+        assert labels.shape == (B,) and labels.is_contiguous(), f"labels must be a contiguous [{B}]"
+
+    def _score_args(self, images, labels, nslices):
+        """(arguments of the score entries, cache key, buffers) for one batch and its labels"""
+        self._check_labels(labels, images.shape[0])
+        args, key, (ws, logits) = self._args(images, nslices)
+        rank, nll = self._score_buffers(logits, key)
+        return args + (self.ptr("head.scale"), _ptr(labels), _ptr(rank), _ptr(nll)), key, (ws, logits, rank, nll)
+
     def _check_images(self, images):
         assert images.dtype == torch.int8 and images.is_contiguous() and images.device == self.device
 
@@ -182,6 +206,19 @@ class NativeEngine:
         self.last_logits = logits
         return (idx.clone(), val.clone()) if copy else (idx, val)
 
+    def score(self, images, labels, nslices=1, copy=False):
+        """images int8 [B, C, H, W], labels int64 device tensor [B] -> (rank int32 [B], nll float64 [B]) device tensors: per image
+        the number of classes the model puts before the label (the label is among the first j exactly when rank < j) and the
+        cross-entropy of the label, as `predict.score_reference` states them.  One native call (the forward, then the score
+        launch behind the slices' join); `last_logits` holds the int32 logits of the same call.  The results are the engine's own
+        buffers for this (batch, nslices): copy=True (or clone) to keep them across calls."""
+        self._use_current_stream()
+        self._check_images(images)
+        args, _, (_, logits, rank, nll) = self._score_args(images, labels, nslices)
+        self._entry("_score", *args)
+        self.last_logits = logits
+        return (rank.clone(), nll.clone()) if copy else (rank, nll)
+
     def _capture(self, suffix, images, args, key, bufs, out):
         """hipGraph of the entry PREFIX + suffix on fixed buffers; returns a callable that replays it and returns `out`"""
         if self._gstream is None:
@@ -217,4 +254,13 @@ class NativeEngine:
         args, key, bufs = self._args(images, nstreams, k)
         replay = self._capture("_predict_graph_create", images, args, key, bufs, bufs[2:])
         self._predict_out[key][3] = True
+        return replay
+
+    def capture_score(self, images, labels, nstreams=1):
+        """hipGraph of one score on fixed buffers; returns a callable that replays it and returns (rank, nll).  A replay reads
+        `images` and `labels` as they are then: both live as long as the callable does."""
+        self._check_images(images)
+        args, key, bufs = self._score_args(images, labels, nstreams)
+        replay = self._capture("_score_graph_create", images, args, key, bufs + (labels,), bufs[2:4])
+        self._score_out[key][3] = True
         return replay

@@ -1,7 +1,8 @@
-"""Top-k accuracy of a frozen model over a file of images and labels: the counterpart of the reference's
-`quant_train.py --evaluate` (validate(), quant_train.py:314-351) without its data loader.
+"""Top-k accuracy — and with --loss the cross-entropy — of a frozen model over a file of images and labels: the counterpart of
+the reference's `quant_train.py --evaluate` (validate(), quant_train.py:314-351) without its data loader.
 
     python tools/evaluate.py data.npz --model deit_tiny --golden tests/golden/deit_tiny_b1.npz
+    python tools/evaluate.py data.npz --model deit_tiny --golden tests/golden/deit_tiny_b1.npz --loss
     python tools/evaluate.py data.npz --model deit_small --state-dict checkpoint.pth.tar --batch 128 --topk 1 5
 
 data.npz holds `labels` [N] and the images in one of three forms:
@@ -17,7 +18,11 @@ The model is a name from ivit_amd.CONFIGS / SWIN_CONFIGS with either
   --golden F      the seeded synthetic weights and the calibrated scales recorded in a tests/golden fixture, or
   --state-dict F  a reference state dict / checkpoint (float parameters and act_scaling_factor buffers; ivit_amd.checkpoint).
 Prints one JSON line {"n", "correct", "acc", "model", "batch"}; under torch.distributed.run every rank evaluates its shard of the
-file and rank 0 prints the reduced result (IVIT_DIST_BACKEND picks the backend, as in bench.py)."""
+file and rank 0 prints the reduced result (IVIT_DIST_BACKEND picks the backend, as in bench.py).
+--loss scores every image on the device (ivit_amd.predict.evaluate(loss=True): rank and negative log-likelihood of the label, any
+--topk, no limit of 16), adds "loss" to the JSON line and prints validate()'s summary after it, ` * Loss 6.9078e+00 Prec@1 0.100
+Prec@5 0.500` (the loss as its meter formats it, quant_train.py:316; a Prec@j per --topk entry).  Without --loss the output is
+unchanged."""
 import argparse
 import json
 import os
@@ -63,6 +68,7 @@ def main():
     ap.add_argument("--resize", type=int, default=0, help="shorter side before the centre crop (default: int(crop / 0.875))")
     ap.add_argument("--resample", choices=("torch", "pil"), default="torch",
                     help="uint8 [N, H, W, 3] images: the torch-pinned resize (default) or the PIL-exact one; ragged files are always pil")
+    ap.add_argument("--loss", action="store_true", help="also the mean cross-entropy of the labels (validate()'s Loss), computed on the device")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/evaluate.py needs a HIP device; the product path has no CPU fallback")
@@ -115,10 +121,13 @@ def main():
                              f"got {images.dtype} {images.shape}")
         mine = torch.from_numpy(np.ascontiguousarray(images[lo:hi])).to(device)      # this rank's share only
     batches = ((mine[a:a + args.batch], share[a:a + args.batch]) for a in range(0, hi - lo, args.batch))
-    out = evaluate(eng, batches, topk=args.topk, transform=transform, rank=rank, world=world)       # ends with the one all_reduce
+    out = evaluate(eng, batches, topk=args.topk, transform=transform, rank=rank, world=world, loss=args.loss)     # ends with the one all_reduce
     if rank == 0:
         print(json.dumps({"n": out["n"], "correct": {str(j): c for j, c in out["correct"].items()},
-                          "acc": {str(j): a for j, a in out["acc"].items()}, "model": args.model, "batch": args.batch, "ranks": world}))
+                          "acc": {str(j): a for j, a in out["acc"].items()}, "model": args.model, "batch": args.batch, "ranks": world,
+                          **({"loss": out["loss"]} if args.loss else {})}))
+        if args.loss:
+            print(" * Loss {:.4e} ".format(out["loss"]) + " ".join("Prec@{} {:.3f}".format(j, a) for j, a in out["acc"].items()))
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
