@@ -1,4 +1,4 @@
-"""include/ivit.h and include/ivit_eval.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
+"""include/ivit.h, include/ivit_eval.h and include/ivit_features.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
 tools/gen_twin_header.py prints the CPU twin's prototypes from it, the tests bind the twin and walk the entry points through it.
 Standard library only, so a tool loads this file without the package (and without torch).
 
@@ -9,6 +9,7 @@ Standard library only, so a tool loads this file without the package (and withou
     ABI.constants   the enum's values and the integer #defines (IVIT_VERSION)
     EVAL_ABI        the same of include/ivit_eval.h, the second public header: ITS functions and constants (IVIT_EVAL_VERSION), with
                     the handles and structs of ivit.h, which it includes, known to it
+    FEATURES_ABI    the same of include/ivit_features.h, the third public header (IVIT_FEATURES_VERSION and the two modes)
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -28,6 +29,7 @@ import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ivit.h")
 EVAL_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_eval.h")
+FEATURES_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_features.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -167,3 +169,5 @@ with open(HEADER) as _f:
     ABI = parse(_f.read())
 with open(EVAL_HEADER) as _f:
     EVAL_ABI = parse(_f.read(), base=ABI)
+with open(FEATURES_HEADER) as _f:
+    FEATURES_ABI = parse(_f.read(), base=ABI)

@@ -1,10 +1,11 @@
-// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h) over the gfx950 kernels.
+// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
 // range predicates rq_fast / rq_fast2 / attn_fast that choose instantiations and refuse calls.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <float.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -29,6 +30,7 @@
 #include "ivit_swin12.h"
 #include "ivit_topk.h"
 #include "ivit_score.h"
+#include "ivit_features.h"
 #include "ivit_preprocess.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
@@ -1958,5 +1960,34 @@ int ivit_logits_score(ivit_handle h, const int32_t *logits, const float *scale, 
 }
 
 }  // extern "C"
+
+// the argument rules the features entries share (ivit_model.h asks here before its slices are launched: `out` is its feat32 and may be absent)
+static int features_args_ok(ivit_handle h, const char *fn, const int8_t *feat8, int dim, float scale, int mode, const float *out, bool feat32) {
+    const char *bad = nullptr;
+    if (!feat8) bad = "feat8 is null";
+    else if (mode != IVIT_FEATURES_DEQUANT && mode != IVIT_FEATURES_UNIT) bad = "mode must be IVIT_FEATURES_DEQUANT or IVIT_FEATURES_UNIT";
+    else if (out && !(scale > 0.f && scale <= FLT_MAX)) bad = "scale must be finite and positive";
+    else if (dim < 1) bad = "dim must be positive";
+    else if ((uintptr_t)feat8 & 15) bad = "feat8 must be 16-byte aligned";
+    else if ((uintptr_t)out & 15) bad = feat32 ? "feat32 must be 16-byte aligned" : "out must be 16-byte aligned";
+    if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    if ((dim % 16) != 0 || dim > FEATURES_MAX_DIM) {
+        snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 16 and at most %d", fn, FEATURES_MAX_DIM);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return IVIT_OK;
+}
+
+extern "C" int ivit_features_f32(ivit_handle h, const int8_t *feat8, int batch, int dim, float scale, int mode, float *out) {
+    CHECK_H(h);
+    REQUIRE(h, out && batch >= 0, "out is null or batch is negative");
+    if (const int rc = features_args_ok(h, __func__, feat8, dim, scale, mode, out, false)) return rc;
+    if (batch == 0) return IVIT_OK;
+    const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per row
+    if (mode == IVIT_FEATURES_UNIT) features_f32_kernel<true><<<grid, 256, 0, h->stream>>>(feat8, batch, dim, scale, out);
+    else features_f32_kernel<false><<<grid, 256, 0, h->stream>>>(feat8, batch, dim, scale, out);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
 
 #include "ivit_model.h"

@@ -92,6 +92,8 @@ int graph_capture(ivit_handle h, ivit_graph *out, Fwd &&forward) {
 
 // the slice bodies: a failing call ends the slice with its status
 #define RUN(call) do { const int rc_ = (call); if (rc_ != IVIT_OK) return rc_; } while (0)
+// REQUIRE for a check shared by several entries: the refusal names the entry the caller used
+#define REQUIRE_FN(h, fn, cond, msg) do { if (!(cond)) { snprintf((h)->err, sizeof((h)->err), "%s: %s", fn, msg); return IVIT_ERR_INVALID; } } while (0)
 // a fused entry point where it takes the case (`fused`: its status, or IVIT_ERR_UNSUPPORTED without calling it), else the launches it
 // stands for; any other status of the fused entry is the slice's
 template <class Fallback>
@@ -208,7 +210,9 @@ int vit_attention(const ivit_vit_s *m, ivit_handle h, int i, const int8_t *q, co
 // one slice on handle `h`
 // `Bmax`: images of the LARGEST slice of this forward — every slice uses that slice's buffer layout, so the regions
 // zeroed by ivit_vit_workspace_init are the ones the kernels see whatever the (ragged) slice sizes are
-int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, int Bmax, char *ws, int32_t *logits) {
+// `feat8`: the slice's rows of the caller's features [B, D] (include/ivit_features.h), where the final norm writes instead of the
+// workspace, or null; `logits`: null ends the slice in front of the head
+int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, int Bmax, char *ws, int32_t *logits, int8_t *feat8) {
     const ivit_vit_config &c = m->cfg;
     const ivit_vit_params &P = m->prm;
     const int T = m->T, D = c.embed_dim, H = c.num_heads, dh = D / H, Hd = c.hidden_dim, ld = m->ld;
@@ -216,7 +220,7 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
     const SliceLayout L = slice_layout(m, Bmax);
     int8_t *patches = (int8_t *)(ws + L.patches), *a8 = (int8_t *)(ws + L.a8), *q = (int8_t *)(ws + L.q),
            *k = (int8_t *)(ws + L.k), *vt = (int8_t *)(ws + L.vt), *ctx8 = (int8_t *)(ws + L.ctx8),
-           *h8 = (int8_t *)(ws + L.h8), *g8 = (int8_t *)(ws + L.g8), *cls8 = (int8_t *)(ws + L.cls8);
+           *h8 = (int8_t *)(ws + L.h8), *g8 = (int8_t *)(ws + L.g8), *cls8 = feat8 ? feat8 : (int8_t *)(ws + L.cls8);
     int16_t *patch16 = (int16_t *)(ws + L.patch16), *x = (int16_t *)(ws + L.xa), *y = (int16_t *)(ws + L.xb);
     // PatchEmbed + class token + position embedding: one GEMM launch that gathers its A rows from the images and finishes the rows in its
     // epilogue (round 6), or im2col -> GEMM -> embed_finish where that form does not apply
@@ -289,7 +293,7 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
     // final norm on the class-token rows only (row stride T*D; D where the last block left them compact), then the head's int32
     // accumulators
     RUN(ivit_layernorm_requant(h, x, B, D, cls_tail(m) ? (int64_t)D : (int64_t)T * D, P.s_ln, P.n_bias_int, P.n_sc, P.n_dy, cls8));
-    RUN(ivit_linear_i8(h, cls8, P.head_w, P.head_b, logits, B, c.num_classes, D));
+    if (logits) RUN(ivit_linear_i8(h, cls8, P.head_w, P.head_b, logits, B, c.num_classes, D));
     return IVIT_OK;
 }
 
@@ -443,21 +447,44 @@ int ivit_vit_workspace_init(ivit_vit m, void *workspace, size_t bytes, int batch
     return IVIT_OK;
 }
 
-int ivit_vit_forward(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                     int32_t *logits) {
-    if (!m) return IVIT_ERR_INVALID;
+// the slices of one batch: ivit_vit_forward (logits, no feat8) and ivit_vit_features (feat8, logits or none) end here
+static int vit_run(ivit_vit m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                   int8_t *feat8) {
     ivit_handle h = m->h;
     size_t need = 0;
     int rc = ivit_vit_workspace_bytes(m, batch, nslices, &need);
     if (rc != IVIT_OK) return rc;
-    REQUIRE(h, images && logits && workspace && bytes >= need, "bad arguments / workspace too small");
-    REQUIRE(h, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    REQUIRE_FN(h, fn, images && (logits || feat8) && workspace && bytes >= need, "bad arguments / workspace too small");
+    REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     const size_t stride = slice_layout(m, max_slice(batch, nslices)).total;
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
         return run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, max_slice(batch, nslices), (char *)workspace + stride * (size_t)i,
-                         logits + (size_t)b0 * m->cfg.num_classes);
+                         logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
+                         feat8 ? feat8 + (size_t)b0 * m->cfg.embed_dim : nullptr);
     });
+}
+
+int ivit_vit_forward(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                     int32_t *logits) {
+    if (!m) return IVIT_ERR_INVALID;
+    return vit_run(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr);
+}
+
+// forward_features (include/ivit_features.h): every argument checked first, then the slices with the caller's feat8 as the final
+// norm's destination (and the head only with logits), then the fp32 form on the handle's stream, behind the slices' join
+int ivit_vit_features(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                      int8_t *feat8, float scale, int mode, float *feat32) {
+    if (!m) return IVIT_ERR_INVALID;
+    RUN(features_args_ok(m->h, __func__, feat8, m->cfg.embed_dim, scale, mode, feat32, true));
+    RUN(vit_run(m, __func__, images, batch, nslices, workspace, bytes, logits, feat8));
+    return feat32 ? ivit_features_f32(m->h, feat8, batch, m->cfg.embed_dim, scale, mode, feat32) : IVIT_OK;
+}
+
+int ivit_vit_features_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                                   int32_t *logits, int8_t *feat8, float scale, int mode, float *feat32, ivit_graph *out) {
+    if (!m) return IVIT_ERR_INVALID;
+    return graph_capture(m->h, out, [&] { return ivit_vit_features(m, images, batch, nslices, workspace, bytes, logits, feat8, scale, mode, feat32); });
 }
 
 int ivit_vit_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
@@ -572,13 +599,15 @@ int swin_mlp_mode(const ivit_swin_s *m, int bi, int C, long long M) {
     return mlp_plan_fuses(m->mlp_plans[bi], m->blocks[bi].res2_main, m->blocks[bi].res2_res, M) ? 2 : 0;
 }
 
-int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, char *ws, int32_t *logits) {
+// `feat8`: the slice's rows of the caller's features [B, C] (include/ivit_features.h), where the pool writes instead of the
+// workspace, or null; `logits`: null ends the slice in front of the head
+int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, char *ws, int32_t *logits, int8_t *feat8) {
     const ivit_swin_config &c = m->cfg;
     const ivit_swin_params &P = m->prm;
     const SwinLayout Lw = swin_layout(m, B);
     int8_t *patches = (int8_t *)(ws + Lw.patches), *a8 = (int8_t *)(ws + Lw.a8), *qkv = (int8_t *)(ws + Lw.qkv),
            *ctx = (int8_t *)(ws + Lw.ctx), *h8 = (int8_t *)(ws + Lw.h8), *g8 = (int8_t *)(ws + Lw.g8),
-           *pool = (int8_t *)(ws + Lw.pool);
+           *pool = feat8 ? feat8 : (int8_t *)(ws + Lw.pool);
     int16_t *x = (int16_t *)(ws + Lw.xa), *y = (int16_t *)(ws + Lw.xb), *t16 = (int16_t *)(ws + Lw.xc);
     float *zf = (float *)(ws + Lw.zf);
     const int E = c.embed_dim;
@@ -653,7 +682,7 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
     RUN(swin_ln(m, h, x, M, C, P.s_norm_in, P.n, L, false, a8));
     RUN((L & 1) ? ivit_avgpool_requant(h, a8, B, L, C, P.dy_pool, pool)
                 : ivit_avgpool_requant_scaled(h, a8, B, L, C, P.s_pool, P.dy_pool, pool));
-    RUN(ivit_linear_i8(h, pool, P.head_w, P.head_b, logits, B, c.num_classes, C));
+    if (logits) RUN(ivit_linear_i8(h, pool, P.head_w, P.head_b, logits, B, c.num_classes, C));
     return IVIT_OK;
 }
 
@@ -787,21 +816,45 @@ int ivit_swin_fused_mlp_blocks(ivit_swin m, int batch, int blocks_per_stage[4]) 
     return IVIT_OK;
 }
 
-int ivit_swin_forward(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                      int32_t *logits) {
-    if (!m) return IVIT_ERR_INVALID;
+static inline int swin_num_features(const ivit_swin_s *m) { return m->cfg.embed_dim << (m->cfg.num_layers - 1); }
+
+// the slices of one batch: ivit_swin_forward (logits, no feat8) and ivit_swin_features (feat8, logits or none) end here
+static int swin_run(ivit_swin m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                    int8_t *feat8) {
     ivit_handle h = m->h;
     size_t need = 0;
     int rc = ivit_swin_workspace_bytes(m, batch, nslices, &need);
     if (rc != IVIT_OK) return rc;
-    REQUIRE(h, images && logits && workspace && bytes >= need, "bad arguments / workspace too small");
-    REQUIRE(h, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    REQUIRE_FN(h, fn, images && (logits || feat8) && workspace && bytes >= need, "bad arguments / workspace too small");
+    REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     const size_t stride = swin_layout(m, max_slice(batch, nslices)).total;
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
         return swin_run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, (char *)workspace + stride * (size_t)i,
-                              logits + (size_t)b0 * m->cfg.num_classes);
+                              logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
+                              feat8 ? feat8 + (size_t)b0 * swin_num_features(m) : nullptr);
     });
+}
+
+int ivit_swin_forward(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                      int32_t *logits) {
+    if (!m) return IVIT_ERR_INVALID;
+    return swin_run(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr);
+}
+
+// forward_features (include/ivit_features.h): as ivit_vit_features, with the pool's output in the caller's feat8
+int ivit_swin_features(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                       int8_t *feat8, float scale, int mode, float *feat32) {
+    if (!m) return IVIT_ERR_INVALID;
+    RUN(features_args_ok(m->h, __func__, feat8, swin_num_features(m), scale, mode, feat32, true));
+    RUN(swin_run(m, __func__, images, batch, nslices, workspace, bytes, logits, feat8));
+    return feat32 ? ivit_features_f32(m->h, feat8, batch, swin_num_features(m), scale, mode, feat32) : IVIT_OK;
+}
+
+int ivit_swin_features_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
+                                    int32_t *logits, int8_t *feat8, float scale, int mode, float *feat32, ivit_graph *out) {
+    if (!m) return IVIT_ERR_INVALID;
+    return graph_capture(m->h, out, [&] { return ivit_swin_features(m, images, batch, nslices, workspace, bytes, logits, feat8, scale, mode, feat32); });
 }
 
 int ivit_swin_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
@@ -843,3 +896,4 @@ int ivit_swin_score_graph_create(ivit_swin m, const int8_t *images, int batch, i
 }  // extern "C"
 
 #undef RUN
+#undef REQUIRE_FN

@@ -7,9 +7,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .engine import ViTEngine, pack_constants
-from .freeze import freeze_swin, freeze_vit
-from .swin_engine import SwinEngine, pack_swin_constants
+from .engine import ViTEngine, frozen_vit, pack_constants
+from .freeze import freeze_swin, freeze_vit  # noqa: F401  (names this module has always had)
+from .swin_engine import SwinEngine, pack_swin_constants, packed_swin  # noqa: F401
 
 
 def broadcast_packed(packed, rank, world, device):
@@ -48,13 +48,13 @@ def shard_range(total, rank, world):
 def build_engine_broadcast(cfg, weights, scales, device, rank, world):
     consts = f32 = None
     if rank == 0:
-        consts, f32 = freeze_vit(cfg, weights, scales)
+        consts, f32 = frozen_vit(cfg, weights, scales)
     blob, table, f32 = broadcast_constants(consts, f32, rank, world, device)
     return ViTEngine(cfg, None, f32, device=device, blob=blob, table=table)
 
 
 def build_swin_engine_broadcast(cfg, weights, scales, device, rank, world):
-    packed = pack_swin_constants(freeze_swin(cfg, weights, scales)) if rank == 0 else None
+    packed = packed_swin(cfg, weights, scales) if rank == 0 else None
     return SwinEngine(cfg, None, None, device=device, packed=broadcast_packed(packed, rank, world, device))
 
 

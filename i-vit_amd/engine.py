@@ -91,6 +91,13 @@ def vit_native_params(cfg, table, f32, host, base):
     return c, prm, blocks
 
 
+def frozen_vit(cfg, weights, scales):
+    """freeze_vit, and beside its scalars the one scale a caller of the engine needs that no constant holds: "feat.s", the scale of
+    forward_features' output (qact2, vit_quant.py:273).  What the engine is built from, here and behind a broadcast"""
+    consts, f32 = freeze_vit(cfg, weights, scales)
+    return consts, dict(f32, **{"feat.s": np.float32(scales["qact2"])})
+
+
 class ViTEngine(NativeEngine):
     PREFIX = "ivit_vit"
 
@@ -191,11 +198,20 @@ class ViTEngine(NativeEngine):
 
     @classmethod
     def from_float(cls, cfg, weights, scales, device="cuda:0"):
-        consts, f32 = freeze_vit(cfg, weights, scales)
+        consts, f32 = frozen_vit(cfg, weights, scales)
         return cls(cfg, consts, f32, device)
 
     def head_scale(self):
         return self.head_scale_host()
+
+    @property
+    def num_features(self):
+        return self.cfg.embed_dim
+
+    def feature_scale_host(self):
+        if "feat.s" not in self.f32:
+            raise _lib.IvitError("this engine was built without the features' scale: build it with ViTEngine.from_float or frozen_vit")
+        return self.f32["feat.s"]
 
     def workspace(self, B, key=None):
         wkey = (B, key)

@@ -1,10 +1,12 @@
 """NativeEngine — what ViTEngine and SwinEngine share: one frozen model behind the C runners of csrc/ivit_model.h.
 
-The base owns the device and handle, the constants blob, the workspace cache and the four ways into a runner:
+The base owns the device and handle, the constants blob, the workspace cache and the ways into a runner:
 `forward` / `capture` (ivit_<model>_forward, one C call per batch, or its hipGraph), `predict` / `capture_predict` (the same
-with the top-k of the dequantised logits behind them, ivit_<model>_predict) and `score` / `capture_score` (with the labels' rank and
-negative log-likelihood behind them instead, ivit_<model>_score of include/ivit_eval.h).  A subclass names its C prefix, builds its
-parameter structs (`_native_params`) and keeps its `forward_ops`.  torch is used for device memory and streams only.
+with the top-k of the dequantised logits behind them, ivit_<model>_predict), `score` / `capture_score` (with the labels' rank and
+negative log-likelihood behind them instead, ivit_<model>_score of include/ivit_eval.h) and `features` / `capture_features` (the
+reference's forward_features: the integers the head reads and their fp32 form, with or without the head, ivit_<model>_features of
+include/ivit_features.h).  A subclass names its C prefix, builds its parameter structs (`_native_params`), says where its feature
+scale lies (`feature_scale_host`, `num_features`) and keeps its `forward_ops`.  torch is used for device memory and streams only.
 """
 import ctypes
 
@@ -48,7 +50,7 @@ class ShapeCache:
 
 class NativeEngine:
     # "ivit_vit" / "ivit_swin": the entries are PREFIX + _create, _destroy, _workspace_bytes, _forward, _graph_create, _predict,
-    # _predict_graph_create, _score and _score_graph_create
+    # _predict_graph_create, _score, _score_graph_create, _features and _features_graph_create
     PREFIX = None
     MAX_SLICES = 8
 
@@ -66,6 +68,7 @@ class NativeEngine:
         self._graphs = []
         self._predict_out = {}
         self._score_out = {}
+        self._features_out = {}
         self._gstream = None                    # the stream graphs are captured and replayed on, made by the first capture
         self._head_scale_host = None
         self.last_logits = None
@@ -161,6 +164,34 @@ class NativeEngine:
         rank, nll = self._score_buffers(logits, key)
         return args + (self.ptr("head.scale"), _ptr(labels), _ptr(rank), _ptr(nll)), key, (ws, logits, rank, nll)
 
+    @property
+    def num_features(self):
+        """width of a features row: embed_dim of a ViT, embed_dim << (num_layers - 1) of a Swin"""
+        raise NotImplementedError
+
+    def feature_scale_host(self):
+        """host float: the scale of the features' integers (the reference's qact2 of a ViT, qact3 of a Swin)"""
+        raise NotImplementedError
+
+    def _features_buffers(self, logits, key):
+        """(feat8, feat32) of one (batch, slices): the rule of _predict_buffers"""
+        outs = self._features_out
+        hit = outs.get(key)
+        if hit is None or hit[0] is not logits:
+            for old in [q for q, v in outs.items() if not v[3] and q not in self._native_ws]:
+                del outs[old]
+            hit = outs[key] = [logits, torch.empty(key[0], self.num_features, dtype=torch.int8, device=self.device),
+                               torch.empty(key[0], self.num_features, dtype=torch.float32, device=self.device), False]
+        return hit[1], hit[2]
+
+    def _features_args(self, images, normalize, logits, nslices):
+        """(arguments of the features entries, cache key, buffers) for one batch; without `logits` the head's pointer is NULL"""
+        args, key, (ws, lg) = self._args(images, nslices)
+        feat8, feat32 = self._features_buffers(lg, key)
+        mode = _lib.IVIT_FEATURES_UNIT if normalize else _lib.IVIT_FEATURES_DEQUANT
+        return (args[:-1] + (_ptr(lg) if logits else None, _ptr(feat8), float(self.feature_scale_host()), mode, _ptr(feat32)), key,
+                (ws, lg, feat8, feat32))
+
     def _check_images(self, images):
         assert images.dtype == torch.int8 and images.is_contiguous() and images.device == self.device
 
@@ -219,6 +250,24 @@ class NativeEngine:
         self.last_logits = logits
         return (rank.clone(), nll.clone()) if copy else (rank, nll)
 
+    def features(self, images, normalize=False, logits=False, nslices=1, copy=False):
+        """images int8 [B, C, H, W] -> (feat8 int8 [B, num_features], feat32 float32 [B, num_features]) device tensors, or
+        (feat8, feat32, logits) with logits=True: the reference's forward_features.  feat8 holds the integers the head reads (the
+        class-token row after norm -> qact2 of a ViT, the pooled row after qact3 of a Swin; their scale is `feature_scale_host()`),
+        feat32 their fp32 form as `predict.features_reference` states it: feat8 * scale, the reference's fp32 tensor — or with
+        normalize=True the rows at unit Euclidean length.  One native call; without `logits` the head GEMM is not launched, with
+        it the int32 logits are forward's (and `last_logits`).  The results are the engine's own buffers for this (batch,
+        nslices): copy=True (or clone) to keep them across calls."""
+        self._use_current_stream()
+        self._check_images(images)
+        args, _, (_, lg, feat8, feat32) = self._features_args(images, normalize, logits, nslices)
+        self._entry("_features", *args)
+        out = (feat8, feat32)
+        if logits:
+            self.last_logits = lg
+            out += (lg,)
+        return tuple(t.clone() for t in out) if copy else out
+
     def _capture(self, suffix, images, args, key, bufs, out):
         """hipGraph of the entry PREFIX + suffix on fixed buffers; returns a callable that replays it and returns `out`"""
         if self._gstream is None:
@@ -263,4 +312,12 @@ class NativeEngine:
         args, key, bufs = self._score_args(images, labels, nstreams)
         replay = self._capture("_score_graph_create", images, args, key, bufs + (labels,), bufs[2:4])
         self._score_out[key][3] = True
+        return replay
+
+    def capture_features(self, images, normalize=False, logits=False, nstreams=1):
+        """hipGraph of one features on fixed buffers; returns a callable that replays it and returns what `features` returns."""
+        self._check_images(images)
+        args, key, bufs = self._features_args(images, normalize, logits, nstreams)
+        replay = self._capture("_features_graph_create", images, args, key, bufs, bufs[2:4] + ((bufs[1],) if logits else ()))
+        self._features_out[key][3] = True
         return replay

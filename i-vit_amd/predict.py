@@ -10,7 +10,10 @@ vit_quant.py:278-282 / swin_quant.py:560-564), takes the cross-entropy and top-1
     ivit_*_score and their *_graph_create forms, the forward and the launch behind it as one C call, or one hipGraph) follow them;
   * `evaluate` is validate() minus the data loader: hit counts — and with loss=True the sum of the losses — accumulate on the
     device, with device labels nothing inside the loop synchronises, and a multi-rank run ends with ONE all_reduce (DESIGN.md §6:
-    no collective per step).
+    no collective per step);
+  * `features_reference` is the numpy statement of the contract of `ivit_features_f32` (include/ivit_features.h): the fp32 form of
+    the int8 features the reference's forward_features returns (vit_quant.py:254-276, swin_quant.py:540-556), and `embed` is
+    evaluate's loop for them (the engines' `features`).
 """
 import numpy as np
 import torch
@@ -61,6 +64,45 @@ def score_reference(acc, scale, labels):
     m = d.max(axis=1, keepdims=True)
     nll = np.log(np.exp(d - m).sum(axis=1)) - (d[rows, lc] - m[:, 0])
     return (np.where(valid, before, np.iinfo(np.int32).max).astype(np.int32), np.where(valid, nll, np.nan).astype(np.float64))
+
+
+def features_reference(feat8, scale, mode=0):
+    """feat8 int8 [B, dim], scale a float32 value -> float32 [B, dim], every bit.
+
+    mode 0 (IVIT_FEATURES_DEQUANT): fl32(fl32(q) * scale), one conversion and one float32 multiply: the fp32 tensor QuantAct
+    returns in the reference (quant_modules.py:197-206).  mode 1 (IVIT_FEATURES_UNIT): rows of unit Euclidean length; the scale
+    cancels and is not read: ss = sum of q^2 as an exact integer, fl32(float64(q) / sqrt(float64(ss))) with the correctly rounded
+    float64 root and division numpy has; a row of zeros gives zeros.  The scale must be finite and positive in both modes."""
+    q = np.asarray(feat8)
+    scale = np.float32(scale)
+    assert q.ndim == 2 and q.dtype == np.int8
+    if mode not in (0, 1):
+        raise ValueError(f"mode = {mode}: 0 (dequantised) or 1 (unit length)")
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"scale = {scale}: finite and positive")
+    if mode == 0:
+        return q.astype(np.float32) * scale
+    ss = (q.astype(np.int64) ** 2).sum(axis=1)
+    root = np.sqrt(np.where(ss > 0, ss, 1).astype(np.float64))        # a row of zeros: 0 / 1
+    return (q.astype(np.float64) / root[:, None]).astype(np.float32)
+
+
+def embed(engine, batches, transform=None, normalize=True):
+    """evaluate's loop for features: `batches` yields images, or (images, anything) pairs as evaluate takes them; `transform`
+    turns what it yields into the engine's int8 input.  Every batch is one engine.features(images, normalize=normalize) — no
+    head GEMM — and its fp32 rows are kept (a copy: the engine reuses its buffers), in order.  Nothing inside the loop
+    synchronises.  Returns ONE float32 tensor [N, num_features] on the engine's device ([0, num_features] without batches):
+    unit-length rows by default (dot products are cosines), feat8 * scale with normalize=False."""
+    rows = []
+    for images in batches:
+        if isinstance(images, (tuple, list)):
+            images = images[0]
+        if transform is not None:
+            images = transform(images)
+        rows.append(torch.as_tensor(engine.features(images, normalize=normalize)[1]).clone())
+    if not rows:
+        return torch.zeros(0, int(engine.num_features), dtype=torch.float32, device=getattr(engine, "device", "cpu"))
+    return torch.cat(rows)
 
 
 def evaluate(engine, batches, topk=(1, 5), transform=None, rank=0, world=1, loss=False):

@@ -47,6 +47,15 @@ def pack_swin_constants(consts):
     return blob, table, host
 
 
+def packed_swin(cfg, weights, scales, exp_tables=False):
+    """pack_swin_constants(freeze_swin(...)), and in its host part the one scale a caller of the engine needs that no constant
+    holds: "feat.s", the scale of forward_features' output (qact3, swin_quant.py:555).  What the engine is built from, here and
+    behind a broadcast"""
+    blob, table, host = pack_swin_constants(freeze_swin(cfg, weights, scales, exp_tables))
+    host["feat.s"] = ("f", float(np.float32(scales["qact3"])))
+    return blob, table, host
+
+
 def swin_host_scalars(host):
     """(fp32 scalars, by-value dyadics) from the host part of pack_swin_constants"""
     return ({k: v[1] for k, v in host.items() if v[0] == "f"},
@@ -120,7 +129,7 @@ class SwinEngine(NativeEngine):
         exp_tables: see freeze_swin."""
         super().__init__(cfg, device)
         check_swin_windows(cfg)
-        blob, table, host = packed if packed is not None else pack_swin_constants(freeze_swin(cfg, weights, scales, exp_tables))
+        blob, table, host = packed if packed is not None else packed_swin(cfg, weights, scales, exp_tables)
         self.host_consts = host
         self._load(blob, table)
         self.head_scale = self.head_scale_host()
@@ -140,6 +149,15 @@ class SwinEngine(NativeEngine):
 
     def _native_params(self):
         return swin_native_params(self.cfg, self.table, self.f, self.dy, self.blob.data_ptr())
+
+    @property
+    def num_features(self):
+        return self.cfg.num_features
+
+    def feature_scale_host(self):
+        if "feat.s" not in self.f:
+            raise _lib.IvitError("this engine was built without the features' scale: build it from weights and scales, or from packed_swin")
+        return self.f["feat.s"]
 
     def workspace(self, B, key=None):
         if (B, key) in self._ws:

@@ -56,35 +56,23 @@ def build_engine(args, device):
     return cfg, ViTEngine.from_float(cfg, weights, scales, device=device), np.float32(scales["qact_input"])
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+def add_input_arguments(ap):
+    """the data file, the model and its source, the batch and the resize: what tools/embed.py takes too"""
     ap.add_argument("data")
     ap.add_argument("--model", required=True)
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--golden")
     src.add_argument("--state-dict")
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--topk", type=int, nargs="+", default=[1, 5])
     ap.add_argument("--resize", type=int, default=0, help="shorter side before the centre crop (default: int(crop / 0.875))")
     ap.add_argument("--resample", choices=("torch", "pil"), default="torch",
                     help="uint8 [N, H, W, 3] images: the torch-pinned resize (default) or the PIL-exact one; ragged files are always pil")
-    ap.add_argument("--loss", action="store_true", help="also the mean cross-entropy of the labels (validate()'s Loss), computed on the device")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/evaluate.py needs a HIP device; the product path has no CPU fallback")
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    local = int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count()
-    torch.cuda.set_device(local)
-    device = f"cuda:{local}"
-    if world > 1:
-        import torch.distributed as dist
-        dist.init_process_group(os.environ.get("IVIT_DIST_BACKEND", "nccl"), rank=rank, world_size=world)
-    cfg, eng, s_in = build_engine(args, device)
-    d = np.load(args.data)
-    labels = d["labels"].astype(np.int64).reshape(-1)
+
+
+def load_share(d, labels, cfg, s_in, args, device, lo, hi):
+    """images lo .. hi of the opened data file `d` in any of its three forms, uploaded once -> (what batches are sliced from,
+    the transform that turns a slice into the engine's int8 input, or None)"""
     size = args.resize or int(cfg.img_size / 0.875)
-    lo, hi = ivdist.shard_range(len(labels), rank, world)
-    share = torch.from_numpy(labels[lo:hi]).to(device)                           # once: no copy inside evaluate's loop
     transform = None
     if "pixels" in d.files or (args.resample == "pil" and d["images"].dtype == np.uint8):
         from ivit_amd.preprocess import DESC_DTYPE, RaggedImages, eval_transform_pil
@@ -120,6 +108,30 @@ def main():
             raise SystemExit(f"images must be uint8 [N, H, W, 3] or int8 [N, {cfg.in_chans}, {cfg.img_size}, {cfg.img_size}]; "
                              f"got {images.dtype} {images.shape}")
         mine = torch.from_numpy(np.ascontiguousarray(images[lo:hi])).to(device)      # this rank's share only
+    return mine, transform
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    add_input_arguments(ap)
+    ap.add_argument("--topk", type=int, nargs="+", default=[1, 5])
+    ap.add_argument("--loss", action="store_true", help="also the mean cross-entropy of the labels (validate()'s Loss), computed on the device")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/evaluate.py needs a HIP device; the product path has no CPU fallback")
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count()
+    torch.cuda.set_device(local)
+    device = f"cuda:{local}"
+    if world > 1:
+        import torch.distributed as dist
+        dist.init_process_group(os.environ.get("IVIT_DIST_BACKEND", "nccl"), rank=rank, world_size=world)
+    cfg, eng, s_in = build_engine(args, device)
+    d = np.load(args.data)
+    labels = d["labels"].astype(np.int64).reshape(-1)
+    lo, hi = ivdist.shard_range(len(labels), rank, world)
+    share = torch.from_numpy(labels[lo:hi]).to(device)                           # once: no copy inside evaluate's loop
+    mine, transform = load_share(d, labels, cfg, s_in, args, device, lo, hi)
     batches = ((mine[a:a + args.batch], share[a:a + args.batch]) for a in range(0, hi - lo, args.batch))
     out = evaluate(eng, batches, topk=args.topk, transform=transform, rank=rank, world=world, loss=args.loss)     # ends with the one all_reduce
     if rank == 0:
