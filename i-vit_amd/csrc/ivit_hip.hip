@@ -68,6 +68,48 @@ struct ivit_device_guard {
 // refused unless aligned to that width, before anything is launched.  `name` is the argument as the header spells it.
 #define REQUIRE_ALIGNED(h, p, name, bytes) REQUIRE(h, ((uintptr_t)(p) & ((bytes) - 1)) == 0, name " must be " #bytes "-byte aligned")
 #define REQUIRE_A16(h, p, name) REQUIRE_ALIGNED(h, p, name, 16)
+// Overlapping arguments (include/ivit.h, Conventions): an array an entry writes may overlap neither an activation array it reads nor
+// another array it writes; judged on the byte extents [p, p + bytes) the header documents, refused before anything is launched.  Host
+// pointer comparisons only.  ranges_disjoint takes the two ranges, the two argument names as the header spells them and the message
+// (what the arrays are to the entry); a null pointer or an empty range overlaps nothing.
+static inline bool ranges_disjoint(ivit_ctx *h, const char *fn, const void *a, size_t a_bytes, const char *a_name, const void *b, size_t b_bytes,
+                                   const char *b_name, const char *msg) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    if (!a || !b || !a_bytes || !b_bytes || a0 + a_bytes <= b0 || b0 + b_bytes <= a0) return true;
+    snprintf(h->err, sizeof(h->err), "%s: %s and %s overlap: %s", fn, a_name, b_name, msg);
+    return false;
+}
+#define REQUIRE_DISJOINT(h, a, a_bytes, a_name, b, b_bytes, b_name, msg) \
+    do { if (!ranges_disjoint(h, __func__, a, (size_t)(a_bytes), a_name, b, (size_t)(b_bytes), b_name, msg)) return IVIT_ERR_INVALID; } while (0)
+// an in-place pair (the entry's "Overlap:" line names it): the same pointer with the same extent is accepted, every other overlap refused
+#define REQUIRE_DISJOINT_OR_SAME(h, a, a_bytes, a_name, b, b_bytes, b_name, msg) \
+    do { if (!((const void *)(a) == (const void *)(b) && (size_t)(a_bytes) == (size_t)(b_bytes)) && \
+             !ranges_disjoint(h, __func__, a, (size_t)(a_bytes), a_name, b, (size_t)(b_bytes), b_name, msg)) return IVIT_ERR_INVALID; } while (0)
+// bytes spanned by `rows` rows of `payload` elements at a pitch of `pitch` elements, `elem` bytes each: (rows - 1) * pitch + payload
+static inline size_t span_bytes(long long rows, long long pitch, long long payload, size_t elem) {
+    return rows > 0 ? (size_t)((rows - 1) * pitch + payload) * elem : 0;
+}
+#define OVL_IN "an output may not overlap an activation input"
+#define OVL_OUT "two arrays the entry writes may not overlap"
+// the qkv scatter's arrays (ivit_linear_i8_qkv and its planned / LayerNorm-headed forms): the input against q, k and v, and the three
+// among themselves; q and k are [B*H, T, dh], v the same at ldv == 0 and B*H*dh rows of T at a pitch of ldv otherwise.  `fn`: the entry
+static int qkv_disjoint(ivit_ctx *h, const char *fn, const void *x, size_t x_bytes, const char *x_name, const int8_t *q, const int8_t *k,
+                        const int8_t *vt, int B, int T, int H, int dh, int ldv) {
+    const size_t nqk = (size_t)B * H * T * dh, nv = ldv == 0 ? nqk : span_bytes((long long)B * H * dh, ldv, T, 1);
+    const bool ok = ranges_disjoint(h, fn, x, x_bytes, x_name, q, nqk, "q", OVL_IN) && ranges_disjoint(h, fn, x, x_bytes, x_name, k, nqk, "k", OVL_IN) &&
+                    ranges_disjoint(h, fn, x, x_bytes, x_name, vt, nv, "vt", OVL_IN) && ranges_disjoint(h, fn, q, nqk, "q", k, nqk, "k", OVL_OUT) &&
+                    ranges_disjoint(h, fn, q, nqk, "q", vt, nv, "vt", OVL_OUT) && ranges_disjoint(h, fn, k, nqk, "k", vt, nv, "vt", OVL_OUT);
+    return ok ? IVIT_OK : IVIT_ERR_INVALID;
+}
+// the batched NT products: batch b of an operand spans (rows - 1) * ld + payload elements from b * stride (strides in elements, A's
+// elements a_elem bytes wide, C's four); a negative stride is outside what the extents describe and is not judged
+static int bmm_disjoint(ivit_ctx *h, const char *fn, const void *A, size_t a_elem, const int8_t *B, const int32_t *C, int nb, int M, int N, int K,
+                        int lda, int ldb, int ldc, long long strideA, long long strideB, long long strideC) {
+    if (strideA < 0 || strideB < 0 || strideC < 0 || lda < 0 || ldb < 0 || ldc < 0) return IVIT_OK;
+    const size_t nA = ((size_t)(nb - 1) * strideA + span_bytes(M, lda, K, 1)) * a_elem, nB = (size_t)(nb - 1) * strideB + span_bytes(N, ldb, K, 1);
+    const size_t nC = ((size_t)(nb - 1) * strideC + span_bytes(M, ldc, N, 1)) * 4;
+    return ranges_disjoint(h, fn, A, nA, "A", C, nC, "C", OVL_IN) && ranges_disjoint(h, fn, B, nB, "B", C, nC, "C", OVL_IN) ? IVIT_OK : IVIT_ERR_INVALID;
+}
 #define LAUNCH_CHECK(h) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { snprintf((h)->err, sizeof((h)->err), "%s: %s", __func__, hipGetErrorString(e_)); return IVIT_ERR_HIP; } } while (0)
 
 // Launch `Kernel` with `lds` bytes of dynamic LDS.  Above 64 KB a launch needs hipFuncAttributeMaxDynamicSharedMemorySize: set once
@@ -177,6 +219,7 @@ int ivit_quantize_input_f32(ivit_handle h, const float *x, float scale, int8_t *
     REQUIRE(h, x && q && n >= 0 && scale > 0.f, "bad arguments");
     REQUIRE_A16(h, x, "x");                 // four floats per load, four packed bytes per store
     REQUIRE_ALIGNED(h, q, "q", 4);
+    REQUIRE_DISJOINT(h, x, (size_t)n * 4, "x", q, (size_t)n, "q", OVL_IN);
     if (n == 0) return IVIT_OK;
     quantize_input_kernel<<<grid_for(h, n, 1024), 256, 0, h->stream>>>(x, scale, q, n);
     LAUNCH_CHECK(h);
@@ -193,6 +236,12 @@ int ivit_resize_center_crop_u8(ivit_handle h, const uint8_t *hwc, int B, int H0,
     if (H0 <= W0) { Hr = size; Wr = (int)((long long)size * W0 / H0); }
     else { Wr = size; Hr = (int)((long long)size * H0 / W0); }
     REQUIRE(h, crop <= Hr && crop <= Wr, "crop larger than the resized image");
+    {
+        const size_t nin = (size_t)B * H0 * W0 * 3, nws = (size_t)B * H0 * crop * 3 * sizeof(float), nout = (size_t)B * crop * crop * 3;
+        REQUIRE_DISJOINT(h, hwc, nin, "hwc", workspace, nws, "workspace", OVL_IN);
+        REQUIRE_DISJOINT(h, hwc, nin, "hwc", out_hwc, nout, "out_hwc", OVL_IN);
+        REQUIRE_DISJOINT(h, workspace, nws, "workspace", out_hwc, nout, "out_hwc", OVL_OUT);
+    }
     const int top = (int)__builtin_rint((Hr - crop) / 2.0), left = (int)__builtin_rint((Wr - crop) / 2.0);
     resize_h_kernel<<<grid_for(h, (long long)B * H0 * crop, 256), 256, 0, h->stream>>>(hwc, B, H0, W0, Wr, left, crop, workspace);
     resize_v_kernel<<<grid_for(h, (long long)B * crop * crop, 256), 256, 0, h->stream>>>(workspace, B, H0, Hr, top, crop, out_hwc);
@@ -205,6 +254,7 @@ int ivit_normalize_quantize_u8(ivit_handle h, const uint8_t *hwc, int B, int H, 
     CHECK_H(h);
     REQUIRE(h, hwc && nchw && mean && std_ && B > 0 && H > 0 && W > 0 && scale > 0.f, "bad arguments");
     REQUIRE(h, std_[0] != 0.f && std_[1] != 0.f && std_[2] != 0.f, "zero std");
+    REQUIRE_DISJOINT(h, hwc, (size_t)B * H * W * 3, "hwc", nchw, (size_t)B * H * W * 3, "nchw", OVL_IN);
     normalize_quantize_u8_kernel<<<grid_for(h, (long long)B * H * W, 256), 256, 0, h->stream>>>(
         hwc, B, H, W, mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], scale, nchw);
     LAUNCH_CHECK(h);
@@ -232,6 +282,13 @@ static int launch_pil_eval(ivit_handle h, const char *fn, const uint8_t *pixels,
     }
     const int nbands = (crop + PIL_BAND - 1) / PIL_BAND;
     if ((long long)nbands * B > 0x7fffffffLL) return fail("B * ceil(crop / 32) exceeds the grid", -1);
+    {   // the output against the whole pixel blob [pixels, pixels + pixels_bytes) and the device descriptor table
+        const size_t nout = (size_t)B * crop * crop * 3;
+        const char *oname = NCHW ? "nchw" : "out_hwc";
+        if (!ranges_disjoint(h, fn, pixels, pixels_bytes, "pixels", out, nout, oname, OVL_IN) ||
+            !ranges_disjoint(h, fn, desc_dev, (size_t)B * sizeof(ivit_image_desc), "desc_dev", out, nout, oname, OVL_IN))
+            return IVIT_ERR_INVALID;
+    }
     for (int i = 0; i < B; ++i) {
         const ivit_image_desc &d = desc_host[i];
         if (d.h <= 0 || d.w <= 0) return fail("non-positive side", i);
@@ -350,6 +407,7 @@ int ivit_linear_i8(ivit_handle h, const int8_t *x, const int8_t *w, const int32_
     REQUIRE(h, x && w && acc && M > 0 && N > 0 && K > 0, "bad arguments");
     REQUIRE(h, (K % 16) == 0, "K must be a multiple of 16");
     REQUIRE_A16(h, x, "x");                 // acc: 32-bit scalar stores (gemm_nt_kernel, EPI_RAW32)
+    REQUIRE_DISJOINT(h, x, (size_t)M * K, "x", acc, (size_t)M * N * 4, "acc", OVL_IN);
     GemmArgs a = linear_args(x, w, bias, M, N, K);
     a.out = acc;
     return launch_gemm<false, EPI_RAW32>(h, a, 1);
@@ -363,6 +421,7 @@ int ivit_linear_i8_requant(ivit_handle h, const int8_t *x, const int8_t *w, cons
     REQUIRE(h, bits == 8 || bits == 16, "bits must be 8 or 16");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, out, "out");
+    REQUIRE_DISJOINT(h, x, (size_t)M * K, "x", out, (size_t)M * N * (bits / 8), "out", OVL_IN);
     GemmArgs a = linear_args(x, w, bias, M, N, K);
     a.out = out; a.dy_ch = dy_ch;
     if (const int nct = wreg_nct(a)) return bits == 8 ? launch_wreg<EPI_RQ8_CH>(h, a, nct) : launch_wreg<EPI_RQ16_CH>(h, a, nct);
@@ -379,6 +438,7 @@ int ivit_linear_i8_requant8_store16(ivit_handle h, const int8_t *x, const int8_t
     REQUIRE(h, (K % 16) == 0, "K must be a multiple of 16");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, out, "out16");
+    REQUIRE_DISJOINT(h, x, (size_t)M * K, "x", out, (size_t)M * N * 2, "out16", OVL_IN);
     GemmArgs a = linear_args(x, w, bias, M, N, K);
     a.out = out; a.dy_ch = dy_ch;
     if (wreg_nct(a) || !use_gemm2(a)) {
@@ -397,6 +457,12 @@ int ivit_linear_i8_requant_residual(ivit_handle h, const int8_t *x, const int8_t
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, residual, "residual");
     REQUIRE_A16(h, out, "out");
+    REQUIRE_DISJOINT(h, x, (size_t)M * K, "x", out, (size_t)M * N * 2, "out", OVL_IN);
+    // residual == out is the in-place form x = x + f(x).  In gemm_nt_kernel and gemm_glds_kernel a lane loads the eight identity values
+    // of (grow, gcol) under the same grow < M, gcol < N test as its store of those eight elements, load first; gemm_wreg_kernel's lane
+    // loads the identity of its own row and channels ahead of the MFMAs and stores the same elements behind them, and a lane past M
+    // loads row M - 1 but stores nothing (every store is under `live`).  No lane loads an element that another lane stores.
+    REQUIRE_DISJOINT_OR_SAME(h, residual, (size_t)M * N * 2, "residual", out, (size_t)M * N * 2, "out", OVL_IN);
     GemmArgs a = linear_args(x, w, bias, M, N, K);
     a.out = out; a.dy_ch = dy_ch; a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual;
     if (const int nct = wreg_nct(a)) return launch_wreg<EPI_RQ16_CH_RES>(h, a, nct);
@@ -416,6 +482,7 @@ int ivit_linear_i8_qkv(ivit_handle h, const int8_t *x, const int8_t *w, const in
     REQUIRE_A16(h, vt, "vt");
     REQUIRE(h, ldv == 0 || ldv >= T, "ldv < T (0 = v row-major [B*H, T, dh])");
     const int D = H * dh;
+    if (int st = qkv_disjoint(h, __func__, x, (size_t)B * T * D, "x", q, k, vt, B, T, H, dh, ldv)) return st;
     GemmArgs a = linear_args(x, w, bias, B * T, 3 * D, D);
     a.dy_ch = dy_ch; a.q = q; a.k = k; a.vt = vt;
     a.T = T; a.H = H; a.dh = dh; a.ldv = ldv; a.D = D;
@@ -432,6 +499,7 @@ int ivit_bmm_nt_i8(ivit_handle h, const int8_t *A, const int8_t *B, int32_t *C, 
             "lda/ldb/strides must be multiples of 16");
     REQUIRE_A16(h, A, "A");                 // C: 32-bit scalar stores (gemm_nt_kernel, EPI_RAW32)
     REQUIRE_A16(h, B, "B");
+    if (int st = bmm_disjoint(h, __func__, A, 1, B, C, nb, M, N, K, lda, ldb, ldc, strideA, strideB, strideC)) return st;
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
@@ -447,6 +515,7 @@ int ivit_bmm_nt_u16i8(ivit_handle h, const uint16_t *A, const int8_t *B, int32_t
             "lda must be a multiple of 8, ldb of 16");
     REQUIRE_A16(h, A, "A");
     REQUIRE_A16(h, B, "B");
+    if (int st = bmm_disjoint(h, __func__, A, 2, B, C, nb, M, N, K, lda, ldb, ldc, strideA, strideB, strideC)) return st;
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
@@ -462,6 +531,8 @@ int ivit_attn_qk_requant(ivit_handle h, const int8_t *q, const int8_t *k, ivit_d
     REQUIRE_A16(h, q, "q");
     REQUIRE_A16(h, k, "k");
     REQUIRE_A16(h, scores8, "scores8");
+    REQUIRE_DISJOINT(h, q, (size_t)BH * T * dh, "q", scores8, span_bytes((long long)BH * T, lds, T, 1), "scores8", OVL_IN);
+    REQUIRE_DISJOINT(h, k, (size_t)BH * T * dh, "k", scores8, span_bytes((long long)BH * T, lds, T, 1), "scores8", OVL_IN);
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = q; a.B = k; a.M = T; a.N = T; a.K = dh; a.lda = dh; a.ldb = dh; a.ldc = lds;
@@ -478,6 +549,8 @@ int ivit_attn_pv_requant(ivit_handle h, const uint16_t *p, const int8_t *vt, ivi
     REQUIRE_A16(h, p, "p");
     REQUIRE_A16(h, vt, "vt");
     REQUIRE_A16(h, ctx8, "ctx8");
+    REQUIRE_DISJOINT(h, p, span_bytes((long long)B * H * T, ldp, T, 2), "p", ctx8, (size_t)B * T * H * dh, "ctx8", OVL_IN);
+    REQUIRE_DISJOINT(h, vt, span_bytes((long long)B * H * dh, ldv, T, 1), "vt", ctx8, (size_t)B * T * H * dh, "ctx8", OVL_IN);
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = p; a.B = vt; a.M = T; a.N = dh; a.K = T; a.lda = ldp; a.ldb = ldv; a.ldc = H * dh;
@@ -791,6 +864,7 @@ int ivit_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan pl, const int
     REQUIRE(h, bits == 8 || bits == 16, "bits must be 8 or 16");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, out, "out");
+    REQUIRE_DISJOINT(h, x, (size_t)M * pl->K, "x", out, (size_t)M * pl->N * (bits / 8), "out", OVL_IN);
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy;
     if (bits == 8 && ws_plan_ok(pl, M))      // prepared plan: tokens of a CU in LDS, weight slabs in registers
@@ -805,6 +879,7 @@ int ivit_layernorm_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan pl,
     REQUIRE(h, pl && x16 && bias_int && sc && ln_dy && out8 && M > 0, "bad arguments");
     REQUIRE_A16(h, x16, "x16");
     REQUIRE_A16(h, out8, "out8");
+    REQUIRE_DISJOINT(h, x16, (size_t)M * pl->K * 2, "x16", out8, (size_t)M * pl->N, "out8", OVL_IN);
     if (!ws_plan_ok(pl, M)) {
         snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 192 or 384 plan", __func__);
         return IVIT_ERR_UNSUPPORTED;
@@ -819,6 +894,12 @@ int ivit_linear_i8_requant_residual_planned(ivit_handle h, ivit_linear_plan pl, 
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, residual, "residual");
     REQUIRE_A16(h, out, "out");
+    REQUIRE_DISJOINT(h, x, (size_t)M * pl->K, "x", out, (size_t)M * pl->N * 2, "out", OVL_IN);
+    // residual == out is refused on a plan, though the unplanned entry takes it: gemm_ps_kernel and gemm_as_kernel request a sub-tile's
+    // identity pieces asynchronously, rounds ahead of its epilogue and at offsets clamped into the array for rows past M, and
+    // gemm_ws_qkv_kernel's epilogue reads them per 32-token tile; that every such load is ordered before the store of its element by
+    // the lane that owns it has not been shown for these three, and the launcher picks among them by shape
+    REQUIRE_DISJOINT(h, residual, (size_t)M * pl->N * 2, "residual", out, (size_t)M * pl->N * 2, "out", OVL_IN);
     GemmArgs a = linear_args(x, pl->w, pl->bias, M, pl->N, pl->K);
     a.out = out; a.dy_ch = pl->dy; a.dy_main = dy_main; a.dy_res = dy_res; a.residual = residual;
     const bool res_fast = rq_fast2(dy_main, dy_res);
@@ -837,6 +918,14 @@ int ivit_linear_i8_requant_residual_layernorm_planned(ivit_handle h, ivit_linear
     REQUIRE_A16(h, residual, "residual");
     REQUIRE_A16(h, out, "out");
     REQUIRE_A16(h, ln_out8, "ln_out8");
+    {   // residual == out included: the LayerNorm tail re-reads out through L1, where the identity loads may have left stale lines
+        const size_t n16 = (size_t)M * pl->N * 2, n8 = (size_t)M * pl->N;
+        REQUIRE_DISJOINT(h, x, (size_t)M * pl->K, "x", out, n16, "out", OVL_IN);
+        REQUIRE_DISJOINT(h, x, (size_t)M * pl->K, "x", ln_out8, n8, "ln_out8", OVL_IN);
+        REQUIRE_DISJOINT(h, residual, n16, "residual", out, n16, "out", OVL_IN);
+        REQUIRE_DISJOINT(h, residual, n16, "residual", ln_out8, n8, "ln_out8", OVL_IN);
+        REQUIRE_DISJOINT(h, out, n16, "out", ln_out8, n8, "ln_out8", OVL_OUT);
+    }
     if (!(pl->wf && rq_fast2(dy_main, dy_res) && pl->K == Ws384Geo::K && pl->N == Ws384Geo::K && M < (1 << 26))) {
         snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a 384 x 384 plan and residual multipliers in the fast range", __func__);
         return IVIT_ERR_UNSUPPORTED;
@@ -856,6 +945,7 @@ int ivit_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan pl, const int8_t 
     REQUIRE(h, ldv == 0 || ldv >= T, "ldv < T (0 = v row-major [B*H, T, dh])");
     const int D = H * dh;
     REQUIRE(h, pl->N == 3 * D && pl->K == D, "plan shape is not [3*H*dh, H*dh]");
+    if (int st = qkv_disjoint(h, __func__, x, (size_t)B * T * D, "x", q, k, vt, B, T, H, dh, ldv)) return st;
     GemmArgs a = linear_args(x, pl->w, pl->bias, B * T, 3 * D, D);
     a.dy_ch = pl->dy; a.q = q; a.k = k; a.vt = vt;
     a.T = T; a.H = H; a.dh = dh; a.ldv = ldv; a.D = D;
@@ -901,6 +991,7 @@ int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan pl,
     REQUIRE_A16(h, vt, "vt");
     REQUIRE(h, pl->N == 3 * H * dh && pl->K == H * dh, "plan shape is not [3*H*dh, H*dh]");
     REQUIRE(h, ldv == 0 || (ldv >= T && ldv % 16 == 0), "ldv: 0 (v row-major [B*H, T, dh]) or a multiple of 16 >= T (v^T)");
+    if (int st = qkv_disjoint(h, __func__, x16, (size_t)B * T * H * dh * 2, "x16", q, k, vt, B, T, H, dh, ldv)) return st;
     if (!qkv_ws_ok(pl, B, T, H, dh, ldv)) {
         snprintf(h->err, sizeof(h->err), "%s: needs ivit_linear_plan_prepare_ws on a K = 192 or 384, dh = 64 plan, B*H*T*64 < 2^31, and K = 192 "
                                          "with B*H*64*ldv < 2^31 for v^T", __func__);
@@ -1102,6 +1193,10 @@ int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, cons
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, residual, "residual");
     REQUIRE_A16(h, out, "out");
+    // residual == out is refused: the lock-step and role-split kernels fetch a unit's identity rows in fc2's epilogue with rows past
+    // M - 1 of a 16-token tile clamped to row M - 1, which another tile's lanes store
+    REQUIRE_DISJOINT(h, x, (size_t)M * p->width, "x", out, (size_t)M * p->width * 2, "out", OVL_IN);
+    REQUIRE_DISJOINT(h, residual, (size_t)M * p->width * 2, "residual", out, (size_t)M * p->width * 2, "out", OVL_IN);
     return mlp_fused_launch(h, p, x, gelu_table, dy_main, dy_res, residual, out, M, 0.f, nullptr, nullptr, nullptr);
 }
 
@@ -1113,6 +1208,12 @@ int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16
     REQUIRE_A16(h, x16, "x16");
     REQUIRE_A16(h, scratch8, "scratch8");
     REQUIRE_A16(h, out, "out");
+    {   // x16 is fetched twice, for the LayerNorm and for the identity branch, by different lanes at different times: no in-place form
+        const size_t n16 = (size_t)M * p->width * 2, n8 = (size_t)M * p->width;
+        REQUIRE_DISJOINT(h, x16, n16, "x16", scratch8, n8, "scratch8", OVL_IN);
+        REQUIRE_DISJOINT(h, x16, n16, "x16", out, n16, "out", OVL_IN);
+        REQUIRE_DISJOINT(h, scratch8, n8, "scratch8", out, n16, "out", OVL_OUT);
+    }
     if (p->width != MLP_C) {
         snprintf(h->err, sizeof(h->err), "%s: the LayerNorm prologue exists at width 384 only", __func__);      // not at 192, not at 256
         return IVIT_ERR_UNSUPPORTED;
@@ -1192,6 +1293,24 @@ static int attention_fused_impl(ivit_handle h, const int8_t *q, const int8_t *k,
     REQUIRE_A16(h, vt, "vt");
     REQUIRE_A16(h, ctx8, "ctx8");
     REQUIRE(h, ((ldv % 16) == 0 && ldv >= T) || (ldv == 0 && rowtab), "ldv must be a multiple of 16 and >= T (0 = v row-major: ivit_attention_fused_rowlut only)");
+    if (dh > 0) {
+        const char *oname = cls_out ? "ctx_cls" : "ctx8";
+        const char *fn = rowtab ? (cls_out ? "ivit_attention_fused_rowlut_cls" : "ivit_attention_fused_rowlut")
+                                : aq ? (cls_out ? "ivit_attention_fused_lut_cls" : "ivit_attention_fused_lut")
+                                     : (cls_out ? "ivit_attention_fused_cls" : "ivit_attention_fused");
+        const size_t nqk = (size_t)B * H * T * dh, nv = ldv == 0 ? nqk : span_bytes((long long)B * H * dh, ldv, T, 1);
+        const size_t nctx = (size_t)B * (cls_out ? 1 : T) * H * dh, nx16 = (size_t)B * T * H * dh * 2, nxc = (size_t)B * H * dh * 2;
+        const struct { const void *p; size_t n; const char *name; } in[4] = {{q, nqk, "q"}, {k, nqk, "k"}, {vt, nv, "vt"}, {x16, nx16, "x16"}};
+        for (const auto &i : in)
+            if (!ranges_disjoint(h, fn, i.p, i.n, i.name, ctx8, nctx, oname, OVL_IN) || !ranges_disjoint(h, fn, i.p, i.n, i.name, x_cls, nxc, "x_cls", OVL_IN))
+                return IVIT_ERR_INVALID;
+        if (!ranges_disjoint(h, fn, ctx8, nctx, oname, x_cls, nxc, "x_cls", OVL_OUT)) return IVIT_ERR_INVALID;
+    }
+    if (rowtab && !attn_fast(dy_qk, dy_pv)) {       // the row-table kernel is built with FAST = true only
+        snprintf(h->err, sizeof(h->err), "ivit_attention_fused_rowlut%s: requant multipliers out of the fast range (use ivit_attention_fused_lut%s)",
+                 cls_out ? "_cls" : "", cls_out ? "_cls" : "");
+        return IVIT_ERR_UNSUPPORTED;
+    }
     if (dh != 64 || T > 640) {
         snprintf(h->err, sizeof(h->err), "ivit_attention_fused: built for dh == 64, T <= 640");
         return IVIT_ERR_UNSUPPORTED;
@@ -1323,6 +1442,7 @@ extern "C" int ivit_gather_rows_i16(ivit_handle h, const int16_t *x, int64_t row
     REQUIRE(h, (C % 8) == 0 && (row_stride % 8) == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0, "C and row_stride multiples of 8, x and out 16-byte aligned");
     const long long n = (long long)rows * (C / 8);
     REQUIRE(h, n < (1LL << 31) * 256, "too many rows");
+    REQUIRE_DISJOINT(h, x, span_bytes(rows, row_stride, C, 2), "x", out, (size_t)rows * C * 2, "out", OVL_IN);
     gather_rows16_kernel<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(x, row_stride, C / 8, n, out);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1330,9 +1450,14 @@ extern "C" int ivit_gather_rows_i16(ivit_handle h, const int16_t *x, int64_t row
 
 // ---------------------------------------------------------------- requant
 template <typename ZT>
-static int requant_any(ivit_handle h, const ZT *z, const ivit_dyadic *dy, int nch, const int32_t *z_id,
+static int requant_any(ivit_handle h, const char *fn, const ZT *z, const ivit_dyadic *dy, int nch, const int32_t *z_id,
                        const ivit_dyadic *dy_id, int bits, void *out, int64_t rows, int C) {
     const long long total = (long long)rows * C;
+    {   // z == out is refused at every width: requant_kernel and requant_vec8_kernel declare z and out __restrict__
+        const size_t nz = (size_t)total * sizeof(ZT), nout = (size_t)total * (bits / 8);
+        if (!ranges_disjoint(h, fn, z, nz, "z", out, nout, "out", OVL_IN)) return IVIT_ERR_INVALID;
+        if (!ranges_disjoint(h, fn, z_id, (size_t)total * 4, "z_id", out, nout, "out", OVL_IN)) return IVIT_ERR_INVALID;
+    }
     // per-channel tables keep the element-per-lane form (coalesced constant loads), and so does an output that is not 16-byte aligned:
     // requant_vec8_kernel stores 8 (8-bit) or 16 (16-bit) bytes at once, requant_kernel one element.  Same integers
     if ((C % 8) == 0 && nch == 1 && ((uintptr_t)out & 15) == 0) {
@@ -1360,7 +1485,7 @@ int ivit_requant_i32(ivit_handle h, const int32_t *z, const ivit_dyadic *dy, int
     REQUIRE(h, nch == 1 || nch == C, "nch must be 1 or C");
     REQUIRE(h, bits == 8 || bits == 16 || bits == 32, "bits must be 8, 16 or 32");
     REQUIRE(h, (z_id == nullptr) == (dy_id == nullptr), "z_id and dy_id go together");
-    return requant_any<int32_t>(h, z, dy, nch, z_id, dy_id, bits, out, rows, C);
+    return requant_any<int32_t>(h, __func__, z, dy, nch, z_id, dy_id, bits, out, rows, C);
 }
 
 int ivit_requant_i16(ivit_handle h, const int16_t *z, const ivit_dyadic *dy, int nch, const int32_t *z_id,
@@ -1370,7 +1495,7 @@ int ivit_requant_i16(ivit_handle h, const int16_t *z, const ivit_dyadic *dy, int
     REQUIRE(h, nch == 1 || nch == C, "nch must be 1 or C");
     REQUIRE(h, bits == 8 || bits == 16 || bits == 32, "bits must be 8, 16 or 32");
     REQUIRE(h, (z_id == nullptr) == (dy_id == nullptr), "z_id and dy_id go together");
-    return requant_any<int16_t>(h, z, dy, nch, z_id, dy_id, bits, out, rows, C);
+    return requant_any<int16_t>(h, __func__, z, dy, nch, z_id, dy_id, bits, out, rows, C);
 }
 
 int ivit_requant_f32(ivit_handle h, const float *z, const ivit_dyadic *dy, int nch, const int32_t *z_id,
@@ -1380,7 +1505,7 @@ int ivit_requant_f32(ivit_handle h, const float *z, const ivit_dyadic *dy, int n
     REQUIRE(h, nch == 1 || nch == C, "nch must be 1 or C");
     REQUIRE(h, bits == 8 || bits == 16 || bits == 32, "bits must be 8, 16 or 32");
     REQUIRE(h, (z_id == nullptr) == (dy_id == nullptr), "z_id and dy_id go together");
-    return requant_any<float>(h, z, dy, nch, z_id, dy_id, bits, out, rows, C);
+    return requant_any<float>(h, __func__, z, dy, nch, z_id, dy_id, bits, out, rows, C);
 }
 
 // ---------------------------------------------------------------- shift/norm kernels
@@ -1390,6 +1515,7 @@ int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in
     CHECK_H(h);
     REQUIRE(h, x && out && rows > 0 && n > 0 && ld_in >= n && ld_out >= n && scale > 0.f, "bad arguments");
     REQUIRE(h, out_bits == 8 || out_bits == 16, "out_bits must be 8 or 16");
+    REQUIRE_DISJOINT(h, x, span_bytes(rows, ld_in, n, 1), "x", out, span_bytes(rows, ld_out, n, 2), "out", OVL_IN);
     const size_t lds = (size_t)4 * n * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "row too long for LDS staging");
     if (int st = launch_dyn<shiftmax_kernel>(h, (unsigned)((rows + 3) / 4), 256, lds, x, rows, n, ld_in, scale, out_bits, out, ld_out)) return st;
@@ -1447,6 +1573,7 @@ int ivit_shiftgelu(ivit_handle h, const int8_t *x, int64_t rows, int C, float sc
     REQUIRE(h, (C % 16) == 0, "C must be a multiple of 16");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, out16, "out16");
+    REQUIRE_DISJOINT(h, x, (size_t)rows * C, "x", out16, (size_t)rows * C * 2, "out16", OVL_IN);
     int lo, hi;
     shiftgelu_product_range(scale, &lo, &hi);
     if (lo < -32768 || hi > 32767) {
@@ -1468,6 +1595,8 @@ int ivit_shiftgelu_requant(ivit_handle h, const int8_t *x, int64_t rows, int C, 
     REQUIRE(h, (C % 16) == 0, "C must be a multiple of 16");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, out8, "out8");
+    // x == out8 is refused like every other overlap: shiftgelu_kernel declares x and out __restrict__ and reads each chunk twice
+    REQUIRE_DISJOINT(h, x, (size_t)rows * C, "x", out8, (size_t)rows * C, "out8", OVL_IN);
     shiftgelu_kernel<true><<<(unsigned)((rows + 3) / 4), 256, 0, h->stream>>>(x, rows, C, scale, dy, out8);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1488,6 +1617,7 @@ int ivit_shiftgelu_requant_lut(ivit_handle h, const int8_t *x, int64_t rows, int
     REQUIRE(h, (C % 16) == 0, "C must be a multiple of 16");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, out8, "out8");
+    REQUIRE_DISJOINT(h, x, (size_t)rows * C, "x", out8, (size_t)rows * C, "out8", OVL_IN);
     // half a wavefront per row, row in registers: ITER = ceil(C / 512) chunks of 16 bytes per lane
     constexpr bool lut_old = false;
     const int iter = (C / 16 + 31) / 32;
@@ -1509,6 +1639,7 @@ int ivit_layernorm(ivit_handle h, const int16_t *x, int64_t rows, int C, float s
     REQUIRE(h, (C % 8) == 0, "C must be a multiple of 8");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, z, "z");
+    REQUIRE_DISJOINT(h, x, (size_t)rows * C * 2, "x", z, (size_t)rows * C * 4, "z", OVL_IN);
     const size_t lds = (size_t)8 * C * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
     if (int st = launch_dyn<layernorm_kernel<false>>(h, (unsigned)((rows + 7) / 8), 256, lds, x, rows, C, C, scale, bias_int, sc, nullptr, z)) return st;
@@ -1533,6 +1664,7 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
     REQUIRE(h, (C % 8) == 0 && (row_stride % 8) == 0 && row_stride >= C, "C, row_stride multiples of 8");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, out8, "out8");
+    REQUIRE_DISJOINT(h, x, span_bytes(rows, row_stride, C, 2), "x", out8, (size_t)rows * C, "out8", OVL_IN);
     {   // production form: the row in registers, 4 S lanes per row (ivit_layernorm.h)
 #define LNR(CC, S) LNR_LAUNCH(CC, S, false, row_stride, 0)
         switch (C) {
@@ -1578,6 +1710,7 @@ int ivit_patch_merge_layernorm_requant(ivit_handle h, const int16_t *x, int B, i
     REQUIRE(h, x && bias_int && sc && dy_ch && out8 && B > 0 && R > 0 && (R % 2) == 0 && C > 0 && scale > 0.f, "bad arguments");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, out8, "out8");
+    REQUIRE_DISJOINT(h, x, (size_t)B * R * R * C * 2, "x", out8, (size_t)B * R * R * C, "out8", OVL_IN);
     const long long rows = (long long)B * (R / 2) * (R / 2);
 #define LNM(CC, S) LNR_LAUNCH(CC, S, true, 0, R)
     switch (4 * C) {
@@ -1600,6 +1733,7 @@ int ivit_shiftmax_masked(ivit_handle h, const int8_t *x, int64_t rows, int n, in
     CHECK_H(h);
     REQUIRE(h, x && out && rows > 0 && n > 0 && ld_in >= n && ld_out >= n && scale > 0.f, "bad arguments");
     REQUIRE(h, out_bits == 8 || out_bits == 16, "out_bits must be 8 or 16");
+    REQUIRE_DISJOINT(h, x, span_bytes(rows, ld_in, n, 1), "x", out, span_bytes(rows, ld_out, n, 2), "out", OVL_IN);
     REQUIRE(h, mask == nullptr || (nW > 0 && H > 0), "mask needs nW, H");
     const size_t lds = (size_t)4 * n * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "row too long for LDS staging");
@@ -1615,6 +1749,7 @@ int ivit_requant_i32_bcast(ivit_handle h, const int32_t *z, ivit_dyadic dy, cons
     CHECK_H(h);
     REQUIRE(h, z && z_id && out && total > 0 && id_period > 0, "bad arguments");
     REQUIRE(h, bits == 8 || bits == 16, "bits must be 8 or 16");
+    REQUIRE_DISJOINT(h, z, (size_t)total * 4, "z", out, (size_t)total * (bits / 8), "out", OVL_IN);
     const int g = grid_for(h, total, 256 * 4);
     if (bits == 8) requant_bcast_kernel<8><<<g, 256, 0, h->stream>>>(z, dy, z_id, id_period, dy_id, out, total);
     else requant_bcast_kernel<16><<<g, 256, 0, h->stream>>>(z, dy, z_id, id_period, dy_id, out, total);
@@ -1626,6 +1761,7 @@ int ivit_avgpool_requant(ivit_handle h, const int8_t *x, int B, int L, int C, iv
     CHECK_H(h);
     REQUIRE(h, x && out8 && B > 0 && L > 0 && C > 0, "bad arguments");
     REQUIRE(h, (L & 1) == 1, "token count must be odd (no rounding ties; see kernel comment)");
+    REQUIRE_DISJOINT(h, x, (size_t)B * L * C, "x", out8, (size_t)B * C, "out8", OVL_IN);
     avgpool_requant_kernel<<<(unsigned)((B * C + 255) / 256), 256, 0, h->stream>>>(x, B, L, C, 0.f, dy, out8);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1635,6 +1771,7 @@ int ivit_avgpool_requant_scaled(ivit_handle h, const int8_t *x, int B, int L, in
                                 int8_t *out8) {
     CHECK_H(h);
     REQUIRE(h, x && out8 && B > 0 && L > 0 && C > 0 && scale > 0.f, "bad arguments");
+    REQUIRE_DISJOINT(h, x, (size_t)B * L * C, "x", out8, (size_t)B * C, "out8", OVL_IN);
     avgpool_requant_kernel<<<(unsigned)((B * C + 255) / 256), 256, 0, h->stream>>>(x, B, L, C, scale, dy, out8);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1650,6 +1787,7 @@ int ivit_layernorm_tokenorder_requant(ivit_handle h, const int16_t *x, int64_t r
                                       int tokens_per_image, int8_t *out8) {
     CHECK_H(h);
     REQUIRE(h, x && bias_int && sc && dy && out8 && rows > 0 && C > 0 && scale > 0.f && tokens_per_image > 0, "bad arguments");
+    REQUIRE_DISJOINT(h, x, (size_t)rows * C * 2, "x", out8, (size_t)rows * C, "out8", OVL_IN);
     const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
     int st;
@@ -1674,6 +1812,7 @@ int ivit_patch_norm_tokenorder(ivit_handle h, const int8_t *x8, int64_t rows, in
                                int16_t *out16) {
     CHECK_H(h);
     REQUIRE(h, x8 && bias_int && sc && dy_ch && out16 && rows > 0 && C > 0 && scale > 0.f && tokens_per_image > 0, "bad arguments");
+    REQUIRE_DISJOINT(h, x8, (size_t)rows * C, "x8", out16, (size_t)rows * C * 2, "out16", OVL_IN);
     const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
     int st;
@@ -1697,6 +1836,7 @@ int ivit_layernorm_tokenorder(ivit_handle h, const int16_t *x, int64_t rows, int
                               const float *bias_int, const float *sc, int tokens_per_image, float *z) {
     CHECK_H(h);
     REQUIRE(h, x && bias_int && sc && z && rows > 0 && C > 0 && scale > 0.f && tokens_per_image > 0, "bad arguments");
+    REQUIRE_DISJOINT(h, x, (size_t)rows * C * 2, "x", z, (size_t)rows * C * 4, "z", OVL_IN);
     const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
     if (int st = launch_dyn<layernorm_tokenorder_kernel<0, 0>>(h, (unsigned)((rows + LNT_ROWS - 1) / LNT_ROWS), 256, lds, x, rows, C, scale, bias_int, sc,
@@ -1728,6 +1868,7 @@ int ivit_im2col_patch(ivit_handle h, const int8_t *img, int B, int Cin, int H, i
     REQUIRE(h, (H % P) == 0 && (W % P) == 0 && (P % 4) == 0 && (W % 4) == 0, "H,W multiples of P; P,W multiples of 4");
     REQUIRE_A16(h, img, "img");
     REQUIRE_A16(h, rows, "rows");
+    REQUIRE_DISJOINT(h, img, (size_t)B * Cin * H * W, "img", rows, (size_t)B * Cin * H * W, "rows", OVL_IN);
     const size_t lds = (size_t)Cin * P * W;
     REQUIRE(h, lds <= 64 * 1024, "patch strip too large for LDS staging");
     if (P == 16 && Cin == 3 && (W % 16) == 0 && B <= 65535)
@@ -1745,6 +1886,7 @@ int ivit_embed_finish(ivit_handle h, const int16_t *patch16, const int32_t *z_cl
     REQUIRE(h, (long long)T * D / 8 < (1 << 22) && B <= 65535, "T * D / 8 < 2^22, B < 2^16");
     REQUIRE_A16(h, patch16, "patch16");
     REQUIRE_A16(h, x16, "x16");
+    REQUIRE_DISJOINT(h, patch16, (size_t)B * (T - 1) * D * 2, "patch16", x16, (size_t)B * T * D * 2, "x16", OVL_IN);
     const int fast = rq_fast2(dy_x, dy_pos);
     embed_finish_kernel<<<dim3((unsigned)((T * (D / 8) + 255) / 256), (unsigned)B), 256, 0, h->stream>>>(
         patch16, z_cls, pos, dy_x, dy_pos, x16, T, D, 1.0f / (float)(D / 8), fast);
@@ -1760,6 +1902,7 @@ int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int C, int H, i
     REQUIRE_A16(h, images, "images");
     REQUIRE_A16(h, x16, "x16");
     const int gh = H / P, gw = W / P, np = gh * gw, K = C * P * P, T = np + 1;
+    REQUIRE_DISJOINT(h, images, (size_t)B * C * H * W, "images", x16, (size_t)B * T * D * 2, "x16", OVL_IN);
     const bool fast = rq_fast2(dy_x, dy_pos);
     GemmArgs a = linear_args(images, w, bias, B * np, D, K);
     if (P != 16 || H % 16 || W % 16 || (D % 8) != 0 || (K % 64) != 0 || !fast || !use_gemm2(a) || (long long)B * np >= (1ll << 30) ||
@@ -1825,6 +1968,7 @@ static int window_attention_impl(ivit_handle h, const int8_t *qkv, ivit_dyadic d
     REQUIRE(h, qkv && relb && ctx && B > 0 && R > 0 && heads > 0, "bad arguments");
     REQUIRE_A16(h, qkv, "qkv");
     REQUIRE_A16(h, ctx, "ctx");
+    if (dh > 0) REQUIRE_DISJOINT(h, qkv, (size_t)B * R * R * 3 * heads * dh, "qkv", ctx, (size_t)B * R * R * heads * dh, "ctx", OVL_IN);
     if (window == 12) return window_attention12_launch(h, qkv, dy_qk, dy_a, relb, s_softmax, aq != nullptr, dy_pv, ctx, B, R,
                                                        shift, heads, dh);
     if (window != 7 || dh != 32 || (R % 7) != 0) {
@@ -1885,6 +2029,13 @@ int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32
                    int hidden) {
     CHECK_H(h);
     REQUIRE(h, x && w1 && dy1 && gelu_table && w2 && dy2 && residual && out && M > 0, "bad arguments");
+    if ((C == Mlp128Geo::C && hidden == Mlp128Geo::HD) || (C == MF_C && hidden == MF_HD)) {
+        // judged at the two widths the entry is built for: at any other (C, hidden) it addresses nothing, and the extents of a shape it
+        // refuses as unsupported describe no array.  residual == out refused: all three kernels fetch the identity of rows past M - 1
+        // of a tile from row M - 1
+        REQUIRE_DISJOINT(h, x, (size_t)M * C, "x", out, (size_t)M * C * 2, "out", OVL_IN);
+        REQUIRE_DISJOINT(h, residual, (size_t)M * C * 2, "residual", out, (size_t)M * C * 2, "out", OVL_IN);
+    }
     if (C == Mlp128Geo::C && hidden == Mlp128Geo::HD)
         return mlp128_launch(h, x, w1, b1, dy1, gelu_table, w2, b2, dy2, dy_main, dy_res, residual, out, M);
     if (C != MF_C || hidden != MF_HD) {
@@ -1916,6 +2067,7 @@ int ivit_patch_merge_gather(ivit_handle h, const void *x, int in_bits, int B, in
     if (in_bits == 16) REQUIRE_A16(h, x, "x");
     else REQUIRE_ALIGNED(h, x, "x", 8);
     REQUIRE_A16(h, out, "out");
+    REQUIRE_DISJOINT(h, x, (size_t)B * R * R * C * (in_bits / 8), "x", out, (size_t)B * R * R * C * 2, "out", OVL_IN);
     const long long total = (long long)B * R * R * C / 8;
     if (in_bits == 8) patch_merge_gather_kernel<int8_t><<<grid_for(h, total, 1024), 256, 0, h->stream>>>((const int8_t *)x, B, R, C, out);
     else patch_merge_gather_kernel<int16_t><<<grid_for(h, total, 1024), 256, 0, h->stream>>>((const int16_t *)x, B, R, C, out);
@@ -1926,6 +2078,7 @@ int ivit_patch_merge_gather(ivit_handle h, const void *x, int in_bits, int B, in
 int ivit_widen_i8_i16(ivit_handle h, const int8_t *x, int16_t *out, int64_t n) {
     CHECK_H(h);
     REQUIRE(h, x && out && n >= 0, "bad arguments");
+    REQUIRE_DISJOINT(h, x, (size_t)n, "x", out, (size_t)n * 2, "out", OVL_IN);
     if (n == 0) return IVIT_OK;
     widen_i8_i16_kernel<<<grid_for(h, n, 1024), 256, 0, h->stream>>>(x, out, n);
     LAUNCH_CHECK(h);
@@ -1937,6 +2090,12 @@ int ivit_logits_topk(ivit_handle h, const int32_t *logits, const float *scale, i
     CHECK_H(h);
     REQUIRE(h, logits && scale && idx && batch >= 0 && num_classes >= 1, "bad arguments");
     REQUIRE(h, k >= 1 && k <= TOPK_MAX_K && k <= num_classes, "k must be in 1 .. min(16, num_classes)");
+    {
+        const size_t nin = (size_t)batch * num_classes * 4, nout = (size_t)batch * k * 4;
+        REQUIRE_DISJOINT(h, logits, nin, "logits", idx, nout, "idx", OVL_IN);
+        REQUIRE_DISJOINT(h, logits, nin, "logits", val, nout, "val", OVL_IN);
+        REQUIRE_DISJOINT(h, idx, nout, "idx", val, nout, "val", OVL_OUT);
+    }
     if (batch == 0) return IVIT_OK;
     const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per image; 64-bit sum: no overflow near INT_MAX
     if (num_classes <= TOPK_REG_CLASSES) logits_topk_kernel<true><<<grid, 256, 0, h->stream>>>(logits, scale, batch, num_classes, k, idx, val);

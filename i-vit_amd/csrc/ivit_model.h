@@ -94,6 +94,26 @@ int graph_capture(ivit_handle h, ivit_graph *out, Fwd &&forward) {
 #define RUN(call) do { const int rc_ = (call); if (rc_ != IVIT_OK) return rc_; } while (0)
 // REQUIRE for a check shared by several entries: the refusal names the entry the caller used
 #define REQUIRE_FN(h, fn, cond, msg) do { if (!(cond)) { snprintf((h)->err, sizeof((h)->err), "%s: %s", fn, msg); return IVIT_ERR_INVALID; } } while (0)
+// the runners' arrays (include/ivit.h, overlapping arguments): the workspace is written throughout, the logits at the end (null: none)
+static int runner_disjoint(ivit_handle h, const char *fn, const int8_t *images, size_t img_bytes, const void *workspace, size_t ws_bytes,
+                           const int32_t *logits, size_t logit_bytes) {
+    return ranges_disjoint(h, fn, images, img_bytes, "images", workspace, ws_bytes, "workspace", OVL_IN) &&
+                   ranges_disjoint(h, fn, images, img_bytes, "images", logits, logit_bytes, "logits", OVL_IN) &&
+                   ranges_disjoint(h, fn, workspace, ws_bytes, "workspace", logits, logit_bytes, "logits", OVL_OUT)
+               ? IVIT_OK : IVIT_ERR_INVALID;
+}
+// idx / val of the predict entries against the forward's arrays and each other, judged BEFORE the forward is launched (ivit_logits_topk
+// judges logits / idx / val again behind it); a batch the workspace query refuses is left to the forward's own argument checks
+static int predict_disjoint(ivit_handle h, const char *fn, const int8_t *images, size_t img_bytes, const void *workspace, size_t ws_bytes,
+                            const int32_t *logits, size_t logit_bytes, const int32_t *idx, const float *val, size_t k_bytes) {
+    const struct { const void *p; size_t n; const char *name; } out[2] = {{idx, k_bytes, "idx"}, {val, k_bytes, "val"}};
+    for (const auto &o : out)
+        if (!ranges_disjoint(h, fn, images, img_bytes, "images", o.p, o.n, o.name, OVL_IN) ||
+            !ranges_disjoint(h, fn, workspace, ws_bytes, "workspace", o.p, o.n, o.name, OVL_OUT) ||
+            !ranges_disjoint(h, fn, logits, logit_bytes, "logits", o.p, o.n, o.name, OVL_OUT))
+            return IVIT_ERR_INVALID;
+    return ranges_disjoint(h, fn, idx, k_bytes, "idx", val, k_bytes, "val", OVL_OUT) ? IVIT_OK : IVIT_ERR_INVALID;
+}
 // a fused entry point where it takes the case (`fused`: its status, or IVIT_ERR_UNSUPPORTED without calling it), else the launches it
 // stands for; any other status of the fused entry is the slice's
 template <class Fallback>
@@ -457,6 +477,7 @@ static int vit_run(ivit_vit m, const char *fn, const int8_t *images, int batch, 
     REQUIRE_FN(h, fn, images && (logits || feat8) && workspace && bytes >= need, "bad arguments / workspace too small");
     REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    if (int st = runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, (size_t)batch * m->cfg.num_classes * 4)) return st;
     const size_t stride = slice_layout(m, max_slice(batch, nslices)).total;
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
         return run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, max_slice(batch, nslices), (char *)workspace + stride * (size_t)i,
@@ -498,6 +519,9 @@ int ivit_vit_predict(ivit_vit m, const int8_t *images, int batch, int nslices, v
                      const float *head_scale, int k, int32_t *idx, float *val) {
     if (!m) return IVIT_ERR_INVALID;
     REQUIRE(m->h, head_scale && idx && k >= 1 && k <= TOPK_MAX_K && k <= m->cfg.num_classes, "head_scale / idx null or k outside 1 .. min(16, num_classes)");
+    if (size_t need = 0; batch > 0 && ivit_vit_workspace_bytes(m, batch, nslices, &need) == IVIT_OK)
+        RUN(predict_disjoint(m->h, __func__, images, (size_t)batch * m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size, workspace, need, logits,
+                             (size_t)batch * m->cfg.num_classes * 4, idx, val, (size_t)batch * k * 4));
     RUN(ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits));
     return ivit_logits_topk(m->h, logits, head_scale, batch, m->cfg.num_classes, k, idx, val);
 }
@@ -828,6 +852,7 @@ static int swin_run(ivit_swin m, const char *fn, const int8_t *images, int batch
     REQUIRE_FN(h, fn, images && (logits || feat8) && workspace && bytes >= need, "bad arguments / workspace too small");
     REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    if (int st = runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, (size_t)batch * m->cfg.num_classes * 4)) return st;
     const size_t stride = swin_layout(m, max_slice(batch, nslices)).total;
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
         return swin_run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, (char *)workspace + stride * (size_t)i,
@@ -867,6 +892,9 @@ int ivit_swin_predict(ivit_swin m, const int8_t *images, int batch, int nslices,
                      const float *head_scale, int k, int32_t *idx, float *val) {
     if (!m) return IVIT_ERR_INVALID;
     REQUIRE(m->h, head_scale && idx && k >= 1 && k <= TOPK_MAX_K && k <= m->cfg.num_classes, "head_scale / idx null or k outside 1 .. min(16, num_classes)");
+    if (size_t need = 0; batch > 0 && ivit_swin_workspace_bytes(m, batch, nslices, &need) == IVIT_OK)
+        RUN(predict_disjoint(m->h, __func__, images, (size_t)batch * m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size, workspace, need, logits,
+                             (size_t)batch * m->cfg.num_classes * 4, idx, val, (size_t)batch * k * 4));
     RUN(ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits));
     return ivit_logits_topk(m->h, logits, head_scale, batch, m->cfg.num_classes, k, idx, val);
 }

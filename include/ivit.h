@@ -21,6 +21,21 @@
  *     address aligned to its element — a row sub-view with an odd pitch, a slice of a batch.  Weights, biases, dyadic tables,
  *     LayerNorm constants and Shiftmax tables are read in 16-byte pieces throughout: keep them 16-byte aligned (a
  *     256-byte-aligned constants blob does);
+ *   - overlapping arguments: an array an entry writes — an output, or a scratch such as scratch8 or a workspace — may overlap
+ *     neither an activation array the entry reads nor another array it writes.  Overlap is judged on extents, [p, p + extent) in
+ *     bytes, where extent is the span this header documents the entry as addressing: a dense [rows, n] array is rows * n elements,
+ *     a pitched or strided one (ld, ldv, lds, ldp, the row_stride of ivit_layernorm_requant and ivit_gather_rows_i16, the batch
+ *     strides of ivit_bmm_nt_*) is (rows - 1) * pitch + row payload, pad columns between rows included.  An overlapping call is
+ *     refused with IVIT_ERR_INVALID before anything is launched, before any decision that would yield IVIT_ERR_UNSUPPORTED (the
+ *     row-table attention entries judge their multipliers' range first, as they always did), and ivit_last_error contains the word
+ *     "overlap" and the two argument names.  Arrays that merely touch are accepted.  Two inputs may overlap freely.  Weights,
+ *     biases, dyadic tables, LUTs and whatever a plan holds are constants: the caller must not write them during a call, and they are
+ *     not checked.  The "Overlap:" line in front of an entry states its rule.  ONE entry declares an (input, output) pair in place,
+ *     ivit_linear_i8_requant_residual with residual == out (the reference's x = x + f(x)): the SAME pointer with the SAME extent is
+ *     accepted and gives, bit for bit, the bytes of the call on disjoint arrays; every other overlap of that pair is still refused.
+ *     The planned and fused forms of the identity branch need a second buffer (ping-pong x / y as ivit_vit_forward does).  The
+ *     whole-model runners refuse images, workspace and logits that overlap, and the predict entries idx and val against those three
+ *     and each other, before the forward is launched;
  *   - activations are carried as INTEGERS plus an fp32 scale held by the caller
  *     (the reference carries fp32 "integer*scale" tensors; X = fl(Q*s) is
  *     re-derived inside the kernels where its rounding matters).
@@ -101,11 +116,13 @@ const char *ivit_last_error(ivit_handle h);
 /* ---- a4  QuantAct.forward, input branch  (quant_modules.py:194-196 ->
  * quant_utils.py:77-96, 12-48):  q = clamp(rne(fl(fl(1/s)*x)), -128, 127)            */
 /* Alignment: x 16-byte aligned, q 4-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: q may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_quantize_input_f32(ivit_handle h, const float *x, float scale, int8_t *q, int64_t n);
 /* ToTensor -> Normalize(mean, std) -> the same input QuantAct, from uint8 pixels on the device
  * (utils/data_utils.py:89-91: transforms.ToTensor, transforms.Normalize; then vit_quant.py:257):
  * hwc uint8 [B, H, W, 3] (a centre-cropped image as PIL hands it over) -> nchw int8 [B, 3, H, W].
  * mean / std are HOST arrays of 3 floats.  Resize / crop: ivit_resize_center_crop_u8 below.       */
+/* Overlap: nchw may not overlap hwc: IVIT_ERR_INVALID, nothing launched. */
 int ivit_normalize_quantize_u8(ivit_handle h, const uint8_t *hwc, int B, int H, int W, const float mean_host[3],
                                const float std_host[3], float scale, int8_t *nchw);
 
@@ -120,6 +137,7 @@ int ivit_normalize_quantize_u8(ivit_handle h, const uint8_t *hwc, int B, int H, 
  *   - ivit_resize_center_crop_u8_pil and ivit_eval_transform_u8 below are pinned to PIL's own bytes
  *     (tests/golden/pil_resize.npz) and take images of different sizes in one call.  A count that is to equal the
  *     reference's `quant_train.py --evaluate` goes through those.                                                         */
+/* Overlap: workspace and out_hwc may overlap neither hwc nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_resize_center_crop_u8(ivit_handle h, const uint8_t *hwc, int B, int H0, int W0, int size, int crop,
                                float *workspace, uint8_t *out_hwc);
 
@@ -143,7 +161,8 @@ typedef struct ivit_image_desc {
  * launched.  The kernel reads ONLY the device copy: a replay of a captured graph reads the device table again, so whatever it
  * holds then must describe images for which the captured call's checks hold (inside pixels_bytes, crop inside the resized image).
  * Every image that ivit_resize_center_crop_u8 accepts is accepted.  No workspace.  pixels, the offsets and the output take any
- * address (byte accesses only).                                                                                          */
+ * address (byte accesses only).
+ * Overlap: out_hwc may not overlap pixels (all pixels_bytes of it) or desc_dev: IVIT_ERR_INVALID, nothing launched. */
 int ivit_resize_center_crop_u8_pil(ivit_handle h, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *desc_host,
                                    const ivit_image_desc *desc_dev, int B, int size, int crop, uint8_t *out_hwc);
 
@@ -152,7 +171,8 @@ int ivit_resize_center_crop_u8_pil(ivit_handle h, const uint8_t *pixels, size_t 
  * 3 x 256 table of ivit_normalize_quantize_u8 with the HWC -> CHW transpose, nchw int8 [B, 3, crop, crop]; the cropped uint8
  * image is never written.  Equal, byte for byte, to ivit_normalize_quantize_u8 on PIL's bytes: the pin is PIL
  * (tests/golden/pil_resize.npz).  Descriptors, checks, graph replay and alignment as above; mean_host / std_host are HOST
- * arrays of 3 floats.                                                                                                     */
+ * arrays of 3 floats.
+ * Overlap: nchw may not overlap pixels (all pixels_bytes of it) or desc_dev: IVIT_ERR_INVALID, nothing launched. */
 int ivit_eval_transform_u8(ivit_handle h, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *desc_host,
                            const ivit_image_desc *desc_dev, int B, int size, int crop, const float mean_host[3],
                            const float std_host[3], float scale, int8_t *nchw);
@@ -160,12 +180,14 @@ int ivit_eval_transform_u8(ivit_handle h, const uint8_t *pixels, size_t pixels_b
 /* ---- a1  QuantLinear.forward  (quant_modules.py:67-97) — integer accumulators.
  * acc[i,j] = sum_k x[i,k]*w[j,k] + bias[j];  x int8 [M,K], w int8 [N,K], K % 16 == 0. */
 /* Alignment: x 16-byte aligned; acc takes any int32 address (a slice of a batch's logits); IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: acc may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias,
                    int32_t *acc, int M, int N, int K);
 
 /* a1 + a3: the QuantLinear -> QuantAct pairs of the reference, fused.
  * out = clamp_bits(rq(acc[i,j], dy_ch[j]));  bits = 8 (int8 out) or 16 (int16 out).    */
 /* Alignment: x and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8_requant(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias,
                            const ivit_dyadic *dy_ch, int bits, void *out, int M, int N, int K);
 
@@ -173,6 +195,7 @@ int ivit_linear_i8_requant(ivit_handle h, const int8_t *x, const int8_t *w, cons
  * (vit_quant.py:84-85,135,141; layers_quant.py:150-151):
  * t = clamp16(rq(acc, dy_ch[j])); out = clamp16(rq(t, dy_main) + rq(residual, dy_res)). */
 /* Alignment: x, residual and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: residual == out (the same pointer, the same extent) is the in place form and gives the bytes of the call on disjoint arrays. Any other overlap of out with x or residual: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8_requant_residual(ivit_handle h, const int8_t *x, const int8_t *w,
                                     const int32_t *bias, const ivit_dyadic *dy_ch,
                                     ivit_dyadic dy_main, ivit_dyadic dy_res,
@@ -185,6 +208,7 @@ int ivit_linear_i8_requant_residual(ivit_handle h, const int8_t *x, const int8_t
  * Columns t >= T of v^T are not written (by the _planned form neither), and no entry that takes v^T or a padded uint16 p
  * (ivit_bmm_nt_u16i8, ivit_attn_pv_requant, ivit_attention_fused*) reads them: they need not be zero. */
 /* Alignment: x, q, k and vt 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: q, k and vt may overlap neither x nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8_qkv(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias,
                        const ivit_dyadic *dy_ch, int8_t *q, int8_t *k, int8_t *vt, int B, int T,
                        int H, int dh, int ldv);
@@ -214,11 +238,14 @@ int ivit_linear_plan_destroy(ivit_linear_plan p);
 /* pipelined_ok: the persistent kernel may be used; single_fma_ok: its one-FMA requant form is exact.        */
 int ivit_linear_plan_query(ivit_linear_plan p, int *pipelined_ok, int *single_fma_ok);
 /* Alignment: x and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, int bits, void *out, int M);
 /* Alignment: x, residual and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out may not overlap x or residual: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8_requant_residual_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, ivit_dyadic dy_main,
                                             ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int M);
 /* Alignment: x, q, k and vt 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: q, k and vt may overlap neither x nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, int8_t *q, int8_t *k, int8_t *vt,
                                int B, int T, int H, int dh, int ldv);
 /* Round 6: K = 384 layers on the kernel that keeps a CU's tokens in LDS and a 64-channel slab of weights in registers
@@ -238,6 +265,7 @@ int ivit_linear_plan_prepare_ws(ivit_handle h, ivit_linear_plan p);
  * IVIT_ERR_UNSUPPORTED (nothing launched) unless the plan is a prepared K = 384 one.  On a prepared plan
  * ivit_linear_i8_requant_planned(bits = 8) runs on the same kernel.                                                            */
 /* Alignment: x16 and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out8 may not overlap x16: IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan p, const int16_t *x16, float scale,
                                              const float *bias_int, const float *sc, const ivit_dyadic *ln_dy, int8_t *out8, int M);
 /* attn.proj + qact2 with the identity branch + norm2 + qact3 of a D = 384 block in ONE launch (vit_quant.py:137-140):
@@ -246,11 +274,13 @@ int ivit_layernorm_linear_i8_requant_planned(ivit_handle h, ivit_linear_plan p, 
  * the plan is a prepared 384 x 384 one and both residual multipliers are in the fast range (|m * 2^-e| < 2^9).  Measured SLOWER
  * than the two launches in the DeiT-S forward (profiles/README.md, round 6): the native runner does not use it.            */
 /* Alignment: x, residual, out and ln_out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out and ln_out8 may overlap neither x and residual nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8_requant_residual_layernorm_planned(ivit_handle h, ivit_linear_plan p, const int8_t *x, ivit_dyadic dy_main,
                                                       ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int M,
                                                       float ln_scale, const float *ln_bias_int, const float *ln_sc,
                                                       const ivit_dyadic *ln_dy, int8_t *ln_out8);
 /* Alignment: x16, q, k and v 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: q, k and v may overlap neither x16 nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan p, const int16_t *x16, float scale,
                                          const float *bias_int, const float *sc, const ivit_dyadic *ln_dy, int8_t *q,
                                          int8_t *k, int8_t *v, int B, int T, int H, int dh);
@@ -262,6 +292,7 @@ int ivit_layernorm_linear_i8_qkv_planned(ivit_handle h, ivit_linear_plan p, cons
  * ivit_linear_i8_qkv.  Columns t >= T of v^T are not written.  IVIT_ERR_UNSUPPORTED (nothing launched) where the ldv == 0 entry returns
  * it, and for v^T on a K = 384 plan or with B*H*64*ldv >= 2^31.                                                               */
 /* Alignment: x16, q, k and vt 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: q, k and vt may overlap neither x16 nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan p, const int16_t *x16, float scale,
                                              const float *bias_int, const float *sc, const ivit_dyadic *ln_dy, int8_t *q,
                                              int8_t *k, int8_t *vt, int B, int T, int H, int dh, int ldv);
@@ -270,12 +301,14 @@ int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan p, 
  * C[b] = A[b] (M x K) * B[b]^T (B[b] is N x K), int32.  q·kᵀ: A=q, B=k.
  * lda/ldb/ldc in elements, strides per batch in elements; lda,ldb % 16 == 0.            */
 /* Alignment: A and B 16-byte aligned; C takes any int32 address; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: C may not overlap A or B: IVIT_ERR_INVALID, nothing launched. */
 int ivit_bmm_nt_i8(ivit_handle h, const int8_t *A, const int8_t *B, int32_t *C, int nb, int M,
                    int N, int K, int lda, int ldb, int ldc, int64_t strideA, int64_t strideB,
                    int64_t strideC);
 /* attn·v with the 16-bit Shiftmax output as A (values 0..32768): exact, two int8 MFMA
  * passes (a-16384 = 256*hi + lo) + 16384*colsum(B).  B = vᵀ [N=dh, K=T].                */
 /* Alignment: A and B 16-byte aligned; C takes any int32 address; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: C may not overlap A or B: IVIT_ERR_INVALID, nothing launched. */
 int ivit_bmm_nt_u16i8(ivit_handle h, const uint16_t *A, const int8_t *B, int32_t *C, int nb,
                       int M, int N, int K, int lda, int ldb, int ldc, int64_t strideA,
                       int64_t strideB, int64_t strideC);
@@ -283,11 +316,13 @@ int ivit_bmm_nt_u16i8(ivit_handle h, const uint16_t *A, const int8_t *B, int32_t
 /* a2 + a3, attention-shaped (vit_quant.py:70-74, 79-83):
  * scores8[bh,i,j] = clamp8(rq(q[bh,i,:]·k[bh,j,:], dy));  scores8 is [B*H, T, lds]; columns j >= T of a row are not written. */
 /* Alignment: q, k and scores8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: scores8 may not overlap q or k: IVIT_ERR_INVALID, nothing launched. */
 int ivit_attn_qk_requant(ivit_handle h, const int8_t *q, const int8_t *k, ivit_dyadic dy,
                          int8_t *scores8, int BH, int T, int dh, int lds);
 /* ctx8[b,i,h*dh+d] = clamp8(rq(sum_j p[bh,i,j]*v[bh,j,d], dy));  p is [B*H,T,ldp] uint16,
  * vt is [B*H,dh,ldv];  ctx8 is [B,T,H*dh] (heads merged, vit_quant.py:81).               */
 /* Alignment: p, vt and ctx8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx8 may not overlap p or vt: IVIT_ERR_INVALID, nothing launched. */
 int ivit_attn_pv_requant(ivit_handle h, const uint16_t *p, const int8_t *vt, ivit_dyadic dy,
                          int8_t *ctx8, int B, int H, int T, int dh, int ldp, int ldv);
 
@@ -297,6 +332,7 @@ int ivit_attn_pv_requant(ivit_handle h, const uint16_t *p, const int8_t *vt, ivi
  * q,k [B*H,T,dh], vt [B*H,dh,ldv] (as written by ivit_linear_i8_qkv), ctx8 [B,T,H*dh].
  * Built for dh == 64 and T <= 640 (DeiT/ViT at 224 and 384); else IVIT_ERR_UNSUPPORTED.   */
 /* Alignment: q, k, vt and ctx8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx8 may not overlap q, k or vt: IVIT_ERR_INVALID, nothing launched. */
 int ivit_attention_fused(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                          ivit_dyadic dy_qk, float s_softmax, ivit_dyadic dy_pv, int8_t *ctx8,
                          int B, int H, int T, int dh, int ldv);
@@ -307,6 +343,7 @@ int ivit_attention_fused(ivit_handle h, const int8_t *q, const int8_t *k, const 
  * exp_t float [t_count], exp_cls uint8 [256] (device; exp_aq and exp_t 16-byte aligned, exp_cls 4-byte aligned — they are
  * copied into LDS in 16-byte pieces; IVIT_ERR_INVALID otherwise).  Same integers as ivit_attention_fused.        */
 /* Alignment: q, k, vt and ctx8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx8 may not overlap q, k or vt: IVIT_ERR_INVALID, nothing launched. */
 int ivit_attention_fused_lut(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                              ivit_dyadic dy_qk, float s_softmax, const uint16_t *exp_aq, const float *exp_t,
                              const uint8_t *exp_cls, int nclass, int t_count, int dmin, ivit_dyadic dy_pv,
@@ -326,6 +363,7 @@ int ivit_attention_fused_lut(ivit_handle h, const int8_t *q, const int8_t *k, co
 int ivit_shiftmax_rowtable(ivit_handle h, const uint16_t *exp_aq, const float *exp_t, const uint8_t *exp_cls,
                            int nclass, int t_count, int dmin, float *rowtab);
 /* Alignment: q, k, vt and ctx8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx8 may not overlap q, k or vt: IVIT_ERR_INVALID, nothing launched. */
 int ivit_attention_fused_rowlut(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                                 ivit_dyadic dy_qk, float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv,
                                 int8_t *ctx8, int B, int H, int T, int dh, int ldv);
@@ -337,21 +375,25 @@ int ivit_attention_fused_rowlut(ivit_handle h, const int8_t *q, const int8_t *k,
  * — the identity rows of the attn.proj that follows (vit_quant.py:135).  ctx_cls, x16 and x_cls 16-byte aligned; otherwise the
  * arguments, limits and status codes of the whole-T entry of the same Shiftmax form.                                               */
 /* Alignment: q, k and vt 16-byte aligned, like ctx_cls, x16 and x_cls; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx_cls and x_cls may overlap neither q, k, vt and x16 nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_attention_fused_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                              ivit_dyadic dy_qk, float s_softmax, ivit_dyadic dy_pv, int8_t *ctx_cls,
                              const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
 /* Alignment: q, k and vt 16-byte aligned, like ctx_cls, x16 and x_cls; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx_cls and x_cls may overlap neither q, k, vt and x16 nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_attention_fused_lut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                                  ivit_dyadic dy_qk, float s_softmax, const uint16_t *exp_aq, const float *exp_t,
                                  const uint8_t *exp_cls, int nclass, int t_count, int dmin, ivit_dyadic dy_pv,
                                  int8_t *ctx_cls, const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
 /* Alignment: q, k and vt 16-byte aligned, like ctx_cls, x16 and x_cls; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx_cls and x_cls may overlap neither q, k, vt and x16 nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_attention_fused_rowlut_cls(ivit_handle h, const int8_t *q, const int8_t *k, const int8_t *vt,
                                     ivit_dyadic dy_qk, float s_softmax, const float *rowtab, int dmin, ivit_dyadic dy_pv,
                                     int8_t *ctx_cls, const int16_t *x16, int16_t *x_cls, int B, int H, int T, int dh, int ldv);
 /* out[r, :] = x[r * row_stride : r * row_stride + C] for r < rows (16-bit values; x[:, 0] of vit_quant.py:272 with
  * row_stride = T * C): the identity-row copy above as a launch of its own.  C and row_stride multiples of 8, 16-byte aligned.    */
 /* Alignment: x and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_gather_rows_i16(ivit_handle h, const int16_t *x, int64_t rows, int C, int64_t row_stride, int16_t *out);
 
 /* ---- a3  QuantAct.forward with a previous scale -> fixedpoint_mul.forward
@@ -359,12 +401,15 @@ int ivit_gather_rows_i16(ivit_handle h, const int16_t *x, int64_t rows, int C, i
  * the I-LayerNorm output exceeds int32), [rows, C];  dy has nch = 1 or C entries;
  * optional identity z_id (int32, same shape) with scalar dy_id;  bits 8 -> int8 out,
  * 16 -> int16 out, 32 -> int32 out.                                                      */
+/* Overlap: out may not overlap z or z_id: IVIT_ERR_INVALID, nothing launched. */
 int ivit_requant_i32(ivit_handle h, const int32_t *z, const ivit_dyadic *dy, int nch,
                      const int32_t *z_id, const ivit_dyadic *dy_id, int bits, void *out,
                      int64_t rows, int C);
+/* Overlap: out may not overlap z or z_id: IVIT_ERR_INVALID, nothing launched. */
 int ivit_requant_i16(ivit_handle h, const int16_t *z, const ivit_dyadic *dy, int nch,
                      const int32_t *z_id, const ivit_dyadic *dy_id, int bits, void *out,
                      int64_t rows, int C);
+/* Overlap: out may not overlap z or z_id: IVIT_ERR_INVALID, nothing launched. */
 int ivit_requant_f32(ivit_handle h, const float *z, const ivit_dyadic *dy, int nch,
                      const int32_t *z_id, const ivit_dyadic *dy_id, int bits, void *out,
                      int64_t rows, int C);
@@ -373,6 +418,7 @@ int ivit_requant_f32(ivit_handle h, const float *z, const ivit_dyadic *dy, int n
  * x int8 [rows, n] (row stride ld_in), per-tensor scale; out_bits 16 (ViT/DeiT) or 8 (Swin);
  * integer probabilities with scale 2^-(out_bits-1), stored uint16 (16-bit results reach
  * 32768).  fp32-faithful interior incl. torch's CPU summation order.                     */
+/* Overlap: out may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in, float scale,
                   int out_bits, uint16_t *out, int ld_out);
 
@@ -384,10 +430,12 @@ int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in
  * and returns IVIT_ERR_UNSUPPORTED (nothing launched, the message names the scale) when they leave int16.
  * The 8-bit forms below carry the product in 32 bits and equal the reference at every positive scale.  */
 /* Alignment: x and out16 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out16 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_shiftgelu(ivit_handle h, const int8_t *x, int64_t rows, int C, float scale,
                    int16_t *out16);
 /* a6 + a3 (layers_quant.py:146-147): ... -> clamp8(rq(Q*sigmoid_int, dy))               */
 /* Alignment: x and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out8 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_shiftgelu_requant(ivit_handle h, const int8_t *x, int64_t rows, int C, float scale,
                            ivit_dyadic dy, int8_t *out8);
 
@@ -397,6 +445,7 @@ int ivit_shiftgelu_requant(ivit_handle h, const int8_t *x, int64_t rows, int C, 
  * a row max plus byte gathers (HBM-bound instead of VALU-bound).                          */
 int ivit_shiftgelu_build_table(ivit_handle h, float scale, ivit_dyadic dy, int8_t *table);
 /* Alignment: x and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out8 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_shiftgelu_requant_lut(ivit_handle h, const int8_t *x, int64_t rows, int C,
                                const int8_t *table, int8_t *out8);
 
@@ -405,11 +454,13 @@ int ivit_shiftgelu_requant_lut(ivit_handle h, const int8_t *x, int64_t rows, int
  * sc[c] = fl(sf*w[c]) from the host.  z[i,c] = rne(fl(fl(out*sc)/sc)) as float — the
  * integer the following QuantAct derives (quant_utils.py:220).                           */
 /* Alignment: x and z 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: z may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm(ivit_handle h, const int16_t *x, int64_t rows, int C, float scale,
                    const float *bias_int, const float *sc, float *z);
 /* a7 + a3 (vit_quant.py:131-132): ... -> clamp8(rq(z, dy_ch[c])).  row_stride in
  * elements lets the final norm read only the class-token rows (vit_quant.py:271-272).    */
 /* Alignment: x and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out8 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
                            int64_t row_stride, float scale, const float *bias_int,
                            const float *sc, const ivit_dyadic *dy_ch, int8_t *out8);
@@ -419,11 +470,13 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
  * embedding (vit_quant.py:259-265).
  * ivit_im2col_patch: NCHW int8 image -> [B*gh*gw, Cin*P*P] rows in conv-weight order.    */
 /* Alignment: img and rows 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: rows may not overlap img: IVIT_ERR_INVALID, nothing launched. */
 int ivit_im2col_patch(ivit_handle h, const int8_t *img, int B, int Cin, int H, int W, int P,
                       int8_t *rows);
 /* x16[b,0,:]  = clamp16(rq(z_cls[:], dy_x) + rq(pos[0,:], dy_pos))
  * x16[b,1+i,:] = clamp16(rq(patch16[b,i,:], dy_x) + rq(pos[1+i,:], dy_pos))             */
 /* Alignment: patch16 and x16 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: x16 may not overlap patch16: IVIT_ERR_INVALID, nothing launched. */
 int ivit_embed_finish(ivit_handle h, const int16_t *patch16, const int32_t *z_cls,
                       const int16_t *pos, ivit_dyadic dy_x, ivit_dyadic dy_pos, int16_t *x16,
                       int B, int T, int D);
@@ -433,6 +486,7 @@ int ivit_embed_finish(ivit_handle h, const int16_t *patch16, const int32_t *z_cl
  * dy_ch [D] as for ivit_linear_i8_requant(bits = 16).  x16 == ivit_im2col_patch -> ivit_linear_i8_requant(16) -> ivit_embed_finish.
  * IVIT_ERR_UNSUPPORTED (nothing launched) unless P == 16, H and W multiples of 16, Cin*P*P a multiple of 64 and |dy_x|, |dy_pos| < 2^9. */
 /* Alignment: images and x16 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: x16 may not overlap images: IVIT_ERR_INVALID, nothing launched. */
 int ivit_patch_embed(ivit_handle h, const int8_t *images, int B, int Cin, int H, int W, int P, const int8_t *w,
                      const int32_t *bias, const ivit_dyadic *dy_ch, const int32_t *z_cls, const int16_t *pos,
                      ivit_dyadic dy_x, ivit_dyadic dy_pos, int16_t *x16, int D);
@@ -580,24 +634,29 @@ int ivit_swin_graph_create(ivit_swin m, const int8_t *images, int batch, int nsl
  * IntSoftmax on `attn + mask` (:151-156): float mask [nW, n, n] (0 / -100.0) added to fl(Q*s)
  * before the division by s; row r of the flattened [B_, H, n] rows uses window (r/(H*n)) % nW.
  * mask == NULL: identical to ivit_shiftmax.                                                */
+/* Overlap: out may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_shiftmax_masked(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in, float scale,
                          int out_bits, const float *mask, int nW, int H, uint16_t *out, int ld_out);
 /* QuantAct with an identity that repeats every id_period elements (relative position bias
  * [H,N,N] broadcast over windows, :149): out = clamp(rq(z[i],dy) + rq(z_id[i % period],dy_id)) */
+/* Overlap: out may not overlap z: IVIT_ERR_INVALID, nothing launched. */
 int ivit_requant_i32_bcast(ivit_handle h, const int32_t *z, ivit_dyadic dy, const int32_t *z_id,
                            int64_t id_period, ivit_dyadic dy_id, int bits, void *out, int64_t total);
 /* AdaptiveAvgPool1d(1) over L (odd) tokens + QuantAct(8) (:553-555): x int8 [B,L,C] -> [B,C]   */
+/* Overlap: out8 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_avgpool_requant(ivit_handle h, const int8_t *x, int B, int L, int C, ivit_dyadic dy,
                          int8_t *out8);
 /* The same for any L, given the input scale: with L even rounding ties are reachable and are
  * decided by the reference's fp32 sequence (fl(Q*s), torch's token-sum order, fl(sum/L),
  * rint(fl(mean/s))), restated exactly; odd L gives the outputs of ivit_avgpool_requant.      */
+/* Overlap: out8 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_avgpool_requant_scaled(ivit_handle h, const int8_t *x, int B, int L, int C, float scale,
                                 ivit_dyadic dy, int8_t *out8);
 /* IntLayerNorm whose row sums follow torch's order for a TOKEN-contiguous input — what the
  * reference computes in Swin stage 0, where activations keep the layout of
  * flatten(2).transpose(1,2) (layers_quant.py:188).  Same outputs as
  * ivit_layernorm otherwise.                                                                */
+/* Overlap: z may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm_tokenorder(ivit_handle h, const int16_t *x, int64_t rows, int C, float scale,
                               const float *bias_int, const float *sc, int tokens_per_image, float *z);
 
@@ -605,12 +664,14 @@ int ivit_layernorm_tokenorder(ivit_handle h, const int16_t *x, int64_t rows, int
  * vectorised kernel) x, out8, bias_int and sc must be 16-byte aligned: IVIT_ERR_INVALID otherwise; the same holds for
  * ivit_patch_norm_tokenorder below.                                                              */
 /* Alignment: at C = 96 / 128 x and out8 16-byte aligned (the other widths take any element-aligned address); IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out8 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm_tokenorder_requant(ivit_handle h, const int16_t *x, int64_t rows, int C, float scale,
                                       const float *bias_int, const float *sc, const ivit_dyadic *dy,
                                       int tokens_per_image, int8_t *out8);
 /* PatchEmbed's tail in one pass (layers_quant.py:193-195, swin_quant.py:543): int8 conv output ->
  * norm (token-order sums) -> qact (16 bit, per-channel dy_ch) -> qact1 (16 bit, per-tensor dy2).          */
 /* Alignment: at C = 96 / 128 x8 and out16 16-byte aligned (the other widths take any element-aligned address); IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out16 may not overlap x8: IVIT_ERR_INVALID, nothing launched. */
 int ivit_patch_norm_tokenorder(ivit_handle h, const int8_t *x8, int64_t rows, int C, float scale,
                                const float *bias_int, const float *sc, const ivit_dyadic *dy_ch,
                                ivit_dyadic dy2, int tokens_per_image, int16_t *out16);
@@ -623,6 +684,7 @@ int ivit_patch_norm_tokenorder(ivit_handle h, const int8_t *x8, int64_t rows, in
  * relative_position_index, dy(qact_table -> qact2)); dy_a = dy(qact_attn1 -> qact2).
  * Built for window 7 (R % 7 == 0) and window 12 (R % 12 == 0, relb 16-byte aligned), dh 32.  */
 /* Alignment: qkv and ctx 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx may not overlap qkv: IVIT_ERR_INVALID, nothing launched. */
 int ivit_window_attention_fused(ivit_handle h, const int8_t *qkv, ivit_dyadic dy_qk, ivit_dyadic dy_a,
                                 const int16_t *relb, float s_softmax, ivit_dyadic dy_pv, int8_t *ctx,
                                 int B, int R, int window, int shift, int heads, int dh);
@@ -632,6 +694,7 @@ int ivit_window_attention_fused(ivit_handle h, const int8_t *qkv, ivit_dyadic dy
  * form, because the float -100 enters between the requotient's multiply and divide.  Same integers as the entry above.
  * Window 7 only (IVIT_ERR_UNSUPPORTED at window 12).                                                                  */
 /* Alignment: qkv and ctx 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: ctx may not overlap qkv: IVIT_ERR_INVALID, nothing launched. */
 int ivit_window_attention_fused_lut(ivit_handle h, const int8_t *qkv, ivit_dyadic dy_qk, ivit_dyadic dy_a,
                                     const int16_t *relb, float s_softmax, const uint16_t *exp_aq, const float *exp_t,
                                     const uint8_t *exp_cls, int nclass, int t_count, int dmin, ivit_dyadic dy_pv,
@@ -645,6 +708,7 @@ int ivit_window_attention_fused_lut(ivit_handle h, const int8_t *qkv, ivit_dyadi
  * dy1, dy2 must be 16-byte aligned, and residual multipliers >= 2^9 are IVIT_ERR_UNSUPPORTED with nothing launched);
  * other shapes: IVIT_ERR_UNSUPPORTED.                                                                   */
 /* Alignment: x, residual and out 16-byte aligned (C = 128: residual and out 8-byte aligned); IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out may not overlap x or residual (judged at the two shapes the entry is built for, an unsupported shape addresses nothing): IVIT_ERR_INVALID, nothing launched. */
 int ivit_mlp_fused(ivit_handle h, const int8_t *x, const int8_t *w1, const int32_t *b1, const ivit_dyadic *dy1,
                    const int8_t *gelu_table, const int8_t *w2, const int32_t *b2, const ivit_dyadic *dy2,
                    ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual, int16_t *out, int64_t M,
@@ -667,6 +731,7 @@ int ivit_mlp_plan_destroy(ivit_mlp_plan p);
  * A width-192 or width-256 plan has the lock-step kernel only: 0 and 1 succeed, 2 returns IVIT_ERR_UNSUPPORTED and changes nothing.  */
 int ivit_mlp_plan_select(ivit_mlp_plan p, int kernel);
 /* Alignment: x, residual and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out may not overlap x or residual: IVIT_ERR_INVALID, nothing launched. */
 int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, const int8_t *gelu_table,
                            ivit_dyadic dy_main, ivit_dyadic dy_res, const int16_t *residual, int16_t *out,
                            int64_t M);
@@ -676,6 +741,7 @@ int ivit_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int8_t *x, cons
  * ivit_layernorm_requant followed by ivit_mlp_fused_planned.  IVIT_ERR_UNSUPPORTED (nothing launched) where ivit_mlp_fused_planned is,
  * where the launch would run on the lock-step kernel (fewer than two units per CU), and on a width-192 or width-256 plan.         */
 /* Alignment: x16, scratch8 and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: scratch8 and out may overlap neither x16 nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int,
                                      const float *sc, const ivit_dyadic *ln_dy, int8_t *scratch8, const int8_t *gelu_table,
                                      ivit_dyadic dy_main, ivit_dyadic dy_res, int16_t *out, int64_t M);
@@ -688,25 +754,30 @@ int ivit_layernorm_mlp_fused_planned(ivit_handle h, ivit_mlp_plan p, const int16
  * (ivit_set_cu_share included).  out overlapping x16 is IVIT_ERR_INVALID.  IVIT_ERR_UNSUPPORTED (nothing launched) on a plan of
  * another width (256) and for residual multipliers outside the fast range.                                                       */
 /* Alignment: x16 and out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out may not overlap x16 (see above): IVIT_ERR_INVALID, nothing launched. */
 int ivit_layernorm_mlp_lockstep_planned(ivit_handle h, ivit_mlp_plan p, const int16_t *x16, float scale, const float *bias_int,
                                         const float *sc, const ivit_dyadic *ln_dy, const int8_t *gelu_table, ivit_dyadic dy_main,
                                         ivit_dyadic dy_res, int16_t *out, int64_t M);
 /* PatchMerging's 2x2 gather (swin_quant.py:336-342): x [B,R,R,C] (in_bits 8 or 16) ->
  * int16 [B, (R/2)^2, 4C], channel blocks in the reference's torch.cat order.                  */
 /* Alignment: x 16-byte aligned (8-byte at in_bits = 8), out 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_patch_merge_gather(ivit_handle h, const void *x, int in_bits, int B, int R, int C, int16_t *out);
 /* The same gather folded into the I-LayerNorm + QuantAct(8) that follows it in PatchMerging.forward (swin_quant.py:336-349:
  * gather, self.norm over 4C, qact1) — x int16 [B,R,R,C] -> out8 int8 [B (R/2)^2, 4C]; the gathered tensor never exists.  Same
  * integers as ivit_patch_merge_gather + ivit_layernorm_requant.  C in {96, 128, 192, 256, 384}; else IVIT_ERR_UNSUPPORTED.      */
 /* Alignment: x and out8 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out8 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_patch_merge_layernorm_requant(ivit_handle h, const int16_t *x, int B, int R, int C, float scale,
                                        const float *bias_int, const float *sc, const ivit_dyadic *dy_ch, int8_t *out8);
+/* Overlap: out may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_widen_i8_i16(ivit_handle h, const int8_t *x, int16_t *out, int64_t n);
 /* PatchMerging's reduction -> qact2 (swin_quant.py:343-349: QuantLinear(4C, 2C, bias = False) then an 8-bit QuantAct) whose consumer is the
  * next stage's 16-bit stream: out16 = clamp8(rq(acc + bias, dy_ch[n])) stored as int16 [M][N] — ivit_linear_i8_requant(bits = 8) followed by
  * ivit_widen_i8_i16 in one launch, same integers.  gemm_glds_kernel's shapes only (K % 32 == 0, K >= 64, not the short-K streaming kernel's):
  * IVIT_ERR_UNSUPPORTED otherwise, nothing launched.                                                                                  */
 /* Alignment: x and out16 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
+/* Overlap: out16 may not overlap x: IVIT_ERR_INVALID, nothing launched. */
 int ivit_linear_i8_requant8_store16(ivit_handle h, const int8_t *x, const int8_t *w, const int32_t *bias, const ivit_dyadic *dy_ch,
                                     int16_t *out16, int M, int N, int K);
 
@@ -720,6 +791,7 @@ int ivit_linear_i8_requant8_store16(ivit_handle h, const int8_t *x, const int8_t
  * by ascending class index — row b of idx is the first k entries of np.lexsort((arange(num_classes), -(v[b] + 0.0))); val holds the
  * bits of v, -0.0 included.  Non-finite scale entries are OUTSIDE the contract (no frozen model has one).
  * 1 <= k <= min(16, num_classes), IVIT_ERR_INVALID otherwise (nothing launched).  One launch (csrc/ivit_topk.h).                    */
+/* Overlap: idx and val may overlap neither logits nor each other: IVIT_ERR_INVALID, nothing launched. */
 int ivit_logits_topk(ivit_handle h, const int32_t *logits, const float *scale, int batch, int num_classes, int k, int32_t *idx,
                      float *val);
 /* validate()'s `output = model(images)` + `output.topk(...)` (quant_train.py:334, :338) as one call: ivit_vit_forward /

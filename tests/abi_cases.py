@@ -8,6 +8,8 @@ or ("in" | "out", array[, pad]).  `pad` describes bytes inside the array that ar
     ("zero", n)        an input's pad columns that include/ivit.h REQUIRES to be zero;
     ("free", mask)     an output of which only mask's bytes are pinned (the others may or may not be written).
 `ALIGN` records, per entry and activation argument, what happens when that one pointer is element-aligned but not 16-byte aligned.
+`INPLACE` records the (input, output) pairs an entry accepts at the same address; every other overlap of an output with an activation
+input or another output is refused (`check_overlap`).
 
 The second half is the arena harness: every array in its own [guard | payload | guard] allocation, on numpy or on the device."""
 import ctypes
@@ -362,6 +364,10 @@ def hip_cases(H, rng):
         w, b, d = _layer(rng, N, K, 16)
         add("linear_i8_requant", [I(i8(M, K)), I(w), I(b), I(d), 16, O(np.zeros((M, N), np.int16)), M, N, K])
         add("linear_i8_requant_residual", [I(i8(M, K)), I(w), I(b), I(d), dyv(dm), dyv(dr), I(i16(M, N)), O(np.zeros((M, N), np.int16)), M, N, K])
+    # the kernel behind the in-place pair of INPLACE that no other case reaches: K = 48 is below gemm_glds_kernel's shapes
+    # (gemm_nt_kernel, 128-row tiles: two whole ones and a ragged third)
+    w, b, d = _layer(rng, 96, 48, 16)
+    add("linear_i8_requant_residual", [I(i8(257, 48)), I(w), I(b), I(d), dyv(dm), dyv(dr), I(i16(257, 96)), O(np.zeros((257, 96), np.int16)), 257, 96, 48])
 
     # ---- whole-T fused attention in its table forms, and the class-token forms: T = 17 (one ragged 16-row query tile + 1) and 65
     tabs = iv.freeze.shiftmax_tables(ATT_SCALE)
@@ -574,7 +580,12 @@ class Arena:
             pay[~self.valid] = 0 if self.kind == "zero" else byte
             img[self.off:self.off + self.nbytes] = pay
         self.byte = byte
+        self.image = img
         self.mem.put(self.buf, img)
+
+    def unchanged(self):
+        """the whole allocation still holds what the last fill put there"""
+        return np.array_equal(self.mem.get(self.buf), self.image)
 
     def read(self):
         """-> (payload bytes, number of guard bytes that no longer hold the fill)"""
@@ -774,3 +785,184 @@ def check_alignment(fn, H, args, mem, refs, idx, outcome, aligned, what, tile_ro
     for i, (pay, front, back) in enumerate(outs):
         if front or back or (pay != 0xA5).any():
             raise ContractError(f"{what}: refused, but output {i} was written")
+
+
+# ---------------------------------------------------------------- overlapping arguments
+# include/ivit.h, "overlapping arguments": an array an entry writes (an ("out", ...) argument, scratch included) may overlap neither an
+# activation input (the ("in", ...) arguments ALIGN lists) nor another array the entry writes; the call is refused with
+# IVIT_ERR_INVALID before anything is launched.  INPLACE lists the exceptions: entry -> {(input index, output index): reason}, indices
+# as in ALIGN — the same pointer with the same extent is accepted and gives the bytes of the call on disjoint arrays.  Everything not
+# listed is refused.  Filled in from the kernels every launcher can start (csrc/ivit_hip.hip), not from runs; a pair is listed only if
+# every element of the input is loaded only by the lane that stores it, before that store, in every one of those kernels.
+INPLACE = {
+    # gemm_nt_kernel, gemm_glds_kernel: the epilogue lane of (grow, gcol) loads eight identity values under the same grow < M,
+    # gcol < N test as its store of those eight elements, the load first.  gemm_wreg_kernel: a lane loads the identity of its own row
+    # and channels ahead of the MFMAs and stores those elements behind them; a lane past M loads row M - 1 but every store is under
+    # `live`, so that value reaches no store.  All three take a GemmArgs by value: no pointer is declared __restrict__.
+    # Cases: the twinned table at M = 300 and 173 (gemm_glds_kernel<EPI, 128>, 3 and 2 row tiles; the 256-row instantiation is
+    # reached by no call at all: tests/test_memory_contract_cpu.py::test_glds_256_row_tile_is_unreachable), M = 8209
+    # (gemm_wreg_kernel), M = 257 at K = 48 (gemm_nt_kernel, 3 row tiles).
+    # The PLANNED form stays refused: gemm_ps_kernel / gemm_as_kernel request identity pieces asynchronously rounds ahead of the
+    # epilogue at offsets clamped for rows past M, gemm_ws_qkv_kernel reads row min(row, M - 1); their order against the stores of the
+    # owning lanes is not established, and the launcher picks among five kernels by shape.
+    "linear_i8_requant_residual": {(6, 7): "residual == out: each epilogue lane loads exactly the identity elements it stores, load first"},
+}
+# Decided the other way, by the same reading:
+#   requant_i16 (z == out at 16 bits), shiftgelu_requant (x == out8), shiftgelu_requant_lut: requant_kernel, requant_vec8_kernel,
+#     shiftgelu_kernel and the shiftgelu_lut kernels declare input and output __restrict__; lane by lane each element is loaded only by
+#     the lane that stores it, but aliasing two __restrict__ pointers is undefined whatever the lanes do, and no kernel changes here;
+#   mlp_fused (swin_mlp_fused_kernel, swin_mlp_rs_kernel, mlp128_kernel), mlp_fused_planned (mlp192 / mlp256 / mlp384_kernel,
+#     mlp384rs_kernel): the identity of rows past M - 1 of a tile is row M - 1 (min(tok, M - 1)), which another tile's lanes store, and
+#     in the role-split kernels the identity is loaded by consumer waves while producer waves of the same workgroup are a unit ahead;
+#   layernorm_mlp_fused_planned: x16 is fetched twice (LayerNorm head, identity branch) by different lanes at different times;
+#   layernorm_mlp_lockstep_planned, linear_i8_requant_residual_layernorm_planned: fixed (the latter re-reads `out` through L1).
+ALWAYS_REFUSED = ("layernorm_mlp_lockstep_planned", "linear_i8_requant_residual_layernorm_planned")
+
+
+def _is_array(a):
+    return isinstance(a, tuple) and a[0] in ("in", "out")
+
+
+def overlap_pairs(name, args, inputs=None):
+    """[(first index, second index)] of one case: every (activation input, output) and every (output, output) pair; the activation
+    inputs are the ones ALIGN lists for the entry (`inputs`: given instead, for an entry that is in no table)"""
+    ins = [i for i in sorted(ALIGN.get(name, {}) if inputs is None else inputs) if _is_array(args[i]) and args[i][0] == "in"]
+    outs = [i for i, a in enumerate(args) if _is_array(a) and a[0] == "out"]
+    return [(i, o) for i in ins for o in outs] + [(o1, o2) for k, o1 in enumerate(outs) for o2 in outs[k + 1:]]
+
+
+def overlap_table_gaps():
+    """records of INPLACE that name no entry with a case, an input that is no activation input or an output that is no output of every
+    case, arrays of different size, or an entry that is refused by decree: must be empty"""
+    cases = [(n, a) for v in (0, 1) for n, a in _cases(np.random.default_rng(0), v)] + [(n, a) for n, a, _ in hip_cases(None, np.random.default_rng(0))]
+    wrong = []
+    for name, pairs in INPLACE.items():
+        mine = [args for n, args in cases if n == name]
+        if not mine or name in ALWAYS_REFUSED:
+            wrong.append((name, "no case / refused by decree"))
+        for (i, o), reason in pairs.items():
+            ok = reason and i in ALIGN.get(name, {}) and all(
+                _is_array(args[i]) and args[i][0] == "in" and _is_array(args[o]) and args[o][0] == "out" and args[i][1].nbytes == args[o][1].nbytes
+                for args in mine)
+            if not ok:
+                wrong.append((name, i, o))
+    return wrong
+
+
+def _r256(n):
+    return (n + 255) // 256 * 256
+
+
+def overlap_placements(na, nb):
+    """{placement: (offset of a, offset of b)} of two arrays of na and nb bytes; all offsets multiples of 256 (16 inside a short a)"""
+    pl = {"same start": (0, 0), "b begins inside a": (0, 256 if na >= 512 else 16)}
+    back = 256 * ((nb - 1) // 256)
+    if back:
+        pl["b ends inside a"] = (back, 0)
+    pl["b behind a"] = (0, _r256(na))
+    pl["a behind b"] = (_r256(nb), 0)
+    return pl
+
+
+class _Shared:
+    """two argument arrays in ONE allocation, at byte offsets `offs` from a 256-byte boundary, with the 1 MiB guards on both sides of
+    their union: a call that is wrongly not refused still addresses only this allocation"""
+    def __init__(self, mem, specs, offs, tile_rows):
+        self.mem, self.specs = mem, specs                 # specs: [(is_out, array, valid mask, kind)]
+        for _, arr, _, _ in specs:
+            _fits(arr, tile_rows)
+        span = max(o + s[1].nbytes for o, s in zip(offs, specs))
+        self.size = 2 * GUARD + span + 2 * PAYLOAD_ALIGN
+        self.buf, base = mem.alloc(self.size)
+        origin = GUARD + (-(base + GUARD)) % PAYLOAD_ALIGN
+        self.off = [origin + o for o in offs]
+        self.ptr = [_P(base + o) for o in self.off]
+        assert min(self.off) >= GUARD and max(o + s[1].nbytes for o, s in zip(self.off, specs)) + GUARD <= self.size
+
+    def fill(self, out_fill, in_fill):
+        img = np.full(self.size, in_fill, np.uint8)
+        for off, (is_out, arr, _, _) in zip(self.off, self.specs):
+            if is_out:
+                img[off:off + arr.nbytes] = out_fill
+        for off, (is_out, arr, valid, kind) in zip(self.off, self.specs):       # the data last: an input under an output keeps it
+            if not is_out:
+                pay = np.ascontiguousarray(arr).view(np.uint8).reshape(-1).copy()
+                pay[~valid] = 0 if kind == "zero" else in_fill
+                img[off:off + arr.nbytes] = pay
+        self.image = img
+        self.mem.put(self.buf, img)
+
+
+def check_overlap(fn, H, args, mem, refs, what, tile_rows=TILE_ROWS, name=None, inplace=None, inputs=None, argnames=None):
+    """the overlap contract on one case: every pair of overlap_pairs in every placement of overlap_placements, inside one shared
+    allocation.  An overlapping placement is refused (IVIT_ERR_INVALID, `overlap` in the message, no byte of any arena changed) unless
+    it is the same start of an INPLACE pair of equal size: that one runs twice and gives the bytes of the plain call both times.  The
+    adjacent placements succeed with the bytes of the plain call, which keeps an entry from over-estimating an extent.
+    H: the handle object (H.h, H.lib.ivit_last_error); name: the entry (its INPLACE record, unless `inplace` is given);
+    argnames: the entry's parameter names as the header spells them, handle not counted (default: include/ivit.h's, by `name`) — a
+    refusal names both arguments of the pair"""
+    inplace = INPLACE.get(name, {}) if inplace is None else inplace
+    if argnames is None and name is not None:
+        argnames = [p.name for p in _lib.ABI.functions["ivit_" + name].params[1:]]
+    want = plain_outputs(fn, H.h, args, mem, refs)
+    arr_idx = [i for i, a in enumerate(args) if _is_array(a)]
+    out_rank = {i: k for k, i in enumerate(i for i in arr_idx if args[i][0] == "out")}
+    spec = {i: (args[i][0] == "out", args[i][1]) + _valid_mask(args[i][1], args[i][2] if len(args[i]) > 2 else None) for i in arr_idx}
+    own = {i: Arena(mem, args[i][1], args[i][0] == "out", args[i][2] if len(args[i]) > 2 else None, 0, tile_rows) for i in arr_idx}
+
+    def verify(sh, pair, others, ran, label):
+        """ran: the call was to succeed.  Outputs hold `want` where the entry documents a write; nothing else changed anywhere"""
+        mem.sync()
+        img = mem.get(sh.buf)
+        allowed = np.zeros(sh.size, bool)
+        for off, idx in zip(sh.off, pair):
+            is_out, arr, valid, kind = spec[idx]
+            if is_out and ran:
+                got = img[off:off + arr.nbytes]
+                if not np.array_equal(np.where(valid, got, 0), want[out_rank[idx]]):
+                    raise ContractError(f"{label}: argument {idx}: {int((np.where(valid, got, 0) != want[out_rank[idx]]).sum())} bytes differ from the call on disjoint arrays")
+                allowed[off:off + arr.nbytes] |= (valid if kind != "free" else True)
+        bad = int(((img != sh.image) & ~allowed).sum())
+        if bad:
+            raise ContractError(f"{label}: {bad} bytes changed in the shared allocation outside what the entry documents as written")
+        for idx in others:
+            ar = own[idx]
+            if ar.is_out and ran:
+                pay, front, back = ar.read()
+                if front or back or not np.array_equal(np.where(ar.valid, pay, 0), want[out_rank[idx]]):
+                    raise ContractError(f"{label}: output argument {idx} differs from the call on disjoint arrays, or its guards changed")
+                if ar.kind != "free" and (pay[~ar.valid] != ar.byte).any():
+                    raise ContractError(f"{label}: output argument {idx}: bytes written that the entry documents as not written")
+            elif not ar.unchanged():
+                raise ContractError(f"{label}: argument {idx}, which is not part of the pair, was written")
+
+    for a, b in overlap_pairs(name, args, inputs):
+        na, nb = args[a][1].nbytes, args[b][1].nbytes
+        others = [i for i in arr_idx if i not in (a, b)]
+        for place, (oa, ob) in overlap_placements(na, nb).items():
+            label = f"{what}, arguments {a} and {b}, {place}"
+            overlapping = oa < ob + nb and ob < oa + na
+            assert overlapping == (place in ("same start", "b begins inside a", "b ends inside a")), label
+            in_place = place == "same start" and na == nb and (a, b) in inplace
+            sh = _Shared(mem, [spec[a], spec[b]], (oa, ob), tile_rows)
+            ptr = {a: sh.ptr[0], b: sh.ptr[1], **{i: own[i].ptr for i in others}}
+            for run in range(2 if in_place else 1):
+                sh.fill(0xA5, 0x7F)
+                for i in others:
+                    own[i].fill(0xA5 if own[i].is_out else 0x7F)
+                mem.sync()
+                queue = iter(arr_idx)
+                ran = in_place or not overlapping
+                try:
+                    _run(fn, H.h, args, lambda arr, is_out: (ptr[next(queue)], None), refs, 0 if ran else _lib.IVIT_ERR_INVALID)
+                except AssertionError as e:
+                    mem.sync()
+                    raise ContractError(f"{label}: status {e.args[0] if e.args else '?'}, expected {'IVIT_OK' if ran else 'IVIT_ERR_INVALID (not refused)'}"
+                                        f"{'' if overlapping else ': ' + H.lib.ivit_last_error(H.h).decode()}") from None
+                if not ran:
+                    msg = H.lib.ivit_last_error(H.h).decode()
+                    if "overlap" not in msg:
+                        raise ContractError(f"{label}: refused, but not with a message about the overlap: {msg!r}")
+                    if argnames and not (argnames[a] in msg and argnames[b] in msg):
+                        raise ContractError(f"{label}: refused, but the message does not name {argnames[a]} and {argnames[b]}: {msg!r}")
+                verify(sh, (a, b), others, ran, label + (f", run {run + 1}" if in_place else ""))

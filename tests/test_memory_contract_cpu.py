@@ -143,3 +143,92 @@ def test_harness_catches_planted_bugs():
         A.check_contract(rowsum_unmasked, None, pargs, mem)
     zargs = [("in", xp, ("zero", 5)), ("out", np.zeros(4, np.int16)), 4, 5, 8]      # a pad the header demands to be zero stays zero
     assert np.array_equal(A.check_contract(rowsum_unmasked, None, zargs, mem)[0].view(np.int16), np.full(4, 15, np.int16))
+
+
+# ---------------------------------------------------------------- overlapping arguments: the table, the header, the harness
+def test_overlap_table_is_consistent():
+    """every record of abi_cases.INPLACE names an entry with cases, an activation input and an output that are arrays of equal size in
+    every case of it, and carries its reason; the two entries refused by decree are not in it"""
+    assert not A.overlap_table_gaps(), A.overlap_table_gaps()
+    for name in A.ALWAYS_REFUSED:
+        assert name not in A.INPLACE and name in A.ALIGN
+
+
+def _header_comment_in_front_of(hdr, name):
+    """the text between the end of the previous declaration and the prototype of ivit_<name>"""
+    import re
+    m = re.search(r"\bint ivit_%s\(" % re.escape(name), hdr)
+    assert m, name
+    return hdr[hdr.rfind(";", 0, m.start()) + 1:m.start()]
+
+
+def test_header_has_an_overlap_line_for_every_entry_with_arrays():
+    """include/ivit.h states the contract once and has an "Overlap:" line in front of every entry with an ALIGN record; the line speaks
+    of an in-place form, and names both arguments of the pair, exactly where abi_cases.INPLACE has a record; the entries whose kernels
+    declare their pointers __restrict__ are not among them"""
+    import os
+    import re
+    from conftest import ROOT
+    from ivit_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "ivit.h")).read()
+    assert "overlapping arguments:" in hdr[:hdr.index("#ifndef IVIT_H")]
+    # (the two ragged front-end entries are in no table: tests/test_pil_resize_gpu.py runs them)
+    for name in sorted(A.ALIGN) + ["resize_center_crop_u8_pil", "eval_transform_u8"]:
+        lines = re.findall(r"\bOverlap:.*?\*/", _header_comment_in_front_of(hdr, name), re.S)     # a comment of its own, or the end of the entry's
+        assert len(lines) == 1, (name, lines)
+        assert ("in place" in lines[0]) == (name in A.INPLACE), (name, lines[0])
+        params = _lib.ABI.functions["ivit_" + name].params
+        for i, o in A.INPLACE.get(name, {}):
+            assert re.search(r"\b%s == %s\b" % (params[i + 1].name, params[o + 1].name), lines[0]), (name, lines[0])
+    assert "IVIT_VERSION 111" in hdr
+    assert not {"requant_i16", "shiftgelu_requant", "shiftgelu_requant_lut"} & set(A.INPLACE)
+
+
+class _FakeHandle:
+    """what check_overlap asks of a handle, for entries written in Python: .h, and .lib.ivit_last_error(h)"""
+    def __init__(self):
+        self.h, self.lib, self.err = None, self, b""
+
+    def ivit_last_error(self, h):
+        return self.err
+
+
+def _planted(F, extent_of_x=lambda n: 2 * n, refuses=True, sequential=False):
+    """out[i] = x[i] + 1 over n int16 values; sequential: out[i] = x[i] + x[(i + 1) % n] (mod 2^16), one element at a time from the last
+    to the first, so that in place x[i + 1] already holds out[i + 1].  Refuses an `out` that overlaps [x, x + extent_of_x(n)) unless it
+    is x itself"""
+    def entry(h, x, out, n):
+        lo, hi = x.value, x.value + extent_of_x(n)
+        if refuses and out.value != x.value and out.value < hi and lo < out.value + 2 * n:
+            F.err = b"planted: x and out overlap"
+            return 1
+        xs, os_ = _view(x, n, np.int16), _view(out, n, np.int16)
+        if not sequential:
+            os_[:] = xs + 1
+            return 0
+        first = int(xs[0])
+        for i in range(n - 1, -1, -1):
+            os_.view(np.uint16)[i] = (int(xs[i]) + (int(xs[i + 1]) if i + 1 < n else first)) & 0xFFFF
+        return 0
+    return entry
+
+
+def test_overlap_harness_catches_planted_entries():
+    """check_overlap on four entries written in Python: the sound one (refuses overlaps, elementwise in place) passes; one that does
+    not refuse, one declared in place whose result depends on the order of its loads and stores, and one that over-estimates the
+    extent of its input (and so refuses arrays that merely touch) are each caught with their own message"""
+    mem, F = A.NumpyMem(), _FakeHandle()
+    n = 640                     # 1280 bytes, a multiple of 256: the adjacent placements touch, so two bytes too many are seen
+    x = np.arange(-320, 320, dtype=np.int16)
+    args = [("in", x), ("out", np.zeros(n, np.int16)), n]
+    kw = dict(inputs=(0,), inplace={(0, 1): "elementwise"})
+    A.check_overlap(_planted(F), F, args, mem, None, "sound", **kw)
+    with pytest.raises(A.ContractError, match="not refused"):
+        A.check_overlap(_planted(F, refuses=False), F, args, mem, None, "never refuses", inputs=(0,), inplace={})
+    with pytest.raises(A.ContractError, match="same start, run 1: argument 1: .* bytes differ from the call on disjoint arrays"):
+        A.check_overlap(_planted(F, sequential=True), F, args, mem, None, "order-dependent", **kw)
+    with pytest.raises(A.ContractError, match="b behind a: status 1, expected IVIT_OK: planted: x and out overlap"):
+        A.check_overlap(_planted(F, extent_of_x=lambda n: 2 * n + 2), F, args, mem, None, "over-estimated extent", **kw)
+    # a pair that is NOT declared in place is refused at the same start too: the sound entry, asked without its record, is caught
+    with pytest.raises(A.ContractError, match="same start: status 0, expected IVIT_ERR_INVALID"):
+        A.check_overlap(_planted(F), F, args, mem, None, "undeclared", inputs=(0,), inplace={})

@@ -4,9 +4,12 @@ Operators: every case of both tables of tests/abi_cases.py runs with each array 
 device arena and must (1) leave both guards of every output and the bytes it documents as not written untouched, under two fills,
 and write every other byte; (2) give the same bytes when the surroundings of its inputs (guards and pad columns) change from 0x7F
 to 0xFF; (3) give the bytes of the same call on plain allocations, and of the CPU twin where it has one; (4) behave as
-abi_cases.ALIGN records when one activation pointer is moved one element off its 16-byte boundary.
+abi_cases.ALIGN records when one activation pointer is moved one element off its 16-byte boundary.  A test of its own,
+test_overlap_contract, lays every output of every case over each activation input and each other output (abi_cases.check_overlap):
+refused before anything is launched, or, for the pairs abi_cases.INPLACE declares, the bytes of the call on disjoint arrays.
 
 Runners: a forward on a workspace that held garbage gives the logits of a forward on a clean one."""
+import ctypes
 import functools
 
 import numpy as np
@@ -84,6 +87,24 @@ def test_memory_contract(H, twin, name):
             for idx, outcome in A.ALIGN.get(name, {}).items():                        # check 4
                 if args[idx] is not None:
                     A.check_alignment(fn, H, args, mem, refs, idx, outcome, got, what, rows)
+        finally:
+            teardown()
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_overlap_contract(H, name):
+    """include/ivit.h, overlapping arguments: an array an entry writes laid over an activation input or over another array it writes
+    is refused before anything is launched, unless abi_cases.INPLACE lists the pair (then the same pointer gives the bytes of the
+    call on disjoint arrays, twice); arrays that merely touch are accepted.  Every case of both tables, every pair, every placement
+    of abi_cases.overlap_placements, each inside one allocation of the test's own."""
+    mem = A.TorchMem()
+    fn = getattr(H.lib, "ivit_" + name)
+    todo = cases_of(H, name)
+    assert todo
+    for label, args, setup, _ in todo:
+        refs, teardown = setup() if setup else (None, lambda: None)
+        try:
+            A.check_overlap(fn, H, args, mem, refs, f"ivit_{name} ({label})", A.TILE_ROWS_OF.get(name, A.TILE_ROWS), name=name)
         finally:
             teardown()
 
@@ -199,6 +220,51 @@ def test_runner_on_dirty_workspace_mixed_shiftmax_forms(B, ns):
     imgs = _images(g, cfg, B)
     want, _ = orc.OracleViT(cfg, w, scales).forward(imgs)
     _dirty_workspace_forwards(eng, imgs, ns, np.asarray(want), np.asarray(want))
+
+
+@pytest.mark.parametrize("fname", ["micro_vit_b2.npz", "micro_swin_b2.npz"])
+def test_runners_refuse_overlapping_arrays(fname):
+    """the whole-model entries: images, workspace and logits of a forward, and idx / val of a predict against those three and each
+    other, laid over one another are refused before anything is launched (status, message with both names, no byte of any buffer
+    changed).  Every substituted pointer lies inside a buffer of the engine's own that holds the substituted extent, so a call that
+    is wrongly not refused still addresses only memory the test owns; the unchanged call then gives the golden logits."""
+    if fname in VIT_MODELS:
+        g, cfg, _, eng = _vit(fname)
+    else:
+        g, cfg, eng = _swin(fname)
+    B, ns, k = 2, 1, 3
+    imgs = torch.from_numpy(_images(g, cfg, B)).cuda()
+    eng._use_current_stream()
+    args, _, (ws, logits, idx, val) = eng._args(imgs, ns, k)
+    lib, P = eng.h.lib, (lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off))
+    n_img, n_log, n_k = imgs.numel(), logits.numel() * 4, idx.numel() * 4
+    assert ws.numel() >= 4096 + max(n_img, n_log) and n_log >= 16 + n_k and n_img >= n_k
+    IMG, WS, LOG, IDX, VAL = 1, 4, 6, 9, 10                     # positions in the predict entries' argument list
+    forward = [(IMG, P(ws), "images", "workspace"), (IMG, P(ws, 4096), "images", "workspace"), (LOG, P(ws, 4096), "workspace", "logits"),
+               (LOG, P(imgs), "images", "logits")]
+    predict = [(IDX, P(logits), "logits", "idx"), (VAL, P(logits, 16), "logits", "val"), (VAL, P(idx), "idx", "val"), (IDX, P(ws, 4096), "workspace", "idx"),
+               (VAL, P(imgs), "images", "val")]
+    bufs = (ws, logits, idx, val)
+    for entry, n_args, table in (("_forward", 7, forward), ("_predict", 11, forward + predict)):
+        fn = getattr(lib, eng.PREFIX + entry)
+        for pos, ptr, name_a, name_b in table:
+            for t, fill in zip(bufs, (0x5A, -7, -7, -7.0)):
+                t.fill_(fill)
+            torch.cuda.synchronize()
+            call = list(args[:n_args])
+            call[pos] = ptr
+            st = fn(*call)
+            msg = lib.ivit_last_error(eng.h.h).decode()
+            torch.cuda.synchronize()
+            assert st == _lib.IVIT_ERR_INVALID, (entry, pos, name_a, name_b, st)
+            assert "overlap" in msg and name_a in msg and name_b in msg, msg
+            for t, fill in zip(bufs, (0x5A, -7, -7, -7.0)):
+                assert (t == fill).all(), (entry, pos, "a refused call wrote one of its arrays")
+    eng._workspace_init(ws, B, ns)
+    assert getattr(lib, eng.PREFIX + "_predict")(*args) == 0
+    torch.cuda.synchronize()
+    n = min(B, int(g["batch"]))
+    assert np.array_equal(logits.cpu().numpy()[:n], g["logits_int"][:n])
 
 
 def test_harness_sees_device_writes_and_reads_outside_the_arrays(H):

@@ -120,6 +120,18 @@ def test_memory_contract(H, k, nchw):
         A.check_alignment(fn, H, args, mem, None, idx, "exact", got, name)
 
 
+@pytest.mark.parametrize("nchw", [False, True], ids=["hwc", "nchw"])
+def test_overlap_contract(H, nchw):
+    """include/ivit.h, overlapping arguments, for the two ragged entries (they are in no table of abi_cases): the output laid over
+    the pixel blob or over the device descriptor table is refused before anything is launched, with both names in the message and no
+    byte changed; touching arrays give the bytes of the plain call.  Three images of different sizes, the placements of
+    abi_cases.overlap_placements inside one allocation of the test's own."""
+    rng = np.random.Generator(np.random.PCG64(5))
+    ims = [_gen(rng, 40, 50), _gen(rng, 30, 64), _gen(rng, 44, 33)]
+    name, args, keep = _args(ims, 24, 20, nchw)
+    A.check_overlap(getattr(H.lib, name), H, args, A.TorchMem(), None, name, name=name[len("ivit_"):], inputs=(0, 3), inplace={})
+
+
 # ---------------------------------------------------------------- refusals
 def _refused(H, name, args, word):
     mem = A.TorchMem()
