@@ -1,8 +1,9 @@
-"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h and include/ivit_features.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
+"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h and include/ivit_attnmap.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
 restated here: the Structures, the status codes and every argtypes / restype are derived from the headers by _abi.py (the mapping
 rule is stated there).  ivit.h is frozen at IVIT_VERSION 111: ABI / SIGNATURES / RESTYPES are its prototypes and stay what they are;
-the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES, and of ivit_features.h,
-under FEATURES_ABI / FEATURES_SIGNATURES / FEATURES_RESTYPES.
+the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES, of ivit_features.h,
+under FEATURES_ABI / FEATURES_SIGNATURES / FEATURES_RESTYPES, and of ivit_attnmap.h, under ATTNMAP_ABI / ATTNMAP_SIGNATURES /
+ATTNMAP_RESTYPES.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -71,6 +72,16 @@ _features_signatures = _abi.signatures(FEATURES_ABI, _structs)
 FEATURES_RESTYPES = {name: ret for name, (ret, args) in _features_signatures.items()}
 FEATURES_SIGNATURES = {name: args for name, (ret, args) in _features_signatures.items()}
 
+# include/ivit_attnmap.h, likewise
+ATTNMAP_ABI = _abi.ATTNMAP_ABI
+IVIT_ATTNMAP_VERSION, IVIT_ATTNMAP_HEADS, IVIT_ATTNMAP_MEAN = (
+    ATTNMAP_ABI.constants[n] for n in ("IVIT_ATTNMAP_VERSION", "IVIT_ATTNMAP_HEADS", "IVIT_ATTNMAP_MEAN"))
+assert set(ATTNMAP_ABI.structs) == set(ABI.structs) and not set(ATTNMAP_ABI.functions) & (
+    set(ABI.functions) | set(EVAL_ABI.functions) | set(FEATURES_ABI.functions))
+_attnmap_signatures = _abi.signatures(ATTNMAP_ABI, _structs)
+ATTNMAP_RESTYPES = {name: ret for name, (ret, args) in _attnmap_signatures.items()}
+ATTNMAP_SIGNATURES = {name: args for name, (ret, args) in _attnmap_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -79,7 +90,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -133,6 +144,14 @@ def bind_features(lib):
     return lib
 
 
+def bind_attnmap(lib):
+    """the same for every prototype of include/ivit_attnmap.h"""
+    for name, args in ATTNMAP_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, ATTNMAP_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -144,7 +163,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH))))
+    _lib = bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH)))))
     return _lib
 
 

@@ -1,4 +1,4 @@
-// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h) over the gfx950 kernels.
+// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -31,6 +31,7 @@
 #include "ivit_topk.h"
 #include "ivit_score.h"
 #include "ivit_features.h"
+#include "ivit_attnmap.h"
 #include "ivit_preprocess.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
@@ -2145,6 +2146,71 @@ extern "C" int ivit_features_f32(ivit_handle h, const int8_t *feat8, int batch, 
     const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per row
     if (mode == IVIT_FEATURES_UNIT) features_f32_kernel<true><<<grid, 256, 0, h->stream>>>(feat8, batch, dim, scale, out);
     else features_f32_kernel<false><<<grid, 256, 0, h->stream>>>(feat8, batch, dim, scale, out);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- class-token attention maps (include/ivit_attnmap.h)
+// the shape rules of ivit_attention_cls_probs (ivit_model.h asks here for its model, before its slices are launched)
+static int attnmap_shape_ok(ivit_handle h, const char *fn, int T, int dh) {
+    if ((dh % 16) != 0 || dh > ATTNMAP_MAX_DH || T > ATTNMAP_MAX_T) {
+        snprintf(h->err, sizeof(h->err), "%s: dh must be a multiple of 16 and at most %d, T at most %d", fn, ATTNMAP_MAX_DH, ATTNMAP_MAX_T);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return IVIT_OK;
+}
+
+extern "C" int ivit_attention_cls_probs(ivit_handle h, const int8_t *q, const int8_t *k, ivit_dyadic dy_qk, float s_softmax, uint16_t *p_cls, int B,
+                                        int H, int T, int dh) {
+    CHECK_H(h);
+    REQUIRE(h, q && k && p_cls && B > 0 && H > 0 && T > 0 && dh > 0, "q, k or p_cls is null, or B, H, T, dh is not positive");
+    REQUIRE(h, s_softmax > 0.f && s_softmax <= FLT_MAX, "s_softmax must be finite and positive");
+    REQUIRE_A16(h, q, "q");
+    REQUIRE_A16(h, k, "k");
+    REQUIRE_ALIGNED(h, p_cls, "p_cls", 2);
+    const size_t nqk = (size_t)B * H * T * dh, np = (size_t)B * H * T * 2;
+    REQUIRE_DISJOINT(h, q, nqk, "q", p_cls, np, "p_cls", OVL_IN);
+    REQUIRE_DISJOINT(h, k, nqk, "k", p_cls, np, "p_cls", OVL_IN);
+    if (const int rc = attnmap_shape_ok(h, __func__, T, dh)) return rc;
+    const long long BH = (long long)B * H;
+    REQUIRE(h, BH <= 0x7fffffffLL, "B * H does not fit an int");
+    const size_t lds = (size_t)4 * T * sizeof(float);            // at most 16 KB
+    attn_cls_probs_kernel<<<(unsigned)((BH + 3) / 4), 256, lds, h->stream>>>(q, k, dy_qk.m * dy_qk.r, s_softmax, p_cls, (int)BH, T, dh);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// the argument rules of the fp32 map (ivit_model.h asks here too: `out` is its map32 and may be absent there)
+static int attnmap_map_args_ok(ivit_handle h, const char *fn, const uint16_t *p_cls, const char *p_name, long long rows, int H, int T, int mode,
+                               const float *out, const char *out_name) {
+    char msg[96] = "";
+    if (!p_cls) snprintf(msg, sizeof(msg), "%s is null", p_name);
+    else if (rows < 0 || H < 1 || T < 1) snprintf(msg, sizeof(msg), "rows is negative, or H or T is not positive");
+    else if (mode != IVIT_ATTNMAP_HEADS && mode != IVIT_ATTNMAP_MEAN) snprintf(msg, sizeof(msg), "mode must be IVIT_ATTNMAP_HEADS or IVIT_ATTNMAP_MEAN");
+    else if ((uintptr_t)p_cls & 1) snprintf(msg, sizeof(msg), "%s must be 2-byte aligned", p_name);
+    else if ((uintptr_t)out & 3) snprintf(msg, sizeof(msg), "%s must be 4-byte aligned", out_name);
+    if (msg[0]) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, msg); return IVIT_ERR_INVALID; }
+    return IVIT_OK;
+}
+static inline size_t attnmap_map_bytes(long long rows, int H, int T, int mode) {
+    return (size_t)rows * (mode == IVIT_ATTNMAP_MEAN ? 1 : H) * (size_t)(T - 1) * 4;
+}
+
+extern "C" int ivit_attention_map_f32(ivit_handle h, const uint16_t *p_cls, int64_t rows, int H, int T, int mode, float *out) {
+    CHECK_H(h);
+    REQUIRE(h, out, "out is null");
+    if (const int rc = attnmap_map_args_ok(h, __func__, p_cls, "p_cls", rows, H, T, mode, out, "out")) return rc;
+    REQUIRE_DISJOINT(h, p_cls, (size_t)rows * H * T * 2, "p_cls", out, attnmap_map_bytes(rows, H, T, mode), "out", OVL_IN);
+    if (H > ATTNMAP_MAX_H || T > ATTNMAP_MAX_T) {
+        snprintf(h->err, sizeof(h->err), "%s: H must be at most %d and T at most %d", __func__, ATTNMAP_MAX_H, ATTNMAP_MAX_T);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    const long long total = (long long)rows * (mode == IVIT_ATTNMAP_MEAN ? 1 : H) * (T - 1);
+    if (total == 0) return IVIT_OK;
+    REQUIRE(h, (total + 255) / 256 <= 0x7fffffffLL, "too many rows for one launch");
+    const unsigned grid = (unsigned)((total + 255) / 256);
+    if (mode == IVIT_ATTNMAP_MEAN) attn_map_f32_kernel<true><<<grid, 256, 0, h->stream>>>(p_cls, (long long)rows, H, T, out);
+    else attn_map_f32_kernel<false><<<grid, 256, 0, h->stream>>>(p_cls, (long long)rows, H, T, out);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

@@ -227,12 +227,25 @@ int vit_attention(const ivit_vit_s *m, ivit_handle h, int i, const int8_t *q, co
                : ivit_attention_fused(h, q, k, vt, b.dy_qk, b.s_softmax, b.dy_pv, ctx, B, H, T, dh, ldv);
 }
 
+// the class-token rows a caller taps (include/ivit_attnmap.h): block indices, strictly ascending; the slice's first row of plane 0 of
+// the caller's attn16 [nblocks, batch, H, T]; and the plane stride batch * H * T in elements
+struct AttnTap {
+    const int *blocks;
+    int nblocks;
+    uint16_t *attn16;
+    size_t plane;
+};
+
 // one slice on handle `h`
 // `Bmax`: images of the LARGEST slice of this forward — every slice uses that slice's buffer layout, so the regions
 // zeroed by ivit_vit_workspace_init are the ones the kernels see whatever the (ragged) slice sizes are
 // `feat8`: the slice's rows of the caller's features [B, D] (include/ivit_features.h), where the final norm writes instead of the
 // workspace, or null; `logits`: null ends the slice in front of the head
-int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, int Bmax, char *ws, int32_t *logits, int8_t *feat8) {
+// `tap`: null, or the blocks whose class-token probabilities go to the caller's attn16, one ivit_attention_cls_probs directly behind
+// the block's qkv launch (q and k have the same [B*H, T, dh] layout whichever qkv or attention form the block takes); with neither
+// logits nor feat8 the slice ends behind the last tap
+int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, int Bmax, char *ws, int32_t *logits, int8_t *feat8,
+              const AttnTap *tap = nullptr) {
     const ivit_vit_config &c = m->cfg;
     const ivit_vit_params &P = m->prm;
     const int T = m->T, D = c.embed_dim, H = c.num_heads, dh = D / H, Hd = c.hidden_dim, ld = m->ld;
@@ -252,6 +265,7 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
                      RUN(ivit_linear_i8_requant(h, patches, P.pe_w, P.pe_b, P.pe_dy, 16, patch16, B * m->num_patches, D, m->Kp));
                      return ivit_embed_finish(h, patch16, P.z_cls, P.pos, P.dy_x, P.dy_pos, x, B, T, D);
                  }));
+    int tapped = 0;
     for (int i = 0; i < c.depth; ++i) {
         const ivit_vit_block &b = m->blocks[i];
         // a layer on the row-table attention takes v ROW-major (ldv = 0: the qkv GEMM stores 16 bytes per lane instead of 16 byte
@@ -270,6 +284,10 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
                          RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, a8));
                          return ivit_linear_i8_qkv_planned(h, m->plans[4 * i], a8, q, k, vt, B, T, H, dh, ldv);
                      }));
+        if (tap && tapped < tap->nblocks && tap->blocks[tapped] == i) {
+            RUN(ivit_attention_cls_probs(h, q, k, b.dy_qk, b.s_softmax, tap->attn16 + tap->plane * (size_t)tapped, B, H, T, dh));
+            if (++tapped == tap->nblocks && !logits && !feat8) return IVIT_OK;
+        }
         if (tail) {
             ctx8 = patches;
             RUN(vit_attention(m, h, i, q, k, vt, ctx8, B, ldv, true, x, patch16));
@@ -467,22 +485,25 @@ int ivit_vit_workspace_init(ivit_vit m, void *workspace, size_t bytes, int batch
     return IVIT_OK;
 }
 
-// the slices of one batch: ivit_vit_forward (logits, no feat8) and ivit_vit_features (feat8, logits or none) end here
+// the slices of one batch: ivit_vit_forward (logits, no feat8), ivit_vit_features (feat8, logits or none) and ivit_vit_attention (a tap,
+// logits or none) end here.  `tap`: the caller's block list and attn16 as a whole; every slice gets its own rows of it
 static int vit_run(ivit_vit m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                   int8_t *feat8) {
+                   int8_t *feat8, const AttnTap *tap = nullptr) {
     ivit_handle h = m->h;
     size_t need = 0;
     int rc = ivit_vit_workspace_bytes(m, batch, nslices, &need);
     if (rc != IVIT_OK) return rc;
-    REQUIRE_FN(h, fn, images && (logits || feat8) && workspace && bytes >= need, "bad arguments / workspace too small");
+    REQUIRE_FN(h, fn, images && (logits || feat8 || tap) && workspace && bytes >= need, "bad arguments / workspace too small");
     REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     if (int st = runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, (size_t)batch * m->cfg.num_classes * 4)) return st;
     const size_t stride = slice_layout(m, max_slice(batch, nslices)).total;
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
+        AttnTap mine;
+        if (tap) { mine = *tap; mine.attn16 += (size_t)b0 * m->cfg.num_heads * m->T; }
         return run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, max_slice(batch, nslices), (char *)workspace + stride * (size_t)i,
                          logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
-                         feat8 ? feat8 + (size_t)b0 * m->cfg.embed_dim : nullptr);
+                         feat8 ? feat8 + (size_t)b0 * m->cfg.embed_dim : nullptr, tap ? &mine : nullptr);
     });
 }
 
@@ -506,6 +527,49 @@ int ivit_vit_features_graph_create(ivit_vit m, const int8_t *images, int batch, 
                                    int32_t *logits, int8_t *feat8, float scale, int mode, float *feat32, ivit_graph *out) {
     if (!m) return IVIT_ERR_INVALID;
     return graph_capture(m->h, out, [&] { return ivit_vit_features(m, images, batch, nslices, workspace, bytes, logits, feat8, scale, mode, feat32); });
+}
+
+// the class token's attention rows (include/ivit_attnmap.h): every argument checked first — the block list, the fp32 map's rules, the
+// five arrays pairwise (images / workspace / logits again in vit_run) —, then the slices with their taps, then the fp32 map on the
+// handle's stream, behind the slices' join
+int ivit_vit_attention(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                       const int *blocks_host, int nblocks, uint16_t *attn16, int mode, float *map32) {
+    if (!m) return IVIT_ERR_INVALID;
+    ivit_handle h = m->h;
+    const int H = m->cfg.num_heads, T = m->T;
+    REQUIRE(h, blocks_host && nblocks >= 1 && nblocks <= m->cfg.depth, "blocks_host is null or nblocks outside 1 .. depth");
+    for (int t = 0; t < nblocks; ++t)
+        REQUIRE(h, blocks_host[t] >= 0 && blocks_host[t] < m->cfg.depth && (t == 0 || blocks_host[t] > blocks_host[t - 1]),
+                "blocks_host must be strictly ascending block indices in [0, depth)");
+    RUN(attnmap_map_args_ok(h, __func__, attn16, "attn16", (long long)nblocks * std::max(batch, 0), H, T, mode, map32, "map32"));
+    if (size_t need = 0; batch > 0 && ivit_vit_workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
+        const size_t rows = (size_t)nblocks * batch;
+        const struct { const void *p; size_t n; const char *name; const char *msg; } a[5] = {
+            {images, (size_t)batch * m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size, "images", OVL_IN},
+            {workspace, need, "workspace", OVL_OUT},
+            {logits, (size_t)batch * m->cfg.num_classes * 4, "logits", OVL_OUT},
+            {attn16, rows * H * T * 2, "attn16", OVL_OUT},
+            {map32, attnmap_map_bytes((long long)rows, H, T, mode), "map32", OVL_OUT}};
+        for (int i = 0; i < 5; ++i)
+            for (int j = std::max(i + 1, 3); j < 5; ++j)        // the pairs among the first three are vit_run's
+                if (!ranges_disjoint(h, __func__, a[i].p, a[i].n, a[i].name, a[j].p, a[j].n, a[j].name, i == 0 ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
+    }
+    RUN(attnmap_shape_ok(h, __func__, T, m->cfg.embed_dim / H));
+    if (map32 && H > ATTNMAP_MAX_H) {
+        snprintf(h->err, sizeof(h->err), "%s: the fp32 map takes at most %d heads", __func__, ATTNMAP_MAX_H);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    const AttnTap tap = {blocks_host, nblocks, attn16, (size_t)std::max(batch, 0) * H * T};
+    RUN(vit_run(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr, &tap));
+    return map32 ? ivit_attention_map_f32(h, attn16, (int64_t)nblocks * batch, H, T, mode, map32) : IVIT_OK;
+}
+
+int ivit_vit_attention_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                                    const int *blocks_host, int nblocks, uint16_t *attn16, int mode, float *map32, ivit_graph *out) {
+    if (!m) return IVIT_ERR_INVALID;
+    return graph_capture(m->h, out, [&] {
+        return ivit_vit_attention(m, images, batch, nslices, workspace, bytes, logits, blocks_host, nblocks, attn16, mode, map32);
+    });
 }
 
 int ivit_vit_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,

@@ -2,6 +2,8 @@
 
 `forward` / `capture` / `predict` / `capture_predict` are NativeEngine's (ivit_amd.native): the whole
 batch goes to the native runner (`ivit_vit_forward`, csrc/ivit_model.h) in one C call.
+`attention` / `capture_attention` are this engine's own: the same runner with the class token's
+attention probabilities of chosen blocks tapped (`ivit_vit_attention`, include/ivit_attnmap.h).
 `forward_ops` issues the same kernels one C-ABI call at a time from Python (used by the
 per-operator timing in bench.py and by the parity tests of the unfused attention path).
 Both follow the call order of the reference `VisionTransformer.forward`
@@ -113,6 +115,7 @@ class ViTEngine(NativeEngine):
         # scalar dyadics are passed by value: keep host copies
         self.host = host_scalars(blob if isinstance(blob, np.ndarray) else self.blob.cpu().numpy(), table)
         self._ws = {}
+        self._attention_out = {}
         self.fused_attention = (cfg.head_dim == 64 and cfg.num_tokens <= 640)
         self.use_exp_tables = True      # forward_ops only: False issues the arithmetic Shiftmax (cross-check)
         # per-layer ShiftGELU(+requant) tables, built on-device by the faithful kernel code
@@ -212,6 +215,72 @@ class ViTEngine(NativeEngine):
         if "feat.s" not in self.f32:
             raise _lib.IvitError("this engine was built without the features' scale: build it with ViTEngine.from_float or frozen_vit")
         return self.f32["feat.s"]
+
+    # ---- the class token's attention rows (include/ivit_attnmap.h).  A ViT / DeiT feature: SwinEngine has no `attention`, a Swin has
+    # no class token
+    def _attention_blocks(self, blocks):
+        """an int or a sequence of block indices, negative ones counting from the end -> strictly ascending tuple in [0, depth)"""
+        depth = self.cfg.depth
+        seq = (blocks,) if isinstance(blocks, (int, np.integer)) else tuple(blocks)
+        if not seq:
+            raise ValueError("blocks is empty")
+        out = []
+        for b in seq:
+            if not isinstance(b, (int, np.integer)) or not -depth <= b < depth:
+                raise ValueError(f"block {b!r}: an integer in [-{depth}, {depth})")
+            out.append(int(b) % depth)
+        if any(b <= a for a, b in zip(out, out[1:])):
+            raise ValueError(f"blocks {seq} -> {tuple(out)}: the indices must be strictly ascending")
+        return tuple(out)
+
+    def _attention_args(self, images, blocks, heads, logits, nslices):
+        """(arguments of the attention entries, cache key, buffers, what the caller gets) for one batch: attn16 and map32 live beside the
+        logits buffer and follow its rule (_predict_buffers), one set per (batch, slices, blocks, heads)"""
+        blocks = self._attention_blocks(blocks)
+        args, key, (ws, lg) = self._args(images, nslices)
+        cfg, n, B = self.cfg, len(blocks), images.shape[0]
+        H, T, g = cfg.num_heads, cfg.num_tokens, cfg.img_size // cfg.patch_size
+        assert T == g * g + 1, "one class token in front of a square grid of patches"
+        okey = key + (blocks, bool(heads))
+        outs = self._attention_out
+        hit = outs.get(okey)
+        if hit is None or hit[0] is not lg:
+            for old in [q for q, v in outs.items() if not v[4] and q[:2] not in self._native_ws]:
+                del outs[old]
+            hit = outs[okey] = [lg, torch.empty(n, B, H, T, dtype=torch.uint16, device=self.device),
+                                torch.empty((n, B, H, T - 1) if heads else (n, B, T - 1), dtype=torch.float32, device=self.device),
+                                (ctypes.c_int * n)(*blocks), False]
+        _, attn16, map32, blocks_host, _ = hit
+        mode = _lib.IVIT_ATTNMAP_HEADS if heads else _lib.IVIT_ATTNMAP_MEAN
+        args = args[:-1] + (_P(lg.data_ptr()) if logits else None, blocks_host, n, _P(attn16.data_ptr()), mode, _P(map32.data_ptr()))
+        maps = map32.view(n, B, H, g, g) if heads else map32.view(n, B, g, g)
+        return args, okey, (ws, lg, attn16, map32, blocks_host), (attn16, maps) + ((lg,) if logits else ())
+
+    def attention(self, images, blocks=-1, heads=False, logits=False, nslices=1, copy=False):
+        """images int8 [B, C, H, W] -> (attn16, maps), or (attn16, maps, logits) with logits=True: what the class token attends to in
+        the blocks asked for (an int or a sequence; negative indices count from the end; strictly ascending after that, else
+        ValueError).  attn16 uint16 [n, B, heads, T]: plane t is row 0 of blocks.{blocks[t]}.attn.int_softmax of the reference
+        (vit_quant.py:76), the same integers, scale 2^-15 (`predict.attention_reference`).  maps float32 [n, B, gh, gw]: the
+        patch columns of those rows on the patch grid, the mean over the heads — or [n, B, heads, gh, gw] with heads=True, each
+        head's own (`predict.attention_map_reference`).  One native call: one small launch per tapped block behind its qkv launch
+        and one for the maps.  Without `logits` the forward ends behind the last tapped block; with it the int32 logits are
+        forward's (and `last_logits`).  The results are the engine's own buffers for this (batch, nslices, blocks, heads):
+        copy=True (or clone) to keep them across calls."""
+        self._use_current_stream()
+        self._check_images(images)
+        args, _, bufs, out = self._attention_args(images, blocks, heads, logits, nslices)
+        self._entry("_attention", *args)
+        if logits:
+            self.last_logits = bufs[1]
+        return tuple(t.clone() for t in out) if copy else out
+
+    def capture_attention(self, images, blocks=-1, heads=False, logits=False, nstreams=1):
+        """hipGraph of one attention on fixed buffers; returns a callable that replays it and returns what `attention` returns."""
+        self._check_images(images)
+        args, okey, bufs, out = self._attention_args(images, blocks, heads, logits, nstreams)
+        replay = self._capture("_attention_graph_create", images, args, okey, bufs, out)
+        self._attention_out[okey][4] = True
+        return replay
 
     def workspace(self, B, key=None):
         wkey = (B, key)

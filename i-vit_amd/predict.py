@@ -13,7 +13,10 @@ vit_quant.py:278-282 / swin_quant.py:560-564), takes the cross-entropy and top-1
     no collective per step);
   * `features_reference` is the numpy statement of the contract of `ivit_features_f32` (include/ivit_features.h): the fp32 form of
     the int8 features the reference's forward_features returns (vit_quant.py:254-276, swin_quant.py:540-556), and `embed` is
-    evaluate's loop for them (the engines' `features`).
+    evaluate's loop for them (the engines' `features`);
+  * `attention_reference` is the numpy statement of the contract of `ivit_attention_cls_probs` (include/ivit_attnmap.h): row 0 of
+    IntSoftmax's output (vit_quant.py:70-76, quant_modules.py:469-497) from a block's q and k, and `attention_map_reference` that of
+    `ivit_attention_map_f32`, the fp32 map over the patches (ViTEngine's `attention`).
 """
 import numpy as np
 import torch
@@ -85,6 +88,107 @@ def features_reference(feat8, scale, mode=0):
     ss = (q.astype(np.int64) ** 2).sum(axis=1)
     root = np.sqrt(np.where(ss > 0, ss, 1).astype(np.float64))        # a row of zeros: 0 / 1
     return (q.astype(np.float64) / root[:, None]).astype(np.float32)
+
+
+def _dyadic_mr(dy):
+    """(m, r) as float64 from a pair, a [1, 2] array or anything with .m and .r (a Dyadic, or a one-element array of them)"""
+    if hasattr(dy, "m"):
+        return np.float64(dy.m), np.float64(dy.r)
+    if not isinstance(dy, np.ndarray) and hasattr(dy, "__len__") and len(dy) == 1 and hasattr(dy[0], "m"):
+        return np.float64(dy[0].m), np.float64(dy[0].r)
+    m, r = np.asarray(dy, dtype=np.float64).reshape(2)
+    return m, r
+
+
+def _torch_order_sum(e):
+    """float32 [R, n] -> float32 [R]: the sum over the last axis in the order torch's CPU kernel adds a contiguous float32 row
+    (torch_order_sum32 of csrc/ivit_device.h is the same statement): 32 accumulators, element 32 i + a into
+    accumulator a, closed into a second level every 16 steps, a third every 256; whole 8-vectors left over into accumulators 0..7;
+    p[l] = ((a[l] + a[8 + l]) + a[16 + l]) + a[24 + l]; the scalar tail summed first, then p[0] .. p[7] onto it.  Every addition
+    rounds to float32."""
+    e = np.ascontiguousarray(e, dtype=np.float32)
+    R, n = e.shape
+    nvec, size = n >> 3, n >> 5
+    a0, a1, a2, a3 = (np.zeros((R, 32), np.float32) for _ in range(4))
+    i = 0
+    while i + 16 <= size:
+        for _ in range(16):
+            a0 = a0 + e[:, 32 * i:32 * i + 32]
+            i += 1
+        a1, a0 = a1 + a0, np.zeros_like(a0)
+        if i & 0xF0:
+            continue
+        a2, a1 = a2 + a1, np.zeros_like(a1)
+        if i & 0xF00:
+            continue
+        a3, a2 = a3 + a2, np.zeros_like(a2)
+    while i < size:
+        a0 = a0 + e[:, 32 * i:32 * i + 32]
+        i += 1
+    a0 = ((a0 + a1) + a2) + a3
+    for v in range(size * 4, nvec):
+        a0[:, :8] = a0[:, :8] + e[:, 8 * v:8 * v + 8]
+    p = ((a0[:, 0:8] + a0[:, 8:16]) + a0[:, 16:24]) + a0[:, 24:32]
+    fin = np.zeros(R, np.float32)
+    for k in range(nvec * 8, n):
+        fin = fin + e[:, k]
+    if nvec:
+        for l in range(8):
+            fin = fin + p[:, l]
+    assert fin.dtype == np.float32
+    return fin
+
+
+def attention_reference(q, k, dy_qk, s_softmax):
+    """q, k int8 [BH, T, dh] (a block's query and key, one [T, dh] per image and head), dy_qk the multiplier (m, r) of qact_attn1,
+    s_softmax its scale -> uint16 [BH, T]: the class token's attention probabilities, row 0 of IntSoftmax's output, scale 2^-15.
+
+    acc[j] = q[0] . k[j] as an exact integer; sc8 = clip(rint((float64(acc) * m) * r), -128, 127) (quant_utils.py:229-251).  Then
+    IntSoftmax.forward in float32, one rounding per operation (quant_modules.py:469-497): x = fl(fl(sc8 * s) / s) minus its row
+    maximum; t = max(x + floor(x / 2) - floor(x / 16), 15 x0) with x0 = floor(-1 / s); qq = floor(t / x0); e = max(floor((fl(t - x0 qq) / 2
+    - x0) * 2^(15 - qq)), 0); S = min(sum e, 2^31) in torch's order; F = floor(fl(1 / S) * 2^31); p = floor(fl(e * F) / 2^16).  Of q only
+    row 0 is read."""
+    f32 = np.float32
+    q, k = np.asarray(q), np.asarray(k)
+    assert q.dtype == np.int8 and k.dtype == np.int8 and q.ndim == 3 and q.shape == k.shape
+    s = f32(s_softmax)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError(f"s_softmax = {s}: finite and positive")
+    m, r = _dyadic_mr(dy_qk)
+    acc = np.einsum("bd,bjd->bj", q[:, 0].astype(np.int64), k.astype(np.int64))
+    sc8 = np.clip(np.rint((acc.astype(np.float64) * m) * r), -128, 127).astype(f32)
+    xt = (sc8 * s) / s
+    x = xt - xt.max(axis=1, keepdims=True)
+    x0 = np.floor(f32(-1.0) / s)
+    t = x + np.floor(x * f32(0.5))
+    t = np.maximum(t - np.floor(x * f32(0.0625)), f32(15.0) * x0)
+    qq = np.floor(t / x0)
+    e = (t - x0 * qq) * f32(0.5) - x0
+    e = np.maximum(np.floor(np.ldexp(e, (15 - qq).astype(np.int32))), f32(0.0))
+    assert xt.dtype == t.dtype == e.dtype == f32
+    S = np.minimum(_torch_order_sum(e), f32(2147483648.0))
+    F = np.floor((f32(1.0) / S) * f32(2147483648.0))
+    p = np.floor((e * F[:, None]) * f32(2.0 ** -16))
+    assert p.dtype == f32
+    return p.astype(np.uint16)
+
+
+def attention_map_reference(attn16, heads=False):
+    """attn16 uint16 [..., H, T] -> float32, the patch columns 1 .. T - 1 only, every bit.
+
+    heads=True (IVIT_ATTNMAP_HEADS): [..., H, T - 1], p * 2^-15, exact: the float32 tensor IntSoftmax returns in the reference.
+    heads=False (IVIT_ATTNMAP_MEAN): [..., T - 1], the mean over the heads: S = sum_h p as an exact integer, float64(S) /
+    float64(H * 32768) rounded ONCE to float32 (S and H * 32768 are below 2^24: this is the correctly rounded float32 quotient)."""
+    p = np.asarray(attn16)
+    assert p.dtype == np.uint16 and p.ndim >= 2
+    H = p.shape[-2]
+    if not 1 <= H <= 511:
+        raise ValueError(f"{H} heads: 1 .. 511 (the sum must stay below 2^24)")
+    p = p[..., 1:]
+    if heads:
+        return p.astype(np.float32) * np.float32(2.0 ** -15)
+    S = p.astype(np.int64).sum(axis=-2)
+    return (S.astype(np.float64) / np.float64(H * 32768)).astype(np.float32)
 
 
 def embed(engine, batches, transform=None, normalize=True):
