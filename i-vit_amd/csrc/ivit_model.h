@@ -2,7 +2,9 @@
 // "whole-model runner").  Each chains the C-ABI entry points of ivit_hip.hip in the order of the
 // reference's forward (vit_quant.py:254-282, swin_quant.py) and owns its ShiftGELU tables and plans.
 // What is not about a model is written once, first: SliceRunner (the slice streams, events and
-// handles), fork_join, graph_capture, RUN / fused_or and gelu_table.  Included at the end of ivit_hip.hip.
+// handles), fork_join, graph_capture, RUN / fused_or and gelu_table.  Then each model: its struct, slice layout, slice body and create /
+// destroy / queries.  Last, once for both models, the runner entries: run_slices (what a runner checks, and in which order, before it
+// launches) and one body each for forward, predict, score and features.  Included at the end of ivit_hip.hip.
 #pragma once
 #include <vector>
 
@@ -68,14 +70,17 @@ int fork_join(const SliceRunner &r, ivit_handle h, int batch, int nslices, Body 
     return IVIT_OK;
 }
 
-// `forward()` captured on the handle's stream into an executable graph
-template <class Fwd>
-int graph_capture(ivit_handle h, ivit_graph *out, Fwd &&forward) {
+// the *_graph_create forms: `entry(m, args...)`, the eager entry itself (so a refusal names it), captured on the stream of the model's
+// handle into an executable graph
+template <class M, class Entry, class... Args>
+int graph_capture(M *m, ivit_graph *out, Entry entry, Args... args) {
+    if (!m) return IVIT_ERR_INVALID;
+    ivit_handle h = m->h;
     REQUIRE(h, out, "null argument");
     REQUIRE(h, h->stream != nullptr, "graph capture needs a non-default stream on the handle");
     hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) { snprintf(h->err, sizeof(h->err), "begin capture: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    const int rc = forward();
+    const int rc = entry(m, args...);
     hipGraph_t graph = nullptr;
     e = hipStreamEndCapture(h->stream, &graph);
     if (rc != IVIT_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -119,6 +124,15 @@ static int predict_disjoint(ivit_handle h, const char *fn, const int8_t *images,
 template <class Fallback>
 int fused_or(int fused, Fallback &&fallback) { return fused == IVIT_ERR_UNSUPPORTED ? fallback() : fused; }
 
+// the class-token rows a caller taps (include/ivit_attnmap.h): block indices, strictly ascending; the slice's first row of plane 0 of
+// the caller's attn16 [nblocks, batch, H, T]; and the plane stride batch * H * T in elements
+struct AttnTap {
+    const int *blocks;
+    int nblocks;
+    uint16_t *attn16;
+    size_t plane;
+};
+
 // block i's ShiftGELU table
 template <class Model>
 int8_t *gelu_table(const Model *m, int i) { return m->gelu_tab + (size_t)i * 65536; }
@@ -126,6 +140,8 @@ int8_t *gelu_table(const Model *m, int i) { return m->gelu_tab + (size_t)i * 655
 }  // namespace
 
 struct ivit_vit_s {
+    // the entries a refusal of the shared workspace query and of the shared forward names
+    static constexpr const char *WS_ENTRY = "ivit_vit_workspace_bytes", *FWD_ENTRY = "ivit_vit_forward";
     ivit_handle h;                    // the caller's handle (its stream is the parent stream)
     ivit_vit_config cfg;
     ivit_vit_params prm;
@@ -227,15 +243,6 @@ int vit_attention(const ivit_vit_s *m, ivit_handle h, int i, const int8_t *q, co
                : ivit_attention_fused(h, q, k, vt, b.dy_qk, b.s_softmax, b.dy_pv, ctx, B, H, T, dh, ldv);
 }
 
-// the class-token rows a caller taps (include/ivit_attnmap.h): block indices, strictly ascending; the slice's first row of plane 0 of
-// the caller's attn16 [nblocks, batch, H, T]; and the plane stride batch * H * T in elements
-struct AttnTap {
-    const int *blocks;
-    int nblocks;
-    uint16_t *attn16;
-    size_t plane;
-};
-
 // one slice on handle `h`
 // `Bmax`: images of the LARGEST slice of this forward — every slice uses that slice's buffer layout, so the regions
 // zeroed by ivit_vit_workspace_init are the ones the kernels see whatever the (ragged) slice sizes are
@@ -245,7 +252,7 @@ struct AttnTap {
 // the block's qkv launch (q and k have the same [B*H, T, dh] layout whichever qkv or attention form the block takes); with neither
 // logits nor feat8 the slice ends behind the last tap
 int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, int Bmax, char *ws, int32_t *logits, int8_t *feat8,
-              const AttnTap *tap = nullptr) {
+              const AttnTap *tap) {
     const ivit_vit_config &c = m->cfg;
     const ivit_vit_params &P = m->prm;
     const int T = m->T, D = c.embed_dim, H = c.num_heads, dh = D / H, Hd = c.hidden_dim, ld = m->ld;
@@ -335,6 +342,17 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
     return IVIT_OK;
 }
 
+// what run_slices asks of a model: the workspace bytes of one slice of `Bmax` images, the width of a features row, and slice_run — one
+// slice of `nb` images, the batch's images b0 onward, on its own rows of logits, feat8 and (from here on) the tap
+inline size_t slice_stride(const ivit_vit_s *m, int Bmax) { return slice_layout(m, Bmax).total; }
+inline int num_features(const ivit_vit_s *m) { return m->cfg.embed_dim; }
+int slice_run(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int b0, int nb, int Bmax, char *ws, int32_t *logits, int8_t *feat8,
+              const AttnTap *tap) {
+    AttnTap mine;
+    if (tap) { mine = *tap; mine.attn16 += (size_t)b0 * m->cfg.num_heads * m->T; }
+    return run_slice(m, h, images, nb, Bmax, ws, logits, feat8, tap ? &mine : nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -419,13 +437,6 @@ int ivit_vit_destroy(ivit_vit m) {
     return IVIT_OK;
 }
 
-int ivit_vit_workspace_bytes(ivit_vit m, int batch, int nslices, size_t *bytes) {
-    if (!m) return IVIT_ERR_INVALID;
-    REQUIRE(m->h, bytes && batch > 0 && nslices >= 1 && nslices <= m->max_slices && nslices <= batch, "bad arguments");
-    *bytes = slice_layout(m, max_slice(batch, nslices)).total * (size_t)nslices;
-    return IVIT_OK;
-}
-
 int ivit_vit_fused_mlp_blocks(ivit_vit m, int batch, int *blocks) {
     if (!m) return IVIT_ERR_INVALID;
     REQUIRE(m->h, blocks && batch > 0, "bad arguments");
@@ -485,153 +496,12 @@ int ivit_vit_workspace_init(ivit_vit m, void *workspace, size_t bytes, int batch
     return IVIT_OK;
 }
 
-// the slices of one batch: ivit_vit_forward (logits, no feat8), ivit_vit_features (feat8, logits or none) and ivit_vit_attention (a tap,
-// logits or none) end here.  `tap`: the caller's block list and attn16 as a whole; every slice gets its own rows of it
-static int vit_run(ivit_vit m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                   int8_t *feat8, const AttnTap *tap = nullptr) {
-    ivit_handle h = m->h;
-    size_t need = 0;
-    int rc = ivit_vit_workspace_bytes(m, batch, nslices, &need);
-    if (rc != IVIT_OK) return rc;
-    REQUIRE_FN(h, fn, images && (logits || feat8 || tap) && workspace && bytes >= need, "bad arguments / workspace too small");
-    REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
-    if (int st = runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, (size_t)batch * m->cfg.num_classes * 4)) return st;
-    const size_t stride = slice_layout(m, max_slice(batch, nslices)).total;
-    return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
-        AttnTap mine;
-        if (tap) { mine = *tap; mine.attn16 += (size_t)b0 * m->cfg.num_heads * m->T; }
-        return run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, max_slice(batch, nslices), (char *)workspace + stride * (size_t)i,
-                         logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
-                         feat8 ? feat8 + (size_t)b0 * m->cfg.embed_dim : nullptr, tap ? &mine : nullptr);
-    });
-}
-
-int ivit_vit_forward(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                     int32_t *logits) {
-    if (!m) return IVIT_ERR_INVALID;
-    return vit_run(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr);
-}
-
-// forward_features (include/ivit_features.h): every argument checked first, then the slices with the caller's feat8 as the final
-// norm's destination (and the head only with logits), then the fp32 form on the handle's stream, behind the slices' join
-int ivit_vit_features(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                      int8_t *feat8, float scale, int mode, float *feat32) {
-    if (!m) return IVIT_ERR_INVALID;
-    RUN(features_args_ok(m->h, __func__, feat8, m->cfg.embed_dim, scale, mode, feat32, true));
-    RUN(vit_run(m, __func__, images, batch, nslices, workspace, bytes, logits, feat8));
-    return feat32 ? ivit_features_f32(m->h, feat8, batch, m->cfg.embed_dim, scale, mode, feat32) : IVIT_OK;
-}
-
-int ivit_vit_features_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                                   int32_t *logits, int8_t *feat8, float scale, int mode, float *feat32, ivit_graph *out) {
-    if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] { return ivit_vit_features(m, images, batch, nslices, workspace, bytes, logits, feat8, scale, mode, feat32); });
-}
-
-// the class token's attention rows (include/ivit_attnmap.h): every argument checked first — the block list, the fp32 map's rules, the
-// five arrays pairwise (images / workspace / logits again in vit_run) —, then the slices with their taps, then the fp32 map on the
-// handle's stream, behind the slices' join
-int ivit_vit_attention(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                       const int *blocks_host, int nblocks, uint16_t *attn16, int mode, float *map32) {
-    if (!m) return IVIT_ERR_INVALID;
-    ivit_handle h = m->h;
-    const int H = m->cfg.num_heads, T = m->T;
-    REQUIRE(h, blocks_host && nblocks >= 1 && nblocks <= m->cfg.depth, "blocks_host is null or nblocks outside 1 .. depth");
-    for (int t = 0; t < nblocks; ++t)
-        REQUIRE(h, blocks_host[t] >= 0 && blocks_host[t] < m->cfg.depth && (t == 0 || blocks_host[t] > blocks_host[t - 1]),
-                "blocks_host must be strictly ascending block indices in [0, depth)");
-    RUN(attnmap_map_args_ok(h, __func__, attn16, "attn16", (long long)nblocks * std::max(batch, 0), H, T, mode, map32, "map32"));
-    if (size_t need = 0; batch > 0 && ivit_vit_workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
-        const size_t rows = (size_t)nblocks * batch;
-        const struct { const void *p; size_t n; const char *name; const char *msg; } a[5] = {
-            {images, (size_t)batch * m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size, "images", OVL_IN},
-            {workspace, need, "workspace", OVL_OUT},
-            {logits, (size_t)batch * m->cfg.num_classes * 4, "logits", OVL_OUT},
-            {attn16, rows * H * T * 2, "attn16", OVL_OUT},
-            {map32, attnmap_map_bytes((long long)rows, H, T, mode), "map32", OVL_OUT}};
-        for (int i = 0; i < 5; ++i)
-            for (int j = std::max(i + 1, 3); j < 5; ++j)        // the pairs among the first three are vit_run's
-                if (!ranges_disjoint(h, __func__, a[i].p, a[i].n, a[i].name, a[j].p, a[j].n, a[j].name, i == 0 ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
-    }
-    RUN(attnmap_shape_ok(h, __func__, T, m->cfg.embed_dim / H));
-    if (map32 && H > ATTNMAP_MAX_H) {
-        snprintf(h->err, sizeof(h->err), "%s: the fp32 map takes at most %d heads", __func__, ATTNMAP_MAX_H);
-        return IVIT_ERR_UNSUPPORTED;
-    }
-    const AttnTap tap = {blocks_host, nblocks, attn16, (size_t)std::max(batch, 0) * H * T};
-    RUN(vit_run(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr, &tap));
-    return map32 ? ivit_attention_map_f32(h, attn16, (int64_t)nblocks * batch, H, T, mode, map32) : IVIT_OK;
-}
-
-int ivit_vit_attention_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                                    const int *blocks_host, int nblocks, uint16_t *attn16, int mode, float *map32, ivit_graph *out) {
-    if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] {
-        return ivit_vit_attention(m, images, batch, nslices, workspace, bytes, logits, blocks_host, nblocks, attn16, mode, map32);
-    });
-}
-
-int ivit_vit_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                          int32_t *logits, ivit_graph *out) {
-    if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] { return ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits); });
-}
-
-// the forward, then the top-k of its logits on the handle's stream: behind the slices' join, so inside a capture it is one more node
-int ivit_vit_predict(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                     const float *head_scale, int k, int32_t *idx, float *val) {
-    if (!m) return IVIT_ERR_INVALID;
-    REQUIRE(m->h, head_scale && idx && k >= 1 && k <= TOPK_MAX_K && k <= m->cfg.num_classes, "head_scale / idx null or k outside 1 .. min(16, num_classes)");
-    if (size_t need = 0; batch > 0 && ivit_vit_workspace_bytes(m, batch, nslices, &need) == IVIT_OK)
-        RUN(predict_disjoint(m->h, __func__, images, (size_t)batch * m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size, workspace, need, logits,
-                             (size_t)batch * m->cfg.num_classes * 4, idx, val, (size_t)batch * k * 4));
-    RUN(ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits));
-    return ivit_logits_topk(m->h, logits, head_scale, batch, m->cfg.num_classes, k, idx, val);
-}
-
-int ivit_vit_predict_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                                  int32_t *logits, const float *head_scale, int k, int32_t *idx, float *val, ivit_graph *out) {
-    if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] { return ivit_vit_predict(m, images, batch, nslices, workspace, bytes, logits, head_scale, k, idx, val); });
-}
-
-// the forward, then rank and nll of the labels among its logits (include/ivit_eval.h): the same place behind the slices' join
-int ivit_vit_score(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                   const float *head_scale, const int64_t *labels, int32_t *rank, double *nll) {
-    if (!m) return IVIT_ERR_INVALID;
-    REQUIRE(m->h, head_scale && labels && (rank || nll), "head_scale / labels null, or rank and nll both null");
-    RUN(ivit_vit_forward(m, images, batch, nslices, workspace, bytes, logits));
-    return ivit_logits_score(m->h, logits, head_scale, labels, batch, m->cfg.num_classes, rank, nll);
-}
-
-int ivit_vit_score_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                                int32_t *logits, const float *head_scale, const int64_t *labels, int32_t *rank, double *nll,
-                                ivit_graph *out) {
-    if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] { return ivit_vit_score(m, images, batch, nslices, workspace, bytes, logits, head_scale, labels, rank, nll); });
-}
-
-int ivit_graph_launch(ivit_graph g) {
-    if (!g) return IVIT_ERR_INVALID;
-    hipError_t e = hipGraphLaunch(g->exec, g->h->stream);
-    if (e != hipSuccess) { snprintf(g->h->err, sizeof(g->h->err), "graph launch: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
-    return IVIT_OK;
-}
-
-int ivit_graph_destroy(ivit_graph g) {
-    if (!g) return IVIT_ERR_INVALID;
-    (void)hipGraphExecDestroy(g->exec);
-    (void)hipGraphDestroy(g->graph);
-    delete g;
-    return IVIT_OK;
-}
-
 }  // extern "C"
 
 // =====================================================================================================
 // Swin runner
 struct ivit_swin_s {
+    static constexpr const char *WS_ENTRY = "ivit_swin_workspace_bytes", *FWD_ENTRY = "ivit_swin_forward";
     ivit_handle h;
     ivit_swin_config cfg;
     ivit_swin_params prm;
@@ -774,6 +644,14 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
     return IVIT_OK;
 }
 
+// what run_slices asks of a model, as for the ViT.  A slice lays its buffers out for its own images; a Swin has no class token to tap
+inline size_t slice_stride(const ivit_swin_s *m, int Bmax) { return swin_layout(m, Bmax).total; }
+inline int num_features(const ivit_swin_s *m) { return m->cfg.embed_dim << (m->cfg.num_layers - 1); }
+inline int slice_run(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int /*b0*/, int nb, int /*Bmax*/, char *ws, int32_t *logits,
+                     int8_t *feat8, const AttnTap * /*tap*/) {
+    return swin_run_slice(m, h, images, nb, ws, logits, feat8);
+}
+
 }  // namespace
 
 extern "C" {
@@ -883,13 +761,6 @@ int ivit_swin_create(ivit_handle h, const ivit_swin_config *cfg, const ivit_swin
     return IVIT_OK;
 }
 
-int ivit_swin_workspace_bytes(ivit_swin m, int batch, int nslices, size_t *bytes) {
-    if (!m) return IVIT_ERR_INVALID;
-    REQUIRE(m->h, bytes && batch > 0 && nslices >= 1 && nslices <= m->max_slices && nslices <= batch, "bad arguments");
-    *bytes = swin_layout(m, max_slice(batch, nslices)).total * (size_t)nslices;
-    return IVIT_OK;
-}
-
 int ivit_swin_fused_mlp_blocks(ivit_swin m, int batch, int blocks_per_stage[4]) {
     if (!m) return IVIT_ERR_INVALID;
     REQUIRE(m->h, blocks_per_stage && batch > 0, "bad arguments");
@@ -904,85 +775,185 @@ int ivit_swin_fused_mlp_blocks(ivit_swin m, int batch, int blocks_per_stage[4]) 
     return IVIT_OK;
 }
 
-static inline int swin_num_features(const ivit_swin_s *m) { return m->cfg.embed_dim << (m->cfg.num_layers - 1); }
+}  // extern "C"
 
-// the slices of one batch: ivit_swin_forward (logits, no feat8) and ivit_swin_features (feat8, logits or none) end here
-static int swin_run(ivit_swin m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                    int8_t *feat8) {
+// =====================================================================================================
+// The runner entries, once for both models: M is ivit_vit_s or ivit_swin_s.  A body reads in_chans, img_size and num_classes from
+// m->cfg (both configurations spell them alike), the names in its refusals from `fn`, M::WS_ENTRY and M::FWD_ENTRY, and the rest
+// through slice_stride, num_features and slice_run
+namespace {
+
+template <class M>
+size_t image_bytes(const M *m) { return (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size; }
+template <class M>
+size_t logit_bytes(const M *m, int batch) { return (size_t)batch * m->cfg.num_classes * 4; }
+
+template <class M>
+int workspace_bytes(M *m, int batch, int nslices, size_t *bytes) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE_FN(m->h, M::WS_ENTRY, bytes && batch > 0 && nslices >= 1 && nslices <= m->max_slices && nslices <= batch, "bad arguments");
+    *bytes = slice_stride(m, max_slice(batch, nslices)) * (size_t)nslices;
+    return IVIT_OK;
+}
+
+// THE place a runner checks its arguments, and the order it does so in, before anything is launched: the workspace query, the
+// pointers and the workspace's size and alignment, the three arrays of every runner pairwise; then the slices of the batch.  forward
+// (logits, no feat8), features (feat8, logits or none) and ivit_vit_attention (a tap, logits or none) end here.  `tap`: the caller's
+// block list and attn16 as a whole; slice_run gives every slice its own rows of it
+template <class M>
+int run_slices(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+               int8_t *feat8, const AttnTap *tap = nullptr) {
     ivit_handle h = m->h;
     size_t need = 0;
-    int rc = ivit_swin_workspace_bytes(m, batch, nslices, &need);
-    if (rc != IVIT_OK) return rc;
-    REQUIRE_FN(h, fn, images && (logits || feat8) && workspace && bytes >= need, "bad arguments / workspace too small");
+    RUN(workspace_bytes(m, batch, nslices, &need));
+    REQUIRE_FN(h, fn, images && (logits || feat8 || tap) && workspace && bytes >= need, "bad arguments / workspace too small");
     REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    const size_t img_bytes = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
-    if (int st = runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, (size_t)batch * m->cfg.num_classes * 4)) return st;
-    const size_t stride = swin_layout(m, max_slice(batch, nslices)).total;
+    const size_t img_bytes = image_bytes(m);
+    RUN(runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, logit_bytes(m, batch)));
+    const int Bmax = max_slice(batch, nslices);
+    const size_t stride = slice_stride(m, Bmax);
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
-        return swin_run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, (char *)workspace + stride * (size_t)i,
-                              logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
-                              feat8 ? feat8 + (size_t)b0 * swin_num_features(m) : nullptr);
+        return slice_run(m, sh, images + (size_t)b0 * img_bytes, b0, nb, Bmax, (char *)workspace + stride * (size_t)i,
+                         logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
+                         feat8 ? feat8 + (size_t)b0 * num_features(m) : nullptr, tap);
     });
 }
 
-int ivit_swin_forward(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                      int32_t *logits) {
+template <class M>
+int runner_forward(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits) {
     if (!m) return IVIT_ERR_INVALID;
-    return swin_run(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr);
+    return run_slices(m, fn, images, batch, nslices, workspace, bytes, logits, nullptr);
 }
 
-// forward_features (include/ivit_features.h): as ivit_vit_features, with the pool's output in the caller's feat8
-int ivit_swin_features(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                       int8_t *feat8, float scale, int mode, float *feat32) {
+// the forward, then the top-k of its logits on the handle's stream: behind the slices' join, so inside a capture it is one more node
+template <class M>
+int runner_predict(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                   const float *head_scale, int k, int32_t *idx, float *val) {
     if (!m) return IVIT_ERR_INVALID;
-    RUN(features_args_ok(m->h, __func__, feat8, swin_num_features(m), scale, mode, feat32, true));
-    RUN(swin_run(m, __func__, images, batch, nslices, workspace, bytes, logits, feat8));
-    return feat32 ? ivit_features_f32(m->h, feat8, batch, swin_num_features(m), scale, mode, feat32) : IVIT_OK;
-}
-
-int ivit_swin_features_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                                    int32_t *logits, int8_t *feat8, float scale, int mode, float *feat32, ivit_graph *out) {
-    if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] { return ivit_swin_features(m, images, batch, nslices, workspace, bytes, logits, feat8, scale, mode, feat32); });
-}
-
-int ivit_swin_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                           int32_t *logits, ivit_graph *out) {
-    if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] { return ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits); });
-}
-
-int ivit_swin_predict(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                     const float *head_scale, int k, int32_t *idx, float *val) {
-    if (!m) return IVIT_ERR_INVALID;
-    REQUIRE(m->h, head_scale && idx && k >= 1 && k <= TOPK_MAX_K && k <= m->cfg.num_classes, "head_scale / idx null or k outside 1 .. min(16, num_classes)");
-    if (size_t need = 0; batch > 0 && ivit_swin_workspace_bytes(m, batch, nslices, &need) == IVIT_OK)
-        RUN(predict_disjoint(m->h, __func__, images, (size_t)batch * m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size, workspace, need, logits,
-                             (size_t)batch * m->cfg.num_classes * 4, idx, val, (size_t)batch * k * 4));
-    RUN(ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits));
+    REQUIRE_FN(m->h, fn, head_scale && idx && k >= 1 && k <= TOPK_MAX_K && k <= m->cfg.num_classes,
+               "head_scale / idx null or k outside 1 .. min(16, num_classes)");
+    if (size_t need = 0; batch > 0 && workspace_bytes(m, batch, nslices, &need) == IVIT_OK)
+        RUN(predict_disjoint(m->h, fn, images, image_bytes(m) * batch, workspace, need, logits, logit_bytes(m, batch), idx, val, (size_t)batch * k * 4));
+    RUN(runner_forward(m, M::FWD_ENTRY, images, batch, nslices, workspace, bytes, logits));
     return ivit_logits_topk(m->h, logits, head_scale, batch, m->cfg.num_classes, k, idx, val);
 }
 
-int ivit_swin_predict_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                                  int32_t *logits, const float *head_scale, int k, int32_t *idx, float *val, ivit_graph *out) {
-    if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] { return ivit_swin_predict(m, images, batch, nslices, workspace, bytes, logits, head_scale, k, idx, val); });
-}
-
 // the forward, then rank and nll of the labels among its logits (include/ivit_eval.h): the same place behind the slices' join
-int ivit_swin_score(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-                    const float *head_scale, const int64_t *labels, int32_t *rank, double *nll) {
+template <class M>
+int runner_score(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                 const float *head_scale, const int64_t *labels, int32_t *rank, double *nll) {
     if (!m) return IVIT_ERR_INVALID;
-    REQUIRE(m->h, head_scale && labels && (rank || nll), "head_scale / labels null, or rank and nll both null");
-    RUN(ivit_swin_forward(m, images, batch, nslices, workspace, bytes, logits));
+    REQUIRE_FN(m->h, fn, head_scale && labels && (rank || nll), "head_scale / labels null, or rank and nll both null");
+    RUN(runner_forward(m, M::FWD_ENTRY, images, batch, nslices, workspace, bytes, logits));
     return ivit_logits_score(m->h, logits, head_scale, labels, batch, m->cfg.num_classes, rank, nll);
 }
 
-int ivit_swin_score_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes,
-                                 int32_t *logits, const float *head_scale, const int64_t *labels, int32_t *rank, double *nll,
-                                 ivit_graph *out) {
+// forward_features (include/ivit_features.h): every argument checked first, then the slices with the caller's feat8 as the destination
+// of the final norm (ViT) or the pool (Swin) — and the head only with logits —, then the fp32 form on the handle's stream, behind the
+// slices' join
+template <class M>
+int runner_features(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                    int8_t *feat8, float scale, int mode, float *feat32) {
     if (!m) return IVIT_ERR_INVALID;
-    return graph_capture(m->h, out, [&] { return ivit_swin_score(m, images, batch, nslices, workspace, bytes, logits, head_scale, labels, rank, nll); });
+    RUN(features_args_ok(m->h, fn, feat8, num_features(m), scale, mode, feat32, true));
+    RUN(run_slices(m, fn, images, batch, nslices, workspace, bytes, logits, feat8));
+    return feat32 ? ivit_features_f32(m->h, feat8, batch, num_features(m), scale, mode, feat32) : IVIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// the nine runner entries of a model, written once and stamped for both: P is "ivit_vit" or "ivit_swin", the prefix of the entries and
+// the handle type alike.  Each is one call of its shared body under its own name; a *_graph_create form captures the eager entry
+#define RUNNER_ENTRIES(P) \
+    int P##_workspace_bytes(P m, int batch, int nslices, size_t *bytes) { return workspace_bytes(m, batch, nslices, bytes); } \
+    int P##_forward(P m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits) { \
+        return runner_forward(m, __func__, images, batch, nslices, workspace, bytes, logits); \
+    } \
+    int P##_graph_create(P m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits, ivit_graph *out) { \
+        return graph_capture(m, out, P##_forward, images, batch, nslices, workspace, bytes, logits); \
+    } \
+    int P##_predict(P m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits, \
+                    const float *head_scale, int k, int32_t *idx, float *val) { \
+        return runner_predict(m, __func__, images, batch, nslices, workspace, bytes, logits, head_scale, k, idx, val); \
+    } \
+    int P##_predict_graph_create(P m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits, \
+                                 const float *head_scale, int k, int32_t *idx, float *val, ivit_graph *out) { \
+        return graph_capture(m, out, P##_predict, images, batch, nslices, workspace, bytes, logits, head_scale, k, idx, val); \
+    } \
+    int P##_score(P m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits, \
+                  const float *head_scale, const int64_t *labels, int32_t *rank, double *nll) { \
+        return runner_score(m, __func__, images, batch, nslices, workspace, bytes, logits, head_scale, labels, rank, nll); \
+    } \
+    int P##_score_graph_create(P m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits, \
+                               const float *head_scale, const int64_t *labels, int32_t *rank, double *nll, ivit_graph *out) { \
+        return graph_capture(m, out, P##_score, images, batch, nslices, workspace, bytes, logits, head_scale, labels, rank, nll); \
+    } \
+    int P##_features(P m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits, int8_t *feat8, \
+                     float scale, int mode, float *feat32) { \
+        return runner_features(m, __func__, images, batch, nslices, workspace, bytes, logits, feat8, scale, mode, feat32); \
+    } \
+    int P##_features_graph_create(P m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits, \
+                                  int8_t *feat8, float scale, int mode, float *feat32, ivit_graph *out) { \
+        return graph_capture(m, out, P##_features, images, batch, nslices, workspace, bytes, logits, feat8, scale, mode, feat32); \
+    }
+RUNNER_ENTRIES(ivit_vit)
+RUNNER_ENTRIES(ivit_swin)
+#undef RUNNER_ENTRIES
+
+// the class token's attention rows (include/ivit_attnmap.h), ViT only: every argument checked first — the block list, the fp32 map's
+// rules, the five arrays pairwise (images / workspace / logits again in run_slices) —, then the slices with their taps, then the fp32 map
+// on the handle's stream, behind the slices' join
+int ivit_vit_attention(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                       const int *blocks_host, int nblocks, uint16_t *attn16, int mode, float *map32) {
+    if (!m) return IVIT_ERR_INVALID;
+    ivit_handle h = m->h;
+    const int H = m->cfg.num_heads, T = m->T;
+    REQUIRE(h, blocks_host && nblocks >= 1 && nblocks <= m->cfg.depth, "blocks_host is null or nblocks outside 1 .. depth");
+    for (int t = 0; t < nblocks; ++t)
+        REQUIRE(h, blocks_host[t] >= 0 && blocks_host[t] < m->cfg.depth && (t == 0 || blocks_host[t] > blocks_host[t - 1]),
+                "blocks_host must be strictly ascending block indices in [0, depth)");
+    RUN(attnmap_map_args_ok(h, __func__, attn16, "attn16", (long long)nblocks * std::max(batch, 0), H, T, mode, map32, "map32"));
+    if (size_t need = 0; batch > 0 && workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
+        const size_t rows = (size_t)nblocks * batch;
+        const struct { const void *p; size_t n; const char *name; } a[5] = {
+            {images, image_bytes(m) * batch, "images"},
+            {workspace, need, "workspace"},
+            {logits, logit_bytes(m, batch), "logits"},
+            {attn16, rows * H * T * 2, "attn16"},
+            {map32, attnmap_map_bytes((long long)rows, H, T, mode), "map32"}};
+        for (int i = 0; i < 5; ++i)
+            for (int j = std::max(i + 1, 3); j < 5; ++j)        // the pairs among the first three are run_slices'
+                if (!ranges_disjoint(h, __func__, a[i].p, a[i].n, a[i].name, a[j].p, a[j].n, a[j].name, i == 0 ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
+    }
+    RUN(attnmap_shape_ok(h, __func__, T, m->cfg.embed_dim / H));
+    if (map32 && H > ATTNMAP_MAX_H) {
+        snprintf(h->err, sizeof(h->err), "%s: the fp32 map takes at most %d heads", __func__, ATTNMAP_MAX_H);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    const AttnTap tap = {blocks_host, nblocks, attn16, (size_t)std::max(batch, 0) * H * T};
+    RUN(run_slices(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr, &tap));
+    return map32 ? ivit_attention_map_f32(h, attn16, (int64_t)nblocks * batch, H, T, mode, map32) : IVIT_OK;
+}
+int ivit_vit_attention_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                                    const int *blocks_host, int nblocks, uint16_t *attn16, int mode, float *map32, ivit_graph *out) {
+    return graph_capture(m, out, ivit_vit_attention, images, batch, nslices, workspace, bytes, logits, blocks_host, nblocks, attn16, mode, map32);
+}
+
+int ivit_graph_launch(ivit_graph g) {
+    if (!g) return IVIT_ERR_INVALID;
+    hipError_t e = hipGraphLaunch(g->exec, g->h->stream);
+    if (e != hipSuccess) { snprintf(g->h->err, sizeof(g->h->err), "graph launch: %s", hipGetErrorString(e)); return IVIT_ERR_HIP; }
+    return IVIT_OK;
+}
+
+int ivit_graph_destroy(ivit_graph g) {
+    if (!g) return IVIT_ERR_INVALID;
+    (void)hipGraphExecDestroy(g->exec);
+    (void)hipGraphDestroy(g->graph);
+    delete g;
+    return IVIT_OK;
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from .freeze import freeze_vit
-from .native import NativeEngine
+from .native import NativeEngine, SideOutputs
 
 _P = ctypes.c_void_p
 
@@ -115,7 +115,7 @@ class ViTEngine(NativeEngine):
         # scalar dyadics are passed by value: keep host copies
         self.host = host_scalars(blob if isinstance(blob, np.ndarray) else self.blob.cpu().numpy(), table)
         self._ws = {}
-        self._attention_out = {}
+        self._attention_out = SideOutputs(self._native_ws)
         self.fused_attention = (cfg.head_dim == 64 and cfg.num_tokens <= 640)
         self.use_exp_tables = True      # forward_ops only: False issues the arithmetic Shiftmax (cross-check)
         # per-layer ShiftGELU(+requant) tables, built on-device by the faithful kernel code
@@ -235,22 +235,16 @@ class ViTEngine(NativeEngine):
 
     def _attention_args(self, images, blocks, heads, logits, nslices):
         """(arguments of the attention entries, cache key, buffers, what the caller gets) for one batch: attn16 and map32 live beside the
-        logits buffer and follow its rule (_predict_buffers), one set per (batch, slices, blocks, heads)"""
+        logits buffer and follow its rule (native.SideOutputs), one set per (batch, slices, blocks, heads)"""
         blocks = self._attention_blocks(blocks)
         args, key, (ws, lg) = self._args(images, nslices)
         cfg, n, B = self.cfg, len(blocks), images.shape[0]
         H, T, g = cfg.num_heads, cfg.num_tokens, cfg.img_size // cfg.patch_size
         assert T == g * g + 1, "one class token in front of a square grid of patches"
         okey = key + (blocks, bool(heads))
-        outs = self._attention_out
-        hit = outs.get(okey)
-        if hit is None or hit[0] is not lg:
-            for old in [q for q, v in outs.items() if not v[4] and q[:2] not in self._native_ws]:
-                del outs[old]
-            hit = outs[okey] = [lg, torch.empty(n, B, H, T, dtype=torch.uint16, device=self.device),
-                                torch.empty((n, B, H, T - 1) if heads else (n, B, T - 1), dtype=torch.float32, device=self.device),
-                                (ctypes.c_int * n)(*blocks), False]
-        _, attn16, map32, blocks_host, _ = hit
+        attn16, map32, blocks_host = self._attention_out.get(okey, lg, lambda: (
+            self._empty(torch.uint16, n, B, H, T), self._empty(torch.float32, *((n, B, H, T - 1) if heads else (n, B, T - 1))),
+            (ctypes.c_int * n)(*blocks)))
         mode = _lib.IVIT_ATTNMAP_HEADS if heads else _lib.IVIT_ATTNMAP_MEAN
         args = args[:-1] + (_P(lg.data_ptr()) if logits else None, blocks_host, n, _P(attn16.data_ptr()), mode, _P(map32.data_ptr()))
         maps = map32.view(n, B, H, g, g) if heads else map32.view(n, B, g, g)
@@ -266,21 +260,16 @@ class ViTEngine(NativeEngine):
         and one for the maps.  Without `logits` the forward ends behind the last tapped block; with it the int32 logits are
         forward's (and `last_logits`).  The results are the engine's own buffers for this (batch, nslices, blocks, heads):
         copy=True (or clone) to keep them across calls."""
-        self._use_current_stream()
-        self._check_images(images)
-        args, _, bufs, out = self._attention_args(images, blocks, heads, logits, nslices)
-        self._entry("_attention", *args)
-        if logits:
-            self.last_logits = bufs[1]
-        return tuple(t.clone() for t in out) if copy else out
+        def plan():
+            args, _, bufs, out = self._attention_args(images, blocks, heads, logits, nslices)
+            return args, bufs[1] if logits else None, out
+        return self._eager("_attention", images, copy, plan)
 
     def capture_attention(self, images, blocks=-1, heads=False, logits=False, nstreams=1):
         """hipGraph of one attention on fixed buffers; returns a callable that replays it and returns what `attention` returns."""
         self._check_images(images)
         args, okey, bufs, out = self._attention_args(images, blocks, heads, logits, nstreams)
-        replay = self._capture("_attention_graph_create", images, args, okey, bufs, out)
-        self._attention_out[okey][4] = True
-        return replay
+        return self._capture("_attention_graph_create", images, args, okey, bufs, out, self._attention_out)
 
     def workspace(self, B, key=None):
         wkey = (B, key)

@@ -5,7 +5,9 @@ The base owns the device and handle, the constants blob, the workspace cache and
 with the top-k of the dequantised logits behind them, ivit_<model>_predict), `score` / `capture_score` (with the labels' rank and
 negative log-likelihood behind them instead, ivit_<model>_score of include/ivit_eval.h) and `features` / `capture_features` (the
 reference's forward_features: the integers the head reads and their fp32 form, with or without the head, ivit_<model>_features of
-include/ivit_features.h).  A subclass names its C prefix, builds its parameter structs (`_native_params`), says where its feature
+include/ivit_features.h).  Every eager way is its arguments and one `_eager` call, every captured way its arguments and one
+`_capture` call; what lives beside a logits buffer (idx / val, rank / nll, feat8 / feat32, a ViT's attn16 / map32) follows the one
+rule of `SideOutputs`.  A subclass names its C prefix, builds its parameter structs (`_native_params`), says where its feature
 scale lies (`feature_scale_host`, `num_features`) and keeps its `forward_ops`.  torch is used for device memory and streams only.
 """
 import ctypes
@@ -48,6 +50,28 @@ class ShapeCache:
         return self.items[key]
 
 
+class SideOutputs:
+    """key -> make(), for outputs that live beside a logits buffer of the workspace cache `ws`; key[:2] is that buffer's (batch,
+    nslices).  THE rule of every side output: the engine's own, overwritten by the next call of the same key; built again when the
+    key is new or its logits buffer is no longer this one (the shape was evicted and rebuilt); before a build every entry that is not
+    pinned and whose (batch, nslices) has left `ws` is dropped; a pinned key — a captured graph refers to its tensors — never is."""
+
+    def __init__(self, ws):
+        self.ws = ws
+        self.items, self.pinned = {}, set()
+
+    def pin(self, key):
+        self.pinned.add(key)
+
+    def get(self, key, logits, make):
+        hit = self.items.get(key)
+        if hit is None or hit[0] is not logits:
+            for old in [q for q in self.items if q not in self.pinned and q[:2] not in self.ws]:
+                del self.items[old]
+            hit = self.items[key] = (logits, make())
+        return hit[1]
+
+
 class NativeEngine:
     # "ivit_vit" / "ivit_swin": the entries are PREFIX + _create, _destroy, _workspace_bytes, _forward, _graph_create, _predict,
     # _predict_graph_create, _score, _score_graph_create, _features and _features_graph_create
@@ -66,9 +90,8 @@ class NativeEngine:
         self._native_ws = ShapeCache(self._make_buffers)
         self._graph_keys = self._native_ws.pinned
         self._graphs = []
-        self._predict_out = {}
-        self._score_out = {}
-        self._features_out = {}
+        # (idx, val) per (batch, slices, k); (rank, nll) and (feat8, feat32) per (batch, slices): one SideOutputs per kind
+        self._predict_out, self._score_out, self._features_out = (SideOutputs(self._native_ws) for _ in range(3))
         self._gstream = None                    # the stream graphs are captured and replayed on, made by the first capture
         self._head_scale_host = None
         self.last_logits = None
@@ -130,28 +153,8 @@ class NativeEngine:
         """(workspace, logits) of one (batch, slices), the engine's own: see ShapeCache"""
         return self._native_ws.get((B, nslices))
 
-    def _predict_buffers(self, logits, key):
-        """(idx, val) of one (batch, slices, k): they live beside the logits buffer and follow its rule — the engine's own,
-        overwritten by the next call of the same shape, pinned while a captured graph refers to them"""
-        outs = self._predict_out
-        hit = outs.get(key)
-        if hit is None or hit[0] is not logits:          # first use, or the logits buffer of this shape was evicted and rebuilt
-            for old in [q for q, v in outs.items() if not v[3] and q[:2] not in self._native_ws]:
-                del outs[old]
-            hit = outs[key] = [logits, torch.empty(key[0], key[2], dtype=torch.int32, device=self.device),
-                               torch.empty(key[0], key[2], dtype=torch.float32, device=self.device), False]
-        return hit[1], hit[2]
-
-    def _score_buffers(self, logits, key):
-        """(rank, nll) of one (batch, slices): the rule of _predict_buffers"""
-        outs = self._score_out
-        hit = outs.get(key)
-        if hit is None or hit[0] is not logits:
-            for old in [q for q, v in outs.items() if not v[3] and q not in self._native_ws]:
-                del outs[old]
-            hit = outs[key] = [logits, torch.empty(key[0], dtype=torch.int32, device=self.device),
-                               torch.empty(key[0], dtype=torch.float64, device=self.device), False]
-        return hit[1], hit[2]
+    def _empty(self, dtype, *shape):
+        return torch.empty(*shape, dtype=dtype, device=self.device)
 
     def _check_labels(self, labels, B):
         assert isinstance(labels, torch.Tensor) and labels.dtype == torch.int64 and labels.device == self.device, "labels: int64 device tensor"
@@ -159,9 +162,10 @@ class NativeEngine:
 
     def _score_args(self, images, labels, nslices):
         """(arguments of the score entries, cache key, buffers) for one batch and its labels"""
-        self._check_labels(labels, images.shape[0])
+        B = images.shape[0]
+        self._check_labels(labels, B)
         args, key, (ws, logits) = self._args(images, nslices)
-        rank, nll = self._score_buffers(logits, key)
+        rank, nll = self._score_out.get(key, logits, lambda: (self._empty(torch.int32, B), self._empty(torch.float64, B)))
         return args + (self.ptr("head.scale"), _ptr(labels), _ptr(rank), _ptr(nll)), key, (ws, logits, rank, nll)
 
     @property
@@ -173,21 +177,11 @@ class NativeEngine:
         """host float: the scale of the features' integers (the reference's qact2 of a ViT, qact3 of a Swin)"""
         raise NotImplementedError
 
-    def _features_buffers(self, logits, key):
-        """(feat8, feat32) of one (batch, slices): the rule of _predict_buffers"""
-        outs = self._features_out
-        hit = outs.get(key)
-        if hit is None or hit[0] is not logits:
-            for old in [q for q, v in outs.items() if not v[3] and q not in self._native_ws]:
-                del outs[old]
-            hit = outs[key] = [logits, torch.empty(key[0], self.num_features, dtype=torch.int8, device=self.device),
-                               torch.empty(key[0], self.num_features, dtype=torch.float32, device=self.device), False]
-        return hit[1], hit[2]
-
     def _features_args(self, images, normalize, logits, nslices):
         """(arguments of the features entries, cache key, buffers) for one batch; without `logits` the head's pointer is NULL"""
         args, key, (ws, lg) = self._args(images, nslices)
-        feat8, feat32 = self._features_buffers(lg, key)
+        shape = (images.shape[0], self.num_features)
+        feat8, feat32 = self._features_out.get(key, lg, lambda: (self._empty(torch.int8, *shape), self._empty(torch.float32, *shape)))
         mode = _lib.IVIT_FEATURES_UNIT if normalize else _lib.IVIT_FEATURES_DEQUANT
         return (args[:-1] + (_ptr(lg) if logits else None, _ptr(feat8), float(self.feature_scale_host()), mode, _ptr(feat32)), key,
                 (ws, lg, feat8, feat32))
@@ -206,8 +200,21 @@ class NativeEngine:
         args = (self.model, _ptr(images), B, nslices, _ptr(ws), ws.numel(), _ptr(logits))
         if k is None:
             return args, (B, nslices), bufs
-        idx, val = self._predict_buffers(logits, (B, nslices, int(k)))
-        return args + (self.ptr("head.scale"), int(k), _ptr(idx), _ptr(val)), (B, nslices, int(k)), bufs + (idx, val)
+        key = (B, nslices, int(k))
+        idx, val = self._predict_out.get(key, logits, lambda: (self._empty(torch.int32, B, key[2]), self._empty(torch.float32, B, key[2])))
+        return args + (self.ptr("head.scale"), key[2], _ptr(idx), _ptr(val)), key, bufs + (idx, val)
+
+    def _eager(self, suffix, images, copy, plan):
+        """one call of the entry PREFIX + suffix on the current stream.  `plan()` — an `_args` kind, asked once the stream is set: a
+        fresh workspace is initialised on it — gives (C arguments, the logits buffer if the caller is to find it in `last_logits`
+        or None, results); returns the results, cloned with `copy`"""
+        self._use_current_stream()
+        self._check_images(images)
+        args, logits, out = plan()
+        self._entry(suffix, *args)
+        if logits is not None:
+            self.last_logits = logits
+        return tuple(t.clone() for t in out) if copy else out
 
     def forward(self, images, nslices=1, copy=False):
         """images: int8 device tensor [B, C, H, W] (already quantised, scale s_in) -> int32 logits
@@ -218,11 +225,10 @@ class NativeEngine:
         The returned tensor is the engine's OWN output buffer for this (batch, nslices): the next forward /
         graph replay of the same shape overwrites it (nothing is allocated per call).  Pass copy=True — or
         clone it — when results of several batches are kept (an eval loop collecting logits)."""
-        self._check_images(images)
-        self._use_current_stream()
-        args, _, (_, logits) = self._args(images, nslices)
-        self._entry("_forward", *args)
-        return logits.clone() if copy else logits
+        def plan():
+            args, _, (_, logits) = self._args(images, nslices)
+            return args, None, (logits,)
+        return self._eager("_forward", images, copy, plan)[0]
 
     def predict(self, images, k=5, nslices=1, copy=False):
         """images int8 [B, C, H, W] -> (idx int32 [B, k], val float32 [B, k]) device tensors: the k best classes of every image in
@@ -230,12 +236,10 @@ class NativeEngine:
         launch behind the slices' join); the head scale is read where it lies in the constants blob.  The int32 logits of the same
         call are in `last_logits`.  Like forward(), the results are the engine's own buffers for this (batch, nslices, k):
         copy=True (or clone) to keep them across calls.  1 <= k <= min(16, num_classes)."""
-        self._use_current_stream()
-        self._check_images(images)
-        args, _, (_, logits, idx, val) = self._args(images, nslices, k)
-        self._entry("_predict", *args)
-        self.last_logits = logits
-        return (idx.clone(), val.clone()) if copy else (idx, val)
+        def plan():
+            args, _, (_, logits, idx, val) = self._args(images, nslices, k)
+            return args, logits, (idx, val)
+        return self._eager("_predict", images, copy, plan)
 
     def score(self, images, labels, nslices=1, copy=False):
         """images int8 [B, C, H, W], labels int64 device tensor [B] -> (rank int32 [B], nll float64 [B]) device tensors: per image
@@ -243,12 +247,10 @@ class NativeEngine:
         cross-entropy of the label, as `predict.score_reference` states them.  One native call (the forward, then the score
         launch behind the slices' join); `last_logits` holds the int32 logits of the same call.  The results are the engine's own
         buffers for this (batch, nslices): copy=True (or clone) to keep them across calls."""
-        self._use_current_stream()
-        self._check_images(images)
-        args, _, (_, logits, rank, nll) = self._score_args(images, labels, nslices)
-        self._entry("_score", *args)
-        self.last_logits = logits
-        return (rank.clone(), nll.clone()) if copy else (rank, nll)
+        def plan():
+            args, _, (_, logits, rank, nll) = self._score_args(images, labels, nslices)
+            return args, logits, (rank, nll)
+        return self._eager("_score", images, copy, plan)
 
     def features(self, images, normalize=False, logits=False, nslices=1, copy=False):
         """images int8 [B, C, H, W] -> (feat8 int8 [B, num_features], feat32 float32 [B, num_features]) device tensors, or
@@ -258,18 +260,14 @@ class NativeEngine:
         normalize=True the rows at unit Euclidean length.  One native call; without `logits` the head GEMM is not launched, with
         it the int32 logits are forward's (and `last_logits`).  The results are the engine's own buffers for this (batch,
         nslices): copy=True (or clone) to keep them across calls."""
-        self._use_current_stream()
-        self._check_images(images)
-        args, _, (_, lg, feat8, feat32) = self._features_args(images, normalize, logits, nslices)
-        self._entry("_features", *args)
-        out = (feat8, feat32)
-        if logits:
-            self.last_logits = lg
-            out += (lg,)
-        return tuple(t.clone() for t in out) if copy else out
+        def plan():
+            args, _, (_, lg, feat8, feat32) = self._features_args(images, normalize, logits, nslices)
+            return args, lg if logits else None, (feat8, feat32) + ((lg,) if logits else ())
+        return self._eager("_features", images, copy, plan)
 
-    def _capture(self, suffix, images, args, key, bufs, out):
-        """hipGraph of the entry PREFIX + suffix on fixed buffers; returns a callable that replays it and returns `out`"""
+    def _capture(self, suffix, images, args, key, bufs, out, side=None):
+        """hipGraph of the entry PREFIX + suffix on fixed buffers; returns a callable that replays it and returns `out`.  `side`:
+        the SideOutputs that `key` is then pinned in"""
         if self._gstream is None:
             self._gstream = torch.cuda.Stream(self.device)
         torch.cuda.synchronize(self.device)
@@ -277,9 +275,11 @@ class NativeEngine:
         g = _P()
         self._entry(suffix, *args, ctypes.byref(g))
         # the graph replays on its buffers and on `images`: all live as long as the replay closure does, and the workspace
-        # entry is pinned against eviction
+        # entry — with it the side outputs' — is pinned against eviction
         self._graphs.append((g,) + bufs + (images,))
         self._native_ws.pin(key[:2])
+        if side is not None:
+            side.pin(key)
         lib, gs, dev = self.h.lib, self._gstream, self.device
 
         def replay(_keep=bufs + (images,)):
@@ -301,23 +301,19 @@ class NativeEngine:
         """hipGraph of one predict on fixed buffers; returns a callable that replays it and returns (idx, val)."""
         self._check_images(images)
         args, key, bufs = self._args(images, nstreams, k)
-        replay = self._capture("_predict_graph_create", images, args, key, bufs, bufs[2:])
-        self._predict_out[key][3] = True
-        return replay
+        return self._capture("_predict_graph_create", images, args, key, bufs, bufs[2:], self._predict_out)
 
     def capture_score(self, images, labels, nstreams=1):
         """hipGraph of one score on fixed buffers; returns a callable that replays it and returns (rank, nll).  A replay reads
         `images` and `labels` as they are then: both live as long as the callable does."""
         self._check_images(images)
         args, key, bufs = self._score_args(images, labels, nstreams)
-        replay = self._capture("_score_graph_create", images, args, key, bufs + (labels,), bufs[2:4])
-        self._score_out[key][3] = True
-        return replay
+        return self._capture("_score_graph_create", images, args, key, bufs + (labels,), bufs[2:4], self._score_out)
 
     def capture_features(self, images, normalize=False, logits=False, nstreams=1):
         """hipGraph of one features on fixed buffers; returns a callable that replays it and returns what `features` returns."""
         self._check_images(images)
         args, key, bufs = self._features_args(images, normalize, logits, nstreams)
-        replay = self._capture("_features_graph_create", images, args, key, bufs, bufs[2:4] + ((bufs[1],) if logits else ()))
-        self._features_out[key][3] = True
-        return replay
+        return self._capture("_features_graph_create", images, args, key, bufs, bufs[2:4] + ((bufs[1],) if logits else ()),
+                             self._features_out)
+
