@@ -1,4 +1,4 @@
-// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h) over the gfx950 kernels.
+// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -32,6 +32,7 @@
 #include "ivit_score.h"
 #include "ivit_features.h"
 #include "ivit_attnmap.h"
+#include "ivit_classmap.h"
 #include "ivit_preprocess.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
@@ -2211,6 +2212,48 @@ extern "C" int ivit_attention_map_f32(ivit_handle h, const uint16_t *p_cls, int6
     const unsigned grid = (unsigned)((total + 255) / 256);
     if (mode == IVIT_ATTNMAP_MEAN) attn_map_f32_kernel<true><<<grid, 256, 0, h->stream>>>(p_cls, (long long)rows, H, T, out);
     else attn_map_f32_kernel<false><<<grid, 256, 0, h->stream>>>(p_cls, (long long)rows, H, T, out);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- class-activation maps of a Swin (include/ivit_classmap.h)
+// the argument rules of ivit_class_map (ivit_model.h asks here for its model and the caller's arrays, before its slices are launched):
+// pointers, counts, alignment, the five overlapping pairs, then the width
+static int classmap_args_ok(ivit_handle h, const char *fn, const int8_t *tok8, const int8_t *head_w, const int32_t *idx, int batch, int L, int C,
+                            int num_classes, int k, const float *class_scale, const int32_t *cam32, const float *map32) {
+    const char *bad = nullptr;
+    if (!tok8 || !head_w || !idx || !cam32) bad = "tok8, head_w, idx or cam32 is null";
+    else if (batch < 1 || L < 1 || C < 1 || num_classes < 1) bad = "batch, L, C or num_classes is not positive";
+    else if (k < 1 || k > CLASSMAP_MAX_K) bad = "k must be in 1 .. 16";
+    else if (!class_scale != !map32) bad = "class_scale and map32 must both be null or both be set";
+    else if ((uintptr_t)tok8 & 15) bad = "tok8 must be 16-byte aligned";
+    else if ((uintptr_t)head_w & 15) bad = "head_w must be 16-byte aligned";
+    else if ((uintptr_t)idx & 3) bad = "idx must be 4-byte aligned";
+    else if ((uintptr_t)class_scale & 3) bad = "class_scale must be 4-byte aligned";
+    else if ((uintptr_t)cam32 & 3) bad = "cam32 must be 4-byte aligned";
+    else if ((uintptr_t)map32 & 3) bad = "map32 must be 4-byte aligned";
+    else if ((long long)batch * k > 0x7fffffffLL) bad = "batch * k does not fit an int";
+    if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    const size_t ntok = (size_t)batch * L * C, nidx = (size_t)batch * k * 4, nmap = (size_t)batch * k * L * 4;
+    if (!ranges_disjoint(h, fn, tok8, ntok, "tok8", cam32, nmap, "cam32", OVL_IN) || !ranges_disjoint(h, fn, tok8, ntok, "tok8", map32, nmap, "map32", OVL_IN) ||
+        !ranges_disjoint(h, fn, idx, nidx, "idx", cam32, nmap, "cam32", OVL_IN) || !ranges_disjoint(h, fn, idx, nidx, "idx", map32, nmap, "map32", OVL_IN) ||
+        !ranges_disjoint(h, fn, cam32, nmap, "cam32", map32, nmap, "map32", OVL_OUT))
+        return IVIT_ERR_INVALID;
+    if ((C % 16) != 0 || C > CLASSMAP_MAX_C) {
+        snprintf(h->err, sizeof(h->err), "%s: C must be a multiple of 16 and at most %d", fn, CLASSMAP_MAX_C);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return IVIT_OK;
+}
+
+extern "C" int ivit_class_map(ivit_handle h, const int8_t *tok8, const int8_t *head_w, const int32_t *idx, int batch, int L, int C, int num_classes,
+                              int k, const float *class_scale, int32_t *cam32, float *map32) {
+    CHECK_H(h);
+    if (const int rc = classmap_args_ok(h, __func__, tok8, head_w, idx, batch, L, C, num_classes, k, class_scale, cam32, map32)) return rc;
+    const int BK = batch * k;
+    const unsigned grid = (unsigned)((BK + 3ll) / 4);            // one wavefront per (image, class slot)
+    if (map32) class_map_kernel<true><<<grid, 256, 0, h->stream>>>(tok8, head_w, idx, class_scale, cam32, map32, BK, k, L, C, num_classes);
+    else class_map_kernel<false><<<grid, 256, 0, h->stream>>>(tok8, head_w, idx, nullptr, cam32, nullptr, BK, k, L, C, num_classes);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

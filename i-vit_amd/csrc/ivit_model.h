@@ -347,7 +347,7 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
 inline size_t slice_stride(const ivit_vit_s *m, int Bmax) { return slice_layout(m, Bmax).total; }
 inline int num_features(const ivit_vit_s *m) { return m->cfg.embed_dim; }
 int slice_run(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int b0, int nb, int Bmax, char *ws, int32_t *logits, int8_t *feat8,
-              const AttnTap *tap) {
+              const AttnTap *tap, int8_t * /*tok8: a Swin's*/) {
     AttnTap mine;
     if (tap) { mine = *tap; mine.attn16 += (size_t)b0 * m->cfg.num_heads * m->T; }
     return run_slice(m, h, images, nb, Bmax, ws, logits, feat8, tap ? &mine : nullptr);
@@ -559,7 +559,9 @@ int swin_mlp_mode(const ivit_swin_s *m, int bi, int C, long long M) {
 
 // `feat8`: the slice's rows of the caller's features [B, C] (include/ivit_features.h), where the pool writes instead of the
 // workspace, or null; `logits`: null ends the slice in front of the head
-int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, char *ws, int32_t *logits, int8_t *feat8) {
+// `tok8`: the slice's rows of the caller's final-stage tokens [B, L, C] (include/ivit_classmap.h), where the final norm writes instead
+// of the workspace and the pool reads, or null; without logits and without feat8 the slice ends behind the final norm
+int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, char *ws, int32_t *logits, int8_t *feat8, int8_t *tok8) {
     const ivit_swin_config &c = m->cfg;
     const ivit_swin_params &P = m->prm;
     const SwinLayout Lw = swin_layout(m, B);
@@ -637,19 +639,23 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
         }
     }
     const int C = E << (c.num_layers - 1);
+    if (tok8) a8 = tok8;
     RUN(swin_ln(m, h, x, M, C, P.s_norm_in, P.n, L, false, a8));
+    if (!logits && !feat8) return IVIT_OK;
     RUN((L & 1) ? ivit_avgpool_requant(h, a8, B, L, C, P.dy_pool, pool)
                 : ivit_avgpool_requant_scaled(h, a8, B, L, C, P.s_pool, P.dy_pool, pool));
     if (logits) RUN(ivit_linear_i8(h, pool, P.head_w, P.head_b, logits, B, c.num_classes, C));
     return IVIT_OK;
 }
 
-// what run_slices asks of a model, as for the ViT.  A slice lays its buffers out for its own images; a Swin has no class token to tap
+// what run_slices asks of a model, as for the ViT.  A slice lays its buffers out for its own images; a Swin has no class token to tap,
+// and gives every slice its own rows of the caller's final-stage tokens instead
 inline size_t slice_stride(const ivit_swin_s *m, int Bmax) { return swin_layout(m, Bmax).total; }
 inline int num_features(const ivit_swin_s *m) { return m->cfg.embed_dim << (m->cfg.num_layers - 1); }
-inline int slice_run(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int /*b0*/, int nb, int /*Bmax*/, char *ws, int32_t *logits,
-                     int8_t *feat8, const AttnTap * /*tap*/) {
-    return swin_run_slice(m, h, images, nb, ws, logits, feat8);
+inline int final_tokens(const ivit_swin_s *m) { const int r = m->grid >> (m->cfg.num_layers - 1); return r * r; }
+inline int slice_run(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int b0, int nb, int /*Bmax*/, char *ws, int32_t *logits,
+                     int8_t *feat8, const AttnTap * /*tap*/, int8_t *tok8) {
+    return swin_run_slice(m, h, images, nb, ws, logits, feat8, tok8 ? tok8 + (size_t)b0 * final_tokens(m) * num_features(m) : nullptr);
 }
 
 }  // namespace
@@ -799,14 +805,15 @@ int workspace_bytes(M *m, int batch, int nslices, size_t *bytes) {
 // THE place a runner checks its arguments, and the order it does so in, before anything is launched: the workspace query, the
 // pointers and the workspace's size and alignment, the three arrays of every runner pairwise; then the slices of the batch.  forward
 // (logits, no feat8), features (feat8, logits or none) and ivit_vit_attention (a tap, logits or none) end here.  `tap`: the caller's
-// block list and attn16 as a whole; slice_run gives every slice its own rows of it
+// block list and attn16 as a whole; slice_run gives every slice its own rows of it.  `tok8`: a Swin's final-stage tokens as a whole
+// (ivit_swin_class_map, logits or none), likewise
 template <class M>
 int run_slices(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-               int8_t *feat8, const AttnTap *tap = nullptr) {
+               int8_t *feat8, const AttnTap *tap = nullptr, int8_t *tok8 = nullptr) {
     ivit_handle h = m->h;
     size_t need = 0;
     RUN(workspace_bytes(m, batch, nslices, &need));
-    REQUIRE_FN(h, fn, images && (logits || feat8 || tap) && workspace && bytes >= need, "bad arguments / workspace too small");
+    REQUIRE_FN(h, fn, images && (logits || feat8 || tap || tok8) && workspace && bytes >= need, "bad arguments / workspace too small");
     REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = image_bytes(m);
     RUN(runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, logit_bytes(m, batch)));
@@ -815,7 +822,7 @@ int run_slices(M *m, const char *fn, const int8_t *images, int batch, int nslice
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
         return slice_run(m, sh, images + (size_t)b0 * img_bytes, b0, nb, Bmax, (char *)workspace + stride * (size_t)i,
                          logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
-                         feat8 ? feat8 + (size_t)b0 * num_features(m) : nullptr, tap);
+                         feat8 ? feat8 + (size_t)b0 * num_features(m) : nullptr, tap, tok8);
     });
 }
 
@@ -939,6 +946,48 @@ int ivit_vit_attention(ivit_vit m, const int8_t *images, int batch, int nslices,
 int ivit_vit_attention_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
                                     const int *blocks_host, int nblocks, uint16_t *attn16, int mode, float *map32, ivit_graph *out) {
     return graph_capture(m, out, ivit_vit_attention, images, batch, nslices, workspace, bytes, logits, blocks_host, nblocks, attn16, mode, map32);
+}
+
+// class-activation maps (include/ivit_classmap.h), Swin only: every argument checked first — the mode and what it requires, the rules
+// of ivit_class_map for the model's head and the caller's arrays, the eight arrays pairwise (images / workspace / logits again in
+// run_slices) —, then the slices with the caller's tok8 as the destination of the final norm, then on the handle's stream, behind
+// the slices' join, the top-k of the logits (TOPK mode) and the one launch of the maps
+int ivit_swin_class_map(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                        const float *head_scale, int mode, int k, int32_t *idx, float *val, int8_t *tok8, const float *class_scale,
+                        int32_t *cam32, float *map32) {
+    if (!m) return IVIT_ERR_INVALID;
+    ivit_handle h = m->h;
+    const int L = final_tokens(m), C = num_features(m), ncls = m->cfg.num_classes;
+    REQUIRE(h, mode == IVIT_CLASSMAP_TOPK || mode == IVIT_CLASSMAP_GIVEN, "mode must be IVIT_CLASSMAP_TOPK or IVIT_CLASSMAP_GIVEN");
+    const bool given = mode == IVIT_CLASSMAP_GIVEN;
+    if (given) REQUIRE(h, !val, "val must be null in IVIT_CLASSMAP_GIVEN mode (idx is the caller's)");
+    else REQUIRE(h, logits && head_scale && k <= ncls, "IVIT_CLASSMAP_TOPK mode needs logits and head_scale, and k at most num_classes");
+    REQUIRE_ALIGNED(h, val, "val", 4);
+    RUN(classmap_args_ok(h, __func__, tok8, m->prm.head_w, idx, batch, L, C, ncls, k, class_scale, cam32, map32));
+    if (size_t need = 0; workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
+        const size_t nk = (size_t)batch * k * 4, nmap = nk * L;
+        const struct { const void *p; size_t n; const char *name; bool read_only; } a[8] = {
+            {images, image_bytes(m) * batch, "images", true}, {workspace, need, "workspace", false},
+            {logits, logit_bytes(m, batch), "logits", false}, {idx, nk, "idx", given},
+            {val, nk, "val", false},                          {tok8, (size_t)batch * L * C, "tok8", false},
+            {cam32, nmap, "cam32", false},                    {map32, nmap, "map32", false}};
+        for (int i = 0; i < 8; ++i)
+            for (int j = std::max(i + 1, 3); j < 8; ++j) {       // the pairs among the first three are run_slices'
+                if (a[i].read_only && a[j].read_only) continue;  // images and the caller's idx: both only read
+                if (!ranges_disjoint(h, __func__, a[i].p, a[i].n, a[i].name, a[j].p, a[j].n, a[j].name,
+                                     a[i].read_only || a[j].read_only ? OVL_IN : OVL_OUT))
+                    return IVIT_ERR_INVALID;
+            }
+    }
+    RUN(run_slices(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr, nullptr, tok8));
+    if (!given) RUN(ivit_logits_topk(h, logits, head_scale, batch, ncls, k, idx, val));
+    return ivit_class_map(h, tok8, m->prm.head_w, idx, batch, L, C, ncls, k, class_scale, cam32, map32);
+}
+int ivit_swin_class_map_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                                     const float *head_scale, int mode, int k, int32_t *idx, float *val, int8_t *tok8,
+                                     const float *class_scale, int32_t *cam32, float *map32, ivit_graph *out) {
+    return graph_capture(m, out, ivit_swin_class_map, images, batch, nslices, workspace, bytes, logits, head_scale, mode, k, idx, val, tok8,
+                         class_scale, cam32, map32);
 }
 
 int ivit_graph_launch(ivit_graph g) {

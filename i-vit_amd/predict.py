@@ -16,7 +16,9 @@ vit_quant.py:278-282 / swin_quant.py:560-564), takes the cross-entropy and top-1
     evaluate's loop for them (the engines' `features`);
   * `attention_reference` is the numpy statement of the contract of `ivit_attention_cls_probs` (include/ivit_attnmap.h): row 0 of
     IntSoftmax's output (vit_quant.py:70-76, quant_modules.py:469-497) from a block's q and k, and `attention_map_reference` that of
-    `ivit_attention_map_f32`, the fp32 map over the patches (ViTEngine's `attention`).
+    `ivit_attention_map_f32`, the fp32 map over the patches (ViTEngine's `attention`);
+  * `class_map_reference` is the numpy statement of the contract of `ivit_class_map` (include/ivit_classmap.h): a Swin's
+    class-activation maps, the head's weight rows against every final-stage token, in exact integers (SwinEngine's `class_map`).
 """
 import numpy as np
 import torch
@@ -189,6 +191,38 @@ def attention_map_reference(attn16, heads=False):
         return p.astype(np.float32) * np.float32(2.0 ** -15)
     S = p.astype(np.int64).sum(axis=-2)
     return (S.astype(np.float64) / np.float64(H * 32768)).astype(np.float32)
+
+
+def class_map_reference(tok8, head_w, idx, class_scale=None):
+    """tok8 int8 [B, L, C] (a Swin's final-stage tokens behind norm -> qact2, swin_quant.py:551-552), head_w int8 [num_classes, C] (the
+    head's weight_integer, quant_modules.py:67-83), idx int32 [B, k] -> (cam32 int32 [B, k, L], map32 float32 [B, k, L] or None).
+
+    cam32[b, j, t] = sum_c int(head_w[idx[b, j], c]) * int(tok8[b, t, c]), an exact integer: |cam32| <= 128 * 127 * C < 2^24 for
+    C <= 1024, the limit of the entry.  With class_scale float32 [num_classes] = fl32(s_tok * fc_scaling_factor) (quant_modules.py:96-97
+    with qact2's scale in place of qact3's): map32 = fl32(fl32(cam32) * class_scale[idx]), an exact conversion and ONE float32
+    multiply, the contract of `topk_reference`'s v.  An index outside [0, num_classes) gives a cam32 row of zeros and a map32 row of
+    NaN (`score_reference`'s convention for such a label); duplicate indices in a row are allowed.
+
+    The exact identity behind the maps: sum_t cam32[b, j, t] == head_w[c] . sum_t tok8[b, t, :].  The pool's requantisation of that
+    token sum (swin_quant.py:553-555) is what the head reads, so the sum of a map explains logits - bias up to that single
+    requantisation."""
+    tok8, head_w, idx = np.asarray(tok8), np.asarray(head_w), np.asarray(idx)
+    assert tok8.dtype == np.int8 and tok8.ndim == 3 and head_w.dtype == np.int8 and head_w.ndim == 2 and head_w.shape[1] == tok8.shape[2]
+    assert idx.dtype == np.int32 and idx.ndim == 2 and idx.shape[0] == tok8.shape[0]
+    ncls, C = head_w.shape
+    if C % 16 or C > 1024:
+        raise ValueError(f"C = {C}: a multiple of 16, at most 1024 (the sums must stay below 2^24)")
+    valid = (idx >= 0) & (idx < ncls)
+    rows = head_w[np.where(valid, idx, 0)].astype(np.int64)                  # [B, k, C]
+    cam = np.einsum("bjc,btc->bjt", rows, tok8.astype(np.int64))
+    cam32 = np.where(valid[:, :, None], cam, 0).astype(np.int32)
+    if class_scale is None:
+        return cam32, None
+    class_scale = np.asarray(class_scale)
+    assert class_scale.dtype == np.float32 and class_scale.shape == (ncls,)
+    map32 = cam32.astype(np.float32) * class_scale[np.where(valid, idx, 0)][:, :, None]
+    assert map32.dtype == np.float32
+    return cam32, np.where(valid[:, :, None], map32, np.float32(np.nan)).astype(np.float32)
 
 
 def embed(engine, batches, transform=None, normalize=True):

@@ -13,7 +13,9 @@ PatchMerging :328-349; PatchEmbed layers_quant.py:184-196) on the fused kernels:
 
 Constants are derived once on the host with the reference's fp32/fp64 operation order
 (`freeze.freeze_swin`).  `forward` / `capture` / `predict` / `capture_predict` are NativeEngine's
-(ivit_amd.native); `forward_ops` issues the same forward one C-ABI call per operator.
+(ivit_amd.native); `class_map` / `capture_class_map` are this engine's own: the same runner with the
+final-stage tokens handed out and the class-activation maps behind them (`ivit_swin_class_map`,
+include/ivit_classmap.h); `forward_ops` issues the same forward one C-ABI call per operator.
 torch is used for device memory and streams only.
 """
 import ctypes
@@ -23,8 +25,8 @@ import torch
 
 from . import _lib
 from .engine import pack_constants
-from .freeze import freeze_swin         # lives beside freeze_vit; importable from here as before
-from .native import NativeEngine
+from .freeze import freeze_swin, quantize_weight         # freeze_swin lives beside freeze_vit; importable from here as before
+from .native import NativeEngine, SideOutputs, _ptr
 
 _P = ctypes.c_void_p
 
@@ -144,6 +146,14 @@ class SwinEngine(NativeEngine):
                 self.h.call("ivit_shiftgelu_build_table", self.f[p + "mlp.s_gelu"], self.dy[p + "mlp.dy_gelu"], _P(tab.data_ptr()))
                 self.gelu[p] = tab
         self._ws = {}
+        # class maps: (idx, val, tok8, cam32, map32) per (batch, slices, k, classes given), beside the logits buffer like every side
+        # output; and the unit of a map, fl32(s_tok * fc_scaling_factor[c]) (quant_modules.py:96-97 with qact2's scale in place of
+        # qact3's), built here once from the head's float weights: no frozen constant holds the head's weight scale by itself
+        self._class_map_out = SideOutputs(self._native_ws)
+        self._class_scale = None
+        if weights is not None:
+            fc_sf = quantize_weight(weights["head.weight"])[1]
+            self._class_scale = torch.from_numpy((np.float32(self.token_scale_host()) * fc_sf).astype(np.float32)).to(self.device)
         self._streams = []              # forward_ops with nslices > 1
         self.use_exp_tables = True      # forward_ops only: False issues the arithmetic Shiftmax in every window (cross-check)
 
@@ -158,6 +168,70 @@ class SwinEngine(NativeEngine):
         if "feat.s" not in self.f:
             raise _lib.IvitError("this engine was built without the features' scale: build it from weights and scales, or from packed_swin")
         return self.f["feat.s"]
+
+    # ---- class-activation maps and dense token features (include/ivit_classmap.h).  A Swin feature: the final-stage tokens all pass
+    # qact2 and so share one scale; ViTEngine has no `class_map` (its patch rows have no scale), SwinEngine still no `attention`
+    def token_scale_host(self):
+        """host float: the scale of the final-stage tokens' integers (the reference's qact2, swin_quant.py:552)"""
+        return self.f["pool.s_in"]
+
+    @property
+    def class_scale(self):
+        """device float32 [num_classes]: fl32(token_scale * head.fc_scaling_factor[c]), the unit of class c's map"""
+        if self._class_scale is None:
+            raise _lib.IvitError("this engine was built without the head's float weights (a broadcast package): class_scale needs "
+                                 "their per-class scale; build the engine from weights and scales")
+        return self._class_scale
+
+    def _class_map_args(self, images, k, classes, logits, nslices):
+        """(arguments of the class-map entries, cache key, buffers, what the caller gets) for one batch: val, tok8, cam32, map32 —
+        and idx unless the caller gives the classes — live beside the logits buffer and follow its rule (SideOutputs)"""
+        cfg, B, C = self.cfg, images.shape[0], self.num_features
+        g = cfg.grid >> (cfg.num_layers - 1)
+        given = classes is not None
+        if given:
+            assert isinstance(classes, torch.Tensor) and classes.dtype == torch.int32 and classes.device == self.device, "classes: int32 device tensor"
+            assert classes.ndim == 2 and classes.shape[0] == B and classes.is_contiguous(), f"classes must be a contiguous [{B}, k]"
+            k = classes.shape[1]
+        elif not logits:
+            raise ValueError("the k best classes are read off the logits: logits=False goes with classes=")
+        k = int(k)
+        args, key, (ws, lg) = self._args(images, nslices)
+        okey = key + (k, given)
+        e = self._empty
+        idx, val, tok8, cam32, map32 = self._class_map_out.get(okey, lg, lambda: (
+            None if given else e(torch.int32, B, k), None if given else e(torch.float32, B, k), e(torch.int8, B, g * g, C),
+            e(torch.int32, B, k, g * g), e(torch.float32, B, k, g * g)))
+        if given:
+            idx = classes
+        mode = _lib.IVIT_CLASSMAP_GIVEN if given else _lib.IVIT_CLASSMAP_TOPK
+        args = args[:-1] + (_ptr(lg) if logits else None, self.ptr("head.scale"), mode, k, _ptr(idx), None if given else _ptr(val),
+                            _ptr(tok8), _ptr(self.class_scale), _ptr(cam32), _ptr(map32))
+        return args, okey, (ws, lg, idx, tok8, cam32, map32) + (() if given else (val,)), (idx, val, tok8, cam32, map32.view(B, k, g, g))
+
+    def class_map(self, images, k=5, classes=None, logits=True, nslices=1, copy=False):
+        """images int8 [B, C, H, W] -> (idx, val, tok8, cam32, maps) device tensors: what each final-stage token contributes to a class.
+        classes=None: idx int32 [B, k] and val float32 [B, k] are predict's, the k best classes of this forward.  classes = an int32
+        device tensor [B, k] (e.g. the labels): those classes — idx is that tensor, val None; an index outside the classes gives a map
+        of zeros / NaN.  tok8 int8 [B, L, C]: the tokens behind norm -> qact2 (swin_quant.py:551-552), L = gh * gw in row-major grid
+        order, C = num_features, scale `token_scale_host()` — the dense features of the backbone.  cam32 int32 [B, k, L]: the head's
+        weight row of the class against every token, exact (`predict.class_map_reference`).  maps float32 [B, k, gh, gw]:
+        cam32 * class_scale[class], one multiply.  One native call: the final norm writes the caller's rows, the top-k and ONE launch
+        for the maps follow behind the slices' join.  With logits=False (classes given) the forward ends behind the final norm:
+        no pool, no head; else the int32 logits are forward's (and `last_logits`).  The results are the engine's own buffers for
+        this (batch, nslices, k, mode): copy=True (or clone) to keep them across calls."""
+        def plan():
+            args, _, bufs, out = self._class_map_args(images, k, classes, logits, nslices)
+            return args, bufs[1] if logits else None, out
+        out = self._eager("_class_map", images, False, plan)
+        return tuple(t if t is None else t.clone() for t in out) if copy else out
+
+    def capture_class_map(self, images, k=5, classes=None, logits=True, nstreams=1):
+        """hipGraph of one class_map on fixed buffers; returns a callable that replays it and returns what `class_map` returns.  A
+        replay reads `images` — and `classes`, if given — as they are then."""
+        self._check_images(images)
+        args, okey, bufs, out = self._class_map_args(images, k, classes, logits, nstreams)
+        return self._capture("_class_map_graph_create", images, args, okey, bufs, out, self._class_map_out)
 
     def workspace(self, B, key=None):
         if (B, key) in self._ws:
