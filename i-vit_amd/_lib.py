@@ -1,9 +1,10 @@
-"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h and include/ivit_classmap.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
+"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h and include/ivit_hidden.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
 restated here: the Structures, the status codes and every argtypes / restype are derived from the headers by _abi.py (the mapping
 rule is stated there).  ivit.h is frozen at IVIT_VERSION 111: ABI / SIGNATURES / RESTYPES are its prototypes and stay what they are;
 the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES, of ivit_features.h,
 under FEATURES_ABI / FEATURES_SIGNATURES / FEATURES_RESTYPES, of ivit_attnmap.h, under ATTNMAP_ABI / ATTNMAP_SIGNATURES /
-ATTNMAP_RESTYPES, and of ivit_classmap.h, under CLASSMAP_ABI / CLASSMAP_SIGNATURES / CLASSMAP_RESTYPES.
+ATTNMAP_RESTYPES, of ivit_classmap.h, under CLASSMAP_ABI / CLASSMAP_SIGNATURES / CLASSMAP_RESTYPES, and of ivit_hidden.h, under
+HIDDEN_ABI / HIDDEN_SIGNATURES / HIDDEN_RESTYPES.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -92,6 +93,16 @@ _classmap_signatures = _abi.signatures(CLASSMAP_ABI, _structs)
 CLASSMAP_RESTYPES = {name: ret for name, (ret, args) in _classmap_signatures.items()}
 CLASSMAP_SIGNATURES = {name: args for name, (ret, args) in _classmap_signatures.items()}
 
+# include/ivit_hidden.h, likewise
+HIDDEN_ABI = _abi.HIDDEN_ABI
+IVIT_HIDDEN_VERSION, IVIT_HIDDEN_TOKENS, IVIT_HIDDEN_GRID = (
+    HIDDEN_ABI.constants[n] for n in ("IVIT_HIDDEN_VERSION", "IVIT_HIDDEN_TOKENS", "IVIT_HIDDEN_GRID"))
+assert set(HIDDEN_ABI.structs) == set(ABI.structs) and not set(HIDDEN_ABI.functions) & (
+    set(ABI.functions) | set(EVAL_ABI.functions) | set(FEATURES_ABI.functions) | set(ATTNMAP_ABI.functions) | set(CLASSMAP_ABI.functions))
+_hidden_signatures = _abi.signatures(HIDDEN_ABI, _structs)
+HIDDEN_RESTYPES = {name: ret for name, (ret, args) in _hidden_signatures.items()}
+HIDDEN_SIGNATURES = {name: args for name, (ret, args) in _hidden_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -100,7 +111,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -170,6 +181,14 @@ def bind_classmap(lib):
     return lib
 
 
+def bind_hidden(lib):
+    """the same for every prototype of include/ivit_hidden.h"""
+    for name, args in HIDDEN_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, HIDDEN_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -181,7 +200,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH))))))
+    _lib = bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH)))))))
     return _lib
 
 

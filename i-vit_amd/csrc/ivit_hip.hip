@@ -1,4 +1,5 @@
-// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h) over the gfx950 kernels.
+// ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
+// include/ivit_hidden.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -33,6 +34,7 @@
 #include "ivit_features.h"
 #include "ivit_attnmap.h"
 #include "ivit_classmap.h"
+#include "ivit_hidden.h"
 #include "ivit_preprocess.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
@@ -2254,6 +2256,47 @@ extern "C" int ivit_class_map(ivit_handle h, const int8_t *tok8, const int8_t *h
     const unsigned grid = (unsigned)((BK + 3ll) / 4);            // one wavefront per (image, class slot)
     if (map32) class_map_kernel<true><<<grid, 256, 0, h->stream>>>(tok8, head_w, idx, class_scale, cam32, map32, BK, k, L, C, num_classes);
     else class_map_kernel<false><<<grid, 256, 0, h->stream>>>(tok8, head_w, idx, nullptr, cam32, nullptr, BK, k, L, C, num_classes);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- hidden states: the fp32 form of a block's output (include/ivit_hidden.h)
+// the argument rules of ivit_hidden_f32 (ivit_model.h asks here for its model's planes, before its slices are launched): pointers, counts,
+// the row range, the scale, the layout, alignment, the overlapping pair, then the width
+static int hidden_args_ok(ivit_handle h, const char *fn, const int16_t *x16, const char *x_name, float scale, long long batch, int T, int C, int t0,
+                          int layout, const float *out, const char *out_name) {
+    char bad[96] = "";
+    if (!x16 || !out) snprintf(bad, sizeof(bad), "%s or %s is null", x_name, out_name);
+    else if (batch < 1 || T < 1 || C < 1) snprintf(bad, sizeof(bad), "batch, T or C is not positive");
+    else if (t0 < 0 || t0 >= T) snprintf(bad, sizeof(bad), "t0 must be in [0, T)");
+    else if (!(scale > 0.f && scale <= FLT_MAX)) snprintf(bad, sizeof(bad), "scale must be finite and positive");
+    else if (layout != IVIT_HIDDEN_TOKENS && layout != IVIT_HIDDEN_GRID) snprintf(bad, sizeof(bad), "layout must be IVIT_HIDDEN_TOKENS or IVIT_HIDDEN_GRID");
+    else if ((uintptr_t)x16 & 15) snprintf(bad, sizeof(bad), "%s must be 16-byte aligned", x_name);
+    else if ((uintptr_t)out & 15) snprintf(bad, sizeof(bad), "%s must be 16-byte aligned", out_name);
+    else if (batch > 0x7fffffffLL || (long long)(T - t0) * C > 0x7fffffffLL * 8) snprintf(bad, sizeof(bad), "batch or an image's rows do not fit an int");
+    if (bad[0]) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    if (!ranges_disjoint(h, fn, x16, (size_t)batch * T * C * 2, x_name, out, (size_t)batch * (T - t0) * C * 4, out_name, OVL_IN)) return IVIT_ERR_INVALID;
+    if ((C % 8) != 0) {
+        snprintf(h->err, sizeof(h->err), "%s: C must be a multiple of 8", fn);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return IVIT_OK;
+}
+
+extern "C" int ivit_hidden_f32(ivit_handle h, const int16_t *x16, float scale, int batch, int T, int C, int t0, int layout, float *out) {
+    CHECK_H(h);
+    if (const int rc = hidden_args_ok(h, __func__, x16, "x16", scale, batch, T, C, t0, layout, out, "out")) return rc;
+    const int N = T - t0;
+    const unsigned gy = (unsigned)std::min(batch, 65535);                  // the kernels stride over the images beyond
+    if (layout == IVIT_HIDDEN_GRID) {
+        const long long tiles = ((N + HIDDEN_TILE - 1ll) / HIDDEN_TILE) * ((C + HIDDEN_TILE - 1ll) / HIDDEN_TILE);
+        REQUIRE(h, tiles <= 0x7fffffffLL, "too many tiles for one launch");
+        hidden_f32_kernel<true><<<dim3((unsigned)tiles, gy), 256, 0, h->stream>>>(x16, scale, batch, T, C, t0, out);
+    } else {
+        const long long per = (long long)N * (C / 8);                       // 16-byte pieces of an image: one per thread, strided beyond 2^28
+        const unsigned gx = (unsigned)std::min<long long>((per + 255) / 256, 1 << 20);
+        hidden_f32_kernel<false><<<dim3(gx, gy), 256, 0, h->stream>>>(x16, scale, batch, T, C, t0, out);
+    }
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

@@ -133,6 +133,18 @@ struct AttnTap {
     size_t plane;
 };
 
+// the block / stage outputs a caller taps (include/ivit_hidden.h): indices, strictly ascending; the slice's first row of plane 0 of the
+// caller's hid16; and where plane j lies from there, in elements: j * plane for a ViT (planes of batch * T * D), off[j] for a Swin
+// (planes of different sizes, packed; slice_run adds the slice's rows).  The last launch of a tapped block writes there instead of
+// into the workspace, and from then on the stream `x` is the caller's plane: every later write goes to a workspace buffer
+struct HidTap {
+    const int *idx;
+    int n;
+    int16_t *hid16;
+    size_t plane;
+    size_t off[4];
+};
+
 // block i's ShiftGELU table
 template <class Model>
 int8_t *gelu_table(const Model *m, int i) { return m->gelu_tab + (size_t)i * 65536; }
@@ -251,8 +263,13 @@ int vit_attention(const ivit_vit_s *m, ivit_handle h, int i, const int8_t *q, co
 // `tap`: null, or the blocks whose class-token probabilities go to the caller's attn16, one ivit_attention_cls_probs directly behind
 // the block's qkv launch (q and k have the same [B*H, T, dh] layout whichever qkv or attention form the block takes); with neither
 // logits nor feat8 the slice ends behind the last tap
+// `hid`: null, or the blocks whose 16-bit output (qact4, vit_quant.py:141-143) goes to the caller's hid16 (include/ivit_hidden.h): the
+// block's last launch writes the slice's rows of the caller's plane, which is the stream from there on.  The stream is never written in
+// place: the proj launch writes the workspace buffer `x` is not (other), the Mlp launch the one its input is not — or the plane.  A
+// tapped last block runs on all rows (the class-token tail has B of them); with neither logits nor feat8 the slice ends behind the
+// last tapped block
 int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, int Bmax, char *ws, int32_t *logits, int8_t *feat8,
-              const AttnTap *tap) {
+              const AttnTap *tap, const HidTap *hid = nullptr) {
     const ivit_vit_config &c = m->cfg;
     const ivit_vit_params &P = m->prm;
     const int T = m->T, D = c.embed_dim, H = c.num_heads, dh = D / H, Hd = c.hidden_dim, ld = m->ld;
@@ -261,7 +278,11 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
     int8_t *patches = (int8_t *)(ws + L.patches), *a8 = (int8_t *)(ws + L.a8), *q = (int8_t *)(ws + L.q),
            *k = (int8_t *)(ws + L.k), *vt = (int8_t *)(ws + L.vt), *ctx8 = (int8_t *)(ws + L.ctx8),
            *h8 = (int8_t *)(ws + L.h8), *g8 = (int8_t *)(ws + L.g8), *cls8 = feat8 ? feat8 : (int8_t *)(ws + L.cls8);
-    int16_t *patch16 = (int16_t *)(ws + L.patch16), *x = (int16_t *)(ws + L.xa), *y = (int16_t *)(ws + L.xb);
+    int16_t *patch16 = (int16_t *)(ws + L.patch16), *const xa = (int16_t *)(ws + L.xa), *const xb = (int16_t *)(ws + L.xb), *x = xa;
+    // the workspace stream buffer that `cur` is not (xa behind a caller's plane): without a tap xa -> xb -> xa, block after block
+    auto other = [&](const int16_t *cur) { return cur == xa ? xb : xa; };
+    // the class-token tail computes B rows of the last block: not where the caller asked for that block's output
+    const bool tailed = cls_tail(m) && !(hid && hid->idx[hid->n - 1] == c.depth - 1);
     // PatchEmbed + class token + position embedding: one GEMM launch that gathers its A rows from the images and finishes the rows in its
     // epilogue (round 6), or im2col -> GEMM -> embed_finish where that form does not apply
     RUN(fused_or((m->Kp == c.in_chans * c.patch_size * c.patch_size)
@@ -272,7 +293,7 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
                      RUN(ivit_linear_i8_requant(h, patches, P.pe_w, P.pe_b, P.pe_dy, 16, patch16, B * m->num_patches, D, m->Kp));
                      return ivit_embed_finish(h, patch16, P.z_cls, P.pos, P.dy_x, P.dy_pos, x, B, T, D);
                  }));
-    int tapped = 0;
+    int tapped = 0, hidden = 0;
     for (int i = 0; i < c.depth; ++i) {
         const ivit_vit_block &b = m->blocks[i];
         // a layer on the row-table attention takes v ROW-major (ldv = 0: the qkv GEMM stores 16 bytes per lane instead of 16 byte
@@ -280,7 +301,7 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         const int ldv = (m->fused_attention && m->has_rowtab[i]) ? 0 : ld;
         // last block: from the attention on, the B class-token rows only (cls_tail), compact in the buffers PatchEmbed has left:
         // context rows in `patches`, the identity rows — copied by the attention launch — in `patch16`
-        const bool tail = i == c.depth - 1 && cls_tail(m);
+        const bool tail = i == c.depth - 1 && tailed;
         const int Mb = tail ? B : M;      // rows behind the attention
         // norm1's 8-bit output has one consumer: where the qkv GEMM keeps a CU's tokens in LDS it is computed there (round 6; D = 192 too,
         // with v in either layout)
@@ -293,8 +314,9 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
                      }));
         if (tap && tapped < tap->nblocks && tap->blocks[tapped] == i) {
             RUN(ivit_attention_cls_probs(h, q, k, b.dy_qk, b.s_softmax, tap->attn16 + tap->plane * (size_t)tapped, B, H, T, dh));
-            if (++tapped == tap->nblocks && !logits && !feat8) return IVIT_OK;
+            if (++tapped == tap->nblocks && !logits && !feat8 && !hid) return IVIT_OK;
         }
+        int16_t *y = other(x);          // proj's destination
         if (tail) {
             ctx8 = patches;
             RUN(vit_attention(m, h, i, q, k, vt, ctx8, B, ldv, true, x, patch16));
@@ -315,7 +337,10 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         const bool mlp_fast = mlp_plan_fuses(m->mlp_plans[i], b.res2_main, b.res2_res, Mb);
         const bool ln_lockstep = ln_mlp_plan_fuses(h, m->mlp_plans[i], b.res2_main, b.res2_res, Mb) == LN_MLP_LOCKSTEP;
         RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, Mb));
-        { int16_t *t = x; x = y; y = t; }
+        const bool hid_here = hid && hidden < hid->n && hid->idx[hidden] == i;
+        // the Mlp's destination: the caller's plane for a tapped block, else the workspace buffer its input is not (the tail: patch16,
+        // which the proj launch has read)
+        { int16_t *t = x; x = y; y = hid_here ? hid->hid16 + hid->plane * (size_t)hidden : tail ? t : other(x); }
         const int8_t *tab = gelu_table(m, i);
         RUN(fused_or(mlp_fast ? ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8, tab, b.res2_main,
                                                                  b.res2_res, y, Mb)
@@ -333,11 +358,12 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
                                              return ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 3], g8, b.res2_main, b.res2_res, x, y, Mb);
                                          });
                      }));
-        { int16_t *t = x; x = y; y = t; }
+        x = y;
+        if (hid_here && ++hidden == hid->n && !logits && !feat8 && !(tap && tapped < tap->nblocks)) return IVIT_OK;
     }
     // final norm on the class-token rows only (row stride T*D; D where the last block left them compact), then the head's int32
     // accumulators
-    RUN(ivit_layernorm_requant(h, x, B, D, cls_tail(m) ? (int64_t)D : (int64_t)T * D, P.s_ln, P.n_bias_int, P.n_sc, P.n_dy, cls8));
+    RUN(ivit_layernorm_requant(h, x, B, D, tailed ? (int64_t)D : (int64_t)T * D, P.s_ln, P.n_bias_int, P.n_sc, P.n_dy, cls8));
     if (logits) RUN(ivit_linear_i8(h, cls8, P.head_w, P.head_b, logits, B, c.num_classes, D));
     return IVIT_OK;
 }
@@ -346,11 +372,17 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
 // slice of `nb` images, the batch's images b0 onward, on its own rows of logits, feat8 and (from here on) the tap
 inline size_t slice_stride(const ivit_vit_s *m, int Bmax) { return slice_layout(m, Bmax).total; }
 inline int num_features(const ivit_vit_s *m) { return m->cfg.embed_dim; }
+// ... and of its hidden states (include/ivit_hidden.h): how many sites it has (blocks), the tokens and the width of site i's plane
+inline int hidden_sites(const ivit_vit_s *m) { return m->cfg.depth; }
+inline int hidden_tokens(const ivit_vit_s *m, int) { return m->T; }
+inline int hidden_width(const ivit_vit_s *m, int) { return m->cfg.embed_dim; }
 int slice_run(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int b0, int nb, int Bmax, char *ws, int32_t *logits, int8_t *feat8,
-              const AttnTap *tap, int8_t * /*tok8: a Swin's*/) {
+              const AttnTap *tap, int8_t * /*tok8: a Swin's*/, const HidTap *hid) {
     AttnTap mine;
     if (tap) { mine = *tap; mine.attn16 += (size_t)b0 * m->cfg.num_heads * m->T; }
-    return run_slice(m, h, images, nb, Bmax, ws, logits, feat8, tap ? &mine : nullptr);
+    HidTap planes;
+    if (hid) { planes = *hid; planes.hid16 += (size_t)b0 * hidden_tokens(m, 0) * hidden_width(m, 0); }
+    return run_slice(m, h, images, nb, Bmax, ws, logits, feat8, tap ? &mine : nullptr, hid ? &planes : nullptr);
 }
 
 }  // namespace
@@ -561,14 +593,21 @@ int swin_mlp_mode(const ivit_swin_s *m, int bi, int C, long long M) {
 // workspace, or null; `logits`: null ends the slice in front of the head
 // `tok8`: the slice's rows of the caller's final-stage tokens [B, L, C] (include/ivit_classmap.h), where the final norm writes instead
 // of the workspace and the pool reads, or null; without logits and without feat8 the slice ends behind the final norm
-int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, char *ws, int32_t *logits, int8_t *feat8, int8_t *tok8) {
+// `hid`: null, or the stages whose output — that of the stage's last block, in front of PatchMerging — goes to the caller's hid16
+// (include/ivit_hidden.h): that block's Mlp launch writes the slice's rows of the caller's plane, which is the stream from there on.
+// As in run_slice the stream is never written in place; behind a tapped stage the merge's reduction writes the next stage's stream
+// into the workspace, never into the plane.  With neither logits, feat8 nor tok8 the slice ends behind the last tapped stage
+int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, char *ws, int32_t *logits, int8_t *feat8, int8_t *tok8,
+                   const HidTap *hid = nullptr) {
     const ivit_swin_config &c = m->cfg;
     const ivit_swin_params &P = m->prm;
     const SwinLayout Lw = swin_layout(m, B);
     int8_t *patches = (int8_t *)(ws + Lw.patches), *a8 = (int8_t *)(ws + Lw.a8), *qkv = (int8_t *)(ws + Lw.qkv),
            *ctx = (int8_t *)(ws + Lw.ctx), *h8 = (int8_t *)(ws + Lw.h8), *g8 = (int8_t *)(ws + Lw.g8),
            *pool = feat8 ? feat8 : (int8_t *)(ws + Lw.pool);
-    int16_t *x = (int16_t *)(ws + Lw.xa), *y = (int16_t *)(ws + Lw.xb), *t16 = (int16_t *)(ws + Lw.xc);
+    int16_t *const xa = (int16_t *)(ws + Lw.xa), *const xb = (int16_t *)(ws + Lw.xb), *x = xa, *t16 = (int16_t *)(ws + Lw.xc);
+    auto other = [&](const int16_t *cur) { return cur == xa ? xb : xa; };      // the workspace stream buffer that `cur` is not
+    int hidden = 0;
     float *zf = (float *)(ws + Lw.zf);
     const int E = c.embed_dim;
     int res = m->grid, L = res * res;
@@ -586,6 +625,7 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             const int shift = (bj % 2 == 0 || res <= c.window_size) ? 0 : c.window_size / 2;
             const int wsz = res <= c.window_size ? res : c.window_size;     // SwinTransformerBlock.__init__
             const ivit_linear_plan *lp = &m->lin_plans[2 * bi];
+            int16_t *y = other(x);      // proj's destination
             // norm1 inside the qkv launch where that layer runs on gemm_ws_qkv_kernel (C = 384, activations in natural token order)
             RUN(fused_or((lp[0] && li != 0) ? ivit_layernorm_linear_i8_requant_planned(h, lp[0], x, b.s_in, b.n1.bias_int, b.n1.sc, b.n1.dy, qkv, (int)M)
                                             : IVIT_ERR_UNSUPPORTED,
@@ -603,7 +643,10 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
                                                 wsz, shift, heads, C / heads));
             if (lp[1]) RUN(ivit_linear_i8_requant_residual_planned(h, lp[1], ctx, b.res1_main, b.res1_res, x, y, (int)M));
             else RUN(ivit_linear_i8_requant_residual(h, ctx, b.proj.w, b.proj.b, b.proj.dy, b.res1_main, b.res1_res, x, y, (int)M, C, C));
-            { int16_t *t = x; x = y; y = t; }
+            // the Mlp's destination: the caller's plane for the last block of a tapped stage, else the workspace buffer its input is not
+            const bool hid_here = hid && hidden < hid->n && hid->idx[hidden] == li && bj == c.depths[li] - 1;
+            x = y;
+            y = hid_here ? hid->hid16 + hid->off[hidden] : other(x);
             const int mlp_mode = swin_mlp_mode(m, bi, C, M);
             // norm2 is a launch of its own in every stage.  (In the head of the C = 384 stage's fused Mlp it measured slower: Swin-T b256,
             // two slices, 4.76 against 4.70 ms same-box; the LayerNorm launch of one slice overlaps the other slice's kernels)
@@ -618,7 +661,8 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
                 RUN(ivit_shiftgelu_requant_lut(h, h8, M, c.mlp_ratio * C, gelu_table(m, bi), g8));
                 RUN(ivit_linear_i8_requant_residual(h, g8, b.fc2.w, b.fc2.b, b.fc2.dy, b.res2_main, b.res2_res, x, y, (int)M, C, c.mlp_ratio * C));
             }
-            { int16_t *t = x; x = y; y = t; }
+            x = y;
+            if (hid_here && ++hidden == hid->n && !logits && !feat8 && !tok8) return IVIT_OK;
         }
         if (li < c.num_layers - 1) {     // PatchMerging: gather -> LN(4C) -> qact1(8) -> reduction -> qact2(8)
             const ivit_swin_merge &g = m->merges[li];
@@ -631,6 +675,7 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
                 RUN(ivit_patch_merge_gather(h, x, 16, B, res_in, C, t16));
                 return swin_ln(m, h, t16, M, 4 * C, g.s_in, g.n, L, false, a8);
             }));
+            if (x != xa && x != xb) x = xa;      // behind a tapped stage `x` is the caller's plane: the next stage's stream starts in the workspace
             // reduction -> qact2(8), stored as the 16-bit stream the next stage reads (round 6: the widening pass was 16 us per merge)
             RUN(fused_or(ivit_linear_i8_requant8_store16(h, a8, g.red.w, nullptr, g.red.dy, x, (int)M, 2 * C, 4 * C), [&] {
                 RUN(ivit_linear_i8_requant(h, a8, g.red.w, nullptr, g.red.dy, 8, ctx, (int)M, 2 * C, 4 * C));
@@ -653,9 +698,19 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
 inline size_t slice_stride(const ivit_swin_s *m, int Bmax) { return swin_layout(m, Bmax).total; }
 inline int num_features(const ivit_swin_s *m) { return m->cfg.embed_dim << (m->cfg.num_layers - 1); }
 inline int final_tokens(const ivit_swin_s *m) { const int r = m->grid >> (m->cfg.num_layers - 1); return r * r; }
+// its hidden states are by stage: (grid >> s)^2 tokens of width embed_dim << s
+inline int hidden_sites(const ivit_swin_s *m) { return m->cfg.num_layers; }
+inline int hidden_tokens(const ivit_swin_s *m, int s) { const int r = m->grid >> s; return r * r; }
+inline int hidden_width(const ivit_swin_s *m, int s) { return m->cfg.embed_dim << s; }
 inline int slice_run(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int b0, int nb, int /*Bmax*/, char *ws, int32_t *logits,
-                     int8_t *feat8, const AttnTap * /*tap*/, int8_t *tok8) {
-    return swin_run_slice(m, h, images, nb, ws, logits, feat8, tok8 ? tok8 + (size_t)b0 * final_tokens(m) * num_features(m) : nullptr);
+                     int8_t *feat8, const AttnTap * /*tap*/, int8_t *tok8, const HidTap *hid) {
+    HidTap planes;
+    if (hid) {
+        planes = *hid;
+        for (int j = 0; j < hid->n; ++j) planes.off[j] += (size_t)b0 * hidden_tokens(m, hid->idx[j]) * hidden_width(m, hid->idx[j]);
+    }
+    return swin_run_slice(m, h, images, nb, ws, logits, feat8, tok8 ? tok8 + (size_t)b0 * final_tokens(m) * num_features(m) : nullptr,
+                          hid ? &planes : nullptr);
 }
 
 }  // namespace
@@ -806,14 +861,15 @@ int workspace_bytes(M *m, int batch, int nslices, size_t *bytes) {
 // pointers and the workspace's size and alignment, the three arrays of every runner pairwise; then the slices of the batch.  forward
 // (logits, no feat8), features (feat8, logits or none) and ivit_vit_attention (a tap, logits or none) end here.  `tap`: the caller's
 // block list and attn16 as a whole; slice_run gives every slice its own rows of it.  `tok8`: a Swin's final-stage tokens as a whole
-// (ivit_swin_class_map, logits or none), likewise
+// (ivit_swin_class_map, logits or none), likewise.  `hid`: the caller's block / stage list and hid16 as a whole (the hidden_states
+// entries, logits or none), likewise
 template <class M>
 int run_slices(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-               int8_t *feat8, const AttnTap *tap = nullptr, int8_t *tok8 = nullptr) {
+               int8_t *feat8, const AttnTap *tap = nullptr, int8_t *tok8 = nullptr, const HidTap *hid = nullptr) {
     ivit_handle h = m->h;
     size_t need = 0;
     RUN(workspace_bytes(m, batch, nslices, &need));
-    REQUIRE_FN(h, fn, images && (logits || feat8 || tap || tok8) && workspace && bytes >= need, "bad arguments / workspace too small");
+    REQUIRE_FN(h, fn, images && (logits || feat8 || tap || tok8 || hid) && workspace && bytes >= need, "bad arguments / workspace too small");
     REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = image_bytes(m);
     RUN(runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, logit_bytes(m, batch)));
@@ -822,7 +878,7 @@ int run_slices(M *m, const char *fn, const int8_t *images, int batch, int nslice
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
         return slice_run(m, sh, images + (size_t)b0 * img_bytes, b0, nb, Bmax, (char *)workspace + stride * (size_t)i,
                          logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
-                         feat8 ? feat8 + (size_t)b0 * num_features(m) : nullptr, tap, tok8);
+                         feat8 ? feat8 + (size_t)b0 * num_features(m) : nullptr, tap, tok8, hid);
     });
 }
 
@@ -988,6 +1044,104 @@ int ivit_swin_class_map_graph_create(ivit_swin m, const int8_t *images, int batc
                                      const float *class_scale, int32_t *cam32, float *map32, ivit_graph *out) {
     return graph_capture(m, out, ivit_swin_class_map, images, batch, nslices, workspace, bytes, logits, head_scale, mode, k, idx, val, tok8,
                          class_scale, cam32, map32);
+}
+
+}  // extern "C"
+
+namespace {
+
+// hidden states (include/ivit_hidden.h).  The scale of a site is a host float the model was created with: of a ViT block's output
+// the next block's s_ln1 (s_ln behind the last), of a Swin stage's output the merge's s_in (s_norm_in behind the last stage)
+inline float hidden_scale(const ivit_vit_s *m, int i) { return i + 1 < m->cfg.depth ? m->blocks[i + 1].s_ln1 : m->prm.s_ln; }
+inline float hidden_scale(const ivit_swin_s *m, int s) { return s + 1 < m->cfg.num_layers ? m->merges[s].s_in : m->prm.s_norm_in; }
+
+// both hidden_states entries: every argument checked first — the list, hid16, the layout, alignment, the planes' sizes, the rules of
+// ivit_hidden_f32 for every plane, the five arrays pairwise (images / workspace / logits again in run_slices) —, then the slices with
+// the caller's planes as the destination of the tapped blocks' last launches, then on the handle's stream, behind the slices' join,
+// one ivit_hidden_f32 per plane.  `t0`: 1 drops the class row of a ViT's GRID form.  `list_name`: the list as the header spells it
+template <class M>
+int runner_hidden(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                  const int *list_host, int n, const char *list_name, int16_t *hid16, int layout, float *hid32, bool class_row) {
+    if (!m) return IVIT_ERR_INVALID;
+    ivit_handle h = m->h;
+    const int sites = hidden_sites(m);
+    bool list_ok = list_host && n >= 1 && n <= sites;
+    for (int j = 0; list_ok && j < n; ++j) list_ok = list_host[j] >= 0 && list_host[j] < sites && (j == 0 || list_host[j] > list_host[j - 1]);
+    if (!list_ok) {
+        snprintf(h->err, sizeof(h->err), "%s: %s must be 1 .. %d strictly ascending indices in [0, %d)", fn, list_name, sites, sites);
+        return IVIT_ERR_INVALID;
+    }
+    REQUIRE_FN(h, fn, hid16, "hid16 is null");
+    REQUIRE_FN(h, fn, !hid32 || layout == IVIT_HIDDEN_TOKENS || layout == IVIT_HIDDEN_GRID, "layout must be IVIT_HIDDEN_TOKENS or IVIT_HIDDEN_GRID");
+    REQUIRE_FN(h, fn, ((uintptr_t)hid16 & 15) == 0, "hid16 must be 16-byte aligned");
+    REQUIRE_FN(h, fn, ((uintptr_t)hid32 & 15) == 0, "hid32 must be 16-byte aligned");
+    const int t0 = (class_row && hid32 && layout == IVIT_HIDDEN_GRID) ? 1 : 0;
+    const size_t nb = (size_t)std::max(batch, 0);
+    HidTap tap = {list_host, n, hid16, 0, {0, 0, 0, 0}};
+    std::vector<size_t> at16(n + 1, 0), at32(n + 1, 0);               // where plane j starts, in elements
+    for (int j = 0; j < n; ++j) {
+        const size_t T = hidden_tokens(m, list_host[j]), C = hidden_width(m, list_host[j]);
+        // a slice's rows of a plane start b0 * T * C elements in: 16-byte aligned for every b0
+        REQUIRE_FN(h, fn, (T * C) % 8 == 0, "the tokens times the width of a tapped plane must be a multiple of 8");
+        at16[j + 1] = at16[j] + nb * T * C;
+        at32[j + 1] = at32[j] + nb * (T - t0) * C;
+        if (j < 4) tap.off[j] = at16[j];
+    }
+    tap.plane = at16[1];
+    if (hid32 && batch > 0)
+        for (int j = 0; j < n; ++j)
+            RUN(hidden_args_ok(h, fn, hid16 + at16[j], "hid16", hidden_scale(m, list_host[j]), batch, hidden_tokens(m, list_host[j]),
+                               hidden_width(m, list_host[j]), t0, layout, hid32 + at32[j], "hid32"));
+    if (size_t need = 0; batch > 0 && workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
+        const struct { const void *p; size_t n; const char *name; } a[5] = {
+            {images, image_bytes(m) * batch, "images"},
+            {workspace, need, "workspace"},
+            {logits, logit_bytes(m, batch), "logits"},
+            {hid16, at16[n] * 2, "hid16"},
+            {hid32, at32[n] * 4, "hid32"}};
+        for (int i = 0; i < 5; ++i)
+            for (int j = std::max(i + 1, 3); j < 5; ++j)        // the pairs among the first three are run_slices'
+                if (!ranges_disjoint(h, fn, a[i].p, a[i].n, a[i].name, a[j].p, a[j].n, a[j].name, i == 0 ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
+    }
+    RUN(run_slices(m, fn, images, batch, nslices, workspace, bytes, logits, nullptr, nullptr, nullptr, &tap));
+    for (int j = 0; hid32 && j < n; ++j)
+        RUN(ivit_hidden_f32(h, hid16 + at16[j], hidden_scale(m, list_host[j]), batch, hidden_tokens(m, list_host[j]), hidden_width(m, list_host[j]),
+                            t0, layout, hid32 + at32[j]));
+    return IVIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ivit_vit_hidden_scale(ivit_vit m, int block, float *scale_host) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, scale_host && block >= 0 && block < m->cfg.depth, "scale_host is null or block outside [0, depth)");
+    *scale_host = hidden_scale(m, block);
+    return IVIT_OK;
+}
+int ivit_swin_hidden_scale(ivit_swin m, int stage, float *scale_host) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE(m->h, scale_host && stage >= 0 && stage < m->cfg.num_layers, "scale_host is null or stage outside [0, num_layers)");
+    *scale_host = hidden_scale(m, stage);
+    return IVIT_OK;
+}
+
+int ivit_vit_hidden_states(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                           const int *blocks_host, int nblocks, int16_t *hid16, int layout, float *hid32) {
+    return runner_hidden(m, __func__, images, batch, nslices, workspace, bytes, logits, blocks_host, nblocks, "blocks_host", hid16, layout, hid32, true);
+}
+int ivit_vit_hidden_states_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                                        const int *blocks_host, int nblocks, int16_t *hid16, int layout, float *hid32, ivit_graph *out) {
+    return graph_capture(m, out, ivit_vit_hidden_states, images, batch, nslices, workspace, bytes, logits, blocks_host, nblocks, hid16, layout, hid32);
+}
+int ivit_swin_hidden_states(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                            const int *stages_host, int nstages, int16_t *hid16, int layout, float *hid32) {
+    return runner_hidden(m, __func__, images, batch, nslices, workspace, bytes, logits, stages_host, nstages, "stages_host", hid16, layout, hid32, false);
+}
+int ivit_swin_hidden_states_graph_create(ivit_swin m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
+                                         const int *stages_host, int nstages, int16_t *hid16, int layout, float *hid32, ivit_graph *out) {
+    return graph_capture(m, out, ivit_swin_hidden_states, images, batch, nslices, workspace, bytes, logits, stages_host, nstages, hid16, layout, hid32);
 }
 
 int ivit_graph_launch(ivit_graph g) {

@@ -2,6 +2,7 @@
 
 `forward` / `capture` / `predict` / `capture_predict` are NativeEngine's (ivit_amd.native): the whole
 batch goes to the native runner (`ivit_vit_forward`, csrc/ivit_model.h) in one C call.
+`hidden_states` / `capture_hidden_states` (block outputs, include/ivit_hidden.h) are NativeEngine's with a ViT's planes.
 `attention` / `capture_attention` are this engine's own: the same runner with the class token's
 attention probabilities of chosen blocks tapped (`ivit_vit_attention`, include/ivit_attnmap.h).
 `forward_ops` issues the same kernels one C-ABI call at a time from Python (used by the
@@ -19,7 +20,7 @@ import torch
 
 from . import _lib
 from .freeze import freeze_vit
-from .native import NativeEngine, SideOutputs
+from .native import NativeEngine, SideOutputs, ascending_indices
 
 _P = ctypes.c_void_p
 
@@ -220,18 +221,7 @@ class ViTEngine(NativeEngine):
     # no class token
     def _attention_blocks(self, blocks):
         """an int or a sequence of block indices, negative ones counting from the end -> strictly ascending tuple in [0, depth)"""
-        depth = self.cfg.depth
-        seq = (blocks,) if isinstance(blocks, (int, np.integer)) else tuple(blocks)
-        if not seq:
-            raise ValueError("blocks is empty")
-        out = []
-        for b in seq:
-            if not isinstance(b, (int, np.integer)) or not -depth <= b < depth:
-                raise ValueError(f"block {b!r}: an integer in [-{depth}, {depth})")
-            out.append(int(b) % depth)
-        if any(b <= a for a, b in zip(out, out[1:])):
-            raise ValueError(f"blocks {seq} -> {tuple(out)}: the indices must be strictly ascending")
-        return tuple(out)
+        return ascending_indices(blocks, self.cfg.depth, "block")
 
     def _attention_args(self, images, blocks, heads, logits, nslices):
         """(arguments of the attention entries, cache key, buffers, what the caller gets) for one batch: attn16 and map32 live beside the
@@ -270,6 +260,36 @@ class ViTEngine(NativeEngine):
         self._check_images(images)
         args, okey, bufs, out = self._attention_args(images, blocks, heads, logits, nstreams)
         return self._capture("_attention_graph_create", images, args, okey, bufs, out, self._attention_out)
+
+    # ---- hidden states (include/ivit_hidden.h): the outputs of chosen blocks, NativeEngine's with a ViT's planes
+    HIDDEN_CLASS_ROW = True
+    HIDDEN_SITE = "block"
+
+    def _hidden_sites(self):
+        return self.cfg.depth
+
+    def _hidden_plane(self, i):
+        return self.cfg.num_tokens, self.cfg.embed_dim, self.cfg.img_size // self.cfg.patch_size
+
+    def _hidden_views(self, hid16, hid32, planes, B, layout):
+        (T, D, g), n = planes[0], len(planes)
+        assert T == g * g + 1, "one class token in front of a square grid of patches"
+        if hid32 is not None:
+            hid32 = hid32.view(n, B, D, g, g) if layout == "grid" else hid32.view(n, B, T, D)
+        return hid16.view(n, B, T, D), hid32
+
+    def hidden_states(self, images, blocks=-1, layout=None, logits=False, nslices=1, copy=False):
+        """images int8 [B, C, H, W] -> (hid16, hid32), or (hid16, hid32, logits) with logits=True: the outputs of the blocks asked
+        for (normalised as `attention`'s are).  hid16 int16 [n, B, T, D]: plane j holds the integers of
+        blocks.{blocks[j]}.qact4 of the reference (vit_quant.py:141-143), class row included, scale `hidden_scale_host(blocks[j])`.
+        hid32: None (layout=None), float32 [n, B, T, D] (layout="tokens") or [n, B, D, gh, gw] (layout="grid": the patch rows on
+        the patch grid, channel-major; the class token has no place there) — `predict.hidden_reference` of hid16.  See
+        NativeEngine.hidden_states; a tap of the last block runs that block on all rows, the logits are forward's all the same."""
+        return super().hidden_states(images, blocks, layout, logits, nslices, copy)
+
+    def capture_hidden_states(self, images, blocks=-1, layout=None, logits=False, nstreams=1):
+        """hipGraph of one hidden_states on fixed buffers; returns a callable that replays it and returns what it returns"""
+        return super().capture_hidden_states(images, blocks, layout, logits, nstreams)
 
     def workspace(self, B, key=None):
         wkey = (B, key)

@@ -5,7 +5,8 @@ The base owns the device and handle, the constants blob, the workspace cache and
 with the top-k of the dequantised logits behind them, ivit_<model>_predict), `score` / `capture_score` (with the labels' rank and
 negative log-likelihood behind them instead, ivit_<model>_score of include/ivit_eval.h) and `features` / `capture_features` (the
 reference's forward_features: the integers the head reads and their fp32 form, with or without the head, ivit_<model>_features of
-include/ivit_features.h).  Every eager way is its arguments and one `_eager` call, every captured way its arguments and one
+include/ivit_features.h) and `hidden_states` / `capture_hidden_states` (the 16-bit outputs of chosen blocks or stages and their
+fp32 form, ivit_<model>_hidden_states of include/ivit_hidden.h).  Every eager way is its arguments and one `_eager` call, every captured way its arguments and one
 `_capture` call; what lives beside a logits buffer (idx / val, rank / nll, feat8 / feat32, a ViT's attn16 / map32) follows the one
 rule of `SideOutputs`.  A subclass names its C prefix, builds its parameter structs (`_native_params`), says where its feature
 scale lies (`feature_scale_host`, `num_features`) and keeps its `forward_ops`.  torch is used for device memory and streams only.
@@ -22,6 +23,29 @@ _P = ctypes.c_void_p
 
 def _ptr(t):
     return _P(t.data_ptr())
+
+
+def _clone(out):
+    """clones of the tensors of a result, tuples of them and None kept as they are"""
+    if isinstance(out, tuple):
+        return tuple(_clone(t) for t in out)
+    return out if out is None else out.clone()
+
+
+def ascending_indices(indices, n, what):
+    """an int or a sequence of indices, negative ones counting from the end -> strictly ascending tuple in [0, n); ValueError
+    otherwise.  `what`: what an index names (a block, a stage), for the error texts.  THE rule of every index list an engine takes"""
+    seq = (indices,) if isinstance(indices, (int, np.integer)) else tuple(indices)
+    if not seq:
+        raise ValueError(f"no {what} given")
+    out = []
+    for b in seq:
+        if not isinstance(b, (int, np.integer)) or not -n <= b < n:
+            raise ValueError(f"{what} {b!r}: an integer in [-{n}, {n})")
+        out.append(int(b) % n)
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"{what}s {seq} -> {tuple(out)}: the indices must be strictly ascending")
+    return tuple(out)
 
 
 class ShapeCache:
@@ -92,6 +116,7 @@ class NativeEngine:
         self._graphs = []
         # (idx, val) per (batch, slices, k); (rank, nll) and (feat8, feat32) per (batch, slices): one SideOutputs per kind
         self._predict_out, self._score_out, self._features_out = (SideOutputs(self._native_ws) for _ in range(3))
+        self._hidden_out = SideOutputs(self._native_ws)     # (hid16, hid32, index list) per (batch, slices, sites, layout)
         self._gstream = None                    # the stream graphs are captured and replayed on, made by the first capture
         self._head_scale_host = None
         self.last_logits = None
@@ -185,6 +210,76 @@ class NativeEngine:
         mode = _lib.IVIT_FEATURES_UNIT if normalize else _lib.IVIT_FEATURES_DEQUANT
         return (args[:-1] + (_ptr(lg) if logits else None, _ptr(feat8), float(self.feature_scale_host()), mode, _ptr(feat32)), key,
                 (ws, lg, feat8, feat32))
+
+    # ---- hidden states (include/ivit_hidden.h): the outputs of chosen blocks (ViT) or stages (Swin).  A subclass says how many sites
+    # it has, what a plane looks like and whether row 0 is a class token
+    HIDDEN_CLASS_ROW = False        # True: the grid form drops row 0 of every plane
+    HIDDEN_SITE = "site"            # what an index names, for the error texts
+
+    def _hidden_sites(self):
+        """number of sites: depth of a ViT, num_layers of a Swin"""
+        raise NotImplementedError
+
+    def _hidden_plane(self, i):
+        """(tokens, width, grid side) of site i's output"""
+        raise NotImplementedError
+
+    def _hidden_views(self, hid16, hid32, planes, B, layout):
+        """what the caller gets for the packed buffers: per-model views"""
+        raise NotImplementedError
+
+    def hidden_scale_host(self, i):
+        """host float: the per-tensor scale of site i's output (the reference's blocks.{i}.qact4 of a ViT, that of the last block
+        of stage i of a Swin), as the native model holds it; negative indices count from the end"""
+        n = self._hidden_sites()
+        if not isinstance(i, (int, np.integer)) or not -n <= i < n:
+            raise ValueError(f"{self.HIDDEN_SITE} {i!r}: an integer in [-{n}, {n})")
+        s = ctypes.c_float()
+        self._entry("_hidden_scale", self.model, int(i) % n, ctypes.byref(s))
+        return float(s.value)
+
+    def _hidden_list(self, sites):
+        return ascending_indices(sites, self._hidden_sites(), self.HIDDEN_SITE)
+
+    def _hidden_args(self, images, sites, layout, logits, nslices):
+        """(arguments of the hidden_states entries, cache key, buffers, what the caller gets) for one batch: hid16 and hid32 are
+        packed plane after plane, live beside the logits buffer and follow its rule (SideOutputs)"""
+        sites = self._hidden_list(sites)
+        if layout not in (None, "tokens", "grid"):
+            raise ValueError(f"layout = {layout!r}: None, 'tokens' or 'grid'")
+        args, key, (ws, lg) = self._args(images, nslices)
+        B, n = images.shape[0], len(sites)
+        planes = [self._hidden_plane(i) for i in sites]
+        t0 = 1 if (self.HIDDEN_CLASS_ROW and layout == "grid") else 0
+        n16, n32 = sum(B * T * C for T, C, _ in planes), sum(B * (T - t0) * C for T, C, _ in planes)
+        okey = key + (sites, layout)
+        hid16, hid32, host = self._hidden_out.get(okey, lg, lambda: (
+            self._empty(torch.int16, n16), None if layout is None else self._empty(torch.float32, n32), (ctypes.c_int * n)(*sites)))
+        mode = _lib.IVIT_HIDDEN_GRID if layout == "grid" else _lib.IVIT_HIDDEN_TOKENS
+        args = args[:-1] + (_ptr(lg) if logits else None, host, n, _ptr(hid16), mode, None if hid32 is None else _ptr(hid32))
+        out = self._hidden_views(hid16, hid32, planes, B, layout) + ((lg,) if logits else ())
+        return args, okey, (ws, lg, hid16, hid32, host), out
+
+    def hidden_states(self, images, sites=-1, layout=None, logits=False, nslices=1, copy=False):
+        """images int8 [B, C, H, W] -> (hid16, hid32), or (hid16, hid32, logits) with logits=True: the 16-bit outputs of the sites
+        asked for (an int or a sequence; negative indices count from the end; strictly ascending after that, else ValueError) — the
+        integers of the reference's closing QuantAct of a block, qact4, whose scale is `hidden_scale_host(i)` — and, with layout
+        "tokens" or "grid", their fp32 form as `predict.hidden_reference` states it (None with layout=None).  One native call: the
+        last launch of a tapped block writes the caller's plane, no copy; one launch per plane for the fp32 form.  Without `logits`
+        the forward ends behind the last site asked for; with it the int32 logits are forward's (and `last_logits`).  The results
+        are the engine's own buffers for this (batch, nslices, sites, layout): copy=True (or clone) to keep them across calls."""
+        def plan():
+            args, _, bufs, out = self._hidden_args(images, sites, layout, logits, nslices)
+            return args, bufs[1] if logits else None, out
+        out = self._eager("_hidden_states", images, False, plan)
+        return _clone(out) if copy else out
+
+    def capture_hidden_states(self, images, sites=-1, layout=None, logits=False, nstreams=1):
+        """hipGraph of one hidden_states on fixed buffers; returns a callable that replays it and returns what `hidden_states`
+        returns.  A replay reads `images` as they are then."""
+        self._check_images(images)
+        args, okey, bufs, out = self._hidden_args(images, sites, layout, logits, nstreams)
+        return self._capture("_hidden_states_graph_create", images, args, okey, tuple(b for b in bufs if b is not None), out, self._hidden_out)
 
     def _check_images(self, images):
         assert images.dtype == torch.int8 and images.is_contiguous() and images.device == self.device

@@ -18,7 +18,9 @@ vit_quant.py:278-282 / swin_quant.py:560-564), takes the cross-entropy and top-1
     IntSoftmax's output (vit_quant.py:70-76, quant_modules.py:469-497) from a block's q and k, and `attention_map_reference` that of
     `ivit_attention_map_f32`, the fp32 map over the patches (ViTEngine's `attention`);
   * `class_map_reference` is the numpy statement of the contract of `ivit_class_map` (include/ivit_classmap.h): a Swin's
-    class-activation maps, the head's weight rows against every final-stage token, in exact integers (SwinEngine's `class_map`).
+    class-activation maps, the head's weight rows against every final-stage token, in exact integers (SwinEngine's `class_map`);
+  * `hidden_reference` is the numpy statement of the contract of `ivit_hidden_f32` (include/ivit_hidden.h): the fp32 form of a
+    block's or a stage's 16-bit output, the integers times the site's scale (the engines' `hidden_states`).
 """
 import numpy as np
 import torch
@@ -223,6 +225,32 @@ def class_map_reference(tok8, head_w, idx, class_scale=None):
     map32 = cam32.astype(np.float32) * class_scale[np.where(valid, idx, 0)][:, :, None]
     assert map32.dtype == np.float32
     return cam32, np.where(valid[:, :, None], map32, np.float32(np.nan)).astype(np.float32)
+
+
+def hidden_reference(q16, scale, layout="tokens", t0=0):
+    """q16 int16 [B, T, C] (the integers of a block's closing QuantAct, qact4: vit_quant.py:141-143, SwinTransformerBlock.forward),
+    scale the site's per-tensor scale -> float32 [B, T - t0, C] (layout "tokens") or [B, C, T - t0] (layout "grid", channel-major:
+    the caller views the last axis as gh x gw).
+
+    out = fl32(fl32(q) * scale) for the rows t0 .. T - 1 of every image: the conversion of an int16 is exact, then ONE float32
+    multiply — the tensor QuantAct.forward returns in the reference (x = q * s, quant_modules.py:204-206), bit for bit.  t0 = 1
+    drops a ViT's class row.  The grid form is the transpose of the tokens form, nothing else.  scale must be finite and positive,
+    C a multiple of 8 (the limits of the entry)."""
+    q16 = np.asarray(q16)
+    assert q16.dtype == np.int16 and q16.ndim == 3
+    B, T, C = q16.shape
+    scale = np.float32(scale)
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"scale = {scale!r}: finite and positive")
+    if C % 8:
+        raise ValueError(f"C = {C}: a multiple of 8")
+    if not 0 <= t0 < T:
+        raise ValueError(f"t0 = {t0}: in [0, {T})")
+    if layout not in ("tokens", "grid"):
+        raise ValueError(f"layout = {layout!r}: 'tokens' or 'grid'")
+    out = q16[:, t0:, :].astype(np.float32) * scale
+    assert out.dtype == np.float32
+    return np.ascontiguousarray(out if layout == "tokens" else out.transpose(0, 2, 1))
 
 
 def embed(engine, batches, transform=None, normalize=True):

@@ -15,7 +15,8 @@ Constants are derived once on the host with the reference's fp32/fp64 operation 
 (`freeze.freeze_swin`).  `forward` / `capture` / `predict` / `capture_predict` are NativeEngine's
 (ivit_amd.native); `class_map` / `capture_class_map` are this engine's own: the same runner with the
 final-stage tokens handed out and the class-activation maps behind them (`ivit_swin_class_map`,
-include/ivit_classmap.h); `forward_ops` issues the same forward one C-ABI call per operator.
+include/ivit_classmap.h); `hidden_states` / `capture_hidden_states` (stage outputs, the feature pyramid,
+include/ivit_hidden.h) are NativeEngine's with a Swin's planes; `forward_ops` issues the same forward one C-ABI call per operator.
 torch is used for device memory and streams only.
 """
 import ctypes
@@ -232,6 +233,39 @@ class SwinEngine(NativeEngine):
         self._check_images(images)
         args, okey, bufs, out = self._class_map_args(images, k, classes, logits, nstreams)
         return self._capture("_class_map_graph_create", images, args, okey, bufs, out, self._class_map_out)
+
+    # ---- hidden states (include/ivit_hidden.h): the outputs of chosen stages, NativeEngine's with a Swin's planes
+    HIDDEN_SITE = "stage"
+
+    def _hidden_sites(self):
+        return self.cfg.num_layers
+
+    def _hidden_plane(self, i):
+        res = self.cfg.grid >> i
+        return res * res, self.cfg.embed_dim << i, res
+
+    def _hidden_views(self, hid16, hid32, planes, B, layout):
+        v16, v32, o16 = [], [], 0
+        for L, C, res in planes:                             # no class row: both buffers are packed alike
+            v16.append(hid16[o16:o16 + B * L * C].view(B, L, C))
+            if hid32 is not None:
+                p = hid32[o16:o16 + B * L * C]
+                v32.append(p.view(B, C, res, res) if layout == "grid" else p.view(B, L, C))
+            o16 += B * L * C
+        return tuple(v16), (tuple(v32) if hid32 is not None else None)
+
+    def hidden_states(self, images, stages=-1, layout=None, logits=False, nslices=1, copy=False):
+        """images int8 [B, C, H, W] -> (hid16, hid32), or (hid16, hid32, logits) with logits=True: the feature pyramid.  hid16: a
+        tuple of int16 views [B, L_s, C_s], one per stage asked for — the output of the stage's last block in front of
+        PatchMerging (BasicLayer.forward), L_s = (grid >> s)^2 row-major over the stage's grid, C_s = embed_dim << s, scale
+        `hidden_scale_host(s)`.  hid32: None (layout=None) or a tuple of float32 views, [B, L_s, C_s] (layout="tokens") or
+        [B, C_s, res_s, res_s] (layout="grid") — `predict.hidden_reference` of the plane.  The views share one packed buffer each.
+        See NativeEngine.hidden_states."""
+        return super().hidden_states(images, stages, layout, logits, nslices, copy)
+
+    def capture_hidden_states(self, images, stages=-1, layout=None, logits=False, nstreams=1):
+        """hipGraph of one hidden_states on fixed buffers; returns a callable that replays it and returns what it returns"""
+        return super().capture_hidden_states(images, stages, layout, logits, nstreams)
 
     def workspace(self, B, key=None):
         if (B, key) in self._ws:
