@@ -1,4 +1,4 @@
-"""include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h and include/ivit_hidden.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
+"""include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h and include/ivit_search.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
 tools/gen_twin_header.py prints the CPU twin's prototypes from it, the tests bind the twin and walk the entry points through it.
 Standard library only, so a tool loads this file without the package (and without torch).
 
@@ -13,6 +13,7 @@ Standard library only, so a tool loads this file without the package (and withou
     ATTNMAP_ABI     the same of include/ivit_attnmap.h, the fourth (IVIT_ATTNMAP_VERSION and the two modes of the fp32 map)
     CLASSMAP_ABI    the same of include/ivit_classmap.h, the fifth (IVIT_CLASSMAP_VERSION and the two modes of the runner)
     HIDDEN_ABI      the same of include/ivit_hidden.h, the sixth (IVIT_HIDDEN_VERSION and the two layouts of the fp32 form)
+    SEARCH_ABI      the same of include/ivit_search.h, the seventh (IVIT_SEARCH_VERSION)
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -36,6 +37,7 @@ FEATURES_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_features.h")
 ATTNMAP_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_attnmap.h")
 CLASSMAP_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_classmap.h")
 HIDDEN_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_hidden.h")
+SEARCH_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_search.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -183,3 +185,5 @@ with open(CLASSMAP_HEADER) as _f:
     CLASSMAP_ABI = parse(_f.read(), base=ABI)
 with open(HIDDEN_HEADER) as _f:
     HIDDEN_ABI = parse(_f.read(), base=ABI)
+with open(SEARCH_HEADER) as _f:
+    SEARCH_ABI = parse(_f.read(), base=ABI)

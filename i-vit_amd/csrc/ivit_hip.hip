@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h) over the gfx950 kernels.
+// include/ivit_hidden.h, include/ivit_search.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -35,6 +35,7 @@
 #include "ivit_attnmap.h"
 #include "ivit_classmap.h"
 #include "ivit_hidden.h"
+#include "ivit_search.h"
 #include "ivit_preprocess.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
@@ -2297,6 +2298,132 @@ extern "C" int ivit_hidden_f32(ivit_handle h, const int16_t *x16, float scale, i
         const unsigned gx = (unsigned)std::min<long long>((per + 255) / 256, 1 << 20);
         hidden_f32_kernel<false><<<dim3(gx, gy), 256, 0, h->stream>>>(x16, scale, batch, T, C, t0, out);
     }
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- gallery search (include/ivit_search.h)
+extern "C" int ivit_gallery_inv_norms(ivit_handle h, const int8_t *gallery, int64_t rows, int dim, float *inv_norm) {
+    CHECK_H(h);
+    REQUIRE(h, gallery && inv_norm && rows >= 0, "gallery or inv_norm is null, or rows is negative");
+    REQUIRE_A16(h, gallery, "gallery");
+    if (dim < 16 || dim > 65536 || (dim % 16) != 0) {
+        snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 16 in 16 .. 65536", __func__);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    REQUIRE_DISJOINT(h, gallery, (size_t)rows * dim, "gallery", inv_norm, (size_t)rows * 4, "inv_norm", OVL_IN);
+    if (rows == 0) return IVIT_OK;
+    const unsigned grid = (unsigned)std::min<long long>((rows + 15) / 16, 1 << 20);          // 16 rows per block, strided beyond
+    gallery_inv_norms_kernel<<<grid, 256, 0, h->stream>>>(gallery, (long long)rows, dim, inv_norm);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// the limits ivit_search_workspace_bytes and ivit_search_topk share, and the number of parts: the caller's, or about two workgroups
+// per CU of the handle's share in parts of at least 1024 rows (a part begins with every score surviving and ends with a compaction)
+static int search_shape_ok(ivit_handle h, const char *fn, int nq, long long rows, int dim, int k, int splits, int *parts) {
+    const char *bad = nullptr;
+    if (nq < 0 || rows < 0) bad = "nq or rows is negative";
+    else if (k < 1 || k > SEARCH_MAX_K || k > rows) bad = "k must be in 1 .. min(64, rows)";
+    else if (splits < 0 || splits > 65535) bad = "splits must be in 0 .. 65535";
+    if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    if (dim < SEARCH_MIN_DIM || dim > SEARCH_MAX_DIM || (dim % 64) != 0) {
+        snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 64 in 64 .. 1024", fn);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    long long s = splits;
+    if (s == 0) {
+        const long long cols = std::max(1ll, ((long long)nq + SEARCH_QB - 1) / SEARCH_QB);
+        s = std::max(1ll, std::min((2ll * persistent_cus(h) + cols - 1) / cols, rows / 1024));
+    }
+    *parts = (int)s;
+    return IVIT_OK;
+}
+
+extern "C" int ivit_search_workspace_bytes(ivit_handle h, int nq, int64_t rows, int dim, int k, int splits, size_t *bytes) {
+    CHECK_H(h);
+    REQUIRE(h, bytes, "bytes is null");
+    int parts = 0;
+    if (const int rc = search_shape_ok(h, __func__, nq, rows, dim, k, splits, &parts)) return rc;
+    *bytes = (size_t)nq * parts * k * 8;
+    return IVIT_OK;
+}
+
+// the second phase: the keys of a query in registers where they fit (16 or 64 per lane), rescanned from memory beyond
+template <bool PAIRS>
+static void search_select_launch(ivit_handle h, const unsigned long long *keys, const int32_t *idx_in, const float *val_in, int nq, long long n, int k,
+                                 int32_t *idx, float *val) {
+    const unsigned grid = (unsigned)((nq + 3ll) / 4);                       // one wavefront per query
+    if (n <= 1024) search_select_kernel<PAIRS, 16><<<grid, 256, 0, h->stream>>>(keys, idx_in, val_in, nq, n, k, idx, val);
+    else if (n <= 4096) search_select_kernel<PAIRS, 64><<<grid, 256, 0, h->stream>>>(keys, idx_in, val_in, nq, n, k, idx, val);
+    else search_select_kernel<PAIRS, 0><<<grid, 256, 0, h->stream>>>(keys, idx_in, val_in, nq, n, k, idx, val);
+}
+
+template <int KS>
+static int search_scan_launch(ivit_handle h, dim3 grid, size_t lds, const SearchArgs &a) {
+    return launch_dyn<search_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS)>>(h, grid, dim3(256), lds, a);
+}
+
+extern "C" int ivit_search_topk(ivit_handle h, const int8_t *query, int nq, const int8_t *gallery, int64_t rows, int dim, const float *weight,
+                                int k, int32_t index_base, int splits, void *workspace, size_t bytes, int32_t *idx, float *val) {
+    CHECK_H(h);
+    REQUIRE(h, query && gallery && idx && workspace, "query, gallery, idx or workspace is null");
+    int parts = 0;
+    if (const int rc = search_shape_ok(h, __func__, nq, rows, dim, k, splits, &parts)) return rc;
+    REQUIRE(h, index_base >= 0 && (long long)index_base + rows <= 0x7fffffffLL, "index_base must be >= 0 and index_base + rows <= 2^31 - 1");
+    const size_t nws = (size_t)nq * parts * k * 8;
+    REQUIRE(h, bytes >= nws, "workspace too small (ivit_search_workspace_bytes)");
+    REQUIRE_A16(h, query, "query");
+    REQUIRE_A16(h, gallery, "gallery");
+    REQUIRE_ALIGNED(h, workspace, "workspace", 8);
+    {
+        const size_t nout = (size_t)nq * k * 4;
+        const struct { const void *p; size_t n; const char *name; } ins[3] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"},
+                                                                           {weight, (size_t)rows * 4, "weight"}};
+        for (const auto &i : ins) {
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, idx, nout, "idx", OVL_IN);
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, val, nout, "val", OVL_IN);
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, workspace, bytes, "workspace", OVL_IN);
+        }
+        REQUIRE_DISJOINT(h, idx, nout, "idx", val, nout, "val", OVL_OUT);
+        REQUIRE_DISJOINT(h, idx, nout, "idx", workspace, bytes, "workspace", OVL_OUT);
+        REQUIRE_DISJOINT(h, val, nout, "val", workspace, bytes, "workspace", OVL_OUT);
+    }
+    if (nq == 0) return IVIT_OK;
+    SearchArgs a;
+    a.query = query; a.gallery = gallery; a.weight = weight; a.ws = (unsigned long long *)workspace;
+    a.rows = rows; a.per = (rows + parts - 1) / parts;
+    a.nq = nq; a.k = k; a.index_base = index_base; a.parts = parts;
+    const dim3 grid((unsigned)(((long long)nq + SEARCH_QB - 1) / SEARCH_QB), (unsigned)parts);
+    const size_t lds = search_lds_bytes(k);
+    int rc = IVIT_OK;
+    switch (dim / 64) {
+#define SEARCH_CASE(KS) case KS: rc = search_scan_launch<KS>(h, grid, lds, a); break;
+        SEARCH_CASE(1) SEARCH_CASE(2) SEARCH_CASE(3) SEARCH_CASE(4) SEARCH_CASE(5) SEARCH_CASE(6) SEARCH_CASE(7) SEARCH_CASE(8)
+        SEARCH_CASE(9) SEARCH_CASE(10) SEARCH_CASE(11) SEARCH_CASE(12) SEARCH_CASE(13) SEARCH_CASE(14) SEARCH_CASE(15) SEARCH_CASE(16)
+#undef SEARCH_CASE
+    }
+    if (rc != IVIT_OK) return rc;
+    LAUNCH_CHECK(h);
+    search_select_launch<false>(h, a.ws, nullptr, nullptr, nq, (long long)parts * k, k, idx, val);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_search_merge(ivit_handle h, const int32_t *idx_in, const float *val_in, int nq, int ncand, int k, int32_t *idx, float *val) {
+    CHECK_H(h);
+    REQUIRE(h, idx_in && val_in && idx && nq >= 0, "idx_in, val_in or idx is null, or nq is negative");
+    REQUIRE(h, k >= 1 && k <= SEARCH_MAX_K && ncand >= k, "k must be in 1 .. min(64, ncand)");
+    {
+        const size_t nin = (size_t)nq * ncand * 4, nout = (size_t)nq * k * 4;
+        REQUIRE_DISJOINT(h, idx_in, nin, "idx_in", idx, nout, "idx", OVL_IN);
+        REQUIRE_DISJOINT(h, idx_in, nin, "idx_in", val, nout, "val", OVL_IN);
+        REQUIRE_DISJOINT(h, val_in, nin, "val_in", idx, nout, "idx", OVL_IN);
+        REQUIRE_DISJOINT(h, val_in, nin, "val_in", val, nout, "val", OVL_IN);
+        REQUIRE_DISJOINT(h, idx, nout, "idx", val, nout, "val", OVL_OUT);
+    }
+    if (nq == 0) return IVIT_OK;
+    search_select_launch<true>(h, nullptr, idx_in, val_in, nq, (long long)ncand, k, idx, val);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

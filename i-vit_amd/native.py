@@ -6,7 +6,8 @@ with the top-k of the dequantised logits behind them, ivit_<model>_predict), `sc
 negative log-likelihood behind them instead, ivit_<model>_score of include/ivit_eval.h) and `features` / `capture_features` (the
 reference's forward_features: the integers the head reads and their fp32 form, with or without the head, ivit_<model>_features of
 include/ivit_features.h) and `hidden_states` / `capture_hidden_states` (the 16-bit outputs of chosen blocks or stages and their
-fp32 form, ivit_<model>_hidden_states of include/ivit_hidden.h).  Every eager way is its arguments and one `_eager` call, every captured way its arguments and one
+fp32 form, ivit_<model>_hidden_states of include/ivit_hidden.h); `retrieve` is `features` with a gallery search behind it
+(include/ivit_search.h, ivit_amd/search.py).  Every eager way is its arguments and one `_eager` call, every captured way its arguments and one
 `_capture` call; what lives beside a logits buffer (idx / val, rank / nll, feat8 / feat32, a ViT's attn16 / map32) follows the one
 rule of `SideOutputs`.  A subclass names its C prefix, builds its parameter structs (`_native_params`), says where its feature
 scale lies (`feature_scale_host`, `num_features`) and keeps its `forward_ops`.  torch is used for device memory and streams only.
@@ -359,6 +360,16 @@ class NativeEngine:
             args, _, (_, lg, feat8, feat32) = self._features_args(images, normalize, logits, nslices)
             return args, lg if logits else None, (feat8, feat32) + ((lg,) if logits else ())
         return self._eager("_features", images, copy, plan)
+
+    def retrieve(self, images, gallery, k=20, nslices=1, copy=False):
+        """images int8 [B, C, H, W], gallery an `ivit_amd.search.Gallery` of this backbone's features -> (idx int32 [B, k], val
+        float32 [B, k], feat8 int8 [B, num_features]) device tensors: `features` without the head, then `gallery.search(feat8, k)`
+        on the same stream (include/ivit_search.h) — the k nearest gallery rows of every image as `predict.search_reference`
+        states them.  idx / val are the gallery's buffers for this (B, k), feat8 the engine's: copy=True (or clone) to keep them."""
+        feat8 = self.features(images, nslices=nslices)[0]
+        idx, val = gallery.search(feat8, k=k)
+        out = (idx, val, feat8)
+        return tuple(t.clone() for t in out) if copy else out
 
     def _capture(self, suffix, images, args, key, bufs, out, side=None):
         """hipGraph of the entry PREFIX + suffix on fixed buffers; returns a callable that replays it and returns `out`.  `side`:

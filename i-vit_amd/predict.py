@@ -20,7 +20,11 @@ vit_quant.py:278-282 / swin_quant.py:560-564), takes the cross-entropy and top-1
   * `class_map_reference` is the numpy statement of the contract of `ivit_class_map` (include/ivit_classmap.h): a Swin's
     class-activation maps, the head's weight rows against every final-stage token, in exact integers (SwinEngine's `class_map`);
   * `hidden_reference` is the numpy statement of the contract of `ivit_hidden_f32` (include/ivit_hidden.h): the fp32 form of a
-    block's or a stage's 16-bit output, the integers times the site's scale (the engines' `hidden_states`).
+    block's or a stage's 16-bit output, the integers times the site's scale (the engines' `hidden_states`);
+  * `search_reference` and `inv_norms_reference` are the numpy statements of the contracts of `ivit_search_topk` and
+    `ivit_gallery_inv_norms` (include/ivit_search.h): the k nearest rows of an int8 gallery by exact dot product or by cosine
+    (`ivit_amd.search.Gallery`, the engines' `retrieve`); `embed8` is `embed`'s loop keeping the integers, `knn_evaluate` is
+    `evaluate`'s with the weighted k-NN vote (`ivit_amd.search.knn_classify`) in place of the head.
 """
 import numpy as np
 import torch
@@ -251,6 +255,98 @@ def hidden_reference(q16, scale, layout="tokens", t0=0):
     out = q16[:, t0:, :].astype(np.float32) * scale
     assert out.dtype == np.float32
     return np.ascontiguousarray(out if layout == "tokens" else out.transpose(0, 2, 1))
+
+
+SEARCH_MAX_K = 64   # SEARCH_MAX_K of csrc/ivit_search.h
+
+
+def inv_norms_reference(gallery8):
+    """gallery8 int8 [rows, dim] -> float32 [rows], every bit: ss = sum of q^2 as an exact integer, fl32(1.0 / sqrt(float64(ss))) with
+    the correctly rounded float64 root and division numpy has, rounded to float32 once; a row of zeros gives +0.0 (the idiom of
+    `features_reference`, mode 1).  As the `weight` of `search_reference` it makes the order of a query's neighbours the cosine
+    order."""
+    g = np.asarray(gallery8)
+    assert g.ndim == 2 and g.dtype == np.int8
+    ss = (g.astype(np.int64) ** 2).sum(axis=1)
+    inv = np.float64(1.0) / np.sqrt(np.where(ss > 0, ss, 1).astype(np.float64))
+    return np.where(ss > 0, inv, 0.0).astype(np.float32)
+
+
+def search_reference(query8, gallery8, weight, k, index_base=0):
+    """query8 int8 [nq, dim], gallery8 int8 [rows, dim], weight float32 [rows] or None -> (idx int32 [nq, k], val float32 [nq, k]).
+
+    dot[b, g] = query8[b] . gallery8[g] as an exact integer (|dot| <= 2^24 for dim <= 1024: its float32 form is exact);
+    v[b, g] = fl32(fl32(dot) * weight[g]), or fl32(dot) without a weight.  The order is `topk_reference`'s: descending by value,
+    -0.0 and +0.0 equal, equal values by ascending gallery index: row b of idx is index_base + the first k entries of
+    np.lexsort((arange(rows), -(v[b] + 0.0))); val holds the bits of v.  1 <= k <= min(64, rows); index_base >= 0 and
+    index_base + rows <= 2^31 - 1.  It is `topk_reference` on the dot products wherever both apply (k <= 16)."""
+    q, g = np.asarray(query8), np.asarray(gallery8)
+    assert q.ndim == 2 and g.ndim == 2 and q.dtype == np.int8 and g.dtype == np.int8 and q.shape[1] == g.shape[1]
+    rows = g.shape[0]
+    if not 1 <= k <= min(SEARCH_MAX_K, rows):
+        raise ValueError(f"k = {k} outside 1 .. min({SEARCH_MAX_K}, {rows})")
+    if index_base < 0 or index_base + rows > 2 ** 31 - 1:
+        raise ValueError(f"index_base = {index_base}: >= 0 and index_base + rows <= 2^31 - 1")
+    dot = q.astype(np.int32) @ g.astype(np.int32).T
+    v = dot.astype(np.float32)
+    if weight is not None:
+        weight = np.asarray(weight, dtype=np.float32)
+        assert weight.shape == (rows,)
+        v = v * weight[None, :]                                       # one float32 multiply
+    assert v.dtype == np.float32
+    cols = np.arange(rows)
+    idx = np.stack([np.lexsort((cols, -(row + np.float32(0.0))))[:k] for row in v]).reshape(-1, k) if len(v) else np.zeros((0, k), np.int64)
+    val = np.take_along_axis(v, idx.astype(np.int64), axis=1)
+    return (idx + index_base).astype(np.int32), val
+
+
+def _images_of(item, transform):
+    images = item[0] if isinstance(item, (tuple, list)) else item
+    return images if transform is None else transform(images)
+
+
+def embed8(engine, batches, transform=None):
+    """`embed`'s loop keeping the integers: every batch is one engine.features(images) — no head GEMM — and its int8 rows are kept
+    (a copy: the engine reuses its buffers), in order.  Nothing inside the loop synchronises.  Returns (feat8 int8
+    [N, num_features] on the engine's device, scale): the integers the head reads and their scale (`feature_scale_host()`), what
+    `ivit_amd.search.Gallery` takes."""
+    rows = [torch.as_tensor(engine.features(_images_of(item, transform))[0]).clone() for item in batches]
+    scale = float(engine.feature_scale_host())
+    if not rows:
+        return torch.zeros(0, int(engine.num_features), dtype=torch.int8, device=getattr(engine, "device", "cpu")), scale
+    return torch.cat(rows), scale
+
+
+def knn_evaluate(engine, gallery, batches, k=20, T=0.07, topk=(1, 5), transform=None):
+    """`evaluate`'s loop and return dict with the weighted k-NN vote in place of the head: `batches` yields (images, labels);
+    every batch is one engine.retrieve(images, gallery, k) and one `search.knn_classify` of its neighbours against
+    `gallery.labels` (cosines: the query's inverse norm is applied to a cosine gallery's values), and counts, for every j of `topk`,
+    the images whose label is among the first j classes of the vote.  The hit counts stay on the device until the loop ends.
+    Returns {"n": images, "correct": {j: count}, "acc": {j: 100 * count / n}}."""
+    from .search import knn_classify, query_inv_norms
+    topk = tuple(int(j) for j in topk)
+    if not topk or min(topk) < 1:
+        raise ValueError("topk must name ranks >= 1")
+    if gallery.labels is None:
+        raise ValueError("knn_evaluate needs a gallery with labels")
+    kk = min(max(topk), int(gallery.num_classes))
+    n, hits = 0, None
+    for images, labels in batches:
+        if transform is not None:
+            images = transform(images)
+        idx, val, feat8 = engine.retrieve(images, gallery, k=k)
+        order, _ = knn_classify(idx, val, gallery.labels, gallery.num_classes, T=T,
+                                query_inv_norm=query_inv_norms(feat8) if gallery.cosine else None)
+        labels = torch.as_tensor(labels).to(device=order.device, dtype=torch.int64, non_blocking=True).reshape(-1, 1)
+        within = (order[:, :kk] == labels).cumsum(1) > 0
+        step = torch.stack([within[:, min(j, kk) - 1].sum() for j in topk])
+        hits = step if hits is None else hits + step
+        n += order.shape[0]
+    if hits is None:
+        hits = torch.zeros(len(topk), dtype=torch.int64, device=getattr(engine, "device", "cpu"))
+    c = [int(v) for v in hits.cpu().tolist()]
+    correct = {j: c[t] for t, j in enumerate(topk)}
+    return {"n": n, "correct": correct, "acc": {j: (100.0 * v / n if n else float("nan")) for j, v in correct.items()}}
 
 
 def embed(engine, batches, transform=None, normalize=True):
