@@ -1,10 +1,12 @@
 // ivit_model.h — native runners for the frozen integer DeiT/ViT and Swin forwards (include/ivit.h,
 // "whole-model runner").  Each chains the C-ABI entry points of ivit_hip.hip in the order of the
 // reference's forward (vit_quant.py:254-282, swin_quant.py) and owns its ShiftGELU tables and plans.
-// What is not about a model is written once, first: SliceRunner (the slice streams, events and
-// handles), fork_join, graph_capture, RUN / fused_or and gelu_table.  Then each model: its struct, slice layout, slice body and create /
-// destroy / queries.  Last, once for both models, the runner entries: run_slices (what a runner checks, and in which order, before it
-// launches) and one body each for forward, predict, score and features.  Included at the end of ivit_hip.hip.
+// What is not about a model is written once, first: SliceRunner (the slice streams, events and handles), fork_join, graph_capture,
+// RUN / fused_or, the argument checks several entries share (extents_disjoint, index_list_ok), RunOut (every destination a forward
+// can write for its caller, and where a slice ends) and gelu_table.  Then each model: its struct, slice layout, slice body (run_slice,
+// overloaded) and create / destroy / queries.  Last, once for both models, the runner entries: slice_view and run_slices (where a
+// slice lies in the caller's arrays; what a runner checks, and in which order, before it launches) and one body per kind of entry.
+// Included at the end of ivit_hip.hip.
 #pragma once
 #include <vector>
 
@@ -99,50 +101,79 @@ int graph_capture(M *m, ivit_graph *out, Entry entry, Args... args) {
 #define RUN(call) do { const int rc_ = (call); if (rc_ != IVIT_OK) return rc_; } while (0)
 // REQUIRE for a check shared by several entries: the refusal names the entry the caller used
 #define REQUIRE_FN(h, fn, cond, msg) do { if (!(cond)) { snprintf((h)->err, sizeof((h)->err), "%s: %s", fn, msg); return IVIT_ERR_INVALID; } } while (0)
-// the runners' arrays (include/ivit.h, overlapping arguments): the workspace is written throughout, the logits at the end (null: none)
-static int runner_disjoint(ivit_handle h, const char *fn, const int8_t *images, size_t img_bytes, const void *workspace, size_t ws_bytes,
-                           const int32_t *logits, size_t logit_bytes) {
-    return ranges_disjoint(h, fn, images, img_bytes, "images", workspace, ws_bytes, "workspace", OVL_IN) &&
-                   ranges_disjoint(h, fn, images, img_bytes, "images", logits, logit_bytes, "logits", OVL_IN) &&
-                   ranges_disjoint(h, fn, workspace, ws_bytes, "workspace", logits, logit_bytes, "logits", OVL_OUT)
-               ? IVIT_OK : IVIT_ERR_INVALID;
+// the overlap table of an entry (include/ivit.h, overlapping arguments): every array it reads or writes, as the header spells it.
+// extents_disjoint judges the pairs (i, j) with j >= `from`, the first array this caller is responsible for: an entry judges the pairs
+// that involve its extra arrays before it calls run_slices, which judges those among images, workspace and logits.  Two arrays that
+// are only read may overlap; the first overlap found is the refusal
+struct Extent { const void *p; size_t bytes; const char *name; bool read_only; };
+template <int N>
+int extents_disjoint(ivit_handle h, const char *fn, const Extent (&a)[N], int from) {
+    for (int i = 0; i < N; ++i)
+        for (int j = std::max(i + 1, from); j < N; ++j)
+            if (!(a[i].read_only && a[j].read_only) &&
+                !ranges_disjoint(h, fn, a[i].p, a[i].bytes, a[i].name, a[j].p, a[j].bytes, a[j].name, a[i].read_only || a[j].read_only ? OVL_IN : OVL_OUT))
+                return IVIT_ERR_INVALID;
+    return IVIT_OK;
 }
-// idx / val of the predict entries against the forward's arrays and each other, judged BEFORE the forward is launched (ivit_logits_topk
-// judges logits / idx / val again behind it); a batch the workspace query refuses is left to the forward's own argument checks
-static int predict_disjoint(ivit_handle h, const char *fn, const int8_t *images, size_t img_bytes, const void *workspace, size_t ws_bytes,
-                            const int32_t *logits, size_t logit_bytes, const int32_t *idx, const float *val, size_t k_bytes) {
-    const struct { const void *p; size_t n; const char *name; } out[2] = {{idx, k_bytes, "idx"}, {val, k_bytes, "val"}};
-    for (const auto &o : out)
-        if (!ranges_disjoint(h, fn, images, img_bytes, "images", o.p, o.n, o.name, OVL_IN) ||
-            !ranges_disjoint(h, fn, workspace, ws_bytes, "workspace", o.p, o.n, o.name, OVL_OUT) ||
-            !ranges_disjoint(h, fn, logits, logit_bytes, "logits", o.p, o.n, o.name, OVL_OUT))
-            return IVIT_ERR_INVALID;
-    return ranges_disjoint(h, fn, idx, k_bytes, "idx", val, k_bytes, "val", OVL_OUT) ? IVIT_OK : IVIT_ERR_INVALID;
+// a caller's list of blocks or stages: `n` strictly ascending indices in [0, sites); `name`: the list as the header spells it
+inline int index_list_ok(ivit_handle h, const char *fn, const int *list, int n, const char *name, int sites) {
+    bool ok = list && n >= 1 && n <= sites;
+    for (int j = 0; ok && j < n; ++j) ok = list[j] >= 0 && list[j] < sites && (j == 0 || list[j] > list[j - 1]);
+    if (ok) return IVIT_OK;
+    snprintf(h->err, sizeof(h->err), "%s: %s must be 1 .. %d strictly ascending indices in [0, %d)", fn, name, sites, sites);
+    return IVIT_ERR_INVALID;
 }
 // a fused entry point where it takes the case (`fused`: its status, or IVIT_ERR_UNSUPPORTED without calling it), else the launches it
 // stands for; any other status of the fused entry is the slice's
 template <class Fallback>
 int fused_or(int fused, Fallback &&fallback) { return fused == IVIT_ERR_UNSUPPORTED ? fallback() : fused; }
 
-// the class-token rows a caller taps (include/ivit_attnmap.h): block indices, strictly ascending; the slice's first row of plane 0 of
-// the caller's attn16 [nblocks, batch, H, T]; and the plane stride batch * H * T in elements
-struct AttnTap {
-    const int *blocks;
-    int nblocks;
-    uint16_t *attn16;
-    size_t plane;
-};
+// What a forward writes for its caller: every destination a runner entry can ask for — the whole batch's as the entry fills it in,
+// one slice's as run_slice sees it (slice_view).  An absent destination is null or empty; an entry sets only what its model has
+struct RunOut {
+    explicit RunOut(int32_t *logits_) : logits(logits_) {}
+    int32_t *logits;              // the head's accumulators [batch, num_classes]; null: no head launch
+    // the features [batch, num_features] (include/ivit_features.h): the final norm (ViT) or the pool (Swin) writes here, not the workspace
+    int8_t *feat8 = nullptr;
+    // a Swin's final-stage tokens [batch, L, C] (include/ivit_classmap.h), tok_image = L * C: the final norm writes here, the pool reads it
+    int8_t *tok8 = nullptr; size_t tok_image = 0;
+    // a ViT's class-token probabilities (include/ivit_attnmap.h) of blocks[n], strictly ascending, into attn16 [n, batch, H, T]: one
+    // ivit_attention_cls_probs directly behind the block's qkv launch (q and k have the same [B*H, T, dh] layout whichever qkv or
+    // attention form the block takes).  image = H * T and plane = batch * H * T elements; a slice's attn16 is its first row of plane 0
+    struct {
+        const int *blocks = nullptr; int n = 0;
+        uint16_t *attn16 = nullptr;
+        size_t image = 0, plane = 0;
+        uint16_t *rows(int t) const { return attn16 + plane * (size_t)t; }
+    } attn;
+    // the 16-bit outputs of idx[n], strictly ascending — blocks of a ViT (qact4, vit_quant.py:141-143), stages of a Swin (the stage's
+    // last block, in front of PatchMerging) — into the caller's packed hid16 (include/ivit_hidden.h).  Plane j starts start[j] elements
+    // in and takes image[j] = T_j * C_j elements per image; a slice's rows follow those of the b0 images before it.  The last launch of
+    // a tapped block writes there instead of into the workspace, and from then on the stream `x` is the caller's plane.  The stream is
+    // never written in place: every later write goes to a workspace buffer
+    struct {
+        const int *idx = nullptr; int n = 0;
+        int16_t *hid16 = nullptr;
+        const size_t *start = nullptr, *image = nullptr; size_t b0 = 0;
+        int16_t *rows(int j) const { return hid16 + start[j] + b0 * image[j]; }
+    } hid;
+    bool any() const { return logits || feat8 || tok8 || attn.n || hid.n; }
 
-// the block / stage outputs a caller taps (include/ivit_hidden.h): indices, strictly ascending; the slice's first row of plane 0 of the
-// caller's hid16; and where plane j lies from there, in elements: j * plane for a ViT (planes of batch * T * D), off[j] for a Swin
-// (planes of different sizes, packed; slice_run adds the slice's rows).  The last launch of a tapped block writes there instead of
-// into the workspace, and from then on the stream `x` is the caller's plane: every later write goes to a workspace buffer
-struct HidTap {
-    const int *idx;
-    int n;
-    int16_t *hid16;
-    size_t plane;
-    size_t off[4];
+    // THE rule for "nothing the caller asked for lies behind this point, the slice ends here": asked behind an attention tap, behind a
+    // tapped block or stage and behind a Swin's final norm, with the taps taken so far and whether the final norm has run.  feat8 and
+    // logits lie behind everything, a Swin's tok8 behind its last stage.  What the entries ask for — logits, feat8, tok8, the attention
+    // tap, the hidden tap; a ViT has no tok8, a Swin no attention tap — the last launch of the slice, and who asks:
+    //   logits, alone or with any    the head                                              every entry
+    //   feat8, no logits             the final norm (ViT) / the pool (Swin)                features
+    //   ViT attn, no logits          the last tapped block's cls_probs                     ivit_vit_attention
+    //   ViT hid, no logits           the last tapped block's Mlp launch                    hidden_states
+    //   ViT attn and hid             no entry asks for both.  Without logits: the later of the two last taps (the three hand-written
+    //                                conditions this rule replaced ran on to the final norm where that was the attention tap)
+    //   Swin tok8, no logits         the final norm                                        ivit_swin_class_map, IVIT_CLASSMAP_GIVEN
+    //   Swin hid, no logits          the last tapped stage's last Mlp launch, in front of its merge      hidden_states
+    bool done(int tapped, int hidden, bool normed) const {
+        return !logits && !feat8 && tapped >= attn.n && hidden >= hid.n && (normed || !tok8);
+    }
 };
 
 // block i's ShiftGELU table
@@ -210,7 +241,7 @@ inline bool mlp_plan_shape(int C, int Hd) {
     return (C == Mlp384Geo::C && Hd == Mlp384Geo::HD) || (C == Mlp256Geo::C && Hd == Mlp256Geo::HD) || (C == Mlp192Geo::C && Hd == Mlp192Geo::HD);
 }
 
-// THE rule for "this block's Mlp is one ivit_mlp_fused_planned launch at M tokens": run_slice, swin_run_slice and the
+// THE rule for "this block's Mlp is one ivit_mlp_fused_planned launch at M tokens": both run_slice bodies and the
 // ivit_*_fused_mlp_blocks queries all ask here.  No token-count threshold: at width 192 the fused launch measured faster than
 // the three-launch chain at every size tried, 197 tokens (DeiT-T batch 1: 15.8 against 20.0 us) to 200 704 (profiles/README.md)
 inline bool mlp_plan_fuses(ivit_mlp_plan mp, ivit_dyadic res_main, ivit_dyadic res_res, long long /*M*/) {
@@ -255,34 +286,25 @@ int vit_attention(const ivit_vit_s *m, ivit_handle h, int i, const int8_t *q, co
                : ivit_attention_fused(h, q, k, vt, b.dy_qk, b.s_softmax, b.dy_pv, ctx, B, H, T, dh, ldv);
 }
 
-// one slice on handle `h`
-// `Bmax`: images of the LARGEST slice of this forward — every slice uses that slice's buffer layout, so the regions
-// zeroed by ivit_vit_workspace_init are the ones the kernels see whatever the (ragged) slice sizes are
-// `feat8`: the slice's rows of the caller's features [B, D] (include/ivit_features.h), where the final norm writes instead of the
-// workspace, or null; `logits`: null ends the slice in front of the head
-// `tap`: null, or the blocks whose class-token probabilities go to the caller's attn16, one ivit_attention_cls_probs directly behind
-// the block's qkv launch (q and k have the same [B*H, T, dh] layout whichever qkv or attention form the block takes); with neither
-// logits nor feat8 the slice ends behind the last tap
-// `hid`: null, or the blocks whose 16-bit output (qact4, vit_quant.py:141-143) goes to the caller's hid16 (include/ivit_hidden.h): the
-// block's last launch writes the slice's rows of the caller's plane, which is the stream from there on.  The stream is never written in
-// place: the proj launch writes the workspace buffer `x` is not (other), the Mlp launch the one its input is not — or the plane.  A
-// tapped last block runs on all rows (the class-token tail has B of them); with neither logits nor feat8 the slice ends behind the
-// last tapped block
-int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, int Bmax, char *ws, int32_t *logits, int8_t *feat8,
-              const AttnTap *tap, const HidTap *hid = nullptr) {
+// one slice of `B` images on handle `h`, into the slice's view `out` of what the caller asked for (RunOut: what each destination is,
+// and done(), where the slice ends)
+// `Blay`: the images the slice's buffers are laid out for (layout_images)
+// With a hidden tap the proj launch writes the workspace buffer `x` is not (other), the Mlp launch the one its input is not — or the
+// caller's plane.  A tapped last block runs on all rows (the class-token tail has B of them)
+int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, int Blay, char *ws, const RunOut &out) {
     const ivit_vit_config &c = m->cfg;
     const ivit_vit_params &P = m->prm;
     const int T = m->T, D = c.embed_dim, H = c.num_heads, dh = D / H, Hd = c.hidden_dim, ld = m->ld;
     const int M = B * T;
-    const SliceLayout L = slice_layout(m, Bmax);
+    const SliceLayout L = slice_layout(m, Blay);
     int8_t *patches = (int8_t *)(ws + L.patches), *a8 = (int8_t *)(ws + L.a8), *q = (int8_t *)(ws + L.q),
            *k = (int8_t *)(ws + L.k), *vt = (int8_t *)(ws + L.vt), *ctx8 = (int8_t *)(ws + L.ctx8),
-           *h8 = (int8_t *)(ws + L.h8), *g8 = (int8_t *)(ws + L.g8), *cls8 = feat8 ? feat8 : (int8_t *)(ws + L.cls8);
+           *h8 = (int8_t *)(ws + L.h8), *g8 = (int8_t *)(ws + L.g8), *cls8 = out.feat8 ? out.feat8 : (int8_t *)(ws + L.cls8);
     int16_t *patch16 = (int16_t *)(ws + L.patch16), *const xa = (int16_t *)(ws + L.xa), *const xb = (int16_t *)(ws + L.xb), *x = xa;
     // the workspace stream buffer that `cur` is not (xa behind a caller's plane): without a tap xa -> xb -> xa, block after block
     auto other = [&](const int16_t *cur) { return cur == xa ? xb : xa; };
     // the class-token tail computes B rows of the last block: not where the caller asked for that block's output
-    const bool tailed = cls_tail(m) && !(hid && hid->idx[hid->n - 1] == c.depth - 1);
+    const bool tailed = cls_tail(m) && !(out.hid.n && out.hid.idx[out.hid.n - 1] == c.depth - 1);
     // PatchEmbed + class token + position embedding: one GEMM launch that gathers its A rows from the images and finishes the rows in its
     // epilogue (round 6), or im2col -> GEMM -> embed_finish where that form does not apply
     RUN(fused_or((m->Kp == c.in_chans * c.patch_size * c.patch_size)
@@ -312,9 +334,9 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
                          RUN(ivit_layernorm_requant(h, x, M, D, D, b.s_ln1, b.n1_bias_int, b.n1_sc, b.n1_dy, a8));
                          return ivit_linear_i8_qkv_planned(h, m->plans[4 * i], a8, q, k, vt, B, T, H, dh, ldv);
                      }));
-        if (tap && tapped < tap->nblocks && tap->blocks[tapped] == i) {
-            RUN(ivit_attention_cls_probs(h, q, k, b.dy_qk, b.s_softmax, tap->attn16 + tap->plane * (size_t)tapped, B, H, T, dh));
-            if (++tapped == tap->nblocks && !logits && !feat8 && !hid) return IVIT_OK;
+        if (tapped < out.attn.n && out.attn.blocks[tapped] == i) {
+            RUN(ivit_attention_cls_probs(h, q, k, b.dy_qk, b.s_softmax, out.attn.rows(tapped), B, H, T, dh));
+            if (out.done(++tapped, hidden, false)) return IVIT_OK;
         }
         int16_t *y = other(x);          // proj's destination
         if (tail) {
@@ -337,10 +359,10 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
         const bool mlp_fast = mlp_plan_fuses(m->mlp_plans[i], b.res2_main, b.res2_res, Mb);
         const bool ln_lockstep = ln_mlp_plan_fuses(h, m->mlp_plans[i], b.res2_main, b.res2_res, Mb) == LN_MLP_LOCKSTEP;
         RUN(ivit_linear_i8_requant_residual_planned(h, m->plans[4 * i + 1], ctx8, b.res1_main, b.res1_res, x, y, Mb));
-        const bool hid_here = hid && hidden < hid->n && hid->idx[hidden] == i;
+        const bool hid_here = hidden < out.hid.n && out.hid.idx[hidden] == i;
         // the Mlp's destination: the caller's plane for a tapped block, else the workspace buffer its input is not (the tail: patch16,
         // which the proj launch has read)
-        { int16_t *t = x; x = y; y = hid_here ? hid->hid16 + hid->plane * (size_t)hidden : tail ? t : other(x); }
+        { int16_t *t = x; x = y; y = hid_here ? out.hid.rows(hidden) : tail ? t : other(x); }
         const int8_t *tab = gelu_table(m, i);
         RUN(fused_or(mlp_fast ? ivit_layernorm_mlp_fused_planned(h, m->mlp_plans[i], x, b.s_ln2, b.n2_bias_int, b.n2_sc, b.n2_dy, a8, tab, b.res2_main,
                                                                  b.res2_res, y, Mb)
@@ -359,31 +381,25 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
                                          });
                      }));
         x = y;
-        if (hid_here && ++hidden == hid->n && !logits && !feat8 && !(tap && tapped < tap->nblocks)) return IVIT_OK;
+        if (hid_here && out.done(tapped, ++hidden, false)) return IVIT_OK;
     }
     // final norm on the class-token rows only (row stride T*D; D where the last block left them compact), then the head's int32
     // accumulators
     RUN(ivit_layernorm_requant(h, x, B, D, tailed ? (int64_t)D : (int64_t)T * D, P.s_ln, P.n_bias_int, P.n_sc, P.n_dy, cls8));
-    if (logits) RUN(ivit_linear_i8(h, cls8, P.head_w, P.head_b, logits, B, c.num_classes, D));
+    if (out.logits) RUN(ivit_linear_i8(h, cls8, P.head_w, P.head_b, out.logits, B, c.num_classes, D));
     return IVIT_OK;
 }
 
-// what run_slices asks of a model: the workspace bytes of one slice of `Bmax` images, the width of a features row, and slice_run — one
-// slice of `nb` images, the batch's images b0 onward, on its own rows of logits, feat8 and (from here on) the tap
+// what run_slices asks of a model: the workspace bytes of one slice of `Bmax` images, the images a slice of `nb` lays its buffers
+// out for — those of the LARGEST slice of the forward, so the regions zeroed by ivit_vit_workspace_init are the ones the kernels see
+// whatever the (ragged) slice sizes are —, the width of a features row, and run_slice
 inline size_t slice_stride(const ivit_vit_s *m, int Bmax) { return slice_layout(m, Bmax).total; }
+inline int layout_images(const ivit_vit_s *, int, int Bmax) { return Bmax; }
 inline int num_features(const ivit_vit_s *m) { return m->cfg.embed_dim; }
 // ... and of its hidden states (include/ivit_hidden.h): how many sites it has (blocks), the tokens and the width of site i's plane
 inline int hidden_sites(const ivit_vit_s *m) { return m->cfg.depth; }
 inline int hidden_tokens(const ivit_vit_s *m, int) { return m->T; }
 inline int hidden_width(const ivit_vit_s *m, int) { return m->cfg.embed_dim; }
-int slice_run(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int b0, int nb, int Bmax, char *ws, int32_t *logits, int8_t *feat8,
-              const AttnTap *tap, int8_t * /*tok8: a Swin's*/, const HidTap *hid) {
-    AttnTap mine;
-    if (tap) { mine = *tap; mine.attn16 += (size_t)b0 * m->cfg.num_heads * m->T; }
-    HidTap planes;
-    if (hid) { planes = *hid; planes.hid16 += (size_t)b0 * hidden_tokens(m, 0) * hidden_width(m, 0); }
-    return run_slice(m, h, images, nb, Bmax, ws, logits, feat8, tap ? &mine : nullptr, hid ? &planes : nullptr);
-}
 
 }  // namespace
 
@@ -589,22 +605,16 @@ int swin_mlp_mode(const ivit_swin_s *m, int bi, int C, long long M) {
     return mlp_plan_fuses(m->mlp_plans[bi], m->blocks[bi].res2_main, m->blocks[bi].res2_res, M) ? 2 : 0;
 }
 
-// `feat8`: the slice's rows of the caller's features [B, C] (include/ivit_features.h), where the pool writes instead of the
-// workspace, or null; `logits`: null ends the slice in front of the head
-// `tok8`: the slice's rows of the caller's final-stage tokens [B, L, C] (include/ivit_classmap.h), where the final norm writes instead
-// of the workspace and the pool reads, or null; without logits and without feat8 the slice ends behind the final norm
-// `hid`: null, or the stages whose output — that of the stage's last block, in front of PatchMerging — goes to the caller's hid16
-// (include/ivit_hidden.h): that block's Mlp launch writes the slice's rows of the caller's plane, which is the stream from there on.
-// As in run_slice the stream is never written in place; behind a tapped stage the merge's reduction writes the next stage's stream
-// into the workspace, never into the plane.  With neither logits, feat8 nor tok8 the slice ends behind the last tapped stage
-int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, char *ws, int32_t *logits, int8_t *feat8, int8_t *tok8,
-                   const HidTap *hid = nullptr) {
+// one slice of `B` images on handle `h`, into the slice's view `out` of what the caller asked for (RunOut), its buffers laid out for
+// `Blay` images.  As in the ViT's run_slice the stream is never written in place; behind a tapped stage the merge's reduction writes the
+// next stage's stream into the workspace, never into the caller's plane
+int run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, int Blay, char *ws, const RunOut &out) {
     const ivit_swin_config &c = m->cfg;
     const ivit_swin_params &P = m->prm;
-    const SwinLayout Lw = swin_layout(m, B);
+    const SwinLayout Lw = swin_layout(m, Blay);
     int8_t *patches = (int8_t *)(ws + Lw.patches), *a8 = (int8_t *)(ws + Lw.a8), *qkv = (int8_t *)(ws + Lw.qkv),
            *ctx = (int8_t *)(ws + Lw.ctx), *h8 = (int8_t *)(ws + Lw.h8), *g8 = (int8_t *)(ws + Lw.g8),
-           *pool = feat8 ? feat8 : (int8_t *)(ws + Lw.pool);
+           *pool = out.feat8 ? out.feat8 : (int8_t *)(ws + Lw.pool);
     int16_t *const xa = (int16_t *)(ws + Lw.xa), *const xb = (int16_t *)(ws + Lw.xb), *x = xa, *t16 = (int16_t *)(ws + Lw.xc);
     auto other = [&](const int16_t *cur) { return cur == xa ? xb : xa; };      // the workspace stream buffer that `cur` is not
     int hidden = 0;
@@ -644,9 +654,9 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
             if (lp[1]) RUN(ivit_linear_i8_requant_residual_planned(h, lp[1], ctx, b.res1_main, b.res1_res, x, y, (int)M));
             else RUN(ivit_linear_i8_requant_residual(h, ctx, b.proj.w, b.proj.b, b.proj.dy, b.res1_main, b.res1_res, x, y, (int)M, C, C));
             // the Mlp's destination: the caller's plane for the last block of a tapped stage, else the workspace buffer its input is not
-            const bool hid_here = hid && hidden < hid->n && hid->idx[hidden] == li && bj == c.depths[li] - 1;
+            const bool hid_here = hidden < out.hid.n && out.hid.idx[hidden] == li && bj == c.depths[li] - 1;
             x = y;
-            y = hid_here ? hid->hid16 + hid->off[hidden] : other(x);
+            y = hid_here ? out.hid.rows(hidden) : other(x);
             const int mlp_mode = swin_mlp_mode(m, bi, C, M);
             // norm2 is a launch of its own in every stage.  (In the head of the C = 384 stage's fused Mlp it measured slower: Swin-T b256,
             // two slices, 4.76 against 4.70 ms same-box; the LayerNorm launch of one slice overlaps the other slice's kernels)
@@ -662,7 +672,7 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
                 RUN(ivit_linear_i8_requant_residual(h, g8, b.fc2.w, b.fc2.b, b.fc2.dy, b.res2_main, b.res2_res, x, y, (int)M, C, c.mlp_ratio * C));
             }
             x = y;
-            if (hid_here && ++hidden == hid->n && !logits && !feat8 && !tok8) return IVIT_OK;
+            if (hid_here && out.done(0, ++hidden, false)) return IVIT_OK;
         }
         if (li < c.num_layers - 1) {     // PatchMerging: gather -> LN(4C) -> qact1(8) -> reduction -> qact2(8)
             const ivit_swin_merge &g = m->merges[li];
@@ -684,34 +694,24 @@ int swin_run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, in
         }
     }
     const int C = E << (c.num_layers - 1);
-    if (tok8) a8 = tok8;
+    if (out.tok8) a8 = out.tok8;
     RUN(swin_ln(m, h, x, M, C, P.s_norm_in, P.n, L, false, a8));
-    if (!logits && !feat8) return IVIT_OK;
+    if (out.done(0, hidden, true)) return IVIT_OK;
     RUN((L & 1) ? ivit_avgpool_requant(h, a8, B, L, C, P.dy_pool, pool)
                 : ivit_avgpool_requant_scaled(h, a8, B, L, C, P.s_pool, P.dy_pool, pool));
-    if (logits) RUN(ivit_linear_i8(h, pool, P.head_w, P.head_b, logits, B, c.num_classes, C));
+    if (out.logits) RUN(ivit_linear_i8(h, pool, P.head_w, P.head_b, out.logits, B, c.num_classes, C));
     return IVIT_OK;
 }
 
-// what run_slices asks of a model, as for the ViT.  A slice lays its buffers out for its own images; a Swin has no class token to tap,
-// and gives every slice its own rows of the caller's final-stage tokens instead
+// what run_slices asks of a model, as for the ViT.  A slice lays its buffers out for its own images
 inline size_t slice_stride(const ivit_swin_s *m, int Bmax) { return swin_layout(m, Bmax).total; }
+inline int layout_images(const ivit_swin_s *, int nb, int) { return nb; }
 inline int num_features(const ivit_swin_s *m) { return m->cfg.embed_dim << (m->cfg.num_layers - 1); }
 inline int final_tokens(const ivit_swin_s *m) { const int r = m->grid >> (m->cfg.num_layers - 1); return r * r; }
 // its hidden states are by stage: (grid >> s)^2 tokens of width embed_dim << s
 inline int hidden_sites(const ivit_swin_s *m) { return m->cfg.num_layers; }
 inline int hidden_tokens(const ivit_swin_s *m, int s) { const int r = m->grid >> s; return r * r; }
 inline int hidden_width(const ivit_swin_s *m, int s) { return m->cfg.embed_dim << s; }
-inline int slice_run(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int b0, int nb, int /*Bmax*/, char *ws, int32_t *logits,
-                     int8_t *feat8, const AttnTap * /*tap*/, int8_t *tok8, const HidTap *hid) {
-    HidTap planes;
-    if (hid) {
-        planes = *hid;
-        for (int j = 0; j < hid->n; ++j) planes.off[j] += (size_t)b0 * hidden_tokens(m, hid->idx[j]) * hidden_width(m, hid->idx[j]);
-    }
-    return swin_run_slice(m, h, images, nb, ws, logits, feat8, tok8 ? tok8 + (size_t)b0 * final_tokens(m) * num_features(m) : nullptr,
-                          hid ? &planes : nullptr);
-}
 
 }  // namespace
 
@@ -841,7 +841,7 @@ int ivit_swin_fused_mlp_blocks(ivit_swin m, int batch, int blocks_per_stage[4]) 
 // =====================================================================================================
 // The runner entries, once for both models: M is ivit_vit_s or ivit_swin_s.  A body reads in_chans, img_size and num_classes from
 // m->cfg (both configurations spell them alike), the names in its refusals from `fn`, M::WS_ENTRY and M::FWD_ENTRY, and the rest
-// through slice_stride, num_features and slice_run
+// through slice_stride, layout_images, num_features and run_slice
 namespace {
 
 template <class M>
@@ -857,35 +857,45 @@ int workspace_bytes(M *m, int batch, int nslices, size_t *bytes) {
     return IVIT_OK;
 }
 
-// THE place a runner checks its arguments, and the order it does so in, before anything is launched: the workspace query, the
-// pointers and the workspace's size and alignment, the three arrays of every runner pairwise; then the slices of the batch.  forward
-// (logits, no feat8), features (feat8, logits or none) and ivit_vit_attention (a tap, logits or none) end here.  `tap`: the caller's
-// block list and attn16 as a whole; slice_run gives every slice its own rows of it.  `tok8`: a Swin's final-stage tokens as a whole
-// (ivit_swin_class_map, logits or none), likewise.  `hid`: the caller's block / stage list and hid16 as a whole (the hidden_states
-// entries, logits or none), likewise
+// the slice's view of what the caller asked for: the rows of every destination that belong to the batch's images b0 onward.  THE
+// place a slice is placed in the caller's arrays (the planes of the hidden tap: RunOut::hid.rows, from the b0 set here)
 template <class M>
-int run_slices(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
-               int8_t *feat8, const AttnTap *tap = nullptr, int8_t *tok8 = nullptr, const HidTap *hid = nullptr) {
+RunOut slice_view(const M *m, const RunOut &all, int b0) {
+    RunOut s = all;
+    if (s.logits) s.logits += (size_t)b0 * m->cfg.num_classes;
+    if (s.feat8) s.feat8 += (size_t)b0 * num_features(m);
+    if (s.tok8) s.tok8 += (size_t)b0 * s.tok_image;
+    if (s.attn.n) s.attn.attn16 += (size_t)b0 * s.attn.image;
+    s.hid.b0 = (size_t)b0;
+    return s;
+}
+
+// THE place a runner checks its arguments, and the order it does so in, before anything is launched: the workspace query, the
+// pointers and the workspace's size and alignment, the three arrays of every runner pairwise; then the slices of the batch, each on
+// its view of `out`, the whole batch's destinations as the entry filled them in.  Every entry with a forward in it ends here
+template <class M>
+int run_slices(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, const RunOut &out) {
     ivit_handle h = m->h;
     size_t need = 0;
     RUN(workspace_bytes(m, batch, nslices, &need));
-    REQUIRE_FN(h, fn, images && (logits || feat8 || tap || tok8 || hid) && workspace && bytes >= need, "bad arguments / workspace too small");
+    REQUIRE_FN(h, fn, images && out.any() && workspace && bytes >= need, "bad arguments / workspace too small");
     REQUIRE_FN(h, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const size_t img_bytes = image_bytes(m);
-    RUN(runner_disjoint(h, fn, images, img_bytes * batch, workspace, need, logits, logit_bytes(m, batch)));
+    const Extent a[3] = {{images, img_bytes * batch, "images", true}, {workspace, need, "workspace", false},
+                         {out.logits, logit_bytes(m, batch), "logits", false}};
+    RUN(extents_disjoint(h, fn, a, 0));
     const int Bmax = max_slice(batch, nslices);
     const size_t stride = slice_stride(m, Bmax);
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
-        return slice_run(m, sh, images + (size_t)b0 * img_bytes, b0, nb, Bmax, (char *)workspace + stride * (size_t)i,
-                         logits ? logits + (size_t)b0 * m->cfg.num_classes : nullptr,
-                         feat8 ? feat8 + (size_t)b0 * num_features(m) : nullptr, tap, tok8, hid);
+        return run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, layout_images(m, nb, Bmax), (char *)workspace + stride * (size_t)i,
+                         slice_view(m, out, b0));
     });
 }
 
 template <class M>
 int runner_forward(M *m, const char *fn, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits) {
     if (!m) return IVIT_ERR_INVALID;
-    return run_slices(m, fn, images, batch, nslices, workspace, bytes, logits, nullptr);
+    return run_slices(m, fn, images, batch, nslices, workspace, bytes, RunOut(logits));
 }
 
 // the forward, then the top-k of its logits on the handle's stream: behind the slices' join, so inside a capture it is one more node
@@ -895,8 +905,14 @@ int runner_predict(M *m, const char *fn, const int8_t *images, int batch, int ns
     if (!m) return IVIT_ERR_INVALID;
     REQUIRE_FN(m->h, fn, head_scale && idx && k >= 1 && k <= TOPK_MAX_K && k <= m->cfg.num_classes,
                "head_scale / idx null or k outside 1 .. min(16, num_classes)");
-    if (size_t need = 0; batch > 0 && workspace_bytes(m, batch, nslices, &need) == IVIT_OK)
-        RUN(predict_disjoint(m->h, fn, images, image_bytes(m) * batch, workspace, need, logits, logit_bytes(m, batch), idx, val, (size_t)batch * k * 4));
+    // idx / val against the forward's arrays and each other, judged BEFORE the forward is launched (ivit_logits_topk judges logits /
+    // idx / val again behind it); a batch the workspace query refuses is left to the forward's own argument checks
+    if (size_t need = 0; batch > 0 && workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
+        const size_t nk = (size_t)batch * k * 4;
+        const Extent a[5] = {{images, image_bytes(m) * batch, "images", true}, {workspace, need, "workspace", false},
+                             {logits, logit_bytes(m, batch), "logits", false}, {idx, nk, "idx", false}, {val, nk, "val", false}};
+        RUN(extents_disjoint(m->h, fn, a, 3));
+    }
     RUN(runner_forward(m, M::FWD_ENTRY, images, batch, nslices, workspace, bytes, logits));
     return ivit_logits_topk(m->h, logits, head_scale, batch, m->cfg.num_classes, k, idx, val);
 }
@@ -919,7 +935,9 @@ int runner_features(M *m, const char *fn, const int8_t *images, int batch, int n
                     int8_t *feat8, float scale, int mode, float *feat32) {
     if (!m) return IVIT_ERR_INVALID;
     RUN(features_args_ok(m->h, fn, feat8, num_features(m), scale, mode, feat32, true));
-    RUN(run_slices(m, fn, images, batch, nslices, workspace, bytes, logits, feat8));
+    RunOut out(logits);
+    out.feat8 = feat8;
+    RUN(run_slices(m, fn, images, batch, nslices, workspace, bytes, out));
     return feat32 ? ivit_features_f32(m->h, feat8, batch, num_features(m), scale, mode, feat32) : IVIT_OK;
 }
 
@@ -973,30 +991,24 @@ int ivit_vit_attention(ivit_vit m, const int8_t *images, int batch, int nslices,
     if (!m) return IVIT_ERR_INVALID;
     ivit_handle h = m->h;
     const int H = m->cfg.num_heads, T = m->T;
-    REQUIRE(h, blocks_host && nblocks >= 1 && nblocks <= m->cfg.depth, "blocks_host is null or nblocks outside 1 .. depth");
-    for (int t = 0; t < nblocks; ++t)
-        REQUIRE(h, blocks_host[t] >= 0 && blocks_host[t] < m->cfg.depth && (t == 0 || blocks_host[t] > blocks_host[t - 1]),
-                "blocks_host must be strictly ascending block indices in [0, depth)");
+    RUN(index_list_ok(h, __func__, blocks_host, nblocks, "blocks_host", m->cfg.depth));
     RUN(attnmap_map_args_ok(h, __func__, attn16, "attn16", (long long)nblocks * std::max(batch, 0), H, T, mode, map32, "map32"));
     if (size_t need = 0; batch > 0 && workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
         const size_t rows = (size_t)nblocks * batch;
-        const struct { const void *p; size_t n; const char *name; } a[5] = {
-            {images, image_bytes(m) * batch, "images"},
-            {workspace, need, "workspace"},
-            {logits, logit_bytes(m, batch), "logits"},
-            {attn16, rows * H * T * 2, "attn16"},
-            {map32, attnmap_map_bytes((long long)rows, H, T, mode), "map32"}};
-        for (int i = 0; i < 5; ++i)
-            for (int j = std::max(i + 1, 3); j < 5; ++j)        // the pairs among the first three are run_slices'
-                if (!ranges_disjoint(h, __func__, a[i].p, a[i].n, a[i].name, a[j].p, a[j].n, a[j].name, i == 0 ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
+        const Extent a[5] = {{images, image_bytes(m) * batch, "images", true}, {workspace, need, "workspace", false},
+                             {logits, logit_bytes(m, batch), "logits", false}, {attn16, rows * H * T * 2, "attn16", false},
+                             {map32, attnmap_map_bytes((long long)rows, H, T, mode), "map32", false}};
+        RUN(extents_disjoint(h, __func__, a, 3));
     }
     RUN(attnmap_shape_ok(h, __func__, T, m->cfg.embed_dim / H));
     if (map32 && H > ATTNMAP_MAX_H) {
         snprintf(h->err, sizeof(h->err), "%s: the fp32 map takes at most %d heads", __func__, ATTNMAP_MAX_H);
         return IVIT_ERR_UNSUPPORTED;
     }
-    const AttnTap tap = {blocks_host, nblocks, attn16, (size_t)std::max(batch, 0) * H * T};
-    RUN(run_slices(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr, &tap));
+    RunOut out(logits);
+    out.attn.blocks = blocks_host; out.attn.n = nblocks; out.attn.attn16 = attn16;
+    out.attn.image = (size_t)H * T; out.attn.plane = (size_t)std::max(batch, 0) * H * T;
+    RUN(run_slices(m, __func__, images, batch, nslices, workspace, bytes, out));
     return map32 ? ivit_attention_map_f32(h, attn16, (int64_t)nblocks * batch, H, T, mode, map32) : IVIT_OK;
 }
 int ivit_vit_attention_graph_create(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,
@@ -1022,20 +1034,14 @@ int ivit_swin_class_map(ivit_swin m, const int8_t *images, int batch, int nslice
     RUN(classmap_args_ok(h, __func__, tok8, m->prm.head_w, idx, batch, L, C, ncls, k, class_scale, cam32, map32));
     if (size_t need = 0; workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
         const size_t nk = (size_t)batch * k * 4, nmap = nk * L;
-        const struct { const void *p; size_t n; const char *name; bool read_only; } a[8] = {
-            {images, image_bytes(m) * batch, "images", true}, {workspace, need, "workspace", false},
-            {logits, logit_bytes(m, batch), "logits", false}, {idx, nk, "idx", given},
-            {val, nk, "val", false},                          {tok8, (size_t)batch * L * C, "tok8", false},
-            {cam32, nmap, "cam32", false},                    {map32, nmap, "map32", false}};
-        for (int i = 0; i < 8; ++i)
-            for (int j = std::max(i + 1, 3); j < 8; ++j) {       // the pairs among the first three are run_slices'
-                if (a[i].read_only && a[j].read_only) continue;  // images and the caller's idx: both only read
-                if (!ranges_disjoint(h, __func__, a[i].p, a[i].n, a[i].name, a[j].p, a[j].n, a[j].name,
-                                     a[i].read_only || a[j].read_only ? OVL_IN : OVL_OUT))
-                    return IVIT_ERR_INVALID;
-            }
+        const Extent a[8] = {{images, image_bytes(m) * batch, "images", true}, {workspace, need, "workspace", false},
+                             {logits, logit_bytes(m, batch), "logits", false}, {idx, nk, "idx", given}, {val, nk, "val", false},
+                             {tok8, (size_t)batch * L * C, "tok8", false}, {cam32, nmap, "cam32", false}, {map32, nmap, "map32", false}};
+        RUN(extents_disjoint(h, __func__, a, 3));       // images and the caller's idx: both only read
     }
-    RUN(run_slices(m, __func__, images, batch, nslices, workspace, bytes, logits, nullptr, nullptr, tok8));
+    RunOut out(logits);
+    out.tok8 = tok8; out.tok_image = (size_t)L * C;
+    RUN(run_slices(m, __func__, images, batch, nslices, workspace, bytes, out));
     if (!given) RUN(ivit_logits_topk(h, logits, head_scale, batch, ncls, k, idx, val));
     return ivit_class_map(h, tok8, m->prm.head_w, idx, batch, L, C, ncls, k, class_scale, cam32, map32);
 }
@@ -1055,6 +1061,15 @@ namespace {
 inline float hidden_scale(const ivit_vit_s *m, int i) { return i + 1 < m->cfg.depth ? m->blocks[i + 1].s_ln1 : m->prm.s_ln; }
 inline float hidden_scale(const ivit_swin_s *m, int s) { return s + 1 < m->cfg.num_layers ? m->merges[s].s_in : m->prm.s_norm_in; }
 
+// both hidden_scale entries; `refusal`: the entry's own text
+template <class M>
+int runner_hidden_scale(M *m, const char *fn, int site, float *scale_host, const char *refusal) {
+    if (!m) return IVIT_ERR_INVALID;
+    REQUIRE_FN(m->h, fn, scale_host && site >= 0 && site < hidden_sites(m), refusal);
+    *scale_host = hidden_scale(m, site);
+    return IVIT_OK;
+}
+
 // both hidden_states entries: every argument checked first — the list, hid16, the layout, alignment, the planes' sizes, the rules of
 // ivit_hidden_f32 for every plane, the five arrays pairwise (images / workspace / logits again in run_slices) —, then the slices with
 // the caller's planes as the destination of the tapped blocks' last launches, then on the handle's stream, behind the slices' join,
@@ -1064,46 +1079,35 @@ int runner_hidden(M *m, const char *fn, const int8_t *images, int batch, int nsl
                   const int *list_host, int n, const char *list_name, int16_t *hid16, int layout, float *hid32, bool class_row) {
     if (!m) return IVIT_ERR_INVALID;
     ivit_handle h = m->h;
-    const int sites = hidden_sites(m);
-    bool list_ok = list_host && n >= 1 && n <= sites;
-    for (int j = 0; list_ok && j < n; ++j) list_ok = list_host[j] >= 0 && list_host[j] < sites && (j == 0 || list_host[j] > list_host[j - 1]);
-    if (!list_ok) {
-        snprintf(h->err, sizeof(h->err), "%s: %s must be 1 .. %d strictly ascending indices in [0, %d)", fn, list_name, sites, sites);
-        return IVIT_ERR_INVALID;
-    }
+    RUN(index_list_ok(h, fn, list_host, n, list_name, hidden_sites(m)));
     REQUIRE_FN(h, fn, hid16, "hid16 is null");
     REQUIRE_FN(h, fn, !hid32 || layout == IVIT_HIDDEN_TOKENS || layout == IVIT_HIDDEN_GRID, "layout must be IVIT_HIDDEN_TOKENS or IVIT_HIDDEN_GRID");
     REQUIRE_FN(h, fn, ((uintptr_t)hid16 & 15) == 0, "hid16 must be 16-byte aligned");
     REQUIRE_FN(h, fn, ((uintptr_t)hid32 & 15) == 0, "hid32 must be 16-byte aligned");
     const int t0 = (class_row && hid32 && layout == IVIT_HIDDEN_GRID) ? 1 : 0;
     const size_t nb = (size_t)std::max(batch, 0);
-    HidTap tap = {list_host, n, hid16, 0, {0, 0, 0, 0}};
-    std::vector<size_t> at16(n + 1, 0), at32(n + 1, 0);               // where plane j starts, in elements
+    std::vector<size_t> at16(n + 1, 0), at32(n + 1, 0), image(n, 0);      // where plane j starts and what an image takes of it, in elements
     for (int j = 0; j < n; ++j) {
         const size_t T = hidden_tokens(m, list_host[j]), C = hidden_width(m, list_host[j]);
         // a slice's rows of a plane start b0 * T * C elements in: 16-byte aligned for every b0
         REQUIRE_FN(h, fn, (T * C) % 8 == 0, "the tokens times the width of a tapped plane must be a multiple of 8");
         at16[j + 1] = at16[j] + nb * T * C;
         at32[j + 1] = at32[j] + nb * (T - t0) * C;
-        if (j < 4) tap.off[j] = at16[j];
+        image[j] = T * C;
     }
-    tap.plane = at16[1];
     if (hid32 && batch > 0)
         for (int j = 0; j < n; ++j)
             RUN(hidden_args_ok(h, fn, hid16 + at16[j], "hid16", hidden_scale(m, list_host[j]), batch, hidden_tokens(m, list_host[j]),
                                hidden_width(m, list_host[j]), t0, layout, hid32 + at32[j], "hid32"));
     if (size_t need = 0; batch > 0 && workspace_bytes(m, batch, nslices, &need) == IVIT_OK) {
-        const struct { const void *p; size_t n; const char *name; } a[5] = {
-            {images, image_bytes(m) * batch, "images"},
-            {workspace, need, "workspace"},
-            {logits, logit_bytes(m, batch), "logits"},
-            {hid16, at16[n] * 2, "hid16"},
-            {hid32, at32[n] * 4, "hid32"}};
-        for (int i = 0; i < 5; ++i)
-            for (int j = std::max(i + 1, 3); j < 5; ++j)        // the pairs among the first three are run_slices'
-                if (!ranges_disjoint(h, fn, a[i].p, a[i].n, a[i].name, a[j].p, a[j].n, a[j].name, i == 0 ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
+        const Extent a[5] = {{images, image_bytes(m) * batch, "images", true}, {workspace, need, "workspace", false},
+                             {logits, logit_bytes(m, batch), "logits", false}, {hid16, at16[n] * 2, "hid16", false},
+                             {hid32, at32[n] * 4, "hid32", false}};
+        RUN(extents_disjoint(h, fn, a, 3));
     }
-    RUN(run_slices(m, fn, images, batch, nslices, workspace, bytes, logits, nullptr, nullptr, nullptr, &tap));
+    RunOut out(logits);
+    out.hid.idx = list_host; out.hid.n = n; out.hid.hid16 = hid16; out.hid.start = at16.data(); out.hid.image = image.data();
+    RUN(run_slices(m, fn, images, batch, nslices, workspace, bytes, out));
     for (int j = 0; hid32 && j < n; ++j)
         RUN(ivit_hidden_f32(h, hid16 + at16[j], hidden_scale(m, list_host[j]), batch, hidden_tokens(m, list_host[j]), hidden_width(m, list_host[j]),
                             t0, layout, hid32 + at32[j]));
@@ -1115,16 +1119,10 @@ int runner_hidden(M *m, const char *fn, const int8_t *images, int batch, int nsl
 extern "C" {
 
 int ivit_vit_hidden_scale(ivit_vit m, int block, float *scale_host) {
-    if (!m) return IVIT_ERR_INVALID;
-    REQUIRE(m->h, scale_host && block >= 0 && block < m->cfg.depth, "scale_host is null or block outside [0, depth)");
-    *scale_host = hidden_scale(m, block);
-    return IVIT_OK;
+    return runner_hidden_scale(m, __func__, block, scale_host, "scale_host is null or block outside [0, depth)");
 }
 int ivit_swin_hidden_scale(ivit_swin m, int stage, float *scale_host) {
-    if (!m) return IVIT_ERR_INVALID;
-    REQUIRE(m->h, scale_host && stage >= 0 && stage < m->cfg.num_layers, "scale_host is null or stage outside [0, num_layers)");
-    *scale_host = hidden_scale(m, stage);
-    return IVIT_OK;
+    return runner_hidden_scale(m, __func__, stage, scale_host, "scale_host is null or stage outside [0, num_layers)");
 }
 
 int ivit_vit_hidden_states(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace, size_t bytes, int32_t *logits,

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, csum, golden_scales, load_golden
+from launch_count import captured_nodes
 
 pytestmark = pytest.mark.gpu
 
@@ -438,6 +439,105 @@ def test_hidden_states_write_only_their_outputs(fname, layout):
     flat16 = torch.cat([t.reshape(-1) for t in want16]) if isinstance(want16, tuple) else want16.reshape(-1)
     flat32 = torch.cat([t.reshape(-1) for t in want32]) if isinstance(want32, tuple) else want32.reshape(-1)
     assert torch.equal(h16.view(torch.int16), flat16) and torch.equal(h32.view(torch.int32), flat32.view(torch.int32))
+
+
+# ---------------------------------------------------------------- 6. where a slice ends
+# The rows of the table above RunOut::done (csrc/ivit_model.h) that nothing above exercises: a headless tap of the last block alone
+# and of a middle block alone (ViT), of stage 0 alone, the last stage with the head, and — the other destination that ends a Swin
+# slice early — the class map in GIVEN mode without logits.  (The row with an attention tap AND a hidden tap has no entry.)  Batch 3,
+# one slice and a ragged 2 + 1: the integers against the oracle's own planes, tokens and logits on fresh images, the fp32 forms
+# against the numpy references, and the launches counted as the nodes of a graph captured around the call.  NODES was recorded from
+# the library of commit 5e8798f, where each exit was a hand-written condition: (case, nslices) -> nodes
+B3 = 3
+NODES = {("vit last", 1): 20, ("vit last", 2): 39, ("vit middle", 1): 12, ("vit middle", 2): 23,
+         ("swin stage 0", 1): 20, ("swin stage 0", 2): 39, ("swin stage 1", 1): 42, ("swin stage 1", 2): 83,
+         ("swin class map given", 1): 40, ("swin class map given", 2): 79}
+
+
+def check_nodes(eng, suffix, args, case, nslices):
+    n = captured_nodes(eng, suffix, args)
+    print("NODES", repr(case), nslices, n)
+    assert n == NODES[case, nslices], (case, nslices, n)
+
+
+@pytest.fixture(scope="module")
+def vit3():
+    from oracle import oracle as orc
+    g, cfg, eng = _engine("micro_vit_b2.npz")
+    imgs = iv.make_images_int8(cfg, B3, seed=91)
+    cap = {}
+    logits, _ = orc.OracleViT(cfg, iv.make_vit_weights(cfg, int(g["seed"])), golden_scales(g)).forward(imgs, capture=cap)
+    return cfg, eng, dev(imgs), cap, logits
+
+
+@pytest.fixture(scope="module")
+def swin3():
+    from oracle import oracle as orc
+    g, cfg, eng = _engine("micro_swin_b2.npz")
+    imgs = iv.make_images_int8(cfg, B3, seed=92)                                 # the fixture holds two images: three fresh ones
+    cap = {}
+    logits, _ = orc.OracleSwin(cfg, iv.make_swin_weights(cfg, int(g["seed"])), golden_scales(g)).forward(imgs, capture=cap)
+    return cfg, eng, dev(imgs), cap, logits
+
+
+@pytest.mark.parametrize("nslices", [1, 2])
+@pytest.mark.parametrize("which", ["last", "middle"])
+def test_vit_headless_tap_of_one_block_ends_the_slice_behind_it(vit3, which, nslices):
+    """the last block alone: the class-token tail is off, the block runs on all rows and the slice ends behind its Mlp launch; a
+    middle block alone: the slice ends there.  No final norm, no head: the logits buffer keeps what it held"""
+    cfg, eng, imgs, cap, _ = vit3
+    i = cfg.depth - 1 if which == "last" else cfg.depth - 2
+    assert 0 <= i and (which == "last" or i < cfg.depth - 1)
+    lg = eng._native_buffers(B3, nslices)[1]
+    lg.fill_(0x5A5A5A5A)
+    hid16, hid32 = eng.hidden_states(imgs, blocks=(i,), layout="tokens", nslices=nslices)
+    want = np.asarray(cap[f"blocks.{i}.qact4"]).reshape(B3, cfg.num_tokens, cfg.embed_dim)
+    assert np.array_equal(hid16[0].cpu().numpy().astype(np.int64), want.astype(np.int64)), (which, nslices)
+    check_hid32(hid16, hid32, eng, (i,), "tokens", True)
+    assert bool((lg == 0x5A5A5A5A).all()), (which, nslices)
+    check_nodes(eng, "_hidden_states", eng._hidden_args(imgs, (i,), "tokens", False, nslices)[0], "vit " + which, nslices)
+
+
+@pytest.mark.parametrize("nslices", [1, 2])
+@pytest.mark.parametrize("stage,logits", [(0, False), (1, True)])
+def test_swin_tap_of_one_stage_with_and_without_the_head(swin3, stage, logits, nslices):
+    """stage 0 alone, headless: the slice ends behind the stage's last Mlp launch, in front of its merge.  The last stage with the
+    head: the whole forward, its last block's output in the caller's plane"""
+    cfg, eng, imgs, cap, ref = swin3
+    assert cfg.num_layers == 2
+    lg = eng._native_buffers(B3, nslices)[1]
+    lg.fill_(0x5A5A5A5A)
+    out = eng.hidden_states(imgs, stages=(stage,), layout="grid", logits=logits, nslices=nslices)
+    L, C, _ = eng._hidden_plane(stage)
+    want = np.asarray(cap[f"layers.{stage}.blocks.{cfg.depths[stage] - 1}.qact4"]).reshape(B3, L, C)
+    assert np.array_equal(out[0][0].cpu().numpy().astype(np.int64), want.astype(np.int64)), (stage, nslices)
+    check_hid32(out[0], out[1], eng, (stage,), "grid", False)
+    if logits:
+        assert np.array_equal(out[2].cpu().numpy(), ref) and out[2].data_ptr() == lg.data_ptr(), nslices
+    else:
+        assert bool((lg == 0x5A5A5A5A).all()), nslices
+    check_nodes(eng, "_hidden_states", eng._hidden_args(imgs, (stage,), "grid", logits, nslices)[0], f"swin stage {stage}", nslices)
+
+
+@pytest.mark.parametrize("nslices", [1, 2])
+def test_swin_headless_class_map_ends_the_slice_behind_the_final_norm(swin3, nslices):
+    """IVIT_CLASSMAP_GIVEN without logits: the final norm writes the caller's tokens and the slice ends — no pool, no head"""
+    from ivit_amd.predict import class_map_reference
+    cfg, eng, imgs, cap, _ = swin3
+    classes = torch.tensor([[1, 0], [2, 9], [0, 3]], dtype=torch.int32, device="cuda")
+    assert cfg.num_classes > 9
+    lg = eng._native_buffers(B3, nslices)[1]
+    lg.fill_(0x5A5A5A5A)
+    idx, val, tok8, cam32, maps = eng.class_map(imgs, classes=classes, logits=False, nslices=nslices)
+    want = np.asarray(cap["qact2"]).reshape(tuple(tok8.shape))
+    assert np.array_equal(tok8.cpu().numpy().astype(np.int64), want.astype(np.int64)), nslices
+    o, _, shp = eng.table["head.w"]
+    head_w = eng.blob[o:o + int(np.prod(shp))].cpu().numpy().view(np.int8).reshape(shp)
+    want_cam, want_map = class_map_reference(want.astype(np.int8), head_w, classes.cpu().numpy(), eng.class_scale.cpu().numpy())
+    assert val is None and np.array_equal(cam32.cpu().numpy(), want_cam)
+    assert np.array_equal(bits(maps.cpu().numpy().reshape(want_map.shape)), bits(want_map))
+    assert bool((lg == 0x5A5A5A5A).all()), nslices
+    check_nodes(eng, "_class_map", eng._class_map_args(imgs, 2, classes, False, nslices)[0], "swin class map given", nslices)
 
 
 # ---------------------------------------------------------------- the tool
