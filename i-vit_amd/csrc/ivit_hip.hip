@@ -117,6 +117,17 @@ static int bmm_disjoint(ivit_ctx *h, const char *fn, const void *A, size_t a_ele
 }
 #define LAUNCH_CHECK(h) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { snprintf((h)->err, sizeof((h)->err), "%s: %s", __func__, hipGetErrorString(e_)); return IVIT_ERR_HIP; } } while (0)
 
+// A launch's global size (blocks x threads) must stay below 2^32: the runtime takes a larger one modulo 2^32 and runs the remainder
+// without an error, so the rows behind it are never written.  An entry whose grid grows with the caller's row count refuses such a
+// call before anything is launched (include/ivit.h, Conventions); `per_block`: rows (images, elements) a block works, for the message
+static inline int launch_fits(ivit_ctx *h, const char *fn, long long blocks, int threads, long long per_block) {
+    if (blocks * threads < (1LL << 32)) return IVIT_OK;
+    snprintf(h->err, sizeof(h->err), "%s: %lld blocks of %d threads are 2^32 work-items or more: one call takes at most %lld rows", fn, blocks, threads,
+             ((1LL << 32) / threads - 1) * per_block);
+    return IVIT_ERR_UNSUPPORTED;
+}
+#define REQUIRE_LAUNCH(h, blocks, threads, per_block) do { if (int st_ = launch_fits(h, __func__, blocks, threads, per_block)) return st_; } while (0)
+
 // Launch `Kernel` with `lds` bytes of dynamic LDS.  Above 64 KB a launch needs hipFuncAttributeMaxDynamicSharedMemorySize: set once
 // per device and kernel for the largest size seen (the attribute is a maximum), so the eager single-stream modes pay no host call
 // per launch; a device ordinal outside the cache sets it every time.  Per DEVICE: ADVICE r5, one process-wide flag left the second
@@ -286,7 +297,7 @@ static int launch_pil_eval(ivit_handle h, const char *fn, const uint8_t *pixels,
         if (!(std_[0] != 0.f && std_[1] != 0.f && std_[2] != 0.f)) return fail("zero std", -1);
     }
     const int nbands = (crop + PIL_BAND - 1) / PIL_BAND;
-    if ((long long)nbands * B > 0x7fffffffLL) return fail("B * ceil(crop / 32) exceeds the grid", -1);
+    if ((long long)nbands * B * PIL_THREADS >= (1LL << 32)) return fail("B * ceil(crop / 32) blocks of 512 threads are 2^32 work-items or more", -1);
     {   // the output against the whole pixel blob [pixels, pixels + pixels_bytes) and the device descriptor table
         const size_t nout = (size_t)B * crop * crop * 3;
         const char *oname = NCHW ? "nchw" : "out_hwc";
@@ -335,6 +346,11 @@ int ivit_eval_transform_u8(ivit_handle h, const uint8_t *pixels, size_t pixels_b
 // ---------------------------------------------------------------- GEMM launchers
 template <bool A16, int EPI>
 static int launch_gemm(ivit_handle h, GemmArgs &a, int nb) {
+    // the matrices of a batched product are gridDim.y: more than 65535 of them are refused here, before the launch would fail
+    if (nb > 65535) {
+        snprintf(h->err, sizeof(h->err), "batched product of %d matrices: one launch takes at most 65535 (nb, BH, B * H <= 65535)", nb);
+        return IVIT_ERR_UNSUPPORTED;
+    }
     const int tm = (a.M + GEMM_BM - 1) / GEMM_BM;
     a.tiles_n = (a.N + GEMM_BN - 1) / GEMM_BN;
     dim3 grid((unsigned)(tm * a.tiles_n), (unsigned)nb, 1);
@@ -1250,6 +1266,7 @@ static int launch_attn2(ivit_handle h, const AttnArgs &a, int BH) {
     const size_t lds = AttCfg<NB>::SMEM + (LUT == 2 ? (size_t)ATT_ROWLINE_BYTES
                                                    : (LUT == 1 ? (size_t)((a.t_count + 3) & ~3) * 4 + (size_t)a.nc * 512 + 256 : 0));
     // (since round 6 every launch of the row-table form is above 64 KB)
+    REQUIRE_LAUNCH(h, BH, ATT_WAVES * 64, 1);
     if (int st = launch_dyn<attn_fused_kernel<NB, FAST, TT, LUT, VROW, CLS>>(h, BH, ATT_WAVES * 64, lds, a)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1448,6 +1465,7 @@ extern "C" int ivit_gather_rows_i16(ivit_handle h, const int16_t *x, int64_t row
     const long long n = (long long)rows * (C / 8);
     REQUIRE(h, n < (1LL << 31) * 256, "too many rows");
     REQUIRE_DISJOINT(h, x, span_bytes(rows, row_stride, C, 2), "x", out, (size_t)rows * C * 2, "out", OVL_IN);
+    REQUIRE_LAUNCH(h, (n + 255) / 256, 256, 256);
     gather_rows16_kernel<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(x, row_stride, C / 8, n, out);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1523,6 +1541,7 @@ int ivit_shiftmax(ivit_handle h, const int8_t *x, int64_t rows, int n, int ld_in
     REQUIRE_DISJOINT(h, x, span_bytes(rows, ld_in, n, 1), "x", out, span_bytes(rows, ld_out, n, 2), "out", OVL_IN);
     const size_t lds = (size_t)4 * n * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "row too long for LDS staging");
+    REQUIRE_LAUNCH(h, (rows + 3) / 4, 256, 4);
     if (int st = launch_dyn<shiftmax_kernel>(h, (unsigned)((rows + 3) / 4), 256, lds, x, rows, n, ld_in, scale, out_bits, out, ld_out)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1588,6 +1607,7 @@ int ivit_shiftgelu(ivit_handle h, const int8_t *x, int64_t rows, int C, float sc
         return IVIT_ERR_UNSUPPORTED;
     }
     ivit_dyadic d = {0.0, 0.0};
+    REQUIRE_LAUNCH(h, (rows + 3) / 4, 256, 4);
     shiftgelu_kernel<false><<<(unsigned)((rows + 3) / 4), 256, 0, h->stream>>>(x, rows, C, scale, d, out16);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1602,6 +1622,7 @@ int ivit_shiftgelu_requant(ivit_handle h, const int8_t *x, int64_t rows, int C, 
     REQUIRE_A16(h, out8, "out8");
     // x == out8 is refused like every other overlap: shiftgelu_kernel declares x and out __restrict__ and reads each chunk twice
     REQUIRE_DISJOINT(h, x, (size_t)rows * C, "x", out8, (size_t)rows * C, "out8", OVL_IN);
+    REQUIRE_LAUNCH(h, (rows + 3) / 4, 256, 4);
     shiftgelu_kernel<true><<<(unsigned)((rows + 3) / 4), 256, 0, h->stream>>>(x, rows, C, scale, dy, out8);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1626,13 +1647,22 @@ int ivit_shiftgelu_requant_lut(ivit_handle h, const int8_t *x, int64_t rows, int
     // half a wavefront per row, row in registers: ITER = ceil(C / 512) chunks of 16 bytes per lane
     constexpr bool lut_old = false;
     const int iter = (C / 16 + 31) / 32;
-    const unsigned grid2 = (unsigned)((rows + 7) / 8);
-    if (lut_old || iter > 6) shiftgelu_lut_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, h->stream>>>(x, rows, C, table, out8);
-    else if (iter == 1) shiftgelu_lut2_kernel<1><<<grid2, 256, 0, h->stream>>>(x, rows, C, table, out8);
-    else if (iter == 2) shiftgelu_lut2_kernel<2><<<grid2, 256, 0, h->stream>>>(x, rows, C, table, out8);
-    else if (iter == 3) shiftgelu_lut2_kernel<3><<<grid2, 256, 0, h->stream>>>(x, rows, C, table, out8);
-    else if (iter == 4) shiftgelu_lut2_kernel<4><<<grid2, 256, 0, h->stream>>>(x, rows, C, table, out8);
-    else shiftgelu_lut2_kernel<6><<<grid2, 256, 0, h->stream>>>(x, rows, C, table, out8);
+    // The runtime takes a launch's global size (blocks x 256 threads) modulo 2^32 and runs the remainder WITHOUT an error (C = 16,
+    // 134 221 828 rows: 513 of 16 777 729 blocks ran, the rows from 4104 on were never written): consecutive ranges of at most 2^25
+    // rows go out as launches of their own, 2^22 (2^23) blocks each
+    constexpr int64_t rows_per_launch = (int64_t)1 << 25;
+    for (int64_t r0 = 0; r0 < rows; r0 += rows_per_launch) {
+        const int64_t nr = std::min<int64_t>(rows - r0, rows_per_launch);
+        const int8_t *xs = x + r0 * C;
+        int8_t *os = out8 + r0 * C;
+        const unsigned grid2 = (unsigned)((nr + 7) / 8);
+        if (lut_old || iter > 6) shiftgelu_lut_kernel<<<(unsigned)((nr + 3) / 4), 256, 0, h->stream>>>(xs, nr, C, table, os);
+        else if (iter == 1) shiftgelu_lut2_kernel<1><<<grid2, 256, 0, h->stream>>>(xs, nr, C, table, os);
+        else if (iter == 2) shiftgelu_lut2_kernel<2><<<grid2, 256, 0, h->stream>>>(xs, nr, C, table, os);
+        else if (iter == 3) shiftgelu_lut2_kernel<3><<<grid2, 256, 0, h->stream>>>(xs, nr, C, table, os);
+        else if (iter == 4) shiftgelu_lut2_kernel<4><<<grid2, 256, 0, h->stream>>>(xs, nr, C, table, os);
+        else shiftgelu_lut2_kernel<6><<<grid2, 256, 0, h->stream>>>(xs, nr, C, table, os);
+    }
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -1647,6 +1677,7 @@ int ivit_layernorm(ivit_handle h, const int16_t *x, int64_t rows, int C, float s
     REQUIRE_DISJOINT(h, x, (size_t)rows * C * 2, "x", z, (size_t)rows * C * 4, "z", OVL_IN);
     const size_t lds = (size_t)8 * C * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
+    REQUIRE_LAUNCH(h, (rows + 7) / 8, 256, 8);
     if (int st = launch_dyn<layernorm_kernel<false>>(h, (unsigned)((rows + 7) / 8), 256, lds, x, rows, C, C, scale, bias_int, sc, nullptr, z)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1656,6 +1687,7 @@ int ivit_layernorm(ivit_handle h, const int16_t *x, int64_t rows, int C, float s
 #define LNR_LAUNCH(CC, S, MERGE, row_stride, merge_R)                                                                     \
     do {                                                                                                                  \
         constexpr int rpb = (LNR_THREADS(S) / 64) * (64 / (4 * S));                                                       \
+        REQUIRE_LAUNCH(h, (rows + rpb - 1) / rpb, LNR_THREADS(S), rpb);                                                   \
         layernorm_reg_kernel<CC, S, MERGE><<<(unsigned)((rows + rpb - 1) / rpb), LNR_THREADS(S), 0, h->stream>>>(        \
             x, rows, row_stride, scale, bias_int, sc, dy_ch, out8, merge_R);                                              \
         LAUNCH_CHECK(h);                                                                                                  \
@@ -1694,6 +1726,7 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
             long long riter = rows / (16LL * 6 * h->num_cu);
             riter = riter < 1 ? 1 : (riter > LN_RITER ? LN_RITER : riter);
             const long long per_block = 16 * riter;
+            REQUIRE_LAUNCH(h, (rows + per_block - 1) / per_block, 256, per_block);
             const unsigned grid = (unsigned)((rows + per_block - 1) / per_block);
             if (int st = launch_dyn<layernorm16_kernel<0>>(h, grid, 256, lds16, x, rows, C, row_stride, scale, bias_int, sc, dy_ch, out8, (int)riter)) return st;
             LAUNCH_CHECK(h);
@@ -1702,6 +1735,7 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
     }
     const size_t lds = (size_t)8 * C * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
+    REQUIRE_LAUNCH(h, (rows + 7) / 8, 256, 8);
     if (int st = launch_dyn<layernorm_kernel<true>>(h, (unsigned)((rows + 7) / 8), 256, lds, x, rows, C, row_stride, scale, bias_int, sc, dy_ch, out8)) return st;
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1742,6 +1776,7 @@ int ivit_shiftmax_masked(ivit_handle h, const int8_t *x, int64_t rows, int n, in
     REQUIRE(h, mask == nullptr || (nW > 0 && H > 0), "mask needs nW, H");
     const size_t lds = (size_t)4 * n * sizeof(float);
     REQUIRE(h, lds <= 160 * 1024, "row too long for LDS staging");
+    REQUIRE_LAUNCH(h, (rows + 3) / 4, 256, 4);
     if (int st = launch_dyn<shiftmax_masked_kernel>(h, (unsigned)((rows + 3) / 4), 256, lds, x, rows, n, ld_in, scale, out_bits, mask,
                                                     nW > 0 ? nW : 1, H > 0 ? H : 1, out, ld_out))
         return st;
@@ -1795,6 +1830,7 @@ int ivit_layernorm_tokenorder_requant(ivit_handle h, const int16_t *x, int64_t r
     REQUIRE_DISJOINT(h, x, (size_t)rows * C * 2, "x", out8, (size_t)rows * C, "out8", OVL_IN);
     const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
+    REQUIRE_LAUNCH(h, (rows + LNT_ROWS - 1) / LNT_ROWS, 256, LNT_ROWS);      // (the 96-row form of C = 96 / 128 has fewer, no larger blocks)
     int st;
     if (C == 96 || C == 128) {          // Swin-T/S and Swin-B stage 0
         REQUIRE(h, (((uintptr_t)x | (uintptr_t)out8 | (uintptr_t)bias_int | (uintptr_t)sc) & 15) == 0,
@@ -1820,6 +1856,7 @@ int ivit_patch_norm_tokenorder(ivit_handle h, const int8_t *x8, int64_t rows, in
     REQUIRE_DISJOINT(h, x8, (size_t)rows * C, "x8", out16, (size_t)rows * C * 2, "out16", OVL_IN);
     const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
+    REQUIRE_LAUNCH(h, (rows + LNT_ROWS - 1) / LNT_ROWS, 256, LNT_ROWS);      // (the 96-row form of C = 96 / 128 has fewer, no larger blocks)
     int st;
     if (C == 96 || C == 128) {
         REQUIRE(h, (((uintptr_t)x8 | (uintptr_t)out16 | (uintptr_t)bias_int | (uintptr_t)sc) & 15) == 0,
@@ -1844,6 +1881,7 @@ int ivit_layernorm_tokenorder(ivit_handle h, const int16_t *x, int64_t rows, int
     REQUIRE_DISJOINT(h, x, (size_t)rows * C * 2, "x", z, (size_t)rows * C * 4, "z", OVL_IN);
     const size_t lds = lnt_lds(C);
     REQUIRE(h, lds <= 160 * 1024, "C too large for LDS staging");
+    REQUIRE_LAUNCH(h, (rows + LNT_ROWS - 1) / LNT_ROWS, 256, LNT_ROWS);      // (the 96-row form of C = 96 / 128 has fewer, no larger blocks)
     if (int st = launch_dyn<layernorm_tokenorder_kernel<0, 0>>(h, (unsigned)((rows + LNT_ROWS - 1) / LNT_ROWS), 256, lds, x, rows, C, scale, bias_int, sc,
                                                                nullptr, tokens_per_image, z, ivit_dyadic{0.0, 0.0}))
         return st;
@@ -1854,6 +1892,7 @@ int ivit_layernorm_tokenorder(ivit_handle h, const int16_t *x, int64_t rows, int
 int ivit_debug_div(ivit_handle h, const float *n, const float *d, float *q_ieee, float *q_lean, int64_t count) {
     CHECK_H(h);
     REQUIRE(h, n && d && q_ieee && q_lean && count > 0, "bad arguments");
+    REQUIRE_LAUNCH(h, (count + 255) / 256, 256, 256);
     debug_div_kernel<<<(unsigned)((count + 255) / 256), 256, 0, h->stream>>>(n, d, q_ieee, q_lean, count);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1862,6 +1901,7 @@ int ivit_debug_div(ivit_handle h, const float *n, const float *d, float *q_ieee,
 int ivit_debug_requotient(ivit_handle h, const float *q, const float *d, float *r_ieee, float *r_markstein, int64_t count) {
     CHECK_H(h);
     REQUIRE(h, q && d && r_ieee && r_markstein && count > 0, "bad arguments");
+    REQUIRE_LAUNCH(h, (count + 255) / 256, 256, 256);
     debug_requotient_kernel<<<(unsigned)((count + 255) / 256), 256, 0, h->stream>>>(q, d, r_ieee, r_markstein, count);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -1878,8 +1918,10 @@ int ivit_im2col_patch(ivit_handle h, const int8_t *img, int B, int Cin, int H, i
     REQUIRE(h, lds <= 64 * 1024, "patch strip too large for LDS staging");
     if (P == 16 && Cin == 3 && (W % 16) == 0 && B <= 65535)
         im2col_patch16_kernel<3><<<dim3((unsigned)(H / P), (unsigned)B), 256, lds, h->stream>>>(img, H, W, rows);
-    else
-        im2col_patch_kernel<<<(unsigned)(B * (H / P)), 256, lds, h->stream>>>(img, B, Cin, H, W, P, rows);
+    else {
+        REQUIRE_LAUNCH(h, (long long)B * (H / P), 256, 1);
+        im2col_patch_kernel<<<(unsigned)((long long)B * (H / P)), 256, lds, h->stream>>>(img, B, Cin, H, W, P, rows);
+    }
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -2102,6 +2144,7 @@ int ivit_logits_topk(ivit_handle h, const int32_t *logits, const float *scale, i
         REQUIRE_DISJOINT(h, idx, nout, "idx", val, nout, "val", OVL_OUT);
     }
     if (batch == 0) return IVIT_OK;
+    REQUIRE_LAUNCH(h, (batch + 3ll) / 4, 256, 4);
     const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per image; 64-bit sum: no overflow near INT_MAX
     if (num_classes <= TOPK_REG_CLASSES) logits_topk_kernel<true><<<grid, 256, 0, h->stream>>>(logits, scale, batch, num_classes, k, idx, val);
     else logits_topk_kernel<false><<<grid, 256, 0, h->stream>>>(logits, scale, batch, num_classes, k, idx, val);
@@ -2115,6 +2158,7 @@ int ivit_logits_score(ivit_handle h, const int32_t *logits, const float *scale, 
     REQUIRE(h, logits && scale && labels && batch >= 0 && num_classes >= 1, "bad arguments");
     REQUIRE(h, rank || nll, "rank and nll are both null");
     if (batch == 0) return IVIT_OK;
+    REQUIRE_LAUNCH(h, (batch + 3ll) / 4, 256, 4);
     const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per image, as ivit_logits_topk
     const long long *lab = (const long long *)labels;
     if (num_classes <= TOPK_REG_CLASSES) logits_score_kernel<true><<<grid, 256, 0, h->stream>>>(logits, scale, lab, batch, num_classes, rank, nll);
@@ -2147,6 +2191,7 @@ extern "C" int ivit_features_f32(ivit_handle h, const int8_t *feat8, int batch, 
     REQUIRE(h, out && batch >= 0, "out is null or batch is negative");
     if (const int rc = features_args_ok(h, __func__, feat8, dim, scale, mode, out, false)) return rc;
     if (batch == 0) return IVIT_OK;
+    REQUIRE_LAUNCH(h, (batch + 3ll) / 4, 256, 4);
     const unsigned grid = (unsigned)((batch + 3ll) / 4);        // one wavefront per row
     if (mode == IVIT_FEATURES_UNIT) features_f32_kernel<true><<<grid, 256, 0, h->stream>>>(feat8, batch, dim, scale, out);
     else features_f32_kernel<false><<<grid, 256, 0, h->stream>>>(feat8, batch, dim, scale, out);
@@ -2178,6 +2223,7 @@ extern "C" int ivit_attention_cls_probs(ivit_handle h, const int8_t *q, const in
     if (const int rc = attnmap_shape_ok(h, __func__, T, dh)) return rc;
     const long long BH = (long long)B * H;
     REQUIRE(h, BH <= 0x7fffffffLL, "B * H does not fit an int");
+    REQUIRE_LAUNCH(h, (BH + 3) / 4, 256, 4);
     const size_t lds = (size_t)4 * T * sizeof(float);            // at most 16 KB
     attn_cls_probs_kernel<<<(unsigned)((BH + 3) / 4), 256, lds, h->stream>>>(q, k, dy_qk.m * dy_qk.r, s_softmax, p_cls, (int)BH, T, dh);
     LAUNCH_CHECK(h);
@@ -2211,7 +2257,7 @@ extern "C" int ivit_attention_map_f32(ivit_handle h, const uint16_t *p_cls, int6
     }
     const long long total = (long long)rows * (mode == IVIT_ATTNMAP_MEAN ? 1 : H) * (T - 1);
     if (total == 0) return IVIT_OK;
-    REQUIRE(h, (total + 255) / 256 <= 0x7fffffffLL, "too many rows for one launch");
+    REQUIRE_LAUNCH(h, (total + 255) / 256, 256, 256);
     const unsigned grid = (unsigned)((total + 255) / 256);
     if (mode == IVIT_ATTNMAP_MEAN) attn_map_f32_kernel<true><<<grid, 256, 0, h->stream>>>(p_cls, (long long)rows, H, T, out);
     else attn_map_f32_kernel<false><<<grid, 256, 0, h->stream>>>(p_cls, (long long)rows, H, T, out);
@@ -2254,6 +2300,7 @@ extern "C" int ivit_class_map(ivit_handle h, const int8_t *tok8, const int8_t *h
     CHECK_H(h);
     if (const int rc = classmap_args_ok(h, __func__, tok8, head_w, idx, batch, L, C, num_classes, k, class_scale, cam32, map32)) return rc;
     const int BK = batch * k;
+    REQUIRE_LAUNCH(h, (BK + 3ll) / 4, 256, 4);
     const unsigned grid = (unsigned)((BK + 3ll) / 4);            // one wavefront per (image, class slot)
     if (map32) class_map_kernel<true><<<grid, 256, 0, h->stream>>>(tok8, head_w, idx, class_scale, cam32, map32, BK, k, L, C, num_classes);
     else class_map_kernel<false><<<grid, 256, 0, h->stream>>>(tok8, head_w, idx, nullptr, cam32, nullptr, BK, k, L, C, num_classes);

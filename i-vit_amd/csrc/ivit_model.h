@@ -396,6 +396,10 @@ int run_slice(const ivit_vit_s *m, ivit_handle h, const int8_t *images, int B, i
 inline size_t slice_stride(const ivit_vit_s *m, int Bmax) { return slice_layout(m, Bmax).total; }
 inline int layout_images(const ivit_vit_s *, int, int Bmax) { return Bmax; }
 inline int num_features(const ivit_vit_s *m) { return m->cfg.embed_dim; }
+// THE rule for "a slice of this many images is more than the model's launches take" (run_slices refuses a larger one before anything
+// is launched): an image of a slice is one gridDim.y of the embedding launches (ivit_patch_embed, ivit_embed_finish: B <= 65535), and
+// without the fused attention every (image, head) is one matrix of the batched products (ivit_attn_qk_requant: B * H <= 65535)
+inline int max_slice_images(const ivit_vit_s *m) { return m->fused_attention ? 65535 : 65535 / m->cfg.num_heads; }
 // ... and of its hidden states (include/ivit_hidden.h): how many sites it has (blocks), the tokens and the width of site i's plane
 inline int hidden_sites(const ivit_vit_s *m) { return m->cfg.depth; }
 inline int hidden_tokens(const ivit_vit_s *m, int) { return m->T; }
@@ -707,6 +711,8 @@ int run_slice(const ivit_swin_s *m, ivit_handle h, const int8_t *images, int B, 
 inline size_t slice_stride(const ivit_swin_s *m, int Bmax) { return swin_layout(m, Bmax).total; }
 inline int layout_images(const ivit_swin_s *, int nb, int) { return nb; }
 inline int num_features(const ivit_swin_s *m) { return m->cfg.embed_dim << (m->cfg.num_layers - 1); }
+// no launch of a Swin slice has an image per gridDim.y (ivit_im2col_patch takes its one-dimensional grid beyond 65535 images)
+inline int max_slice_images(const ivit_swin_s *) { return 0x7fffffff; }
 inline int final_tokens(const ivit_swin_s *m) { const int r = m->grid >> (m->cfg.num_layers - 1); return r * r; }
 // its hidden states are by stage: (grid >> s)^2 tokens of width embed_dim << s
 inline int hidden_sites(const ivit_swin_s *m) { return m->cfg.num_layers; }
@@ -885,6 +891,11 @@ int run_slices(M *m, const char *fn, const int8_t *images, int batch, int nslice
                          {out.logits, logit_bytes(m, batch), "logits", false}};
     RUN(extents_disjoint(h, fn, a, 0));
     const int Bmax = max_slice(batch, nslices);
+    if (Bmax > max_slice_images(m)) {
+        snprintf(h->err, sizeof(h->err), "%s: batch %d in %d slice(s) is %d images per slice, the model takes at most %d per slice: use more slices",
+                 fn, batch, nslices, Bmax, max_slice_images(m));
+        return IVIT_ERR_UNSUPPORTED;
+    }
     const size_t stride = slice_stride(m, Bmax);
     return fork_join(m->run, h, batch, nslices, [&](ivit_handle sh, int i, int b0, int nb) {
         return run_slice(m, sh, images + (size_t)b0 * img_bytes, nb, layout_images(m, nb, Bmax), (char *)workspace + stride * (size_t)i,

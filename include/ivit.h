@@ -36,6 +36,15 @@
  *     The planned and fused forms of the identity branch need a second buffer (ping-pong x / y as ivit_vit_forward does).  The
  *     whole-model runners refuse images, workspace and logits that overlap, and the predict entries idx and val against those three
  *     and each other, before the forward is launched;
+ *   - rows per call: a launch holds fewer than 2^32 work-items (blocks x threads; the runtime would take more modulo 2^32 without
+ *     an error).  An entry whose grid grows with its row count refuses a call beyond that with IVIT_ERR_UNSUPPORTED before anything
+ *     is launched, and ivit_last_error says "2^32 work-items" and the largest row count one call takes: (2^24 - 1) * 4 = 67 108 860
+ *     rows for ivit_shiftmax, ivit_shiftmax_masked, ivit_shiftgelu, ivit_shiftgelu_requant, and as many images for ivit_logits_topk
+ *     and for the entries of the other headers that work one image (row, head, class slot) per wavefront;
+ *     (2^24 - 1) * 8 rows for ivit_layernorm; (2^24 - 1) * 32 for ivit_layernorm_requant at the dispatched widths (C = 96 .. 384;
+ *     (2^23 - 1) * 32 at C = 512 .. 1536) and for the token-order LayerNorms; 2^23 - 1 (image, head) pairs for the fused attention
+ *     entries.  ivit_shiftgelu_requant_lut, the element-wise entries (requant, quantize, widen) and the GEMMs take any row count
+ *     (ranges of 2^25 rows per launch; grid-stride loops);
  *   - activations are carried as INTEGERS plus an fp32 scale held by the caller
  *     (the reference carries fp32 "integer*scale" tensors; X = fl(Q*s) is
  *     re-derived inside the kernels where its rounding matters).
@@ -299,7 +308,9 @@ int ivit_layernorm_linear_i8_qkv_ldv_planned(ivit_handle h, ivit_linear_plan p, 
 
 /* ---- a2  QuantMatMul.forward  (quant_modules.py:223-228), batched, "NT" form:
  * C[b] = A[b] (M x K) * B[b]^T (B[b] is N x K), int32.  q·kᵀ: A=q, B=k.
- * lda/ldb/ldc in elements, strides per batch in elements; lda,ldb % 16 == 0.            */
+ * lda/ldb/ldc in elements, strides per batch in elements; lda,ldb % 16 == 0.
+ * The four batched products below take at most 65535 matrices per call (nb, BH, B * H: one gridDim.y each); more is
+ * IVIT_ERR_UNSUPPORTED, nothing launched.                                                */
 /* Alignment: A and B 16-byte aligned; C takes any int32 address; IVIT_ERR_INVALID otherwise, nothing launched. */
 /* Overlap: C may not overlap A or B: IVIT_ERR_INVALID, nothing launched. */
 int ivit_bmm_nt_i8(ivit_handle h, const int8_t *A, const int8_t *B, int32_t *C, int nb, int M,
@@ -468,7 +479,9 @@ int ivit_layernorm_requant(ivit_handle h, const int16_t *x, int64_t rows, int C,
 /* ---- a8  PatchEmbed.forward: QuantConv2d(kernel=stride=P) -> QuantAct(16)
  * (layers_quant.py:184-196, quant_modules.py:297-330), then class token + position
  * embedding (vit_quant.py:259-265).
- * ivit_im2col_patch: NCHW int8 image -> [B*gh*gw, Cin*P*P] rows in conv-weight order.    */
+ * ivit_im2col_patch: NCHW int8 image -> [B*gh*gw, Cin*P*P] rows in conv-weight order, any B
+ * (B * gh is its grid beyond 65535 images).  ivit_embed_finish and ivit_patch_embed take B <= 65535 (an image is one
+ * gridDim.y): IVIT_ERR_INVALID / IVIT_ERR_UNSUPPORTED beyond, nothing launched.           */
 /* Alignment: img and rows 16-byte aligned; IVIT_ERR_INVALID otherwise, nothing launched. */
 /* Overlap: rows may not overlap img: IVIT_ERR_INVALID, nothing launched. */
 int ivit_im2col_patch(ivit_handle h, const int8_t *img, int B, int Cin, int H, int W, int P,
@@ -560,7 +573,12 @@ int ivit_vit_workspace_init(ivit_vit m, void *workspace, size_t bytes, int batch
 /* images int8 [batch, in_chans, img, img] -> logits int32 [batch, num_classes].
  * nslices == 1: everything on the handle's stream.  nslices > 1: the batch is cut into slices that
  * run on internal streams forked from / joined to the handle's stream with events, so VALU-bound
- * kernels of one slice overlap MFMA-bound GEMMs of another.  Same integers either way.          */
+ * kernels of one slice overlap MFMA-bound GEMMs of another.  Same integers either way.
+ * A slice holds at most 65535 images (an image is one gridDim.y of the embedding launches), and at most 65535 / num_heads where the
+ * model does not run the fused attention (head dim != 64 or more than 640 tokens: an (image, head) is one matrix of the batched
+ * products).  A forward, and every runner entry with a forward in it, whose largest slice ceil(batch / nslices) is larger returns
+ * IVIT_ERR_UNSUPPORTED before anything is launched, with "images per slice" and the limit in ivit_last_error: use more slices.
+ * ivit_swin_forward has no such limit.                                                          */
 int ivit_vit_forward(ivit_vit m, const int8_t *images, int batch, int nslices, void *workspace,
                      size_t bytes, int32_t *logits);
 /* hipGraph of one ivit_vit_forward call with fixed buffers; launch replays it on the handle's
