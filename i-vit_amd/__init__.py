@@ -29,6 +29,7 @@ _LAZY = {
     "SwinEngine": ("swin_engine", "SwinEngine"),
     "load_reference_state_dict": ("checkpoint", "load_reference_state_dict"),
     "topk_reference": ("predict", "topk_reference"), "evaluate": ("predict", "evaluate"),
+    "load_engine": ("model_file", "load_engine"),
 }
 
 

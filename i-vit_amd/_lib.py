@@ -1,10 +1,11 @@
-"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h and include/ivit_search.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
+"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h and include/ivit_modelfile.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
 restated here: the Structures, the status codes and every argtypes / restype are derived from the headers by _abi.py (the mapping
 rule is stated there).  ivit.h is frozen at IVIT_VERSION 111: ABI / SIGNATURES / RESTYPES are its prototypes and stay what they are;
 the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES, of ivit_features.h,
 under FEATURES_ABI / FEATURES_SIGNATURES / FEATURES_RESTYPES, of ivit_attnmap.h, under ATTNMAP_ABI / ATTNMAP_SIGNATURES /
 ATTNMAP_RESTYPES, of ivit_classmap.h, under CLASSMAP_ABI / CLASSMAP_SIGNATURES / CLASSMAP_RESTYPES, of ivit_hidden.h, under
-HIDDEN_ABI / HIDDEN_SIGNATURES / HIDDEN_RESTYPES, and of ivit_search.h, under SEARCH_ABI / SEARCH_SIGNATURES / SEARCH_RESTYPES.
+HIDDEN_ABI / HIDDEN_SIGNATURES / HIDDEN_RESTYPES, of ivit_search.h, under SEARCH_ABI / SEARCH_SIGNATURES / SEARCH_RESTYPES, and of
+ivit_modelfile.h, under MODELFILE_ABI / MODELFILE_SIGNATURES / MODELFILE_RESTYPES.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -113,6 +114,20 @@ _search_signatures = _abi.signatures(SEARCH_ABI, _structs)
 SEARCH_RESTYPES = {name: ret for name, (ret, args) in _search_signatures.items()}
 SEARCH_SIGNATURES = {name: args for name, (ret, args) in _search_signatures.items()}
 
+# include/ivit_modelfile.h, likewise; it declares one struct of its own, ivit_model_info (ModelInfo here), beside those of ivit.h
+MODELFILE_ABI = _abi.MODELFILE_ABI
+IVIT_MODELFILE_VERSION = MODELFILE_ABI.constants["IVIT_MODELFILE_VERSION"]
+assert set(MODELFILE_ABI.structs) == set(ABI.structs) | {"ivit_model_info"} and not set(MODELFILE_ABI.functions) & (
+    set(ABI.functions) | set(EVAL_ABI.functions) | set(FEATURES_ABI.functions) | set(ATTNMAP_ABI.functions) | set(CLASSMAP_ABI.functions)
+    | set(HIDDEN_ABI.functions) | set(SEARCH_ABI.functions))
+_modelfile_structs = dict(_structs)
+_modelfile_structs.update((n, c) for n, c in _abi.structures(MODELFILE_ABI, dict(STRUCT_NAMES, ivit_model_info="ModelInfo")).items()
+                          if n not in _structs)
+ModelInfo = _modelfile_structs["ivit_model_info"]
+_modelfile_signatures = _abi.signatures(MODELFILE_ABI, _modelfile_structs)
+MODELFILE_RESTYPES = {name: ret for name, (ret, args) in _modelfile_signatures.items()}
+MODELFILE_SIGNATURES = {name: args for name, (ret, args) in _modelfile_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -121,7 +136,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -207,6 +222,14 @@ def bind_search(lib):
     return lib
 
 
+def bind_modelfile(lib):
+    """the same for every prototype of include/ivit_modelfile.h"""
+    for name, args in MODELFILE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, MODELFILE_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -218,7 +241,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH))))))))
+    _lib = bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH)))))))))
     return _lib
 
 

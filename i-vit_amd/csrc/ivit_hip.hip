@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h) over the gfx950 kernels.
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -2476,3 +2476,4 @@ extern "C" int ivit_search_merge(ivit_handle h, const int32_t *idx_in, const flo
 }
 
 #include "ivit_model.h"
+#include "ivit_modelfile.h"      // behind the runners: ivit_model_open ends in ivit_vit_create / ivit_swin_create

@@ -104,11 +104,15 @@ def frozen_vit(cfg, weights, scales):
 class ViTEngine(NativeEngine):
     PREFIX = "ivit_vit"
 
-    def __init__(self, cfg, consts, f32, device="cuda:0", blob=None, table=None):
+    def __init__(self, cfg, consts, f32, device="cuda:0", blob=None, table=None, input_scale=None):
         """consts/f32 from freeze.freeze_vit (rank 0) — or a pre-packed (blob, table)
-        received from a broadcast (then `consts` may be None)."""
+        received from a broadcast or read from a model file (then `consts` may be None).  input_scale: the scale of qact_input;
+        by default freeze_vit's "s_in" where f32 holds it."""
         self._plans, self._mlp_plans = {}, {}       # before anything can raise: __del__ reads them
         super().__init__(cfg, device)
+        if input_scale is None and "s_in" in f32:
+            input_scale = f32["s_in"]
+        self._input_scale = None if input_scale is None else float(np.float32(input_scale))
         if blob is None:
             blob, table = pack_constants(consts)
         self.f32 = {k: float(np.float32(v)) for k, v in f32.items()}
@@ -207,6 +211,10 @@ class ViTEngine(NativeEngine):
 
     def head_scale(self):
         return self.head_scale_host()
+
+    def _file_package(self):
+        self.feature_scale_host()                   # a file holds "feat.s": the engine says what to do where it is missing
+        return "vit", {k: ("f", v) for k, v in self.f32.items()}, {}
 
     @property
     def num_features(self):

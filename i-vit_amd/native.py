@@ -120,6 +120,7 @@ class NativeEngine:
         self._hidden_out = SideOutputs(self._native_ws)     # (hid16, hid32, index list) per (batch, slices, sites, layout)
         self._gstream = None                    # the stream graphs are captured and replayed on, made by the first capture
         self._head_scale_host = None
+        self._input_scale = None                # the scale of qact_input, where the engine was told (input_scale_host)
         self.last_logits = None
 
     def _load(self, blob, table):
@@ -140,6 +141,29 @@ class NativeEngine:
             o, _, shp = self.table["head.scale"]
             self._head_scale_host = self.blob[o:o + 4 * int(np.prod(shp))].cpu().numpy().view(np.float32).copy()
         return self._head_scale_host.copy()
+
+    def input_scale_host(self):
+        """host float: the scale the int8 images are quantised at (the reference's qact_input), for an engine built from scales or
+        loaded from a model file; IvitError for an engine that was never told (built from a broadcast package without
+        input_scale=)"""
+        if self._input_scale is None:
+            raise _lib.IvitError("this engine was never told its input scale: build it from scales, load it from a model file, or pass "
+                                 "input_scale= to the constructor")
+        return self._input_scale
+
+    def _file_package(self):
+        """(kind, scalars without "input.s", extras) of model_file.write for this engine"""
+        raise NotImplementedError
+
+    def save(self, path):
+        """the engine as a model file (include/ivit_modelfile.h, ivit_amd.model_file): the configuration, the constants blob as it
+        lies in device memory, the host scalars, the input scale — what `ivit_amd.load_engine` and the C library's
+        `ivit_model_open` read.  Returns `path`.  IvitError where the engine lacks what a file must hold (the input scale, the
+        features' scale, a Swin's class_scale)."""
+        from . import model_file
+        kind, scalars, extras = self._file_package()
+        scalars = dict(scalars, **{"input.s": ("f", float(np.float32(self.input_scale_host())))})
+        return model_file.write(path, kind, self.cfg, self.blob.cpu().numpy(), self.table, scalars, extras)
 
     def _entry(self, suffix, *args):
         name = self.PREFIX + suffix

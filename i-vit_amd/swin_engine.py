@@ -127,10 +127,14 @@ def check_swin_windows(cfg):
 class SwinEngine(NativeEngine):
     PREFIX = "ivit_swin"
 
-    def __init__(self, cfg, weights, scales, device="cuda:0", packed=None, exp_tables=False):
-        """weights/scales: freeze here (rank 0) — or `packed` = (blob, table, host) received from a broadcast.
-        exp_tables: see freeze_swin."""
+    def __init__(self, cfg, weights, scales, device="cuda:0", packed=None, exp_tables=False, input_scale=None, class_scale=None):
+        """weights/scales: freeze here (rank 0) — or `packed` = (blob, table, host) received from a broadcast or read from a model
+        file.  exp_tables: see freeze_swin.  input_scale, class_scale: what a model file carries beside the package (the scale of
+        qact_input; float32 [num_classes], see `class_scale`); by default they come from `scales` and `weights` where those are given."""
         super().__init__(cfg, device)
+        if input_scale is None and scales is not None:
+            input_scale = scales.get("qact_input")
+        self._input_scale = None if input_scale is None else float(np.float32(input_scale))
         check_swin_windows(cfg)
         blob, table, host = packed if packed is not None else packed_swin(cfg, weights, scales, exp_tables)
         self.host_consts = host
@@ -154,7 +158,11 @@ class SwinEngine(NativeEngine):
         self._class_scale = None
         if weights is not None:
             fc_sf = quantize_weight(weights["head.weight"])[1]
-            self._class_scale = torch.from_numpy((np.float32(self.token_scale_host()) * fc_sf).astype(np.float32)).to(self.device)
+            class_scale = (np.float32(self.token_scale_host()) * fc_sf).astype(np.float32)
+        if class_scale is not None:
+            class_scale = np.ascontiguousarray(class_scale, np.float32)
+            assert class_scale.shape == (cfg.num_classes,), "class_scale: float32 [num_classes]"
+            self._class_scale = torch.from_numpy(class_scale).to(self.device)
         self._streams = []              # forward_ops with nslices > 1
         self.use_exp_tables = True      # forward_ops only: False issues the arithmetic Shiftmax in every window (cross-check)
 
@@ -181,8 +189,12 @@ class SwinEngine(NativeEngine):
         """device float32 [num_classes]: fl32(token_scale * head.fc_scaling_factor[c]), the unit of class c's map"""
         if self._class_scale is None:
             raise _lib.IvitError("this engine was built without the head's float weights (a broadcast package): class_scale needs "
-                                 "their per-class scale; build the engine from weights and scales")
+                                 "their per-class scale; build the engine from weights and scales, or load it from a model file")
         return self._class_scale
+
+    def _file_package(self):
+        self.feature_scale_host()                   # a file holds "feat.s" and "class_scale": the engine says where either is missing
+        return "swin", dict(self.host_consts), {"class_scale": self.class_scale.cpu().numpy()}
 
     def _class_map_args(self, images, k, classes, logits, nslices):
         """(arguments of the class-map entries, cache key, buffers, what the caller gets) for one batch: val, tok8, cam32, map32 —

@@ -17,6 +17,8 @@ data.npz holds `labels` [N] and the images in one of three forms:
 The model is a name from ivit_amd.CONFIGS / SWIN_CONFIGS with either
   --golden F      the seeded synthetic weights and the calibrated scales recorded in a tests/golden fixture, or
   --state-dict F  a reference state dict / checkpoint (float parameters and act_scaling_factor buffers; ivit_amd.checkpoint).
+Or, in place of --model and its source, --model-file F: a frozen model file written by tools/freeze.py or `engine.save`
+(include/ivit_modelfile.h); nothing is frozen again, the input scale comes from the file, "model" is the file's configuration name.
 Prints one JSON line {"n", "correct", "acc", "model", "batch"}; under torch.distributed.run every rank evaluates its shard of the
 file and rank 0 prints the reduced result (IVIT_DIST_BACKEND picks the backend, as in bench.py).
 --loss scores every image on the device (ivit_amd.predict.evaluate(loss=True): rank and negative log-likelihood of the label, any
@@ -38,6 +40,18 @@ from ivit_amd.predict import evaluate  # noqa: E402
 
 
 def build_engine(args, device):
+    if args.model_file:
+        if args.model:
+            raise SystemExit("--model-file holds the model: give it without --model")
+        import ivit_amd.model_file as mf
+        try:
+            eng = mf.load_engine(args.model_file, device=device)
+        except mf.ModelFileError as e:
+            raise SystemExit(f"{args.model_file}: {e}")
+        args.model = eng.cfg.name
+        return eng.cfg, eng, np.float32(eng.input_scale_host())
+    if not args.model:
+        raise SystemExit("--model NAME is required with --golden / --state-dict")
     swin = args.model in iv.SWIN_CONFIGS
     cfg = (iv.SWIN_CONFIGS if swin else iv.CONFIGS)[args.model]
     if args.state_dict:
@@ -59,10 +73,11 @@ def build_engine(args, device):
 def add_input_arguments(ap):
     """the data file, the model and its source, the batch and the resize: what tools/embed.py takes too"""
     ap.add_argument("data")
-    ap.add_argument("--model", required=True)
+    ap.add_argument("--model", help="a name from CONFIGS / SWIN_CONFIGS, with --golden or --state-dict")
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--golden")
     src.add_argument("--state-dict")
+    src.add_argument("--model-file", help="a frozen model file (tools/freeze.py, engine.save) in place of --model and its source")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--resize", type=int, default=0, help="shorter side before the centre crop (default: int(crop / 0.875))")
     ap.add_argument("--resample", choices=("torch", "pil"), default="torch",
