@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h) over the gfx950 kernels.
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -36,6 +36,7 @@
 #include "ivit_classmap.h"
 #include "ivit_hidden.h"
 #include "ivit_search.h"
+#include "ivit_probe.h"
 #include "ivit_preprocess.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
@@ -2472,6 +2473,64 @@ extern "C" int ivit_search_merge(ivit_handle h, const int32_t *idx_in, const flo
     if (nq == 0) return IVIT_OK;
     search_select_launch<true>(h, nullptr, idx_in, val_in, nq, (long long)ncand, k, idx, val);
     LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- linear probe (include/ivit_probe.h)
+extern "C" int ivit_probe_accumulate(ivit_handle h, const int8_t *feat8, const int64_t *labels, int64_t rows, int dim, int num_classes, int splits,
+                                     int64_t *gram, int64_t *class_sum, int64_t *count) {
+    CHECK_H(h);
+    REQUIRE(h, feat8 && labels && gram && class_sum && count, "feat8, labels, gram, class_sum or count is null");
+    REQUIRE(h, rows >= 0, "rows is negative");
+    REQUIRE(h, num_classes >= 1 && num_classes <= PROBE_MAX_CLASSES, "num_classes must be in 1 .. 65536");
+    REQUIRE(h, splits >= 0 && splits <= 65535, "splits must be in 0 .. 65535");
+    if (dim < PROBE_MIN_DIM || dim > PROBE_MAX_DIM || (dim % 64) != 0) {
+        snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 64 in 64 .. 1024", __func__);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    REQUIRE_A16(h, feat8, "feat8");
+    REQUIRE_ALIGNED(h, labels, "labels", 8);
+    REQUIRE_ALIGNED(h, gram, "gram", 8);
+    REQUIRE_ALIGNED(h, class_sum, "class_sum", 8);
+    REQUIRE_ALIGNED(h, count, "count", 8);
+    {
+        const struct { const void *p; size_t n; const char *name; } ins[2] = {{feat8, (size_t)rows * dim, "feat8"}, {labels, (size_t)rows * 8, "labels"}},
+            outs[3] = {{gram, (size_t)dim * dim * 8, "gram"}, {class_sum, (size_t)num_classes * dim * 8, "class_sum"}, {count, (size_t)num_classes * 8, "count"}};
+        for (const auto &i : ins)
+            for (const auto &o : outs) REQUIRE_DISJOINT(h, i.p, i.n, i.name, o.p, o.n, o.name, OVL_IN);
+        REQUIRE_DISJOINT(h, gram, outs[0].n, "gram", class_sum, outs[1].n, "class_sum", OVL_OUT);
+        REQUIRE_DISJOINT(h, gram, outs[0].n, "gram", count, outs[2].n, "count", OVL_OUT);
+        REQUIRE_DISJOINT(h, class_sum, outs[1].n, "class_sum", count, outs[2].n, "count", OVL_OUT);
+    }
+    if (rows == 0) return IVIT_OK;
+    ProbeArgs a;
+    a.feat8 = feat8; a.labels = (const long long *)labels;
+    a.gram = (unsigned long long *)gram; a.class_sum = (unsigned long long *)class_sum; a.count = (unsigned long long *)count;
+    a.rows = rows; a.dim = dim; a.num_classes = num_classes; a.nblk = (dim + PROBE_BLK - 1) / PROBE_BLK;
+    const long long cus = persistent_cus(h), nrows = rows;
+    // the parts of a launch: the caller's count, or the library's; `per` rows each, rounded up to `unit`
+    auto parts_of = [&](long long chosen, long long unit, long long *per) {
+        const long long s = splits > 0 ? splits : std::max(1ll, std::min(chosen, 65535ll));
+        *per = ((nrows + s - 1) / s + unit - 1) / unit * unit;
+        return (unsigned)(splits > 0 ? s : (nrows + *per - 1) / *per);
+    };
+    {   // the Gram matrix: about two workgroups per CU, in parts of at least 4096 rows (a part ends with dim^2 atomic adds per block row)
+        const long long pairs = (long long)a.nblk * (a.nblk + 1) / 2;
+        const unsigned parts = parts_of(std::min((2 * cus + pairs - 1) / pairs, nrows / 4096), PROBE_CHUNK, &a.per);
+        probe_gram_kernel<<<dim3((unsigned)pairs, parts), 256, 0, h->stream>>>(a);
+        LAUNCH_CHECK(h);
+    }
+    {   // class sums and counts: privatised in LDS where [num_classes, dim + 1] int32 fit 64 KB, straight global adds otherwise
+        const size_t lds = (size_t)num_classes * (dim + 1) * 4;
+        if (lds <= PROBE_CLASS_LDS_BYTES) {
+            const unsigned parts = parts_of(std::min(2 * cus, nrows / 256), 1, &a.per);
+            probe_class_kernel<true><<<parts, 256, lds, h->stream>>>(a);
+        } else {
+            const unsigned parts = parts_of((nrows * (dim / 16) + 255) / 256, 1, &a.per);                // about one (row, 16 features) per thread
+            probe_class_kernel<false><<<parts, 256, 0, h->stream>>>(a);
+        }
+        LAUNCH_CHECK(h);
+    }
     return IVIT_OK;
 }
 

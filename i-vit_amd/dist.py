@@ -70,3 +70,23 @@ def evaluate_sharded(engine, images, labels, batch, rank, world, topk=(1, 5), tr
         lo, hi, images = 0, hi - lo, images[lo:hi]
     batches = ((images[a:min(a + batch, hi)], labels[a:min(a + batch, hi)]) for a in range(lo, hi, batch))
     return evaluate(engine, batches, topk=topk, transform=transform, rank=rank, world=world, loss=loss)
+
+
+def probe_fit_sharded(engine, images, labels, batch, rank, world, num_classes, ridge=1e-3, transform=None, stats=None):
+    """ivit_amd.predict.probe_fit over THIS rank's contiguous share (shard_range) of `images` / `labels`, in batches of `batch`:
+    every rank accumulates the statistics of its own images (its labels uploaded once, no collective and no host-device copy per
+    step), ONE all_reduce (sum) of the three int64 tensors joins them — exact integers: the same bits on every rank as one process
+    over all the images — and every rank solves the same small system.  Returns the Head on every rank.  `stats`: the caller's own
+    ZEROED ProbeStats to add into; it holds the reduced statistics afterwards (`probe.fit` refits from them with another ridge)."""
+    from .probe import ProbeStats, fit
+    lo, hi = shard_range(len(labels), rank, world)
+    mine = torch.as_tensor(labels)[lo:hi].to(device=engine.device, dtype=torch.int64)
+    if stats is None:
+        stats = ProbeStats(engine.num_features, num_classes, engine.device)
+    for a in range(lo, hi, batch):
+        b = min(a + batch, hi)
+        x = images[a:b]
+        engine.probe_accumulate(transform(x) if transform is not None else x, mine[a - lo:b - lo], stats)
+    if world > 1:
+        stats.all_reduce()
+    return fit(stats, engine.feature_scale_host(), ridge)

@@ -216,6 +216,9 @@ class ViTEngine(NativeEngine):
         self.feature_scale_host()                   # a file holds "feat.s": the engine says what to do where it is missing
         return "vit", {k: ("f", v) for k, v in self.f32.items()}, {}
 
+    def _with_head_engine(self, cfg, blob, table, head):
+        return type(self)(cfg, None, dict(self.f32), device=self.device, blob=blob, table=table, input_scale=self._input_scale)
+
     @property
     def num_features(self):
         return self.cfg.embed_dim

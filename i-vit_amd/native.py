@@ -7,7 +7,8 @@ negative log-likelihood behind them instead, ivit_<model>_score of include/ivit_
 reference's forward_features: the integers the head reads and their fp32 form, with or without the head, ivit_<model>_features of
 include/ivit_features.h) and `hidden_states` / `capture_hidden_states` (the 16-bit outputs of chosen blocks or stages and their
 fp32 form, ivit_<model>_hidden_states of include/ivit_hidden.h); `retrieve` is `features` with a gallery search behind it
-(include/ivit_search.h, ivit_amd/search.py).  Every eager way is its arguments and one `_eager` call, every captured way its arguments and one
+(include/ivit_search.h, ivit_amd/search.py), `probe_accumulate` is `features` with the statistics of a linear probe behind it and
+`with_head` the way a fitted head comes back as a new engine (include/ivit_probe.h, ivit_amd/probe.py).  Every eager way is its arguments and one `_eager` call, every captured way its arguments and one
 `_capture` call; what lives beside a logits buffer (idx / val, rank / nll, feat8 / feat32, a ViT's attn16 / map32) follows the one
 rule of `SideOutputs`.  A subclass names its C prefix, builds its parameter structs (`_native_params`), says where its feature
 scale lies (`feature_scale_host`, `num_features`) and keeps its `forward_ops`.  torch is used for device memory and streams only.
@@ -394,6 +395,48 @@ class NativeEngine:
         idx, val = gallery.search(feat8, k=k)
         out = (idx, val, feat8)
         return tuple(t.clone() for t in out) if copy else out
+
+    # ---- linear probe (include/ivit_probe.h, ivit_amd/probe.py): the statistics of a training pass, and the way back into an engine
+    def probe_accumulate(self, images, labels, stats, nslices=1):
+        """images int8 [B, C, H, W], labels int64 device tensor [B], stats an `ivit_amd.probe.ProbeStats` of this backbone's
+        num_features: `features` without the head, then `stats.add(feat8, labels)` on the same stream (ivit_probe_accumulate) — the
+        batch's Gram matrix, class sums and counts ADDED into `stats` as `predict.probe_stats_reference` states them; a label outside
+        stats.num_classes is ignored.  Nothing is kept of the features and nothing synchronises.  Returns feat8, the engine's own
+        buffer for this (batch, nslices)."""
+        self._check_labels(labels, images.shape[0])
+        feat8 = self.features(images, nslices=nslices)[0]
+        stats.add(feat8, labels)
+        return feat8
+
+    def _with_head_engine(self, cfg, blob, table, head):
+        """a new engine of this class on the repacked constants, through the pre-packed route `load_engine` uses"""
+        raise NotImplementedError
+
+    def with_head(self, head):
+        """head an `ivit_amd.probe.Head` on this backbone's features -> a NEW engine of the same class with that head in place of
+        the one this engine was frozen with: the constants records are taken out of the blob by the table, "head.w", "head.b" and
+        "head.scale" replaced, num_classes set (a Swin's class_scale too: fl32(token_scale * weight_scale[c])), repacked with
+        `pack_constants`; the input scale and the features' scale are kept.  Every entry of the new engine works on the new classes
+        (forward, predict, score, evaluate, class_map, save — and ivit_model_open on the saved file).  This engine is unchanged.
+        IvitError where the engine lacks its features' scale, where the head's width is not num_features or where the head was
+        quantised on another features' scale."""
+        import dataclasses
+        from .engine import pack_constants
+        s_feat = np.float32(self.feature_scale_host())
+        if head.dim != self.num_features:
+            raise _lib.IvitError(f"head.weight is [{head.num_classes}, {head.dim}]: this backbone has {self.num_features} features")
+        if np.float32(head.feature_scale) != s_feat:
+            raise _lib.IvitError(f"the head was quantised on a features' scale of {head.feature_scale!r}, this engine's is {float(s_feat)!r}")
+        blob = self.blob.cpu().numpy()
+        consts = {}
+        for name, (o, dt, shp) in self.table.items():
+            n = int(np.prod(shp)) * np.dtype(dt).itemsize
+            consts[name] = blob[o:o + n].view(np.dtype(dt)).reshape(shp).copy()
+        consts["head.w"] = np.ascontiguousarray(head.w8, np.int8)
+        consts["head.b"] = np.ascontiguousarray(head.b32, np.int32)
+        consts["head.scale"] = np.ascontiguousarray(head.scale, np.float32)
+        blob, table = pack_constants(consts)
+        return self._with_head_engine(dataclasses.replace(self.cfg, num_classes=head.num_classes), blob, table, head)
 
     def _capture(self, suffix, images, args, key, bufs, out, side=None):
         """hipGraph of the entry PREFIX + suffix on fixed buffers; returns a callable that replays it and returns `out`.  `side`:

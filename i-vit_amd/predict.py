@@ -445,3 +445,69 @@ def _evaluate_with_loss(engine, batches, topk, transform, rank, world):
     correct = {j: int(c[1 + t]) for t, j in enumerate(topk)}
     return {"n": n, "correct": correct, "acc": {j: (100.0 * v / n if n else float("nan")) for j, v in correct.items()},
             "loss": c[-1] / n if n else float("nan")}
+
+
+# ---------------------------------------------------------------- linear probe (include/ivit_probe.h, ivit_amd/probe.py)
+def probe_stats_reference(feat8, labels, num_classes):
+    """feat8 int8 [rows, dim], labels integers [rows] -> (gram int64 [dim, dim], class_sum int64 [num_classes, dim], count int64
+    [num_classes]): the statistics `ivit_probe_accumulate` ADDS into its buffers.  Row r takes part iff 0 <= labels[r] < num_classes
+    (as int64: 2^32 + 3 is no class); gram = X^T X over those rows, class_sum[c] the sum of class c's rows, count[c] their number.
+    Exact integers."""
+    x, lab = np.asarray(feat8), np.asarray(labels).astype(np.int64).reshape(-1)
+    assert x.ndim == 2 and x.dtype == np.int8 and lab.shape == (x.shape[0],)
+    C = int(num_classes)
+    keep = (lab >= 0) & (lab < C)
+    x, lab = x[keep].astype(np.int64), lab[keep]
+    gram = x.T @ x
+    class_sum = np.zeros((C, x.shape[1]), np.int64)
+    np.add.at(class_sum, lab, x)
+    count = np.bincount(lab, minlength=C).astype(np.int64)
+    return gram, class_sum, count
+
+
+def probe_system(gram, class_sum, count, ridge=1e-3):
+    """the linear system of the ridge probe from the statistics, float64 throughout -> (A [dim, dim], M [C, dim], mu [dim], n):
+        n = sum(count);  mu = sum_c class_sum[c] / n;  Gc = gram / n - mu mu^T;  M[c] = class_sum[c] / n - (count[c] / n) mu
+        A = Gc + ridge * (trace(Gc) / dim) * I
+    Gc is the features' covariance, M[c] the covariance of the features with class c's indicator; the ridge is relative to the mean
+    feature variance, so one value serves every model."""
+    gram, class_sum, count = (np.asarray(a).astype(np.float64) for a in (gram, class_sum, count))
+    dim = gram.shape[0]
+    n = count.sum()
+    if not n > 0:
+        raise ValueError("the statistics hold no row")
+    mu = class_sum.sum(axis=0) / n
+    Gc = gram / n - np.outer(mu, mu)
+    M = class_sum / n - np.outer(count / n, mu)
+    A = Gc + float(ridge) * (np.trace(Gc) / dim) * np.eye(dim)
+    return A, M, mu, n
+
+
+def probe_fit_reference(gram, class_sum, count, ridge=1e-3):
+    """the statistics -> (V float64 [C, dim], b float64 [C]): V = solve(A, M^T)^T and b[c] = count[c] / n - V[c] . mu with
+    `probe_system`'s A, M, mu, n — the least-squares fit of the classes' indicators on the features' integers x (prediction
+    V[c] . x + b[c], on a 0 .. 1 target).  A class with count 0 gets V[c] = 0 and b[c] = 0."""
+    A, M, mu, n = probe_system(gram, class_sum, count, ridge)
+    cnt = np.asarray(count).astype(np.float64)
+    V = np.linalg.solve(A, M.T).T
+    b = cnt / n - V @ mu
+    empty = cnt == 0
+    V[empty] = 0.0
+    b[empty] = 0.0
+    return V, b
+
+
+def probe_fit(engine, batches, num_classes, ridge=1e-3, transform=None, stats=None):
+    """`embed`'s loop over (images, labels) ending in `probe.fit`: every batch is one engine.probe_accumulate — `features` without the
+    head, then ivit_probe_accumulate on the same stream; no feature is kept and nothing inside the loop synchronises.  Returns the
+    Head for `engine.with_head`.  `stats`: the caller's own ProbeStats to add into — it then holds the statistics afterwards, from
+    which `probe.fit` refits with another ridge without a second pass."""
+    from .probe import ProbeStats, fit
+    if stats is None:
+        stats = ProbeStats(engine.num_features, num_classes, engine.device)
+    for images, labels in batches:
+        if transform is not None:
+            images = transform(images)
+        labels = torch.as_tensor(labels).to(device=engine.device, dtype=torch.int64, non_blocking=True).reshape(-1)
+        engine.probe_accumulate(images, labels, stats)
+    return fit(stats, engine.feature_scale_host(), ridge)

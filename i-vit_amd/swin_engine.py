@@ -169,6 +169,11 @@ class SwinEngine(NativeEngine):
     def _native_params(self):
         return swin_native_params(self.cfg, self.table, self.f, self.dy, self.blob.data_ptr())
 
+    def _with_head_engine(self, cfg, blob, table, head):
+        class_scale = (np.float32(self.token_scale_host()) * np.asarray(head.weight_scale, np.float32)).astype(np.float32)
+        return type(self)(cfg, None, None, device=self.device, packed=(blob, table, dict(self.host_consts)), input_scale=self._input_scale,
+                          class_scale=class_scale)
+
     @property
     def num_features(self):
         return self.cfg.num_features
