@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h) over the gfx950 kernels.
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h) over the gfx950 kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -38,6 +38,7 @@
 #include "ivit_search.h"
 #include "ivit_probe.h"
 #include "ivit_preprocess.h"
+#include "ivit_views.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -340,6 +341,99 @@ int ivit_eval_transform_u8(ivit_handle h, const uint8_t *pixels, size_t pixels_b
                            float scale, int8_t *nchw) {
     CHECK_H(h);
     return launch_pil_eval<true>(h, __func__, pixels, pixels_bytes, desc_host, desc_dev, B, size, crop, mean, std_, scale, nchw);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- image views (include/ivit_views.h, ivit_views.h)
+// The checks of both host tables, then ONE launch over the device tables: ceil(crop / PIL_BAND) x V workgroups.  What the checks
+// establish is what keeps the kernel inside pixels_bytes: every image inside the blob, every box inside its image (the taps of a view
+// stay inside its box), every window inside the resized box.
+template <bool NCHW>
+static int launch_pil_views(ivit_handle h, const char *fn, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *img_host,
+                            const ivit_image_desc *img_dev, int B, const ivit_view_desc *view_host, const ivit_view_desc *view_dev, int V,
+                            int crop, const float *mean, const float *std_, float scale, void *out) {
+    auto fail = [&](const char *what, const char *msg, int i) {
+        if (i >= 0) snprintf(h->err, sizeof(h->err), "%s: %s %d: %s", fn, what, i, msg);
+        else snprintf(h->err, sizeof(h->err), "%s: %s", fn, msg);
+        return IVIT_ERR_INVALID;
+    };
+    if (!(pixels && img_host && img_dev && out && B > 0 && V >= 0 && crop > 0 && (V == 0 || (view_host && view_dev))))
+        return fail("", "bad arguments", -1);
+    if (NCHW) {
+        if (!(mean && std_ && scale > 0.f)) return fail("", "bad arguments", -1);
+        if (!(std_[0] != 0.f && std_[1] != 0.f && std_[2] != 0.f)) return fail("", "zero std", -1);
+    }
+    const int nbands = (crop + PIL_BAND - 1) / PIL_BAND;
+    if ((long long)nbands * V * PIL_THREADS >= (1LL << 32)) return fail("", "V * ceil(crop / 32) blocks of 512 threads are 2^32 work-items or more", -1);
+    {   // the output against the whole pixel blob and both device tables
+        const size_t nout = (size_t)V * crop * crop * 3;
+        const char *oname = NCHW ? "nchw" : "out_hwc";
+        if (!ranges_disjoint(h, fn, pixels, pixels_bytes, "pixels", out, nout, oname, OVL_IN) ||
+            !ranges_disjoint(h, fn, img_dev, (size_t)B * sizeof(ivit_image_desc), "img_dev", out, nout, oname, OVL_IN) ||
+            !ranges_disjoint(h, fn, view_dev, (size_t)V * sizeof(ivit_view_desc), "view_dev", out, nout, oname, OVL_IN))
+            return IVIT_ERR_INVALID;
+    }
+    for (int i = 0; i < B; ++i) {
+        const ivit_image_desc &d = img_host[i];
+        if (d.h <= 0 || d.w <= 0) return fail("image", "non-positive side", i);
+        if (d.offset < 0) return fail("image", "negative offset", i);
+        const unsigned __int128 end = (unsigned __int128)d.offset + (unsigned __int128)d.h * (unsigned __int128)d.w * 3u;
+        if (end > (unsigned __int128)pixels_bytes) return fail("image", "reaches past pixels_bytes", i);
+    }
+    for (int i = 0; i < V; ++i) {
+        const ivit_view_desc &v = view_host[i];
+        if (v.image < 0 || v.image >= B) return fail("view", "image outside the image table", i);
+        const ivit_image_desc &d = img_host[v.image];
+        if (v.bw < 1 || v.bh < 1) return fail("view", "empty box", i);
+        if (v.x0 < 0 || v.y0 < 0 || (long long)v.x0 + v.bw > d.w || (long long)v.y0 + v.bh > d.h) return fail("view", "box outside the image", i);
+        if (v.rw < 1 || v.rh < 1 || v.rw > 65536 || v.rh > 65536) return fail("view", "resized size outside 1 .. 65536", i);
+        if (v.left < 0 || v.top < 0 || (long long)v.left + crop > v.rw || (long long)v.top + crop > v.rh)
+            return fail("view", "window outside the resized box", i);
+        if (v.flip != 0 && v.flip != 1) return fail("view", "flip must be 0 or 1", i);
+    }
+    if (V == 0) return IVIT_OK;
+    const float z = 0.f;
+    const int st = launch_dyn<pil_view_kernel<NCHW>>(h, dim3((unsigned)(nbands * V)), dim3(PIL_THREADS), (size_t)PIL_LDS_BYTES,
+                                                      (const unsigned char *)pixels, img_dev, view_dev, crop, nbands, NCHW ? mean[0] : z,
+                                                      NCHW ? mean[1] : z, NCHW ? mean[2] : z, NCHW ? std_[0] : z, NCHW ? std_[1] : z,
+                                                      NCHW ? std_[2] : z, NCHW ? scale : z, (unsigned char *)out);
+    if (st != IVIT_OK) return st;
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" {
+
+int ivit_view_resize_u8_pil(ivit_handle h, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *img_host,
+                            const ivit_image_desc *img_dev, int B, const ivit_view_desc *view_host, const ivit_view_desc *view_dev, int V,
+                            int crop, uint8_t *out_hwc) {
+    CHECK_H(h);
+    return launch_pil_views<false>(h, __func__, pixels, pixels_bytes, img_host, img_dev, B, view_host, view_dev, V, crop, nullptr, nullptr,
+                                   0.f, out_hwc);
+}
+
+int ivit_view_transform_u8(ivit_handle h, const uint8_t *pixels, size_t pixels_bytes, const ivit_image_desc *img_host,
+                           const ivit_image_desc *img_dev, int B, const ivit_view_desc *view_host, const ivit_view_desc *view_dev, int V,
+                           int crop, const float mean[3], const float std_[3], float scale, int8_t *nchw) {
+    CHECK_H(h);
+    return launch_pil_views<true>(h, __func__, pixels, pixels_bytes, img_host, img_dev, B, view_host, view_dev, V, crop, mean, std_, scale,
+                                  nchw);
+}
+
+int ivit_logits_view_sum(ivit_handle h, const int32_t *logits, int groups, int views, int num_classes, int32_t *out) {
+    CHECK_H(h);
+    REQUIRE(h, logits && out && groups >= 0 && num_classes >= 1, "bad arguments");
+    REQUIRE(h, views >= 1 && views <= VIEW_SUM_MAX_VIEWS, "views must be in 1 .. 64");
+    REQUIRE_DISJOINT(h, logits, (size_t)groups * views * num_classes * 4, "logits", out, (size_t)groups * num_classes * 4, "out", OVL_IN);
+    if (groups == 0) return IVIT_OK;
+    const bool vec = num_classes % 4 == 0 && (((uintptr_t)logits | (uintptr_t)out) & 15) == 0;
+    const long long per = vec ? num_classes / 4 : num_classes, n = (long long)groups * per;
+    const int grid = grid_for(h, n, VIEW_SUM_THREADS);              // a grid-stride stream: at most 16 blocks per CU
+    if (vec) logits_view_sum_kernel<true><<<grid, VIEW_SUM_THREADS, 0, h->stream>>>(logits, n, per, views, out);
+    else logits_view_sum_kernel<false><<<grid, VIEW_SUM_THREADS, 0, h->stream>>>(logits, n, per, views, out);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
 }
 
 }  // extern "C"

@@ -119,6 +119,9 @@ class NativeEngine:
         # (idx, val) per (batch, slices, k); (rank, nll) and (feat8, feat32) per (batch, slices): one SideOutputs per kind
         self._predict_out, self._score_out, self._features_out = (SideOutputs(self._native_ws) for _ in range(3))
         self._hidden_out = SideOutputs(self._native_ws)     # (hid16, hid32, index list) per (batch, slices, sites, layout)
+        # views (include/ivit_views.h): (sum, idx, val) per (groups, k), (sum, rank, nll) per (groups, 0); the scale vector per V
+        self._views_out = ShapeCache(self._make_view_buffers)
+        self._view_scale = {}
         self._gstream = None                    # the stream graphs are captured and replayed on, made by the first capture
         self._head_scale_host = None
         self._input_scale = None                # the scale of qact_input, where the engine was told (input_scale_host)
@@ -394,6 +397,66 @@ class NativeEngine:
         feat8 = self.features(images, nslices=nslices)[0]
         idx, val = gallery.search(feat8, k=k)
         out = (idx, val, feat8)
+        return tuple(t.clone() for t in out) if copy else out
+
+    # ---- views (include/ivit_views.h, ivit_amd/views.py): the mean logits of the V views of every image
+    def _make_view_buffers(self, G, k):
+        ncls = self.cfg.num_classes
+        if k:
+            return self._empty(torch.int32, G, ncls), self._empty(torch.int32, G, k), self._empty(torch.float32, G, k)
+        return self._empty(torch.int32, G, ncls), self._empty(torch.int32, G), self._empty(torch.float64, G)
+
+    def view_scale(self, views):
+        """device float32 [num_classes]: fl32(head_scale / fl32(views)), the scale of a sum over `views` views
+        (`predict.view_scale_reference`); made once per `views` and kept"""
+        if views not in self._view_scale:
+            from .predict import view_scale_reference
+            self._view_scale[views] = torch.from_numpy(view_scale_reference(self.head_scale_host(), views)).to(self.device)
+        return self._view_scale[views]
+
+    @staticmethod
+    def _view_groups(images, views):
+        """number of images behind a batch of views; ValueError where `views` is outside 1 .. 64 or the batch no multiple of it"""
+        from .predict import MAX_VIEWS
+        if not isinstance(views, (int, np.integer)) or not 1 <= views <= MAX_VIEWS:
+            raise ValueError(f"views = {views!r} outside 1 .. {MAX_VIEWS}")
+        if images.shape[0] % views:
+            raise ValueError(f"{images.shape[0]} images are no multiple of {views} views")
+        return images.shape[0] // int(views)
+
+    def _view_sum(self, images, views, k, nslices):
+        """forward on the G * views images, then ivit_logits_view_sum on the same stream -> (G, scale vector, (sum, two side buffers))"""
+        G, views = self._view_groups(images, views), int(views)
+        scale = self.view_scale(views)                      # before the forward: its upload is made once, not in the loop
+        logits = self.forward(images, nslices=nslices)
+        bufs = self._views_out.get((G, int(k)))
+        self.h.call("ivit_logits_view_sum", _ptr(logits), G, views, self.cfg.num_classes, _ptr(bufs[0]))
+        return G, scale, bufs
+
+    def predict_views(self, images, views, k=5, nslices=1, copy=False):
+        """images int8 [G * views, C, H, W], the views of an image in consecutive rows (ivit_amd.views.view_transform of an
+        image-major table) -> (idx int32 [G, k], val float32 [G, k], logits_sum int32 [G, num_classes]) device tensors: `predict`
+        on the MEAN logits of every image's views.  The forward on all G * views images, then ivit_logits_view_sum (the integer
+        sum, saturated: `predict.view_sum_reference`) and ivit_logits_topk with the scale vector fl32(head_scale / fl32(views)),
+        on the same stream: idx and val are `predict.topk_reference` of the sum with `view_scale(views)`.  ValueError before
+        anything runs where views is outside 1 .. 64 or the batch is no multiple of it.  The results are the engine's own buffers
+        for this (G, k): copy=True (or clone) to keep them across calls."""
+        k = int(k)
+        if not 1 <= k <= min(16, self.cfg.num_classes):
+            raise ValueError(f"k = {k} outside 1 .. min(16, {self.cfg.num_classes})")
+        G, scale, (total, idx, val) = self._view_sum(images, views, k, nslices)
+        self.h.call("ivit_logits_topk", _ptr(total), _ptr(scale), G, self.cfg.num_classes, k, _ptr(idx), _ptr(val))
+        out = (idx, val, total)
+        return tuple(t.clone() for t in out) if copy else out
+
+    def score_views(self, images, labels, views, nslices=1, copy=False):
+        """images int8 [G * views, C, H, W] as `predict_views` takes them, labels int64 device tensor [G] -> (rank int32 [G], nll
+        float64 [G]): `score` on the MEAN logits of every image's views — `predict.score_reference` of the views' integer sum with
+        `view_scale(views)`.  Forward, ivit_logits_view_sum and ivit_logits_score on the same stream."""
+        self._check_labels(labels, self._view_groups(images, views))
+        G, scale, (total, rank, nll) = self._view_sum(images, views, 0, nslices)
+        self.h.call("ivit_logits_score", _ptr(total), _ptr(scale), _ptr(labels), G, self.cfg.num_classes, _ptr(rank), _ptr(nll))
+        out = (rank, nll)
         return tuple(t.clone() for t in out) if copy else out
 
     # ---- linear probe (include/ivit_probe.h, ivit_amd/probe.py): the statistics of a training pass, and the way back into an engine

@@ -11,6 +11,9 @@ vit_quant.py:278-282 / swin_quant.py:560-564), takes the cross-entropy and top-1
   * `evaluate` is validate() minus the data loader: hit counts — and with loss=True the sum of the losses — accumulate on the
     device, with device labels nothing inside the loop synchronises, and a multi-rank run ends with ONE all_reduce (DESIGN.md §6:
     no collective per step);
+  * `view_sum_reference` is the numpy statement of the contract of `ivit_logits_view_sum` (include/ivit_views.h): the integer sum of
+    the logits of the views of one image (ivit_amd/views.py); the engines' `predict_views` / `score_views` and
+    `evaluate(..., views=V)` are `predict` / `score` / `evaluate` on the mean logits of V views per image;
   * `features_reference` is the numpy statement of the contract of `ivit_features_f32` (include/ivit_features.h): the fp32 form of
     the int8 features the reference's forward_features returns (vit_quant.py:254-276, swin_quant.py:540-556), and `embed` is
     evaluate's loop for them (the engines' `features`);
@@ -75,6 +78,29 @@ def score_reference(acc, scale, labels):
     m = d.max(axis=1, keepdims=True)
     nll = np.log(np.exp(d - m).sum(axis=1)) - (d[rows, lc] - m[:, 0])
     return (np.where(valid, before, np.iinfo(np.int32).max).astype(np.int32), np.where(valid, nll, np.nan).astype(np.float64))
+
+
+MAX_VIEWS = 64      # VIEW_SUM_MAX_VIEWS of csrc/ivit_views.h
+
+
+def view_sum_reference(acc, views):
+    """acc int32 [G * views, ncls], the views of an image in consecutive rows -> int32 [G, ncls]: the contract of
+    `ivit_logits_view_sum` (include/ivit_views.h).  Row g is the sum of rows g * views .. g * views + views - 1 in int64, saturated to
+    int32.  The views share the head's per-class scale, so `topk_reference` / `score_reference` of the sum with
+    `view_scale_reference(scale, views)` are the values, the order and the loss of the MEAN logits."""
+    acc = np.asarray(acc)
+    assert acc.ndim == 2 and acc.dtype == np.int32
+    if not 1 <= views <= MAX_VIEWS:
+        raise ValueError(f"views = {views} outside 1 .. {MAX_VIEWS}")
+    if acc.shape[0] % views:
+        raise ValueError(f"{acc.shape[0]} rows are no multiple of {views} views")
+    s = acc.reshape(acc.shape[0] // views, views, acc.shape[1]).astype(np.int64).sum(axis=1)
+    return np.clip(s, np.iinfo(np.int32).min, np.iinfo(np.int32).max).astype(np.int32)
+
+
+def view_scale_reference(scale, views):
+    """the scale vector that goes with a sum over `views` views: fl32(scale / fl32(views)), one float32 division per class"""
+    return (np.asarray(scale, dtype=np.float32) / np.float32(views)).astype(np.float32)
 
 
 def features_reference(feat8, scale, mode=0):
@@ -367,7 +393,7 @@ def embed(engine, batches, transform=None, normalize=True):
     return torch.cat(rows)
 
 
-def evaluate(engine, batches, topk=(1, 5), transform=None, rank=0, world=1, loss=False):
+def evaluate(engine, batches, topk=(1, 5), transform=None, rank=0, world=1, loss=False, views=1):
     """validate() of the reference (quant_train.py:314-351) without its data loader — and, unless loss=True, without its loss.
 
     `batches` yields (images, labels) — with world > 1, THIS rank's share of them (ivit_amd.dist.shard_range); `transform`
@@ -385,18 +411,25 @@ def evaluate(engine, batches, topk=(1, 5), transform=None, rank=0, world=1, loss
     launch behind the forward), counts the images with rank < j — any j, no top-k and no clamp — and adds the losses into a
     float64 scalar on the device.  The loop synchronises as little as the other; the counts and the sum travel as ONE float64
     tensor [n, hits..., loss_sum] (integers are exact there up to 2^53) through the one all_reduce.  Returns the same dict
-    plus "loss": loss_sum / n, the reference's `Loss` (NaN if a label lies outside the classes)."""
+    plus "loss": loss_sum / n, the reference's `Loss` (NaN if a label lies outside the classes).
+
+    views=V > 1 (five-crop, ten-crop: ivit_amd/views.py): `transform` yields B * V images for the B labels of a batch, the V views
+    of an image in consecutive rows, and the loop calls engine.predict_views / engine.score_views instead — predictions and loss
+    of the MEAN logits of every image's views.  n counts images, not views.  views=1 is the path above, unchanged."""
     topk = tuple(int(j) for j in topk)
     if not topk or min(topk) < 1:
         raise ValueError("topk must name ranks >= 1")
+    views = int(views)
+    if not 1 <= views <= MAX_VIEWS:
+        raise ValueError(f"views = {views} outside 1 .. {MAX_VIEWS}")
     if loss:
-        return _evaluate_with_loss(engine, batches, topk, transform, rank, world)
+        return _evaluate_with_loss(engine, batches, topk, transform, rank, world, views)
     k = min(max(topk), int(engine.cfg.num_classes))
     n, hits = 0, None                                                   # hits[t]: images whose label is among the first topk[t]
     for images, labels in batches:
         if transform is not None:
             images = transform(images)
-        idx = torch.as_tensor(engine.predict(images, k=k)[0])
+        idx = torch.as_tensor(engine.predict(images, k=k)[0] if views == 1 else engine.predict_views(images, views=views, k=k)[0])
         labels = torch.as_tensor(labels).to(device=idx.device, dtype=torch.int64, non_blocking=True).reshape(-1, 1)
         within = (idx.to(torch.int64) == labels).cumsum(1) > 0         # [B, k]: label among the first j + 1 indices
         step = torch.stack([within[:, min(j, k) - 1].sum() for j in topk])
@@ -418,7 +451,7 @@ def evaluate(engine, batches, topk=(1, 5), transform=None, rank=0, world=1, loss
     return {"n": n, "correct": correct, "acc": {j: (100.0 * v / n if n else float("nan")) for j, v in correct.items()}}
 
 
-def _evaluate_with_loss(engine, batches, topk, transform, rank, world):
+def _evaluate_with_loss(engine, batches, topk, transform, rank, world, views=1):
     """evaluate(loss=True): see there"""
     n, sums = 0, None                                                   # sums: [hits of topk[0], ..., loss_sum] in float64
     for images, labels in batches:
@@ -426,7 +459,7 @@ def _evaluate_with_loss(engine, batches, topk, transform, rank, world):
             images = transform(images)
         device = getattr(engine, "device", "cpu")
         labels = torch.as_tensor(labels).to(device=device, dtype=torch.int64, non_blocking=True).reshape(-1)
-        rk, nll = (torch.as_tensor(t) for t in engine.score(images, labels))
+        rk, nll = (torch.as_tensor(t) for t in (engine.score(images, labels) if views == 1 else engine.score_views(images, labels, views=views)))
         step = torch.stack([(rk < j).sum().to(torch.float64) for j in topk] + [nll.to(torch.float64).sum()])
         sums = step if sums is None else sums + step
         n += rk.shape[0]

@@ -24,7 +24,11 @@ file and rank 0 prints the reduced result (IVIT_DIST_BACKEND picks the backend, 
 --loss scores every image on the device (ivit_amd.predict.evaluate(loss=True): rank and negative log-likelihood of the label, any
 --topk, no limit of 16), adds "loss" to the JSON line and prints validate()'s summary after it, ` * Loss 6.9078e+00 Prec@1 0.100
 Prec@5 0.500` (the loss as its meter formats it, quant_train.py:316; a Prec@j per --topk entry).  Without --loss the output is
-unchanged."""
+unchanged.
+--views 5 / --views 10 (ragged files and --resample pil): five-crop / ten-crop evaluation — the corners and the centre of the resized
+image, and with 10 the same of its mirror image (ivit_amd.views), all views of a batch in one launch, predictions and loss of the
+MEAN logits of every image's views (ivit_amd.predict.evaluate(views=)).  --batch still names the images a forward sees: a batch
+holds max(1, batch // views) images.  Adds "views" to the JSON line."""
 import argparse
 import json
 import os
@@ -111,7 +115,13 @@ def load_share(d, labels, cfg, s_in, args, device, lo, hi):
         desc = np.zeros(hi - lo, DESC_DTYPE)
         desc["offset"], desc["h"], desc["w"] = offsets[lo:hi] - first, shapes[lo:hi, 0], shapes[lo:hi, 1]
         mine = RaggedImages(torch.from_numpy(np.ascontiguousarray(pixels[first:last])).to(device), desc)
-        transform = lambda rag: eval_transform_pil(rag, s_in, size, cfg.img_size)      # noqa: E731
+        nviews = getattr(args, "views", 1)
+        if nviews == 1:
+            transform = lambda rag: eval_transform_pil(rag, s_in, size, cfg.img_size)      # noqa: E731
+        else:
+            from ivit_amd import views as vw
+            table = vw.five_crop_views if nviews == 5 else vw.ten_crop_views
+            transform = lambda rag: vw.view_transform(rag, table(rag, size, cfg.img_size), s_in, cfg.img_size)      # noqa: E731
     else:
         images = d["images"]
         if len(images) != len(labels):
@@ -122,6 +132,8 @@ def load_share(d, labels, cfg, s_in, args, device, lo, hi):
         elif not (images.dtype == np.int8 and images.shape[1:] == (cfg.in_chans, cfg.img_size, cfg.img_size)):
             raise SystemExit(f"images must be uint8 [N, H, W, 3] or int8 [N, {cfg.in_chans}, {cfg.img_size}, {cfg.img_size}]; "
                              f"got {images.dtype} {images.shape}")
+        if getattr(args, "views", 1) != 1:
+            raise SystemExit("--views needs raw pixels on the PIL-exact path: a ragged file, or uint8 images with --resample pil")
         mine = torch.from_numpy(np.ascontiguousarray(images[lo:hi])).to(device)      # this rank's share only
     return mine, transform
 
@@ -131,6 +143,8 @@ def main():
     add_input_arguments(ap)
     ap.add_argument("--topk", type=int, nargs="+", default=[1, 5])
     ap.add_argument("--loss", action="store_true", help="also the mean cross-entropy of the labels (validate()'s Loss), computed on the device")
+    ap.add_argument("--views", type=int, choices=(1, 5, 10), default=1,
+                    help="views per image: 1 the centre crop (default), 5 five-crop, 10 ten-crop; the mean logits are scored")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/evaluate.py needs a HIP device; the product path has no CPU fallback")
@@ -147,12 +161,13 @@ def main():
     lo, hi = ivdist.shard_range(len(labels), rank, world)
     share = torch.from_numpy(labels[lo:hi]).to(device)                           # once: no copy inside evaluate's loop
     mine, transform = load_share(d, labels, cfg, s_in, args, device, lo, hi)
-    batches = ((mine[a:a + args.batch], share[a:a + args.batch]) for a in range(0, hi - lo, args.batch))
-    out = evaluate(eng, batches, topk=args.topk, transform=transform, rank=rank, world=world, loss=args.loss)     # ends with the one all_reduce
+    step = max(1, args.batch // args.views)                                      # a forward still sees about --batch images
+    batches = ((mine[a:a + step], share[a:a + step]) for a in range(0, hi - lo, step))
+    out = evaluate(eng, batches, topk=args.topk, transform=transform, rank=rank, world=world, loss=args.loss, views=args.views)     # ends with the one all_reduce
     if rank == 0:
         print(json.dumps({"n": out["n"], "correct": {str(j): c for j, c in out["correct"].items()},
                           "acc": {str(j): a for j, a in out["acc"].items()}, "model": args.model, "batch": args.batch, "ranks": world,
-                          **({"loss": out["loss"]} if args.loss else {})}))
+                          **({"views": args.views} if args.views != 1 else {}), **({"loss": out["loss"]} if args.loss else {})}))
         if args.loss:
             print(" * Loss {:.4e} ".format(out["loss"]) + " ".join("Prec@{} {:.3f}".format(j, a) for j, a in out["acc"].items()))
     if world > 1:
