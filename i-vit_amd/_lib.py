@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h and include/ivit_views.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
+"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h and include/ivit_cluster.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
 restated here: the Structures, the status codes and every argtypes / restype are derived from the headers by _abi.py (the mapping
 rule is stated there).  ivit.h is frozen at IVIT_VERSION 111: ABI / SIGNATURES / RESTYPES are its prototypes and stay what they are;
 the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES, of ivit_features.h,
@@ -6,7 +6,8 @@ under FEATURES_ABI / FEATURES_SIGNATURES / FEATURES_RESTYPES, of ivit_attnmap.h,
 ATTNMAP_RESTYPES, of ivit_classmap.h, under CLASSMAP_ABI / CLASSMAP_SIGNATURES / CLASSMAP_RESTYPES, of ivit_hidden.h, under
 HIDDEN_ABI / HIDDEN_SIGNATURES / HIDDEN_RESTYPES, of ivit_search.h, under SEARCH_ABI / SEARCH_SIGNATURES / SEARCH_RESTYPES, of
 ivit_modelfile.h, under MODELFILE_ABI / MODELFILE_SIGNATURES / MODELFILE_RESTYPES, of ivit_probe.h, under PROBE_ABI /
-PROBE_SIGNATURES / PROBE_RESTYPES, and of ivit_views.h, under VIEWS_ABI / VIEWS_SIGNATURES / VIEWS_RESTYPES.
+PROBE_SIGNATURES / PROBE_RESTYPES, of ivit_views.h, under VIEWS_ABI / VIEWS_SIGNATURES / VIEWS_RESTYPES, and of ivit_cluster.h, under CLUSTER_ABI /
+CLUSTER_SIGNATURES / CLUSTER_RESTYPES.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -152,6 +153,16 @@ _views_signatures = _abi.signatures(VIEWS_ABI, _views_structs)
 VIEWS_RESTYPES = {name: ret for name, (ret, args) in _views_signatures.items()}
 VIEWS_SIGNATURES = {name: args for name, (ret, args) in _views_signatures.items()}
 
+# include/ivit_cluster.h, by the rule of ivit_probe.h
+CLUSTER_ABI = _abi.CLUSTER_ABI
+IVIT_CLUSTER_VERSION = CLUSTER_ABI.constants["IVIT_CLUSTER_VERSION"]
+assert set(CLUSTER_ABI.structs) == set(ABI.structs) and not set(CLUSTER_ABI.functions) & (
+    set(ABI.functions) | set(EVAL_ABI.functions) | set(FEATURES_ABI.functions) | set(ATTNMAP_ABI.functions) | set(CLASSMAP_ABI.functions)
+    | set(HIDDEN_ABI.functions) | set(SEARCH_ABI.functions) | set(MODELFILE_ABI.functions) | set(PROBE_ABI.functions) | set(VIEWS_ABI.functions))
+_cluster_signatures = _abi.signatures(CLUSTER_ABI, _structs)
+CLUSTER_RESTYPES = {name: ret for name, (ret, args) in _cluster_signatures.items()}
+CLUSTER_SIGNATURES = {name: args for name, (ret, args) in _cluster_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -160,7 +171,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -270,6 +281,14 @@ def bind_views(lib):
     return lib
 
 
+def bind_cluster(lib):
+    """the same for every prototype of include/ivit_cluster.h"""
+    for name, args in CLUSTER_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, CLUSTER_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -281,7 +300,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH)))))))))))
+    _lib = bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH))))))))))))
     return _lib
 
 

@@ -1,5 +1,6 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h) over the gfx950 kernels.
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h) over the gfx950
+// kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
 // device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
@@ -37,6 +38,7 @@
 #include "ivit_hidden.h"
 #include "ivit_search.h"
 #include "ivit_probe.h"
+#include "ivit_cluster.h"
 #include "ivit_preprocess.h"
 #include "ivit_views.h"
 
@@ -2625,6 +2627,142 @@ extern "C" int ivit_probe_accumulate(ivit_handle h, const int8_t *feat8, const i
         }
         LAUNCH_CHECK(h);
     }
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- k-means (include/ivit_cluster.h)
+// the limits the four entries share
+static int kmeans_shape_ok(ivit_handle h, const char *fn, int K, int dim) {
+    if (K < 1 || K > KMEANS_MAX_K) {
+        snprintf(h->err, sizeof(h->err), "%s: K must be in 1 .. 16384", fn);
+        return IVIT_ERR_INVALID;
+    }
+    if (dim < KMEANS_MIN_DIM || dim > KMEANS_MAX_DIM || (dim % 64) != 0) {
+        snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 64 in 64 .. 1024", fn);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    return IVIT_OK;
+}
+
+extern "C" int ivit_kmeans_norms(ivit_handle h, const int8_t *cent, int K, int dim, int32_t *cnorm) {
+    CHECK_H(h);
+    REQUIRE(h, cent && cnorm, "cent or cnorm is null");
+    if (const int rc = kmeans_shape_ok(h, __func__, K, dim)) return rc;
+    REQUIRE_A16(h, cent, "cent");
+    REQUIRE_ALIGNED(h, cnorm, "cnorm", 4);
+    REQUIRE_DISJOINT(h, cent, (size_t)K * dim, "cent", cnorm, (size_t)K * 4, "cnorm", OVL_IN);
+    kmeans_norms_kernel<<<(unsigned)((K + 15) / 16), 256, 0, h->stream>>>(cent, K, dim, cnorm);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+template <int KS>
+static void kmeans_assign_launch(ivit_handle h, unsigned grid, const KMeansAssignArgs &a) {
+    kmeans_assign_kernel<KS, (KS <= KMEANS_PF_MAX_KS)><<<grid, 256, 0, h->stream>>>(a);
+}
+
+extern "C" int ivit_kmeans_assign(ivit_handle h, const int8_t *x, int64_t rows, int dim, const int8_t *cent, const int32_t *cnorm, int K,
+                                  int32_t *assign, int32_t *dist2) {
+    CHECK_H(h);
+    REQUIRE(h, x && cent && cnorm && assign, "x, cent, cnorm or assign is null");
+    REQUIRE(h, rows >= 0, "rows is negative");
+    if (const int rc = kmeans_shape_ok(h, __func__, K, dim)) return rc;
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, cent, "cent");
+    REQUIRE_ALIGNED(h, cnorm, "cnorm", 4);
+    REQUIRE_ALIGNED(h, assign, "assign", 4);
+    REQUIRE_ALIGNED(h, dist2, "dist2", 4);
+    const long long blocks = ((long long)rows + KMEANS_RB - 1) / KMEANS_RB;
+    REQUIRE_LAUNCH(h, blocks, 256, KMEANS_RB);
+    {
+        const size_t nout = (size_t)rows * 4;
+        const struct { const void *p; size_t n; const char *name; } ins[3] = {{x, (size_t)rows * dim, "x"}, {cent, (size_t)K * dim, "cent"},
+                                                                           {cnorm, (size_t)K * 4, "cnorm"}};
+        for (const auto &i : ins) {
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, assign, nout, "assign", OVL_IN);
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, dist2, nout, "dist2", OVL_IN);
+        }
+        REQUIRE_DISJOINT(h, assign, nout, "assign", dist2, nout, "dist2", OVL_OUT);
+    }
+    if (rows == 0) return IVIT_OK;
+    KMeansAssignArgs a;
+    a.x = x; a.cent = cent; a.cnorm = cnorm; a.assign = assign; a.dist2 = dist2; a.rows = rows; a.K = K;
+    switch (dim / 64) {
+#define KMEANS_CASE(KS) case KS: kmeans_assign_launch<KS>(h, (unsigned)blocks, a); break;
+        KMEANS_CASE(1) KMEANS_CASE(2) KMEANS_CASE(3) KMEANS_CASE(4) KMEANS_CASE(5) KMEANS_CASE(6) KMEANS_CASE(7) KMEANS_CASE(8)
+        KMEANS_CASE(9) KMEANS_CASE(10) KMEANS_CASE(11) KMEANS_CASE(12) KMEANS_CASE(13) KMEANS_CASE(14) KMEANS_CASE(15) KMEANS_CASE(16)
+#undef KMEANS_CASE
+    }
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_kmeans_accumulate(ivit_handle h, const int8_t *x, const int32_t *assign, const int32_t *dist2, int64_t rows, int dim, int K,
+                                      int splits, int64_t *sum, int64_t *count, int64_t *inertia) {
+    CHECK_H(h);
+    REQUIRE(h, x && assign && sum && count, "x, assign, sum or count is null");
+    REQUIRE(h, inertia || !dist2, "inertia is null beside a dist2");
+    REQUIRE(h, rows >= 0, "rows is negative");
+    REQUIRE(h, splits >= 0 && splits <= 65535, "splits must be in 0 .. 65535");
+    if (const int rc = kmeans_shape_ok(h, __func__, K, dim)) return rc;
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_ALIGNED(h, assign, "assign", 4);
+    REQUIRE_ALIGNED(h, dist2, "dist2", 4);
+    REQUIRE_ALIGNED(h, sum, "sum", 8);
+    REQUIRE_ALIGNED(h, count, "count", 8);
+    REQUIRE_ALIGNED(h, inertia, "inertia", 8);
+    {
+        const struct { const void *p; size_t n; const char *name; } ins[3] = {{x, (size_t)rows * dim, "x"}, {assign, (size_t)rows * 4, "assign"},
+                                                                           {dist2, (size_t)rows * 4, "dist2"}},
+            outs[3] = {{sum, (size_t)K * dim * 8, "sum"}, {count, (size_t)K * 8, "count"}, {inertia, 8, "inertia"}};
+        for (const auto &i : ins)
+            for (const auto &o : outs) REQUIRE_DISJOINT(h, i.p, i.n, i.name, o.p, o.n, o.name, OVL_IN);
+        REQUIRE_DISJOINT(h, sum, outs[0].n, "sum", count, outs[1].n, "count", OVL_OUT);
+        REQUIRE_DISJOINT(h, sum, outs[0].n, "sum", inertia, 8, "inertia", OVL_OUT);
+        REQUIRE_DISJOINT(h, count, outs[1].n, "count", inertia, 8, "inertia", OVL_OUT);
+    }
+    if (rows == 0) return IVIT_OK;
+    KMeansAccArgs a;
+    a.x = x; a.assign = assign; a.dist2 = dist2;
+    a.sum = (unsigned long long *)sum; a.count = (unsigned long long *)count; a.inertia = (unsigned long long *)inertia;
+    a.rows = rows; a.dim = dim; a.K = K;
+    const long long cus = persistent_cus(h), nrows = rows;
+    // the parts: the caller's count, or the library's — privatised in LDS where [K, dim + 1] int32 fit 64 KB, about two workgroups per
+    // CU in parts of at least 256 rows (a part ends with a flush of the copy); straight global adds otherwise, 64 rows to a workgroup
+    const size_t lds = (size_t)K * (dim + 1) * 4;
+    const bool use_lds = lds <= PROBE_CLASS_LDS_BYTES;
+    const long long chosen = use_lds ? std::min(2 * cus, nrows / 256) : (nrows + 63) / 64;
+    const long long s = splits > 0 ? splits : std::max(1ll, std::min(chosen, 65535ll));
+    a.per = (nrows + s - 1) / s;
+    const unsigned parts = (unsigned)(splits > 0 ? s : (nrows + a.per - 1) / a.per);
+    if (use_lds) kmeans_accumulate_kernel<true><<<parts, 256, lds, h->stream>>>(a);
+    else kmeans_accumulate_kernel<false><<<parts, 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_kmeans_update(ivit_handle h, const int64_t *sum, const int64_t *count, int K, int dim, int8_t *cent, int32_t *cnorm,
+                                  int64_t *moved) {
+    CHECK_H(h);
+    REQUIRE(h, sum && count && cent && cnorm && moved, "sum, count, cent, cnorm or moved is null");
+    if (const int rc = kmeans_shape_ok(h, __func__, K, dim)) return rc;
+    REQUIRE_A16(h, cent, "cent");
+    REQUIRE_ALIGNED(h, cnorm, "cnorm", 4);
+    REQUIRE_ALIGNED(h, sum, "sum", 8);
+    REQUIRE_ALIGNED(h, count, "count", 8);
+    REQUIRE_ALIGNED(h, moved, "moved", 8);
+    {
+        const struct { const void *p; size_t n; const char *name; } ins[2] = {{sum, (size_t)K * dim * 8, "sum"}, {count, (size_t)K * 8, "count"}},
+            outs[3] = {{cent, (size_t)K * dim, "cent"}, {cnorm, (size_t)K * 4, "cnorm"}, {moved, 8, "moved"}};
+        for (const auto &i : ins)
+            for (const auto &o : outs) REQUIRE_DISJOINT(h, i.p, i.n, i.name, o.p, o.n, o.name, OVL_IN);
+        REQUIRE_DISJOINT(h, cent, outs[0].n, "cent", cnorm, outs[1].n, "cnorm", OVL_OUT);
+        REQUIRE_DISJOINT(h, cent, outs[0].n, "cent", moved, 8, "moved", OVL_OUT);
+        REQUIRE_DISJOINT(h, cnorm, outs[1].n, "cnorm", moved, 8, "moved", OVL_OUT);
+    }
+    kmeans_update_kernel<<<(unsigned)((K + 3) / 4), 256, 0, h->stream>>>((const long long *)sum, (const long long *)count, K, dim, cent, cnorm,
+                                                                         (unsigned long long *)moved);
+    LAUNCH_CHECK(h);
     return IVIT_OK;
 }
 

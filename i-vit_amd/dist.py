@@ -90,3 +90,18 @@ def probe_fit_sharded(engine, images, labels, batch, rank, world, num_classes, r
     if world > 1:
         stats.all_reduce()
     return fit(stats, engine.feature_scale_host(), ridge)
+
+
+def kmeans_fit_sharded(engine, images, batch, rank, world, cent0, iters=20, transform=None):
+    """exact integer k-means (ivit_amd.cluster.KMeans) over THIS rank's contiguous share (shard_range) of `images`, from the
+    centroids `cent0` int8 [K, num_features] every rank passes alike (seed them once — `cluster.init_centroids` with one generator —
+    or broadcast rank 0's): the rank embeds its images once (`predict.embed8`, the int8 features kept), and every iteration is assign
+    and accumulate over its own rows, ONE all_reduce (sum) of sum, count and inertia — exact integers: the same bits on every rank
+    as one process over all the images — and the same update everywhere.  Returns (kmeans, feat8 of this rank, inertia_history)."""
+    from .cluster import KMeans
+    from .predict import embed8
+    lo, hi = shard_range(len(images), rank, world)
+    feat8, _ = embed8(engine, (images[a:min(a + batch, hi)] for a in range(lo, hi, batch)), transform)
+    km = KMeans(cent0.shape[0], engine.num_features, engine.device).set_centroids(cent0)
+    km.world = world
+    return km, feat8, km.fit(feat8, iters=iters)

@@ -399,6 +399,17 @@ class NativeEngine:
         out = (idx, val, feat8)
         return tuple(t.clone() for t in out) if copy else out
 
+    def cluster_assign(self, images, kmeans, nslices=1, copy=False):
+        """images int8 [B, C, H, W], kmeans an `ivit_amd.cluster.KMeans` over this backbone's features -> (assign int32 [B], dist2
+        int32 [B], feat8 int8 [B, num_features]) device tensors: `features` without the head, then `kmeans.assign(feat8)` on the
+        same stream (include/ivit_cluster.h) — every image's nearest centroid and its exact squared distance as
+        `predict.kmeans_assign_reference` states them.  assign / dist2 are the KMeans' buffers for this B, feat8 the engine's:
+        copy=True (or clone) to keep them."""
+        feat8 = self.features(images, nslices=nslices)[0]
+        assign, dist2 = kmeans.assign(feat8)
+        out = (assign, dist2, feat8)
+        return tuple(t.clone() for t in out) if copy else out
+
     # ---- views (include/ivit_views.h, ivit_amd/views.py): the mean logits of the V views of every image
     def _make_view_buffers(self, G, k):
         ncls = self.cfg.num_classes

@@ -544,3 +544,88 @@ def probe_fit(engine, batches, num_classes, ridge=1e-3, transform=None, stats=No
         labels = torch.as_tensor(labels).to(device=engine.device, dtype=torch.int64, non_blocking=True).reshape(-1)
         engine.probe_accumulate(images, labels, stats)
     return fit(stats, engine.feature_scale_host(), ridge)
+
+
+# ---------------------------------------------------------------- k-means (include/ivit_cluster.h, ivit_amd/cluster.py)
+KMEANS_MAX_K = 16384   # KMEANS_MAX_K of csrc/ivit_cluster.h
+
+
+def kmeans_norms_reference(cent8):
+    """cent8 int8 [K, dim] -> int32 [K]: cnorm[j] = sum_c cent[j, c]^2, exact (at most 2^24 for dim <= 1024)"""
+    c = np.asarray(cent8)
+    assert c.ndim == 2 and c.dtype == np.int8
+    return (c.astype(np.int32) ** 2).sum(axis=1).astype(np.int32)
+
+
+def kmeans_assign_reference(x8, cent8):
+    """x8 int8 [rows, dim], cent8 int8 [K, dim] -> (assign int32 [rows], dist2 int32 [rows]), what `ivit_kmeans_assign` writes.
+    s[r, j] = 2 dot[r, j] - cnorm[j] with dot the exact int32 product (|s| <= 2^26); assign[r] is the SMALLEST j that maximises
+    s[r, j] (np.argmax returns the first): the nearest centroid in squared Euclidean distance, ties to the lower index;
+    dist2[r] = sum_c x[r, c]^2 - s[r, assign[r]], the exact squared distance."""
+    x, c = np.asarray(x8), np.asarray(cent8)
+    assert x.ndim == 2 and c.ndim == 2 and x.dtype == np.int8 and c.dtype == np.int8 and x.shape[1] == c.shape[1] and c.shape[0] >= 1
+    cn = kmeans_norms_reference(c)
+    xx = (x.astype(np.int32) ** 2).sum(axis=1)
+    assign, dist2 = np.zeros(x.shape[0], np.int32), np.zeros(x.shape[0], np.int32)
+    c32 = c.astype(np.int32).T
+    for a in range(0, x.shape[0], 4096):                               # pieces: the [rows, K] matrix is never whole
+        s = 2 * (x[a:a + 4096].astype(np.int32) @ c32) - cn[None, :]
+        j = np.argmax(s, axis=1)
+        assign[a:a + 4096] = j
+        dist2[a:a + 4096] = xx[a:a + 4096] - s[np.arange(len(j)), j]
+    return assign, dist2
+
+
+def kmeans_stats_reference(x8, assign, dist2, K):
+    """x8 int8 [rows, dim], assign integers [rows], dist2 integers [rows] or None -> (sum int64 [K, dim], count int64 [K], inertia
+    int64 scalar): what `ivit_kmeans_accumulate` ADDS into its buffers.  Row r takes part iff 0 <= assign[r] < K; with dist2 None
+    the inertia is 0 (the entry leaves its buffer untouched)."""
+    x, a = np.asarray(x8), np.asarray(assign).astype(np.int64).reshape(-1)
+    assert x.ndim == 2 and x.dtype == np.int8 and a.shape == (x.shape[0],)
+    K = int(K)
+    keep = (a >= 0) & (a < K)
+    total = np.zeros((K, x.shape[1]), np.int64)
+    np.add.at(total, a[keep], x[keep].astype(np.int64))
+    count = np.bincount(a[keep], minlength=K).astype(np.int64)
+    inertia = np.int64(0) if dist2 is None else np.asarray(dist2).astype(np.int64).reshape(-1)[keep].sum(dtype=np.int64)
+    return total, count, inertia
+
+
+def kmeans_update_reference(total, count, cent8):
+    """sum int64 [K, dim], count int64 [K], cent8 int8 [K, dim] -> (cent' int8 [K, dim], cnorm' int32 [K], moved): what
+    `ivit_kmeans_update` leaves.  For every j with count[j] > 0: cent'[j, c] = (2 sum[j, c] + count[j]) // (2 count[j]) — floor
+    division: the mean rounded half up, always in -128 .. 127 for sums of int8 rows; an empty cluster keeps its centroid.  moved is the
+    number of centroids of which any byte changed."""
+    total, count, c = np.asarray(total).astype(np.int64), np.asarray(count).astype(np.int64), np.asarray(cent8)
+    assert c.dtype == np.int8 and total.shape == c.shape and count.shape == (c.shape[0],)
+    live = count > 0
+    n = np.where(live, count, 1)[:, None]
+    new = np.where(live[:, None], (2 * total + n) // (2 * n), c.astype(np.int64))
+    assert new.min(initial=0) >= -128 and new.max(initial=0) <= 127, "a mean outside int8: the sums are no sums of int8 rows"
+    new = new.astype(np.int8)
+    return new, kmeans_norms_reference(new), int((new != c).any(axis=1).sum())
+
+
+def kmeans_reference(x8, cent0, iters):
+    """`iters` Lloyd iterations from cent0 -> (cent int8 [K, dim], assign int32 [rows], inertia [iters] int64): every iteration is
+    assign (against the centroids it starts with), stats, update; `assign` and inertia[i] are those of iteration i's assignment,
+    the centroids those after the last update.  Rounding the mean to int8 means the inertia need not fall monotonically."""
+    cent = np.asarray(cent0).copy()
+    assign, history = np.zeros(np.asarray(x8).shape[0], np.int32), []
+    for _ in range(int(iters)):
+        assign, dist2 = kmeans_assign_reference(x8, cent)
+        total, count, inertia = kmeans_stats_reference(x8, assign, dist2, cent.shape[0])
+        cent, _, _ = kmeans_update_reference(total, count, cent)
+        history.append(int(inertia))
+    return cent, assign, np.asarray(history, np.int64)
+
+
+def kmeans_fit(engine, batches, K, iters=20, init="kmeans++", generator=None, transform=None):
+    """`embed8` followed by `cluster.KMeans.fit`: the int8 features of the whole dataset are kept on the device (rows x num_features
+    bytes), the centroids seeded on the host by `init` ("sample" or "kmeans++") with `generator` (default: np.random.default_rng(0)),
+    then `iters` Lloyd iterations of three launches each.  Returns (kmeans, feat8, inertia_history)."""
+    from .cluster import KMeans
+    feat8, _ = embed8(engine, batches, transform)
+    km = KMeans(int(K), int(engine.num_features), feat8.device)
+    km.init(feat8, method=init, generator=generator)
+    return km, feat8, km.fit(feat8, iters=iters)
