@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -39,6 +39,7 @@
 #include "ivit_search.h"
 #include "ivit_probe.h"
 #include "ivit_cluster.h"
+#include "ivit_range.h"
 #include "ivit_preprocess.h"
 #include "ivit_views.h"
 
@@ -2762,6 +2763,158 @@ extern "C" int ivit_kmeans_update(ivit_handle h, const int64_t *sum, const int64
     }
     kmeans_update_kernel<<<(unsigned)((K + 3) / 4), 256, 0, h->stream>>>((const long long *)sum, (const long long *)count, K, dim, cent, cnorm,
                                                                          (unsigned long long *)moved);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- range search (include/ivit_range.h)
+// the workspace: the nq * parts int32 counts, their int64 offsets (8-byte aligned behind the counts) and the scan's block sums
+struct RangeLayout {
+    long long n, nb;            // counts; blocks of RANGE_SCAN_BLOCK counts
+    size_t off, bsum, bytes;    // byte offsets of the offsets and the block sums; the whole
+};
+static RangeLayout range_layout(int nq, int parts) {
+    RangeLayout l;
+    l.n = (long long)nq * parts;
+    l.nb = (l.n + RANGE_SCAN_BLOCK - 1) / RANGE_SCAN_BLOCK;
+    l.off = ((size_t)l.n * 4 + 7) & ~(size_t)7;
+    l.bsum = l.off + (size_t)l.n * 8;
+    l.bytes = l.bsum + (size_t)l.nb * 8;
+    return l;
+}
+
+// the limits the three entries share, and the number of parts: the caller's, or that of the search (about two workgroups per CU of the
+// handle's share, in parts of at least 1024 rows)
+static int range_shape_ok(ivit_handle h, const char *fn, int nq, long long rows, int dim, int splits, int *parts) {
+    const char *bad = nullptr;
+    if (nq < 0) bad = "nq is negative";
+    else if (rows < 1) bad = "rows must be at least 1";
+    else if (splits < 0 || splits > 65535) bad = "splits must be in 0 .. 65535";
+    if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    if (dim < SEARCH_MIN_DIM || dim > SEARCH_MAX_DIM || (dim % 64) != 0) {
+        snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 64 in 64 .. 1024", fn);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    long long s = splits;
+    if (s == 0) {
+        const long long cols = std::max(1ll, ((long long)nq + SEARCH_QB - 1) / SEARCH_QB);
+        s = std::max(1ll, std::min((2ll * persistent_cus(h) + cols - 1) / cols, rows / 1024));
+    }
+    if ((long long)nq * s > 0x7fffffffLL) {
+        snprintf(h->err, sizeof(h->err), "%s: nq * parts must be at most 2^31 - 1", fn);
+        return IVIT_ERR_INVALID;
+    }
+    *parts = (int)s;
+    return IVIT_OK;
+}
+
+extern "C" int ivit_range_workspace_bytes(ivit_handle h, int nq, int64_t rows, int dim, int splits, size_t *bytes) {
+    CHECK_H(h);
+    REQUIRE(h, bytes, "bytes is null");
+    int parts = 0;
+    if (const int rc = range_shape_ok(h, __func__, nq, rows, dim, splits, &parts)) return rc;
+    *bytes = range_layout(nq, parts).bytes;
+    return IVIT_OK;
+}
+
+// what ivit_range_count and ivit_range_fill check alike, in the same order, and the kernel's arguments
+static int range_args_ok(ivit_handle h, const char *fn, const int8_t *query, int nq, const int8_t *gallery, long long rows, int dim, const float *weight,
+                         const float *qweight, float threshold, int index_base, int query_base, int triangle, int splits, void *workspace, size_t bytes,
+                         RangeArgs *a, RangeLayout *l) {
+    int parts = 0;
+    if (const int rc = range_shape_ok(h, fn, nq, rows, dim, splits, &parts)) return rc;
+    const char *bad = nullptr;
+    if (index_base < 0 || (long long)index_base + rows > 0x7fffffffLL) bad = "index_base must be >= 0 and index_base + rows <= 2^31 - 1";
+    else if (query_base < 0 || (long long)query_base + nq > 0x7fffffffLL) bad = "query_base must be >= 0 and query_base + nq <= 2^31 - 1";
+    else if (!(threshold >= -FLT_MAX && threshold <= FLT_MAX)) bad = "threshold must be finite";
+    *l = range_layout(nq, parts);
+    if (!bad && bytes < l->bytes) bad = "workspace too small (ivit_range_workspace_bytes)";
+    if (!bad && ((uintptr_t)query & 15)) bad = "query must be 16-byte aligned";
+    if (!bad && ((uintptr_t)gallery & 15)) bad = "gallery must be 16-byte aligned";
+    if (!bad && ((uintptr_t)workspace & 7)) bad = "workspace must be 8-byte aligned";
+    if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    a->query = query; a->gallery = gallery; a->weight = weight; a->qweight = qweight;
+    a->cnt = (int *)workspace; a->off = (const long long *)((char *)workspace + l->off);
+    a->idx = nullptr; a->val = nullptr;
+    a->rows = rows; a->per = (rows + parts - 1) / parts; a->capacity = 0;
+    a->threshold = threshold;
+    a->nq = nq; a->index_base = index_base; a->query_base = query_base; a->triangle = triangle != 0; a->parts = parts;
+    return IVIT_OK;
+}
+
+template <int KS, bool FILL>
+static void range_scan_launch(ivit_handle h, dim3 grid, const RangeArgs &a) {
+    range_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS), FILL><<<grid, 256, 0, h->stream>>>(a);
+}
+
+template <bool FILL>
+static void range_scan_dispatch(ivit_handle h, int dim, const RangeArgs &a) {
+    const dim3 grid((unsigned)(((long long)a.nq + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
+    switch (dim / 64) {
+#define RANGE_CASE(KS) case KS: range_scan_launch<KS, FILL>(h, grid, a); break;
+        RANGE_CASE(1) RANGE_CASE(2) RANGE_CASE(3) RANGE_CASE(4) RANGE_CASE(5) RANGE_CASE(6) RANGE_CASE(7) RANGE_CASE(8)
+        RANGE_CASE(9) RANGE_CASE(10) RANGE_CASE(11) RANGE_CASE(12) RANGE_CASE(13) RANGE_CASE(14) RANGE_CASE(15) RANGE_CASE(16)
+#undef RANGE_CASE
+    }
+}
+
+extern "C" int ivit_range_count(ivit_handle h, const int8_t *query, int nq, const int8_t *gallery, int64_t rows, int dim, const float *weight,
+                                const float *qweight, float threshold, int32_t index_base, int32_t query_base, int triangle, int splits,
+                                void *workspace, size_t bytes, int64_t *row_ptr) {
+    CHECK_H(h);
+    REQUIRE(h, query && gallery && workspace && row_ptr, "query, gallery, workspace or row_ptr is null");
+    RangeArgs a;
+    RangeLayout l;
+    if (const int rc = range_args_ok(h, __func__, query, nq, gallery, rows, dim, weight, qweight, threshold, index_base, query_base, triangle, splits,
+                                     workspace, bytes, &a, &l)) return rc;
+    REQUIRE_ALIGNED(h, row_ptr, "row_ptr", 8);
+    {
+        const size_t nrp = ((size_t)nq + 1) * 8;
+        const struct { const void *p; size_t n; const char *name; } ins[4] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"},
+                                                                           {weight, (size_t)rows * 4, "weight"}, {qweight, (size_t)nq * 4, "qweight"}};
+        for (const auto &i : ins) {
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, workspace, bytes, "workspace", OVL_IN);
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, row_ptr, nrp, "row_ptr", OVL_IN);
+        }
+        REQUIRE_DISJOINT(h, workspace, bytes, "workspace", row_ptr, nrp, "row_ptr", OVL_OUT);
+    }
+    if (nq == 0) return IVIT_OK;
+    range_scan_dispatch<false>(h, dim, a);
+    LAUNCH_CHECK(h);
+    long long *off = (long long *)((char *)workspace + l.off), *bsum = (long long *)((char *)workspace + l.bsum);
+    range_block_sums_kernel<<<(unsigned)l.nb, 256, 0, h->stream>>>(a.cnt, l.n, bsum);
+    LAUNCH_CHECK(h);
+    range_scan_sums_kernel<<<1, 256, 0, h->stream>>>(bsum, l.nb, (long long *)row_ptr + nq);
+    LAUNCH_CHECK(h);
+    range_offsets_kernel<<<(unsigned)l.nb, 256, 0, h->stream>>>(a.cnt, bsum, l.n, a.parts, off, (long long *)row_ptr);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_range_fill(ivit_handle h, const int8_t *query, int nq, const int8_t *gallery, int64_t rows, int dim, const float *weight,
+                               const float *qweight, float threshold, int32_t index_base, int32_t query_base, int triangle, int splits,
+                               void *workspace, size_t bytes, int64_t capacity, int32_t *idx, float *val) {
+    CHECK_H(h);
+    REQUIRE(h, query && gallery && workspace && idx, "query, gallery, workspace or idx is null");
+    REQUIRE(h, capacity >= 0, "capacity is negative");
+    RangeArgs a;
+    RangeLayout l;
+    if (const int rc = range_args_ok(h, __func__, query, nq, gallery, rows, dim, weight, qweight, threshold, index_base, query_base, triangle, splits,
+                                     workspace, bytes, &a, &l)) return rc;
+    {
+        const size_t nout = (size_t)capacity * 4;
+        const struct { const void *p; size_t n; const char *name; } ins[5] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"},
+                                                                           {weight, (size_t)rows * 4, "weight"}, {qweight, (size_t)nq * 4, "qweight"},
+                                                                           {workspace, bytes, "workspace"}};
+        for (const auto &i : ins) {
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, idx, nout, "idx", OVL_IN);
+            REQUIRE_DISJOINT(h, i.p, i.n, i.name, val, nout, "val", OVL_IN);
+        }
+        REQUIRE_DISJOINT(h, idx, nout, "idx", val, nout, "val", OVL_OUT);
+    }
+    if (nq == 0 || capacity == 0) return IVIT_OK;
+    a.idx = idx; a.val = val; a.capacity = capacity;
+    range_scan_dispatch<true>(h, dim, a);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

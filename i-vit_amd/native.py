@@ -399,6 +399,16 @@ class NativeEngine:
         out = (idx, val, feat8)
         return tuple(t.clone() for t in out) if copy else out
 
+    def retrieve_within(self, images, gallery, threshold, nslices=1):
+        """images int8 [B, C, H, W], gallery an `ivit_amd.search.Gallery` of this backbone's features -> (row_ptr int64 [B + 1], idx
+        int32 [total], val float32 [total], feat8 int8 [B, num_features]) device tensors: `features` without the head, then
+        `gallery.within(feat8, threshold)` on the same stream (include/ivit_range.h) — every gallery row whose score against an
+        image is >= threshold (the cosine for a cosine gallery), by ascending row, as `predict.range_reference` states them.
+        `within` synchronises once, to size the result; row_ptr / idx / val are fresh tensors, feat8 the engine's buffer."""
+        feat8 = self.features(images, nslices=nslices)[0]
+        row_ptr, idx, val = gallery.within(feat8, threshold)
+        return row_ptr, idx, val, feat8
+
     def cluster_assign(self, images, kmeans, nslices=1, copy=False):
         """images int8 [B, C, H, W], kmeans an `ivit_amd.cluster.KMeans` over this backbone's features -> (assign int32 [B], dist2
         int32 [B], feat8 int8 [B, num_features]) device tensors: `features` without the head, then `kmeans.assign(feat8)` on the

@@ -326,6 +326,43 @@ def search_reference(query8, gallery8, weight, k, index_base=0):
     return (idx + index_base).astype(np.int32), val
 
 
+def range_reference(query8, gallery8, weight, qweight, threshold, index_base=0, query_base=0, triangle=False):
+    """query8 int8 [nq, dim], gallery8 int8 [rows, dim], weight float32 [rows] or None, qweight float32 [nq] or None -> (row_ptr int64
+    [nq + 1], idx int32 [total], val float32 [total]): the numpy statement of include/ivit_range.h.
+
+    dot[b, g] = query8[b] . gallery8[g] as an exact integer; v[b, g] = fl32(fl32(fl32(dot) * weight[g]) * qweight[b]), two float32
+    multiplies in this order, a None weight / qweight that multiply left out.  (b, g) is a hit if v[b, g] >= threshold (the IEEE
+    comparison: -0.0 >= +0.0 holds) and, with triangle, index_base + g > query_base + b.  Row b of the result holds the hits of query
+    b by ascending g: idx = index_base + g, val the bits of v; row b is idx[row_ptr[b]:row_ptr[b + 1]].  threshold must be finite;
+    the bases >= 0 with index_base + rows <= 2^31 - 1 and query_base + nq <= 2^31 - 1.  With qweight None, v is `search_reference`'s
+    value: a row is that search's entries at k = rows with a value >= threshold, by index."""
+    q, g = np.asarray(query8), np.asarray(gallery8)
+    assert q.ndim == 2 and g.ndim == 2 and q.dtype == np.int8 and g.dtype == np.int8 and q.shape[1] == g.shape[1]
+    nq, rows = q.shape[0], g.shape[0]
+    threshold = np.float32(threshold)
+    if not np.isfinite(threshold):
+        raise ValueError("threshold must be finite")
+    if index_base < 0 or index_base + rows > 2 ** 31 - 1 or query_base < 0 or query_base + nq > 2 ** 31 - 1:
+        raise ValueError("index_base, query_base: >= 0, index_base + rows <= 2^31 - 1 and query_base + nq <= 2^31 - 1")
+    v = (q.astype(np.int32) @ g.astype(np.int32).T).astype(np.float32)
+    if weight is not None:
+        weight = np.asarray(weight, dtype=np.float32)
+        assert weight.shape == (rows,)
+        v = v * weight[None, :]                                       # one float32 multiply
+    if qweight is not None:
+        qweight = np.asarray(qweight, dtype=np.float32)
+        assert qweight.shape == (nq,)
+        v = v * qweight[:, None]                                      # and the second
+    assert v.dtype == np.float32
+    hit = v >= threshold
+    if triangle:
+        hit &= (index_base + np.arange(rows, dtype=np.int64))[None, :] > (query_base + np.arange(nq, dtype=np.int64))[:, None]
+    row_ptr = np.zeros(nq + 1, np.int64)
+    np.cumsum(hit.sum(axis=1), out=row_ptr[1:])
+    b, c = np.nonzero(hit)                                            # row-major: by query, then by ascending g
+    return row_ptr, (c + index_base).astype(np.int32), v[b, c]
+
+
 def _images_of(item, transform):
     images = item[0] if isinstance(item, (tuple, list)) else item
     return images if transform is None else transform(images)
@@ -629,3 +666,12 @@ def kmeans_fit(engine, batches, K, iters=20, init="kmeans++", generator=None, tr
     km = KMeans(int(K), int(engine.num_features), feat8.device)
     km.init(feat8, method=init, generator=generator)
     return km, feat8, km.fit(feat8, iters=iters)
+
+
+def find_duplicates(engine, batches, threshold, transform=None):
+    """`embed8`'s loop followed by `search.duplicates`: every pair i < j of the images `batches` yields whose cosine, as
+    `range_reference` states it on the int8 features, is >= threshold.  Returns (pairs int64 [P, 2], val float32 [P], feat8)."""
+    from .search import duplicates
+    feat8, _ = embed8(engine, batches, transform)
+    pairs, val = duplicates(feat8, threshold, cosine=True)
+    return pairs, val, feat8
