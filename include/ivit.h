@@ -169,6 +169,8 @@ typedef struct ivit_image_desc {
  * both resized sides — and on a failed check returns IVIT_ERR_INVALID with the image's index in ivit_last_error, nothing
  * launched.  The kernel reads ONLY the device copy: a replay of a captured graph reads the device table again, so whatever it
  * holds then must describe images for which the captured call's checks hold (inside pixels_bytes, crop inside the resized image).
+ * The host descriptor table is read at call time by design: a captured call keeps the launch shape it took from it, and a replay
+ * may bring other pixel bytes under the same descriptors.
  * Every image that ivit_resize_center_crop_u8 accepts is accepted.  No workspace.  pixels, the offsets and the output take any
  * address (byte accesses only).
  * Overlap: out_hwc may not overlap pixels (all pixels_bytes of it) or desc_dev: IVIT_ERR_INVALID, nothing launched. */

@@ -54,7 +54,9 @@ typedef struct ivit_view_desc {
  * image (x0, y0 >= 0; x0 + bw <= w; y0 + bh <= h); 1 <= rw, rh <= 65536; the window inside the resized box (left, top >= 0; left +
  * crop <= rw; top + crop <= rh); flip 0 or 1 — and on a failed check returns IVIT_ERR_INVALID with the image's or the view's index
  * in ivit_last_error ("view 3: ..."), nothing launched.  The kernel reads ONLY the device tables: a replay of a captured graph reads
- * them again, so whatever they hold then must describe images and views for which the captured call's checks hold.  B >= 1, crop >=
+ * them again, so whatever they hold then must describe images and views for which the captured call's checks hold.  The host
+ * descriptor tables are read at call time by design: a captured call keeps the launch shape it took from them, and a replay may
+ * bring other pixel bytes under the same descriptors.  B >= 1, crop >=
  * 1, V >= 0; with V == 0 nothing is launched (view_host and view_dev may then be NULL).  ceil(crop / 32) * V blocks of 512 threads
  * must stay below 2^32 work-items: IVIT_ERR_INVALID otherwise.  No workspace.
  * Alignment: none: pixels, the offsets and out_hwc take any address (byte accesses only), the tables are aligned as their structs.

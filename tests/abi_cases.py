@@ -9,7 +9,9 @@ or ("in" | "out", array[, pad]).  `pad` describes bytes inside the array that ar
     ("free", mask)     an output of which only mask's bytes are pinned (the others may or may not be written).
 `ALIGN` records, per entry and activation argument, what happens when that one pointer is element-aligned but not 16-byte aligned.
 `INPLACE` records the (input, output) pairs an entry accepts at the same address; every other overlap of an output with an activation
-input or another output is refused (`check_overlap`).
+input or another output is refused (`check_overlap`).  `twin_table`, `hip_table` and `cases_of` are the tables as the contract tests
+read them, built once per seed; `check_stream_contract` runs one case on a side stream inside a hipGraph capture and replays it
+(tests/test_stream_graph_contract_gpu.py).
 
 The second half is the arena harness: every array in its own [guard | payload | guard] allocation, on numpy or on the device."""
 import ctypes
@@ -182,7 +184,8 @@ def _cases(rng, variant=0):
     return cs
 
 
-def _run(fn, handle, args, to_ptr, refs=None, status=0):
+def _marshal(handle, args, to_ptr, refs=None):
+    """-> (the C argument list of the call, what to_ptr returned beside the pointer for every ("out", ...) argument)"""
     outs, call = [], [handle]
     for a in args:
         if isinstance(a, tuple) and a[0] == "host":          # a HOST array on both sides (mean / std of the normalisation)
@@ -196,6 +199,11 @@ def _run(fn, handle, args, to_ptr, refs=None, status=0):
                 outs.append(buf[1])
         else:
             call.append(a)
+    return call, outs
+
+
+def _run(fn, handle, args, to_ptr, refs=None, status=0):
+    call, outs = _marshal(handle, args, to_ptr, refs)
     st = fn(*call)
     assert st == status, st
     return outs
@@ -223,6 +231,24 @@ def _x16(rng, M, C):
     if M >= 3:
         x[1] = 1234                                       # a zero-variance row
     return x
+
+
+LN_LDS_SCALE = 7.3e-4
+
+
+@functools.lru_cache(maxsize=None)
+def ln_lds_case(C):
+    """Eight rows of C channels (row 3 constant: zero variance), the LayerNorm constants and the oracle's fp32 result at the input
+    scale LN_LDS_SCALE; computed once per C and left unchanged.  ivit_layernorm asks for 8 * C * 4 bytes of dynamic LDS: above 64 KB
+    from C = 2056 on (tests/test_gpu_parity.py, tests/test_stream_graph_contract_gpu.py)."""
+    from oracle import oracle as orc
+    rng = np.random.default_rng(C)
+    w = rng.normal(1.0, 0.4, C).astype(np.float32) * rng.choice([-1.0, 1.0], C).astype(np.float32)
+    bias_int, sc = iv.freeze.layernorm_constants(w, rng.normal(0.0, 0.5, C).astype(np.float32))
+    x = rng.integers(-26000, 26000, (8, C)).astype(np.int16)
+    x[:, : C // 2] //= 64                                         # small and large magnitudes in one row
+    x[3] = 1234
+    return x, bias_int, sc, orc.layernorm(x, LN_LDS_SCALE, bias_int, sc)
 
 
 S_GELU, S_G_OUT = np.float32(0.03), np.float32(0.02)
@@ -495,6 +521,67 @@ def uncovered_entry_points():
     return sorted(every - twinned - hip - set(EXCLUDED)), sorted((set(EXCLUDED) - every) | (set(EXCLUDED) & (twinned | hip)))
 
 
+# ---------------------------------------------------------------- the tables as the contract tests read them: built once, left unchanged
+TWIN_SEED, HIP_SEED = 77, 99    # the seeds of the tables every contract test runs
+SECOND_SEED = 1234              # a second table of the same cases with other array contents (check_stream_contract, step 5)
+
+
+@functools.lru_cache(maxsize=None)
+def twin_table(variant, seed=TWIN_SEED):
+    """_cases of one variant, built once per (variant, seed) and left unchanged (the arenas copy from it)"""
+    return _cases(np.random.default_rng(seed + variant), variant)
+
+
+@functools.lru_cache(maxsize=None)
+def hip_table(H, seed=HIP_SEED):
+    """the device table, built once per (handle, seed) (None: names and arguments only) and left unchanged"""
+    return hip_cases(H, np.random.default_rng(seed))
+
+
+def cases_of(H, name, second=False):
+    """(label, args, setup, twinned) of every case of entry `name` in both tables; second: the tables built from SECOND_SEED — the
+    same cases in the same order with other array contents (tests/test_memory_contract_cpu.py::
+    test_tables_from_two_seeds_agree_in_everything_but_contents)"""
+    out = []
+    for variant in (0, 1):
+        out += [(f"twinned table, variant {variant}, case {i}", args, None, True)
+                for i, (n, args) in enumerate(twin_table(variant, SECOND_SEED if second else TWIN_SEED)) if n == name]
+    # a device-table case of a twinned entry goes through the twin as well, unless it sits behind a plan (another handle protocol)
+    twinned = name in gen_twin_header.TWIN and name not in NO_TWIN_FORM
+    out += [(f"device table, case {i}", args, setup, twinned and (setup is None or not setup.plans))
+            for i, (n, args, setup) in enumerate(hip_table(H, SECOND_SEED if second else HIP_SEED)) if n == name]
+    return out
+
+
+def table_differences(a, b):
+    """what two argument lists of one case differ in BESIDE the contents of their ("in", ...) arrays -> (list of differences, positions
+    of the input arrays whose contents differ, positions of those whose contents are equal)"""
+    diffs, changed, same = [], [], []
+    if len(a) != len(b):
+        return [("length", len(a), len(b))], changed, same
+    for i, (x, y) in enumerate(zip(a, b)):
+        if isinstance(x, tuple) != isinstance(y, tuple) or (isinstance(x, tuple) and x[0] != y[0]):
+            diffs.append((i, "kind"))
+        elif not isinstance(x, tuple):
+            eq = bytes(x) == bytes(y) if isinstance(x, ctypes.Structure) and type(x) is type(y) else type(x) is type(y) and x == y
+            if not eq:
+                diffs.append((i, "scalar", x, y))
+        elif x[0] in ("ref", "host"):
+            if not (np.array_equal(x[1], y[1]) if x[0] == "host" else x[1] == y[1]):
+                diffs.append((i, x[0]))
+        else:
+            if x[1].shape != y[1].shape or x[1].dtype != y[1].dtype or len(x) != len(y):
+                diffs.append((i, "shape, dtype or pad", x[1].shape, y[1].shape))
+                continue
+            if len(x) > 2:
+                p, q = x[2], y[2]
+                if isinstance(p, tuple) != isinstance(q, tuple) or not (p[0] == q[0] and np.array_equal(p[1], q[1]) if isinstance(p, tuple) else p == q):
+                    diffs.append((i, "pad"))
+            if x[0] == "in":
+                (same if np.array_equal(x[1], y[1]) else changed).append(i)
+    return diffs, changed, same
+
+
 # ---------------------------------------------------------------- arenas: [guard | payload | guard] around every array
 GUARD = 1 << 20         # bytes on either side of a payload.  A condition, not a measurement: see _fits
 TILE_ROWS = 256         # the tallest row tile of any kernel in the library (gemm_as_kernel's 256-row units)
@@ -666,6 +753,117 @@ def plain_outputs(fn, handle, args, mem, refs=None):
     outs = _run(fn, handle, args, to_ptr, refs)
     mem.sync()
     return [np.where(m, mem.get(o), 0).astype(np.uint8) for m, o in zip(masks, outs)]
+
+
+# ---------------------------------------------------------------- the handle's stream, and a caller's graph
+def check_stream_contract(fn, H, args, args2, mem, refs=None, what="", eager_first=True):
+    """include/ivit.h, Conventions: every call is asynchronous on the handle's HIP stream, allocates nothing, synchronises nothing and
+    is hipGraph-capturable.  One case on plain allocations of the exact size; `args2` is the same argument list with other contents
+    in its ("in", ...) arrays; H a _lib.Handle on the current stream.  Every buffer exists before the capture begins, and between
+    its begin and its end nothing is allocated and torch is not called.
+      1. want1: the eager call on the current stream;
+      2. the handle moves to a side stream, the outputs are filled 0x5A, the call is captured there in relaxed mode: IVIT_OK, a graph;
+      3. the device is synchronised: every output byte still holds 0x5A (a launch on any stream but the handle's has run by then),
+         and the graph holds at least one node;
+      4. the graph, instantiated and launched on the side stream, gives want1;
+      5. the inputs are overwritten with args2's, the outputs filled 0xA5: the SAME executable graph gives want2, the eager call on
+         args2 (a decision taken on the host at call time would be baked into the graph), and the same bytes when launched again.
+    eager_first=False leaves step 1 out and takes want1 from an eager call AFTER the first replay: the captured call is then the
+    first one the entry sees (tests/first_call_child.py).
+    -> (want1, want2), payload bytes in plain_outputs' form.  Raises ContractError with a message per failure mode."""
+    import torch
+    import hip_runtime
+    rt = hip_runtime.bind(H.lib)
+    want1 = plain_outputs(fn, H.h, args, mem, refs) if eager_first else None
+    ins, outs = [], []
+    masks = [_valid_mask(a[1], a[2] if len(a) > 2 else None)[0] for a in args if _is_array(a) and a[0] == "out"]
+
+    def to_ptr(a, is_out):
+        buf, base = mem.alloc(max(a.nbytes, 1))
+        if is_out:
+            outs.append((buf, max(a.nbytes, 1)))
+        else:
+            mem.put(buf, np.ascontiguousarray(a).view(np.uint8).reshape(-1))
+            ins.append(buf)
+        return _P(base), None
+    call, _ = _marshal(H.h, args, to_ptr, refs)
+
+    def fill(byte):
+        for o, n in outs:
+            mem.put(o, np.full(n, byte, np.uint8))
+        mem.sync()
+
+    def read():
+        mem.sync()
+        return [mem.get(o) for o, _ in outs]
+
+    def payload(raw):
+        return [np.where(m, r[:m.size], 0).astype(np.uint8) for m, r in zip(masks, raw)]
+
+    def differ(got, want):
+        return sum(int((g != w).sum()) for g, w in zip(got, want))
+    side = torch.cuda.Stream()
+    S, graph, gexec = _P(side.cuda_stream), _P(), _P()
+    fill(0x5A)
+    capturing = False
+    try:
+        try:
+            H.set_stream(side.cuda_stream)
+            begun = rt.hipStreamBeginCapture(S, hip_runtime.RELAXED)
+            assert begun == 0, f"hipStreamBeginCapture: hipError {begun}"
+            capturing = True
+            st = fn(*call)
+            capturing = False
+            ended = rt.hipStreamEndCapture(S, ctypes.byref(graph))
+        finally:
+            if capturing:                             # the entry raised: leave no stream capturing
+                rt.hipStreamEndCapture(S, ctypes.byref(graph))
+            H.set_stream(torch.cuda.current_stream().cuda_stream)
+        if st != 0:
+            raise ContractError(f"{what}: status {st} inside a capture: {H.lib.ivit_last_error(H.h).decode()}")
+        if ended != 0 or not graph.value:
+            raise ContractError(f"{what}: the capture ended with hipError {ended} and {'a' if graph.value else 'no'} graph")
+        for j, raw in enumerate(read()):
+            n = int((raw != 0x5A).sum())
+            if n:
+                raise ContractError(f"{what}: {n} bytes of output {j} written before the graph was launched")
+        if rt.node_count(graph) < 1:
+            raise ContractError(f"{what}: launched nothing into the capture")
+        err = rt.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0)
+        assert err == 0 and gexec.value, f"hipGraphInstantiate: hipError {err}"
+
+        def replay():
+            err = rt.hipGraphLaunch(gexec, S)
+            assert err == 0, f"hipGraphLaunch: hipError {err}"
+            return payload(read())
+        got = replay()
+        if want1 is None:
+            want1 = plain_outputs(fn, H.h, args, mem, refs)
+        if differ(got, want1):
+            raise ContractError(f"{what}: first replay differs from the eager call in {differ(got, want1)} bytes")
+        k = 0
+        for a in args2:
+            if _is_array(a) and a[0] == "in":
+                mem.put(ins[k], np.ascontiguousarray(a[1]).view(np.uint8).reshape(-1))
+                k += 1
+        assert k == len(ins)
+        want2 = plain_outputs(fn, H.h, args2, mem, refs)
+        fill(0xA5)
+        got = replay()
+        if differ(got, want2):
+            if not differ(got, want1):
+                raise ContractError(f"{what}: replay on new inputs gives the old outputs")
+            raise ContractError(f"{what}: replay on new inputs differs from the eager call on the new inputs in {differ(got, want2)} bytes")
+        again = replay()
+        if differ(again, got):
+            raise ContractError(f"{what}: second replay of the same inputs differs in {differ(again, got)} bytes")
+        return want1, want2
+    finally:
+        mem.sync()
+        if gexec.value:
+            rt.hipGraphExecDestroy(gexec)
+        if graph.value:
+            rt.hipGraphDestroy(graph)
 
 
 # ---------------------------------------------------------------- alignment of activation pointers

@@ -27,3 +27,23 @@ def views_fixture():
 
 def group_ids():
     return [f"crop{c}" for c, _, _ in views_fixture()[2]]
+
+
+def entry_args(ims, views, crop, nchw, scale=0.03):
+    """one call of ivit_view_transform_u8 (nchw) or ivit_view_resize_u8_pil over the images `ims`
+    -> (entry, argument list in abi_cases' form, (image table, view table): the host copies the call validates)"""
+    import ctypes
+    from ivit_amd import _lib
+    from ivit_amd import preprocess as pp
+    from ivit_amd import views as vw
+    sizes = np.array([im.size for im in ims], np.int64)
+    desc = np.zeros(len(ims), pp.DESC_DTYPE)
+    desc["offset"], desc["h"], desc["w"] = np.cumsum(sizes) - sizes, [im.shape[0] for im in ims], [im.shape[1] for im in ims]
+    pixels = np.concatenate([im.reshape(-1) for im in ims])
+    views = np.ascontiguousarray(views, dtype=vw.VIEW_DTYPE).copy()
+    head = [("in", pixels), pixels.size, desc.ctypes.data_as(ctypes.POINTER(_lib.ImageDesc)), ("in", desc.view(np.uint8).copy()), len(ims),
+            views.ctypes.data_as(ctypes.POINTER(_lib.ViewDesc)), ("in", views.view(np.uint8).copy()), len(views), crop]
+    if nchw:
+        mean, std = np.array(pp.IMAGENET_DEFAULT_MEAN, np.float32), np.array(pp.IMAGENET_DEFAULT_STD, np.float32)
+        return "ivit_view_transform_u8", head + [("host", mean), ("host", std), scale, ("out", np.zeros((len(views), 3, crop, crop), np.int8))], (desc, views)
+    return "ivit_view_resize_u8_pil", head + [("out", np.zeros((len(views), crop, crop, 3), np.uint8))], (desc, views)

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import ivit_amd as iv  # noqa: E402
 from ivit_amd import _lib  # noqa: E402
+from abi_cases import ln_lds_case as _ln_lds_case  # noqa: E402
 
 _P = ctypes.c_void_p
 
@@ -200,24 +201,6 @@ def test_layernorm_requant_vs_oracle_ragged(H, C):
         assert np.array_equal(got[:rows].astype(np.int32), want), (C, rows, stride, int((got[:rows] != want).sum()))
         assert (got[rows] == 77).all()
         assert len(np.unique(want)) > 50
-
-
-_LN_LDS_CASES = {}
-
-
-def _ln_lds_case(C):
-    """Eight rows of C channels (row 3 constant: zero variance), the LayerNorm constants and the oracle's fp32 result; computed once
-    per C and left unchanged."""
-    if C not in _LN_LDS_CASES:
-        from oracle import oracle as orc
-        rng = np.random.default_rng(C)
-        w = rng.normal(1.0, 0.4, C).astype(np.float32) * rng.choice([-1.0, 1.0], C).astype(np.float32)
-        bias_int, sc = iv.freeze.layernorm_constants(w, rng.normal(0.0, 0.5, C).astype(np.float32))
-        x = rng.integers(-26000, 26000, (8, C)).astype(np.int16)
-        x[:, : C // 2] //= 64                                         # small and large magnitudes in one row
-        x[3] = 1234
-        _LN_LDS_CASES[C] = (x, bias_int, sc, orc.layernorm(x, 7.3e-4, bias_int, sc))
-    return _LN_LDS_CASES[C]
 
 
 @pytest.mark.parametrize("device", [0, 1])

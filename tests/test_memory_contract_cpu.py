@@ -3,7 +3,6 @@ twinned entry point of tests/abi_cases.py::_cases runs with each array inside it
 arena and must (1) write nothing outside its outputs, (2) give the same bytes whatever lies around its inputs, (3) give the bytes of
 the same call on plain arrays.  The harness itself is tested with two planted entries that break rules 1 and 2."""
 import ctypes
-import functools
 
 import numpy as np
 import pytest
@@ -16,12 +15,7 @@ def twin():
     return A.load_twin()
 
 
-@functools.lru_cache(maxsize=None)
-def twin_cases(variant):
-    """the table, built once per variant and left unchanged (the arenas copy from it)"""
-    return A._cases(np.random.default_rng(77 + variant), variant)
-
-
+twin_cases = A.twin_table       # the table, built once per variant and left unchanged (the arenas copy from it)
 NAMES = sorted(A.table_names()[0])
 
 
@@ -38,6 +32,34 @@ def test_alignment_table_covers_every_entry_with_arrays():
     missing, wrong = A.alignment_table_gaps()
     assert not missing, f"entries with array arguments and no record in abi_cases.ALIGN: {missing}"
     assert not wrong, f"records of abi_cases.ALIGN that name no array argument: {wrong}"
+
+
+# input arrays that are functions of a case's scalars alone and so hold the same values whatever the seed: entry -> argument indices
+# (the per-tensor dyadics of the requant entries, the Shiftmax tables of one softmax scale)
+SEED_FREE_INPUTS = {"requant_i32": {1, 4}, "requant_i16": {1}, "window_attention_fused_lut": {5, 6, 7}, "shiftmax_rowtable": {0, 1, 2}}
+
+
+def test_tables_from_two_seeds_agree_in_everything_but_contents():
+    """tests/test_stream_graph_contract_gpu.py replays a graph captured on one table's arrays on the arrays of the table built from
+    abi_cases.SECOND_SEED: the two tables must hold the same entries in the same order with the same scalars, dyadics, host arrays,
+    handles, shapes, dtypes and pads, and differ in the contents of their input arrays alone — a case with an rng-drawn scalar fails
+    here, not obscurely on the device.  Every input array differs between the seeds unless SEED_FREE_INPUTS names it."""
+    pairs = []
+    for variant in (0, 1):
+        a, b = A.twin_table(variant), A.twin_table(variant, A.SECOND_SEED)
+        assert [n for n, _ in a] == [n for n, _ in b]
+        pairs += [(n, x, y) for (n, x), (_, y) in zip(a, b)]
+    a, b = A.hip_table(None), A.hip_table(None, A.SECOND_SEED)
+    assert [(n, s is None, s is not None and s.plans) for n, _, s in a] == [(n, s is None, s is not None and s.plans) for n, _, s in b]
+    pairs += [(n, x, y) for (n, x, _), (_, y, _) in zip(a, b)]
+    assert pairs
+    changed = 0
+    for n, x, y in pairs:
+        diffs, differ, same = A.table_differences(x, y)
+        assert not diffs, (n, diffs)
+        assert set(same) <= SEED_FREE_INPUTS.get(n, set()), (n, "input arrays that do not depend on the seed", same)
+        changed += len(differ)
+    assert changed >= len(pairs)
 
 
 def test_glds_256_row_tile_is_unreachable():

@@ -10,7 +10,6 @@ refused before anything is launched, or, for the pairs abi_cases.INPLACE declare
 
 Runners: a forward on a workspace that held garbage gives the logits of a forward on a clean one."""
 import ctypes
-import functools
 
 import numpy as np
 import pytest
@@ -36,30 +35,7 @@ def twin():
     return A.load_twin()
 
 
-@functools.lru_cache(maxsize=None)
-def twin_cases(variant):
-    return A._cases(np.random.default_rng(77 + variant), variant)
-
-
-@functools.lru_cache(maxsize=None)
-def hip_cases(H):
-    """the device table, built once per handle (None: names and arguments only) and left unchanged"""
-    return A.hip_cases(H, np.random.default_rng(99))
-
-
-def cases_of(H, name):
-    """(label, args, setup, twinned) of every case of entry `name` in both tables"""
-    out = []
-    for variant in (0, 1):
-        out += [(f"twinned table, variant {variant}, case {i}", args, None, True)
-                for i, (n, args) in enumerate(twin_cases(variant)) if n == name]
-    # a device-table case of a twinned entry goes through the twin as well, unless it sits behind a plan (another handle protocol)
-    twinned = name in A.gen_twin_header.TWIN and name not in A.NO_TWIN_FORM
-    out += [(f"device table, case {i}", args, setup, twinned and (setup is None or not setup.plans))
-            for i, (n, args, setup) in enumerate(hip_cases(H)) if n == name]
-    return out
-
-
+cases_of = A.cases_of           # (label, args, setup, twinned) of every case of an entry in both tables, built once
 NAMES = sorted(A.table_names()[0] | A.table_names()[1])
 
 

@@ -1,8 +1,6 @@
 """The PIL-exact ragged front end on the device: ivit_resize_center_crop_u8_pil and ivit_eval_transform_u8 against PIL's recorded
 bytes (tests/golden/pil_resize.npz: every byte, no tolerance), their memory contract on the arena harness of tests/abi_cases.py,
 their refusals, the forms of the kernel the fixture's small images cannot reach, and evaluate() end to end."""
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -17,9 +15,9 @@ from ivit_amd import _lib  # noqa: E402
 from ivit_amd import preprocess as pp  # noqa: E402
 from ivit_amd.predict import evaluate  # noqa: E402
 from pil_fixture import case_ids, fixture  # noqa: E402
+from pil_fixture import entry_args as _args  # noqa: E402    -> (entry, argument list in abi_cases' form, keep-alive)
 
 CASES = range(len(case_ids()))
-MEAN, STD = np.array(pp.IMAGENET_DEFAULT_MEAN, np.float32), np.array(pp.IMAGENET_DEFAULT_STD, np.float32)
 
 
 @pytest.fixture(scope="module")
@@ -89,19 +87,6 @@ def test_forms_beyond_the_fixture_equal_the_reference(h, w, size, crop, what):
 
 
 # ---------------------------------------------------------------- memory contract
-def _args(ims, size, crop, nchw, scale=0.03):
-    """-> (entry, argument list in abi_cases' form, keep-alive)"""
-    sizes = np.array([im.size for im in ims], np.int64)
-    desc = np.zeros(len(ims), pp.DESC_DTYPE)
-    desc["offset"], desc["h"], desc["w"] = np.cumsum(sizes) - sizes, [im.shape[0] for im in ims], [im.shape[1] for im in ims]
-    pixels = np.concatenate([im.reshape(-1) for im in ims])
-    head = [("in", pixels), pixels.size, desc.ctypes.data_as(ctypes.POINTER(_lib.ImageDesc)), ("in", desc.view(np.uint8).copy()),
-            len(ims), size, crop]
-    if nchw:
-        return "ivit_eval_transform_u8", head + [("host", MEAN), ("host", STD), scale, ("out", np.zeros((len(ims), 3, crop, crop), np.int8))], desc
-    return "ivit_resize_center_crop_u8_pil", head + [("out", np.zeros((len(ims), crop, crop, 3), np.uint8))], desc
-
-
 @pytest.mark.parametrize("nchw", [False, True], ids=["hwc", "nchw"])
 @pytest.mark.parametrize("k", CASES, ids=case_ids())
 def test_memory_contract(H, k, nchw):

@@ -477,8 +477,9 @@ def test_search_topk_captured_in_a_graph_replays_on_new_queries(H):
     val = torch.zeros(nq, k, dtype=torch.float32, device="cuda")
     args = (P(qbuf), nq, P(case.d_g), rows, dim, P(case.d_w), k, 0, 0, P(ws), nws, P(idx), P(val))
     torch.cuda.synchronize()
+    # eager once, against the reference (a kernel's first launch may be captured as well: tests/test_stream_graph_contract_gpu.py)
     with torch.cuda.stream(stream):
-        h2.call("ivit_search_topk", *args)                        # eager once: the launch attributes are set outside the capture
+        h2.call("ivit_search_topk", *args)
     stream.synchronize()
     ri, rv = case.reference(True, k)
     assert np.array_equal(idx.cpu().numpy(), ri)

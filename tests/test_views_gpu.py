@@ -24,9 +24,9 @@ from ivit_amd import views as vw  # noqa: E402
 from ivit_amd.predict import evaluate, score_reference, topk_reference, view_scale_reference, view_sum_reference  # noqa: E402
 from pil_fixture import case_ids, fixture  # noqa: E402
 from pil_views_fixture import group_ids, views_fixture  # noqa: E402
+from pil_views_fixture import entry_args as _args  # noqa: E402    -> (entry, argument list in abi_cases' form, the host tables)
 
 GROUPS = range(len(group_ids()))
-MEAN, STD = np.array(pp.IMAGENET_DEFAULT_MEAN, np.float32), np.array(pp.IMAGENET_DEFAULT_STD, np.float32)
 ARGNAMES = {name: [p.name for p in _lib.VIEWS_ABI.functions[name].params[1:]] for name in _lib.VIEWS_ABI.functions}
 
 
@@ -133,20 +133,6 @@ def test_a_view_depends_on_no_byte_outside_its_box():
 
 
 # ---------------------------------------------------------------- memory contract
-def _args(ims, views, crop, nchw, scale=0.03):
-    """-> (entry, argument list in abi_cases' form, (image table, view table): the host copies the call validates)"""
-    sizes = np.array([im.size for im in ims], np.int64)
-    desc = np.zeros(len(ims), pp.DESC_DTYPE)
-    desc["offset"], desc["h"], desc["w"] = np.cumsum(sizes) - sizes, [im.shape[0] for im in ims], [im.shape[1] for im in ims]
-    pixels = np.concatenate([im.reshape(-1) for im in ims])
-    views = np.ascontiguousarray(views, dtype=vw.VIEW_DTYPE).copy()
-    head = [("in", pixels), pixels.size, desc.ctypes.data_as(ctypes.POINTER(_lib.ImageDesc)), ("in", desc.view(np.uint8).copy()), len(ims),
-            views.ctypes.data_as(ctypes.POINTER(_lib.ViewDesc)), ("in", views.view(np.uint8).copy()), len(views), crop]
-    if nchw:
-        return "ivit_view_transform_u8", head + [("host", MEAN), ("host", STD), scale, ("out", np.zeros((len(views), 3, crop, crop), np.int8))], (desc, views)
-    return "ivit_view_resize_u8_pil", head + [("out", np.zeros((len(views), crop, crop, 3), np.uint8))], (desc, views)
-
-
 @pytest.mark.parametrize("nchw", [False, True], ids=["hwc", "nchw"])
 @pytest.mark.parametrize("k", GROUPS, ids=group_ids())
 def test_memory_contract(H, k, nchw):
