@@ -1,4 +1,4 @@
-"""include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h and include/ivit_range.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
+"""include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h and include/ivit_jpeg.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
 tools/gen_twin_header.py prints the CPU twin's prototypes from it, the tests bind the twin and walk the entry points through it.
 Standard library only, so a tool loads this file without the package (and without torch).
 
@@ -21,6 +21,8 @@ Standard library only, so a tool loads this file without the package (and withou
                     listed behind those of ivit.h
     CLUSTER_ABI     the same of include/ivit_cluster.h, the eleventh (IVIT_CLUSTER_VERSION)
     RANGE_ABI       the same of include/ivit_range.h, the twelfth (IVIT_RANGE_VERSION)
+    JPEG_ABI        the same of include/ivit_jpeg.h, the thirteenth (IVIT_JPEG_VERSION); it declares a struct (ivit_jpeg_desc) of its own
+                    with fixed-size array members, listed behind those of ivit.h
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -50,6 +52,7 @@ PROBE_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_probe.h")
 VIEWS_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_views.h")
 CLUSTER_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_cluster.h")
 RANGE_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_range.h")
+JPEG_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_jpeg.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -209,3 +212,5 @@ with open(CLUSTER_HEADER) as _f:
     CLUSTER_ABI = parse(_f.read(), base=ABI)
 with open(RANGE_HEADER) as _f:
     RANGE_ABI = parse(_f.read(), base=ABI)
+with open(JPEG_HEADER) as _f:
+    JPEG_ABI = parse(_f.read(), base=ABI)

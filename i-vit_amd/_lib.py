@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h and include/ivit_range.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
+"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h and include/ivit_jpeg.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
 restated here: the Structures, the status codes and every argtypes / restype are derived from the headers by _abi.py (the mapping
 rule is stated there).  ivit.h is frozen at IVIT_VERSION 111: ABI / SIGNATURES / RESTYPES are its prototypes and stay what they are;
 the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES, of ivit_features.h,
@@ -7,7 +7,8 @@ ATTNMAP_RESTYPES, of ivit_classmap.h, under CLASSMAP_ABI / CLASSMAP_SIGNATURES /
 HIDDEN_ABI / HIDDEN_SIGNATURES / HIDDEN_RESTYPES, of ivit_search.h, under SEARCH_ABI / SEARCH_SIGNATURES / SEARCH_RESTYPES, of
 ivit_modelfile.h, under MODELFILE_ABI / MODELFILE_SIGNATURES / MODELFILE_RESTYPES, of ivit_probe.h, under PROBE_ABI /
 PROBE_SIGNATURES / PROBE_RESTYPES, of ivit_views.h, under VIEWS_ABI / VIEWS_SIGNATURES / VIEWS_RESTYPES, of ivit_cluster.h, under CLUSTER_ABI /
-CLUSTER_SIGNATURES / CLUSTER_RESTYPES, and of ivit_range.h, under RANGE_ABI / RANGE_SIGNATURES / RANGE_RESTYPES.
+CLUSTER_SIGNATURES / CLUSTER_RESTYPES, of ivit_range.h, under RANGE_ABI / RANGE_SIGNATURES / RANGE_RESTYPES, and of ivit_jpeg.h, under JPEG_ABI /
+JPEG_SIGNATURES / JPEG_RESTYPES (its struct ivit_jpeg_desc is JpegDesc).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -174,6 +175,20 @@ _range_signatures = _abi.signatures(RANGE_ABI, _structs)
 RANGE_RESTYPES = {name: ret for name, (ret, args) in _range_signatures.items()}
 RANGE_SIGNATURES = {name: args for name, (ret, args) in _range_signatures.items()}
 
+# include/ivit_jpeg.h, by the rule of ivit_views.h: it declares one struct of its own, ivit_jpeg_desc (JpegDesc here)
+JPEG_ABI = _abi.JPEG_ABI
+IVIT_JPEG_VERSION = JPEG_ABI.constants["IVIT_JPEG_VERSION"]
+assert set(JPEG_ABI.structs) == set(ABI.structs) | {"ivit_jpeg_desc"} and not set(JPEG_ABI.functions) & (
+    set(ABI.functions) | set(EVAL_ABI.functions) | set(FEATURES_ABI.functions) | set(ATTNMAP_ABI.functions) | set(CLASSMAP_ABI.functions)
+    | set(HIDDEN_ABI.functions) | set(SEARCH_ABI.functions) | set(MODELFILE_ABI.functions) | set(PROBE_ABI.functions) | set(VIEWS_ABI.functions)
+    | set(CLUSTER_ABI.functions) | set(RANGE_ABI.functions))
+_jpeg_structs = dict(_structs)
+_jpeg_structs.update((n, c) for n, c in _abi.structures(JPEG_ABI, dict(STRUCT_NAMES, ivit_jpeg_desc="JpegDesc")).items() if n not in _structs)
+JpegDesc = _jpeg_structs["ivit_jpeg_desc"]
+_jpeg_signatures = _abi.signatures(JPEG_ABI, _jpeg_structs)
+JPEG_RESTYPES = {name: ret for name, (ret, args) in _jpeg_signatures.items()}
+JPEG_SIGNATURES = {name: args for name, (ret, args) in _jpeg_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -182,7 +197,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _abi.RANGE_HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _abi.RANGE_HEADER, _abi.JPEG_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -308,6 +323,14 @@ def bind_range(lib):
     return lib
 
 
+def bind_jpeg(lib):
+    """the same for every prototype of include/ivit_jpeg.h"""
+    for name, args in JPEG_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, JPEG_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -319,7 +342,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind_range(bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH)))))))))))))
+    _lib = bind_jpeg(bind_range(bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH))))))))))))))
     return _lib
 
 

@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -42,6 +42,8 @@
 #include "ivit_range.h"
 #include "ivit_preprocess.h"
 #include "ivit_views.h"
+#include "ivit_jpeg_host.h"
+#include "ivit_jpeg.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -435,6 +437,101 @@ int ivit_logits_view_sum(ivit_handle h, const int32_t *logits, int groups, int v
     const int grid = grid_for(h, n, VIEW_SUM_THREADS);              // a grid-stride stream: at most 16 blocks per CU
     if (vec) logits_view_sum_kernel<true><<<grid, VIEW_SUM_THREADS, 0, h->stream>>>(logits, n, per, views, out);
     else logits_view_sum_kernel<false><<<grid, VIEW_SUM_THREADS, 0, h->stream>>>(logits, n, per, views, out);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- JPEG input (include/ivit_jpeg.h, ivit_jpeg_host.h, ivit_jpeg.h)
+// The two host entries are ivit_jpeg_host.h's functions.  The reconstruction checks the host table — what keeps both kernels inside
+// coef_count, workspace_bytes and pixels_bytes: every grid recomputed from (w, h, hs, vs), every range inside its buffer, the written
+// ranges ascending — then two launches over the device table, gridDim.y the file, gridDim.x sized for the largest file.
+static inline size_t jpeg_align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+extern "C" {
+
+int ivit_jpeg_query_host(const uint8_t *data_host, size_t bytes, ivit_jpeg_desc *desc_host, int64_t *coef_count, size_t *workspace_bytes,
+                         char *err_host, size_t err_bytes) {
+    return ivit_jpeg_host_query(data_host, bytes, desc_host, coef_count, workspace_bytes, err_host, err_bytes);
+}
+
+int ivit_jpeg_entropy_decode_host(const uint8_t *data_host, size_t bytes, int16_t *coefs_host, int64_t coef_capacity, char *err_host,
+                                  size_t err_bytes) {
+    return ivit_jpeg_host_entropy_decode(data_host, bytes, coefs_host, coef_capacity, err_host, err_bytes);
+}
+
+int ivit_jpeg_workspace_bytes(const ivit_jpeg_desc *desc_host, int B, size_t *bytes) {
+    if (!bytes || B < 0 || (B > 0 && !desc_host)) return IVIT_ERR_INVALID;
+    size_t n = 0;
+    for (int i = 0; i < B; ++i) {
+        const ivit_jpeg_desc &d = desc_host[i];
+        if (d.ncomp != 1 && d.ncomp != 3) return IVIT_ERR_INVALID;
+        for (int c = 0; c < 3; ++c)
+            if (d.bw[c] < 0 || d.bh[c] < 0 || d.bw[c] > 8192 || d.bh[c] > 8192) return IVIT_ERR_INVALID;
+        n += jpeg_align16(ivit_jpeg_host::plane_bytes(d.bw, d.bh, d.ncomp));
+    }
+    *bytes = n;
+    return IVIT_OK;
+}
+
+int ivit_jpeg_reconstruct_u8(ivit_handle h, const int16_t *coefs, int64_t coef_count, const ivit_jpeg_desc *desc_host,
+                             const ivit_jpeg_desc *desc_dev, int B, uint8_t *workspace, size_t workspace_bytes, uint8_t *pixels,
+                             size_t pixels_bytes) {
+    CHECK_H(h);
+    REQUIRE(h, B >= 0 && coef_count >= 0, "bad arguments");
+    if (B == 0) return IVIT_OK;
+    REQUIRE(h, coefs && desc_host && desc_dev && workspace && pixels, "bad arguments");
+    REQUIRE_A16(h, coefs, "coefs");
+    REQUIRE_A16(h, workspace, "workspace");
+    REQUIRE_ALIGNED(h, desc_dev, "desc_dev", 8);
+    const size_t ncoef = (size_t)coef_count * 2, ndesc = (size_t)B * sizeof(ivit_jpeg_desc);
+    REQUIRE_DISJOINT(h, pixels, pixels_bytes, "pixels", workspace, workspace_bytes, "workspace", OVL_OUT);
+    REQUIRE_DISJOINT(h, coefs, ncoef, "coefs", pixels, pixels_bytes, "pixels", OVL_IN);
+    REQUIRE_DISJOINT(h, desc_dev, ndesc, "desc_dev", pixels, pixels_bytes, "pixels", OVL_IN);
+    REQUIRE_DISJOINT(h, coefs, ncoef, "coefs", workspace, workspace_bytes, "workspace", OVL_IN);
+    REQUIRE_DISJOINT(h, desc_dev, ndesc, "desc_dev", workspace, workspace_bytes, "workspace", OVL_IN);
+    auto fail = [&](const char *msg, int i) {
+        snprintf(h->err, sizeof(h->err), "%s: image %d: %s", __func__, i, msg);
+        return IVIT_ERR_INVALID;
+    };
+    long long max_blocks = 0, max_pixels = 0;
+    unsigned __int128 pixel_end = 0, plane_end = 0;
+    for (int i = 0; i < B; ++i) {
+        const ivit_jpeg_desc &d = desc_host[i];
+        if (d.w < 1 || d.h < 1 || d.w > 65535 || d.h > 65535) return fail("side outside 1 .. 65535", i);
+        if (d.ncomp != 1 && d.ncomp != 3) return fail("ncomp must be 1 or 3", i);
+        const bool samp = (d.hs == 1 && d.vs == 1) || (d.ncomp == 3 && d.hs == 2 && (d.vs == 1 || d.vs == 2));
+        if (!samp) return fail("sampling must be 1x1, 2x1 or 2x2 (1x1 with one component)", i);
+        if (d.reserved != 0) return fail("reserved must be 0", i);
+        const int mw = (d.w + 8 * d.hs - 1) / (8 * d.hs), mh = (d.h + 8 * d.vs - 1) / (8 * d.vs);
+        long long blocks = 0;
+        for (int c = 0; c < 3; ++c) {
+            const int bw = c < d.ncomp ? mw * (c == 0 ? d.hs : 1) : 0, bh = c < d.ncomp ? mh * (c == 0 ? d.vs : 1) : 0;
+            if (d.bw[c] != bw || d.bh[c] != bh) return fail("bw / bh are not the block grid of w, h and the sampling", i);
+            blocks += (long long)bw * bh;
+        }
+        if (d.coef_offset < 0 || (d.coef_offset & 7)) return fail("coef_offset must be a non-negative multiple of 8", i);
+        if ((unsigned __int128)d.coef_offset + (unsigned __int128)blocks * 64 > (unsigned __int128)coef_count) return fail("coefficients reach past coef_count", i);
+        if (d.plane_offset < 0 || (d.plane_offset & 15)) return fail("plane_offset must be a non-negative multiple of 16", i);
+        if ((unsigned __int128)d.plane_offset + (unsigned __int128)blocks * 64 > (unsigned __int128)workspace_bytes) return fail("planes reach past workspace_bytes", i);
+        if (d.pixel_offset < 0) return fail("negative pixel_offset", i);
+        const long long npix = (long long)d.w * d.h;
+        if ((unsigned __int128)d.pixel_offset + (unsigned __int128)npix * 3 > (unsigned __int128)pixels_bytes) return fail("pixels reach past pixels_bytes", i);
+        if ((unsigned __int128)d.pixel_offset < pixel_end) return fail("pixel_offset inside an earlier image's pixels", i);
+        if ((unsigned __int128)d.plane_offset < plane_end) return fail("plane_offset inside an earlier image's planes", i);
+        pixel_end = (unsigned __int128)d.pixel_offset + (unsigned __int128)npix * 3;
+        plane_end = (unsigned __int128)d.plane_offset + (unsigned __int128)blocks * 64;
+        max_blocks = std::max(max_blocks, blocks);
+        max_pixels = std::max(max_pixels, npix);
+    }
+    REQUIRE(h, B <= 65535, "one call takes at most 65535 images");
+    const long long g1 = (max_blocks + JPEG_WG_BLOCKS - 1) / JPEG_WG_BLOCKS, g2 = (max_pixels + JPEG_THREADS - 1) / JPEG_THREADS;
+    REQUIRE_LAUNCH(h, g1 * B, JPEG_THREADS, 1);
+    REQUIRE_LAUNCH(h, g2 * B, JPEG_THREADS, 1);
+    jpeg_idct_kernel<<<dim3((unsigned)g1, (unsigned)B), JPEG_THREADS, 0, h->stream>>>((const short *)coefs, desc_dev, workspace);
+    LAUNCH_CHECK(h);
+    jpeg_color_kernel<<<dim3((unsigned)g2, (unsigned)B), JPEG_THREADS, 0, h->stream>>>(workspace, desc_dev, pixels);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

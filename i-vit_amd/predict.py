@@ -32,7 +32,11 @@ vit_quant.py:278-282 / swin_quant.py:560-564), takes the cross-entropy and top-1
 import numpy as np
 import torch
 
-MAX_K = 16          # TOPK_MAX_K of csrc/ivit_topk.h
+# the numpy statements of include/ivit_jpeg.h (both halves of the decoder) live in ivit_amd/jpeg.py, as views_reference does in
+# views.py; they are named here beside the others
+from .jpeg import jpeg_coefficients_reference, jpeg_reference  # noqa: F401
+
+MAX_K = 16         # TOPK_MAX_K of csrc/ivit_topk.h
 
 
 def topk_reference(acc, scale, k):

@@ -14,6 +14,9 @@ data.npz holds `labels` [N] and the images in one of three forms:
                               is uploaded once per rank and every batch is one launch of eval_transform_pil: the bytes PIL hands
                               the reference (utils/data_utils.py:82-92), so the count is the one `quant_train.py --evaluate` gives;
   images int8 [N, C, S, S]    already quantised at the model's input scale, fed as they are.
+With --jpeg-dir DIR the file holds `labels` [N] and `files` [N], names of JPEG files under DIR: every batch is decoded by
+ivit_amd.jpeg.decode (entropy decode on --jpeg-threads host threads, reconstruction on the device: Pillow's bytes; files the decoder
+refuses go through Pillow) and taken through eval_transform_pil, so the count is again the one `quant_train.py --evaluate` gives.
 The model is a name from ivit_amd.CONFIGS / SWIN_CONFIGS with either
   --golden F      the seeded synthetic weights and the calibrated scales recorded in a tests/golden fixture, or
   --state-dict F  a reference state dict / checkpoint (float parameters and act_scaling_factor buffers; ivit_amd.checkpoint).
@@ -93,6 +96,15 @@ def load_share(d, labels, cfg, s_in, args, device, lo, hi):
     the transform that turns a slice into the engine's int8 input, or None)"""
     size = args.resize or int(cfg.img_size / 0.875)
     transform = None
+    if getattr(args, "jpeg_dir", None):
+        from ivit_amd.jpeg import decode
+        from ivit_amd.preprocess import eval_transform_pil
+        if "files" not in d.files or len(d["files"]) != len(labels):
+            raise SystemExit("--jpeg-dir needs `files` [N] beside `labels` [N]")
+        if getattr(args, "views", 1) != 1:
+            raise SystemExit("--views is not available with --jpeg-dir")
+        mine = [os.path.join(args.jpeg_dir, str(f)) for f in d["files"][lo:hi]]
+        return mine, lambda paths: eval_transform_pil(decode(paths, device, threads=args.jpeg_threads)[0], s_in, size, cfg.img_size)
     if "pixels" in d.files or (args.resample == "pil" and d["images"].dtype == np.uint8):
         from ivit_amd.preprocess import DESC_DTYPE, RaggedImages, eval_transform_pil
         if "pixels" in d.files:
@@ -145,6 +157,8 @@ def main():
     ap.add_argument("--loss", action="store_true", help="also the mean cross-entropy of the labels (validate()'s Loss), computed on the device")
     ap.add_argument("--views", type=int, choices=(1, 5, 10), default=1,
                     help="views per image: 1 the centre crop (default), 5 five-crop, 10 ten-crop; the mean logits are scored")
+    ap.add_argument("--jpeg-dir", help="`files` of the data file are JPEG files under this directory, decoded by ivit_amd.jpeg.decode")
+    ap.add_argument("--jpeg-threads", type=int, default=8, help="host threads of the entropy decode (at most 16)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/evaluate.py needs a HIP device; the product path has no CPU fallback")
