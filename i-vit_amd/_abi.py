@@ -1,4 +1,4 @@
-"""include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h and include/ivit_jpeg.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
+"""include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h and include/ivit_jpeg_entropy.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
 tools/gen_twin_header.py prints the CPU twin's prototypes from it, the tests bind the twin and walk the entry points through it.
 Standard library only, so a tool loads this file without the package (and without torch).
 
@@ -23,6 +23,9 @@ Standard library only, so a tool loads this file without the package (and withou
     RANGE_ABI       the same of include/ivit_range.h, the twelfth (IVIT_RANGE_VERSION)
     JPEG_ABI        the same of include/ivit_jpeg.h, the thirteenth (IVIT_JPEG_VERSION); it declares a struct (ivit_jpeg_desc) of its own
                     with fixed-size array members, listed behind those of ivit.h
+    JPEG_ENTROPY_ABI  the same of include/ivit_jpeg_entropy.h, the fourteenth (IVIT_JPEG_ENTROPY_VERSION, the smallest subsequence and
+                    the status codes); it includes ivit_jpeg.h, so its base is JPEG_ABI, and declares three structs of its own
+                    (ivit_jpeg_segment, ivit_jpeg_huff, ivit_jpeg_scan, the last with arrays of the second as members)
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -53,6 +56,7 @@ VIEWS_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_views.h")
 CLUSTER_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_cluster.h")
 RANGE_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_range.h")
 JPEG_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_jpeg.h")
+JPEG_ENTROPY_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_jpeg_entropy.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -214,3 +218,5 @@ with open(RANGE_HEADER) as _f:
     RANGE_ABI = parse(_f.read(), base=ABI)
 with open(JPEG_HEADER) as _f:
     JPEG_ABI = parse(_f.read(), base=ABI)
+with open(JPEG_ENTROPY_HEADER) as _f:
+    JPEG_ENTROPY_ABI = parse(_f.read(), base=JPEG_ABI)

@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h and include/ivit_jpeg.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
+"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h and include/ivit_jpeg_entropy.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
 restated here: the Structures, the status codes and every argtypes / restype are derived from the headers by _abi.py (the mapping
 rule is stated there).  ivit.h is frozen at IVIT_VERSION 111: ABI / SIGNATURES / RESTYPES are its prototypes and stay what they are;
 the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES, of ivit_features.h,
@@ -8,7 +8,8 @@ HIDDEN_ABI / HIDDEN_SIGNATURES / HIDDEN_RESTYPES, of ivit_search.h, under SEARCH
 ivit_modelfile.h, under MODELFILE_ABI / MODELFILE_SIGNATURES / MODELFILE_RESTYPES, of ivit_probe.h, under PROBE_ABI /
 PROBE_SIGNATURES / PROBE_RESTYPES, of ivit_views.h, under VIEWS_ABI / VIEWS_SIGNATURES / VIEWS_RESTYPES, of ivit_cluster.h, under CLUSTER_ABI /
 CLUSTER_SIGNATURES / CLUSTER_RESTYPES, of ivit_range.h, under RANGE_ABI / RANGE_SIGNATURES / RANGE_RESTYPES, and of ivit_jpeg.h, under JPEG_ABI /
-JPEG_SIGNATURES / JPEG_RESTYPES (its struct ivit_jpeg_desc is JpegDesc).
+JPEG_SIGNATURES / JPEG_RESTYPES (its struct ivit_jpeg_desc is JpegDesc), and of ivit_jpeg_entropy.h, under JPEG_ENTROPY_ABI /
+JPEG_ENTROPY_SIGNATURES / JPEG_ENTROPY_RESTYPES (its structs are JpegSegment, JpegHuff and JpegScan).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -189,6 +190,24 @@ _jpeg_signatures = _abi.signatures(JPEG_ABI, _jpeg_structs)
 JPEG_RESTYPES = {name: ret for name, (ret, args) in _jpeg_signatures.items()}
 JPEG_SIGNATURES = {name: args for name, (ret, args) in _jpeg_signatures.items()}
 
+# include/ivit_jpeg_entropy.h, by the rule of ivit_jpeg.h, which it includes: its base is JPEG_ABI, its own structs are ivit_jpeg_segment,
+# ivit_jpeg_huff and ivit_jpeg_scan (JpegSegment, JpegHuff, JpegScan here)
+JPEG_ENTROPY_ABI = _abi.JPEG_ENTROPY_ABI
+IVIT_JPEG_ENTROPY_VERSION, IVIT_JPEG_ENTROPY_MIN_BITS = (
+    JPEG_ENTROPY_ABI.constants[n] for n in ("IVIT_JPEG_ENTROPY_VERSION", "IVIT_JPEG_ENTROPY_MIN_BITS"))
+_JPEG_ENTROPY_STRUCTS = {"ivit_jpeg_segment": "JpegSegment", "ivit_jpeg_huff": "JpegHuff", "ivit_jpeg_scan": "JpegScan"}
+assert set(JPEG_ENTROPY_ABI.structs) == set(JPEG_ABI.structs) | set(_JPEG_ENTROPY_STRUCTS) and not set(JPEG_ENTROPY_ABI.functions) & (
+    set(ABI.functions) | set(EVAL_ABI.functions) | set(FEATURES_ABI.functions) | set(ATTNMAP_ABI.functions) | set(CLASSMAP_ABI.functions)
+    | set(HIDDEN_ABI.functions) | set(SEARCH_ABI.functions) | set(MODELFILE_ABI.functions) | set(PROBE_ABI.functions) | set(VIEWS_ABI.functions)
+    | set(CLUSTER_ABI.functions) | set(RANGE_ABI.functions) | set(JPEG_ABI.functions))
+_jpeg_entropy_structs = dict(_jpeg_structs)
+_jpeg_entropy_structs.update((n, c) for n, c in _abi.structures(JPEG_ENTROPY_ABI, dict(STRUCT_NAMES, ivit_jpeg_desc="JpegDesc", **_JPEG_ENTROPY_STRUCTS)).items()
+                             if n not in _jpeg_structs)
+JpegSegment, JpegHuff, JpegScan = (_jpeg_entropy_structs[n] for n in _JPEG_ENTROPY_STRUCTS)
+_jpeg_entropy_signatures = _abi.signatures(JPEG_ENTROPY_ABI, _jpeg_entropy_structs)
+JPEG_ENTROPY_RESTYPES = {name: ret for name, (ret, args) in _jpeg_entropy_signatures.items()}
+JPEG_ENTROPY_SIGNATURES = {name: args for name, (ret, args) in _jpeg_entropy_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -197,7 +216,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _abi.RANGE_HEADER, _abi.JPEG_HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _abi.RANGE_HEADER, _abi.JPEG_HEADER, _abi.JPEG_ENTROPY_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -331,6 +350,14 @@ def bind_jpeg(lib):
     return lib
 
 
+def bind_jpeg_entropy(lib):
+    """the same for every prototype of include/ivit_jpeg_entropy.h"""
+    for name, args in JPEG_ENTROPY_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, JPEG_ENTROPY_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -342,7 +369,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind_jpeg(bind_range(bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH))))))))))))))
+    _lib = bind_jpeg_entropy(bind_jpeg(bind_range(bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH)))))))))))))))
     return _lib
 
 

@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -44,6 +44,8 @@
 #include "ivit_views.h"
 #include "ivit_jpeg_host.h"
 #include "ivit_jpeg.h"
+#include "ivit_jpeg_scan_host.h"
+#include "ivit_jpeg_entropy.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -532,6 +534,123 @@ int ivit_jpeg_reconstruct_u8(ivit_handle h, const int16_t *coefs, int64_t coef_c
     jpeg_idct_kernel<<<dim3((unsigned)g1, (unsigned)B), JPEG_THREADS, 0, h->stream>>>((const short *)coefs, desc_dev, workspace);
     LAUNCH_CHECK(h);
     jpeg_color_kernel<<<dim3((unsigned)g2, (unsigned)B), JPEG_THREADS, 0, h->stream>>>(workspace, desc_dev, pixels);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- JPEG entropy decode on the device (include/ivit_jpeg_entropy.h)
+// The scan is ivit_jpeg_scan_host.h's function.  The device entry checks the host copies of the three tables — what keeps the kernel
+// inside streams_bytes, workspace_bytes and coef_count: every file's stream, workspace part and coefficients inside their buffers and
+// behind the file before, every segment inside its stream — then one launch of B workgroups over the device copies.
+extern "C" {
+
+int ivit_jpeg_scan_host(const uint8_t *data_host, size_t bytes, ivit_jpeg_desc *desc_host, ivit_jpeg_scan *scan_host, uint8_t *stream_host,
+                        size_t stream_capacity, ivit_jpeg_segment *segments_host, int64_t segment_capacity, int64_t *coef_count,
+                        size_t *workspace_bytes, char *err_host, size_t err_bytes) {
+    return ivit_jpeg_host_scan(data_host, bytes, desc_host, scan_host, stream_host, stream_capacity, segments_host, segment_capacity, coef_count,
+                               workspace_bytes, err_host, err_bytes);
+}
+
+int ivit_jpeg_entropy_workspace_bytes(const ivit_jpeg_scan *scan_host, int B, size_t *bytes) {
+    if (!bytes || B < 0 || (B > 0 && !scan_host)) return IVIT_ERR_INVALID;
+    size_t n = 0;
+    for (int i = 0; i < B; ++i) {
+        if (scan_host[i].stream_bytes < 0 || scan_host[i].stream_bytes >= (1LL << 28) || scan_host[i].segment_count < 0) return IVIT_ERR_INVALID;
+        n += ivit_jpeg_entropy_file_workspace(scan_host[i].stream_bytes, scan_host[i].segment_count);
+    }
+    *bytes = n;
+    return IVIT_OK;
+}
+
+int ivit_jpeg_entropy_decode(ivit_handle h, const uint8_t *streams, size_t streams_bytes, const ivit_jpeg_desc *desc_host,
+                             const ivit_jpeg_desc *desc_dev, const ivit_jpeg_scan *scan_host, const ivit_jpeg_scan *scan_dev,
+                             const ivit_jpeg_segment *segments_host, const ivit_jpeg_segment *segments_dev, int64_t segment_count, int B,
+                             int subsequence_bits, uint8_t *workspace, size_t workspace_bytes, int16_t *coefs, int64_t coef_count,
+                             int32_t *status) {
+    CHECK_H(h);
+    REQUIRE(h, B >= 0 && coef_count >= 0 && segment_count >= 0, "bad arguments");
+    const int S = subsequence_bits == 0 ? JENT_DEFAULT_BITS : subsequence_bits;
+    REQUIRE(h, S >= IVIT_JPEG_ENTROPY_MIN_BITS && S <= 65536 && (S & (S - 1)) == 0, "subsequence_bits must be 0 or a power of two in 128 .. 65536");
+    if (B == 0) return IVIT_OK;
+    REQUIRE(h, streams && desc_host && desc_dev && scan_host && scan_dev && segments_host && segments_dev && workspace && coefs && status,
+            "bad arguments");
+    REQUIRE(h, B <= 65535, "one call takes at most 65535 files");
+    REQUIRE_A16(h, streams, "streams");
+    REQUIRE_A16(h, workspace, "workspace");
+    REQUIRE_A16(h, coefs, "coefs");
+    REQUIRE_ALIGNED(h, desc_dev, "desc_dev", 8);
+    REQUIRE_ALIGNED(h, scan_dev, "scan_dev", 8);
+    REQUIRE_ALIGNED(h, segments_dev, "segments_dev", 8);
+    REQUIRE_ALIGNED(h, status, "status", 4);
+    const size_t ncoef = (size_t)coef_count * 2, nstatus = (size_t)B * 4;
+    const struct { const void *p; size_t n; const char *name; } in[] = {{streams, streams_bytes, "streams"},
+                                                                         {desc_dev, (size_t)B * sizeof(ivit_jpeg_desc), "desc_dev"},
+                                                                         {scan_dev, (size_t)B * sizeof(ivit_jpeg_scan), "scan_dev"},
+                                                                         {segments_dev, (size_t)segment_count * sizeof(ivit_jpeg_segment), "segments_dev"}};
+    REQUIRE_DISJOINT(h, coefs, ncoef, "coefs", status, nstatus, "status", OVL_OUT);
+    REQUIRE_DISJOINT(h, coefs, ncoef, "coefs", workspace, workspace_bytes, "workspace", OVL_OUT);
+    REQUIRE_DISJOINT(h, status, nstatus, "status", workspace, workspace_bytes, "workspace", OVL_OUT);
+    for (const auto &a : in) {
+        if (!ranges_disjoint(h, __func__, a.p, a.n, a.name, coefs, ncoef, "coefs", OVL_IN)) return IVIT_ERR_INVALID;
+        if (!ranges_disjoint(h, __func__, a.p, a.n, a.name, status, nstatus, "status", OVL_IN)) return IVIT_ERR_INVALID;
+        if (!ranges_disjoint(h, __func__, a.p, a.n, a.name, workspace, workspace_bytes, "workspace", OVL_IN)) return IVIT_ERR_INVALID;
+    }
+    auto fail = [&](const char *msg, int i) {
+        snprintf(h->err, sizeof(h->err), "%s: file %d: %s", __func__, i, msg);
+        return IVIT_ERR_INVALID;
+    };
+    unsigned __int128 stream_end = 0, work_end = 0, coef_end = 0;
+    for (int i = 0; i < B; ++i) {
+        const ivit_jpeg_desc &d = desc_host[i];
+        const ivit_jpeg_scan &s = scan_host[i];
+        if (d.w < 1 || d.h < 1 || d.w > 65535 || d.h > 65535) return fail("side outside 1 .. 65535", i);
+        if (d.ncomp != 1 && d.ncomp != 3) return fail("ncomp must be 1 or 3", i);
+        const bool samp = (d.hs == 1 && d.vs == 1) || (d.ncomp == 3 && d.hs == 2 && (d.vs == 1 || d.vs == 2));
+        if (!samp) return fail("sampling must be 1x1, 2x1 or 2x2 (1x1 with one component)", i);
+        if (d.reserved != 0 || s.reserved[0] != 0 || s.reserved[1] != 0) return fail("reserved must be 0", i);
+        const int mw = (d.w + 8 * d.hs - 1) / (8 * d.hs), mh = (d.h + 8 * d.vs - 1) / (8 * d.vs);
+        long long blocks = 0;
+        for (int c = 0; c < 3; ++c) {
+            const int bw = c < d.ncomp ? mw * (c == 0 ? d.hs : 1) : 0, bh = c < d.ncomp ? mh * (c == 0 ? d.vs : 1) : 0;
+            if (d.bw[c] != bw || d.bh[c] != bh) return fail("bw / bh are not the block grid of w, h and the sampling", i);
+            blocks += (long long)bw * bh;
+            if (s.td[c] < 0 || s.td[c] > 1 || s.ta[c] < 0 || s.ta[c] > 1) return fail("td / ta must be 0 or 1", i);
+        }
+        if (d.coef_offset < 0 || (d.coef_offset & 7)) return fail("coef_offset must be a non-negative multiple of 8", i);
+        if ((unsigned __int128)d.coef_offset + (unsigned __int128)blocks * 64 > (unsigned __int128)coef_count) return fail("coefficients reach past coef_count", i);
+        if ((unsigned __int128)d.coef_offset < coef_end) return fail("coef_offset inside an earlier file's coefficients", i);
+        coef_end = (unsigned __int128)d.coef_offset + (unsigned __int128)blocks * 64;
+        if (s.stream_bytes < 0 || s.stream_bytes >= (1LL << 28)) return fail("stream_bytes outside 0 .. 2^28 - 1", i);
+        const long long padded = (s.stream_bytes + 7) / 8 * 8;
+        if (s.stream_offset < 0 || (s.stream_offset & 15)) return fail("stream_offset must be a non-negative multiple of 16", i);
+        if ((unsigned __int128)s.stream_offset + (unsigned __int128)padded > (unsigned __int128)streams_bytes) return fail("stream reaches past streams_bytes", i);
+        if ((unsigned __int128)s.stream_offset < stream_end) return fail("stream_offset inside an earlier file's stream", i);
+        stream_end = (unsigned __int128)s.stream_offset + (unsigned __int128)padded;
+        if (s.restart < 0 || s.restart > 65535) return fail("restart outside 0 .. 65535", i);
+        const long long total = (long long)mw * mh, expected = s.restart ? (total + s.restart - 1) / s.restart : 1;
+        if (s.segment_count != expected) return fail("segment_count is not what restart and the MCUs give", i);
+        if (s.segment_offset < 0 || (unsigned __int128)s.segment_offset + (unsigned __int128)expected > (unsigned __int128)segment_count)
+            return fail("segments reach past segment_count", i);
+        const size_t need = ivit_jpeg_entropy_file_workspace(s.stream_bytes, s.segment_count);
+        if (s.work_offset < 0 || (s.work_offset & 15)) return fail("work_offset must be a non-negative multiple of 16", i);
+        if ((unsigned __int128)s.work_offset + (unsigned __int128)need > (unsigned __int128)workspace_bytes) return fail("workspace part reaches past workspace_bytes", i);
+        if ((unsigned __int128)s.work_offset < work_end) return fail("work_offset inside an earlier file's part", i);
+        work_end = (unsigned __int128)s.work_offset + (unsigned __int128)need;
+        long long bit = 0, mcu = 0;
+        for (long long k = 0; k < expected; ++k) {
+            const ivit_jpeg_segment &g = segments_host[s.segment_offset + k];
+            if (g.bit_offset < bit || (g.bit_offset & 7) || g.bit_count < 0 || (g.bit_count & 7) || g.bit_offset + g.bit_count > s.stream_bytes * 8)
+                return fail("a segment is not whole bytes inside the stream behind the segment before", i);
+            const long long count = s.restart && (k + 1) * s.restart <= total ? s.restart : total - k * (long long)s.restart;
+            if (g.first_mcu != mcu || g.mcu_count != count) return fail("a segment's MCUs are not what restart gives", i);
+            bit = g.bit_offset + g.bit_count;
+            mcu += count;
+        }
+    }
+    jpeg_entropy_kernel<<<dim3((unsigned)B), JENT_THREADS, 0, h->stream>>>(streams, desc_dev, scan_dev, segments_dev, S, workspace, (short *)coefs,
+                                                                          (int *)status);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

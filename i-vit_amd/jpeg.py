@@ -7,7 +7,10 @@ byte, or the file is refused.
     jpeg_reference(data)                both halves: uint8 [h, w, 3]; what the device call writes
     query / entropy_decode              the two host entries of the library (no GPU call)
     reconstruct                         the device entry on a batch of decoded files
-    decode                              files or bytes -> (RaggedImages, fallbacks)
+    decode                              files or bytes -> (RaggedImages, fallbacks); entropy="device" decodes the Huffman streams on the
+                                        device too (include/ivit_jpeg_entropy.h)
+    jpeg_scan_reference(data)           the host pre-pass of the device entropy decode as numpy: (unstuffed bytes, segments)
+    scan / entropy_decode_device        its two entries: the pre-pass of one file (no GPU call), the device decode of a batch
 
 The definition is libjpeg's, with its defaults ("JPEG input", states it line by line): dequantise, the "islow" inverse DCT
 (13-bit constants, a column pass to 2 extra bits, a row pass, +128, the range limit), "fancy" h2v1 / h2v2 chroma upsampling where the
@@ -366,6 +369,45 @@ def jpeg_coefficients_reference(data):
     return info, coefs
 
 
+SEGMENT_DTYPE = np.dtype([("bit_offset", "<i8"), ("bit_count", "<i8"), ("first_mcu", "<i4"), ("mcu_count", "<i4")])     # ivit_jpeg_segment
+
+
+def jpeg_scan_reference(data):
+    """bytes -> (uint8 array: the entropy-coded bytes with the stuffing removed, the markers left out; SEGMENT_DTYPE array: one record
+    per segment) — what csrc/ivit_jpeg_scan_host.h writes, its refusals included (JpegRefused): the restart markers in sequence, as
+    many segments as the restart interval and the MCUs give, EOI behind the last"""
+    d = bytes(data)
+    info, _, ri, pos = _parse(d)
+    total = info.mcus[0] * info.mcus[1]
+    expected = -(-total // ri) if ri else 1
+    out, segs = bytearray(), np.zeros(expected, SEGMENT_DTYPE)
+    for s in range(expected):
+        first, marker = len(out), None
+        while pos < len(d) and marker is None:
+            c = d[pos]
+            pos += 1
+            if c == 0xFF:
+                while pos < len(d) and d[pos] == 0xFF:
+                    pos += 1
+                if pos >= len(d):
+                    break
+                c, pos = d[pos], pos + 1
+                if c != 0:
+                    marker = c
+                    continue
+                c = 0xFF
+            out.append(c)
+        segs[s] = (8 * first, 8 * (len(out) - first), s * ri, min(ri, total - s * ri) if ri else total)
+        if marker is None:
+            raise _invalid("data ends before the last MCU")
+        if s + 1 == expected:
+            if marker != 0xD9:
+                raise _invalid("no EOI behind the last MCU")
+        elif marker != 0xD0 + (s & 7):
+            raise _invalid("restart marker out of sequence")
+    return np.frombuffer(bytes(out), np.uint8), segs
+
+
 # ---------------------------------------------------------------- the device half, as numpy
 def _islow(x):
     """jidctint.c's 1-D pass on the last axis of an int64 array [..., 8], before the descale"""
@@ -522,13 +564,158 @@ def reconstruct(coefs, table, B, pixels, workspace, table_dev=None, h=None):
     return table_dev
 
 
-def decode(files_or_bytes, device, threads=8, fallback="pil"):
+def scan(data, stream=None):
+    """one file -> (JpegDesc and JpegScan with their offsets 0, uint8 array of its unstuffed stream, SEGMENT_DTYPE array, coefficients
+    (int16 elements), plane bytes): the host pre-pass of the device entropy decode.  `stream`: a caller's uint8 array of at least
+    len(data) bytes (a slice of a pinned staging buffer); the stream is zero-filled in it up to a multiple of 8.  No GPU call; ctypes
+    releases the GIL."""
+    lib = _lib.load()
+    if stream is None:
+        stream = np.empty(len(data) + 8, np.uint8)
+    if stream.dtype != np.uint8 or stream.ndim != 1 or not stream.flags.c_contiguous:
+        raise ValueError("stream: a contiguous uint8 array")
+    segs = np.empty(len(data) // 3 + 1, SEGMENT_DTYPE)        # a segment is at least a byte and the two of its marker
+    desc, rec, ncoef, nws, err = _lib.JpegDesc(), _lib.JpegScan(), ctypes.c_int64(), ctypes.c_size_t(), ctypes.create_string_buffer(256)
+    st = lib.ivit_jpeg_scan_host(data, len(data), ctypes.byref(desc), ctypes.byref(rec), ctypes.c_void_p(stream.ctypes.data), stream.size,
+                                 ctypes.c_void_p(segs.ctypes.data), segs.size, ctypes.byref(ncoef), ctypes.byref(nws), err, len(err))
+    if st != IVIT_OK:
+        raise _refusal(st, err)
+    return desc, rec, stream[:rec.stream_bytes], segs[:rec.segment_count].copy(), ncoef.value, nws.value
+
+
+def status_class(code):
+    """a status of ivit_jpeg_entropy_decode -> the host decoder's status for that refusal (include/ivit_jpeg_entropy.h)"""
+    return IVIT_OK if code == 0 else IVIT_ERR_INVALID if 1 <= code <= 5 else IVIT_ERR_UNSUPPORTED
+
+
+def entropy_layout(recs, segments):
+    """places B scanned files back to back: sets stream_offset (multiples of 16), work_offset and segment_offset of every record ->
+    (JpegScan table, concatenated segments, stream bytes, workspace bytes)"""
+    lib = _lib.load()
+    table = (_lib.JpegScan * max(1, len(recs)))()
+    so = wo = go = 0
+    for i, r in enumerate(recs):
+        ctypes.memmove(ctypes.byref(table[i]), ctypes.byref(r), ctypes.sizeof(_lib.JpegScan))
+        table[i].stream_offset, table[i].work_offset, table[i].segment_offset = so, wo, go
+        n = ctypes.c_size_t()
+        if lib.ivit_jpeg_entropy_workspace_bytes(ctypes.byref(r), 1, ctypes.byref(n)) != IVIT_OK:
+            raise ValueError("file %d: a scan record outside what the entry takes" % i)
+        so += _align(_align(r.stream_bytes, 8), 16)
+        wo += n.value
+        go += r.segment_count
+    segs = np.concatenate(list(segments)) if len(recs) else np.zeros(0, SEGMENT_DTYPE)
+    return table, segs, so, wo
+
+
+def entropy_decode_device(streams, desc_table, desc_dev, scan_table, scan_dev, segments, segments_dev, B, workspace, coefs, status, bits=0,
+                          h=None):
+    """the device call: streams / workspace uint8, coefs int16 and status int32 tensors on one device; desc_table / scan_table the host
+    ctypes tables, segments the host SEGMENT_DTYPE array, *_dev uint8 tensors holding their device copies; bits: the subsequence in
+    bits, 0 the default.  Asynchronous on the current stream."""
+    from .quant_modules import handle
+    (h or handle(coefs.device)).call(
+        "ivit_jpeg_entropy_decode", ctypes.c_void_p(streams.data_ptr()), ctypes.c_size_t(streams.numel()), ctypes.cast(desc_table, ctypes.c_void_p),
+        ctypes.c_void_p(desc_dev.data_ptr()), ctypes.cast(scan_table, ctypes.c_void_p), ctypes.c_void_p(scan_dev.data_ptr()),
+        ctypes.c_void_p(segments.ctypes.data), ctypes.c_void_p(segments_dev.data_ptr()), ctypes.c_int64(len(segments)), int(B), int(bits),
+        ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), ctypes.c_void_p(coefs.data_ptr()), ctypes.c_int64(coefs.numel()),
+        ctypes.c_void_p(status.data_ptr()))
+
+
+def _decode_device(datas, device, threads, fall_back, pil_pixels, fallbacks, bits):
+    """decode() with entropy="device": the pool runs the pre-pass of every file into one pinned buffer of streams (every file at the
+    prefix sum of the sizes: no query before the pool), one copy of the streams and one of the tables, the entropy decode and the
+    reconstruction on one stream, one synchronisation.  A file the pre-pass or the device refuses is given to the host decoder for the
+    reason and goes the way the host path sends it."""
+    import torch
+    from .preprocess import DESC_DTYPE, RaggedImages
+    B = len(datas)
+    offs = np.zeros(B + 1, np.int64)
+    offs[1:] = np.cumsum([_align(len(d) + 8, 16) for d in datas])
+    staging = torch.empty(int(offs[-1]), dtype=torch.uint8)
+    if device.type == "cuda":
+        staging = staging.pin_memory()
+    host = staging.numpy()
+
+    def work(i):
+        try:
+            return scan(datas[i], host[offs[i]:offs[i + 1]])
+        except JpegRefused as e:
+            return e
+
+    with ThreadPoolExecutor(threads) as pool:
+        res = list(pool.map(work, range(B)))
+    late, dims = [], {}
+    for i in range(B):                                       # the refusals of the headers first, as the host path meets them
+        if isinstance(res[i], JpegRefused):
+            try:
+                d = query(datas[i])[0]
+                dims[i] = (d.h, d.w)
+                late.append(i)                              # refused behind the headers: the markers of the stream
+            except JpegRefused as e:
+                fall_back(i, e)
+    good = [i for i in range(B) if not isinstance(res[i], JpegRefused)]
+    table, ncoef, _, nws = layout([res[i][0] for i in good], [res[i][4] for i in good], [res[i][5] for i in good])
+    stable, segs, _, wsb = entropy_layout([res[i][1] for i in good], [res[i][3] for i in good])
+    desc = np.zeros(B, DESC_DTYPE)
+    off = 0
+    for i in range(B):
+        hh, ww = pil_pixels[i].shape[:2] if i in pil_pixels else dims[i] if i in dims else (res[i][0].h, res[i][0].w)
+        desc["h"][i], desc["w"][i], desc["offset"][i] = hh, ww, off
+        off += hh * ww * 3
+    for k, i in enumerate(good):
+        table[k].pixel_offset, stable[k].stream_offset = int(desc["offset"][i]), int(offs[i])
+    pixels = torch.empty(max(1, off), dtype=torch.uint8, device=device)
+    status = None
+    if good:
+        n = len(good)
+        parts = [np.frombuffer(table, np.uint8, n * ctypes.sizeof(_lib.JpegDesc)), np.frombuffer(stable, np.uint8, n * ctypes.sizeof(_lib.JpegScan)),
+                 segs.view(np.uint8)]
+        at = np.cumsum([0] + [_align(p.size, 16) for p in parts])
+        blob = torch.zeros(int(at[-1]), dtype=torch.uint8)
+        if device.type == "cuda":
+            blob = blob.pin_memory()
+        for a, p in zip(at, parts):
+            blob.numpy()[a:a + p.size] = p
+        streams = staging.to(device, non_blocking=True)
+        blob_dev = blob.to(device, non_blocking=True)
+        desc_dev, scan_dev, segs_dev = (blob_dev[int(a):int(a) + max(1, p.size)] for a, p in zip(at, parts))
+        coefs = torch.empty(max(8, ncoef), dtype=torch.int16, device=device)
+        work_e = torch.empty(max(16, wsb), dtype=torch.uint8, device=device)
+        work_p = torch.empty(max(16, nws), dtype=torch.uint8, device=device)
+        status = torch.empty(n, dtype=torch.int32, device=device)
+        entropy_decode_device(streams, table, desc_dev, stable, scan_dev, segs, segs_dev, n, work_e, coefs, status, bits)
+        reconstruct(coefs, table, n, pixels, work_p, table_dev=desc_dev)
+        status = status.cpu().numpy()                       # the one synchronisation
+        late = sorted(late + [good[k] for k in np.flatnonzero(status)])
+    for i in late:                                           # the host decoder has the reason (or, a third Huffman table, the coefficients)
+        try:
+            d, c = entropy_decode(datas[i])
+            one, nc, _, nw = layout([d], [c.size], [c.size])
+            one[0].pixel_offset = int(desc["offset"][i])
+            reconstruct(torch.from_numpy(c).to(device), one, 1, pixels, torch.empty(max(16, nw), dtype=torch.uint8, device=device))
+            torch.cuda.current_stream(device).synchronize()
+        except JpegRefused as e:
+            fall_back(i, e)
+            if pil_pixels[i].shape[:2] != (desc["h"][i], desc["w"][i]):
+                raise e
+    fallbacks.sort()
+    for i, a in pil_pixels.items():
+        o = int(desc["offset"][i])
+        pixels[o:o + a.size] = torch.from_numpy(a.reshape(-1)).to(device)
+    return RaggedImages(pixels[:off], desc), fallbacks
+
+
+def decode(files_or_bytes, device, threads=8, fallback="pil", entropy="host", entropy_bits=0):
     """paths or byte strings -> (RaggedImages on `device`, fallbacks): the entropy decode of every file on a pool of `threads` host
     threads (at most 16) into ONE pinned staging buffer, one copy, one reconstruction call.  A file the decoder refuses is decoded by
     PIL (`fallback="pil"`, PIL importable) and uploaded beside the others; `fallbacks` lists (index, reason) of those files.  With
-    any other `fallback`, or without PIL, the first refusal raises JpegRefused with the library's reason."""
+    any other `fallback`, or without PIL, the first refusal raises JpegRefused with the library's reason.  entropy="device": the pool
+    only removes the byte stuffing and finds the markers (ivit_jpeg_scan_host), the Huffman decode runs on the device
+    (ivit_jpeg_entropy_decode, subsequences of `entropy_bits` bits, 0 the default); pixels and fallbacks are the same."""
     import torch
     from .preprocess import DESC_DTYPE, RaggedImages
+    if entropy not in ("host", "device"):
+        raise ValueError("entropy: 'host' or 'device'")
     datas = [_read(x) for x in files_or_bytes]
     if not datas:
         raise ValueError("no images")
@@ -547,6 +734,8 @@ def decode(files_or_bytes, device, threads=8, fallback="pil"):
         pil_pixels[i] = np.array(Image.open(io.BytesIO(datas[i])).convert("RGB"))
         fallbacks.append((i, e.reason))
 
+    if entropy == "device":
+        return _decode_device(datas, device, threads, fall_back, pil_pixels, fallbacks, entropy_bits)
     for i, d in enumerate(datas):
         try:
             info[i] = query(d)

@@ -104,7 +104,7 @@ def load_share(d, labels, cfg, s_in, args, device, lo, hi):
         if getattr(args, "views", 1) != 1:
             raise SystemExit("--views is not available with --jpeg-dir")
         mine = [os.path.join(args.jpeg_dir, str(f)) for f in d["files"][lo:hi]]
-        return mine, lambda paths: eval_transform_pil(decode(paths, device, threads=args.jpeg_threads)[0], s_in, size, cfg.img_size)
+        return mine, lambda paths: eval_transform_pil(decode(paths, device, threads=args.jpeg_threads, entropy=args.jpeg_entropy)[0], s_in, size, cfg.img_size)
     if "pixels" in d.files or (args.resample == "pil" and d["images"].dtype == np.uint8):
         from ivit_amd.preprocess import DESC_DTYPE, RaggedImages, eval_transform_pil
         if "pixels" in d.files:
@@ -159,6 +159,8 @@ def main():
                     help="views per image: 1 the centre crop (default), 5 five-crop, 10 ten-crop; the mean logits are scored")
     ap.add_argument("--jpeg-dir", help="`files` of the data file are JPEG files under this directory, decoded by ivit_amd.jpeg.decode")
     ap.add_argument("--jpeg-threads", type=int, default=8, help="host threads of the entropy decode (at most 16)")
+    ap.add_argument("--jpeg-entropy", choices=("host", "device"), default="host",
+                    help="where the Huffman decode of --jpeg-dir runs: on the host threads, or on the device (include/ivit_jpeg_entropy.h)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/evaluate.py needs a HIP device; the product path has no CPU fallback")

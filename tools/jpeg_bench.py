@@ -1,9 +1,11 @@
-"""Files -> int8 [B, 3, 224, 224] in images/s, two paths on one box, interleaved (include/ivit_jpeg.h, ivit_amd/jpeg.py):
+"""Files -> int8 [B, 3, 224, 224] in images/s, three paths on one box, interleaved (include/ivit_jpeg.h, include/ivit_jpeg_entropy.h,
+ivit_amd/jpeg.py):
 
   pil      Pillow decodes every file on a pool of T threads, pack_images uploads the pixels, ivit_eval_transform_u8
   native   jpeg.decode (entropy decode on T threads, one pinned copy, the device reconstruction), ivit_eval_transform_u8
+  device   jpeg.decode(entropy="device") (the pre-pass on T threads, the Huffman decode and the reconstruction on the device), the same
 
-and, separately, the reconstruction's two launches alone against the bytes they move (coefficients in, planes out and in, pixels
+the device entropy decode's one launch alone at every subsequence size of --bits (HIP events, medians, interleaved), and, separately, the reconstruction's two launches alone against the bytes they move (coefficients in, planes out and in, pixels
 out), with the fraction of the HBM rate (--hbm-gbs, default 8000) that implies, and the host entropy decode alone per core against
 Pillow's whole decode per core.
 
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--threads", type=int, nargs="+", default=[8, 16])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--hbm-gbs", type=float, default=8000.0)
+    ap.add_argument("--bits", type=int, nargs="+", default=[128, 256, 512, 1024, 2048, 4096], help="subsequence sizes of the sweep")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/jpeg_bench.py needs a HIP device")
@@ -76,11 +79,19 @@ def main():
         torch.cuda.synchronize()
         return out
 
-    assert torch.equal(path_pil(8), path_native(8))                   # the same bytes, and both paths warm
+    def path_device(t):
+        batch, fb = J.decode(files, "cuda", threads=t, entropy="device")
+        assert not fb
+        out = pp.eval_transform_pil(batch, scale, size, crop)
+        torch.cuda.synchronize()
+        return out
+
+    want = path_pil(8)
+    assert torch.equal(want, path_native(8)) and torch.equal(want, path_device(8))     # the same bytes, and all paths warm
     for t in args.threads:
-        times = {"pil": [], "native": []}
-        for _ in range(args.rounds):                                  # interleaved: drift of the box hits both alike
-            for name, fn in (("pil", path_pil), ("native", path_native)):
+        times = {"pil": [], "native": [], "device": []}
+        for _ in range(args.rounds):                                  # interleaved: drift of the box hits all alike
+            for name, fn in (("pil", path_pil), ("native", path_native), ("device", path_device)):
                 t0 = time.perf_counter()
                 fn(t)
                 times[name].append(time.perf_counter() - t0)
@@ -103,6 +114,48 @@ def main():
         one["pil"].append(time.perf_counter() - t0)
     res["one_core_entropy_decode_images_per_s"] = round(args.images / min(one["entropy"]), 1)
     res["one_core_pil_decode_images_per_s"] = round(args.images / min(one["pil"]), 1)
+
+    # the device entropy decode alone: one launch per batch, every subsequence size in turn round by round
+    scans = [J.scan(f) for f in files]
+    dtab, nc_e, _, _ = J.layout([x[0] for x in scans], [x[4] for x in scans], [x[5] for x in scans])
+    stab, segs, nstream, wsb = J.entropy_layout([x[1] for x in scans], [x[3] for x in scans])
+    streams = np.zeros(nstream, np.uint8)
+    for k, x in enumerate(scans):
+        streams[stab[k].stream_offset:][:len(x[2])] = x[2]
+    n = len(files)
+    dev = [torch.from_numpy(a.copy()).cuda() for a in (streams, np.frombuffer(dtab, np.uint8, n * 264), np.frombuffer(stab, np.uint8, n * 6008),
+                                                       segs.view(np.uint8))]
+    e_coefs, e_work = torch.empty(nc_e, dtype=torch.int16, device="cuda"), torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    e_status = torch.empty(n, dtype=torch.int32, device="cuda")
+
+    def entropy(bits):
+        J.entropy_decode_device(dev[0], dtab, dev[1], stab, dev[2], segs, dev[3], n, e_work, e_coefs, e_status, bits)
+
+    sweep = {b: [] for b in [0] + args.bits}
+    for b in sweep:                                                   # warm, and the host decoder's coefficients at every size
+        entropy(b)
+        torch.cuda.synchronize()
+        assert not e_status.any().item()
+        got = e_coefs.cpu().numpy()
+        for k in range(0, n, max(1, n // 8)):
+            assert np.array_equal(got[dtab[k].coef_offset:][:scans[k][4]], J.entropy_decode(files[k])[1])
+    for _ in range(max(args.rounds, 5)):
+        for b in sweep:
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            entropy(b)
+            z.record()
+            torch.cuda.synchronize()
+            sweep[b].append(a.elapsed_time(z) * 1e3)
+    for b, us in sweep.items():
+        res["entropy_device_bits%d_us" % b] = round(statistics.median(us), 1)
+        res["entropy_device_bits%d_spread" % b] = round((max(us) - min(us)) / statistics.median(us), 3)
+    res["entropy_device_images_per_s"] = round(n / statistics.median(sweep[0]) * 1e6)
+    res["stream_bytes_mean"] = int(np.mean([len(x[2]) for x in scans]))
+    t0 = time.perf_counter()
+    for f in files:
+        J.scan(f)
+    res["one_core_scan_images_per_s"] = round(n / (time.perf_counter() - t0), 1)
 
     # the reconstruction alone
     table, nc, npx, nws = J.layout([i[0] for i in infos], [i[1] for i in infos], [i[2] for i in infos])
