@@ -1,11 +1,12 @@
 """Exact integer k-means over int8 features (include/ivit_cluster.h): `KMeans` owns the int8 centroids, their norms and the three
 int64 statistics of an iteration on the device; `step` is one Lloyd iteration — ivit_kmeans_assign and ivit_kmeans_accumulate per
 chunk, one ivit_kmeans_update at the end — and `fit` queues `iters` of them with no host round trip.  The seeding (`init`) runs on
-the host with exact integer distances.  `KMeansStats` is what ranks combine with ONE integer all-reduce; `contingency`, `purity`
-and `nmi` are the two numbers people quote for a clustering against labels.  The numpy statements are
+the host with exact integer distances or, with where="device", as greedy k-means++ on the device (`seed`, include/ivit_seed.h).
+`KMeansStats` is what ranks combine with ONE integer all-reduce; `contingency`, `purity` and `nmi` are the two numbers people quote for a clustering against labels.  The numpy statements are
 `predict.kmeans_assign_reference`, `kmeans_stats_reference`, `kmeans_update_reference` and `kmeans_reference`.  torch is used for
 device memory and streams only."""
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -121,14 +122,37 @@ class KMeans:
         self._handle().call("ivit_kmeans_norms", _ptr(self.centroids), self.K, self.dim, _ptr(self.cnorm))
         return self
 
-    def init(self, feat8, method="kmeans++", generator=None, init_rows=65536):
-        """seeds the centroids from the rows of feat8 (one tensor or chunks, as `step` takes them), on the HOST, with exact integer
-        distances; deterministic for a given `generator` (an np.random.Generator; default np.random.default_rng(0)).
+    def init(self, feat8, method="kmeans++", generator=None, init_rows=None, where="host", trials=None):
+        """seeds the centroids from the rows of feat8 (one tensor or chunks, as `step` takes them) with exact integer distances;
+        deterministic for a given `generator` (an np.random.Generator; default np.random.default_rng(0)).
           "sample"    K of the distinct rows, drawn without replacement
           "kmeans++"  D^2 seeding over the distinct rows of at most `init_rows` sampled rows
-        Both return K pairwise distinct rows where the sampled rows hold K distinct ones (ValueError otherwise).  Returns self."""
-        rows = np.concatenate([c.cpu().numpy() for c in _as_chunks(feat8, self.dim)] + [np.zeros((0, self.dim), np.int8)])
-        return self.set_centroids(init_centroids(rows, self.K, method, generator, init_rows))
+        where="host" (the default): every row is copied to the host and seeded there (`init_centroids`; init_rows defaults to 65536).
+        where="device" ("kmeans++" only): greedy k-means++ by `seed` with `trials` candidates per centre — a device tensor is taken
+        as it is, chunks are concatenated on the device, after the host path's row sampling where they hold more than `init_rows`
+        (default 2^22) rows.  Both return K pairwise distinct rows where the (sampled) rows hold K distinct ones (ValueError
+        otherwise).  Returns self."""
+        if where == "host":
+            rows = np.concatenate([c.cpu().numpy() for c in _as_chunks(feat8, self.dim)] + [np.zeros((0, self.dim), np.int8)])
+            return self.set_centroids(init_centroids(rows, self.K, method, generator, 65536 if init_rows is None else init_rows))
+        if where != "device" or method != "kmeans++":
+            raise ValueError(f"where = {where!r}, method = {method!r}: 'host', or 'device' with 'kmeans++'")
+        rng = np.random.default_rng(0) if generator is None else generator
+        if not isinstance(rng, np.random.Generator):
+            raise ValueError("generator must be an np.random.Generator")
+        chunks = [c.to(self.device) for c in _as_chunks(feat8, self.dim)]
+        x = chunks[0] if len(chunks) == 1 else torch.cat(chunks + [torch.zeros(0, self.dim, dtype=torch.int8, device=self.device)])
+        init_rows = 1 << 22 if init_rows is None else int(init_rows)
+        if x.shape[0] > init_rows:
+            keep = np.sort(rng.choice(int(x.shape[0]), size=init_rows, replace=False))
+            x = x[torch.from_numpy(keep).to(self.device)]
+        out = _seed(self._handle(), x, self.K, trials, rng)
+        picked = int(out["picked"].item())
+        if picked < self.K:
+            raise ValueError(f"{picked} distinct rows among the {x.shape[0]} sampled: fewer than K = {self.K}")
+        self.centroids.copy_(out["cent"])
+        self.cnorm.copy_(out["cnorm"])
+        return self
 
     # ---- the launches
     def _on_device(self, chunk):
@@ -251,6 +275,63 @@ def init_centroids(rows, K, method="kmeans++", generator=None, init_rows=65536):
         picked.append(j)
         d = np.minimum(d, _dist2_to(c32, xx, cand[j]))
     return np.ascontiguousarray(cand[picked])
+
+
+# ---------------------------------------------------------------- the device seeding (include/ivit_seed.h)
+MAX_TRIALS = 32                                        # SEED_MAX_TRIALS of csrc/ivit_seed.h
+
+
+def default_trials(K):
+    """2 + floor(ln K), scikit-learn's number of candidates per centre, capped at the 32 a launch evaluates at once"""
+    return min(MAX_TRIALS, 2 + int(math.floor(math.log(int(K)))))
+
+
+def seed_draws(rows, K, trials, generator):
+    """the random input of a seeding: (first, draws uint64 [K, trials]) from the generator, in this order"""
+    first = int(generator.integers(int(rows)))
+    return first, generator.integers(0, 2 ** 64, size=(int(K), int(trials)), dtype=np.uint64)
+
+
+def _seed(handle, feat8, K, trials, rng):
+    """one ivit_kmeans_seed on the handle's stream over a contiguous int8 device tensor: every output of the entry, on the device"""
+    if not isinstance(feat8, torch.Tensor) or feat8.dtype != torch.int8 or feat8.dim() != 2 or not feat8.is_cuda or not feat8.is_contiguous():
+        raise ValueError("feat8: a contiguous int8 device tensor [rows, dim]")
+    rows, dim, K = int(feat8.shape[0]), int(feat8.shape[1]), int(K)
+    trials = default_trials(K) if trials is None else int(trials)
+    if rows < 1:
+        raise ValueError("feat8 holds no row")
+    first, draws = seed_draws(rows, K, trials, rng)
+    nbytes = ctypes.c_size_t(0)
+    st = handle.lib.ivit_kmeans_seed_workspace_bytes(rows, dim, trials, ctypes.byref(nbytes))
+    if st != 0:
+        raise _lib.IvitError(f"ivit_kmeans_seed_workspace_bytes(rows={rows}, dim={dim}, trials={trials}): {handle.lib.ivit_status_string(st).decode()}")
+    dev = feat8.device
+    out = {"cent": torch.empty(K, dim, dtype=torch.int8, device=dev), "cnorm": torch.empty(K, dtype=torch.int32, device=dev),
+           "idx": torch.empty(K, dtype=torch.int32, device=dev), "potential": torch.empty(K, dtype=torch.int64, device=dev),
+           "picked": torch.empty(1, dtype=torch.int32, device=dev)}
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    d = torch.from_numpy(draws.view(np.int64)).to(dev)                  # the same 64 bits
+    handle.call("ivit_kmeans_seed", _ptr(feat8), rows, dim, K, trials, first, _ptr(d), _ptr(ws), nbytes.value, _ptr(out["cent"]),
+                _ptr(out["cnorm"]), _ptr(out["idx"]), _ptr(out["potential"]), _ptr(out["picked"]))
+    for t in (ws, d):
+        t.record_stream(torch.cuda.current_stream(dev))                 # freed here, read by the queued launches
+    return out
+
+
+def seed(feat8, K, trials=None, generator=None):
+    """greedy k-means++ seeding of K centres from the rows of feat8 (a contiguous int8 device tensor [rows, dim]) ON THE DEVICE, as
+    `predict.kmeans_seed_reference` states it: `trials` candidates per centre (None: `default_trials(K)`; 1 is plain k-means++),
+    `first` and the draws from `generator` (an np.random.Generator; default np.random.default_rng(0)) by `seed_draws`.  Queued on the
+    current stream, nothing synchronised.  Returns (idx int32 [K], cent8 int8 [K, dim], potential int64 [K]) on the device; where
+    the rows hold fewer than K distinct ones, idx is -1 from the first centre that could not be drawn."""
+    rng = np.random.default_rng(0) if generator is None else generator
+    if not isinstance(rng, np.random.Generator):
+        raise ValueError("generator must be an np.random.Generator")
+    if not isinstance(feat8, torch.Tensor) or not feat8.is_cuda:
+        raise ValueError("feat8: a contiguous int8 device tensor [rows, dim]")
+    h = _lib.Handle(feat8.device.index, torch.cuda.current_stream(feat8.device).cuda_stream)
+    out = _seed(h, feat8, K, trials, rng)
+    return out["idx"], out["cent"], out["potential"]
 
 
 # ---------------------------------------------------------------- a clustering against labels

@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -46,6 +46,7 @@
 #include "ivit_jpeg.h"
 #include "ivit_jpeg_scan_host.h"
 #include "ivit_jpeg_entropy.h"
+#include "ivit_seed.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -3132,6 +3133,98 @@ extern "C" int ivit_range_fill(ivit_handle h, const int8_t *query, int nq, const
     a.idx = idx; a.val = val; a.capacity = capacity;
     range_scan_dispatch<true>(h, dim, a);
     LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- k-means++ seeding (include/ivit_seed.h)
+// the workspace: the state, xx and mind (int32 per row, each padded to 16 bytes) and the part table (32 int64 per part)
+struct SeedLayout {
+    int parts;
+    size_t xx, mind, tab, bytes;    // byte offsets of the three arrays; the whole
+};
+// the limits both entries share; nullptr where the shape is fine, else the message; *unsupported: the refusal is the dim's
+static const char *seed_shape_bad(long long rows, int dim, int trials, bool *unsupported, SeedLayout *l) {
+    *unsupported = false;
+    if (rows < 1 || rows > 0x7fffffffLL) return "rows must be in 1 .. 2^31 - 1";
+    if (trials < 1 || trials > SEED_MAX_TRIALS) return "trials must be in 1 .. 32";
+    if (dim < KMEANS_MIN_DIM || dim > KMEANS_MAX_DIM || (dim % 64) != 0) {
+        *unsupported = true;
+        return "dim must be a multiple of 64 in 64 .. 1024";
+    }
+    const size_t per_row = ((size_t)rows * 4 + 15) & ~(size_t)15;
+    l->parts = (int)((rows + SEED_PART - 1) / SEED_PART);
+    l->xx = SEED_STATE_BYTES;
+    l->mind = l->xx + per_row;
+    l->tab = l->mind + per_row;
+    l->bytes = l->tab + (size_t)l->parts * SEED_MAX_TRIALS * 8;
+    return nullptr;
+}
+
+extern "C" int ivit_kmeans_seed_workspace_bytes(int64_t rows, int dim, int trials, size_t *bytes) {
+    bool unsupported;
+    SeedLayout l;
+    if (!bytes) return IVIT_ERR_INVALID;
+    if (seed_shape_bad(rows, dim, trials, &unsupported, &l)) return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
+    *bytes = l.bytes;
+    return IVIT_OK;
+}
+
+template <int KS>
+static void seed_scan_launch(ivit_handle h, const SeedArgs &a) {
+    seed_scan_kernel<KS, (KS <= KMEANS_PF_MAX_KS)><<<(unsigned)a.parts, 64, 0, h->stream>>>(a);
+}
+
+extern "C" int ivit_kmeans_seed(ivit_handle h, const int8_t *x, int64_t rows, int dim, int K, int trials, int64_t first, const uint64_t *draws,
+                                void *workspace, size_t workspace_bytes, int8_t *cent, int32_t *cnorm, int32_t *idx, int64_t *potential,
+                                int32_t *picked) {
+    CHECK_H(h);
+    REQUIRE(h, x && draws && workspace && cent && cnorm && idx && potential && picked,
+            "x, draws, workspace, cent, cnorm, idx, potential or picked is null");
+    bool unsupported;
+    SeedLayout l;
+    if (const char *bad = seed_shape_bad(rows, dim, trials, &unsupported, &l)) {
+        snprintf(h->err, sizeof(h->err), "%s: %s", __func__, bad);
+        return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
+    }
+    REQUIRE(h, K >= 1 && K <= KMEANS_MAX_K, "K must be in 1 .. 16384");
+    REQUIRE(h, first >= 0 && first < rows, "first must be a row: 0 <= first < rows");
+    REQUIRE(h, workspace_bytes >= l.bytes, "workspace too small (ivit_kmeans_seed_workspace_bytes)");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, workspace, "workspace");
+    REQUIRE_A16(h, cent, "cent");
+    REQUIRE_ALIGNED(h, draws, "draws", 8);
+    REQUIRE_ALIGNED(h, potential, "potential", 8);
+    REQUIRE_ALIGNED(h, cnorm, "cnorm", 4);
+    REQUIRE_ALIGNED(h, idx, "idx", 4);
+    REQUIRE_ALIGNED(h, picked, "picked", 4);
+    {
+        const struct { const void *p; size_t n; const char *name; } ins[2] = {{x, (size_t)rows * dim, "x"}, {draws, (size_t)K * trials * 8, "draws"}},
+            outs[6] = {{workspace, workspace_bytes, "workspace"}, {cent, (size_t)K * dim, "cent"}, {cnorm, (size_t)K * 4, "cnorm"},
+                       {idx, (size_t)K * 4, "idx"}, {potential, (size_t)K * 8, "potential"}, {picked, 4, "picked"}};
+        for (const auto &i : ins)
+            for (const auto &o : outs) REQUIRE_DISJOINT(h, i.p, i.n, i.name, o.p, o.n, o.name, OVL_IN);
+        for (int i = 0; i < 6; ++i)
+            for (int j = i + 1; j < 6; ++j) REQUIRE_DISJOINT(h, outs[i].p, outs[i].n, outs[i].name, outs[j].p, outs[j].n, outs[j].name, OVL_OUT);
+    }
+    SeedArgs a;
+    char *ws = (char *)workspace;
+    a.x = x; a.draws = (const unsigned long long *)draws;
+    a.st = (SeedState *)ws; a.xx = (int *)(ws + l.xx); a.mind = (int *)(ws + l.mind); a.tab = (unsigned long long *)(ws + l.tab);
+    a.cent = cent; a.cnorm = cnorm; a.idx = idx; a.potential = (unsigned long long *)potential; a.picked = picked;
+    a.rows = rows; a.parts = l.parts; a.dim = dim; a.K = K; a.L = trials; a.first = (int)first;
+    seed_setup_kernel<<<(unsigned)std::min((long long)((rows + 15) / 16), (long long)SEED_SETUP_MAX_BLOCKS), 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    for (int s = 0; s < K; ++s) {
+        switch (dim / 64) {
+#define SEED_CASE(KS) case KS: seed_scan_launch<KS>(h, a); break;
+            SEED_CASE(1) SEED_CASE(2) SEED_CASE(3) SEED_CASE(4) SEED_CASE(5) SEED_CASE(6) SEED_CASE(7) SEED_CASE(8)
+            SEED_CASE(9) SEED_CASE(10) SEED_CASE(11) SEED_CASE(12) SEED_CASE(13) SEED_CASE(14) SEED_CASE(15) SEED_CASE(16)
+#undef SEED_CASE
+        }
+        seed_pick_kernel<<<1, 256, 0, h->stream>>>(a, s);
+        if (s + 1 < K) seed_locate_kernel<<<(unsigned)trials, 256, 0, h->stream>>>(a, s);
+        LAUNCH_CHECK(h);
+    }
     return IVIT_OK;
 }
 

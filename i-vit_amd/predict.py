@@ -661,14 +661,55 @@ def kmeans_reference(x8, cent0, iters):
     return cent, assign, np.asarray(history, np.int64)
 
 
+def kmeans_seed_reference(x, K, first, draws):
+    """x int8 [rows, dim], K, `first` a row index, draws uint64 [K, trials] (row 0 unused) -> (idx int32 [K], cent int8 [K, dim], cnorm
+    int32 [K], potential int64 [K], picked int32 [1]): greedy k-means++ as include/ivit_seed.h defines it and `ivit_kmeans_seed`
+    computes it.  Step s draws `trials` candidates by D^2 — t = (draw * total) >> 64 in Python integers, the candidate the first row
+    whose running sum of `mind` exceeds t — and keeps the lowest candidate of the smallest new potential.  When the potential is 0
+    after p < K centres, picked = p, idx[p:] = -1, potential[p:] = 0 and cent[p:], cnorm[p:] are zeros here (the entry leaves them
+    unwritten).  The distances go through an fp64 product, which is exact: |dot| < 2^24."""
+    x, draws, K, first = np.asarray(x), np.asarray(draws), int(K), int(first)
+    assert x.ndim == 2 and x.dtype == np.int8 and draws.dtype == np.uint64 and draws.ndim == 2 and draws.shape[0] == K and 0 <= first < len(x)
+    xf = x.astype(np.float64)
+    xx = (x.astype(np.int64) ** 2).sum(axis=1)
+
+    def dist(j):
+        return xx - 2 * (xf @ xf[j]).astype(np.int64) + xx[j]
+    idx, potential, picked = np.full(K, -1, np.int32), np.zeros(K, np.int64), K
+    mind = dist(first)
+    idx[0], potential[0] = first, mind.sum()
+    for s in range(1, K):
+        total = int(potential[s - 1])
+        if total == 0:
+            picked = s
+            break
+        cum, best = np.cumsum(mind), None
+        for l in range(draws.shape[1]):
+            t = (int(draws[s, l]) * total) >> 64
+            c = int(np.searchsorted(cum, t, side="right"))
+            pot = int(np.minimum(mind, dist(c)).sum())
+            if best is None or pot < best[0]:                           # strictly smaller: ties stay with the lower l
+                best = (pot, c)
+        potential[s], idx[s] = best
+        mind = np.minimum(mind, dist(best[1]))
+    cent, cnorm = np.zeros((K, x.shape[1]), np.int8), np.zeros(K, np.int32)
+    cent[:picked] = x[idx[:picked]]
+    cnorm[:picked] = xx[idx[:picked]]
+    return idx, cent, cnorm, potential, np.array([picked], np.int32)
+
+
 def kmeans_fit(engine, batches, K, iters=20, init="kmeans++", generator=None, transform=None):
     """`embed8` followed by `cluster.KMeans.fit`: the int8 features of the whole dataset are kept on the device (rows x num_features
-    bytes), the centroids seeded on the host by `init` ("sample" or "kmeans++") with `generator` (default: np.random.default_rng(0)),
-    then `iters` Lloyd iterations of three launches each.  Returns (kmeans, feat8, inertia_history)."""
+    bytes), the centroids seeded by `init` with `generator` (default: np.random.default_rng(0)) — "sample" or "kmeans++" on the host,
+    "kmeans++/device" by the greedy device seeding (`KMeans.init(where="device")`: no copy of the rows to the host) — then `iters`
+    Lloyd iterations of three launches each.  Returns (kmeans, feat8, inertia_history)."""
     from .cluster import KMeans
     feat8, _ = embed8(engine, batches, transform)
     km = KMeans(int(K), int(engine.num_features), feat8.device)
-    km.init(feat8, method=init, generator=generator)
+    if init == "kmeans++/device":
+        km.init(feat8, method="kmeans++", generator=generator, where="device")
+    else:
+        km.init(feat8, method=init, generator=generator)
     return km, feat8, km.fit(feat8, iters=iters)
 
 

@@ -4,8 +4,8 @@
     python tools/kmeans.py data.npz --model-file deit_small.ivit --k 1000 --out clusters.npz --seed 3
 
 data.npz and the model are given as to tools/embed.py (the same loading code); `labels` is optional.  The images are embedded once
-(`predict.kmeans_fit`: the int8 features of the dataset are kept on the device), the centroids seeded by --init on the host from
---seed, then --iters Lloyd iterations of three launches each.  Writes to --out
+(`predict.kmeans_fit`: the int8 features of the dataset are kept on the device), the centroids seeded by --init from --seed (on the host;
+`kmeans++/device` seeds on the device), then --iters Lloyd iterations of three launches each.  Writes to --out
   centroids  int8 [K, num_features]     after the last update
   assign     int32 [N]                  every image's nearest centroid (against those centroids)
   dist2      int32 [N]                  its exact squared distance, in units of the features' scale squared
@@ -30,7 +30,8 @@ def main():
     add_input_arguments(ap)
     ap.add_argument("--k", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--init", choices=("kmeans++", "sample"), default="kmeans++")
+    ap.add_argument("--init", choices=("kmeans++", "sample", "kmeans++/device"), default="kmeans++",
+                    help="kmeans++/device: greedy k-means++ on the device (include/ivit_seed.h), no copy of the features to the host")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", required=True, help="the .npz to write")
     args = ap.parse_args()
