@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -47,6 +47,7 @@
 #include "ivit_jpeg_scan_host.h"
 #include "ivit_jpeg_entropy.h"
 #include "ivit_seed.h"
+#include "ivit_logreg.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -3225,6 +3226,115 @@ extern "C" int ivit_kmeans_seed(ivit_handle h, const int8_t *x, int64_t rows, in
         if (s + 1 < K) seed_locate_kernel<<<(unsigned)trials, 256, 0, h->stream>>>(a, s);
         LAUNCH_CHECK(h);
     }
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- logistic-regression probe (include/ivit_logreg.h)
+// the workspace: the weight pieces, the rows' records, the parts' partial gradients and bias sums (each a multiple of 16 bytes)
+struct LogregLayout {
+    int tiles, parts;
+    long long per;
+    size_t rowst, pW, pb, bytes;    // byte offsets behind the pieces; the whole
+};
+// the limits both entries share; nullptr where the shape is fine, else the message; *unsupported: the refusal is the dim's.
+// cus > 0: the parts of a launch on that many CUs; cus == 0 (the size query): the most parts any device is given
+static const char *logreg_shape_bad(long long N, int dim, int C, int splits, long long cus, bool *unsupported, LogregLayout *l) {
+    *unsupported = false;
+    if (C < 2 || C > LOGREG_MAX_CLASSES) return "C must be in 2 .. 65536";
+    if (splits < 0 || splits > 4096) return "splits must be in 0 .. 4096";
+    if (dim < LOGREG_MIN_DIM || dim > LOGREG_MAX_DIM || (dim % 64) != 0) {
+        *unsupported = true;
+        return "dim must be a multiple of 64 in 64 .. 1024";
+    }
+    if (N < 1 || N >= (1LL << 40) / dim || N >= (1LL << 40) / C) return "N must be at least 1 with N * dim and N * C below 2^40";
+    l->tiles = (C + LOGREG_TILE - 1) / LOGREG_TILE;
+    // the library's choice: about two workgroups per CU over the class tiles, parts of at least 256 rows; never more than 1024 CUs' worth
+    const long long want = splits > 0 ? splits : std::max(1LL, std::min((2 * std::min(cus > 0 ? cus : 1024LL, 1024LL) + l->tiles - 1) / l->tiles, N / 256));
+    const long long s = std::max(want, (N + LOGREG_FLUSH_ROWS - 1) / LOGREG_FLUSH_ROWS);
+    l->per = ((N + s - 1) / s + LOGREG_TILE - 1) / LOGREG_TILE * LOGREG_TILE;
+    l->parts = (int)(cus > 0 || splits > 0 ? (N + l->per - 1) / l->per : s);
+    const size_t cpad = (size_t)l->tiles * LOGREG_TILE;
+    l->rowst = cpad * dim * 2 * LOGREG_PIECES;
+    l->pW = l->rowst + (size_t)N * LOGREG_ROW_BYTES;
+    l->pb = l->pW + (size_t)l->parts * cpad * dim * 4;
+    l->bytes = l->pb + (size_t)l->parts * cpad * 4;
+    return nullptr;
+}
+
+extern "C" int ivit_logreg_workspace_bytes(int64_t N, int dim, int C, int splits, size_t *bytes) {
+    bool unsupported;
+    LogregLayout l;
+    if (!bytes) return IVIT_ERR_INVALID;
+    if (logreg_shape_bad(N, dim, C, splits, 0, &unsupported, &l)) return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
+    *bytes = l.bytes;
+    return IVIT_OK;
+}
+
+template <int NT>
+static void logreg_grad_launch(ivit_handle h, const LogregArgs &a) {
+    logreg_grad_kernel<NT><<<dim3((unsigned)a.tiles, (unsigned)a.parts), 256, 0, h->stream>>>(a);
+}
+
+extern "C" int ivit_logreg_loss_grad(ivit_handle h, const int8_t *feat8, const int32_t *labels, int64_t N, int dim, const float *W, const float *b,
+                                     int C, float x_scale, int splits, void *workspace, size_t workspace_bytes, double *loss, float *grad_W,
+                                     float *grad_b, int64_t *correct) {
+    CHECK_H(h);
+    REQUIRE(h, feat8 && labels && W && b && workspace && loss && grad_W && grad_b && correct,
+            "feat8, labels, W, b, workspace, loss, grad_W, grad_b or correct is null");
+    bool unsupported;
+    LogregLayout l, most;
+    if (const char *bad = logreg_shape_bad(N, dim, C, splits, persistent_cus(h), &unsupported, &l)) {
+        snprintf(h->err, sizeof(h->err), "%s: %s", __func__, bad);
+        return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
+    }
+    (void)logreg_shape_bad(N, dim, C, splits, 0, &unsupported, &most);   // what the size query states: never less than this launch needs
+    REQUIRE(h, std::isfinite(x_scale), "x_scale must be finite");
+    REQUIRE(h, workspace_bytes >= most.bytes, "workspace too small (ivit_logreg_workspace_bytes)");
+    REQUIRE_A16(h, feat8, "feat8");
+    REQUIRE_A16(h, W, "W");
+    REQUIRE_A16(h, grad_W, "grad_W");
+    REQUIRE_A16(h, workspace, "workspace");
+    REQUIRE_ALIGNED(h, loss, "loss", 8);
+    REQUIRE_ALIGNED(h, correct, "correct", 8);
+    REQUIRE_ALIGNED(h, labels, "labels", 4);
+    REQUIRE_ALIGNED(h, b, "b", 4);
+    REQUIRE_ALIGNED(h, grad_b, "grad_b", 4);
+    {
+        const struct { const void *p; size_t n; const char *name; } ins[4] = {{feat8, (size_t)N * dim, "feat8"}, {labels, (size_t)N * 4, "labels"},
+                                                                              {W, (size_t)C * dim * 4, "W"}, {b, (size_t)C * 4, "b"}},
+            outs[5] = {{workspace, workspace_bytes, "workspace"}, {loss, 8, "loss"}, {grad_W, (size_t)C * dim * 4, "grad_W"},
+                       {grad_b, (size_t)C * 4, "grad_b"}, {correct, 16, "correct"}};
+        for (const auto &i : ins)
+            for (const auto &o : outs) REQUIRE_DISJOINT(h, i.p, i.n, i.name, o.p, o.n, o.name, OVL_IN);
+        for (int i = 0; i < 5; ++i)
+            for (int j = i + 1; j < 5; ++j) REQUIRE_DISJOINT(h, outs[i].p, outs[i].n, outs[i].name, outs[j].p, outs[j].n, outs[j].name, OVL_OUT);
+    }
+    const long long row_blocks = (N + LOGREG_RB - 1) / LOGREG_RB;
+    REQUIRE_LAUNCH(h, row_blocks, 256, LOGREG_RB);
+    LogregArgs a;
+    char *ws = (char *)workspace;
+    a.x = feat8; a.labels = labels; a.W = W; a.b = b;
+    a.wp = (v4i *)ws; a.rowst = (v4f *)(ws + l.rowst); a.pW = (float *)(ws + l.pW); a.pb = (float *)(ws + l.pb);
+    a.loss = loss; a.gW = grad_W; a.gb = grad_b; a.correct = (long long *)correct;
+    a.N = N; a.per = l.per; a.dim = dim; a.C = C; a.tiles = l.tiles; a.parts = l.parts; a.xs = x_scale;
+    logreg_pieces_kernel<<<(unsigned)(((long long)l.tiles * (dim / 32) * 64 + 255) / 256), 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    switch (dim / 64) {
+#define LOGREG_CASE(KS) case KS: logreg_rows_kernel<KS><<<(unsigned)row_blocks, 256, 0, h->stream>>>(a); break;
+        LOGREG_CASE(1) LOGREG_CASE(2) LOGREG_CASE(3) LOGREG_CASE(4) LOGREG_CASE(5) LOGREG_CASE(6) LOGREG_CASE(7) LOGREG_CASE(8)
+        LOGREG_CASE(9) LOGREG_CASE(10) LOGREG_CASE(11) LOGREG_CASE(12) LOGREG_CASE(13) LOGREG_CASE(14) LOGREG_CASE(15) LOGREG_CASE(16)
+#undef LOGREG_CASE
+    }
+    LAUNCH_CHECK(h);
+    switch ((dim / 32 + 3) / 4) {                                       // feature tiles of a wavefront of the gradient pass
+#define LOGREG_CASE(NT) case NT: logreg_grad_launch<NT>(h, a); break;
+        LOGREG_CASE(1) LOGREG_CASE(2) LOGREG_CASE(3) LOGREG_CASE(4) LOGREG_CASE(5) LOGREG_CASE(6) LOGREG_CASE(7) LOGREG_CASE(8)
+#undef LOGREG_CASE
+    }
+    LAUNCH_CHECK(h);
+    const unsigned nw = (unsigned)(((size_t)C * dim + 255) / 256), nb = (unsigned)((C + 255) / 256);
+    logreg_reduce_kernel<<<nw + nb + 1, 256, 0, h->stream>>>(a, nw, nb);
+    LAUNCH_CHECK(h);
     return IVIT_OK;
 }
 

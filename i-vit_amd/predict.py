@@ -571,12 +571,22 @@ def probe_fit_reference(gram, class_sum, count, ridge=1e-3):
     return V, b
 
 
-def probe_fit(engine, batches, num_classes, ridge=1e-3, transform=None, stats=None):
+def probe_fit(engine, batches, num_classes, ridge=1e-3, transform=None, stats=None, method="ridge", l2=1e-4, iters=100):
     """`embed`'s loop over (images, labels) ending in `probe.fit`: every batch is one engine.probe_accumulate — `features` without the
     head, then ivit_probe_accumulate on the same stream; no feature is kept and nothing inside the loop synchronises.  Returns the
     Head for `engine.with_head`.  `stats`: the caller's own ProbeStats to add into — it then holds the statistics afterwards, from
-    which `probe.fit` refits with another ridge without a second pass."""
-    from .probe import ProbeStats, fit
+    which `probe.fit` refits with another ridge without a second pass.
+    method="logistic": multinomial logistic regression instead (`probe.fit_logistic` with `l2` and `iters`; `ridge` and `stats` are
+    not used).  An iterative fit reads the features many times, so they are embedded first (`embed8`) and kept on the device: one
+    int8 row per image."""
+    from .probe import ProbeStats, fit, fit_logistic
+    if method == "logistic":
+        items = list(batches)
+        feat8, scale = embed8(engine, items, transform)
+        labels = torch.cat([torch.as_tensor(lab).to(device=engine.device, dtype=torch.int64).reshape(-1) for _, lab in items])
+        return fit_logistic(feat8, labels, num_classes, scale, l2=l2, iters=iters)
+    if method != "ridge":
+        raise ValueError(f"method = {method!r}: 'ridge' or 'logistic'")
     if stats is None:
         stats = ProbeStats(engine.num_features, num_classes, engine.device)
     for images, labels in batches:
@@ -585,6 +595,26 @@ def probe_fit(engine, batches, num_classes, ridge=1e-3, transform=None, stats=No
         labels = torch.as_tensor(labels).to(device=engine.device, dtype=torch.int64, non_blocking=True).reshape(-1)
         engine.probe_accumulate(images, labels, stats)
     return fit(stats, engine.feature_scale_host(), ridge)
+
+
+def logreg_reference(feat8, labels, W, b, x_scale):
+    """feat8 int8 [N, dim], labels integers [N], W [C, dim], b [C], x_scale -> (loss float64, grad_W float64 [C, dim], grad_b float64
+    [C], correct int64 [2]): the outputs of `ivit_logreg_loss_grad` (include/ivit_logreg.h) in float64.  z = x_scale (x W^T) + b over
+    the rows with 0 <= label < C; loss the SUM of logsumexp(z) - z[label]; grad_W = (softmax(z) - onehot)^T x, grad_b its column sums;
+    correct = (the counted rows, those whose first largest logit is the label's)."""
+    x, lab = np.asarray(feat8), np.asarray(labels).astype(np.int64).reshape(-1)
+    W, b = np.asarray(W, np.float64), np.asarray(b, np.float64)
+    assert x.ndim == 2 and x.dtype == np.int8 and lab.shape == (x.shape[0],) and W.shape == (len(b), x.shape[1])
+    keep = (lab >= 0) & (lab < len(b))
+    x, lab = x[keep].astype(np.float64), lab[keep]
+    z = np.float64(np.float32(x_scale)) * (x @ W.T) + b
+    m = z.max(axis=1, keepdims=True) if len(lab) else np.zeros((0, 1))
+    e = np.exp(z - m)
+    lse = m[:, 0] + np.log(e.sum(axis=1))
+    g = e / e.sum(axis=1, keepdims=True)
+    g[np.arange(len(lab)), lab] -= 1.0
+    correct = np.array([len(lab), int((z.argmax(axis=1) == lab).sum()) if len(lab) else 0], np.int64)
+    return np.float64((lse - z[np.arange(len(lab)), lab]).sum()), g.T @ x, g.sum(axis=0), correct
 
 
 # ---------------------------------------------------------------- k-means (include/ivit_cluster.h, ivit_amd/cluster.py)

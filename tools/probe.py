@@ -4,6 +4,10 @@ fit of the new classes on the host (ivit_amd.probe.fit), `engine.with_head`, `sa
 
     python tools/probe.py train.npz --model deit_tiny --golden tests/golden/deit_tiny_b1.npz --classes 37 --out pets.ivit
     python tools/probe.py train.npz --model-file deit_small.ivit --classes 10 --out new.ivit --ridge 1e-2 --eval val.npz
+    python tools/probe.py train.npz --model-file deit_small.ivit --classes 10 --out new.ivit --method logistic --l2 1e-4 --iters 100
+
+--method logistic fits multinomial logistic regression instead (the int8 features are stored on the device, one row per image, and
+every L-BFGS evaluation is one ivit_logreg_loss_grad); its JSON line also holds the fit's iterations, objective and train accuracy.
 
 train.npz and the model are given as to tools/embed.py and tools/evaluate.py (the same loading code: int8 model inputs, uint8
 [N, H, W, 3] images or a packed ragged file; --golden, --state-dict or --model-file); `labels` [N] are the NEW classes, a label outside
@@ -40,6 +44,10 @@ def main():
     ap.add_argument("--classes", type=int, required=True, help="number of new classes")
     ap.add_argument("--out", required=True, help="the model file to write")
     ap.add_argument("--ridge", type=float, default=1e-3, help="relative to the mean feature variance")
+    ap.add_argument("--method", choices=["ridge", "logistic"], default="ridge",
+                    help="logistic: multinomial logistic regression by L-BFGS over the stored int8 features (ivit_amd.probe.fit_logistic)")
+    ap.add_argument("--l2", type=float, default=1e-4, help="logistic: the weight of |W|^2 / 2 beside the mean loss")
+    ap.add_argument("--iters", type=int, default=100, help="logistic: L-BFGS iterations at most")
     ap.add_argument("--eval", help="a data file to evaluate the new engine on")
     ap.add_argument("--topk", type=int, nargs="+", default=[1, 5])
     args = ap.parse_args()
@@ -49,11 +57,15 @@ def main():
     cfg, eng, s_in = build_engine(args, device)
     batches, transform, n = batches_of(args.data, cfg, s_in, args, device)
     stats = ProbeStats(eng.num_features, args.classes, device)
-    head = probe_fit(eng, batches, args.classes, ridge=args.ridge, transform=transform, stats=stats)
+    head = probe_fit(eng, batches, args.classes, ridge=args.ridge, transform=transform, stats=stats, method=args.method, l2=args.l2,
+                     iters=args.iters)
     new = eng.with_head(head)
     new.save(args.out)
-    print(json.dumps({"n": int(n), "used": int(stats.count.sum().item()), "classes": int(args.classes), "ridge": args.ridge, "model": args.model,
-                      "out": args.out}))
+    used = head.fit_info["n"] if args.method == "logistic" else int(stats.count.sum().item())
+    line = {"n": int(n), "used": used, "classes": int(args.classes), "ridge": args.ridge, "model": args.model, "out": args.out}
+    if args.method == "logistic":
+        line.update(method="logistic", l2=args.l2, **{k: head.fit_info[k] for k in ("iterations", "evaluations", "objective", "grad_norm", "train_acc")})
+    print(json.dumps(line))
     if args.eval:
         batches, transform, _ = batches_of(args.eval, cfg, s_in, args, device)
         out = evaluate(new, batches, topk=args.topk, transform=transform)
