@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -48,6 +48,7 @@
 #include "ivit_jpeg_entropy.h"
 #include "ivit_seed.h"
 #include "ivit_logreg.h"
+#include "ivit_gauss.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -3334,6 +3335,141 @@ extern "C" int ivit_logreg_loss_grad(ivit_handle h, const int8_t *feat8, const i
     LAUNCH_CHECK(h);
     const unsigned nw = (unsigned)(((size_t)C * dim + 255) / 256), nb = (unsigned)((C + 255) / 256);
     logreg_reduce_kernel<<<nw + nb + 1, 256, 0, h->stream>>>(a, nw, nb);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- novelty scores (include/ivit_gauss.h)
+// the prepared model: the pieces, then the vector; the workspace: the whitening tiles' partials, the parts' best values and classes
+struct GaussLayout {
+    int qtiles, tiles, per, parts;
+    size_t vec, model_bytes;        // the vector's byte offset in the model; the whole model
+    size_t pbest, pcls, bytes;      // byte offsets in the workspace behind qpart; the whole workspace
+};
+// the limits the four entries share; nullptr where the shape is fine, else the message; *unsupported: the refusal is the dim's.
+// N == 0: the model's side only.  cus > 0: the parts of a launch on that many CUs; cus == 0 (the size query): the most parts any
+// device is given.  The library's choice: cut the table until the grid holds about two workgroups per CU (never more than 1024
+// CUs' worth) — 256 rows are two row blocks, so the table falls into single tiles; from 2 cus row blocks on there is one part
+static const char *gauss_shape_bad(long long N, int dim, int R, int C, int splits, long long cus, bool *unsupported, GaussLayout *l) {
+    *unsupported = false;
+    if (dim < GAUSS_MIN_DIM || dim > GAUSS_MAX_DIM || (dim % 64) != 0) {
+        *unsupported = true;
+        return "dim must be a multiple of 64 in 64 .. 1024";
+    }
+    if (R < GAUSS_TILE || R > dim || (R % GAUSS_TILE) != 0) return "R must be a multiple of 32 in 32 .. dim";
+    if (C < 1 || C > GAUSS_MAX_CLASSES) return "C must be in 1 .. 65536";
+    l->qtiles = R / GAUSS_TILE;
+    l->tiles = l->qtiles + (C + GAUSS_TILE - 1) / GAUSS_TILE;
+    l->vec = (size_t)l->tiles * GAUSS_TILE * dim * 2 * LOGREG_PIECES;
+    l->model_bytes = l->vec + (size_t)l->tiles * GAUSS_TILE * 4;
+    if (N == 0) return nullptr;
+    if (N < 1 || N > 0x7fffffffLL) return "N must be in 1 .. 2^31 - 1";
+    if (splits < 0 || splits > GAUSS_MAX_SPLITS) return "splits must be in 0 .. 256";
+    const long long row_blocks = (N + GAUSS_RB - 1) / GAUSS_RB;
+    const long long want = splits > 0 ? splits : std::min((long long)GAUSS_MAX_SPLITS, (2 * std::min(cus > 0 ? cus : 1024LL, 1024LL) + row_blocks - 1) / row_blocks);
+    l->per = (int)((l->tiles + std::min(want, (long long)l->tiles) - 1) / std::min(want, (long long)l->tiles));
+    l->parts = (l->tiles + l->per - 1) / l->per;
+    const size_t n16 = ((size_t)N * 4 + 15) / 16 * 16;                  // one float or int per row, each array 16-byte aligned
+    l->pbest = (size_t)l->qtiles * n16;
+    l->pcls = l->pbest + (size_t)l->parts * n16;
+    l->bytes = l->pcls + (size_t)l->parts * n16;
+    return nullptr;
+}
+
+extern "C" int ivit_gauss_model_bytes(int dim, int R, int C, size_t *bytes) {
+    bool unsupported;
+    GaussLayout l;
+    if (!bytes) return IVIT_ERR_INVALID;
+    if (gauss_shape_bad(0, dim, R, C, 0, 0, &unsupported, &l)) return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
+    *bytes = l.model_bytes;
+    return IVIT_OK;
+}
+
+extern "C" int ivit_gauss_workspace_bytes(int64_t N, int dim, int R, int C, int splits, size_t *bytes) {
+    bool unsupported;
+    GaussLayout l;
+    if (!bytes || N == 0) return IVIT_ERR_INVALID;
+    if (gauss_shape_bad(N, dim, R, C, splits, 0, &unsupported, &l)) return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
+    *bytes = l.bytes;
+    return IVIT_OK;
+}
+
+extern "C" int ivit_gauss_prepare(ivit_handle h, const float *Wh, const float *t, const float *Wc, const float *bc, int dim, int R, int C, void *model,
+                                  size_t model_bytes) {
+    CHECK_H(h);
+    REQUIRE(h, Wh && t && Wc && bc && model, "Wh, t, Wc, bc or model is null");
+    bool unsupported;
+    GaussLayout l;
+    if (const char *bad = gauss_shape_bad(0, dim, R, C, 0, 0, &unsupported, &l)) {
+        snprintf(h->err, sizeof(h->err), "%s: %s", __func__, bad);
+        return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
+    }
+    REQUIRE(h, model_bytes >= l.model_bytes, "model too small (ivit_gauss_model_bytes)");
+    REQUIRE_A16(h, Wh, "Wh");
+    REQUIRE_A16(h, Wc, "Wc");
+    REQUIRE_A16(h, model, "model");
+    REQUIRE_ALIGNED(h, t, "t", 4);
+    REQUIRE_ALIGNED(h, bc, "bc", 4);
+    REQUIRE_DISJOINT(h, Wh, (size_t)R * dim * 4, "Wh", model, model_bytes, "model", OVL_IN);
+    REQUIRE_DISJOINT(h, t, (size_t)R * 4, "t", model, model_bytes, "model", OVL_IN);
+    REQUIRE_DISJOINT(h, Wc, (size_t)C * dim * 4, "Wc", model, model_bytes, "model", OVL_IN);
+    REQUIRE_DISJOINT(h, bc, (size_t)C * 4, "bc", model, model_bytes, "model", OVL_IN);
+    GaussArgs a = {};
+    a.Wh = Wh; a.t = t; a.Wc = Wc; a.bc = bc;
+    a.pieces = (v4i *)model; a.vec = (float *)((char *)model + l.vec);
+    a.dim = dim; a.R = R; a.C = C; a.qtiles = l.qtiles; a.tiles = l.tiles;
+    gauss_prepare_kernel<<<(unsigned)(((long long)l.tiles * (dim / 32) * 64 + 255) / 256), 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_gauss_score(ivit_handle h, const void *model, size_t model_bytes, const int8_t *feat8, int64_t N, int dim, int R, int C, int splits,
+                                void *workspace, size_t workspace_bytes, float *q, float *best, int32_t *cls, float *dist) {
+    CHECK_H(h);
+    REQUIRE(h, model && feat8 && workspace && q && best && cls && dist, "model, feat8, workspace, q, best, cls or dist is null");
+    bool unsupported;
+    GaussLayout l, most;
+    REQUIRE(h, N != 0, "N must be in 1 .. 2^31 - 1");
+    if (const char *bad = gauss_shape_bad(N, dim, R, C, splits, persistent_cus(h), &unsupported, &l)) {
+        snprintf(h->err, sizeof(h->err), "%s: %s", __func__, bad);
+        return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
+    }
+    (void)gauss_shape_bad(N, dim, R, C, splits, 0, &unsupported, &most);   // what the size query states: never less than this launch needs
+    REQUIRE(h, model_bytes >= l.model_bytes, "model too small (ivit_gauss_model_bytes)");
+    REQUIRE(h, workspace_bytes >= most.bytes, "workspace too small (ivit_gauss_workspace_bytes)");
+    REQUIRE_A16(h, model, "model");
+    REQUIRE_A16(h, feat8, "feat8");
+    REQUIRE_A16(h, workspace, "workspace");
+    REQUIRE_ALIGNED(h, q, "q", 4);
+    REQUIRE_ALIGNED(h, best, "best", 4);
+    REQUIRE_ALIGNED(h, cls, "cls", 4);
+    REQUIRE_ALIGNED(h, dist, "dist", 4);
+    {
+        const struct { const void *p; size_t n; const char *name; } ins[2] = {{model, model_bytes, "model"}, {feat8, (size_t)N * dim, "feat8"}},
+            outs[5] = {{workspace, workspace_bytes, "workspace"}, {q, (size_t)N * 4, "q"}, {best, (size_t)N * 4, "best"}, {cls, (size_t)N * 4, "cls"},
+                       {dist, (size_t)N * 4, "dist"}};
+        for (const auto &i : ins)
+            for (const auto &o : outs) REQUIRE_DISJOINT(h, i.p, i.n, i.name, o.p, o.n, o.name, OVL_IN);
+        for (int i = 0; i < 5; ++i)
+            for (int j = i + 1; j < 5; ++j) REQUIRE_DISJOINT(h, outs[i].p, outs[i].n, outs[i].name, outs[j].p, outs[j].n, outs[j].name, OVL_OUT);
+    }
+    const long long row_blocks = (N + GAUSS_RB - 1) / GAUSS_RB;
+    REQUIRE_LAUNCH(h, row_blocks, 256, GAUSS_RB);
+    GaussArgs a = {};
+    char *ws = (char *)workspace;
+    a.pieces = (v4i *)model; a.vec = (float *)((char *)model + l.vec);
+    a.x = feat8; a.qpart = (float *)ws; a.pbest = (float *)(ws + l.pbest); a.pcls = (int *)(ws + l.pcls);
+    a.q = q; a.best = best; a.cls = cls; a.dist = dist;
+    a.N = N; a.dim = dim; a.R = R; a.C = C; a.qtiles = l.qtiles; a.tiles = l.tiles; a.per = l.per; a.parts = l.parts;
+    const dim3 grid((unsigned)row_blocks, (unsigned)l.parts);
+    switch (dim / 64) {
+#define GAUSS_CASE(KS) case KS: gauss_score_kernel<KS><<<grid, 256, 0, h->stream>>>(a); break;
+        GAUSS_CASE(1) GAUSS_CASE(2) GAUSS_CASE(3) GAUSS_CASE(4) GAUSS_CASE(5) GAUSS_CASE(6) GAUSS_CASE(7) GAUSS_CASE(8)
+        GAUSS_CASE(9) GAUSS_CASE(10) GAUSS_CASE(11) GAUSS_CASE(12) GAUSS_CASE(13) GAUSS_CASE(14) GAUSS_CASE(15) GAUSS_CASE(16)
+#undef GAUSS_CASE
+    }
+    LAUNCH_CHECK(h);
+    gauss_finish_kernel<<<(unsigned)((N + 255) / 256), 256, 0, h->stream>>>(a);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

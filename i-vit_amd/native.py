@@ -420,6 +420,17 @@ class NativeEngine:
         out = (assign, dist2, feat8)
         return tuple(t.clone() for t in out) if copy else out
 
+    def novelty(self, images, model, nslices=1, copy=False):
+        """images int8 [B, C, H, W], model an `ivit_amd.gauss.GaussModel` over this backbone's features -> (dist float32 [B], cls
+        int32 [B], feat8 int8 [B, num_features]) device tensors: `features` without the head, then `gauss.score(feat8, model)` on
+        the same stream (include/ivit_gauss.h) — every image's squared Mahalanobis distance to the nearest class mean and that
+        class, as `predict.gauss_score_reference` states them.  dist / cls are fresh tensors, feat8 the engine's buffer: copy=True
+        (or clone) to keep it."""
+        from .gauss import score
+        feat8 = self.features(images, nslices=nslices)[0]
+        dist, cls = score(feat8, model)[:2]
+        return dist, cls, feat8.clone() if copy else feat8
+
     # ---- views (include/ivit_views.h, ivit_amd/views.py): the mean logits of the V views of every image
     def _make_view_buffers(self, G, k):
         ncls = self.cfg.num_classes

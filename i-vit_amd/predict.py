@@ -617,6 +617,56 @@ def logreg_reference(feat8, labels, W, b, x_scale):
     return np.float64((lse - z[np.arange(len(lab)), lab]).sum()), g.T @ x, g.sum(axis=0), correct
 
 
+# ---------------------------------------------------------------- novelty scores (include/ivit_gauss.h, ivit_amd/gauss.py)
+def gauss_fit_reference(gram, class_sum, count, shrinkage=1e-3, rank=None):
+    """the probe's statistics -> (Wh [R, dim], t [R], Wc [C, dim], bc [C]) float64: the class-conditional Gaussian with a shared
+    covariance, over the features' integers.
+        n_c = count, N = sum n_c, mu_c = class_sum[c] / n_c, mu = sum_c class_sum[c] / N
+        S  = (gram - sum_c class_sum[c] class_sum[c]^T / n_c) / max(N - #nonempty, 1)          the pooled within-class covariance
+        S' = (1 - shrinkage) S + shrinkage (tr S / dim) I;   eigh(S'), eigenvalues descending;   R = rank or dim
+        Wh = L_R^-1/2 U_R^T,  t = -Wh mu,  m_c = Wh mu_c + t,  Wc[c] = 2 Wh^T m_c,  bc[c] = 2 t . m_c - |m_c|^2
+    so that |Wh x + t - m_c|^2 = q - s[c] in `gauss_score_reference`'s terms.  An empty class gets Wc = 0 and bc = -inf.  rank < dim
+    is the distance in the leading principal subspace of S'."""
+    gram, class_sum, count = (np.asarray(a).astype(np.float64) for a in (gram, class_sum, count))
+    dim = gram.shape[0]
+    R = dim if rank is None else int(rank)
+    if R % 32 or not 32 <= R <= dim:
+        raise ValueError(f"rank = {R}: a multiple of 32 in 32 .. {dim}")
+    N, full = count.sum(), count > 0
+    if not N > 0:
+        raise ValueError("the statistics hold no row")
+    mu = class_sum.sum(axis=0) / N
+    mu_c = class_sum[full] / count[full][:, None]
+    S = (gram - class_sum[full].T @ mu_c) / max(N - full.sum(), 1.0)          # sum_c class_sum[c] class_sum[c]^T / n_c = class_sum^T mu_c
+    S = (1.0 - shrinkage) * S + shrinkage * (np.trace(S) / dim) * np.eye(dim)
+    lam, U = np.linalg.eigh(0.5 * (S + S.T))
+    lam, U = lam[::-1][:R], U[:, ::-1][:, :R]
+    if not lam[-1] > 0:
+        raise ValueError("the covariance is singular in the leading subspace: raise the shrinkage or lower the rank")
+    Wh = U.T / np.sqrt(lam)[:, None]
+    t = -Wh @ mu
+    m = mu_c @ Wh.T + t
+    Wc, bc = np.zeros((len(count), dim)), np.full(len(count), -np.inf)
+    Wc[full], bc[full] = 2.0 * m @ Wh, 2.0 * m @ t - (m * m).sum(axis=1)
+    return Wh, t, Wc, bc
+
+
+def gauss_score_reference(feat8, Wh, t, Wc, bc):
+    """feat8 int8 [N, dim] and the model -> (dist, cls int32, q, best) float64 [N]: the outputs of `ivit_gauss_score`
+    (include/ivit_gauss.h) in float64 on the model's values as given.  q = sum_k (Wh x + t)_k^2, s = Wc x + bc, best = max_c s,
+    cls its smallest index, dist = q - best; with every class at -inf: cls 0, best -inf, dist +inf."""
+    x = np.asarray(feat8)
+    assert x.ndim == 2 and x.dtype == np.int8
+    x = x.astype(np.float64)
+    Wh, t, Wc, bc = (np.asarray(a, np.float64) for a in (Wh, t, Wc, bc))
+    z = x @ Wh.T + t
+    q = (z * z).sum(axis=1)
+    s = x @ Wc.T + bc
+    cls = s.argmax(axis=1).astype(np.int32)
+    best = s[np.arange(len(x)), cls]
+    return q - best, cls, q, best
+
+
 # ---------------------------------------------------------------- k-means (include/ivit_cluster.h, ivit_amd/cluster.py)
 KMEANS_MAX_K = 16384   # KMEANS_MAX_K of csrc/ivit_cluster.h
 
