@@ -29,7 +29,9 @@
  * chosen and makes no NaN; if every class is -inf, cls = 0, best = -inf and dist = +inf.  The model's values are finite otherwise.
  * Arithmetic: the products are exact (the model enters the matrix instruction as three bf16 pieces per float, the int8 features are
  * exact in bf16), the sums are fp32 in one fixed order.  No atomics: q, best, cls and dist hold the same bits for every `splits`,
- * every device and every call.
+ * every device and every call.  The exactness of the products assumes that all three pieces of a weight are normal bf16 numbers or
+ * zero, which holds for |weight| >= 2^-102 (a piece lies at most 24 binary places below its value, bf16's smallest normal is
+ * 2^-126); what a smaller weight's pieces become is the matrix instruction's treatment of denormals and is not pinned.
  *
  * Deliberately not here: the fit; per-class covariances (QDA); relative Mahalanobis; the [N, C] scores themselves; a runner-level
  * entry; fp16 / bf16 models.

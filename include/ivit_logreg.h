@@ -27,7 +27,9 @@
  * x_scale * x is x_scale * grad_W) belong to the caller.
  * Arithmetic: the products are exact (W and the probabilities enter the matrix instruction as three bf16 pieces each, the int8
  * features are exact in bf16), the sums are fp32, the loss terms are fp32 and their sum fp64.  No atomics: the same inputs, `splits`
- * and device give the same bits on every call.
+ * and device give the same bits on every call.  The exactness of the products assumes that all three pieces of a value are normal
+ * bf16 numbers or zero, which holds for |value| >= 2^-102 (a piece lies at most 24 binary places below its value, bf16's smallest
+ * normal is 2^-126); what a smaller weight's pieces become is the matrix instruction's treatment of denormals and is not pinned.
  *
  * Deliberately not here: the optimiser (ivit_amd/probe.py: fit_logistic); class weights, label smoothing, sigmoid (multi-label)
  * heads; a gradient with respect to the features; fp16 / bf16 heads; a sharded form (sums of per-rank outputs are the caller's).

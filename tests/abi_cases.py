@@ -1052,8 +1052,11 @@ def _r256(n):
 
 
 def overlap_placements(na, nb):
-    """{placement: (offset of a, offset of b)} of two arrays of na and nb bytes; all offsets multiples of 256 (16 inside a short a)"""
-    pl = {"same start": (0, 0), "b begins inside a": (0, 256 if na >= 512 else 16)}
+    """{placement: (offset of a, offset of b)} of two arrays of na and nb bytes; all offsets multiples of 256 (16 inside a short a;
+    an a of at most 16 bytes — the logistic probe's 8-byte loss — has no 16-byte-aligned inside to begin in)"""
+    pl = {"same start": (0, 0)}
+    if na > 16:
+        pl["b begins inside a"] = (0, 256 if na >= 512 else 16)
     back = 256 * ((nb - 1) // 256)
     if back:
         pl["b ends inside a"] = (back, 0)

@@ -1,5 +1,6 @@
 """ivit_gauss_score (include/ivit_gauss.h) against predict.gauss_score_reference: the shapes at which the scorer changes its path, equal
-scores in two tiles, -inf classes, the same bits for every `splits`, call and graph replay, the refusals, and engine.novelty."""
+scores in two tiles, -inf classes, the same bits for every `splits`, call and graph replay, the refusals, and engine.novelty; every
+width the launcher dispatches on, and one-hot models whose four outputs are known bit for bit (tests/float_cases.py)."""
 import ctypes
 
 import numpy as np
@@ -10,6 +11,7 @@ from conftest import golden_scales, load_golden
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+import float_cases as F  # noqa: E402
 import ivit_amd as iv  # noqa: E402
 from ivit_amd import _lib, gauss  # noqa: E402
 from ivit_amd.predict import gauss_score_reference  # noqa: E402
@@ -32,12 +34,9 @@ SHAPES = [(1, 64, 32, 1, 3), (127, 192, 96, 33, 1), (129, 64, 64, 70, 0), (300, 
 
 
 def case(N, dim, R, C, seed=0):
-    """x and a model whose q and scores are of unit-to-R size"""
-    rng = np.random.default_rng([N, dim, R, C, seed])
-    x = rng.integers(-128, 128, size=(N, dim)).astype(np.int8)
-    Wh, t = (rng.normal(size=(R, dim)) / (74 * np.sqrt(dim))).astype(np.float32), rng.normal(size=R).astype(np.float32)
-    Wc, bc = (4 * rng.normal(size=(C, dim)) / (74 * np.sqrt(dim))).astype(np.float32), rng.normal(size=C).astype(np.float32)
-    return x, gauss.GaussModel(Wh, t, Wc, bc)
+    """x and a model whose q and scores are of unit-to-R size: one generator for the suites and tools/gauss_bench.py"""
+    x, *model = F.gauss_arrays(N, dim, R, C, seed)
+    return x, gauss.GaussModel(*model)
 
 
 def run(x, model, splits=0):
@@ -51,16 +50,50 @@ def reference(x, m):
     return dist, cls, q, best, np.abs(s).max(), top[:, -1] - top[:, -2] if s.shape[1] > 1 else np.full(len(x), np.inf)
 
 
-@pytest.mark.parametrize("N,dim,R,C,splits", SHAPES)
-def test_entry_equals_the_reference(N, dim, R, C, splits):
-    x, model = case(N, dim, R, C)
-    dist, cls, q, best = run(x, model, splits)
-    wd, wc, wq, wb, smax, gap = reference(x, model)
+def check(got, want, q_bound=Q_BOUND, best_bound=BEST_BOUND):
+    dist, cls, q, best = got
+    wd, wc, wq, wb, smax, gap = want
     print("q err %.3e  best err %.3e  dist abs err %.3e" % (np.abs(q - wq).max() / wq.max(), np.abs(best - wb).max() / smax, np.abs(dist - wd).max()))
     clear = gap > 1e-5 * smax
     assert clear.mean() >= 0.99 and np.array_equal(cls[clear], wc[clear]) and cls.dtype == np.int32
-    assert np.abs(q - wq).max() <= Q_BOUND * wq.max() and np.abs(best - wb).max() <= BEST_BOUND * smax
-    assert np.abs(dist - wd).max() <= Q_BOUND * wq.max() + BEST_BOUND * smax
+    assert np.abs(q - wq).max() <= q_bound * wq.max() and np.abs(best - wb).max() <= best_bound * smax
+    assert np.abs(dist - wd).max() <= q_bound * wq.max() + best_bound * smax
+
+
+@pytest.mark.parametrize("N,dim,R,C,splits", SHAPES)
+def test_entry_equals_the_reference(N, dim, R, C, splits):
+    x, model = case(N, dim, R, C)
+    check(run(x, model, splits), reference(x, model))
+
+
+# Every width the launcher dispatches on (tests/float_cases.py), under the same rule with the torch route's error measured on THESE
+# cases (tools/gauss_bench.py --errors on an MI355X; profiles/README.md, "Novelty scores", "Every width and one-hot models"):
+# (TORCH_Q_ERR, TORCH_BEST_ERR) of the list, the bounds twice that.
+WIDTH_TORCH_ERR = (4.558e-7, 9.746e-7)   # the entry's own on that run: 1.939e-7 and 2.677e-7
+
+
+def _ids(cases):
+    return ["-".join(str(v) for v in c) for c in cases]
+
+
+@pytest.mark.parametrize("N,dim,R,C,splits,seed", F.GAUSS_WIDTH_CASES, ids=_ids(F.GAUSS_WIDTH_CASES))
+def test_every_dispatched_width_equals_the_reference(N, dim, R, C, splits, seed):
+    """gauss_score_kernel<KS>, KS = dim / 64 = 1 .. 16; R = dim at the widths of the workload's own backbones"""
+    x, model = case(N, dim, R, C, seed)
+    check(run(x, model, splits), reference(x, model), 2 * WIDTH_TORCH_ERR[0], 2 * WIDTH_TORCH_ERR[1])
+
+
+@pytest.mark.parametrize("dim,R,splits", F.ONEHOT_GAUSS_CASES, ids=_ids(F.ONEHOT_GAUSS_CASES))
+def test_one_hot_models_bit_for_bit(dim, R, splits):
+    """one nonzero weight per table row (24 significant bits, exponents 2^-30 .. 2^30 inside a tile), features that are powers of
+    two: every z and s is one exact product whatever order the matrix instruction adds in, and the header's order fixes q, so all
+    four outputs are known to the bit.  A weight in the wrong place of the prepared layout, a lost piece, a piece scaled wrongly or
+    a class index off by a half moves at least one of them"""
+    x, *model = F.onehot_case(dim, R)
+    want = F.onehot_gauss_expected(x, *model)
+    got = run(np.array(x), gauss.GaussModel(*(np.array(a) for a in model)), splits)      # copies: the case's arrays are read-only
+    for name, g, w in zip(("dist", "cls", "q", "best"), got, want):
+        assert g.dtype == w.dtype and np.array_equal(g, w), (name, int((g != w).sum()), "elements differ")
 
 
 def test_equal_largest_scores_in_two_tiles_take_the_smaller_index():

@@ -1,5 +1,6 @@
 """ivit_logreg_loss_grad (include/ivit_logreg.h) against predict.logreg_reference: the shapes at which the two kernels change their path,
-ignored rows, logits of +-80, equal logits, determinism, a captured graph, the refusals, and fit_logistic end to end."""
+ignored rows, logits of +-80, equal logits, determinism, a captured graph, the refusals, and fit_logistic end to end; then the case
+lists of tests/float_cases.py: every width the launcher dispatches on, both sides of the part-length limit, one-hot weights."""
 import ctypes
 
 import numpy as np
@@ -8,6 +9,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+import float_cases as F  # noqa: E402
 from ivit_amd import _lib  # noqa: E402
 from ivit_amd.predict import logreg_reference  # noqa: E402
 from ivit_amd.probe import fit_logistic, logreg_loss_grad  # noqa: E402
@@ -27,11 +29,7 @@ SHAPES = [(1, 2, 64, 0), (127, 2, 192, 1), (129, 33, 64, 3), (300, 70, 192, 0), 
           (300, 2, 1024, 3), (1, 33, 192, 1), (129, 2, 64, 1), (300, 70, 64, 3), (127, 33, 192, 0)]
 
 
-def case(N, C, dim, seed=0):
-    """x, labels, W, b, x_scale with logits of about unit size"""
-    rng = np.random.default_rng([N, C, dim, seed])
-    return (rng.integers(-128, 128, size=(N, dim)).astype(np.int8), rng.integers(C, size=N).astype(np.int32),
-            (rng.normal(size=(C, dim)) * 0.3 / np.sqrt(dim)).astype(np.float32), rng.normal(size=C).astype(np.float32), 0.05)
+case = F.logreg_case      # x, labels, W, b, x_scale with logits of about unit size: one generator for the suites and tools/logreg_bench.py
 
 
 def run(x, lab, W, b, s, splits=0):
@@ -39,13 +37,13 @@ def run(x, lab, W, b, s, splits=0):
     return [t.cpu().numpy() for t in out]
 
 
-def check(got, want):
+def check(got, want, grad_bound=GRAD_BOUND, loss_bound=LOSS_BOUND):
     loss, gW, gb, correct = got
     print("loss rel err %.3e  grad_W err %.3e  grad_b err %.3e" % (abs(loss[0] - want[0]) / max(abs(want[0]), 1e-300),
           np.abs(gW - want[1]).max() / np.abs(want[1]).max(), np.abs(gb - want[2]).max() / np.abs(want[2]).max()))
     assert np.array_equal(correct, want[3])
-    assert abs(loss[0] - want[0]) <= LOSS_BOUND * abs(want[0])
-    assert np.abs(gW - want[1]).max() <= GRAD_BOUND * np.abs(want[1]).max() and np.abs(gb - want[2]).max() <= GRAD_BOUND * np.abs(want[2]).max()
+    assert abs(loss[0] - want[0]) <= loss_bound * abs(want[0])
+    assert np.abs(gW - want[1]).max() <= grad_bound * np.abs(want[1]).max() and np.abs(gb - want[2]).max() <= grad_bound * np.abs(want[2]).max()
 
 
 @pytest.mark.parametrize("N,C,dim,splits", SHAPES)
@@ -139,3 +137,57 @@ def test_fit_logistic_classifies_as_the_float64_reference_fit():
     xd, ld = torch.from_numpy(x).cuda(), torch.from_numpy(lab).cuda()
     head = fit_logistic([xd[:250], xd[250:]], ld, 5, 0.02, l2=1e-3, iters=100)
     assert (head.logits_reference(x).argmax(axis=1) == pred).mean() >= 0.99
+
+
+# ---------------------------------------------------------------- the case lists of tests/float_cases.py
+# The accuracy rule on three further lists, each with the torch route's error measured on ITS cases (tools/logreg_bench.py --errors on
+# an MI355X; profiles/README.md, "Logistic probe", "Every width, both sides of the part limit, one-hot models"): (TORCH_GRAD_ERR,
+# TORCH_LOSS_ERR) of the list, the bounds twice that.  As above, the gradient figure is the larger of the torch route's two (grad_W).
+WIDTH_TORCH_ERR = (5.761e-7, 6.489e-8)   # every width: the entry's own on that run: 1.728e-7 (grad_b 1.652e-7) and 2.135e-8
+FLUSH_TORCH_ERR = (2.171e-6, 6.945e-8)   # both sides of LOGREG_FLUSH_ROWS: the entry's own: 8.587e-7 (grad_b 3.074e-7) and 1.352e-8
+ONEHOT_TORCH_ERR = (0.0, 5.557e-8)       # one-hot models: every gradient is an exact integer on both routes; the entry's loss: 6.255e-9
+
+
+def _ids(cases):
+    return ["-".join(str(v) for v in c) for c in cases]
+
+
+@pytest.mark.parametrize("N,C,dim,splits,seed", F.LOGREG_WIDTH_CASES, ids=_ids(F.LOGREG_WIDTH_CASES))
+def test_every_dispatched_width_equals_the_reference(N, C, dim, splits, seed):
+    """logreg_rows_kernel<KS>, KS = dim / 64 = 1 .. 16, and logreg_grad_kernel<NT>, NT = 1 .. 8 (two widths each: the feature tiles
+    split evenly over the four wavefronts at one, unevenly at the other)"""
+    x, lab, W, b, s = case(N, C, dim, seed)
+    check(run(x, lab, W, b, s, splits), logreg_reference(x, lab, W, b, s), 2 * WIDTH_TORCH_ERR[0], 2 * WIDTH_TORCH_ERR[1])
+
+
+def _workspace_bytes(N, dim, C, splits):
+    n = ctypes.c_size_t(0)
+    assert _lib.load().ivit_logreg_workspace_bytes(N, dim, C, splits, ctypes.byref(n)) == 0
+    return n.value
+
+
+@pytest.mark.parametrize("N,C,dim,splits,seed", F.LOGREG_FLUSH_CASES, ids=_ids(F.LOGREG_FLUSH_CASES))
+def test_both_sides_of_the_part_length_limit(N, C, dim, splits, seed):
+    """a part of the gradient pass holds at most LOGREG_FLUSH_ROWS rows whatever `splits` asks for: 65536 rows are one part, 65537
+    with splits = 1 two of 32800 and 32737 (ragged), and the size query states at least what the device's layout needs
+    (float_cases.logreg_layout: the launcher's arithmetic restated; tests/test_float_cases_cpu.py checks it without a device)"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    dev, most = F.logreg_layout(N, dim, C, splits, cus), F.logreg_layout(N, dim, C, splits, 0)
+    assert dev["per"] <= F.LOGREG_FLUSH_ROWS and dev["per"] % 32 == 0 and (dev["parts"] - 1) * dev["per"] < N <= dev["parts"] * dev["per"]
+    assert (dev["parts"] == 1) == (N <= F.LOGREG_FLUSH_ROWS)
+    if splits == 1:
+        assert (dev["parts"], dev["per"]) == ((1, 65536) if N == 65536 else (2, 32800))
+    assert _workspace_bytes(N, dim, C, splits) == most["bytes"] >= dev["bytes"]
+    x, lab, W, b, s = case(N, C, dim, seed)
+    check(run(x, lab, W, b, s, splits), logreg_reference(x, lab, W, b, s), 2 * FLUSH_TORCH_ERR[0], 2 * FLUSH_TORCH_ERR[1])
+
+
+@pytest.mark.parametrize("dim,splits", F.ONEHOT_LOGREG_CASES, ids=_ids(F.ONEHOT_LOGREG_CASES))
+def test_one_hot_weights_give_exact_logits(dim, splits):
+    """one nonzero weight per class, 24 significant bits each, exponents 2^-30 .. 2^30 inside a class tile, features that are powers
+    of two: every logit is one exact product, so `correct` has no tolerance (check asserts it exactly) whatever piece or exponent a
+    kernel mishandles; loss and gradient under the accuracy rule"""
+    x, lab, W, b, s = (np.array(a) if isinstance(a, np.ndarray) else a for a in F.onehot_logreg_case(dim))
+    want = logreg_reference(x, lab, W, b, s)
+    assert 0 < want[3][1] < want[3][0] == len(x)
+    check(run(x, lab, W, b, s, splits), want, 2 * ONEHOT_TORCH_ERR[0], 2 * ONEHOT_TORCH_ERR[1])

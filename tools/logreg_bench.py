@@ -1,7 +1,8 @@
 """One loss / gradient evaluation of the logistic probe, timed beside the plain torch route, and the two routes' errors against float64.
 
     python tools/logreg_bench.py                      # N = 100 000, dim = 384, C = 1000: one JSON line of times
-    python tools/logreg_bench.py --errors             # the test shapes: the largest error of each route against logreg_reference
+    python tools/logreg_bench.py --errors             # the test shapes, then the case lists of tests/float_cases.py: the largest
+                                                      # error of each route against logreg_reference, per list
 
 The torch route is what a user writes without the entry: z = (feat8.float() @ W.T) * x_scale + b, log-softmax, p - onehot, two
 matmuls in fp32; its [N, C] matrices are materialised.  Times: device events round `--reps` evaluations, the two routes alternating
@@ -14,19 +15,17 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _ROOT)
+sys.path.insert(0, os.path.join(_ROOT, "tests"))
+import float_cases  # noqa: E402    the generator and the case lists the tests bound (tests/float_cases.py)
 from ivit_amd.predict import logreg_reference  # noqa: E402
 from ivit_amd.probe import logreg_loss_grad  # noqa: E402
 
-# tests/test_logreg_gpu.py: SHAPES, case and (in test_cases) its two further cases under the accuracy rule
+# tests/test_logreg_gpu.py: SHAPES and (in test_cases) its two further cases under the accuracy rule
 SHAPES = [(1, 2, 64, 0), (127, 2, 192, 1), (129, 33, 64, 3), (300, 70, 192, 0), (300, 33, 1024, 1), (129, 70, 1024, 3), (127, 70, 64, 0),
           (300, 2, 1024, 3), (1, 33, 192, 1), (129, 2, 64, 1), (300, 70, 64, 3), (127, 33, 192, 0)]
-
-
-def case(N, C, dim, seed=0):
-    rng = np.random.default_rng([N, C, dim, seed])
-    return (rng.integers(-128, 128, size=(N, dim)).astype(np.int8), rng.integers(C, size=N).astype(np.int32),
-            (rng.normal(size=(C, dim)) * 0.3 / np.sqrt(dim)).astype(np.float32), rng.normal(size=C).astype(np.float32), 0.05)
+case = float_cases.logreg_case
 
 
 def torch_route(x8, lab, W, b, s):
@@ -56,6 +55,27 @@ def test_cases():
     yield ("logits of +-80", x, lab, W, b, s, 1)
 
 
+def further_lists():
+    """(list name, its cases in test_cases' form): the case lists of tests/float_cases.py, each with constants of its own"""
+    yield "every width", [([N, C, dim, splits],) + case(N, C, dim, seed) + (splits,) for N, C, dim, splits, seed in float_cases.LOGREG_WIDTH_CASES]
+    yield "both sides of LOGREG_FLUSH_ROWS", [([N, C, dim, splits],) + case(N, C, dim, seed) + (splits,)
+                                              for N, C, dim, splits, seed in float_cases.LOGREG_FLUSH_CASES]
+    yield "one-hot models", [(["one-hot", dim, splits],) + float_cases.onehot_logreg_case(dim) + (splits,) for dim, splits in float_cases.ONEHOT_LOGREG_CASES]
+
+
+def walk(name, cases):
+    worst = {"torch": [0.0, 0.0, 0.0], "entry": [0.0, 0.0, 0.0]}
+    for label, x, lab, W, b, s, splits in cases:
+        want = logreg_reference(x, lab, W, b, s)
+        dev = [torch.from_numpy(np.array(a)).cuda() for a in (x, lab, W, b)]      # a copy: the one-hot arrays are read-only
+        rows = {"torch": errors([t.cpu().numpy() for t in torch_route(*dev, s)], want),
+                "entry": errors([t.cpu().numpy() for t in logreg_loss_grad(*dev, s, splits)[:3]], want)}
+        for k, e in rows.items():
+            worst[k] = [max(a, c) for a, c in zip(worst[k], e)]
+        print(json.dumps({"case": label, **{k: ["%.3e" % v for v in e] for k, e in rows.items()}}), flush=True)
+    print(json.dumps({"list": name, "worst (loss, grad_W, grad_b)": {k: ["%.3e" % v for v in e] for k, e in worst.items()}}), flush=True)
+
+
 def errors(got, want):
     return (abs(float(np.asarray(got[0]).reshape(-1)[0]) - want[0]) / abs(want[0]), float(np.abs(got[1] - want[1]).max() / np.abs(want[1]).max()),
             float(np.abs(got[2] - want[2]).max() / np.abs(want[2]).max()))
@@ -74,16 +94,9 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/logreg_bench.py needs a HIP device")
     if args.errors:
-        worst = {"torch": [0.0, 0.0, 0.0], "entry": [0.0, 0.0, 0.0]}
-        for name, x, lab, W, b, s, splits in test_cases():
-            want = logreg_reference(x, lab, W, b, s)
-            dev = [torch.from_numpy(a).cuda() for a in (x, lab, W, b)]
-            rows = {"torch": errors([t.cpu().numpy() for t in torch_route(*dev, s)], want),
-                    "entry": errors([t.cpu().numpy() for t in logreg_loss_grad(*dev, s, splits)[:3]], want)}
-            for k, e in rows.items():
-                worst[k] = [max(a, c) for a, c in zip(worst[k], e)]
-            print(json.dumps({"case": name, **{k: ["%.3e" % v for v in e] for k, e in rows.items()}}))
-        print(json.dumps({"worst (loss, grad_W, grad_b)": {k: ["%.3e" % v for v in e] for k, e in worst.items()}}))
+        walk("the test shapes", test_cases())
+        for name, cases in further_lists():
+            walk(name, cases)
         return
     x, lab, W, b, s = case(args.n, args.classes, args.dim)
     dev = [torch.from_numpy(a).cuda() for a in (x, lab, W, b)]
