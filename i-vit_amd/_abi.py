@@ -1,4 +1,4 @@
-"""include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h and include/ivit_gauss.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
+"""include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h and include/ivit_density.h, each parsed once: the only statement of the C-ABI that Python reads.  _lib.py binds libivit_hip.so from them,
 tools/gen_twin_header.py prints the CPU twin's prototypes from it, the tests bind the twin and walk the entry points through it.
 Standard library only, so a tool loads this file without the package (and without torch).
 
@@ -29,6 +29,7 @@ Standard library only, so a tool loads this file without the package (and withou
     SEED_ABI        the same of include/ivit_seed.h, the fifteenth (IVIT_SEED_VERSION)
     LOGREG_ABI      the same of include/ivit_logreg.h, the sixteenth (IVIT_LOGREG_VERSION)
     GAUSS_ABI       the same of include/ivit_gauss.h, the seventeenth (IVIT_GAUSS_VERSION)
+    DENSITY_ABI     the same of include/ivit_density.h, the eighteenth (IVIT_DENSITY_VERSION)
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -63,6 +64,7 @@ JPEG_ENTROPY_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_jpeg_entropy.h
 SEED_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_seed.h")
 LOGREG_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_logreg.h")
 GAUSS_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_gauss.h")
+DENSITY_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_density.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -232,3 +234,5 @@ with open(LOGREG_HEADER) as _f:
     LOGREG_ABI = parse(_f.read(), base=ABI)
 with open(GAUSS_HEADER) as _f:
     GAUSS_ABI = parse(_f.read(), base=ABI)
+with open(DENSITY_HEADER) as _f:
+    DENSITY_ABI = parse(_f.read(), base=ABI)

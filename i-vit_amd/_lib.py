@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h and include/ivit_gauss.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
+"""ctypes binding of the C-ABI in include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h, include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h and include/ivit_density.h (libivit_hip.so, built in-tree).  Nothing of the ABI is
 restated here: the Structures, the status codes and every argtypes / restype are derived from the headers by _abi.py (the mapping
 rule is stated there).  ivit.h is frozen at IVIT_VERSION 111: ABI / SIGNATURES / RESTYPES are its prototypes and stay what they are;
 the entries that came after it are those of ivit_eval.h, under EVAL_ABI / EVAL_SIGNATURES / EVAL_RESTYPES, of ivit_features.h,
@@ -11,7 +11,8 @@ CLUSTER_SIGNATURES / CLUSTER_RESTYPES, of ivit_range.h, under RANGE_ABI / RANGE_
 JPEG_SIGNATURES / JPEG_RESTYPES (its struct ivit_jpeg_desc is JpegDesc), and of ivit_jpeg_entropy.h, under JPEG_ENTROPY_ABI /
 JPEG_ENTROPY_SIGNATURES / JPEG_ENTROPY_RESTYPES (its structs are JpegSegment, JpegHuff and JpegScan), and of ivit_seed.h, under SEED_ABI /
 SEED_SIGNATURES / SEED_RESTYPES, and of ivit_logreg.h, under LOGREG_ABI / LOGREG_SIGNATURES / LOGREG_RESTYPES, and of
-ivit_gauss.h, under GAUSS_ABI / GAUSS_SIGNATURES / GAUSS_RESTYPES.
+ivit_gauss.h, under GAUSS_ABI / GAUSS_SIGNATURES / GAUSS_RESTYPES, and of ivit_density.h, under DENSITY_ABI / DENSITY_SIGNATURES /
+DENSITY_RESTYPES.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -244,6 +245,18 @@ _gauss_signatures = _abi.signatures(GAUSS_ABI, _structs)
 GAUSS_RESTYPES = {name: ret for name, (ret, args) in _gauss_signatures.items()}
 GAUSS_SIGNATURES = {name: args for name, (ret, args) in _gauss_signatures.items()}
 
+# include/ivit_density.h, by the rule of ivit_range.h
+DENSITY_ABI = _abi.DENSITY_ABI
+IVIT_DENSITY_VERSION = DENSITY_ABI.constants["IVIT_DENSITY_VERSION"]
+assert set(DENSITY_ABI.structs) == set(ABI.structs) and not set(DENSITY_ABI.functions) & (
+    set(ABI.functions) | set(EVAL_ABI.functions) | set(FEATURES_ABI.functions) | set(ATTNMAP_ABI.functions) | set(CLASSMAP_ABI.functions)
+    | set(HIDDEN_ABI.functions) | set(SEARCH_ABI.functions) | set(MODELFILE_ABI.functions) | set(PROBE_ABI.functions) | set(VIEWS_ABI.functions)
+    | set(CLUSTER_ABI.functions) | set(RANGE_ABI.functions) | set(JPEG_ABI.functions) | set(JPEG_ENTROPY_ABI.functions) | set(SEED_ABI.functions)
+    | set(LOGREG_ABI.functions) | set(GAUSS_ABI.functions))
+_density_signatures = _abi.signatures(DENSITY_ABI, _structs)
+DENSITY_RESTYPES = {name: ret for name, (ret, args) in _density_signatures.items()}
+DENSITY_SIGNATURES = {name: args for name, (ret, args) in _density_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -252,7 +265,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _abi.RANGE_HEADER, _abi.JPEG_HEADER, _abi.JPEG_ENTROPY_HEADER, _abi.SEED_HEADER, _abi.LOGREG_HEADER, _abi.GAUSS_HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _abi.RANGE_HEADER, _abi.JPEG_HEADER, _abi.JPEG_ENTROPY_HEADER, _abi.SEED_HEADER, _abi.LOGREG_HEADER, _abi.GAUSS_HEADER, _abi.DENSITY_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -418,6 +431,14 @@ def bind_gauss(lib):
     return lib
 
 
+def bind_density(lib):
+    """the same for every prototype of include/ivit_density.h"""
+    for name, args in DENSITY_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, DENSITY_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -429,7 +450,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind_gauss(bind_logreg(bind_seed(bind_jpeg_entropy(bind_jpeg(bind_range(bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH))))))))))))))))))
+    _lib = bind_density(bind_gauss(bind_logreg(bind_seed(bind_jpeg_entropy(bind_jpeg(bind_range(bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH)))))))))))))))))))
     return _lib
 
 

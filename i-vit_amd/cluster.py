@@ -378,3 +378,62 @@ def nmi(table):
     mi = float((p[nz] * np.log(p[nz] / outer[nz])).sum())
     den = (H(pa) + H(pb)) / 2
     return mi / den if den > 0 else 1.0
+
+
+# ---------------------------------------------------------------- density clustering (include/ivit_density.h)
+NONE = 2 ** 31 - 1                                     # DENSITY_NONE of csrc/ivit_density.h: the label of a row that is not core
+
+
+def dbscan(feat8, threshold, min_pts, cosine=True, check_every=4, splits=0):
+    """DBSCAN over the rows of feat8 (a contiguous int8 device tensor [rows, dim]) ON THE DEVICE, as `predict.dbscan_reference`
+    states it, with the rows' inverse norms (ivit_gallery_inv_norms) as the weight for cosine=True and none for the exact integer
+    dot product.  The order of work: ivit_density_degree, ivit_density_init, then batches of `check_every` ivit_density_sweep with
+    ONE read of `changed` per batch (the only synchronisations) until a batch ends on 0, then ivit_density_border.  A sweep after
+    convergence skips every tile, so a larger check_every costs little; the labels depend neither on it nor on `splits`.  Memory is
+    O(rows): no pair list, no [rows, rows] matrix.  Returns (label int32 [rows]: the smallest row of the cluster, -1 for noise; core
+    bool [rows]; degree int32 [rows]; sweeps: the number of sweeps queued)."""
+    if not isinstance(feat8, torch.Tensor) or feat8.dtype != torch.int8 or feat8.dim() != 2 or not feat8.is_cuda or not feat8.is_contiguous():
+        raise ValueError("feat8: a contiguous int8 device tensor [rows, dim]")
+    rows, dim, dev = int(feat8.shape[0]), int(feat8.shape[1]), feat8.device
+    if rows < 1:
+        raise ValueError("feat8 holds no row")
+    if not np.isfinite(np.float32(threshold)):
+        raise ValueError("threshold must be finite")
+    if int(min_pts) < 1 or int(check_every) < 1:
+        raise ValueError("min_pts and check_every must be at least 1")
+    h = _lib.Handle(dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    n = ctypes.c_size_t()
+    h.call("ivit_density_workspace_bytes", rows, dim, int(splits), ctypes.byref(n))
+    new = lambda dt, *shape: torch.empty(*shape, dtype=dt, device=dev)      # noqa: E731
+    ws = new(torch.uint8, n.value)
+    weight = None
+    if cosine:
+        weight = new(torch.float32, rows)
+        h.call("ivit_gallery_inv_norms", _ptr(feat8), rows, dim, _ptr(weight))
+    scan = (_ptr(feat8), rows, dim, _ptr(weight), float(threshold), int(splits), _ptr(ws), n.value)
+    words = ((rows + 31) // 32 + 63) // 64
+    degree, out, changed = new(torch.int32, rows), new(torch.int32, rows), new(torch.int32, 1)
+    label, dirty = [new(torch.int32, rows), new(torch.int32, rows)], [new(torch.int64, words), new(torch.int64, words)]
+    h.call("ivit_density_degree", *scan, _ptr(degree))
+    h.call("ivit_density_init", _ptr(degree), rows, int(min_pts), _ptr(label[0]), _ptr(dirty[0]))
+    sweeps = 0
+    while True:
+        for _ in range(int(check_every)):
+            a, b = sweeps & 1, ~sweeps & 1
+            h.call("ivit_density_sweep", *scan, _ptr(label[a]), _ptr(dirty[a]), _ptr(label[b]), _ptr(dirty[b]), _ptr(changed))
+            sweeps += 1
+        if int(changed.item()) == 0:                                    # the one read of a batch
+            break
+        if sweeps > rows + int(check_every):
+            raise _lib.IvitError("ivit_density_sweep did not converge: labels only fall, so this cannot happen")
+    h.call("ivit_density_border", *scan, _ptr(label[sweeps & 1]), _ptr(out))
+    return out, label[sweeps & 1] != NONE, degree, sweeps
+
+
+def compact_labels(label):
+    """label integer tensor [rows] (`dbscan`: a cluster is named by its smallest row) -> (int32 [rows] on the same device with the
+    clusters numbered 0 .. n_clusters - 1 in ascending order of their label, noise still -1; n_clusters)"""
+    label = torch.as_tensor(label).reshape(-1)
+    names = torch.unique(label[label >= 0])                            # sorted
+    compact = torch.where(label >= 0, torch.searchsorted(names, label.clamp(min=0)), torch.full_like(label, -1))
+    return compact.to(torch.int32), int(names.shape[0])

@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h, include/ivit_density.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -49,6 +49,7 @@
 #include "ivit_seed.h"
 #include "ivit_logreg.h"
 #include "ivit_gauss.h"
+#include "ivit_density.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -3470,6 +3471,174 @@ extern "C" int ivit_gauss_score(ivit_handle h, const void *model, size_t model_b
     }
     LAUNCH_CHECK(h);
     gauss_finish_kernel<<<(unsigned)((N + 255) / 256), 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- density clustering (include/ivit_density.h)
+// the workspace: the rows * parts int32 partial results of a scan, the rows int32 minima of a sweep, a changed byte per tile in whole
+// words of 64 (each array a multiple of 16 bytes)
+struct DensityLayout {
+    long long tiles, words, per;    // tiles of 32 rows; words of the bitmap; tiles of a part
+    int parts;
+    size_t m, flag, bytes;          // byte offsets of the minima and the bytes; the whole
+};
+
+// the limits every entry with rows shares, the parts — the caller's, or about two workgroups per CU of the handle's share in parts of
+// at least 1024 rows; never more than tiles, none of them empty — and the layout
+static int density_shape_ok(ivit_handle h, const char *fn, long long rows, int dim, int splits, DensityLayout *l) {
+    const char *bad = nullptr;
+    if (rows < 1 || rows > 0x7fffffffLL) bad = "rows must be in 1 .. 2^31 - 1";
+    else if (splits < 0 || splits > 65535) bad = "splits must be in 0 .. 65535";
+    if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    if (dim < SEARCH_MIN_DIM || dim > SEARCH_MAX_DIM || (dim % 64) != 0) {
+        snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 64 in 64 .. 1024", fn);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    l->tiles = (rows + SEARCH_TILE - 1) / SEARCH_TILE;
+    l->words = (l->tiles + DENSITY_WORD_TILES - 1) / DENSITY_WORD_TILES;
+    const long long cols = (rows + SEARCH_QB - 1) / SEARCH_QB;
+    long long s = splits;
+    if (s == 0) s = std::max(1ll, std::min((2ll * persistent_cus(h) + cols - 1) / cols, rows / 1024));
+    s = std::min(s, l->tiles);
+    l->per = (l->tiles + s - 1) / s;
+    l->parts = (int)((l->tiles + l->per - 1) / l->per);
+    if (const int rc = launch_fits(h, fn, cols * l->parts, 256, SEARCH_QB)) return rc;
+    l->m = ((size_t)rows * l->parts * 4 + 15) & ~(size_t)15;
+    l->flag = l->m + (((size_t)rows * 4 + 15) & ~(size_t)15);
+    l->bytes = l->flag + (size_t)l->words * DENSITY_WORD_TILES;
+    return IVIT_OK;
+}
+
+extern "C" int ivit_density_workspace_bytes(ivit_handle h, int64_t rows, int dim, int splits, size_t *bytes) {
+    CHECK_H(h);
+    REQUIRE(h, bytes, "bytes is null");
+    DensityLayout l;
+    if (const int rc = density_shape_ok(h, __func__, rows, dim, splits, &l)) return rc;
+    *bytes = l.bytes;
+    return IVIT_OK;
+}
+
+// what the three scanning entries check alike, in the same order, and the scan's arguments
+static int density_args_ok(ivit_handle h, const char *fn, const int8_t *x, long long rows, int dim, const float *weight, float threshold, int splits,
+                           void *workspace, size_t bytes, DensityArgs *a, DensityLayout *l) {
+    if (const int rc = density_shape_ok(h, fn, rows, dim, splits, l)) return rc;
+    const char *bad = nullptr;
+    if (!(threshold >= -FLT_MAX && threshold <= FLT_MAX)) bad = "threshold must be finite";
+    else if (bytes < l->bytes) bad = "workspace too small (ivit_density_workspace_bytes)";
+    else if ((uintptr_t)x & 15) bad = "x must be 16-byte aligned";
+    else if ((uintptr_t)workspace & 15) bad = "workspace must be 16-byte aligned";
+    if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    a->x = x; a->weight = weight; a->label = nullptr; a->dirty = nullptr; a->part = (int *)workspace;
+    a->rows = rows; a->tiles = l->tiles; a->per = l->per; a->threshold = threshold; a->parts = l->parts;
+    return IVIT_OK;
+}
+
+// every array of an entry against every array it writes: inputs first (n_in of them), then the outputs
+struct DensityRange { const void *p; size_t n; const char *name; };
+static int density_disjoint(ivit_handle h, const char *fn, const DensityRange *r, int n_in, int n) {
+    for (int o = n_in; o < n; ++o)
+        for (int i = 0; i < o; ++i)
+            if (!ranges_disjoint(h, fn, r[i].p, r[i].n, r[i].name, r[o].p, r[o].n, r[o].name, i < n_in ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
+    return IVIT_OK;
+}
+
+template <int MODE>
+static void density_scan_dispatch(ivit_handle h, int dim, const DensityArgs &a) {
+    const dim3 grid((unsigned)((a.rows + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
+    switch (dim / 64) {
+#define DENSITY_CASE(KS) case KS: density_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS), MODE><<<grid, 256, 0, h->stream>>>(a); break;
+        DENSITY_CASE(1) DENSITY_CASE(2) DENSITY_CASE(3) DENSITY_CASE(4) DENSITY_CASE(5) DENSITY_CASE(6) DENSITY_CASE(7) DENSITY_CASE(8)
+        DENSITY_CASE(9) DENSITY_CASE(10) DENSITY_CASE(11) DENSITY_CASE(12) DENSITY_CASE(13) DENSITY_CASE(14) DENSITY_CASE(15) DENSITY_CASE(16)
+#undef DENSITY_CASE
+    }
+}
+
+extern "C" int ivit_density_degree(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, float threshold, int splits,
+                                   void *workspace, size_t bytes, int32_t *degree) {
+    CHECK_H(h);
+    REQUIRE(h, x && workspace && degree, "x, workspace or degree is null");
+    DensityArgs a;
+    DensityLayout l;
+    if (const int rc = density_args_ok(h, __func__, x, rows, dim, weight, threshold, splits, workspace, bytes, &a, &l)) return rc;
+    REQUIRE_ALIGNED(h, degree, "degree", 4);
+    const DensityRange r[4] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {workspace, bytes, "workspace"},
+                               {degree, (size_t)rows * 4, "degree"}};
+    if (const int rc = density_disjoint(h, __func__, r, 2, 4)) return rc;
+    density_scan_dispatch<DENSITY_DEGREE>(h, dim, a);
+    LAUNCH_CHECK(h);
+    const DensityFoldArgs f = {a.part, nullptr, degree, rows, a.parts};
+    density_fold_kernel<DENSITY_DEGREE><<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(f);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_density_init(ivit_handle h, const int32_t *degree, int64_t rows, int32_t min_pts, int32_t *label, uint64_t *dirty) {
+    CHECK_H(h);
+    REQUIRE(h, degree && label && dirty, "degree, label or dirty is null");
+    REQUIRE(h, rows >= 1 && rows <= 0x7fffffffLL, "rows must be in 1 .. 2^31 - 1");
+    REQUIRE(h, min_pts >= 1, "min_pts must be at least 1");
+    REQUIRE_ALIGNED(h, degree, "degree", 4);
+    REQUIRE_ALIGNED(h, label, "label", 4);
+    REQUIRE_ALIGNED(h, dirty, "dirty", 8);
+    const long long words = (rows + DENSITY_WORD_ROWS - 1) / DENSITY_WORD_ROWS;
+    const DensityRange r[3] = {{degree, (size_t)rows * 4, "degree"}, {label, (size_t)rows * 4, "label"}, {dirty, (size_t)words * 8, "dirty"}};
+    if (const int rc = density_disjoint(h, __func__, r, 1, 3)) return rc;
+    density_init_kernel<<<(unsigned)words, 256, 0, h->stream>>>(degree, rows, min_pts, label, (unsigned long long *)dirty);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_density_sweep(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, float threshold, int splits,
+                                  void *workspace, size_t bytes, const int32_t *label_in, const uint64_t *dirty_in, int32_t *label_out,
+                                  uint64_t *dirty_out, int32_t *changed) {
+    CHECK_H(h);
+    REQUIRE(h, x && workspace && label_in && dirty_in && label_out && dirty_out && changed,
+            "x, workspace, label_in, dirty_in, label_out, dirty_out or changed is null");
+    DensityArgs a;
+    DensityLayout l;
+    if (const int rc = density_args_ok(h, __func__, x, rows, dim, weight, threshold, splits, workspace, bytes, &a, &l)) return rc;
+    REQUIRE_ALIGNED(h, label_in, "label_in", 4);
+    REQUIRE_ALIGNED(h, label_out, "label_out", 4);
+    REQUIRE_ALIGNED(h, changed, "changed", 4);
+    REQUIRE_ALIGNED(h, dirty_in, "dirty_in", 8);
+    REQUIRE_ALIGNED(h, dirty_out, "dirty_out", 8);
+    const DensityRange r[8] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {label_in, (size_t)rows * 4, "label_in"},
+                               {dirty_in, (size_t)l.words * 8, "dirty_in"}, {workspace, bytes, "workspace"}, {label_out, (size_t)rows * 4, "label_out"},
+                               {dirty_out, (size_t)l.words * 8, "dirty_out"}, {changed, 4, "changed"}};
+    if (const int rc = density_disjoint(h, __func__, r, 4, 8)) return rc;
+    a.label = label_in; a.dirty = (const unsigned long long *)dirty_in;
+    int *m = (int *)((char *)workspace + l.m);
+    unsigned char *flag = (unsigned char *)workspace + l.flag;
+    density_scan_dispatch<DENSITY_SWEEP>(h, dim, a);
+    LAUNCH_CHECK(h);
+    const DensityFoldArgs f = {a.part, nullptr, m, rows, a.parts};
+    density_fold_kernel<DENSITY_SWEEP><<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(f);
+    LAUNCH_CHECK(h);
+    density_jump_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(m, label_in, label_out, flag, rows, l.tiles);
+    LAUNCH_CHECK(h);
+    density_pack_kernel<<<1, 256, 0, h->stream>>>(flag, l.tiles, (unsigned long long *)dirty_out, changed);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_density_border(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, float threshold, int splits,
+                                   void *workspace, size_t bytes, const int32_t *label, int32_t *out) {
+    CHECK_H(h);
+    REQUIRE(h, x && workspace && label && out, "x, workspace, label or out is null");
+    DensityArgs a;
+    DensityLayout l;
+    if (const int rc = density_args_ok(h, __func__, x, rows, dim, weight, threshold, splits, workspace, bytes, &a, &l)) return rc;
+    REQUIRE_ALIGNED(h, label, "label", 4);
+    REQUIRE_ALIGNED(h, out, "out", 4);
+    const DensityRange r[5] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {label, (size_t)rows * 4, "label"},
+                               {workspace, bytes, "workspace"}, {out, (size_t)rows * 4, "out"}};
+    if (const int rc = density_disjoint(h, __func__, r, 3, 5)) return rc;
+    a.label = label;
+    density_scan_dispatch<DENSITY_BORDER>(h, dim, a);
+    LAUNCH_CHECK(h);
+    const DensityFoldArgs f = {a.part, label, out, rows, a.parts};
+    density_fold_kernel<DENSITY_BORDER><<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(f);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

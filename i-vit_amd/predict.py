@@ -800,3 +800,56 @@ def find_duplicates(engine, batches, threshold, transform=None):
     feat8, _ = embed8(engine, batches, transform)
     pairs, val = duplicates(feat8, threshold, cosine=True)
     return pairs, val, feat8
+
+
+def dbscan_reference(x8, weight, threshold, min_pts):
+    """x8 int8 [rows, dim], weight float32 [rows] or None -> (label int32 [rows], core bool [rows], degree int32 [rows]): the numpy
+    statement of include/ivit_density.h.
+
+    dot[i, j] = x8[i] . x8[j] as an exact integer; for i <= j, v{i, j} = fl32(fl32(fl32(dot) * weight[j]) * weight[i]): two float32
+    multiplies, FIRST the weight of the larger index, then that of the smaller (a None weight: both left out) — the value
+    `range_reference(x8, x8, weight, weight, ...)` gives the pair (query i, gallery j), and symmetric by construction.  i and j are
+    neighbours when v{i, j} >= threshold (the IEEE comparison; i == j where its own value passes); degree[i] counts the neighbours
+    of i, core[i] = degree[i] >= min_pts.  A core row's label is the smallest row of its connected component in the graph of
+    core-core neighbour pairs; any other row with a core neighbour takes the smallest label among its core neighbours; every other
+    row is -1.  threshold must be finite, min_pts >= 1."""
+    x = np.asarray(x8)
+    assert x.ndim == 2 and x.dtype == np.int8 and x.shape[0] >= 1
+    rows = x.shape[0]
+    threshold = np.float32(threshold)
+    if not np.isfinite(threshold):
+        raise ValueError("threshold must be finite")
+    if int(min_pts) < 1:
+        raise ValueError("min_pts must be at least 1")
+    v = (x.astype(np.int32) @ x.astype(np.int32).T).astype(np.float32)
+    if weight is not None:
+        weight = np.asarray(weight, dtype=np.float32)
+        assert weight.shape == (rows,)
+        i, j = np.minimum.outer(np.arange(rows), np.arange(rows)), np.maximum.outer(np.arange(rows), np.arange(rows))
+        v = (v * weight[j]) * weight[i]                               # the larger row's weight first: two float32 multiplies
+    assert v.dtype == np.float32
+    adj = v >= threshold
+    assert np.array_equal(adj, adj.T)
+    degree = adj.sum(axis=1).astype(np.int32)
+    core = degree >= int(min_pts)
+    none = np.iinfo(np.int32).max
+    label = np.where(core, np.arange(rows), none).astype(np.int64)
+    among = adj & core[None, :]                                       # [i, j]: j is a core neighbour of i
+    while True:                                                       # the minimum over the core neighbours until nothing falls
+        new = np.where(core, np.minimum(label, np.where(among, label[None, :], none).min(axis=1)), none)
+        if np.array_equal(new, label):
+            break
+        label = new
+    border = np.where(among, label[None, :], none).min(axis=1)
+    label = np.where(core, label, np.where(border == none, -1, border))
+    return label.astype(np.int32), core, degree
+
+
+def dbscan_fit(engine, batches, threshold, min_pts, transform=None):
+    """`embed8`'s loop followed by `cluster.dbscan` on the cosine of the int8 features: returns (label int32 [N], core bool [N],
+    degree int32 [N], feat8) on the engine's device, as `dbscan_reference(feat8, inv_norms_reference(feat8), threshold, min_pts)`
+    states them."""
+    from .cluster import dbscan
+    feat8, _ = embed8(engine, batches, transform)
+    label, core, degree, _ = dbscan(feat8, threshold, min_pts, cosine=True)
+    return label, core, degree, feat8

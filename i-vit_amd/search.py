@@ -4,7 +4,8 @@ chunk with `ivit_search_merge` behind when it was given in pieces; `knn_classify
 for a frozen backbone on the small [B, k] results, `knn_reference` its numpy statement.  The numpy statements of the search itself
 are `predict.search_reference` and `predict.inv_norms_reference`.  `Gallery.within` is the threshold form (include/ivit_range.h: all
 rows with a score >= threshold, in CSR form, `predict.range_reference` its numpy statement), `duplicates` / `cross_matches` the
-self-join and the join of two sets built on it, `duplicate_groups` the connected components of the pairs (host).  torch is used for
+self-join and the join of two sets built on it, `duplicate_groups` the connected components of the pairs (host),
+`duplicate_groups_device` the same components from the rows themselves (include/ivit_density.h).  torch is used for
 device memory and streams, for the vote and for laying the chunks' rows side by side."""
 import ctypes
 
@@ -266,6 +267,16 @@ def duplicate_groups(pairs, n):
         if np.array_equal(new, group):
             return group
         group = new
+
+
+def duplicate_groups_device(feat8, threshold, cosine=True):
+    """feat8 int8 device tensor [N, dim] -> int32 [N] on the device: `duplicate_groups(duplicates(feat8, threshold, cosine)[0], N)`
+    entry for entry — for every row the smallest row of its connected component — without the pair list and without the host:
+    `cluster.dbscan` at min_pts = 1 (include/ivit_density.h), where every row is core."""
+    from .cluster import dbscan
+    label = dbscan(feat8, threshold, 1, cosine=cosine)[0]
+    # a row without a neighbour that does not pass the threshold itself (a row of zeros) is noise there and its own group here
+    return torch.where(label < 0, torch.arange(label.shape[0], dtype=label.dtype, device=label.device), label)
 
 
 def knn_classify(idx, val, labels, num_classes, T=0.07, query_inv_norm=None):
