@@ -30,6 +30,7 @@ Standard library only, so a tool loads this file without the package (and withou
     LOGREG_ABI      the same of include/ivit_logreg.h, the sixteenth (IVIT_LOGREG_VERSION)
     GAUSS_ABI       the same of include/ivit_gauss.h, the seventeenth (IVIT_GAUSS_VERSION)
     DENSITY_ABI     the same of include/ivit_density.h, the eighteenth (IVIT_DENSITY_VERSION)
+    LINKAGE_ABI     the same of include/ivit_linkage.h, the nineteenth (IVIT_LINKAGE_VERSION)
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -65,6 +66,7 @@ SEED_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_seed.h")
 LOGREG_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_logreg.h")
 GAUSS_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_gauss.h")
 DENSITY_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_density.h")
+LINKAGE_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_linkage.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -236,3 +238,5 @@ with open(GAUSS_HEADER) as _f:
     GAUSS_ABI = parse(_f.read(), base=ABI)
 with open(DENSITY_HEADER) as _f:
     DENSITY_ABI = parse(_f.read(), base=ABI)
+with open(LINKAGE_HEADER) as _f:
+    LINKAGE_ABI = parse(_f.read(), base=ABI)

@@ -437,3 +437,94 @@ def compact_labels(label):
     names = torch.unique(label[label >= 0])                            # sorted
     compact = torch.where(label >= 0, torch.searchsorted(names, label.clamp(min=0)), torch.full_like(label, -1))
     return compact.to(torch.int32), int(names.shape[0])
+
+
+# ---------------------------------------------------------------- single-linkage hierarchy (include/ivit_linkage.h)
+class Linkage:
+    """The spanning forest of a single-linkage hierarchy over `rows` rows: u < v int32 [E] and val float32 [E], the edges in the edge
+    order of include/ivit_linkage.h (val descending, then u, then v ascending), as tensors (on the device from `single_linkage`; numpy
+    arrays are taken as host tensors); `rounds`: the Borůvka rounds that merged something."""
+
+    def __init__(self, u, v, val, rows, rounds=0):
+        self.u, self.v, self.val = (torch.as_tensor(t) for t in (u, v, val))
+        self.rows, self.rounds = int(rows), int(rounds)
+
+    def _groups(self, keep):
+        from .search import duplicate_groups
+        return duplicate_groups(torch.stack([self.u[keep], self.v[keep]], 1), self.rows)
+
+    def cut(self, threshold):
+        """int64 [rows] on the host: for every row the smallest row it is connected to through edges with val >= threshold — the
+        components of the graph v >= threshold, `search.duplicate_groups` of `search.duplicates` at that threshold, for ANY threshold at
+        or above the floor the forest was built with."""
+        return self._groups(self.val >= torch.tensor(float(np.float32(threshold)), dtype=torch.float32, device=self.val.device))
+
+    def cut_k(self, n_clusters):
+        """the same after removing the n_clusters - 1 last edges in the edge order: n_clusters groups of a tree (a forest built with a
+        floor starts from its own components)"""
+        if int(n_clusters) < 1:
+            raise ValueError("n_clusters must be at least 1")
+        return self._groups(slice(0, max(0, self.u.shape[0] - (int(n_clusters) - 1))))
+
+    def matrix(self):
+        """float64 [E, 4] on the host, in plain numpy: the linkage matrix in SciPy's convention — step s joins clusters Z[s, 0] < Z[s, 1]
+        (a row, or rows + t for the cluster step t made) at distance Z[s, 2] = -val into one of Z[s, 3] rows — the edges taken in the
+        edge order."""
+        u, v, val = (t.cpu().numpy() for t in (self.u, self.v, self.val))
+        root, name, size = list(range(self.rows)), list(range(self.rows)), [1] * self.rows
+        Z = np.zeros((len(u), 4), np.float64)
+
+        def find(a):
+            while root[a] != a:
+                root[a] = root[root[a]]
+                a = root[a]
+            return a
+        for s in range(len(u)):
+            a, b = find(int(u[s])), find(int(v[s]))
+            Z[s] = min(name[a], name[b]), max(name[a], name[b]), -np.float64(val[s]), size[a] + size[b]
+            root[b], name[a], size[a] = a, self.rows + s, size[a] + size[b]
+        return Z
+
+
+def single_linkage(feat8, cosine=True, floor=None, splits=0, check_every=1):
+    """The single-linkage hierarchy of the rows of feat8 (a contiguous int8 device tensor [rows, dim]) ON THE DEVICE, as
+    `predict.linkage_reference` states it, with the rows' inverse norms (ivit_gallery_inv_norms) as the weight for cosine=True and none
+    for the exact integer dot product; floor None is -infinity (a tree of rows - 1 edges).  ivit_linkage_init, then batches of
+    `check_every` ivit_linkage_round with ONE read of `state` per batch (the only synchronisations) until it reports merged == 0 or one
+    component; a round past the end leaves at once.  The edges depend neither on check_every nor on `splits`.  Memory is O(rows).  The
+    empty slots are dropped and the edges sorted into the edge order with stable torch sorts.  Returns a `Linkage`."""
+    if not isinstance(feat8, torch.Tensor) or feat8.dtype != torch.int8 or feat8.dim() != 2 or not feat8.is_cuda or not feat8.is_contiguous():
+        raise ValueError("feat8: a contiguous int8 device tensor [rows, dim]")
+    rows, dim, dev = int(feat8.shape[0]), int(feat8.shape[1]), feat8.device
+    if rows < 1:
+        raise ValueError("feat8 holds no row")
+    floor = float("-inf") if floor is None else float(np.float32(floor))
+    if math.isnan(floor):
+        raise ValueError("floor must not be NaN")
+    if int(check_every) < 1:
+        raise ValueError("check_every must be at least 1")
+    h = _lib.Handle(dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    n = ctypes.c_size_t()
+    h.call("ivit_linkage_workspace_bytes", rows, dim, int(splits), ctypes.byref(n))
+    new = lambda dt, *shape: torch.empty(*shape, dtype=dt, device=dev)      # noqa: E731
+    ws = new(torch.uint8, n.value)
+    weight = None
+    if cosine:
+        weight = new(torch.float32, rows)
+        h.call("ivit_gallery_inv_norms", _ptr(feat8), rows, dim, _ptr(weight))
+    comp, done, state = new(torch.int32, rows), new(torch.uint8, rows), new(torch.int32, 4)
+    u, v, val = new(torch.int32, rows), new(torch.int32, rows), new(torch.float32, rows)
+    run = tuple(_ptr(t) for t in (comp, done, u, v, val, state))
+    h.call("ivit_linkage_init", rows, *run)
+    while True:
+        for _ in range(int(check_every)):
+            h.call("ivit_linkage_round", _ptr(feat8), rows, dim, _ptr(weight), floor, int(splits), _ptr(ws), n.value, *run)
+        components, merged, rounds, _ = state.tolist()                  # the one read of a batch
+        if merged == 0 or components == 1:
+            break
+    keep = u >= 0
+    edges = [u[keep], v[keep], val[keep]]
+    for key, descending in ((1, False), (0, False), (2, True)):         # v, then u, then val: the last sort is the first criterion
+        order = torch.sort(edges[key], stable=True, descending=descending)[1]
+        edges = [t[order] for t in edges]
+    return Linkage(*edges, rows, rounds)

@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h, include/ivit_density.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h, include/ivit_density.h, include/ivit_linkage.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -50,6 +50,7 @@
 #include "ivit_logreg.h"
 #include "ivit_gauss.h"
 #include "ivit_density.h"
+#include "ivit_linkage.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -3639,6 +3640,106 @@ extern "C" int ivit_density_border(ivit_handle h, const int8_t *x, int64_t rows,
     LAUNCH_CHECK(h);
     const DensityFoldArgs f = {a.part, label, out, rows, a.parts};
     density_fold_kernel<DENSITY_BORDER><<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(f);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+// ---------------------------------------------------------------- single-linkage hierarchy (include/ivit_linkage.h)
+// the workspace: the rows * parts 64-bit keys of a scan, then per row a 64-bit key (rbest), a 64-bit edge (cedge), a 32-bit value
+// (cbest) and a 32-bit parent (each array a multiple of 16 bytes).  The parts are ivit_density.h's (density_shape_ok).
+struct LinkageLayout {
+    DensityLayout d;
+    size_t rbest, cedge, cbest, parent, bytes;
+};
+
+static int linkage_shape_ok(ivit_handle h, const char *fn, long long rows, int dim, int splits, LinkageLayout *l) {
+    if (const int rc = density_shape_ok(h, fn, rows, dim, splits, &l->d)) return rc;
+    const size_t r8 = ((size_t)rows * 8 + 15) & ~(size_t)15, r4 = ((size_t)rows * 4 + 15) & ~(size_t)15;
+    l->rbest = ((size_t)rows * l->d.parts * 8 + 15) & ~(size_t)15;
+    l->cedge = l->rbest + r8;
+    l->cbest = l->cedge + r8;
+    l->parent = l->cbest + r4;
+    l->bytes = l->parent + r4;
+    return IVIT_OK;
+}
+
+extern "C" int ivit_linkage_workspace_bytes(ivit_handle h, int64_t rows, int dim, int splits, size_t *bytes) {
+    CHECK_H(h);
+    REQUIRE(h, bytes, "bytes is null");
+    LinkageLayout l;
+    if (const int rc = linkage_shape_ok(h, __func__, rows, dim, splits, &l)) return rc;
+    *bytes = l.bytes;
+    return IVIT_OK;
+}
+
+// the six arrays a run owns, aligned and disjoint from each other and from what stands in front of them in r (n_in inputs)
+static int linkage_outputs_ok(ivit_handle h, const char *fn, DensityRange *r, int n_in, long long rows, int32_t *comp, uint8_t *done, int32_t *edge_u,
+                              int32_t *edge_v, float *edge_val, int32_t *state) {
+    const DensityRange outs[6] = {{comp, (size_t)rows * 4, "comp"}, {done, (size_t)rows, "done"}, {edge_u, (size_t)rows * 4, "edge_u"},
+                                  {edge_v, (size_t)rows * 4, "edge_v"}, {edge_val, (size_t)rows * 4, "edge_val"}, {state, 16, "state"}};
+    for (int i = 0; i < 6; ++i) {
+        if (i != 1 && ((uintptr_t)outs[i].p & 3)) {
+            snprintf(h->err, sizeof(h->err), "%s: %s must be 4-byte aligned", fn, outs[i].name);
+            return IVIT_ERR_INVALID;
+        }
+        r[n_in + i] = outs[i];
+    }
+    return IVIT_OK;
+}
+
+extern "C" int ivit_linkage_init(ivit_handle h, int64_t rows, int32_t *comp, uint8_t *done, int32_t *edge_u, int32_t *edge_v, float *edge_val,
+                                 int32_t *state) {
+    CHECK_H(h);
+    REQUIRE(h, comp && done && edge_u && edge_v && edge_val && state, "comp, done, edge_u, edge_v, edge_val or state is null");
+    REQUIRE(h, rows >= 1 && rows <= 0x7fffffffLL, "rows must be in 1 .. 2^31 - 1");
+    DensityRange r[6];
+    if (const int rc = linkage_outputs_ok(h, __func__, r, 0, rows, comp, done, edge_u, edge_v, edge_val, state)) return rc;
+    if (const int rc = density_disjoint(h, __func__, r, 0, 6)) return rc;
+    LinkageArgs a = {};
+    a.comp = comp; a.done = done; a.edge_u = edge_u; a.edge_v = edge_v; a.edge_val = edge_val; a.state = state; a.rows = rows;
+    linkage_init_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_linkage_round(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, float floor, int splits, void *workspace,
+                                  size_t bytes, int32_t *comp, uint8_t *done, int32_t *edge_u, int32_t *edge_v, float *edge_val, int32_t *state) {
+    CHECK_H(h);
+    REQUIRE(h, x && workspace && comp && done && edge_u && edge_v && edge_val && state,
+            "x, workspace, comp, done, edge_u, edge_v, edge_val or state is null");
+    LinkageLayout l;
+    if (const int rc = linkage_shape_ok(h, __func__, rows, dim, splits, &l)) return rc;
+    REQUIRE(h, floor == floor, "floor must not be NaN");
+    REQUIRE(h, bytes >= l.bytes, "workspace too small (ivit_linkage_workspace_bytes)");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, workspace, "workspace");
+    DensityRange r[9] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {workspace, bytes, "workspace"}};
+    if (const int rc = linkage_outputs_ok(h, __func__, r, 3, rows, comp, done, edge_u, edge_v, edge_val, state)) return rc;
+    if (const int rc = density_disjoint(h, __func__, r, 2, 9)) return rc;
+    LinkageArgs a = {};
+    char *ws = (char *)workspace;
+    a.x = x; a.weight = weight; a.comp = comp; a.done = done; a.edge_u = edge_u; a.edge_v = edge_v; a.edge_val = edge_val; a.state = state;
+    a.part = (unsigned long long *)ws; a.rbest = (unsigned long long *)(ws + l.rbest); a.cedge = (unsigned long long *)(ws + l.cedge);
+    a.cbest = (unsigned *)(ws + l.cbest); a.parent = (int *)(ws + l.parent);
+    a.rows = rows; a.tiles = l.d.tiles; a.per = l.d.per; a.floor = floor; a.parts = l.d.parts;
+    const dim3 grid((unsigned)((rows + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
+    const unsigned per_row = (unsigned)((rows + 255) / 256);
+    switch (dim / 64) {
+#define LINKAGE_CASE(KS) case KS: linkage_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS)><<<grid, 256, 0, h->stream>>>(a); break;
+        LINKAGE_CASE(1) LINKAGE_CASE(2) LINKAGE_CASE(3) LINKAGE_CASE(4) LINKAGE_CASE(5) LINKAGE_CASE(6) LINKAGE_CASE(7) LINKAGE_CASE(8)
+        LINKAGE_CASE(9) LINKAGE_CASE(10) LINKAGE_CASE(11) LINKAGE_CASE(12) LINKAGE_CASE(13) LINKAGE_CASE(14) LINKAGE_CASE(15) LINKAGE_CASE(16)
+#undef LINKAGE_CASE
+    }
+    LAUNCH_CHECK(h);
+    linkage_fold_kernel<<<per_row, 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    linkage_pick_kernel<<<per_row, 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    linkage_hook_kernel<<<per_row, 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    linkage_jump_kernel<<<per_row, 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    linkage_finish_kernel<<<1, 1, 0, h->stream>>>(state);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }

@@ -853,3 +853,57 @@ def dbscan_fit(engine, batches, threshold, min_pts, transform=None):
     feat8, _ = embed8(engine, batches, transform)
     label, core, degree, _ = dbscan(feat8, threshold, min_pts, cosine=True)
     return label, core, degree, feat8
+
+
+def linkage_reference(x8, weight, floor=None):
+    """x8 int8 [rows, dim], weight float32 [rows] or None -> (u int32 [E], v int32 [E], val float32 [E]): the numpy statement of
+    include/ivit_linkage.h, the single-linkage hierarchy as its spanning forest.
+
+    The values v{i, j} are `dbscan_reference`'s (the larger row's weight first), -0.0 counted and reported as +0.0.  An edge is a pair
+    i < j with v{i, j} >= floor (None: -infinity; NaN is refused); the edges are totally ordered by v descending, then i ascending,
+    then j ascending (np.lexsort), and Kruskal's algorithm takes them in that order, keeping an edge when it joins two components (a
+    union-find).  Returns the kept edges in the edge order: rows - 1 of them at floor = -infinity."""
+    x = np.asarray(x8)
+    assert x.ndim == 2 and x.dtype == np.int8 and x.shape[0] >= 1
+    rows = x.shape[0]
+    floor = np.float32(-np.inf if floor is None else floor)
+    if np.isnan(floor):
+        raise ValueError("floor must not be NaN")
+    val = (x.astype(np.int32) @ x.astype(np.int32).T).astype(np.float32)
+    i, j = np.triu_indices(rows, 1)
+    val = val[i, j]
+    if weight is not None:
+        weight = np.asarray(weight, dtype=np.float32)
+        assert weight.shape == (rows,)
+        val = (val * weight[j]) * weight[i]                           # the larger row's weight first: two float32 multiplies
+    val = val + np.float32(0)                                         # -0.0 -> +0.0
+    assert val.dtype == np.float32
+    keep = val >= floor
+    i, j, val = i[keep], j[keep], val[keep]
+    order = np.lexsort((j, i, -val))                                  # the last key is the first criterion
+    root = list(range(rows))
+
+    def find(a):
+        while root[a] != a:
+            root[a] = root[root[a]]
+            a = root[a]
+        return a
+    kept = []
+    for e in order.tolist():
+        a, b = find(int(i[e])), find(int(j[e]))
+        if a != b:
+            root[max(a, b)] = min(a, b)
+            kept.append(e)
+            if len(kept) == rows - 1:
+                break
+    kept = np.asarray(kept, np.int64)
+    return i[kept].astype(np.int32), j[kept].astype(np.int32), val[kept]
+
+
+def linkage_fit(engine, batches, floor=None, transform=None):
+    """`embed8`'s loop followed by `cluster.single_linkage` on the cosine of the int8 features: returns (linkage, feat8), the
+    `cluster.Linkage` of the images on the engine's device, as `linkage_reference(feat8, inv_norms_reference(feat8), floor)` states
+    its edges."""
+    from .cluster import single_linkage
+    feat8, _ = embed8(engine, batches, transform)
+    return single_linkage(feat8, cosine=True, floor=floor), feat8
