@@ -31,6 +31,8 @@ Standard library only, so a tool loads this file without the package (and withou
     GAUSS_ABI       the same of include/ivit_gauss.h, the seventeenth (IVIT_GAUSS_VERSION)
     DENSITY_ABI     the same of include/ivit_density.h, the eighteenth (IVIT_DENSITY_VERSION)
     LINKAGE_ABI     the same of include/ivit_linkage.h, the nineteenth (IVIT_LINKAGE_VERSION)
+    HDBSCAN_ABI     the same of include/ivit_hdbscan.h, the twentieth (IVIT_HDBSCAN_VERSION); it includes ivit_linkage.h, whose entries
+                    stay LINKAGE_ABI's
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -67,6 +69,7 @@ LOGREG_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_logreg.h")
 GAUSS_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_gauss.h")
 DENSITY_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_density.h")
 LINKAGE_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_linkage.h")
+HDBSCAN_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_hdbscan.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -240,3 +243,5 @@ with open(DENSITY_HEADER) as _f:
     DENSITY_ABI = parse(_f.read(), base=ABI)
 with open(LINKAGE_HEADER) as _f:
     LINKAGE_ABI = parse(_f.read(), base=ABI)
+with open(HDBSCAN_HEADER) as _f:
+    HDBSCAN_ABI = parse(_f.read(), base=ABI)

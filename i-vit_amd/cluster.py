@@ -485,6 +485,179 @@ class Linkage:
             root[b], name[a], size[a] = a, self.rows + s, size[a] + size[b]
         return Z
 
+    def condense(self, min_cluster_size, floor=None):
+        """the `CondensedTree` of this forest as `predict.hdbscan_labels_reference` states it, in plain numpy / Python on the host: Kruskal
+        over GROUPS of equal value (the levels, so no tie order enters), then the walk from the roots.  `floor`: the floor the forest was
+        built with (the roots' birth); None: the lowest edge value."""
+        return CondensedTree(self, min_cluster_size, floor)
+
+
+class CondensedTree:
+    """The condensed tree of HDBSCAN over a `Linkage` (the forest of the mutual-reachability values): cluster c is number rows + c.
+      parent, child, lam, size   int64, int64, float32, int64 [entries]: `child` (a row, size 1, or a cluster with `size` rows) leaves or
+                                 is born out of cluster `parent` at level `lam`
+      birth, name                float32, int64 [clusters]: the level a cluster is born at and its smallest row
+      up                         int64 [clusters]: the parent cluster's number, -1 for a root
+      stability                  float64 [clusters]: math.fsum of float64(lam) - float64(birth) over the rows that leave the cluster,
+                                 one term per row, those that enter a child cluster included
+    Levels, not a binary merge order, define it: the edges of one value are united together and the clusters they join become the
+    children of ONE node."""
+
+    def __init__(self, tree, min_cluster_size, floor=None):
+        mcs, rows = int(min_cluster_size), tree.rows
+        if mcs < 2:
+            raise ValueError("min_cluster_size must be at least 2")
+        u, v, val = (t.cpu().numpy() for t in (tree.u, tree.v, tree.val))
+        self.rows, self.min_cluster_size = rows, mcs
+        # the level dendrogram: node n < rows is row n; a later node holds the nodes one level joined
+        root, node = list(range(rows)), list(range(rows))
+        kids, level, size, low = [None] * rows, [None] * rows, [1] * rows, list(range(rows))
+
+        def find(a):
+            while root[a] != a:
+                root[a] = root[root[a]]
+                a = root[a]
+            return a
+        s = 0
+        while s < len(u):
+            e = s
+            while e < len(u) and val[e] == val[s]:
+                e += 1
+            old = sorted({find(int(a)) for a in u[s:e]} | {find(int(a)) for a in v[s:e]})
+            joined = [node[a] for a in old]
+            for a, b in zip(u[s:e].tolist(), v[s:e].tolist()):
+                a, b = find(a), find(b)
+                root[max(a, b)] = min(a, b)
+            groups = {}
+            for a, n in zip(old, joined):
+                groups.setdefault(find(a), []).append(n)
+            for a, ns in groups.items():
+                node[a] = len(kids)
+                kids.append(ns)
+                level.append(val[s])
+                size.append(sum(size[n] for n in ns))
+                low.append(min(low[n] for n in ns))
+            s = e
+
+        def leaves(n):
+            out, todo = [], [n]
+            while todo:
+                n = todo.pop()
+                if n < rows:
+                    out.append(n)
+                else:
+                    todo.extend(kids[n])
+            return out
+        base = np.float32(floor) if floor is not None else (val[-1] if len(val) else np.float32(0))
+        parent, child, lam, csize, birth, name, up = [], [], [], [], [], [], []
+        todo = []
+        for a in sorted({find(q) for q in range(rows)}):
+            if size[node[a]] >= mcs:
+                todo.append((len(birth), node[a]))
+                birth.append(base), name.append(low[node[a]]), up.append(-1)
+        while todo:
+            c, n = todo.pop()
+            while True:
+                big = [k for k in kids[n] if size[k] >= mcs]
+                for k in kids[n]:
+                    if size[k] < mcs or len(big) == 0:
+                        for q in leaves(k):
+                            parent.append(rows + c), child.append(q), lam.append(level[n]), csize.append(1)
+                if len(big) != 1:
+                    break
+                n = big[0]
+            if len(big) >= 2:
+                for k in big:
+                    parent.append(rows + c), child.append(rows + len(birth)), lam.append(level[n]), csize.append(size[k])
+                    todo.append((len(birth), k))
+                    birth.append(level[n]), name.append(low[k]), up.append(c)
+        self.parent, self.child, self.size = (np.asarray(a, np.int64) for a in (parent, child, csize))
+        self.lam, self.birth = np.asarray(lam, np.float32), np.asarray(birth, np.float32)
+        self.name, self.up = np.asarray(name, np.int64), np.asarray(up, np.int64)
+        terms = [[] for _ in birth]
+        for p, l, n in zip(parent, lam, csize):
+            terms[p - rows] += [float(np.float64(l) - np.float64(birth[p - rows]))] * n
+        self.stability = np.asarray([math.fsum(t) for t in terms], np.float64)
+
+    def select(self, method="eom", allow_single_cluster=False):
+        """int32 [rows] on the host: the smallest row of the selected cluster a row belongs to, -1 for noise.  "eom": bottom-up, a leaf
+        is selected, an inner cluster is selected and its descendants unselected unless the fsum of its children's subtree totals is
+        STRICTLY greater than its stability; "leaf": the leaves.  Where there is exactly one root it is selectable only with
+        allow_single_cluster."""
+        if method not in ("eom", "leaf"):
+            raise ValueError(f"method = {method!r}: 'eom' or 'leaf'")
+        n = len(self.birth)
+        children = [[] for _ in range(n)]
+        for c in range(n):
+            if self.up[c] >= 0:
+                children[self.up[c]].append(c)
+        single = int((self.up < 0).sum()) == 1 and not allow_single_cluster
+        total, chosen = [0.0] * n, [False] * n
+        for c in range(n - 1, -1, -1):                                  # a child's number is above its parent's
+            selectable = not (single and self.up[c] < 0)
+            below = math.fsum(total[k] for k in children[c])
+            if not children[c]:
+                chosen[c], total[c] = selectable, float(self.stability[c]) if selectable else 0.0
+            elif method == "leaf" or not selectable or below > self.stability[c]:
+                total[c] = below
+            else:
+                chosen[c], total[c] = True, float(self.stability[c])
+        owner = np.full(n, -1, np.int64)                                # the selected cluster at or above each cluster, top-down
+        for c in range(n):
+            owner[c] = owner[self.up[c]] if self.up[c] >= 0 and owner[self.up[c]] >= 0 else (self.name[c] if chosen[c] else -1)
+        label = np.full(self.rows, -1, np.int32)
+        is_row = self.child < self.rows
+        label[self.child[is_row]] = owner[self.parent[is_row] - self.rows]
+        return label
+
+
+def _hdbscan_setup(feat8, cosine, splits):
+    if not isinstance(feat8, torch.Tensor) or feat8.dtype != torch.int8 or feat8.dim() != 2 or not feat8.is_cuda or not feat8.is_contiguous():
+        raise ValueError("feat8: a contiguous int8 device tensor [rows, dim]")
+    rows, dim, dev = int(feat8.shape[0]), int(feat8.shape[1]), feat8.device
+    if rows < 1:
+        raise ValueError("feat8 holds no row")
+    h = _lib.Handle(dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    weight = None
+    if cosine:
+        weight = torch.empty(rows, dtype=torch.float32, device=dev)
+        h.call("ivit_gallery_inv_norms", _ptr(feat8), rows, dim, _ptr(weight))
+    return h, rows, dim, dev, weight
+
+
+def _core(h, feat8, rows, dim, weight, min_pts, splits):
+    n = ctypes.c_size_t()
+    h.call("ivit_core_workspace_bytes", rows, dim, int(min_pts), int(splits), ctypes.byref(n))
+    ws, core = torch.empty(n.value, dtype=torch.uint8, device=feat8.device), torch.empty(rows, dtype=torch.float32, device=feat8.device)
+    h.call("ivit_core_similarity", _ptr(feat8), rows, dim, _ptr(weight), int(min_pts), int(splits), _ptr(ws), n.value, _ptr(core))
+    ws.record_stream(torch.cuda.current_stream(feat8.device))           # freed here, read by the queued launches
+    return core
+
+
+def core_similarity(feat8, min_pts, cosine=True, splits=0):
+    """float32 [rows] on the device: for every row of feat8 (a contiguous int8 device tensor [rows, dim]) its min_pts-th largest value
+    among all rows, itself included and equal values with their multiplicity, as `predict.mutual_reachability_reference` states it
+    (ivit_core_similarity; min_pts in 1 .. min(rows, 64)).  `degree >= min_pts` of `dbscan` at a threshold t is `core >= t`.  Queued
+    on the current stream, nothing synchronised."""
+    h, rows, dim, _, weight = _hdbscan_setup(feat8, cosine, splits)
+    return _core(h, feat8, rows, dim, weight, min_pts, splits)
+
+
+def hdbscan(feat8, min_cluster_size=5, min_pts=None, cosine=True, floor=None, selection="eom", allow_single_cluster=False, splits=0, check_every=1):
+    """HDBSCAN over the rows of feat8 (a contiguous int8 device tensor [rows, dim]) as `predict.hdbscan_reference` and
+    `predict.hdbscan_labels_reference` state it; min_pts defaults to min_cluster_size (clipped to the rows).  ON THE DEVICE:
+    ivit_core_similarity, ivit_linkage_init, then batches of `check_every` ivit_reach_round with one read of `state` per batch, as
+    `single_linkage`; the edges are sorted into the edge order there too.  ON THE HOST over those rows - 1 edges: `Linkage.condense`
+    and `CondensedTree.select`.  Memory is O(rows); nothing depends on `splits` or `check_every`.  Returns (label int32 [rows] on the
+    device: the smallest row of the row's cluster, -1 for noise — `compact_labels` numbers them; core float32 [rows]; tree: the
+    `Linkage` of the mutual-reachability forest; condensed: the `CondensedTree`)."""
+    h, rows, dim, dev, weight = _hdbscan_setup(feat8, cosine, splits)
+    min_pts = min(int(min_cluster_size), rows, 64) if min_pts is None else int(min_pts)
+    core = _core(h, feat8, rows, dim, weight, min_pts, splits)
+    tree = _forest(h, feat8, rows, dim, weight, floor, splits, check_every, core)
+    condensed = tree.condense(min_cluster_size, floor)
+    return torch.from_numpy(condensed.select(selection, allow_single_cluster)).to(dev), core, tree, condensed
+
 
 def single_linkage(feat8, cosine=True, floor=None, splits=0, check_every=1):
     """The single-linkage hierarchy of the rows of feat8 (a contiguous int8 device tensor [rows, dim]) ON THE DEVICE, as
@@ -498,27 +671,36 @@ def single_linkage(feat8, cosine=True, floor=None, splits=0, check_every=1):
     rows, dim, dev = int(feat8.shape[0]), int(feat8.shape[1]), feat8.device
     if rows < 1:
         raise ValueError("feat8 holds no row")
+    h = _lib.Handle(dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    weight = None
+    if cosine:
+        weight = torch.empty(rows, dtype=torch.float32, device=dev)
+        h.call("ivit_gallery_inv_norms", _ptr(feat8), rows, dim, _ptr(weight))
+    return _forest(h, feat8, rows, dim, weight, floor, splits, check_every)
+
+
+def _forest(h, feat8, rows, dim, weight, floor, splits, check_every, core=None):
+    """the rounds of `single_linkage` (core None: ivit_linkage_round) or of `hdbscan` (ivit_reach_round over `core`) -> a `Linkage`"""
+    dev = feat8.device
     floor = float("-inf") if floor is None else float(np.float32(floor))
     if math.isnan(floor):
         raise ValueError("floor must not be NaN")
     if int(check_every) < 1:
         raise ValueError("check_every must be at least 1")
-    h = _lib.Handle(dev.index, torch.cuda.current_stream(dev).cuda_stream)
     n = ctypes.c_size_t()
     h.call("ivit_linkage_workspace_bytes", rows, dim, int(splits), ctypes.byref(n))
     new = lambda dt, *shape: torch.empty(*shape, dtype=dt, device=dev)      # noqa: E731
     ws = new(torch.uint8, n.value)
-    weight = None
-    if cosine:
-        weight = new(torch.float32, rows)
-        h.call("ivit_gallery_inv_norms", _ptr(feat8), rows, dim, _ptr(weight))
     comp, done, state = new(torch.int32, rows), new(torch.uint8, rows), new(torch.int32, 4)
     u, v, val = new(torch.int32, rows), new(torch.int32, rows), new(torch.float32, rows)
     run = tuple(_ptr(t) for t in (comp, done, u, v, val, state))
     h.call("ivit_linkage_init", rows, *run)
     while True:
         for _ in range(int(check_every)):
-            h.call("ivit_linkage_round", _ptr(feat8), rows, dim, _ptr(weight), floor, int(splits), _ptr(ws), n.value, *run)
+            if core is None:
+                h.call("ivit_linkage_round", _ptr(feat8), rows, dim, _ptr(weight), floor, int(splits), _ptr(ws), n.value, *run)
+            else:
+                h.call("ivit_reach_round", _ptr(feat8), rows, dim, _ptr(weight), _ptr(core), floor, int(splits), _ptr(ws), n.value, *run)
         components, merged, rounds, _ = state.tolist()                  # the one read of a batch
         if merged == 0 or components == 1:
             break

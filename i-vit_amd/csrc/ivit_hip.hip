@@ -1,5 +1,5 @@
 // ivit_hip.hip — C-ABI (include/ivit.h, include/ivit_eval.h, include/ivit_features.h, include/ivit_attnmap.h, include/ivit_classmap.h,
-// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h, include/ivit_density.h, include/ivit_linkage.h) over the gfx950
+// include/ivit_hidden.h, include/ivit_search.h, include/ivit_modelfile.h, include/ivit_probe.h, include/ivit_views.h, include/ivit_cluster.h, include/ivit_range.h, include/ivit_jpeg.h, include/ivit_jpeg_entropy.h, include/ivit_seed.h, include/ivit_logreg.h, include/ivit_gauss.h, include/ivit_density.h, include/ivit_linkage.h, include/ivit_hdbscan.h) over the gfx950
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
@@ -51,6 +51,7 @@
 #include "ivit_gauss.h"
 #include "ivit_density.h"
 #include "ivit_linkage.h"
+#include "ivit_hdbscan.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -3702,30 +3703,40 @@ extern "C" int ivit_linkage_init(ivit_handle h, int64_t rows, int32_t *comp, uin
     return IVIT_OK;
 }
 
-extern "C" int ivit_linkage_round(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, float floor, int splits, void *workspace,
-                                  size_t bytes, int32_t *comp, uint8_t *done, int32_t *edge_u, int32_t *edge_v, float *edge_val, int32_t *state) {
-    CHECK_H(h);
-    REQUIRE(h, x && workspace && comp && done && edge_u && edge_v && edge_val && state,
-            "x, workspace, comp, done, edge_u, edge_v, edge_val or state is null");
+// one Borůvka round, the plain one (core == nullptr, MODE LINKAGE_PLAIN) or the mutual-reachability one of include/ivit_hdbscan.h: the
+// same checks in the same order, the same five small launches behind the scan
+template <int MODE>
+static int linkage_round(ivit_handle h, const char *fn, const int8_t *x, long long rows, int dim, const float *weight, const float *core, float floor,
+                         int splits, void *workspace, size_t bytes, int32_t *comp, uint8_t *done, int32_t *edge_u, int32_t *edge_v, float *edge_val,
+                         int32_t *state) {
+    constexpr bool REACH = MODE == LINKAGE_REACH;
+    auto refuse = [&](const char *msg) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, msg); return IVIT_ERR_INVALID; };
+    if (!(x && workspace && comp && done && edge_u && edge_v && edge_val && state && (core || !REACH)))
+        return refuse(REACH ? "x, core, workspace, comp, done, edge_u, edge_v, edge_val or state is null"
+                            : "x, workspace, comp, done, edge_u, edge_v, edge_val or state is null");
     LinkageLayout l;
-    if (const int rc = linkage_shape_ok(h, __func__, rows, dim, splits, &l)) return rc;
-    REQUIRE(h, floor == floor, "floor must not be NaN");
-    REQUIRE(h, bytes >= l.bytes, "workspace too small (ivit_linkage_workspace_bytes)");
-    REQUIRE_A16(h, x, "x");
-    REQUIRE_A16(h, workspace, "workspace");
-    DensityRange r[9] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {workspace, bytes, "workspace"}};
-    if (const int rc = linkage_outputs_ok(h, __func__, r, 3, rows, comp, done, edge_u, edge_v, edge_val, state)) return rc;
-    if (const int rc = density_disjoint(h, __func__, r, 2, 9)) return rc;
+    if (const int rc = linkage_shape_ok(h, fn, rows, dim, splits, &l)) return rc;
+    if (!(floor == floor)) return refuse("floor must not be NaN");
+    if (bytes < l.bytes) return refuse("workspace too small (ivit_linkage_workspace_bytes)");
+    if ((uintptr_t)x & 15) return refuse("x must be 16-byte aligned");
+    if ((uintptr_t)workspace & 15) return refuse("workspace must be 16-byte aligned");
+    if ((uintptr_t)core & 3) return refuse("core must be 4-byte aligned");
+    constexpr int n_in = REACH ? 3 : 2;
+    DensityRange r[10] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}};
+    if (REACH) r[2] = {core, (size_t)rows * 4, "core"};
+    r[n_in] = {workspace, bytes, "workspace"};
+    if (const int rc = linkage_outputs_ok(h, fn, r, n_in + 1, rows, comp, done, edge_u, edge_v, edge_val, state)) return rc;
+    if (const int rc = density_disjoint(h, fn, r, n_in, n_in + 7)) return rc;
     LinkageArgs a = {};
     char *ws = (char *)workspace;
     a.x = x; a.weight = weight; a.comp = comp; a.done = done; a.edge_u = edge_u; a.edge_v = edge_v; a.edge_val = edge_val; a.state = state;
     a.part = (unsigned long long *)ws; a.rbest = (unsigned long long *)(ws + l.rbest); a.cedge = (unsigned long long *)(ws + l.cedge);
     a.cbest = (unsigned *)(ws + l.cbest); a.parent = (int *)(ws + l.parent);
-    a.rows = rows; a.tiles = l.d.tiles; a.per = l.d.per; a.floor = floor; a.parts = l.d.parts;
+    a.rows = rows; a.tiles = l.d.tiles; a.per = l.d.per; a.floor = floor; a.parts = l.d.parts; a.core = core;
     const dim3 grid((unsigned)((rows + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
     const unsigned per_row = (unsigned)((rows + 255) / 256);
     switch (dim / 64) {
-#define LINKAGE_CASE(KS) case KS: linkage_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS)><<<grid, 256, 0, h->stream>>>(a); break;
+#define LINKAGE_CASE(KS) case KS: linkage_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS), MODE><<<grid, 256, 0, h->stream>>>(a); break;
         LINKAGE_CASE(1) LINKAGE_CASE(2) LINKAGE_CASE(3) LINKAGE_CASE(4) LINKAGE_CASE(5) LINKAGE_CASE(6) LINKAGE_CASE(7) LINKAGE_CASE(8)
         LINKAGE_CASE(9) LINKAGE_CASE(10) LINKAGE_CASE(11) LINKAGE_CASE(12) LINKAGE_CASE(13) LINKAGE_CASE(14) LINKAGE_CASE(15) LINKAGE_CASE(16)
 #undef LINKAGE_CASE
@@ -3742,6 +3753,84 @@ extern "C" int ivit_linkage_round(ivit_handle h, const int8_t *x, int64_t rows, 
     linkage_finish_kernel<<<1, 1, 0, h->stream>>>(state);
     LAUNCH_CHECK(h);
     return IVIT_OK;
+}
+
+extern "C" int ivit_linkage_round(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, float floor, int splits, void *workspace,
+                                  size_t bytes, int32_t *comp, uint8_t *done, int32_t *edge_u, int32_t *edge_v, float *edge_val, int32_t *state) {
+    CHECK_H(h);
+    return linkage_round<LINKAGE_PLAIN>(h, __func__, x, rows, dim, weight, nullptr, floor, splits, workspace, bytes, comp, done, edge_u, edge_v, edge_val,
+                                        state);
+}
+
+// ---------------------------------------------------------------- HDBSCAN: core similarities, the mutual-reachability round (include/ivit_hdbscan.h)
+// the workspace of the core pass: the rows * parts * min_pts 32-bit ordered values of the scan.  The parts are ivit_density.h's.
+static int core_shape_ok(ivit_handle h, const char *fn, long long rows, int dim, int min_pts, int splits, DensityLayout *l, size_t *bytes) {
+    if (const int rc = density_shape_ok(h, fn, rows, dim, splits, l)) return rc;
+    if (min_pts < 1 || min_pts > CORE_MAX_K || min_pts > rows) {
+        snprintf(h->err, sizeof(h->err), "%s: min_pts must be in 1 .. min(rows, %d)", fn, CORE_MAX_K);
+        return IVIT_ERR_INVALID;
+    }
+    *bytes = ((size_t)rows * l->parts * min_pts * 4 + 15) & ~(size_t)15;
+    return IVIT_OK;
+}
+
+extern "C" int ivit_core_workspace_bytes(ivit_handle h, int64_t rows, int dim, int min_pts, int splits, size_t *bytes) {
+    CHECK_H(h);
+    REQUIRE(h, bytes, "bytes is null");
+    DensityLayout l;
+    size_t n;
+    if (const int rc = core_shape_ok(h, __func__, rows, dim, min_pts, splits, &l, &n)) return rc;
+    *bytes = n;
+    return IVIT_OK;
+}
+
+template <int KS>
+static int core_scan_launch(ivit_handle h, dim3 grid, size_t lds, const CoreArgs &a) {
+    return launch_dyn<core_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS)>>(h, grid, dim3(256), lds, a);
+}
+
+extern "C" int ivit_core_similarity(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, int min_pts, int splits, void *workspace,
+                                    size_t bytes, float *core) {
+    CHECK_H(h);
+    REQUIRE(h, x && workspace && core, "x, workspace or core is null");
+    DensityLayout l;
+    size_t need;
+    if (const int rc = core_shape_ok(h, __func__, rows, dim, min_pts, splits, &l, &need)) return rc;
+    REQUIRE(h, bytes >= need, "workspace too small (ivit_core_workspace_bytes)");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, workspace, "workspace");
+    REQUIRE_ALIGNED(h, core, "core", 4);
+    const DensityRange r[4] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {workspace, bytes, "workspace"},
+                               {core, (size_t)rows * 4, "core"}};
+    if (const int rc = density_disjoint(h, __func__, r, 2, 4)) return rc;
+    REQUIRE_LAUNCH(h, (rows + 3) / 4, 256, 4);
+    CoreArgs a = {};
+    a.x = x; a.weight = weight; a.ws = (unsigned *)workspace; a.core = core;
+    a.rows = rows; a.tiles = l.tiles; a.per = l.per; a.k = min_pts; a.parts = l.parts;
+    const dim3 grid((unsigned)((rows + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
+    const size_t lds = core_lds_bytes(min_pts);
+    int rc = IVIT_OK;
+    switch (dim / 64) {
+#define CORE_CASE(KS) case KS: rc = core_scan_launch<KS>(h, grid, lds, a); break;
+        CORE_CASE(1) CORE_CASE(2) CORE_CASE(3) CORE_CASE(4) CORE_CASE(5) CORE_CASE(6) CORE_CASE(7) CORE_CASE(8)
+        CORE_CASE(9) CORE_CASE(10) CORE_CASE(11) CORE_CASE(12) CORE_CASE(13) CORE_CASE(14) CORE_CASE(15) CORE_CASE(16)
+#undef CORE_CASE
+    }
+    if (rc) return rc;
+    LAUNCH_CHECK(h);
+    const unsigned per_wave = (unsigned)((rows + 3) / 4);                   // one wavefront per row
+    if ((long long)a.parts * min_pts <= 1024) core_select_kernel<16><<<per_wave, 256, 0, h->stream>>>(a);
+    else core_select_kernel<0><<<per_wave, 256, 0, h->stream>>>(a);
+    LAUNCH_CHECK(h);
+    return IVIT_OK;
+}
+
+extern "C" int ivit_reach_round(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, const float *core, float floor, int splits,
+                                void *workspace, size_t bytes, int32_t *comp, uint8_t *done, int32_t *edge_u, int32_t *edge_v, float *edge_val,
+                                int32_t *state) {
+    CHECK_H(h);
+    return linkage_round<LINKAGE_REACH>(h, __func__, x, rows, dim, weight, core, floor, splits, workspace, bytes, comp, done, edge_u, edge_v, edge_val,
+                                        state);
 }
 
 #include "ivit_model.h"

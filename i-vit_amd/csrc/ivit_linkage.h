@@ -14,7 +14,7 @@
 //              0xFFFFFFFF - g, and the larger key is the better edge; ordered() is topk_key's map (unsigned order == float order, -0.0
 //              folded into +0.0), never 0 for a value that is not NaN, so key 0 is "no edge".
 //
-// linkage_scan_kernel<KS, PF>   dim = 64 KS.  Grid (tiles of 128 resident rows) x (parts of the same rows, whole tiles of 32); four
+// linkage_scan_kernel<KS, PF, MODE>   dim = 64 KS; ONE source for the plain round and the mutual-reachability round below.  Grid (tiles of 128 resident rows) x (parts of the same rows, whole tiles of 32); four
 //   wavefronts per workgroup that share nothing.  Wavefront w keeps rows 128 bx + 32 w .. + 31 as the B operands of
 //   v_mfma_i32_32x32x32_i8 and walks the tiles of its part in ascending order; after 2 KS MFMAs lane l holds, for resident row l % 32,
 //   the 16 values of tile rows (r & 3) + 8 (r >> 2) + 4 (l / 32), ascending in r.  A lane keeps ONE running best (value, g), NaN / -1
@@ -27,6 +27,14 @@
 //   ends alike: ONE exchange with lane l ^ 32 combines the two lanes of a row (the larger key), lanes 0 .. 31 store part[row * parts +
 //   part], ONE plain store per (row, part); the wavefronts of part 0 also reset their rows' entries of cbest / cedge and the first
 //   of them the hook counter, which the later launches of the round fill.  No LDS, no scratch; no atomics in the scan.
+//   MODE  LINKAGE_PLAIN  the edge value is v (include/ivit_linkage.h).
+//         LINKAGE_REACH  the edge value is m{q, g} = min(v, core[q], core[g]) (include/ivit_hdbscan.h), v counted as v + 0.0f.  The tile
+//                        rows' core values travel with their weights (prefetched with them where PFC is on), the resident row's cq is
+//                        loaded once.  v is an upper bound of m: the compare of a tile stays !(v <= best) and v >= floor on v, and only
+//                        a survivor pays the two minimums, the floor test on m and the compare of m.  THE SATURATION EXIT: m{q, .} <=
+//                        cq and the walk ascends in g, so a row one of whose two lanes holds best == cq at the end of a tile has its
+//                        final edge of this part; one ballot per tile, its two halves ORed, against the active rows' mask, and the
+//                        wavefront leaves the walk when every active row is settled.
 //
 // linkage_fold_kernel     a thread per row: the largest key of its parts -> rbest[row]; its ordered value goes into cbest[comp[row]]
 //                         with an integer atomicMax (skipped where a relaxed read shows it is already there: the value only grows).
@@ -67,9 +75,12 @@ struct LinkageArgs {
     long long rows, tiles, per;         // part s covers tiles [s * per, min(tiles, (s + 1) * per))
     float floor;
     int parts;
+    const float *core;                  // [rows]: LINKAGE_REACH
 };
 
 #define LINKAGE_NO_EDGE 0xFFFFFFFFFFFFFFFFull
+#define LINKAGE_PLAIN 0
+#define LINKAGE_REACH 1
 
 __device__ __forceinline__ unsigned long long linkage_key(float v, int g) {
     unsigned u = __float_as_uint(v);
@@ -78,9 +89,11 @@ __device__ __forceinline__ unsigned long long linkage_key(float v, int g) {
     return ((unsigned long long)u << 32) | (0xFFFFFFFFu - (unsigned)g);
 }
 
-template <int KS, bool PF>
+template <int KS, bool PF, int MODE, bool PFC = PF>
 __global__ __launch_bounds__(256) void linkage_scan_kernel(LinkageArgs p) {
     constexpr int NF = 2 * KS, DIM = 64 * KS;
+    constexpr bool REACH = MODE == LINKAGE_REACH;
+    constexpr int NC = REACH ? 16 : 1;                                   // core values beside a tile's weights
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
     const long long q0 = ((long long)blockIdx.x * 4 + wave) * SEARCH_QW;
     if (q0 >= p.rows || p.state[1] == 0) return;                         // whole wavefronts leave: nothing below synchronises a block
@@ -103,6 +116,17 @@ __global__ __launch_bounds__(256) void linkage_scan_kernel(LinkageArgs p) {
         }
         const float qw = p.weight ? p.weight[qrow] : 1.0f;
         const float flr = p.floor;
+        float cq = 0.0f;                                                 // REACH: this row's core similarity, the bound of its m
+        unsigned act = 0u;                                               // REACH: the active rows of the wavefront, a bit per row
+        if constexpr (REACH) {
+            cq = p.core[qrow] + 0.0f;
+            const unsigned long long b = __ballot(active);
+            act = (unsigned)b | (unsigned)(b >> 32);
+        }
+        auto load_core = [&](long long g0, float (&c)[NC]) {
+#pragma unroll
+            for (int r = 0; r < NC; ++r) c[r] = p.core[min(g0 + ((r & 3) + 8 * (r >> 2) + 4 * half), last_row)];
+        };
         auto load_tile = [&](long long g0, v4i (&a)[NF], float (&w)[16]) {
             const int8_t *src = p.x + (size_t)min(g0 + l31, last_row) * DIM + 16 * half;
 #pragma unroll
@@ -113,13 +137,18 @@ __global__ __launch_bounds__(256) void linkage_scan_kernel(LinkageArgs p) {
 
         v4i a[NF];
         float w[16];
+        float c[NC];
         if constexpr (PF) load_tile(t_begin * SEARCH_TILE, a, w);
+        if constexpr (REACH && PFC) load_core(t_begin * SEARCH_TILE, c);
         for (long long t = t_begin; t < t_end; ++t) {
             const long long g0 = t * SEARCH_TILE;
             v4i an[PF ? NF : 1];
             float wn[PF ? 16 : 1];
+            float cn[REACH && PFC ? 16 : 1];
             if constexpr (PF) load_tile(min(t + 1, t_end - 1) * SEARCH_TILE, an, wn);         // no next tile: this one again, from the cache
             else load_tile(g0, a, w);
+            if constexpr (REACH && PFC) load_core(min(t + 1, t_end - 1) * SEARCH_TILE, cn);
+            else if constexpr (REACH) load_core(g0, c);
             v16i acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0;
@@ -136,23 +165,40 @@ __global__ __launch_bounds__(256) void linkage_scan_kernel(LinkageArgs p) {
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
                 const bool up = row > diag;                              // the larger row's weight first
                 v[r] = __fmul_rn(topk_value(acc[r], up ? w[r] : qw), up ? qw : w[r]);
+                if constexpr (REACH) v[r] += 0.0f;                       // -0.0 -> +0.0 before any minimum
                 if (row < nrow && v[r] >= flr && !(v[r] <= bestv)) mask |= 1u << r;
             }
             if (__any(mask != 0u)) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {                           // ascending g; row < nrow: inside the array
                     const int g = (int)g0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    if ((mask & (1u << r)) && !(v[r] <= bestv) && p.comp[g] != mine) {
+                    if constexpr (REACH) {
+                        if ((mask & (1u << r)) && !(v[r] <= bestv)) {
+                            const float m = fminf(fminf(v[r], cq), c[r]) + 0.0f;
+                            if (m >= flr && !(m <= bestv) && p.comp[g] != mine) {
+                                bestv = m;
+                                bestg = g;
+                            }
+                        }
+                    } else if ((mask & (1u << r)) && !(v[r] <= bestv) && p.comp[g] != mine) {
                         bestv = v[r];
                         bestg = g;
                     }
                 }
+            }
+            if constexpr (REACH) {                                       // the saturation exit: behind the reads of the accumulators
+                const unsigned long long b = __ballot(bestg >= 0 && bestv == cq);
+                if ((((unsigned)b | (unsigned)(b >> 32)) & act) == act) break;
             }
             if constexpr (PF) {
 #pragma unroll
                 for (int f = 0; f < NF; ++f) a[f] = an[f];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) w[r] = wn[r];
+            }
+            if constexpr (REACH && PFC) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) c[r] = cn[r];
             }
         }
     }

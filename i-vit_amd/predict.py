@@ -878,6 +878,11 @@ def linkage_reference(x8, weight, floor=None):
         val = (val * weight[j]) * weight[i]                           # the larger row's weight first: two float32 multiplies
     val = val + np.float32(0)                                         # -0.0 -> +0.0
     assert val.dtype == np.float32
+    return _kruskal_forest(rows, i, j, val, floor)
+
+
+def _kruskal_forest(rows, i, j, val, floor):
+    """the pairs i < j with their float32 values -> the forest of include/ivit_linkage.h over the pairs with val >= floor"""
     keep = val >= floor
     i, j, val = i[keep], j[keep], val[keep]
     order = np.lexsort((j, i, -val))                                  # the last key is the first criterion
@@ -907,3 +912,130 @@ def linkage_fit(engine, batches, floor=None, transform=None):
     from .cluster import single_linkage
     feat8, _ = embed8(engine, batches, transform)
     return single_linkage(feat8, cosine=True, floor=floor), feat8
+
+
+def mutual_reachability_reference(x8, weight, min_pts):
+    """x8 int8 [rows, dim], weight float32 [rows] or None -> (core float32 [rows], m float32 [rows, rows]): the values of
+    include/ivit_hdbscan.h from the dense matrix.
+
+    v{i, j} is `dbscan_reference`'s value (the larger row's weight first), -0.0 counted as +0.0 before any use.  core[i] is the
+    min_pts-th largest element of row i of v, the diagonal included and equal values with their multiplicity (a descending sort,
+    element min_pts - 1); min_pts in 1 .. min(rows, 64).  m{i, j} = min(v{i, j}, core[i], core[j]); its diagonal is not part of the
+    definition (no edge joins a row to itself)."""
+    x = np.asarray(x8)
+    assert x.ndim == 2 and x.dtype == np.int8 and x.shape[0] >= 1
+    rows = x.shape[0]
+    if not 1 <= int(min_pts) <= min(rows, 64):
+        raise ValueError("min_pts must be in 1 .. min(rows, 64)")
+    v = (x.astype(np.int32) @ x.astype(np.int32).T).astype(np.float32)
+    if weight is not None:
+        weight = np.asarray(weight, dtype=np.float32)
+        assert weight.shape == (rows,)
+        i, j = np.minimum.outer(np.arange(rows), np.arange(rows)), np.maximum.outer(np.arange(rows), np.arange(rows))
+        v = (v * weight[j]) * weight[i]                               # the larger row's weight first: two float32 multiplies
+    v = v + np.float32(0)                                             # -0.0 -> +0.0
+    assert v.dtype == np.float32 and np.array_equal(v, v.T)
+    core = -np.sort(-v, axis=1)[:, int(min_pts) - 1]
+    return core, np.minimum(v, np.minimum(core[:, None], core[None, :]))
+
+
+def hdbscan_reference(x8, weight, min_pts, floor=None):
+    """-> (core float32 [rows], u int32 [E], v int32 [E], val float32 [E]): the numpy statement of include/ivit_hdbscan.h — the core
+    similarities and the forest of `linkage_reference` (its edge order, its Kruskal) over m of `mutual_reachability_reference` in
+    place of v.  floor None is -infinity; NaN is refused."""
+    core, m = mutual_reachability_reference(x8, weight, min_pts)
+    floor = np.float32(-np.inf if floor is None else floor)
+    if np.isnan(floor):
+        raise ValueError("floor must not be NaN")
+    i, j = np.triu_indices(m.shape[0], 1)
+    return (core,) + _kruskal_forest(m.shape[0], i, j, m[i, j], floor)
+
+
+def hdbscan_labels_reference(m_dense, min_cluster_size, floor=None, selection="eom", allow_single_cluster=False):
+    """m_dense float32 [rows, rows], symmetric (the diagonal is ignored) -> (label int32 [rows], stability {smallest row at birth,
+    birth level: float}): the condensed tree, the stabilities and the selection of HDBSCAN by brute force on the dense matrix — no
+    edge list, no union-find — so that `cluster.Linkage.condense` has a check that shares nothing with it.
+
+    Levels.  Only pairs with m >= floor exist (None: all).  At a level L the clusters are the connected components of the graph
+    m >= L.  They are read off the bottleneck matrix B[i, j], the largest L at which i and j are connected (the maximum over paths of
+    the minimum along the path: a min-max closure over every intermediate row, n passes over the matrix): the components at L are the
+    classes of B >= L, and no component changes at a level that is no value of B, so the walk visits the values of B.
+    Roots: the components of B >= floor (floor None: the lowest value of B, where all rows are one component) with at least
+    min_cluster_size rows, born at that level; rows of smaller components are noise.
+    Walk, for a cluster C born at birth(C), upwards through the levels L >= birth(C): past L the rows still in C fall into the
+    components of B > L, those with at least min_cluster_size rows being big.  Two or more big: C ends, each big one is a new
+    cluster born at L, a child of C.  Exactly one: C continues as that one.  None: C ends.  A row leaves C at L when it is in C
+    before L and not after: the rows of the small components, and EVERY remaining row where C ends (those that enter a new cluster
+    included: each row of C leaves it exactly once).
+    Stability S(C) = math.fsum over the rows p of C of float64(L_p) - float64(birth(C)): one term per row, order-independent.
+    Selection, bottom-up.  "eom": a leaf is selected; an inner cluster is selected and its descendants unselected unless the fsum of
+    its children's subtree totals is STRICTLY greater than S(C) (then the total of C is that sum).  "leaf": the leaves.  Where
+    there is exactly one root it is selectable only with allow_single_cluster.  A row's label is the smallest row (at birth) of the
+    selected cluster it was born into, or -1.  min_cluster_size >= 2."""
+    import math
+    m = np.asarray(m_dense, np.float32)
+    rows = m.shape[0]
+    assert m.shape == (rows, rows) and int(min_cluster_size) >= 2 and selection in ("eom", "leaf")
+    mcs = int(min_cluster_size)
+    B = np.where(m >= np.float32(-np.inf if floor is None else floor), m, np.float32(-np.inf)).astype(np.float32)
+    np.fill_diagonal(B, np.inf)
+    for k in range(rows):
+        B = np.maximum(B, np.minimum(B[:, k, None], B[None, k, :]))
+    off = B[~np.eye(rows, dtype=bool)]
+    levels = np.unique(off[np.isfinite(off)])                         # ascending
+    label = np.full(rows, -1, np.int32)
+    if not len(levels):
+        return label, {}
+    base = levels[0] if floor is None else np.float32(floor)
+
+    def classes(members, reach):
+        """the classes of the equivalence `reach` among `members`, each an array of rows"""
+        sub = reach[np.ix_(members, members)]
+        first = sub.argmax(axis=1)                                    # the first member of the row's class
+        return [members[first == f] for f in np.unique(first)]
+
+    clusters = []                                                     # dicts: rows at birth, birth, children, stability
+
+    def grow(members, birth):
+        c = {"rows": members, "birth": birth, "children": [], "terms": []}
+        clusters.append(c)
+        cur = members
+        for L in levels[levels >= birth]:
+            parts = classes(cur, B > L)
+            if len(parts) == 1:
+                continue
+            big = [q for q in parts if len(q) >= mcs]
+            if len(big) == 1:
+                c["terms"] += [float(np.float64(L) - np.float64(birth))] * (len(cur) - len(big[0]))
+                cur = big[0]
+                continue
+            c["terms"] += [float(np.float64(L) - np.float64(birth))] * len(cur)
+            c["children"] = [grow(q, L) for q in big]
+            break
+        c["stability"] = math.fsum(c["terms"])
+        return c
+
+    roots = [grow(q, base) for q in classes(np.arange(rows), B >= base) if len(q) >= mcs]
+
+    def choose(c, selectable):
+        """-> (subtree total, the selected clusters of the subtree)"""
+        if not c["children"]:
+            return (c["stability"], [c]) if selectable else (0.0, [])
+        below = [choose(k, True) for k in c["children"]]
+        total, picked = math.fsum(t for t, _ in below), [s for _, sel in below for s in sel]
+        if selection == "leaf" or not selectable or total > c["stability"]:
+            return total, picked
+        return c["stability"], [c]
+    for r in roots:
+        for c in choose(r, allow_single_cluster or len(roots) > 1)[1]:
+            label[c["rows"]] = c["rows"].min()
+    return label, {(int(c["rows"].min()), float(c["birth"])): c["stability"] for c in clusters}
+
+
+def hdbscan_fit(engine, batches, min_cluster_size=5, min_pts=None, floor=None, selection="eom", allow_single_cluster=False, transform=None):
+    """`embed8`'s loop followed by `cluster.hdbscan` on the cosine of the int8 features: returns (label, core, tree, condensed, feat8)
+    — `hdbscan_reference(feat8, inv_norms_reference(feat8), min_pts, floor)` states core and the tree's edges,
+    `hdbscan_labels_reference` on the matrix of `mutual_reachability_reference` the labels."""
+    from .cluster import hdbscan
+    feat8, _ = embed8(engine, batches, transform)
+    return hdbscan(feat8, min_cluster_size, min_pts, cosine=True, floor=floor, selection=selection, allow_single_cluster=allow_single_cluster) + (feat8,)
