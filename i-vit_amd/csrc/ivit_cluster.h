@@ -49,6 +49,7 @@
 #define KMEANS_RB (4 * KMEANS_RW)                  // rows of a workgroup
 #define KMEANS_TILE 32                             // centroids of a tile: the M of the MFMA
 #define KMEANS_PF_MAX_KS 7                         // prefetch the next tile up to dim 448: two wavefronts per SIMD still fit
+__host__ __device__ constexpr bool kmeans_prefetch(int KS) { return KS <= KMEANS_PF_MAX_KS; }
 #define KMEANS_WHOLE_MAX_KS 12                     // up to dim 768 a tile's loads are issued together, above it in two halves
 #define KMEANS_BIAS (1 << 26)                      // s + KMEANS_BIAS > 0
 

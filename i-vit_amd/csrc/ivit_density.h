@@ -1,11 +1,9 @@
 // ivit_density.h — density clustering (include/ivit_density.h): DBSCAN over int8 rows as label propagation, the adjacency never
 // written.  Per row only the NUMBER of its neighbours (the degree pass) or the SMALLEST LABEL among them (a sweep, the border pass) is
-// needed, and a scan that keeps the scores in registers produces either directly.  Takes from ivit_search.h the work shape
-// (SEARCH_QW, SEARCH_QB, SEARCH_TILE, SEARCH_PF_MAX_KS) and topk_value, from ivit_range.h the lane layout of a tile.
+// needed, and a scan that keeps the scores in registers produces either directly.  The work shape, the lane layout of a tile
+// (scan_tile_row), its bounds and the value of a pair are those of ivit_scan.h.
 //
-//   value      v{b, g} = fl32(fl32(fl32(dot) * weight[max(b, g)]) * weight[min(b, g)]): first the weight of the LARGER row, then that of
-//              the smaller, chosen per element by g > b: one value per unordered pair, whichever of the two is the resident row.  A
-//              NULL weight is two multiplications by 1.0f (the same bits).
+//   value      v{b, g} = scan_pair_value of ivit_scan.h, defined there: one value per unordered pair.
 //   neighbour  v >= threshold (the IEEE comparison), g == b included.
 //
 // density_scan_kernel<KS, PF, MODE>  dim = 64 KS; ONE source for the three passes, so that they cannot disagree about a neighbour.
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(256) void density_scan_kernel(DensityArgs p) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) a[f] = *reinterpret_cast<const v4i *>(src + 32 * f);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) w[r] = p.weight ? p.weight[min(g0 + ((r & 3) + 8 * (r >> 2) + 4 * half), last_row)] : 1.0f;
+            for (int r = 0; r < 16; ++r) w[r] = p.weight ? p.weight[min(g0 + scan_tile_row(r, half), last_row)] : 1.0f;
         };
 
         long long t = next_tile();
@@ -132,15 +130,15 @@ __global__ __launch_bounds__(256) void density_scan_kernel(DensityArgs p) {
 #pragma unroll
                 for (int f = 0; f < NF; ++f) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[f], qf[f], acc, 0, 0, 0);
 
-                const int nrow = active ? (int)min((long long)SEARCH_TILE, p.rows - g0) : 0;  // rows of this tile inside the array
+                const int nrow = active ? scan_nrow(p.rows, g0) : 0; // rows of this tile inside the array
                 // tile row `row` is row g = g0 + row of the array: g > b exactly when row > b - g0
-                const int diag = (int)max(-1ll, min((long long)SEARCH_TILE, q0 + l31 - g0));
+                const int diag = scan_diag(q0 + l31 - g0);
                 unsigned mask = 0u;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int row = scan_tile_row(r, half);
                     const bool up = row > diag;                          // the larger row's weight first
-                    const float v = __fmul_rn(topk_value(acc[r], up ? w[r] : qw), up ? qw : w[r]);
+                    const float v = scan_pair_value(acc[r], w[r], qw, up);
                     if (row < nrow && v >= thr) mask |= 1u << r;
                 }
                 if (__any(mask != 0u)) {
@@ -148,7 +146,8 @@ __global__ __launch_bounds__(256) void density_scan_kernel(DensityArgs p) {
                         best += __popc(mask);
                     } else {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r)                      // row < nrow: inside the array
+                        for (int r = 0; r < 16; ++r)                      // row < nrow: inside the array.  scan_tile_row(r, half, g0) written out:
+                            // through the call the sweep and border passes allocate differently (one register more at dim 832)
                             if (mask & (1u << r)) best = min(best, p.label[g0 + (r & 3) + 8 * (r >> 2) + 4 * half]);
                     }
                 }

@@ -3,8 +3,8 @@
 // kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // The launch idioms every entry point shares are defined once, below ivit_ctx: launch_dyn (the dynamic-LDS attribute, cached per
-// device and kernel, then the launch), with_bool / with_width (one spelling of a launch for a pair of instantiations), and the
-// range predicates rq_fast / rq_fast2 / attn_fast that choose instantiations and refuse calls.
+// device and kernel, then the launch), with_bool / with_width / with_ks (one spelling of a launch for a family of instantiations),
+// args_disjoint (an entry's arrays as one table for the overlap rule), and the range predicates rq_fast / rq_fast2 / attn_fast that choose instantiations and refuse calls.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <float.h>
@@ -111,6 +111,15 @@ static inline size_t span_bytes(long long rows, long long pitch, long long paylo
 }
 #define OVL_IN "an output may not overlap an activation input"
 #define OVL_OUT "two arrays the entry writes may not overlap"
+// The same rule as a table: the arrays of an entry, its inputs first (n_in of them), then what it writes; every array is judged
+// against every array the entry writes that stands behind it, output by output.
+struct ArgRange { const void *p; size_t n; const char *name; };
+static int args_disjoint(ivit_ctx *h, const char *fn, const ArgRange *r, int n_in, int n) {
+    for (int o = n_in; o < n; ++o)
+        for (int i = 0; i < o; ++i)
+            if (!ranges_disjoint(h, fn, r[i].p, r[i].n, r[i].name, r[o].p, r[o].n, r[o].name, i < n_in ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
+    return IVIT_OK;
+}
 // the qkv scatter's arrays (ivit_linear_i8_qkv and its planned / LayerNorm-headed forms): the input against q, k and v, and the three
 // among themselves; q and k are [B*H, T, dh], v the same at ldv == 0 and B*H*dh rows of T at a pitch of ldv otherwise.  `fn`: the entry
 static int qkv_disjoint(ivit_ctx *h, const char *fn, const void *x, size_t x_bytes, const char *x_name, const int8_t *q, const int8_t *k,
@@ -173,6 +182,15 @@ template <class F>
 static inline auto with_width(int C, F &&f) {
     if (C == 96) return f(std::integral_constant<int, 96>{});
     return f(std::integral_constant<int, 128>{});
+}
+// f(std::integral_constant<int, KS>{}) with KS = dim / 64: the sixteen widths of the kernels over int8 feature rows, dim = 64 .. 1024
+// (the entries have refused every other dim: what is not one of the first fifteen is the sixteenth)
+template <int KS = 1, class F>
+static inline auto with_ks(int dim, F &&f) {
+    if constexpr (KS < 16) {
+        if (dim / 64 != KS) return with_ks<KS + 1>(dim, f);
+    }
+    return f(std::integral_constant<int, KS>{});
 }
 
 // The range predicates: they choose which instantiation runs and which calls are refused, so each has ONE definition.
@@ -2726,11 +2744,6 @@ static void search_select_launch(ivit_handle h, const unsigned long long *keys, 
     else search_select_kernel<PAIRS, 0><<<grid, 256, 0, h->stream>>>(keys, idx_in, val_in, nq, n, k, idx, val);
 }
 
-template <int KS>
-static int search_scan_launch(ivit_handle h, dim3 grid, size_t lds, const SearchArgs &a) {
-    return launch_dyn<search_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS)>>(h, grid, dim3(256), lds, a);
-}
-
 extern "C" int ivit_search_topk(ivit_handle h, const int8_t *query, int nq, const int8_t *gallery, int64_t rows, int dim, const float *weight,
                                 int k, int32_t index_base, int splits, void *workspace, size_t bytes, int32_t *idx, float *val) {
     CHECK_H(h);
@@ -2743,19 +2756,10 @@ extern "C" int ivit_search_topk(ivit_handle h, const int8_t *query, int nq, cons
     REQUIRE_A16(h, query, "query");
     REQUIRE_A16(h, gallery, "gallery");
     REQUIRE_ALIGNED(h, workspace, "workspace", 8);
-    {
-        const size_t nout = (size_t)nq * k * 4;
-        const struct { const void *p; size_t n; const char *name; } ins[3] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"},
-                                                                           {weight, (size_t)rows * 4, "weight"}};
-        for (const auto &i : ins) {
-            REQUIRE_DISJOINT(h, i.p, i.n, i.name, idx, nout, "idx", OVL_IN);
-            REQUIRE_DISJOINT(h, i.p, i.n, i.name, val, nout, "val", OVL_IN);
-            REQUIRE_DISJOINT(h, i.p, i.n, i.name, workspace, bytes, "workspace", OVL_IN);
-        }
-        REQUIRE_DISJOINT(h, idx, nout, "idx", val, nout, "val", OVL_OUT);
-        REQUIRE_DISJOINT(h, idx, nout, "idx", workspace, bytes, "workspace", OVL_OUT);
-        REQUIRE_DISJOINT(h, val, nout, "val", workspace, bytes, "workspace", OVL_OUT);
-    }
+    const size_t nout = (size_t)nq * k * 4;
+    const ArgRange r[6] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"}, {weight, (size_t)rows * 4, "weight"},
+                           {idx, nout, "idx"}, {val, nout, "val"}, {workspace, bytes, "workspace"}};
+    if (const int rc = args_disjoint(h, __func__, r, 3, 6)) return rc;
     if (nq == 0) return IVIT_OK;
     SearchArgs a;
     a.query = query; a.gallery = gallery; a.weight = weight; a.ws = (unsigned long long *)workspace;
@@ -2763,14 +2767,8 @@ extern "C" int ivit_search_topk(ivit_handle h, const int8_t *query, int nq, cons
     a.nq = nq; a.k = k; a.index_base = index_base; a.parts = parts;
     const dim3 grid((unsigned)(((long long)nq + SEARCH_QB - 1) / SEARCH_QB), (unsigned)parts);
     const size_t lds = search_lds_bytes(k);
-    int rc = IVIT_OK;
-    switch (dim / 64) {
-#define SEARCH_CASE(KS) case KS: rc = search_scan_launch<KS>(h, grid, lds, a); break;
-        SEARCH_CASE(1) SEARCH_CASE(2) SEARCH_CASE(3) SEARCH_CASE(4) SEARCH_CASE(5) SEARCH_CASE(6) SEARCH_CASE(7) SEARCH_CASE(8)
-        SEARCH_CASE(9) SEARCH_CASE(10) SEARCH_CASE(11) SEARCH_CASE(12) SEARCH_CASE(13) SEARCH_CASE(14) SEARCH_CASE(15) SEARCH_CASE(16)
-#undef SEARCH_CASE
-    }
-    if (rc != IVIT_OK) return rc;
+    if (const int rc = with_ks(dim, [&](auto KS) { return launch_dyn<search_scan_kernel<KS(), scan_prefetch(KS())>>(h, grid, dim3(256), lds, a); }))
+        return rc;
     LAUNCH_CHECK(h);
     search_select_launch<false>(h, a.ws, nullptr, nullptr, nq, (long long)parts * k, k, idx, val);
     LAUNCH_CHECK(h);
@@ -2781,14 +2779,9 @@ extern "C" int ivit_search_merge(ivit_handle h, const int32_t *idx_in, const flo
     CHECK_H(h);
     REQUIRE(h, idx_in && val_in && idx && nq >= 0, "idx_in, val_in or idx is null, or nq is negative");
     REQUIRE(h, k >= 1 && k <= SEARCH_MAX_K && ncand >= k, "k must be in 1 .. min(64, ncand)");
-    {
-        const size_t nin = (size_t)nq * ncand * 4, nout = (size_t)nq * k * 4;
-        REQUIRE_DISJOINT(h, idx_in, nin, "idx_in", idx, nout, "idx", OVL_IN);
-        REQUIRE_DISJOINT(h, idx_in, nin, "idx_in", val, nout, "val", OVL_IN);
-        REQUIRE_DISJOINT(h, val_in, nin, "val_in", idx, nout, "idx", OVL_IN);
-        REQUIRE_DISJOINT(h, val_in, nin, "val_in", val, nout, "val", OVL_IN);
-        REQUIRE_DISJOINT(h, idx, nout, "idx", val, nout, "val", OVL_OUT);
-    }
+    const size_t nin = (size_t)nq * ncand * 4, nout = (size_t)nq * k * 4;
+    const ArgRange r[4] = {{idx_in, nin, "idx_in"}, {val_in, nin, "val_in"}, {idx, nout, "idx"}, {val, nout, "val"}};
+    if (const int rc = args_disjoint(h, __func__, r, 2, 4)) return rc;
     if (nq == 0) return IVIT_OK;
     search_select_launch<true>(h, nullptr, idx_in, val_in, nq, (long long)ncand, k, idx, val);
     LAUNCH_CHECK(h);
@@ -2879,11 +2872,6 @@ extern "C" int ivit_kmeans_norms(ivit_handle h, const int8_t *cent, int K, int d
     return IVIT_OK;
 }
 
-template <int KS>
-static void kmeans_assign_launch(ivit_handle h, unsigned grid, const KMeansAssignArgs &a) {
-    kmeans_assign_kernel<KS, (KS <= KMEANS_PF_MAX_KS)><<<grid, 256, 0, h->stream>>>(a);
-}
-
 extern "C" int ivit_kmeans_assign(ivit_handle h, const int8_t *x, int64_t rows, int dim, const int8_t *cent, const int32_t *cnorm, int K,
                                   int32_t *assign, int32_t *dist2) {
     CHECK_H(h);
@@ -2910,12 +2898,7 @@ extern "C" int ivit_kmeans_assign(ivit_handle h, const int8_t *x, int64_t rows, 
     if (rows == 0) return IVIT_OK;
     KMeansAssignArgs a;
     a.x = x; a.cent = cent; a.cnorm = cnorm; a.assign = assign; a.dist2 = dist2; a.rows = rows; a.K = K;
-    switch (dim / 64) {
-#define KMEANS_CASE(KS) case KS: kmeans_assign_launch<KS>(h, (unsigned)blocks, a); break;
-        KMEANS_CASE(1) KMEANS_CASE(2) KMEANS_CASE(3) KMEANS_CASE(4) KMEANS_CASE(5) KMEANS_CASE(6) KMEANS_CASE(7) KMEANS_CASE(8)
-        KMEANS_CASE(9) KMEANS_CASE(10) KMEANS_CASE(11) KMEANS_CASE(12) KMEANS_CASE(13) KMEANS_CASE(14) KMEANS_CASE(15) KMEANS_CASE(16)
-#undef KMEANS_CASE
-    }
+    with_ks(dim, [&](auto KS) { kmeans_assign_kernel<KS(), kmeans_prefetch(KS())><<<(unsigned)blocks, 256, 0, h->stream>>>(a); });
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -3064,20 +3047,10 @@ static int range_args_ok(ivit_handle h, const char *fn, const int8_t *query, int
     return IVIT_OK;
 }
 
-template <int KS, bool FILL>
-static void range_scan_launch(ivit_handle h, dim3 grid, const RangeArgs &a) {
-    range_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS), FILL><<<grid, 256, 0, h->stream>>>(a);
-}
-
 template <bool FILL>
 static void range_scan_dispatch(ivit_handle h, int dim, const RangeArgs &a) {
     const dim3 grid((unsigned)(((long long)a.nq + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
-    switch (dim / 64) {
-#define RANGE_CASE(KS) case KS: range_scan_launch<KS, FILL>(h, grid, a); break;
-        RANGE_CASE(1) RANGE_CASE(2) RANGE_CASE(3) RANGE_CASE(4) RANGE_CASE(5) RANGE_CASE(6) RANGE_CASE(7) RANGE_CASE(8)
-        RANGE_CASE(9) RANGE_CASE(10) RANGE_CASE(11) RANGE_CASE(12) RANGE_CASE(13) RANGE_CASE(14) RANGE_CASE(15) RANGE_CASE(16)
-#undef RANGE_CASE
-    }
+    with_ks(dim, [&](auto KS) { range_scan_kernel<KS(), scan_prefetch(KS()), FILL><<<grid, 256, 0, h->stream>>>(a); });
 }
 
 extern "C" int ivit_range_count(ivit_handle h, const int8_t *query, int nq, const int8_t *gallery, int64_t rows, int dim, const float *weight,
@@ -3090,16 +3063,9 @@ extern "C" int ivit_range_count(ivit_handle h, const int8_t *query, int nq, cons
     if (const int rc = range_args_ok(h, __func__, query, nq, gallery, rows, dim, weight, qweight, threshold, index_base, query_base, triangle, splits,
                                      workspace, bytes, &a, &l)) return rc;
     REQUIRE_ALIGNED(h, row_ptr, "row_ptr", 8);
-    {
-        const size_t nrp = ((size_t)nq + 1) * 8;
-        const struct { const void *p; size_t n; const char *name; } ins[4] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"},
-                                                                           {weight, (size_t)rows * 4, "weight"}, {qweight, (size_t)nq * 4, "qweight"}};
-        for (const auto &i : ins) {
-            REQUIRE_DISJOINT(h, i.p, i.n, i.name, workspace, bytes, "workspace", OVL_IN);
-            REQUIRE_DISJOINT(h, i.p, i.n, i.name, row_ptr, nrp, "row_ptr", OVL_IN);
-        }
-        REQUIRE_DISJOINT(h, workspace, bytes, "workspace", row_ptr, nrp, "row_ptr", OVL_OUT);
-    }
+    const ArgRange r[6] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"}, {weight, (size_t)rows * 4, "weight"},
+                           {qweight, (size_t)nq * 4, "qweight"}, {workspace, bytes, "workspace"}, {row_ptr, ((size_t)nq + 1) * 8, "row_ptr"}};
+    if (const int rc = args_disjoint(h, __func__, r, 4, 6)) return rc;
     if (nq == 0) return IVIT_OK;
     range_scan_dispatch<false>(h, dim, a);
     LAUNCH_CHECK(h);
@@ -3123,17 +3089,10 @@ extern "C" int ivit_range_fill(ivit_handle h, const int8_t *query, int nq, const
     RangeLayout l;
     if (const int rc = range_args_ok(h, __func__, query, nq, gallery, rows, dim, weight, qweight, threshold, index_base, query_base, triangle, splits,
                                      workspace, bytes, &a, &l)) return rc;
-    {
-        const size_t nout = (size_t)capacity * 4;
-        const struct { const void *p; size_t n; const char *name; } ins[5] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"},
-                                                                           {weight, (size_t)rows * 4, "weight"}, {qweight, (size_t)nq * 4, "qweight"},
-                                                                           {workspace, bytes, "workspace"}};
-        for (const auto &i : ins) {
-            REQUIRE_DISJOINT(h, i.p, i.n, i.name, idx, nout, "idx", OVL_IN);
-            REQUIRE_DISJOINT(h, i.p, i.n, i.name, val, nout, "val", OVL_IN);
-        }
-        REQUIRE_DISJOINT(h, idx, nout, "idx", val, nout, "val", OVL_OUT);
-    }
+    const size_t nout = (size_t)capacity * 4;
+    const ArgRange r[7] = {{query, (size_t)nq * dim, "query"}, {gallery, (size_t)rows * dim, "gallery"}, {weight, (size_t)rows * 4, "weight"},
+                           {qweight, (size_t)nq * 4, "qweight"}, {workspace, bytes, "workspace"}, {idx, nout, "idx"}, {val, nout, "val"}};
+    if (const int rc = args_disjoint(h, __func__, r, 5, 7)) return rc;      // the fill pass only reads its workspace
     if (nq == 0 || capacity == 0) return IVIT_OK;
     a.idx = idx; a.val = val; a.capacity = capacity;
     range_scan_dispatch<true>(h, dim, a);
@@ -3172,11 +3131,6 @@ extern "C" int ivit_kmeans_seed_workspace_bytes(int64_t rows, int dim, int trial
     if (seed_shape_bad(rows, dim, trials, &unsupported, &l)) return unsupported ? IVIT_ERR_UNSUPPORTED : IVIT_ERR_INVALID;
     *bytes = l.bytes;
     return IVIT_OK;
-}
-
-template <int KS>
-static void seed_scan_launch(ivit_handle h, const SeedArgs &a) {
-    seed_scan_kernel<KS, (KS <= KMEANS_PF_MAX_KS)><<<(unsigned)a.parts, 64, 0, h->stream>>>(a);
 }
 
 extern "C" int ivit_kmeans_seed(ivit_handle h, const int8_t *x, int64_t rows, int dim, int K, int trials, int64_t first, const uint64_t *draws,
@@ -3220,12 +3174,7 @@ extern "C" int ivit_kmeans_seed(ivit_handle h, const int8_t *x, int64_t rows, in
     seed_setup_kernel<<<(unsigned)std::min((long long)((rows + 15) / 16), (long long)SEED_SETUP_MAX_BLOCKS), 256, 0, h->stream>>>(a);
     LAUNCH_CHECK(h);
     for (int s = 0; s < K; ++s) {
-        switch (dim / 64) {
-#define SEED_CASE(KS) case KS: seed_scan_launch<KS>(h, a); break;
-            SEED_CASE(1) SEED_CASE(2) SEED_CASE(3) SEED_CASE(4) SEED_CASE(5) SEED_CASE(6) SEED_CASE(7) SEED_CASE(8)
-            SEED_CASE(9) SEED_CASE(10) SEED_CASE(11) SEED_CASE(12) SEED_CASE(13) SEED_CASE(14) SEED_CASE(15) SEED_CASE(16)
-#undef SEED_CASE
-        }
+        with_ks(dim, [&](auto KS) { seed_scan_kernel<KS(), kmeans_prefetch(KS())><<<(unsigned)a.parts, 64, 0, h->stream>>>(a); });
         seed_pick_kernel<<<1, 256, 0, h->stream>>>(a, s);
         if (s + 1 < K) seed_locate_kernel<<<(unsigned)trials, 256, 0, h->stream>>>(a, s);
         LAUNCH_CHECK(h);
@@ -3323,7 +3272,7 @@ extern "C" int ivit_logreg_loss_grad(ivit_handle h, const int8_t *feat8, const i
     a.N = N; a.per = l.per; a.dim = dim; a.C = C; a.tiles = l.tiles; a.parts = l.parts; a.xs = x_scale;
     logreg_pieces_kernel<<<(unsigned)(((long long)l.tiles * (dim / 32) * 64 + 255) / 256), 256, 0, h->stream>>>(a);
     LAUNCH_CHECK(h);
-    switch (dim / 64) {
+    switch (dim / 64) {                                                 // spelled out, not with_ks: tests/test_float_cases_cpu.py reads this table
 #define LOGREG_CASE(KS) case KS: logreg_rows_kernel<KS><<<(unsigned)row_blocks, 256, 0, h->stream>>>(a); break;
         LOGREG_CASE(1) LOGREG_CASE(2) LOGREG_CASE(3) LOGREG_CASE(4) LOGREG_CASE(5) LOGREG_CASE(6) LOGREG_CASE(7) LOGREG_CASE(8)
         LOGREG_CASE(9) LOGREG_CASE(10) LOGREG_CASE(11) LOGREG_CASE(12) LOGREG_CASE(13) LOGREG_CASE(14) LOGREG_CASE(15) LOGREG_CASE(16)
@@ -3465,7 +3414,7 @@ extern "C" int ivit_gauss_score(ivit_handle h, const void *model, size_t model_b
     a.q = q; a.best = best; a.cls = cls; a.dist = dist;
     a.N = N; a.dim = dim; a.R = R; a.C = C; a.qtiles = l.qtiles; a.tiles = l.tiles; a.per = l.per; a.parts = l.parts;
     const dim3 grid((unsigned)row_blocks, (unsigned)l.parts);
-    switch (dim / 64) {
+    switch (dim / 64) {                                                 // spelled out, not with_ks: tests/test_float_cases_cpu.py reads this table
 #define GAUSS_CASE(KS) case KS: gauss_score_kernel<KS><<<grid, 256, 0, h->stream>>>(a); break;
         GAUSS_CASE(1) GAUSS_CASE(2) GAUSS_CASE(3) GAUSS_CASE(4) GAUSS_CASE(5) GAUSS_CASE(6) GAUSS_CASE(7) GAUSS_CASE(8)
         GAUSS_CASE(9) GAUSS_CASE(10) GAUSS_CASE(11) GAUSS_CASE(12) GAUSS_CASE(13) GAUSS_CASE(14) GAUSS_CASE(15) GAUSS_CASE(16)
@@ -3478,17 +3427,14 @@ extern "C" int ivit_gauss_score(ivit_handle h, const void *model, size_t model_b
 }
 
 // ---------------------------------------------------------------- density clustering (include/ivit_density.h)
-// the workspace: the rows * parts int32 partial results of a scan, the rows int32 minima of a sweep, a changed byte per tile in whole
-// words of 64 (each array a multiple of 16 bytes)
-struct DensityLayout {
-    long long tiles, words, per;    // tiles of 32 rows; words of the bitmap; tiles of a part
+// The self-joins (density clustering, the linkage rounds, the core pass) walk the rows of one array as whole tiles of 32, split into
+// parts: the limits every such entry shares, and the parts — the caller's, or about two workgroups per CU of the handle's share in
+// parts of at least 1024 rows; never more than tiles, none of them empty
+struct TileParts {
+    long long tiles, per;           // tiles of 32 rows; tiles of a part
     int parts;
-    size_t m, flag, bytes;          // byte offsets of the minima and the bytes; the whole
 };
-
-// the limits every entry with rows shares, the parts — the caller's, or about two workgroups per CU of the handle's share in parts of
-// at least 1024 rows; never more than tiles, none of them empty — and the layout
-static int density_shape_ok(ivit_handle h, const char *fn, long long rows, int dim, int splits, DensityLayout *l) {
+static int tile_parts_ok(ivit_handle h, const char *fn, long long rows, int dim, int splits, TileParts *t) {
     const char *bad = nullptr;
     if (rows < 1 || rows > 0x7fffffffLL) bad = "rows must be in 1 .. 2^31 - 1";
     else if (splits < 0 || splits > 65535) bad = "splits must be in 0 .. 65535";
@@ -3497,16 +3443,27 @@ static int density_shape_ok(ivit_handle h, const char *fn, long long rows, int d
         snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 64 in 64 .. 1024", fn);
         return IVIT_ERR_UNSUPPORTED;
     }
-    l->tiles = (rows + SEARCH_TILE - 1) / SEARCH_TILE;
-    l->words = (l->tiles + DENSITY_WORD_TILES - 1) / DENSITY_WORD_TILES;
+    t->tiles = (rows + SEARCH_TILE - 1) / SEARCH_TILE;
     const long long cols = (rows + SEARCH_QB - 1) / SEARCH_QB;
     long long s = splits;
     if (s == 0) s = std::max(1ll, std::min((2ll * persistent_cus(h) + cols - 1) / cols, rows / 1024));
-    s = std::min(s, l->tiles);
-    l->per = (l->tiles + s - 1) / s;
-    l->parts = (int)((l->tiles + l->per - 1) / l->per);
-    if (const int rc = launch_fits(h, fn, cols * l->parts, 256, SEARCH_QB)) return rc;
-    l->m = ((size_t)rows * l->parts * 4 + 15) & ~(size_t)15;
+    s = std::min(s, t->tiles);
+    t->per = (t->tiles + s - 1) / s;
+    t->parts = (int)((t->tiles + t->per - 1) / t->per);
+    return launch_fits(h, fn, cols * t->parts, 256, SEARCH_QB);
+}
+
+// the workspace: the rows * parts int32 partial results of a scan, the rows int32 minima of a sweep, a changed byte per tile in whole
+// words of 64 (each array a multiple of 16 bytes)
+struct DensityLayout {
+    TileParts t;
+    long long words;                // words of the bitmap
+    size_t m, flag, bytes;          // byte offsets of the minima and the bytes; the whole
+};
+static int density_shape_ok(ivit_handle h, const char *fn, long long rows, int dim, int splits, DensityLayout *l) {
+    if (const int rc = tile_parts_ok(h, fn, rows, dim, splits, &l->t)) return rc;
+    l->words = (l->t.tiles + DENSITY_WORD_TILES - 1) / DENSITY_WORD_TILES;
+    l->m = ((size_t)rows * l->t.parts * 4 + 15) & ~(size_t)15;
     l->flag = l->m + (((size_t)rows * 4 + 15) & ~(size_t)15);
     l->bytes = l->flag + (size_t)l->words * DENSITY_WORD_TILES;
     return IVIT_OK;
@@ -3532,28 +3489,14 @@ static int density_args_ok(ivit_handle h, const char *fn, const int8_t *x, long 
     else if ((uintptr_t)workspace & 15) bad = "workspace must be 16-byte aligned";
     if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
     a->x = x; a->weight = weight; a->label = nullptr; a->dirty = nullptr; a->part = (int *)workspace;
-    a->rows = rows; a->tiles = l->tiles; a->per = l->per; a->threshold = threshold; a->parts = l->parts;
-    return IVIT_OK;
-}
-
-// every array of an entry against every array it writes: inputs first (n_in of them), then the outputs
-struct DensityRange { const void *p; size_t n; const char *name; };
-static int density_disjoint(ivit_handle h, const char *fn, const DensityRange *r, int n_in, int n) {
-    for (int o = n_in; o < n; ++o)
-        for (int i = 0; i < o; ++i)
-            if (!ranges_disjoint(h, fn, r[i].p, r[i].n, r[i].name, r[o].p, r[o].n, r[o].name, i < n_in ? OVL_IN : OVL_OUT)) return IVIT_ERR_INVALID;
+    a->rows = rows; a->tiles = l->t.tiles; a->per = l->t.per; a->threshold = threshold; a->parts = l->t.parts;
     return IVIT_OK;
 }
 
 template <int MODE>
 static void density_scan_dispatch(ivit_handle h, int dim, const DensityArgs &a) {
     const dim3 grid((unsigned)((a.rows + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
-    switch (dim / 64) {
-#define DENSITY_CASE(KS) case KS: density_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS), MODE><<<grid, 256, 0, h->stream>>>(a); break;
-        DENSITY_CASE(1) DENSITY_CASE(2) DENSITY_CASE(3) DENSITY_CASE(4) DENSITY_CASE(5) DENSITY_CASE(6) DENSITY_CASE(7) DENSITY_CASE(8)
-        DENSITY_CASE(9) DENSITY_CASE(10) DENSITY_CASE(11) DENSITY_CASE(12) DENSITY_CASE(13) DENSITY_CASE(14) DENSITY_CASE(15) DENSITY_CASE(16)
-#undef DENSITY_CASE
-    }
+    with_ks(dim, [&](auto KS) { density_scan_kernel<KS(), scan_prefetch(KS()), MODE><<<grid, 256, 0, h->stream>>>(a); });
 }
 
 extern "C" int ivit_density_degree(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, float threshold, int splits,
@@ -3564,9 +3507,9 @@ extern "C" int ivit_density_degree(ivit_handle h, const int8_t *x, int64_t rows,
     DensityLayout l;
     if (const int rc = density_args_ok(h, __func__, x, rows, dim, weight, threshold, splits, workspace, bytes, &a, &l)) return rc;
     REQUIRE_ALIGNED(h, degree, "degree", 4);
-    const DensityRange r[4] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {workspace, bytes, "workspace"},
+    const ArgRange r[4] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {workspace, bytes, "workspace"},
                                {degree, (size_t)rows * 4, "degree"}};
-    if (const int rc = density_disjoint(h, __func__, r, 2, 4)) return rc;
+    if (const int rc = args_disjoint(h, __func__, r, 2, 4)) return rc;
     density_scan_dispatch<DENSITY_DEGREE>(h, dim, a);
     LAUNCH_CHECK(h);
     const DensityFoldArgs f = {a.part, nullptr, degree, rows, a.parts};
@@ -3584,8 +3527,8 @@ extern "C" int ivit_density_init(ivit_handle h, const int32_t *degree, int64_t r
     REQUIRE_ALIGNED(h, label, "label", 4);
     REQUIRE_ALIGNED(h, dirty, "dirty", 8);
     const long long words = (rows + DENSITY_WORD_ROWS - 1) / DENSITY_WORD_ROWS;
-    const DensityRange r[3] = {{degree, (size_t)rows * 4, "degree"}, {label, (size_t)rows * 4, "label"}, {dirty, (size_t)words * 8, "dirty"}};
-    if (const int rc = density_disjoint(h, __func__, r, 1, 3)) return rc;
+    const ArgRange r[3] = {{degree, (size_t)rows * 4, "degree"}, {label, (size_t)rows * 4, "label"}, {dirty, (size_t)words * 8, "dirty"}};
+    if (const int rc = args_disjoint(h, __func__, r, 1, 3)) return rc;
     density_init_kernel<<<(unsigned)words, 256, 0, h->stream>>>(degree, rows, min_pts, label, (unsigned long long *)dirty);
     LAUNCH_CHECK(h);
     return IVIT_OK;
@@ -3605,10 +3548,10 @@ extern "C" int ivit_density_sweep(ivit_handle h, const int8_t *x, int64_t rows, 
     REQUIRE_ALIGNED(h, changed, "changed", 4);
     REQUIRE_ALIGNED(h, dirty_in, "dirty_in", 8);
     REQUIRE_ALIGNED(h, dirty_out, "dirty_out", 8);
-    const DensityRange r[8] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {label_in, (size_t)rows * 4, "label_in"},
+    const ArgRange r[8] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {label_in, (size_t)rows * 4, "label_in"},
                                {dirty_in, (size_t)l.words * 8, "dirty_in"}, {workspace, bytes, "workspace"}, {label_out, (size_t)rows * 4, "label_out"},
                                {dirty_out, (size_t)l.words * 8, "dirty_out"}, {changed, 4, "changed"}};
-    if (const int rc = density_disjoint(h, __func__, r, 4, 8)) return rc;
+    if (const int rc = args_disjoint(h, __func__, r, 4, 8)) return rc;
     a.label = label_in; a.dirty = (const unsigned long long *)dirty_in;
     int *m = (int *)((char *)workspace + l.m);
     unsigned char *flag = (unsigned char *)workspace + l.flag;
@@ -3617,9 +3560,9 @@ extern "C" int ivit_density_sweep(ivit_handle h, const int8_t *x, int64_t rows, 
     const DensityFoldArgs f = {a.part, nullptr, m, rows, a.parts};
     density_fold_kernel<DENSITY_SWEEP><<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(f);
     LAUNCH_CHECK(h);
-    density_jump_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(m, label_in, label_out, flag, rows, l.tiles);
+    density_jump_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(m, label_in, label_out, flag, rows, l.t.tiles);
     LAUNCH_CHECK(h);
-    density_pack_kernel<<<1, 256, 0, h->stream>>>(flag, l.tiles, (unsigned long long *)dirty_out, changed);
+    density_pack_kernel<<<1, 256, 0, h->stream>>>(flag, l.t.tiles, (unsigned long long *)dirty_out, changed);
     LAUNCH_CHECK(h);
     return IVIT_OK;
 }
@@ -3633,9 +3576,9 @@ extern "C" int ivit_density_border(ivit_handle h, const int8_t *x, int64_t rows,
     if (const int rc = density_args_ok(h, __func__, x, rows, dim, weight, threshold, splits, workspace, bytes, &a, &l)) return rc;
     REQUIRE_ALIGNED(h, label, "label", 4);
     REQUIRE_ALIGNED(h, out, "out", 4);
-    const DensityRange r[5] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {label, (size_t)rows * 4, "label"},
+    const ArgRange r[5] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {label, (size_t)rows * 4, "label"},
                                {workspace, bytes, "workspace"}, {out, (size_t)rows * 4, "out"}};
-    if (const int rc = density_disjoint(h, __func__, r, 3, 5)) return rc;
+    if (const int rc = args_disjoint(h, __func__, r, 3, 5)) return rc;
     a.label = label;
     density_scan_dispatch<DENSITY_BORDER>(h, dim, a);
     LAUNCH_CHECK(h);
@@ -3647,16 +3590,16 @@ extern "C" int ivit_density_border(ivit_handle h, const int8_t *x, int64_t rows,
 
 // ---------------------------------------------------------------- single-linkage hierarchy (include/ivit_linkage.h)
 // the workspace: the rows * parts 64-bit keys of a scan, then per row a 64-bit key (rbest), a 64-bit edge (cedge), a 32-bit value
-// (cbest) and a 32-bit parent (each array a multiple of 16 bytes).  The parts are ivit_density.h's (density_shape_ok).
+// (cbest) and a 32-bit parent (each array a multiple of 16 bytes).  The parts are those of every self-join (tile_parts_ok).
 struct LinkageLayout {
-    DensityLayout d;
+    TileParts t;
     size_t rbest, cedge, cbest, parent, bytes;
 };
 
 static int linkage_shape_ok(ivit_handle h, const char *fn, long long rows, int dim, int splits, LinkageLayout *l) {
-    if (const int rc = density_shape_ok(h, fn, rows, dim, splits, &l->d)) return rc;
+    if (const int rc = tile_parts_ok(h, fn, rows, dim, splits, &l->t)) return rc;
     const size_t r8 = ((size_t)rows * 8 + 15) & ~(size_t)15, r4 = ((size_t)rows * 4 + 15) & ~(size_t)15;
-    l->rbest = ((size_t)rows * l->d.parts * 8 + 15) & ~(size_t)15;
+    l->rbest = ((size_t)rows * l->t.parts * 8 + 15) & ~(size_t)15;
     l->cedge = l->rbest + r8;
     l->cbest = l->cedge + r8;
     l->parent = l->cbest + r4;
@@ -3674,9 +3617,9 @@ extern "C" int ivit_linkage_workspace_bytes(ivit_handle h, int64_t rows, int dim
 }
 
 // the six arrays a run owns, aligned and disjoint from each other and from what stands in front of them in r (n_in inputs)
-static int linkage_outputs_ok(ivit_handle h, const char *fn, DensityRange *r, int n_in, long long rows, int32_t *comp, uint8_t *done, int32_t *edge_u,
+static int linkage_outputs_ok(ivit_handle h, const char *fn, ArgRange *r, int n_in, long long rows, int32_t *comp, uint8_t *done, int32_t *edge_u,
                               int32_t *edge_v, float *edge_val, int32_t *state) {
-    const DensityRange outs[6] = {{comp, (size_t)rows * 4, "comp"}, {done, (size_t)rows, "done"}, {edge_u, (size_t)rows * 4, "edge_u"},
+    const ArgRange outs[6] = {{comp, (size_t)rows * 4, "comp"}, {done, (size_t)rows, "done"}, {edge_u, (size_t)rows * 4, "edge_u"},
                                   {edge_v, (size_t)rows * 4, "edge_v"}, {edge_val, (size_t)rows * 4, "edge_val"}, {state, 16, "state"}};
     for (int i = 0; i < 6; ++i) {
         if (i != 1 && ((uintptr_t)outs[i].p & 3)) {
@@ -3693,9 +3636,9 @@ extern "C" int ivit_linkage_init(ivit_handle h, int64_t rows, int32_t *comp, uin
     CHECK_H(h);
     REQUIRE(h, comp && done && edge_u && edge_v && edge_val && state, "comp, done, edge_u, edge_v, edge_val or state is null");
     REQUIRE(h, rows >= 1 && rows <= 0x7fffffffLL, "rows must be in 1 .. 2^31 - 1");
-    DensityRange r[6];
+    ArgRange r[6];
     if (const int rc = linkage_outputs_ok(h, __func__, r, 0, rows, comp, done, edge_u, edge_v, edge_val, state)) return rc;
-    if (const int rc = density_disjoint(h, __func__, r, 0, 6)) return rc;
+    if (const int rc = args_disjoint(h, __func__, r, 0, 6)) return rc;
     LinkageArgs a = {};
     a.comp = comp; a.done = done; a.edge_u = edge_u; a.edge_v = edge_v; a.edge_val = edge_val; a.state = state; a.rows = rows;
     linkage_init_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, h->stream>>>(a);
@@ -3722,25 +3665,20 @@ static int linkage_round(ivit_handle h, const char *fn, const int8_t *x, long lo
     if ((uintptr_t)workspace & 15) return refuse("workspace must be 16-byte aligned");
     if ((uintptr_t)core & 3) return refuse("core must be 4-byte aligned");
     constexpr int n_in = REACH ? 3 : 2;
-    DensityRange r[10] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}};
+    ArgRange r[10] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}};
     if (REACH) r[2] = {core, (size_t)rows * 4, "core"};
     r[n_in] = {workspace, bytes, "workspace"};
     if (const int rc = linkage_outputs_ok(h, fn, r, n_in + 1, rows, comp, done, edge_u, edge_v, edge_val, state)) return rc;
-    if (const int rc = density_disjoint(h, fn, r, n_in, n_in + 7)) return rc;
+    if (const int rc = args_disjoint(h, fn, r, n_in, n_in + 7)) return rc;
     LinkageArgs a = {};
     char *ws = (char *)workspace;
     a.x = x; a.weight = weight; a.comp = comp; a.done = done; a.edge_u = edge_u; a.edge_v = edge_v; a.edge_val = edge_val; a.state = state;
     a.part = (unsigned long long *)ws; a.rbest = (unsigned long long *)(ws + l.rbest); a.cedge = (unsigned long long *)(ws + l.cedge);
     a.cbest = (unsigned *)(ws + l.cbest); a.parent = (int *)(ws + l.parent);
-    a.rows = rows; a.tiles = l.d.tiles; a.per = l.d.per; a.floor = floor; a.parts = l.d.parts; a.core = core;
+    a.rows = rows; a.tiles = l.t.tiles; a.per = l.t.per; a.floor = floor; a.parts = l.t.parts; a.core = core;
     const dim3 grid((unsigned)((rows + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
     const unsigned per_row = (unsigned)((rows + 255) / 256);
-    switch (dim / 64) {
-#define LINKAGE_CASE(KS) case KS: linkage_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS), MODE><<<grid, 256, 0, h->stream>>>(a); break;
-        LINKAGE_CASE(1) LINKAGE_CASE(2) LINKAGE_CASE(3) LINKAGE_CASE(4) LINKAGE_CASE(5) LINKAGE_CASE(6) LINKAGE_CASE(7) LINKAGE_CASE(8)
-        LINKAGE_CASE(9) LINKAGE_CASE(10) LINKAGE_CASE(11) LINKAGE_CASE(12) LINKAGE_CASE(13) LINKAGE_CASE(14) LINKAGE_CASE(15) LINKAGE_CASE(16)
-#undef LINKAGE_CASE
-    }
+    with_ks(dim, [&](auto KS) { linkage_scan_kernel<KS(), scan_prefetch(KS()), MODE><<<grid, 256, 0, h->stream>>>(a); });
     LAUNCH_CHECK(h);
     linkage_fold_kernel<<<per_row, 256, 0, h->stream>>>(a);
     LAUNCH_CHECK(h);
@@ -3763,9 +3701,9 @@ extern "C" int ivit_linkage_round(ivit_handle h, const int8_t *x, int64_t rows, 
 }
 
 // ---------------------------------------------------------------- HDBSCAN: core similarities, the mutual-reachability round (include/ivit_hdbscan.h)
-// the workspace of the core pass: the rows * parts * min_pts 32-bit ordered values of the scan.  The parts are ivit_density.h's.
-static int core_shape_ok(ivit_handle h, const char *fn, long long rows, int dim, int min_pts, int splits, DensityLayout *l, size_t *bytes) {
-    if (const int rc = density_shape_ok(h, fn, rows, dim, splits, l)) return rc;
+// the workspace of the core pass: the rows * parts * min_pts 32-bit ordered values of the scan.  The parts are those of every self-join.
+static int core_shape_ok(ivit_handle h, const char *fn, long long rows, int dim, int min_pts, int splits, TileParts *l, size_t *bytes) {
+    if (const int rc = tile_parts_ok(h, fn, rows, dim, splits, l)) return rc;
     if (min_pts < 1 || min_pts > CORE_MAX_K || min_pts > rows) {
         snprintf(h->err, sizeof(h->err), "%s: min_pts must be in 1 .. min(rows, %d)", fn, CORE_MAX_K);
         return IVIT_ERR_INVALID;
@@ -3777,46 +3715,35 @@ static int core_shape_ok(ivit_handle h, const char *fn, long long rows, int dim,
 extern "C" int ivit_core_workspace_bytes(ivit_handle h, int64_t rows, int dim, int min_pts, int splits, size_t *bytes) {
     CHECK_H(h);
     REQUIRE(h, bytes, "bytes is null");
-    DensityLayout l;
+    TileParts l;
     size_t n;
     if (const int rc = core_shape_ok(h, __func__, rows, dim, min_pts, splits, &l, &n)) return rc;
     *bytes = n;
     return IVIT_OK;
 }
 
-template <int KS>
-static int core_scan_launch(ivit_handle h, dim3 grid, size_t lds, const CoreArgs &a) {
-    return launch_dyn<core_scan_kernel<KS, (KS <= SEARCH_PF_MAX_KS)>>(h, grid, dim3(256), lds, a);
-}
-
 extern "C" int ivit_core_similarity(ivit_handle h, const int8_t *x, int64_t rows, int dim, const float *weight, int min_pts, int splits, void *workspace,
                                     size_t bytes, float *core) {
     CHECK_H(h);
     REQUIRE(h, x && workspace && core, "x, workspace or core is null");
-    DensityLayout l;
+    TileParts l;
     size_t need;
     if (const int rc = core_shape_ok(h, __func__, rows, dim, min_pts, splits, &l, &need)) return rc;
     REQUIRE(h, bytes >= need, "workspace too small (ivit_core_workspace_bytes)");
     REQUIRE_A16(h, x, "x");
     REQUIRE_A16(h, workspace, "workspace");
     REQUIRE_ALIGNED(h, core, "core", 4);
-    const DensityRange r[4] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {workspace, bytes, "workspace"},
+    const ArgRange r[4] = {{x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"}, {workspace, bytes, "workspace"},
                                {core, (size_t)rows * 4, "core"}};
-    if (const int rc = density_disjoint(h, __func__, r, 2, 4)) return rc;
+    if (const int rc = args_disjoint(h, __func__, r, 2, 4)) return rc;
     REQUIRE_LAUNCH(h, (rows + 3) / 4, 256, 4);
     CoreArgs a = {};
     a.x = x; a.weight = weight; a.ws = (unsigned *)workspace; a.core = core;
     a.rows = rows; a.tiles = l.tiles; a.per = l.per; a.k = min_pts; a.parts = l.parts;
     const dim3 grid((unsigned)((rows + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
-    const size_t lds = core_lds_bytes(min_pts);
-    int rc = IVIT_OK;
-    switch (dim / 64) {
-#define CORE_CASE(KS) case KS: rc = core_scan_launch<KS>(h, grid, lds, a); break;
-        CORE_CASE(1) CORE_CASE(2) CORE_CASE(3) CORE_CASE(4) CORE_CASE(5) CORE_CASE(6) CORE_CASE(7) CORE_CASE(8)
-        CORE_CASE(9) CORE_CASE(10) CORE_CASE(11) CORE_CASE(12) CORE_CASE(13) CORE_CASE(14) CORE_CASE(15) CORE_CASE(16)
-#undef CORE_CASE
-    }
-    if (rc) return rc;
+    const size_t lds = search_lds_bytes(min_pts, CORE_SLOT);
+    if (const int rc = with_ks(dim, [&](auto KS) { return launch_dyn<core_scan_kernel<KS(), scan_prefetch(KS())>>(h, grid, dim3(256), lds, a); }))
+        return rc;
     LAUNCH_CHECK(h);
     const unsigned per_wave = (unsigned)((rows + 3) / 4);                   // one wavefront per row
     if ((long long)a.parts * min_pts <= 1024) core_select_kernel<16><<<per_wave, 256, 0, h->stream>>>(a);

@@ -1,17 +1,16 @@
 // ivit_linkage.h — the single-linkage hierarchy (include/ivit_linkage.h): the maximum-similarity spanning forest of int8 rows by
 // Borůvka rounds, the [rows, rows] matrix never written.  Per round every row needs ONE thing from a pass over all rows: its best
 // neighbour outside its own component, and a scan that keeps the scores in registers produces it directly.  Takes from ivit_search.h
-// the work shape (SEARCH_QW, SEARCH_QB, SEARCH_TILE, SEARCH_PF_MAX_KS), topk_value and the inverse of the ordered value
-// (search_key_value), from ivit_density.h the geometry of the scan and the value of a pair.
+// the work shape (SEARCH_QW, SEARCH_QB, SEARCH_TILE, SEARCH_PF_MAX_KS: ivit_scan.h), from ivit_topk.h topk_value, the key of a value
+// and the inverse of the ordered value, from ivit_scan.h the geometry of the scan and the value of a pair (scan_pair_value).
 //
-//   value      v{b, g} as csrc/ivit_density.h: fl32(fl32(fl32(dot) * weight[max(b, g)]) * weight[min(b, g)]), one value per unordered
-//              pair, whichever of the two is the resident row.
+//   value      v{b, g} = scan_pair_value of ivit_scan.h: one value per unordered pair, whichever of the two is the resident row.
 //   edge order v descending (-0.0 equal to +0.0), then the smaller row ascending, then the larger row ascending: total.
 //   FOR A FIXED ROW q the order of its edges {q, g} is "largest v, then smallest g".  Among edges of equal v those with g < q have the
 //              smaller row g < q and stand before every edge with g > q (smaller row q); among the former the smaller row IS g, among
 //              the latter the smaller row is q for all and the larger row IS g.  Both runs ascend in g and the first lies below the
-//              second: ascending g throughout.  A row's best edge is therefore one 64-bit key, LINKAGE key = ordered(v) << 32 |
-//              0xFFFFFFFF - g, and the larger key is the better edge; ordered() is topk_key's map (unsigned order == float order, -0.0
+//              second: ascending g throughout.  A row's best edge is therefore one 64-bit key, topk_key(v, g) = topk_ordered(v) << 32 |
+//              0xFFFFFFFF - g, and the larger key is the better edge; topk_ordered is ivit_topk.h's map (unsigned order == float order, -0.0
 //              folded into +0.0), never 0 for a value that is not NaN, so key 0 is "no edge".
 //
 // linkage_scan_kernel<KS, PF, MODE>   dim = 64 KS; ONE source for the plain round and the mutual-reachability round below.  Grid (tiles of 128 resident rows) x (parts of the same rows, whole tiles of 32); four
@@ -82,13 +81,6 @@ struct LinkageArgs {
 #define LINKAGE_PLAIN 0
 #define LINKAGE_REACH 1
 
-__device__ __forceinline__ unsigned long long linkage_key(float v, int g) {
-    unsigned u = __float_as_uint(v);
-    u = u == 0x80000000u ? 0u : u;                                       // topk_key's map of a value
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (0xFFFFFFFFu - (unsigned)g);
-}
-
 template <int KS, bool PF, int MODE, bool PFC = PF>
 __global__ __launch_bounds__(256) void linkage_scan_kernel(LinkageArgs p) {
     constexpr int NF = 2 * KS, DIM = 64 * KS;
@@ -125,14 +117,14 @@ __global__ __launch_bounds__(256) void linkage_scan_kernel(LinkageArgs p) {
         }
         auto load_core = [&](long long g0, float (&c)[NC]) {
 #pragma unroll
-            for (int r = 0; r < NC; ++r) c[r] = p.core[min(g0 + ((r & 3) + 8 * (r >> 2) + 4 * half), last_row)];
+            for (int r = 0; r < NC; ++r) c[r] = p.core[min(g0 + scan_tile_row(r, half), last_row)];
         };
         auto load_tile = [&](long long g0, v4i (&a)[NF], float (&w)[16]) {
             const int8_t *src = p.x + (size_t)min(g0 + l31, last_row) * DIM + 16 * half;
 #pragma unroll
             for (int f = 0; f < NF; ++f) a[f] = *reinterpret_cast<const v4i *>(src + 32 * f);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) w[r] = p.weight ? p.weight[min(g0 + ((r & 3) + 8 * (r >> 2) + 4 * half), last_row)] : 1.0f;
+            for (int r = 0; r < 16; ++r) w[r] = p.weight ? p.weight[min(g0 + scan_tile_row(r, half), last_row)] : 1.0f;
         };
 
         v4i a[NF];
@@ -155,23 +147,23 @@ __global__ __launch_bounds__(256) void linkage_scan_kernel(LinkageArgs p) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[f], qf[f], acc, 0, 0, 0);
 
-            const int nrow = active ? (int)min((long long)SEARCH_TILE, p.rows - g0) : 0;      // rows of this tile inside the array
+            const int nrow = active ? scan_nrow(p.rows, g0) : 0; // rows of this tile inside the array
             // tile row `row` is row g = g0 + row of the array: g > b exactly when row > b - g0
-            const int diag = (int)max(-1ll, min((long long)SEARCH_TILE, q0 + l31 - g0));
+            const int diag = scan_diag(q0 + l31 - g0);
             float v[16];
             unsigned mask = 0u;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int row = scan_tile_row(r, half);
                 const bool up = row > diag;                              // the larger row's weight first
-                v[r] = __fmul_rn(topk_value(acc[r], up ? w[r] : qw), up ? qw : w[r]);
+                v[r] = scan_pair_value(acc[r], w[r], qw, up);
                 if constexpr (REACH) v[r] += 0.0f;                       // -0.0 -> +0.0 before any minimum
                 if (row < nrow && v[r] >= flr && !(v[r] <= bestv)) mask |= 1u << r;
             }
             if (__any(mask != 0u)) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {                           // ascending g; row < nrow: inside the array
-                    const int g = (int)g0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int g = scan_tile_row(r, half, (int)g0);
                     if constexpr (REACH) {
                         if ((mask & (1u << r)) && !(v[r] <= bestv)) {
                             const float m = fminf(fminf(v[r], cq), c[r]) + 0.0f;
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(256) void linkage_scan_kernel(LinkageArgs p) {
         }
     }
 
-    unsigned long long key = bestg >= 0 ? linkage_key(bestv, bestg) : 0ull;
+    unsigned long long key = bestg >= 0 ? topk_key(bestv, bestg) : 0ull;
     const unsigned long long other = __shfl_xor(key, 32);                // the two lanes of a row; every lane of the wavefront is here
     key = other > key ? other : key;
     if (half == 0 && live) {
@@ -260,7 +252,7 @@ __global__ __launch_bounds__(256) void linkage_hook_kernel(LinkageArgs p) {
                     hooked = true;
                     p.edge_u[c] = i;
                     p.edge_v[c] = j;
-                    p.edge_val[c] = search_key_value((unsigned long long)p.cbest[c] << 32);
+                    p.edge_val[c] = topk_ordered_value(p.cbest[c]);
                 }
             }
         }

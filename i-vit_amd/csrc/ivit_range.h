@@ -1,8 +1,8 @@
 // ivit_range.h — range search (include/ivit_range.h): every gallery row whose score against a query reaches a threshold, in CSR form,
 // the gallery read twice, the scores never written.  Deterministic without a sort and without an atomic: the first pass counts the
 // hits of every (query, part of the gallery), an exclusive scan in query-major order turns the counts into positions, the second pass
-// — THE SAME kernel source, so that the two cannot disagree about a hit — writes every hit at its position.  Takes nothing from
-// ivit_search.h but the work shape (SEARCH_QW, SEARCH_QB, SEARCH_TILE, SEARCH_PF_MAX_KS) and topk_value.
+// — THE SAME kernel source, so that the two cannot disagree about a hit — writes every hit at its position.  The work shape, the lane layout of a
+// tile (scan_tile_row) and its bounds (scan_nrow, scan_diag) are those of ivit_scan.h.
 //
 //   value   v[b, g] = fl32(topk_value(dot[b, g], weight[g]) * qweight[b]): one conversion and two fp32 multiplies in this order, a NULL
 //           weight / qweight a multiplication by 1.0f (the same bits, -0.0 included).
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void range_scan_kernel(RangeArgs p) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) a[f] = *reinterpret_cast<const v4i *>(src + 32 * f);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) w[r] = p.weight ? p.weight[min(g0 + ((r & 3) + 8 * (r >> 2) + 4 * half), last_row)] : 1.0f;
+        for (int r = 0; r < 16; ++r) w[r] = p.weight ? p.weight[min(g0 + scan_tile_row(r, half), last_row)] : 1.0f;
     };
 
     // the diagonal as seen from this lane's query, in rows of the gallery; without the triangle so far below that every row is above it.
@@ -111,14 +111,14 @@ __global__ __launch_bounds__(256) void range_scan_kernel(RangeArgs p) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[f], qf[f], acc, 0, 0, 0);
 
-        const int nrow = live ? (int)min((long long)SEARCH_TILE, g_end - g0) : 0;      // rows of this tile inside the part
+        const int nrow = live ? scan_nrow(g_end, g0) : 0; // rows of this tile inside the part
         // a row of the tile is above the diagonal when row > (query_base + b) - (index_base + g0); -1 lets every row pass
-        const int diag = (int)max(-1ll, min((long long)SEARCH_TILE, dq - g0));
+        const int diag = scan_diag(dq - g0);
         float v[16];
         unsigned mask = 0u;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int row = scan_tile_row(r, half);
             v[r] = __fmul_rn(topk_value(acc[r], w[r]), qw);
             if (row < nrow && row > diag && v[r] >= thr) mask |= 1u << r;
         }
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void range_scan_kernel(RangeArgs p) {
                                           __popc(mask & group & ((1u << r) - 1u));
                         const long long pos = cursor + ahead;
                         if ((unsigned long long)pos < (unsigned long long)p.capacity) {
-                            p.idx[pos] = c0 + (r & 3) + 8 * j + 4 * half;
+                            p.idx[pos] = scan_tile_row(r, half, c0);
                             if (p.val) p.val[pos] = v[r];
                         }
                     }

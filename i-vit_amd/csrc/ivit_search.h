@@ -41,21 +41,18 @@
 // Plain vector stores only, no scratch.
 #pragma once
 #include "../../include/ivit_search.h"
-#include "ivit_topk.h"
+#include "ivit_scan.h"
 
 #define SEARCH_MAX_K 64
 #define SEARCH_MIN_DIM 64
 #define SEARCH_MAX_DIM 1024
-#define SEARCH_QW 32                               // queries of a wavefront: the N of the MFMA
-#define SEARCH_QB (4 * SEARCH_QW)                  // queries of a workgroup
-#define SEARCH_TILE 32                             // gallery rows of a tile: the M of the MFMA
-#define SEARCH_PF_MAX_KS 8                         // prefetch the next tile up to dim 512
 
+// the candidate slots of a resident row in LDS, `slot` bytes each (8: a packed key here; 4: an ordered value in ivit_hdbscan.h)
 __host__ __device__ __forceinline__ int search_nslot(int k) { return k <= 16 ? 64 : 128; }
 __host__ __device__ __forceinline__ int search_kcap(int k) { return k <= 16 ? 16 : 64; }
-// bytes between two queries' slots: one spare slot, so that the 32 queries of a wavefront start in different banks
-__host__ __device__ __forceinline__ int search_qstride(int k) { return search_nslot(k) * 8 + 8; }
-__host__ __device__ __forceinline__ size_t search_lds_bytes(int k) { return (size_t)SEARCH_QB * search_qstride(k); }
+// bytes between two rows' slots: one spare slot, so that the 32 rows of a wavefront start in different banks
+__host__ __device__ __forceinline__ int search_qstride(int k, int slot = 8) { return search_nslot(k) * slot + slot; }
+__host__ __device__ __forceinline__ size_t search_lds_bytes(int k, int slot = 8) { return (size_t)SEARCH_QB * search_qstride(k, slot); }
 
 __device__ __forceinline__ unsigned long long search_pack(unsigned long long key, unsigned vbits) {
     const unsigned lo = (unsigned)key;                                   // 0xFFFFFFFF - c: bit 31 is set for every c < 2^31
@@ -63,8 +60,7 @@ __device__ __forceinline__ unsigned long long search_pack(unsigned long long key
 }
 __device__ __forceinline__ int search_key_index(unsigned long long p) { return (int)(0x7FFFFFFFu - ((unsigned)p >> 1)); }
 __device__ __forceinline__ float search_key_value(unsigned long long p) {
-    unsigned u = (unsigned)(p >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;                      // topk_key's map, inverted
+    unsigned u = __float_as_uint(topk_ordered_value((unsigned)(p >> 32)));
     if ((unsigned)p & 1u) u = 0x80000000u;                               // a zero that was -0.0
     return __uint_as_float(u);
 }
@@ -84,30 +80,31 @@ __device__ __forceinline__ void search_wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// Compaction of all 32 queries of a wavefront at once, lane q < 32 working ALONE on query q's nslot slots (unused ones hold 0): k rounds of
+// Compaction of all 32 queries of a wavefront at once, lane q < 32 working ALONE on query q's nslot slots of type SLOT (unused ones hold 0): k rounds of
 // selection by swapping — round j finds the largest of slots j .. nslot - 1 and swaps it into slot j — then every slot behind the k-th
 // is zeroed.  Afterwards slots 0 .. k-1 hold the k best, best first (0 beyond what there is).  No lane reads what another wrote inside:
 // the two fences order it against the appends before and the readers behind.  The scan's loads are independent (LDS pipelines them); a
 // wave-wide maximum per rank and query instead (the rounds of logits_topk_kernel, one query at a time) is six dependent cross-lane
 // exchanges per rank: the whole search was 3.1 x slower with it at 131 072 rows (profiles/README.md, "Gallery search").
+template <class SLOT>
 __device__ __forceinline__ void search_compact_all(char *wbase, int qstride, int nslot, int k, int lane) {
     search_wave_sync();
     if (lane < SEARCH_QW) {
-        unsigned long long *s = reinterpret_cast<unsigned long long *>(wbase + (size_t)lane * qstride);
+        SLOT *s = reinterpret_cast<SLOT *>(wbase + (size_t)lane * qstride);
         for (int j = 0; j < k; ++j) {
-            unsigned long long best = s[j];
+            SLOT best = s[j];
             int pos = j;
 #pragma unroll 8
             for (int i = j + 1; i < nslot; ++i) {
-                const unsigned long long e = s[i];
+                const SLOT e = s[i];
                 if (e > best) { best = e; pos = i; }
             }
-            if (best == 0ull) break;                                     // nothing is left: the rest is zeros already
-            const unsigned long long t = s[j];
+            if (best == 0) break;                                        // nothing is left: the rest is zeros already
+            const SLOT t = s[j];
             s[pos] = t;
             s[j] = best;
         }
-        for (int i = k; i < nslot; ++i) s[i] = 0ull;
+        for (int i = k; i < nslot; ++i) s[i] = 0;
     }
     search_wave_sync();
 }
@@ -140,7 +137,7 @@ __global__ __launch_bounds__(256) void search_scan_kernel(SearchArgs p) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) a[f] = *reinterpret_cast<const v4i *>(src + 32 * f);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) w[r] = p.weight ? p.weight[min(g0 + ((r & 3) + 8 * (r >> 2) + 4 * half), last_row)] : 1.0f;
+        for (int r = 0; r < 16; ++r) w[r] = p.weight ? p.weight[min(g0 + scan_tile_row(r, half), last_row)] : 1.0f;
     };
 
     unsigned long long thr = 0ull;                                       // this lane's query: its k-th best key so far
@@ -161,11 +158,11 @@ __global__ __launch_bounds__(256) void search_scan_kernel(SearchArgs p) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[f], qf[f], acc, 0, 0, 0);
 
-        const int nrow = (int)min((long long)SEARCH_TILE, g_end - g0);   // rows of this tile inside the part
+        const int nrow = scan_nrow(g_end, g0);         // rows of this tile inside the part
         unsigned sv = 0u;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int row = scan_tile_row(r, half);
             if (row < nrow && topk_value(acc[r], w[r]) >= tv) sv |= 1u << r;
         }
         if (__any(sv != 0u)) {
@@ -173,13 +170,13 @@ __global__ __launch_bounds__(256) void search_scan_kernel(SearchArgs p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (sv & (1u << r)) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int row = scan_tile_row(r, half);
                     const unsigned long long key = search_pack(topk_key(acc[r], w[r], c0 + row), __float_as_uint(topk_value(acc[r], w[r])));
                     if (key > thr) pend[cnt++] = key;                    // cnt <= CL - 16 before the tile: room for all 16
                 }
             }
             if (__any(cnt > CL - 16)) {                                  // a run that could not take another tile: wave-uniform
-                search_compact_all(wbase, qstride, nslot, k, lane);
+                search_compact_all<unsigned long long>(wbase, qstride, nslot, k, lane);
                 thr = best[k - 1];                                       // both lanes of a query read its new k-th
                 tv = thr ? search_key_value(thr) : -__builtin_inff();
                 cnt = 0;
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(256) void search_scan_kernel(SearchArgs p) {
         }
     }
 
-    search_compact_all(wbase, qstride, nslot, k, lane);
+    search_compact_all<unsigned long long>(wbase, qstride, nslot, k, lane);
     const int nlive = (int)min((long long)SEARCH_QW, p.nq - q0);
     for (int q = 0; q < nlive; ++q)
         if (lane < k)

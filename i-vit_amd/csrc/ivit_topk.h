@@ -27,13 +27,20 @@
 
 __device__ __forceinline__ float topk_value(int acc, float scale) { return __fmul_rn((float)acc, scale); }
 
-// 0 is no class's key (the low word of a real key is 0xFFFFFFFF - c > 0 for c < 2^31): it stands for "nothing"
-__device__ __forceinline__ unsigned long long topk_key(int acc, float scale, int c) {
-    unsigned u = __float_as_uint(topk_value(acc, scale));
+// The library's ONE order-preserving map of an fp32 value to an unsigned: unsigned order == float order, -0.0 folded into +0.0; never
+// 0 for a value that is not NaN.  The inverse gives a folded zero back as +0.0.
+__device__ __forceinline__ unsigned topk_ordered(float v) {
+    unsigned u = __float_as_uint(v);
     u = u == 0x80000000u ? 0u : u;                                   // -0.0 ties +0.0
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                  // unsigned order == float order
-    return ((unsigned long long)u << 32) | (0xFFFFFFFFu - (unsigned)c);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+__device__ __forceinline__ float topk_ordered_value(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+
+// 0 is no class's key (the low word of a real key is 0xFFFFFFFF - c > 0 for c < 2^31): it stands for "nothing"
+__device__ __forceinline__ unsigned long long topk_key(float v, int c) {
+    return ((unsigned long long)topk_ordered(v) << 32) | (0xFFFFFFFFu - (unsigned)c);
+}
+__device__ __forceinline__ unsigned long long topk_key(int acc, float scale, int c) { return topk_key(topk_value(acc, scale), c); }
 
 __device__ __forceinline__ unsigned long long topk_wave_max(unsigned long long v) {
 #pragma unroll

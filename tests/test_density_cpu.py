@@ -76,3 +76,9 @@ def test_dbscan_reference_at_min_pts_1_is_duplicate_groups(cosine):
         assert np.array_equal(core, degree >= 1) and (core.all() or not cosine), float(thr)
         assert np.array_equal(np.where(label < 0, np.arange(70), label), duplicate_groups(pairs, 70)), float(thr)
     assert 1 < len(np.unique(dbscan_reference(x, w, np.float32(np.percentile(v, 90)), 1)[0])) < 70
+
+
+# ---------------------------------------------------------------- the kernels in the code object
+def test_density_kernels_in_code_object_without_scratch(tmp_path):
+    from test_search_cpu import check_scan_kernels_in_code_object
+    check_scan_kernels_in_code_object(tmp_path, "density_scan_kernel", ["Li0E", "Li1E", "Li2E"])        # degree, sweep, border

@@ -70,3 +70,9 @@ def test_planted_blobs_and_scattered_rows():
     assert np.array_equal(want, names)
     _, u, v, val = hdbscan_reference(x, w, 5)
     assert np.array_equal(Linkage(u, v, val, 34).condense(5).select(), want)
+
+
+# ---------------------------------------------------------------- the kernels in the code object
+def test_core_kernels_in_code_object_without_scratch(tmp_path):
+    from test_search_cpu import check_scan_kernels_in_code_object
+    check_scan_kernels_in_code_object(tmp_path, "core_scan_kernel", [""])                                # the candidate slots are dynamic LDS

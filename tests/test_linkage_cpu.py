@@ -61,3 +61,10 @@ def test_cut_k_and_matrix():
     Z = tree.matrix()
     assert Z.shape == (96, 4) and Z.dtype == np.float64 and Z[-1, 3] == 97 and (np.diff(Z[:, 2]) >= 0).all() and (Z[:, 0] < Z[:, 1]).all()
     assert sorted(Z[:, :2].astype(np.int64).ravel().tolist()) == list(range(2 * 96))       # every row and every cluster but the last joins once
+
+
+# ---------------------------------------------------------------- the kernels in the code object
+def test_linkage_kernels_in_code_object_without_scratch(tmp_path):
+    from test_search_cpu import check_scan_kernels_in_code_object
+    # the plain round and the mutual-reachability round; the core values are prefetched wherever the tile is
+    check_scan_kernels_in_code_object(tmp_path, "linkage_scan_kernel", ["Li0E", "Li1E"], second_pf=True)

@@ -242,3 +242,9 @@ def test_duplicate_groups_is_the_smallest_index_of_the_component():
     assert (g == np.arange(11)).sum() == 9                # keep: one row per component
     with pytest.raises(ValueError):
         duplicate_groups(np.array([[0, 11]]), 11)
+
+
+# ---------------------------------------------------------------- the kernels in the code object
+def test_range_kernels_in_code_object_without_scratch(tmp_path):
+    from test_search_cpu import check_scan_kernels_in_code_object
+    check_scan_kernels_in_code_object(tmp_path, "range_scan_kernel", ["Lb0E", "Lb1E"])                  # count, fill

@@ -233,3 +233,29 @@ def test_search_kernels_in_code_object_without_scratch(tmp_path):
     assert len(select) == 6 and len(norms) == 1, (select, norms)     # keys or (val, idx) pairs x 16 / 64 keys per lane in registers / rescanned
     for k in scan + select + norms:                                 # no scratch, no spills; the candidate slots are dynamic LDS
         assert kernels[k] == (0, 0, 0), (k, kernels[k])
+
+
+def check_scan_kernels_in_code_object(tmp_path, name, modes, second_pf=False):
+    """The same for another kernel of the shared scan (csrc/ivit_scan.h), `name`<KS, PF, ...>: `modes` are the manglings of the template
+    arguments behind PF, one per mode (second_pf: a last argument that repeats PF); each mode has its 16 widths, prefetches up to dim 512,
+    and has no scratch, spill or static LDS."""
+    from test_cabi_cpu import _device_code_object
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if not os.path.exists(readelf):
+        readelf = shutil.which("llvm-readelf")
+    assert readelf, "llvm-readelf not found"
+    co = tmp_path / "dev.co"
+    co.write_bytes(_device_code_object(iv.build()))
+    notes = subprocess.run([readelf, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
+    found = {}
+    for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
+        nm = re.search(r"\.name:\s+_Z\d+%sILi(\d+)ELb([01])E(\w*?)%sEv\w+" % (name, r"Lb\2E" if second_pf else ""), blk)
+        if nm:
+            res = tuple(int(re.search(r"\.%s:\s+(\d+)" % f, blk).group(1)) for f in ("private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size"))
+            found.setdefault(nm.group(3), {})[int(nm.group(1))] = (nm.group(2) == "1", res)
+    assert sorted(found) == sorted(modes), (sorted(found), modes)
+    for mode, widths in found.items():
+        assert sorted(widths) == list(range(1, 17)), (name, mode, sorted(widths))       # dim = 64 .. 1024 in steps of 64, one instantiation each
+        for ks, (pf, res) in widths.items():
+            assert pf == (ks <= 8), (name, mode, ks)                                    # the next tile is prefetched up to dim 512
+            assert res == (0, 0, 0), (name, mode, ks, res)
