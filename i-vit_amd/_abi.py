@@ -33,6 +33,8 @@ Standard library only, so a tool loads this file without the package (and withou
     LINKAGE_ABI     the same of include/ivit_linkage.h, the nineteenth (IVIT_LINKAGE_VERSION)
     HDBSCAN_ABI     the same of include/ivit_hdbscan.h, the twentieth (IVIT_HDBSCAN_VERSION); it includes ivit_linkage.h, whose entries
                     stay LINKAGE_ABI's
+    KTH_ABI         the same of include/ivit_kth.h, the twenty-first (IVIT_KTH_VERSION); it includes ivit_hdbscan.h, whose entries stay
+                    HDBSCAN_ABI's
 
 A Decl is (name, base, ptr, array, type): base type name, pointer depth, array length or None, and the type as text.
 
@@ -70,6 +72,7 @@ GAUSS_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_gauss.h")
 DENSITY_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_density.h")
 LINKAGE_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_linkage.h")
 HDBSCAN_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_hdbscan.h")
+KTH_HEADER = os.path.join(os.path.dirname(HEADER), "ivit_kth.h")
 
 Decl = collections.namedtuple("Decl", "name base ptr array type")
 Function = collections.namedtuple("Function", "ret params text")
@@ -245,3 +248,5 @@ with open(LINKAGE_HEADER) as _f:
     LINKAGE_ABI = parse(_f.read(), base=ABI)
 with open(HDBSCAN_HEADER) as _f:
     HDBSCAN_ABI = parse(_f.read(), base=ABI)
+with open(KTH_HEADER) as _f:
+    KTH_ABI = parse(_f.read(), base=ABI)

@@ -13,7 +13,7 @@ JPEG_ENTROPY_SIGNATURES / JPEG_ENTROPY_RESTYPES (its structs are JpegSegment, Jp
 SEED_SIGNATURES / SEED_RESTYPES, and of ivit_logreg.h, under LOGREG_ABI / LOGREG_SIGNATURES / LOGREG_RESTYPES, and of
 ivit_gauss.h, under GAUSS_ABI / GAUSS_SIGNATURES / GAUSS_RESTYPES, and of ivit_density.h, under DENSITY_ABI / DENSITY_SIGNATURES /
 DENSITY_RESTYPES, and of ivit_linkage.h, under LINKAGE_ABI / LINKAGE_SIGNATURES / LINKAGE_RESTYPES, and of ivit_hdbscan.h, under
-HDBSCAN_ABI / HDBSCAN_SIGNATURES / HDBSCAN_RESTYPES.
+HDBSCAN_ABI / HDBSCAN_SIGNATURES / HDBSCAN_RESTYPES, and of ivit_kth.h, under KTH_ABI / KTH_SIGNATURES / KTH_RESTYPES.
 
 The product path has NO CPU fallback: if the HIP library is missing or a call
 fails, an exception is raised.
@@ -282,6 +282,19 @@ _hdbscan_signatures = _abi.signatures(HDBSCAN_ABI, _structs)
 HDBSCAN_RESTYPES = {name: ret for name, (ret, args) in _hdbscan_signatures.items()}
 HDBSCAN_SIGNATURES = {name: args for name, (ret, args) in _hdbscan_signatures.items()}
 
+# include/ivit_kth.h, by the rule of ivit_hdbscan.h
+KTH_HEADER = _abi.KTH_HEADER
+KTH_ABI = _abi.KTH_ABI
+IVIT_KTH_VERSION = KTH_ABI.constants["IVIT_KTH_VERSION"]
+assert set(KTH_ABI.structs) == set(ABI.structs) and not set(KTH_ABI.functions) & (
+    set(ABI.functions) | set(EVAL_ABI.functions) | set(FEATURES_ABI.functions) | set(ATTNMAP_ABI.functions) | set(CLASSMAP_ABI.functions)
+    | set(HIDDEN_ABI.functions) | set(SEARCH_ABI.functions) | set(MODELFILE_ABI.functions) | set(PROBE_ABI.functions) | set(VIEWS_ABI.functions)
+    | set(CLUSTER_ABI.functions) | set(RANGE_ABI.functions) | set(JPEG_ABI.functions) | set(JPEG_ENTROPY_ABI.functions) | set(SEED_ABI.functions)
+    | set(LOGREG_ABI.functions) | set(GAUSS_ABI.functions) | set(DENSITY_ABI.functions) | set(LINKAGE_ABI.functions) | set(HDBSCAN_ABI.functions))
+_kth_signatures = _abi.signatures(KTH_ABI, _structs)
+KTH_RESTYPES = {name: ret for name, (ret, args) in _kth_signatures.items()}
+KTH_SIGNATURES = {name: args for name, (ret, args) in _kth_signatures.items()}
+
 
 class IvitError(RuntimeError):
     pass
@@ -290,7 +303,7 @@ class IvitError(RuntimeError):
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
-    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _abi.RANGE_HEADER, _abi.JPEG_HEADER, _abi.JPEG_ENTROPY_HEADER, _abi.SEED_HEADER, _abi.LOGREG_HEADER, _abi.GAUSS_HEADER, _abi.DENSITY_HEADER, _abi.LINKAGE_HEADER, _abi.HDBSCAN_HEADER, _THIS])      # the flags live in this file
+    newest = max(os.path.getmtime(p) for p in srcs + [_abi.HEADER, _abi.EVAL_HEADER, _abi.FEATURES_HEADER, _abi.ATTNMAP_HEADER, _abi.CLASSMAP_HEADER, _abi.HIDDEN_HEADER, _abi.SEARCH_HEADER, _abi.MODELFILE_HEADER, _abi.PROBE_HEADER, _abi.VIEWS_HEADER, _abi.CLUSTER_HEADER, _abi.RANGE_HEADER, _abi.JPEG_HEADER, _abi.JPEG_ENTROPY_HEADER, _abi.SEED_HEADER, _abi.LOGREG_HEADER, _abi.GAUSS_HEADER, _abi.DENSITY_HEADER, _abi.LINKAGE_HEADER, _abi.HDBSCAN_HEADER, _abi.KTH_HEADER, _THIS])      # the flags live in this file
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= newest:
         return SO_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -480,6 +493,14 @@ def bind_hdbscan(lib):
     return lib
 
 
+def bind_kth(lib):
+    """the same for every prototype of include/ivit_kth.h"""
+    for name, args in KTH_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, KTH_RESTYPES[name]
+    return lib
+
+
 _lib = None
 
 
@@ -491,7 +512,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise IvitError(f"{SO_PATH} not built — run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback for the product path")
-    _lib = bind_hdbscan(bind_linkage(bind_density(bind_gauss(bind_logreg(bind_seed(bind_jpeg_entropy(bind_jpeg(bind_range(bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH)))))))))))))))))))))
+    _lib = bind_kth(bind_hdbscan(bind_linkage(bind_density(bind_gauss(bind_logreg(bind_seed(bind_jpeg_entropy(bind_jpeg(bind_range(bind_cluster(bind_views(bind_probe(bind_modelfile(bind_search(bind_hidden(bind_classmap(bind_attnmap(bind_features(bind_eval(bind(ctypes.CDLL(SO_PATH))))))))))))))))))))))
     return _lib
 
 

@@ -625,7 +625,32 @@ def _hdbscan_setup(feat8, cosine, splits):
     return h, rows, dim, dev, weight
 
 
+def _kth(h, feat8, rows, dim, weight, k, splits):
+    """ivit_kth_similarity as a self-join -> (kth float32 [rows], above int64 [rows])"""
+    n = ctypes.c_size_t()
+    h.call("ivit_kth_workspace_bytes", rows, rows, dim, int(splits), 1, ctypes.byref(n))
+    new = lambda dt, m: torch.empty(m, dtype=dt, device=feat8.device)      # noqa: E731
+    ws, kth, above = new(torch.uint8, n.value) if n.value else None, new(torch.float32, rows), new(torch.int64, rows)
+    h.call("ivit_kth_similarity", _ptr(feat8), rows, _ptr(feat8), rows, dim, _ptr(weight), None, int(k), 1, int(splits), _ptr(ws), n.value,
+           _ptr(kth), _ptr(above))
+    if ws is not None:
+        ws.record_stream(torch.cuda.current_stream(feat8.device))       # freed here, read by the queued launches
+    return kth, above
+
+
+def kth_similarity(feat8, k, cosine=True, splits=0):
+    """(kth float32 [rows], above int64 [rows]) on the device: for every row of feat8 (a contiguous int8 device tensor [rows, dim]) its
+    k-th largest value among all rows, itself included and equal values with their multiplicity, and the number of rows strictly above
+    it, as `predict.kth_reference(feat8, feat8, weight, None, k, self_join=True)` states them (ivit_kth_similarity: an exact radix
+    select, k in 1 .. rows).  For k <= 64 kth is `core_similarity`'s, bit for bit.  Queued on the current stream, nothing
+    synchronised; nothing depends on `splits`."""
+    h, rows, dim, _, weight = _hdbscan_setup(feat8, cosine, splits)
+    return _kth(h, feat8, rows, dim, weight, k, splits)
+
+
 def _core(h, feat8, rows, dim, weight, min_pts, splits):
+    if int(min_pts) > 64:                                               # beyond the candidate lists of ivit_core_similarity: the radix select
+        return _kth(h, feat8, rows, dim, weight, min_pts, splits)[0]
     n = ctypes.c_size_t()
     h.call("ivit_core_workspace_bytes", rows, dim, int(min_pts), int(splits), ctypes.byref(n))
     ws, core = torch.empty(n.value, dtype=torch.uint8, device=feat8.device), torch.empty(rows, dtype=torch.float32, device=feat8.device)
@@ -637,7 +662,8 @@ def _core(h, feat8, rows, dim, weight, min_pts, splits):
 def core_similarity(feat8, min_pts, cosine=True, splits=0):
     """float32 [rows] on the device: for every row of feat8 (a contiguous int8 device tensor [rows, dim]) its min_pts-th largest value
     among all rows, itself included and equal values with their multiplicity, as `predict.mutual_reachability_reference` states it
-    (ivit_core_similarity; min_pts in 1 .. min(rows, 64)).  `degree >= min_pts` of `dbscan` at a threshold t is `core >= t`.  Queued
+    (ivit_core_similarity for min_pts in 1 .. min(rows, 64); above 64, up to rows, ivit_kth_similarity, the same values by radix
+    select as `predict.kth_reference` states them).  `degree >= min_pts` of `dbscan` at a threshold t is `core >= t`.  Queued
     on the current stream, nothing synchronised."""
     h, rows, dim, _, weight = _hdbscan_setup(feat8, cosine, splits)
     return _core(h, feat8, rows, dim, weight, min_pts, splits)
@@ -645,7 +671,8 @@ def core_similarity(feat8, min_pts, cosine=True, splits=0):
 
 def hdbscan(feat8, min_cluster_size=5, min_pts=None, cosine=True, floor=None, selection="eom", allow_single_cluster=False, splits=0, check_every=1):
     """HDBSCAN over the rows of feat8 (a contiguous int8 device tensor [rows, dim]) as `predict.hdbscan_reference` and
-    `predict.hdbscan_labels_reference` state it; min_pts defaults to min_cluster_size (clipped to the rows).  ON THE DEVICE:
+    `predict.hdbscan_labels_reference` state it; min_pts defaults to min_cluster_size (clipped to the rows and to 64; an EXPLICIT
+    min_pts may go up to the rows: above 64 the core similarities come from ivit_kth_similarity).  ON THE DEVICE:
     ivit_core_similarity, ivit_linkage_init, then batches of `check_every` ivit_reach_round with one read of `state` per batch, as
     `single_linkage`; the edges are sorted into the edge order there too.  ON THE HOST over those rows - 1 edges: `Linkage.condense`
     and `CondensedTree.select`.  Memory is O(rows); nothing depends on `splits` or `check_every`.  Returns (label int32 [rows] on the

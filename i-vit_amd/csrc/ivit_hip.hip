@@ -52,6 +52,7 @@
 #include "ivit_density.h"
 #include "ivit_linkage.h"
 #include "ivit_hdbscan.h"
+#include "ivit_kth.h"
 
 #define IVIT_MAX_DEVICES 64     // per-device caches of launch attributes (larger ordinals simply do not cache)
 struct ivit_ctx {
@@ -3758,6 +3759,83 @@ extern "C" int ivit_reach_round(ivit_handle h, const int8_t *x, int64_t rows, in
     CHECK_H(h);
     return linkage_round<LINKAGE_REACH>(h, __func__, x, rows, dim, weight, core, floor, splits, workspace, bytes, comp, done, edge_u, edge_v, edge_val,
                                         state);
+}
+
+// ---------------------------------------------------------------- neighbour order statistics: radix select (include/ivit_kth.h)
+// the limits both entries share, the parts of x (whole tiles of 32; the caller's count, or about ONE workgroup per CU of the handle's
+// share — the histograms take the CU's LDS — in parts of at least 1024 rows; none of them empty) and the split form's workspace
+static int kth_shape_ok(ivit_handle h, const char *fn, long long nq, long long rows, int dim, int splits, int self_join, TileParts *t, size_t *bytes) {
+    const char *bad = nullptr;
+    if (nq < 0) bad = "nq is negative";
+    else if (rows < 1 || rows > 0x7fffffffLL) bad = "rows must be in 1 .. 2^31 - 1";
+    else if (splits < 0 || splits > 65535) bad = "splits must be in 0 .. 65535";
+    else if (self_join && nq != rows) bad = "self_join: nq must equal rows";
+    if (bad) { snprintf(h->err, sizeof(h->err), "%s: %s", fn, bad); return IVIT_ERR_INVALID; }
+    if (dim < SEARCH_MIN_DIM || dim > SEARCH_MAX_DIM || (dim % 64) != 0) {
+        snprintf(h->err, sizeof(h->err), "%s: dim must be a multiple of 64 in 64 .. 1024", fn);
+        return IVIT_ERR_UNSUPPORTED;
+    }
+    t->tiles = (rows + SEARCH_TILE - 1) / SEARCH_TILE;
+    const long long cols = std::max(1ll, (nq + SEARCH_QB - 1) / SEARCH_QB);
+    long long s = splits;
+    if (s == 0) s = std::max(1ll, std::min((persistent_cus(h) + cols - 1) / cols, rows / 1024));
+    s = std::min(s, t->tiles);
+    t->per = (t->tiles + s - 1) / s;
+    t->parts = (int)((t->tiles + t->per - 1) / t->per);
+    *bytes = t->parts > 1 ? (size_t)nq * t->parts * KTH_BINS * 4 : 0;
+    return launch_fits(h, fn, cols * t->parts, 256, SEARCH_QB);
+}
+
+extern "C" int ivit_kth_workspace_bytes(ivit_handle h, int nq, int64_t rows, int dim, int splits, int self_join, size_t *bytes) {
+    CHECK_H(h);
+    REQUIRE(h, bytes, "bytes is null");
+    TileParts t;
+    size_t n;
+    if (const int rc = kth_shape_ok(h, __func__, nq, rows, dim, splits, self_join, &t, &n)) return rc;
+    *bytes = n;
+    return IVIT_OK;
+}
+
+template <bool SELF>
+static int kth_scan_dispatch(ivit_handle h, int dim, const KthArgs &a) {
+    const dim3 grid((unsigned)((a.nq + SEARCH_QB - 1) / SEARCH_QB), (unsigned)a.parts);
+    return with_ks(dim, [&](auto KS) { return launch_dyn<kth_scan_kernel<KS(), scan_prefetch(KS()), SELF>>(h, grid, dim3(256), KTH_LDS_BYTES, a); });
+}
+
+extern "C" int ivit_kth_similarity(ivit_handle h, const int8_t *q, int nq, const int8_t *x, int64_t rows, int dim, const float *weight, const float *qweight,
+                                   int64_t k, int self_join, int splits, void *workspace, size_t bytes, float *kth, int64_t *above) {
+    CHECK_H(h);
+    REQUIRE(h, q && x && kth && above, "q, x, kth or above is null");
+    TileParts t;
+    size_t need;
+    if (const int rc = kth_shape_ok(h, __func__, nq, rows, dim, splits, self_join, &t, &need)) return rc;
+    REQUIRE(h, k >= 1 && k <= rows, "k must be in 1 .. rows");
+    REQUIRE(h, !self_join || q == x, "self_join: q must be x");
+    REQUIRE(h, bytes >= need, "workspace too small (ivit_kth_workspace_bytes)");
+    REQUIRE(h, need == 0 || workspace, "workspace is null");
+    REQUIRE_A16(h, q, "q");
+    REQUIRE_A16(h, x, "x");
+    REQUIRE_A16(h, workspace, "workspace");
+    REQUIRE_ALIGNED(h, above, "above", 8);
+    REQUIRE_ALIGNED(h, kth, "kth", 4);
+    const ArgRange r[7] = {{q, (size_t)nq * dim, "q"}, {x, (size_t)rows * dim, "x"}, {weight, (size_t)rows * 4, "weight"},
+                           {qweight, self_join ? 0 : (size_t)nq * 4, "qweight"}, {workspace, workspace ? bytes : 0, "workspace"},
+                           {kth, (size_t)nq * 4, "kth"}, {above, (size_t)nq * 8, "above"}};
+    if (const int rc = args_disjoint(h, __func__, r, 4, 7)) return rc;
+    REQUIRE_LAUNCH(h, ((long long)nq + 3) / 4, 256, 4);
+    if (nq == 0) return IVIT_OK;
+    KthArgs a = {};
+    a.q = q; a.x = x; a.weight = weight; a.qweight = qweight; a.hist = (unsigned *)workspace; a.kth = kth; a.above = (long long *)above;
+    a.nq = nq; a.rows = rows; a.tiles = t.tiles; a.per = t.per; a.k = k; a.parts = t.parts;
+    const unsigned per_wave = (unsigned)(((long long)nq + 3) / 4);          // the pick: one wavefront per query
+    for (a.pass = 0; a.pass < (t.parts == 1 ? 1 : 4); ++a.pass) {           // one part: the scan runs the four passes itself
+        if (const int rc = self_join ? kth_scan_dispatch<true>(h, dim, a) : kth_scan_dispatch<false>(h, dim, a)) return rc;
+        LAUNCH_CHECK(h);
+        if (t.parts == 1) break;
+        kth_pick_kernel<<<per_wave, 256, 0, h->stream>>>(a);
+        LAUNCH_CHECK(h);
+    }
+    return IVIT_OK;
 }
 
 #include "ivit_model.h"

@@ -431,6 +431,17 @@ class NativeEngine:
         dist, cls = score(feat8, model)[:2]
         return dist, cls, feat8.clone() if copy else feat8
 
+    def knn_novelty(self, images, gallery, k, nslices=1, copy=False):
+        """images int8 [B, C, H, W], gallery an `ivit_amd.search.Gallery` (one device chunk) of this backbone's features -> (score
+        float32 [B], feat8 int8 [B, num_features]) device tensors: `features` without the head, then `gallery.kth(feat8, k)` on the
+        same stream (include/ivit_kth.h) — every image's similarity to its k-th nearest gallery row (the cosine for a cosine
+        gallery) as `predict.kth_reference` states it, for any k up to the gallery's rows: the non-parametric novelty score beside
+        `novelty`, LOW where the image is far from the gallery.  score is a fresh tensor, feat8 the engine's buffer: copy=True (or
+        clone) to keep it."""
+        feat8 = self.features(images, nslices=nslices)[0]
+        score = gallery.kth(feat8, k)[0]
+        return score, feat8.clone() if copy else feat8
+
     # ---- views (include/ivit_views.h, ivit_amd/views.py): the mean logits of the V views of every image
     def _make_view_buffers(self, G, k):
         ncls = self.cfg.num_classes

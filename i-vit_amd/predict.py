@@ -920,13 +920,14 @@ def mutual_reachability_reference(x8, weight, min_pts):
 
     v{i, j} is `dbscan_reference`'s value (the larger row's weight first), -0.0 counted as +0.0 before any use.  core[i] is the
     min_pts-th largest element of row i of v, the diagonal included and equal values with their multiplicity (a descending sort,
-    element min_pts - 1); min_pts in 1 .. min(rows, 64).  m{i, j} = min(v{i, j}, core[i], core[j]); its diagonal is not part of the
-    definition (no edge joins a row to itself)."""
+    element min_pts - 1); min_pts in 1 .. rows (ivit_core_similarity serves 1 .. 64, ivit_kth_similarity every min_pts: above 64
+    `cluster.hdbscan` takes core from it, and `kth_reference(x8, x8, weight, None, min_pts, True)` states the same core).
+    m{i, j} = min(v{i, j}, core[i], core[j]); its diagonal is not part of the definition (no edge joins a row to itself)."""
     x = np.asarray(x8)
     assert x.ndim == 2 and x.dtype == np.int8 and x.shape[0] >= 1
     rows = x.shape[0]
-    if not 1 <= int(min_pts) <= min(rows, 64):
-        raise ValueError("min_pts must be in 1 .. min(rows, 64)")
+    if not 1 <= int(min_pts) <= rows:
+        raise ValueError("min_pts must be in 1 .. rows")
     v = (x.astype(np.int32) @ x.astype(np.int32).T).astype(np.float32)
     if weight is not None:
         weight = np.asarray(weight, dtype=np.float32)
@@ -949,6 +950,43 @@ def hdbscan_reference(x8, weight, min_pts, floor=None):
         raise ValueError("floor must not be NaN")
     i, j = np.triu_indices(m.shape[0], 1)
     return (core,) + _kruskal_forest(m.shape[0], i, j, m[i, j], floor)
+
+
+def kth_values_reference(q8, x8, weight, qweight, self_join):
+    """-> float32 [nq, rows]: the dense values of include/ivit_kth.h, -0.0 as +0.0.  self_join False: `range_reference`'s value,
+    fl32(fl32(fl32(dot) * weight[g]) * qweight[b]), a None array left out.  self_join True (q8 is x8, qweight is ignored):
+    `dbscan_reference`'s, the larger row's weight first."""
+    q, x = np.asarray(q8), np.asarray(x8)
+    assert q.ndim == 2 and x.ndim == 2 and q.dtype == np.int8 and x.dtype == np.int8 and q.shape[1] == x.shape[1] and x.shape[0] >= 1
+    v = (q.astype(np.float64) @ x.astype(np.float64).T).astype(np.float32)       # exact: |dot| <= 2^14 dim, an integer in both formats
+    assert q.shape[1] <= 1024
+    if weight is not None:
+        weight = np.asarray(weight, dtype=np.float32)
+        assert weight.shape == (x.shape[0],)
+    if self_join:
+        assert q.shape == x.shape and np.array_equal(q, x)
+        if weight is not None:
+            n = np.arange(x.shape[0])
+            v = (v * weight[np.maximum.outer(n, n)]) * weight[np.minimum.outer(n, n)]
+    else:
+        if weight is not None:
+            v = v * weight[None, :]
+        if qweight is not None:
+            v = v * np.asarray(qweight, dtype=np.float32).reshape(-1, 1)
+    v = v + np.float32(0)
+    assert v.dtype == np.float32
+    return v
+
+
+def kth_reference(q8, x8, weight, qweight, k, self_join=False):
+    """-> (kth float32 [nq], above int64 [nq]): the numpy statement of include/ivit_kth.h — every row of `kth_values_reference` sorted
+    descending, element k - 1 (equal values with their multiplicity), and the number of values strictly above it; k in 1 .. rows, with
+    no upper limit of 64.  For k <= 64, self_join gives `mutual_reachability_reference`'s core bit for bit."""
+    v = kth_values_reference(q8, x8, weight, qweight, self_join)
+    if not 1 <= int(k) <= v.shape[1]:
+        raise ValueError("k must be in 1 .. rows")
+    kth = -np.sort(-v, axis=1)[:, int(k) - 1]
+    return kth, (v > kth[:, None]).sum(axis=1).astype(np.int64)
 
 
 def hdbscan_labels_reference(m_dense, min_cluster_size, floor=None, selection="eom", allow_single_cluster=False):

@@ -127,6 +127,41 @@ class Gallery:
             self.h.call("ivit_search_merge", _ptr(ci), _ptr(cv), nq, int(ci.shape[1]), k, _ptr(idx), _ptr(val))
         return (idx.clone(), val.clone()) if copy else (idx, val)
 
+    def kth(self, query8, k, query_weight="auto"):
+        """query8 int8 device tensor [nq, dim] -> (kth float32 [nq], above int64 [nq]) device tensors, as
+        `predict.kth_reference(query8, gallery, inv_norm or None, query_weight, k)` states them: every query's k-th largest score over
+        ALL rows of the gallery, equal scores with their multiplicity, and the number of rows strictly above it — for any k in
+        1 .. rows (ivit_kth_similarity: an exact radix select, four streams of the gallery whatever k is).  query_weight as `within`
+        takes it: "auto" makes kth the cosine for a cosine gallery; with None, kth is `search`'s val[:, k - 1] for k <= 64.  On the
+        current stream, nothing synchronised; fresh tensors.  A gallery of ONE device chunk only: the select is exact over the rows
+        of one call, and the order statistic of several chunks is not a function of the chunks' own."""
+        assert isinstance(query8, torch.Tensor) and query8.dtype == torch.int8 and query8.is_contiguous() and query8.device == self.device
+        assert query8.dim() == 2 and query8.shape[1] == self.dim, f"query8 must be [nq, {self.dim}]"
+        if len(self.chunks) != 1 or not self.chunks[0].is_cuda:
+            raise ValueError("Gallery.kth needs a gallery of one device chunk: the k-th value over several chunks is not exact from the chunks' own")
+        k, nq = int(k), int(query8.shape[0])
+        if not 1 <= k <= self.rows:
+            raise ValueError(f"k = {k} outside 1 .. {self.rows}")
+        if nq == 0:
+            return torch.empty(0, dtype=torch.float32, device=self.device), torch.empty(0, dtype=torch.int64, device=self.device)
+        self.h.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        if isinstance(query_weight, str):
+            if query_weight != "auto":
+                raise ValueError('query_weight: "auto", None or a float32 tensor [nq]')
+            qw = self._inv_norms(query8) if self.cosine and nq else None
+        else:
+            qw = query_weight
+            assert qw is None or (qw.dtype == torch.float32 and qw.is_contiguous() and qw.shape == (nq,) and qw.device == self.device)
+        n = ctypes.c_size_t()
+        self.h.call("ivit_kth_workspace_bytes", nq, self.rows, self.dim, 0, 0, ctypes.byref(n))
+        new = lambda dt, m: torch.empty(m, dtype=dt, device=self.device)      # noqa: E731
+        ws, kth, above = new(torch.uint8, n.value) if n.value else None, new(torch.float32, nq), new(torch.int64, nq)
+        self.h.call("ivit_kth_similarity", _ptr(query8), nq, _ptr(self.chunks[0]), self.rows, self.dim, _ptr(self.inv_norm), _ptr(qw), k, 0, 0,
+                    _ptr(ws), n.value, _ptr(kth), _ptr(above))
+        if ws is not None:
+            ws.record_stream(torch.cuda.current_stream(self.device))    # freed here, read by the queued launches
+        return kth, above
+
     def _inv_norms(self, feat8):
         """float32 [n] device tensor: ivit_gallery_inv_norms of any int8 rows on the device (the queries' weights for a cosine)"""
         out = torch.empty(int(feat8.shape[0]), dtype=torch.float32, device=self.device)
